@@ -32,15 +32,26 @@ sequences in flight per GPU (a sequence is two HIP streams -- the tiers run next
 hardware queues ROCm gives a process: with more in flight, streams share queues and wait for each other; measured 2 / 3 / 4 / 6:
 530 / 484 / 518 / 507 M proofs/s, profiles/EXPERIMENTS.md), each on its own ctx + HIP stream and each over a DIFFERENT witness (other seed: a
 validator verifying consecutive witnesses; no step re-reads the bytes the previous step on its slot left in
-L2 / Infinity Cache): every step is still a full pass over a full batch; `single_stream` in the JSON line is
+L2 / Infinity Cache): every pass is still a full pass over a full batch; `single_stream` in the --full line is
 the same number of passes strictly one after the other (alternating witnesses), and `roofline.achieved` always
-refers to ONE launch.  A timed "step" is repeated --inner times back to back (default 30) so that the timed
-region is >= 100 ms; all per-step figures are per single pass.  The config-3 line also carries `strong`: the
-config-4 block witness split over the same N GPUs (strong scaling), measured right after.
+refers to ONE launch.  A timed "step" is --inner passes back to back (default 30) so that the timed region is
+>= 100 ms: `ms_per_step` is one such step, `ms_per_pass` one pass.  The --full config-3 line also carries `strong`:
+the config-4 block witness split over the same N GPUs (strong scaling), measured right after.
 
-Prints ONE JSON line (rank 0) with `roofline` (HBM; algorithmic bytes per
-launch / average kernel duration measured with HIP events on the launch
-stream) and, at N = 1, `cpu_baseline` (the CPU oracle timed on this host).
+A plain run does only what the headline figure needs: set up, warm up, time the
+K steps, write the timed path's outputs (--dump-outputs DIR) and print ONE JSON
+line (rank 0) with metric / value / unit / ms_per_step / higher_is_better / dtype.
+--full adds everything else, each taking runs of its own: the checks of the timed
+statuses against the constructed expectation, `roofline` (HBM; algorithmic bytes
+per launch / average kernel duration measured with HIP events on the launch
+stream; the VALU peak; per-kernel figures), `single_stream`, `strong`, at N = 1
+`cpu_baseline` (the CPU oracle timed on this host, checked against the GPU's
+statuses) and, for the default config-3 run, the `extra` legs.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its
+last step (per-proof statuses and per-root failure counts per launch sequence,
+digests, roots) as DIR/<name>.npy in float32; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -143,18 +154,43 @@ def parse():
     ap.add_argument("--messages", type=int, default=1 << 20, help="config2: 136-byte messages per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
-                    help="config3 at N = 1: skip the short extra legs (config 2, mptize, config 5 at 8 blocks) that the default run "
-                         "appends to the line as `extra` so that the driver's record carries them")
+                    help="config3 at N = 1: skip the short extra legs (config 2, mptize, config 5 at 8 blocks) that a --full run "
+                         "appends to the line as `extra` so that its record carries them")
     ap.add_argument("--extra-seconds", type=int, default=420, help="wall-clock budget of all extra legs together")
     ap.add_argument("--max-seconds", type=int, default=1500,
                     help="wall-clock guard: past this the process prints a JSON line with \"error\" (rank 0) and exits with rc 4 "
                          "instead of hanging (a rendezvous or RCCL initialisation that never completes)")
     ap.add_argument("--rendezvous-seconds", type=int, default=180, help="N > 1: timeout of the process-group rendezvous and of every collective")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the checks of the timed statuses, rooflines, single-stream and strong-scaling "
+                         "legs, the CPU baseline and the default config-3 run's extra legs (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
     if args.allreduce_every < 1:
         ap.error("--allreduce-every must be >= 1 (1 = a verdict per pass; --inner = one exchange per timed step)")
     return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: every array of `arrays` (name -> tensor / ndarray) as out_dir/<name>.npy in float32 (float64 where a
+    value would not be exact in float32); a rank of N > 1 adds `_rank<r>` to its names."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        exact32 = a.dtype.kind in "biu" and (a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24))
+        conv[name if world == 1 else f"{name}_rank{rank}"] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} B is more than {DUMP_MAX_BYTES} B"
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline_config3(w, target_seconds, gpu_status=None):
@@ -512,6 +548,11 @@ def run_comm_bench(args):
         one_pass()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # every device's statuses and the exchanged per-root verdict of the last pass
+        outputs = {}
+        for d, (_, status, fails, _) in enumerate(slots):
+            outputs[f"status_device{d}"], outputs[f"root_fail_count_device{d}"] = status.cpu().clone(), fails.cpu().clone()
+        dump_outputs(args.dump_outputs, outputs)
     want = sum(s[0].n_invalid for s in slots)
     for w, status, fails, _ in slots:
         assert torch.equal(status, w.expected), "verify statuses differ from the constructed expectation"
@@ -583,7 +624,7 @@ def run_proof_bench(args, make_witness, S, steps, warmup, inner, dev, local_rank
     import torch.distributed as dist
     from phant_amd import mpt as M
 
-    n_wit = max(S, 2)
+    n_wit = max(S, 2) if args.full else S  # (--full: the single-stream leg alternates between two witnesses)
     wits = [make_witness(k) for k in range(n_wit)]
     K = max(1, min(args.allreduce_every, inner))  # passes per verdict exchange (1: a verdict per witness, what a validator needs)
     w0 = wits[0]
@@ -616,6 +657,7 @@ def run_proof_bench(args, make_witness, S, steps, warmup, inner, dev, local_rank
     filled = [0] * S                       # passes written into the slot's current block
     block_of = [0] * S                     # which block that is
     reduced_ev = [[None, None] for _ in range(S)]   # event behind the last exchange of block b of slot k
+    last_row = [None] * S                  # (block, row) the slot's last pass wrote its verdict into
     exchanged = {"n": 0}
 
     def exchange(k):
@@ -644,6 +686,7 @@ def run_proof_bench(args, make_witness, S, steps, warmup, inner, dev, local_rank
             # statuses + per-root verdict of this pass
             M.verify_batch_dev(w_.batch, status=status_, ctx=c_, fail_count=fails_[block_of[k], filled[k]])
         wrote[k][block_of[k]][filled[k]] = True
+        last_row[k] = (block_of[k], filled[k])
         filled[k] += 1
         if filled[k] == K:
             exchange(k)
@@ -683,6 +726,19 @@ def run_proof_bench(args, make_witness, S, steps, warmup, inner, dev, local_rank
     flush()  # (the last, possibly short, blocks: every verdict of the timed passes has been exchanged when the clock stops)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    passes = steps * inner
+    out = {"wits": wits, "n_units": n_units, "elapsed": elapsed, "passes": passes, "ms_per_pass": elapsed / passes * 1e3,
+           "value": n_units * world * passes / elapsed}
+    if args.dump_outputs:  # what the caller of each launch sequence received from its last timed pass
+        out["outputs"] = {}
+        for k, (_, _, status_, fails_, _) in enumerate(slots):
+            out["outputs"][f"status_slot{k}"] = status_.cpu().clone()
+            out["outputs"][f"root_fail_count_slot{k}"] = fails_[last_row[k]].cpu().clone()
+    if not args.full:
+        for k, (_, c_, _, _, _) in enumerate(slots):
+            if c_ is not ctx:
+                c_.close()
+        return out
 
     # correctness of what was timed: the statuses, and every row of the verdict blocks = the witness's failures over ALL ranks
     for k, (_, _, status_, fails_, w_) in enumerate(slots):
@@ -759,13 +815,11 @@ def run_proof_bench(args, make_witness, S, steps, warmup, inner, dev, local_rank
                         bound = slots[0][1].verify_bound_experiment(wits[0].batch, 20)
                 except Exception as exc:  # diagnostics never cost the headline its line
                     bound = {"error": repr(exc)}
-    passes = steps * inner
-    out = {"wits": wits, "status0": timed_status0, "kernels": kernels, "bound": bound if isinstance(bound, dict) and "together_ms" in bound else None, "tiers": tiers, "n_units": n_units, "elapsed": elapsed, "passes": passes, "ms_per_pass": elapsed / passes * 1e3,
-           "value": n_units * world * passes / elapsed,
+    out.update({"status0": timed_status0, "kernels": kernels, "bound": bound if isinstance(bound, dict) and "together_ms" in bound else None, "tiers": tiers,
            "single": {"value": n_units * world * passes / e1, "ms_per_pass": e1 / passes * 1e3, "ms_per_step": e1 / steps * 1e3},
            "k_avg_ms": k_evt_ms, "k_synced_ms": sum(kms) / len(kms), "k_min_ms": min(kms), "hashed": hashed,
            "verdict_exchange": {"passes_per_allreduce": K, "allreduces_on_this_rank": exchanged["n"],
-                                "stream": "own (event-fed)" if world > 1 else None}}
+                                "stream": "own (event-fed)" if world > 1 else None}})
     for k, (st_, c_, _, _, _) in enumerate(slots):
         if c_ is not ctx:
             c_.close()
@@ -794,8 +848,8 @@ def relaunch_under_torchrun(args):
 
 
 def extra_legs(args):
-    """The default run's short extra legs, each a bench.py process of its own (own ctx, own JSON line with its own `roofline`
-    and oracle check), so that the driver's record of the default command carries more than config 3."""
+    """The --full config-3 run's short extra legs, each a bench.py --full process of its own (own ctx, own JSON line with its own
+    `roofline` and oracle check), so that the record of the full run carries more than config 3."""
     import subprocess
     legs = [("config2", ["--workload", "config2", "--steps", "10", "--warmup", "2", "--cpu-seconds", "3"]),
             ("mptize_1M_keys", ["--workload", "mptize", "--keys", "1000000", "--steps", "10", "--warmup", "2", "--cpu-seconds", "3"]),
@@ -812,7 +866,7 @@ def extra_legs(args):
         if left < 30:
             out[name] = {"error": "skipped: the extra legs' wall-clock budget is spent"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extra", "--max-seconds", str(int(left)), *argv]
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extra", "--max-seconds", str(int(left)), *argv]
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=left + 30)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -911,6 +965,7 @@ def main():
     single = None
     extra = {}
     strong = None
+    outputs = None  # --dump-outputs: name -> what the timed path computed in its last step
     S = 1
     inner = 1
     if proofs_like:
@@ -929,18 +984,19 @@ def main():
                             local_rank, world, rank, ctx)
         w = r["wits"][0]
         b = w.batch
-        n_units, elapsed, value, single, k_avg_ms = r["n_units"], r["elapsed"], r["value"], r["single"], r["k_avg_ms"]
+        n_units, elapsed, value, single, k_avg_ms = r["n_units"], r["elapsed"], r["value"], r.get("single"), r.get("k_avg_ms")
         alg_bytes = b.algorithmic_bytes()
         ms_per_pass = r["ms_per_pass"]
         ms_per_step = ms_per_pass * inner
-        timed_status0 = r["status0"]
+        timed_status0 = r.get("status0")
+        outputs = r.get("outputs")
         if args.workload == "config3":
             metric, unit = "mpt_proofs_verified_per_sec_depth%d" % args.depth, "proofs/s"
             workload = (f"config3: {args.proofs} synthetic depth-{args.depth} account proofs per GPU against one "
                         f"state root ({w.nodes_per_proof - 1} x 532 B full branches + 112 B leaf, "
                         f"{w.bytes_per_proof} B and {w.perms_per_proof} Keccak-f per proof, 1% corrupted/exclusion, "
                         f"no cross-proof dedup); every launch sequence in flight verifies its own witness (seeds 2.."
-                        f"{1 + max(S, 2)}: distinct data per slot), {inner} back-to-back passes per timed step"
+                        f"{1 + len(r['wits'])}: distinct data per slot), {inner} back-to-back passes per timed step"
                         + ("" if args.proof_order == "random" else "; PROOFS IN ASCENDING KEY ORDER (not BASELINE's order)"))
         else:
             metric, unit = "mpt_proofs_verified_per_sec_block_witness", "proofs/s"
@@ -950,8 +1006,8 @@ def main():
                         f"{w.nodes_per_proof:.2f} nodes, {w.bytes_per_proof:.0f} B and {w.perms_per_proof:.1f} "
                         f"Keccak-f per proof on average, 1% corrupted/exclusion); distinct witness per slot, "
                         f"{inner} back-to-back passes per timed step")
-        extra = {"kernel_synced_avg_ms": r["k_synced_ms"], "verdict_exchange": r["verdict_exchange"]}
-        if r["hashed"] is not None:
+        extra = {"kernel_synced_avg_ms": r["k_synced_ms"], "verdict_exchange": r["verdict_exchange"]} if args.full else {}
+        if args.full and r["hashed"] is not None:
             hashed = r["hashed"]
             kf = int(sum((c + 1) * h for c, h in enumerate(hashed)))
             # the second roofline of this path: Keccak-f is integer-VALU-bound.  Peak = what the product's round function
@@ -983,7 +1039,7 @@ def main():
                               "(0.121 ms) is out of reach for this hashing next to ANY stream on this chip -- what is left between one "
                               "launch and together_ms is all the shallow tier's own shape can still give")
                 extra["bound_experiment"] = be
-        if args.workload == "config3" and not args.no_strong:
+        if args.full and args.workload == "config3" and not args.no_strong:
             # BASELINE config 4 next to it: ONE block witness split over the same N GPUs (strong scaling): accounts by
             # top key nibble, contracts dealt out whole, one all-reduce of the per-root verdicts per pass
             del r
@@ -1202,7 +1258,23 @@ def main():
         value = n_units * world * args.steps * inner / elapsed
         ms_per_pass = elapsed / (args.steps * inner) * 1e3
         ms_per_step = ms_per_pass * inner
+        if args.dump_outputs:  # what the timed path's caller received from the last step
+            import numpy as np
+            if args.workload == "nodeset":
+                outputs = {}
+                for k, (_, _, _, _, status_, fails_) in enumerate(ns_slots):
+                    outputs[f"status_slot{k}"], outputs[f"root_fail_count_slot{k}"] = status_.cpu().clone(), fails_.cpu().clone()
+            elif streamed:  # (the last step submits every witness of the rotation once)
+                outputs = {f"status_witness{k}": h.status.clone() for k, h in enumerate(hosts)}
+            elif args.workload == "mptize":
+                outputs = {"root": root.cpu().clone()}
+            elif args.workload == "block_roots":
+                outputs = {"roots": roots_out.reshape(3, 32).copy()}
+            else:  # config2: a fixed, seeded sample of the digests (all 2^20 of them would be 128 MB in float32)
+                rows = np.sort(np.random.default_rng(0).choice(n_units, size=min(n_units, 1 << 17), replace=False))
+                outputs = {"digest_sample": out[torch.from_numpy(rows).to(out.device)].cpu(), "digest_sample_rows": rows}
 
+    if not proofs_like and args.full:
         # correctness of what was timed
         cpu_check_status = None
         if args.workload == "nodeset":
@@ -1295,7 +1367,7 @@ def main():
                                              "waves per SIMD",
                               "note": "one Keccak-f per node and rate block, counted from the trie's shape (bench.trie_keccak_f) / "
                                       "device time of one call (first kernel start to last kernel end)"}}
-    achieved = alg_bytes / (k_avg_ms * 1e-3) / 1e9
+    achieved = alg_bytes / (k_avg_ms * 1e-3) / 1e9 if args.full else None
 
     pipeline = ("two-tier verify pipeline = hash_deep_kernel (in-place hashing of the deep levels, helper stream) next to the "
                 "shallow tier (propose_kernel + dedup_kernel + hash_list_kernel: the copies of the upper trie levels are byte-compared "
@@ -1308,7 +1380,7 @@ def main():
         "scaling": "strong" if args.workload == "config4" else "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
         "config": {"workload": workload, "units_per_gpu_per_step": n_units, "parallelism": f"key-sharded x{world}",
                    **({"parity_basis": "derived: the reference has no verifier (TODO at src/engine_api/execution_payload.zig:177-178), "
-                                       "so no known answer exists; statuses are checked against the constructed expectation here and, "
+                                       "so no known answer exists; statuses are checked against the constructed expectation here (--full) and, "
                                        "in tests/, against oracle/verify.c over proofs extracted from tries whose roots the "
                                        "reference's own vectors pin (DESIGN.md section 5)"} if proofs_like or streamed or
                       args.workload == "nodeset" else {}),
@@ -1318,7 +1390,7 @@ def main():
                    "timed_region_ms": ms_per_step * args.steps,
                    "step": f"a timed step = {inner} back-to-back pass(es) of the path over a resident batch; ms_per_step x steps = the "
                            "timed region, ms_per_pass = one pass (`value` = units per pass / ms_per_pass)"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        **({} if not args.full else {"roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
                      "throughput_GBps": value / world * alg_bytes / n_units / 1e9,  # algorithmic bytes x the measured
                      "throughput_frac": value / world * alg_bytes / n_units / 1e9 / HBM_PEAK_GBS,  # rate (launches overlap)
@@ -1340,12 +1412,12 @@ def main():
                                 if args.workload == "mptize" else
                                 "node-set pipeline = set_classify_kernel + set_hash_kernel + set_walk_kernel"
                                 if (streamed and args.nodeset) else pipeline),
-                     "kernel_avg_ms": k_avg_ms, "algorithmic_bytes_per_launch": alg_bytes, **extra},
+                     "kernel_avg_ms": k_avg_ms, "algorithmic_bytes_per_launch": alg_bytes, **extra}}),
     }
     # the scalars a reader of the compacted line needs next to `frac` ("report VALU utilisation next to the
     # HBM fraction"): the hashing is integer-VALU-bound, so the HBM fraction a launch could reach at most is the one it would have
     # if it took exactly as long as its permutations take at the chip's measured Keccak-f rate
-    rf = line["roofline"]
+    rf = line.get("roofline") or {}
     if isinstance(rf.get("valu"), dict) and rf["valu"].get("peak"):
         rf["valu_frac"] = rf["valu"]["frac"]
         t_valu_ms = rf["keccak_f_run"] / (rf["valu"]["peak"] * 1e9) * 1e3
@@ -1363,7 +1435,7 @@ def main():
                         "frac": h2d / world / 63.0, "slots": slots,
                         "note": "PCIe Gen5 x16 spec; the streamed rate is H2D-bound, the kernels of one witness "
                                 "take roofline.kernel_avg_ms"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.workload == "mptize":
             line["cpu_baseline"] = cpu_baseline_mptize(keys_t, vals_t, n_units, root, args.cpu_seconds)
         elif args.workload == "block_roots":
@@ -1380,11 +1452,13 @@ def main():
             line["cpu_baseline"] = cpu_baseline_config2(blob, n_units, args.cpu_seconds)
     if rccl_world is not None:
         line["rccl_world"] = rccl_world
-    if (rank == 0 and world == 1 and args.workload == "config3" and not args.no_extra and args.proofs == 100_000 and
+    if (args.full and rank == 0 and world == 1 and args.workload == "config3" and not args.no_extra and args.proofs == 100_000 and
             args.verify_mode == "flat" and not args.no_strong and not args.no_cpu_baseline and args.proof_order == "random"):
         # (only the default-sized headline run: the sweeps and A/B scripts call with other sizes or --no-extra)
         line["extra"] = extra_legs(args)
         line["extra_keys"] = sorted(line["extra"])
+    if args.dump_outputs and outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

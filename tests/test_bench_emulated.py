@@ -122,7 +122,7 @@ def _check_contract(line, steps, warmup):
 @pytest.mark.parametrize("mode,streams,inner", [("flat", 3, 2), ("flat", 1, 1), ("nodedup", 2, 1)] if suite.FULL else
                          [("flat", 3, 2), ("nodedup", 2, 1)])
 def test_config3_dry_run(mode, streams, inner):
-    line = _bench(["--proofs", "300", "--steps", "3", "--warmup", "1", "--verify-mode", mode, "--streams",
+    line = _bench(["--full", "--proofs", "300", "--steps", "3", "--warmup", "1", "--verify-mode", mode, "--streams",
                    str(streams), "--cpu-seconds", "0.2", "--inner", str(inner), "--block-scale", "0.01"])
     _check_contract(line, 3, 1)
     assert line["metric"] == "mpt_proofs_verified_per_sec_depth8" and line["unit"] == "proofs/s"
@@ -144,8 +144,8 @@ def test_config3_dry_run(mode, streams, inner):
 
 
 def test_config3_forced_tier_split_dry_run():
-    line = _bench(["--proofs", "200", "--steps", "1", "--warmup", "0", "--streams", "1", "--cpu-seconds", "0.2", "--inner", "1",
-                   "--dedup-levels", "3", "--no-strong"])
+    line = _bench(["--full", "--proofs", "200", "--steps", "1", "--warmup", "0", "--streams", "1", "--cpu-seconds", "0.2", "--inner",
+                   "1", "--dedup-levels", "3", "--no-strong"])
     _check_contract(line, 1, 0)
     assert line["config"]["dedup_levels"] == 3 and "strong" not in line
     # the VALU peak is measured in the run; every kernel of the two-tier pipeline has its own roofline entry (tiers serialised)
@@ -163,13 +163,13 @@ def test_config3_forced_tier_split_dry_run():
 
 
 def test_config3_fewer_steps_than_slots():
-    line = _bench(["--proofs", "200", "--steps", "1", "--warmup", "0", "--streams", "4", "--cpu-seconds", "0.2", "--inner", "1",
-                   "--no-strong"])
+    line = _bench(["--full", "--proofs", "200", "--steps", "1", "--warmup", "0", "--streams", "4", "--cpu-seconds", "0.2", "--inner",
+                   "1", "--no-strong"])
     _check_contract(line, 1, 0)
 
 
 def test_config4_dry_run():
-    line = _bench(["--workload", "config4", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--streams",
+    line = _bench(["--full", "--workload", "config4", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--streams",
                    "2", "--cpu-seconds", "0.2", "--inner", "1"])
     _check_contract(line, 2, 1)
     assert line["metric"] == "mpt_proofs_verified_per_sec_block_witness" and line["scaling"] == "strong"
@@ -178,46 +178,89 @@ def test_config4_dry_run():
 
 
 def test_config2_dry_run():
-    line = _bench(["--workload", "config2", "--messages", "3000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--inner", "2"])
+    line = _bench(["--full", "--workload", "config2", "--messages", "3000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--inner", "2"])
     _check_contract(line, 2, 1)
     assert line["metric"] == "keccak256_136B_hashes_per_sec" and line["config"]["units_per_gpu_per_step"] == 3000
 
 
 def test_nodeset_and_config5_dry_run():
-    line = _bench(["--workload", "nodeset", "--proofs", "300", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--inner", "1"])
+    line = _bench(["--full", "--workload", "nodeset", "--proofs", "300", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--inner", "1"])
     _check_contract(line, 2, 1)
     assert line["cpu_baseline"]["oracle_matches_timed_gpu_statuses"] is True and line["roofline"]["valu"]["frac"] > 0
     assert line["roofline"]["nodes_hashed"] == line["roofline"]["nodes_shipped"] > 300
     # config 5 with every block witness shipped as a node set (phant_mpt_verify_nodeset_submit)
-    line = _bench(["--workload", "config5", "--nodeset", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2"])
+    line = _bench(["--full", "--workload", "config5", "--nodeset", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2"])
     _check_contract(line, 2, 1)
     assert line["metric"] == "mpt_proofs_verified_per_sec_block_witness_streamed_nodeset" and "pcie" in line
     assert line["cpu_baseline"]["oracle_matches_timed_gpu_statuses"] is True
     assert line["roofline"]["nodes_hashed"] == line["roofline"]["nodes_shipped"]
-    line = _bench(["--workload", "config5", "--stream-proofs", "150", "--steps", "5", "--warmup", "1",
+    line = _bench(["--full", "--workload", "config5", "--stream-proofs", "150", "--steps", "5", "--warmup", "1",
                    "--cpu-seconds", "0.2"])
     _check_contract(line, 5, 1)
     assert "pcie" in line and line["metric"] == "mpt_proofs_verified_per_sec_depth8_streamed"
     # the default: block witnesses (config 4's shape) in rotation
-    line = _bench(["--workload", "config5", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2"])
+    line = _bench(["--full", "--workload", "config5", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2"])
     _check_contract(line, 2, 1)
     assert line["metric"] == "mpt_proofs_verified_per_sec_block_witness_streamed" and "pcie" in line
     assert line["config"]["units_per_gpu_per_step"] == 200 + 15 * 8 + 4 * 40 + 1 * 600
 
 
 def test_block_roots_dry_run():
-    line = _bench(["--workload", "block_roots", "--items", "20", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2"])
+    line = _bench(["--full", "--workload", "block_roots", "--items", "20", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2"])
     _check_contract(line, 1, 1)
     assert line["metric"] == "mpt_block_index_roots_per_sec" and line["config"]["units_per_gpu_per_step"] == 3
     assert line["cpu_baseline"]["cores"] == 1 and line["cpu_baseline"]["ms_per_call_of_three"] > 0
 
 
 def test_mptize_dry_run():
-    line = _bench(["--workload", "mptize", "--keys", "3000", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2"])
+    line = _bench(["--full", "--workload", "mptize", "--keys", "3000", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2"])
     _check_contract(line, 1, 1)
     assert line["metric"] == "mpt_trie_keys_hashed_per_sec" and line["config"]["units_per_gpu_per_step"] == 3000
     assert line["cpu_baseline"]["root_matches_gpu"] is True
     assert line["roofline"]["algorithmic_bytes_per_launch"] == 3000 * (32 + 78) + 32
+
+
+_PLAIN_RUNS = {
+    "config3": ["--proofs", "300", "--steps", "2", "--warmup", "1", "--streams", "2", "--inner", "2", "--no-strong",
+                "--cpu-seconds", "0.2"],
+    "config2": ["--workload", "config2", "--messages", "3000", "--steps", "2", "--warmup", "1", "--inner", "2", "--cpu-seconds", "0.2"],
+    "nodeset": ["--workload", "nodeset", "--proofs", "300", "--steps", "2", "--warmup", "1", "--inner", "1", "--streams", "2",
+                "--cpu-seconds", "0.2"],
+    "config5-nodeset": ["--workload", "config5", "--nodeset", "--block-scale", "0.01", "--steps", "1", "--warmup", "1",
+                        "--cpu-seconds", "0.2"],
+    "mptize": ["--workload", "mptize", "--keys", "3000", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2"],
+    "block_roots": ["--workload", "block_roots", "--items", "20", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2"],
+}
+_PLAIN_IDS = list(_PLAIN_RUNS) if suite.FULL else ["config3", "config2", "mptize"]
+
+
+@pytest.mark.parametrize("argv", [_PLAIN_RUNS[k] for k in _PLAIN_IDS], ids=_PLAIN_IDS)
+def test_plain_run_is_lean_and_dumps_what_the_full_run_computes(argv, tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own; --dump-outputs writes the timed
+    path's outputs of the last step, and they are the ones a --full run (whose own checks hold them against the constructed
+    expectation and the oracle) writes for the same arguments."""
+    import numpy as np
+    plain = _bench([*argv, "--dump-outputs", str(tmp_path / "plain")])
+    steps = int(argv[argv.index("--steps") + 1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "ms_per_pass", "config"):
+        assert k in plain, k
+    for k in ("roofline", "cpu_baseline", "single_stream", "strong", "extra"):
+        assert k not in plain, k
+    assert plain["steps"] == steps and plain["value"] > 0 and plain["higher_is_better"] is True
+    c = plain["config"]
+    assert abs(plain["ms_per_step"] * steps - c["timed_region_ms"]) <= 1e-9 * max(1.0, c["timed_region_ms"])
+    assert abs(plain["value"] - c["units_per_gpu_per_step"] / (plain["ms_per_pass"] * 1e-3)) <= 1e-6 * plain["value"]
+    full = _bench(["--full", *argv, "--dump-outputs", str(tmp_path / "full")])
+    assert full["metric"] == plain["metric"] and full["unit"] == plain["unit"] and "roofline" in full and "cpu_baseline" in full
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert n.endswith(".npy") and a.dtype in (np.float32, np.float64) and a.size > 0, n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
 
 
 def _rank_main(rank, world, port, argv, q):
@@ -244,12 +287,12 @@ def _rank_main(rank, world, port, argv, q):
 
 
 _TWO_RANK_RUNS = {
-    "config3": ["--gpus", "2", "--proofs", "200", "--steps", "2", "--warmup", "1", "--streams", "3", "--inner", "2", "--block-scale", "0.01"],
-    "config3-verdicts-every-2-passes": ["--gpus", "2", "--proofs", "200", "--steps", "2", "--warmup", "1", "--streams", "2", "--inner", "3",
+    "config3": ["--full", "--gpus", "2", "--proofs", "200", "--steps", "2", "--warmup", "1", "--streams", "3", "--inner", "2", "--block-scale", "0.01"],
+    "config3-verdicts-every-2-passes": ["--full", "--gpus", "2", "--proofs", "200", "--steps", "2", "--warmup", "1", "--streams", "2", "--inner", "3",
                                         "--allreduce-every", "2", "--block-scale", "0.01"],
-    "config3-fewer-steps-than-slots": ["--gpus", "2", "--proofs", "200", "--steps", "1", "--warmup", "0", "--streams", "4", "--inner", "1",
+    "config3-fewer-steps-than-slots": ["--full", "--gpus", "2", "--proofs", "200", "--steps", "1", "--warmup", "0", "--streams", "4", "--inner", "1",
                                        "--no-strong"],
-    "config4": ["--gpus", "2", "--workload", "config4", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--streams", "2",
+    "config4": ["--full", "--gpus", "2", "--workload", "config4", "--block-scale", "0.01", "--steps", "2", "--warmup", "1", "--streams", "2",
                 "--inner", "1"],
 }
 _TWO_RANK_IDS = list(_TWO_RANK_RUNS) if suite.FULL else ["config3-verdicts-every-2-passes", "config4"]

@@ -35,7 +35,7 @@ def test_torchrun_two_gpus_matches_one_gpu():
     if _devices() < 2:
         pytest.skip("one GPU visible")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "2", "--warmup", "1", "--proofs", "20000", "--no-cpu-baseline", "--max-seconds", "600"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--proofs", "20000", "--no-cpu-baseline", "--max-seconds", "600"]
     p2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                          "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", *common], cwd=ROOT, env=env,
                         capture_output=True, text=True, timeout=900)
@@ -65,9 +65,9 @@ def test_two_ranks_one_device_gloo():
         pytest.skip("no GPU")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PHANT_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--one-device", "--steps", "2",
-                        "--warmup", "1", "--proofs", "20000", "--no-cpu-baseline", "--max-seconds", "600"], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=900)
+                        "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--one-device", "--full",
+                        "--steps", "2", "--warmup", "1", "--proofs", "20000", "--no-cpu-baseline", "--max-seconds", "600"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     two = _line(p.stdout)
     assert "error" not in two and two["n_gpus"] == 2 and two["value"] > 0
@@ -77,8 +77,9 @@ def test_two_ranks_one_device_gloo():
     assert two["strong"]["predicted"]["n_gpus"] == 2 and two["strong"]["value"] > 0
     # the same control flow for node-set witnesses
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--one-device", "--workload",
-                        "nodeset", "--steps", "2", "--warmup", "1", "--proofs", "20000", "--no-cpu-baseline", "--max-seconds", "600"],
+                        "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--one-device", "--full",
+                        "--workload", "nodeset", "--steps", "2", "--warmup", "1", "--proofs", "20000", "--no-cpu-baseline",
+                        "--max-seconds", "600"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     ns = _line(p.stdout)
@@ -102,8 +103,8 @@ def test_the_wall_clock_guard_prints_an_error_line():
     """One GPU is enough for this one: a run that cannot finish in --max-seconds ends with a parseable line and rc 4."""
     if _devices() < 1:
         pytest.skip("no GPU")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "2000", "--inner", "50", "--max-seconds", "20", "--no-cpu-baseline",
-                        "--no-strong"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2000", "--inner", "50", "--max-seconds", "20",
+                        "--no-cpu-baseline", "--no-strong"], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 4, (p.returncode, p.stderr[-1500:])
     line = _line(p.stdout)
     assert line["value"] is None and "wall-clock guard" in line["error"]

@@ -21,6 +21,7 @@ ulimit -c 0
 mkdir -p gpurun_out/ab
 one() {  # label so env... -- args
   label=$1; so=$2; shift 2; envs=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done; [ "$1" = "--" ] && shift
+  set -- --full "$@"  # (the lines below read roofline / single_stream)
   cp tools/_ab/$so.so phant_amd/libphant_gpu.so
   env "${envs[@]}" timeout 300 python bench.py --no-cpu-baseline --no-strong "$@" 2>gpurun_out/ab/$label.err | grep "^{" | tail -1 > gpurun_out/ab/$label.json
   python - "$label" <<'P'

@@ -9,7 +9,7 @@ tail -1 "$OUT/smoke.log"
 if [ "$2" != "nopytest" ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q --timeout 400 > "$OUT/pytest_gpu.log" 2>&1; tail -3 "$OUT/pytest_gpu.log"
 fi
-b() { tag=$1; shift; timeout 400 python bench.py "$@" 2>&1 | grep '^{' | tail -1 > "$OUT/bench_$tag.json"; python - <<PY
+b() { tag=$1; shift; timeout 400 python bench.py --full "$@" 2>&1 | grep '^{' | tail -1 > "$OUT/bench_$tag.json"; python - <<PY
 import json
 try:
     d = json.load(open("$OUT/bench_$tag.json"))

@@ -14,7 +14,7 @@ for l in open("$OUT/sweep.jsonl"):
     d = json.loads(l)
     print(d["mode"], d["dedup_levels"], d["env"], "ok" if d["ok"] else "WRONG", "wall", d["wall_ms"], "event", d["event_ms"], "min", d["event_min_ms"], "hashed", d["nodes_hashed"])
 PY
-timeout 300 python bench.py --no-cpu-baseline --no-strong 2>&1 | grep '^{' | tail -1 > "$OUT/bench_config3.json"
+timeout 300 python bench.py --full --no-cpu-baseline --no-strong 2>&1 | grep '^{' | tail -1 > "$OUT/bench_config3.json"
 python -c "
 import json; d = json.load(open('$OUT/bench_config3.json'))
 print('config3', round(d['value'] / 1e6, 1), 'M/s ms', round(d['ms_per_step'], 4), 'kernel', round(d['roofline']['kernel_avg_ms'], 4), 'single', d.get('single_stream', {}).get('ms_per_pass'))"

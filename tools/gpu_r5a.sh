@@ -9,7 +9,7 @@ tail -1 "$OUT/smoke.log"
 timeout 900 python -m pytest tests/test_gpu_verify.py tests/test_gpu_x_verify_more.py -x -q --timeout 600 2>&1 | tail -5 | tee "$OUT/pytest_verify.log"
 line() {  # label, env..., -- bench args
   label=$1; shift; envs=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done; [ "$1" = "--" ] && shift
-  env "${envs[@]}" timeout 400 python bench.py --no-extra "$@" 2>"$OUT/$label.err" | grep '^{' | tail -1 > "$OUT/$label.json"
+  env "${envs[@]}" timeout 400 python bench.py --full --no-extra "$@" 2>"$OUT/$label.err" | grep '^{' | tail -1 > "$OUT/$label.json"
   python - "$OUT/$label.json" "$label" <<'P'
 import json, sys
 try:

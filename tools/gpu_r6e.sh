@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out/r6e; mkdir -p "$OUT"; ulimit -c 0; export TMPDIR=/tmp PYTHONUNBUFFERED=1; R=$PWD
 true
 true
-T0=$(date +%s); timeout 1200 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); timeout 1200 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r6e/bench_default.json"))

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out/r6m; mkdir -p "$OUT"; ulimit -c 0; export TMPDIR=/tmp PYTHONUNBUFFERED=1; R=$PWD
 T0=$(date +%s); timeout 2400 python -m pytest tests -m gpu -x -q > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc $? in $(( $(date +%s) - T0 )) s"; tail -3 "$OUT/pytest_gpu.log"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee "$OUT/smoke.log"
-T0=$(date +%s); timeout 1200 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench.py wall: $(( $(date +%s) - T0 )) s rc $?"
+T0=$(date +%s); timeout 1200 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench.py wall: $(( $(date +%s) - T0 )) s rc $?"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r6m/bench_default.json"))

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out/${1:-trie}
 mkdir -p "$OUT"; ulimit -c 0; export TMPDIR=/tmp PYTHONUNBUFFERED=1; R=$PWD
 timeout 300 python -m pytest tests/test_gpu_trie.py tests/test_gpu_comm.py -x -q --timeout 200 2>&1 | tail -3
-timeout 300 python bench.py --workload mptize --cpu-seconds 8 --steps 10 2>&1 | grep '^{' | tail -1 > "$OUT/bench_mptize.json"
+timeout 300 python bench.py --full --workload mptize --cpu-seconds 8 --steps 10 2>&1 | grep '^{' | tail -1 > "$OUT/bench_mptize.json"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench_mptize.json"))

@@ -20,7 +20,7 @@ for r in $(seq 1 $ROUNDS); do
     k=0
     for setting in "$@"; do
       k=$((k+1))
-      env $setting timeout 300 python bench.py --workload mptize --keys $keys --no-cpu-baseline --steps 10 2>&1 | grep '^{' | tail -1 > "$OUT/s${k}_${keys}_$r.json"; line "$OUT/s${k}_${keys}_$r.json" "$setting keys=$keys"
+      env $setting timeout 300 python bench.py --full --workload mptize --keys $keys --no-cpu-baseline --steps 10 2>&1 | grep '^{' | tail -1 > "$OUT/s${k}_${keys}_$r.json"; line "$OUT/s${k}_${keys}_$r.json" "$setting keys=$keys"
     done
   done
 done
