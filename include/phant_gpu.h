@@ -74,6 +74,9 @@ extern "C" {
                                        contradicts what the witness declares (storageHash, codeHash, nonce,
                                        balance, slot value), or its root is not anchored because the
                                        account proof above it failed */
+#define PHANT_PROOF_BAD_VALUE 23    /* phant_exec_witness_prestate only: the proof is valid, but the value it proves is not a
+                                       canonical account body rlp([nonce, balance, storageRoot, codeHash]) / slot value
+                                       rlp(minimal non-zero integer of 1..32 bytes) */
 
 typedef struct phant_ctx phant_ctx;
 
@@ -394,6 +397,60 @@ PHANT_API int32_t phant_witness_get(const phant_witness *w, phant_witness_info *
  * (tests, tools), not a validation. */
 PHANT_API int32_t phant_witness_verify(phant_ctx *ctx, const phant_witness *w, const uint8_t *expected_state_root,
                                        uint8_t *status, uint32_t *n_failed);
+
+/* ------------------------------------------------------- execution witness -> pre-state
+ * The witness stateless clients exchange DECLARES nothing: every trie node once in any order, the bytecodes, and the preimages of
+ * the touched keys --
+ *   { "state": ["0x<rlp node>", ...], "codes": ["0x<bytecode>", ...], "keys": ["0x<20-byte address>" | "0x<address ++ 32-byte slot>", ...] }
+ * ("codes" may be absent; unknown members such as "headers" are skipped; hex as phant_witness_parse_json).  Accounts are the distinct
+ * addresses of the keys (20-byte keys and the prefixes of 52-byte ones) in order of first appearance; slots are grouped under their
+ * account in order of first appearance; duplicate keys collapse.  A key of any other length is PHANT_E_INVALID_ARG (message: its
+ * index and the byte offset; a 32-byte slot without its address is not supported).
+ * phant_exec_witness_prestate resolves the pre-state the block runs on (src/state/statedb.zig:32 StateDB.init(accounts)) out of the
+ * proofs, on the GPU, with ONE host synchronisation: trie keys hashed, the set hashed ONCE and walked twice -- the accounts from
+ * state_root (the parent header's: the CALLER's trusted root, required), then every slot from the storage root its account's
+ * proven leaf carries --, leaves decoded strictly, and every code hashed (next to the node-set kernels) and matched to the
+ * proven codeHash.  Per account: status (PHANT_PROOF_*; a leaf that is no canonical account body: PHANT_PROOF_BAD_VALUE), nonce,
+ * balance (32 bytes big-endian), storage root and code hash (an ABSENT account: the empty account), code_index = the lowest index
+ * of a code whose keccak256 is the codeHash, PHANT_CODE_NONE for an empty codeHash or a code the witness does not carry (counted
+ * in n_missing_code, not a failure: a block may never load it).  Per slot: status (PHANT_PROOF_MISMATCH: its account is neither
+ * PRESENT nor ABSENT) and value (32 bytes big-endian, zero when ABSENT).  n_failed = accounts and slots neither PRESENT nor
+ * ABSENT; n_unused_codes = codes no PRESENT account's codeHash matches.  Output pointers are caller-owned host memory (NULL: not
+ * wanted), sized by phant_exec_witness_info's counts. */
+#define PHANT_CODE_NONE 0xffffffffu
+typedef struct phant_exec_witness phant_exec_witness;
+typedef struct phant_exec_witness_info {
+    uint32_t struct_size; /* = sizeof(phant_exec_witness_info) */
+    uint32_t n_accounts, n_slots, n_codes, total_nodes;
+    uint64_t nodes_len, code_bytes;
+    const uint8_t *addresses;   /* n_accounts x 20 */
+    const uint32_t *slot_first; /* n_accounts + 1: account i owns slots [slot_first[i], slot_first[i + 1]) */
+    const uint8_t *slots;       /* n_slots x 32: the slot preimages */
+    const uint8_t *codes;
+    const uint64_t *code_off;   /* n_codes + 1 */
+    const uint8_t *nodes;
+    const uint64_t *node_off;   /* total_nodes + 1 */
+} phant_exec_witness_info;
+typedef struct phant_prestate {
+    uint32_t struct_size; /* = sizeof(phant_prestate) */
+    uint8_t *account_status;  /* n_accounts */
+    uint64_t *nonces;         /* n_accounts */
+    uint8_t *balances;        /* n_accounts x 32 */
+    uint8_t *storage_roots;   /* n_accounts x 32 */
+    uint8_t *code_hashes;     /* n_accounts x 32 */
+    uint32_t *code_index;     /* n_accounts */
+    uint8_t *slot_status;     /* n_slots */
+    uint8_t *slot_vals;       /* n_slots x 32 */
+    uint32_t n_failed, n_missing_code, n_unused_codes;
+} phant_prestate;
+/* err (optional, err_cap bytes) receives a message with the byte offset on PHANT_E_INVALID_ARG */
+PHANT_API int32_t phant_exec_witness_parse_json(const char *json, uint64_t len, phant_exec_witness **out, char *err,
+                                                uint32_t err_cap);
+PHANT_API void phant_exec_witness_free(phant_exec_witness *w);
+/* pointers stay valid until phant_exec_witness_free */
+PHANT_API int32_t phant_exec_witness_get(const phant_exec_witness *w, phant_exec_witness_info *info);
+PHANT_API int32_t phant_exec_witness_prestate(phant_ctx *ctx, const phant_exec_witness *w, const uint8_t *state_root,
+                                              phant_prestate *out);
 
 /* ---------------------------------------------------------------- trie root
  * Replaces src/mpt/mpt.zig:38 `mptize(arena, list: []const KeyVal) !Hash32`

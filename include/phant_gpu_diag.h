@@ -87,7 +87,8 @@ enum {
     PHANT_DIAG_SORT_PREFIX_BITS,      /* state root: the device sort on this many key bits, ties left undecided (-1: its own choice) */
     PHANT_DIAG_SORT_REPAIR_BITS,      /* ... ties repaired (-1: its own choice) */
     PHANT_DIAG_NODESET_WAVE_MAX,      /* node-set witnesses of up to this many nodes are hashed a node per wave (default 2 048; 0: never) */
-    PHANT_DIAG_TRIE_SMALL_MAX_KEYS    /* trie hasher: up to this many keys a call takes the two-launch pass for small tries (-1: the default, 0: never) */
+    PHANT_DIAG_TRIE_SMALL_MAX_KEYS,   /* trie hasher: up to this many keys a call takes the two-launch pass for small tries (-1: the default, 0: never) */
+    PHANT_DIAG_CODE_HASH_FORM         /* phant_exec_witness_prestate: the codes hashed 0 = a half wave per code (the default), 1 = a lane per code */
 };
 PHANT_API int32_t phant_diag_set(phant_ctx *ctx, uint32_t knob, int64_t value);
 

@@ -34,6 +34,8 @@ PROOF_EXTRA_NODES = 19
 PROOF_MISSING_NODE = 20
 PROOF_BAD_INPUT = 21
 PROOF_MISMATCH = 22
+PROOF_BAD_VALUE = 23
+CODE_NONE = 0xFFFFFFFF
 
 # every symbol include/phant_gpu.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
@@ -76,6 +78,10 @@ SYMBOLS = {
     "phant_witness_free": (None, [_vp]),
     "phant_witness_get": (_i32, [_vp, _vp]),
     "phant_witness_verify": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "phant_exec_witness_parse_json": (_i32, [C.c_char_p, _u64, C.POINTER(_vp), C.c_char_p, _u32]),
+    "phant_exec_witness_free": (None, [_vp]),
+    "phant_exec_witness_get": (_i32, [_vp, _vp]),
+    "phant_exec_witness_prestate": (_i32, [_vp, _vp, _vp, _vp]),
     "phant_mpt_root": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "phant_mpt_root_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_strip_first_nibble": (_i32, [_vp, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),

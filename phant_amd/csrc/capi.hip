@@ -25,6 +25,9 @@
 struct phant_witness {
     phant::Witness w;
 };
+struct phant_exec_witness {
+    phant::ExecWitness w;
+};
 
 // The workspace of the node-set pipeline (mpt_verify_nodeset.hip): zeroed when it is allocated, never cleared afterwards -- every
 // launch on it carries an epoch greater than all before it.
@@ -66,6 +69,10 @@ struct phant_ctx {
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_pending = false;
+    // phant_exec_witness_prestate: the codes are hashed on a helper stream of their own, next to the node-set kernels (created on
+    // first use); code_form: PHANT_DIAG_CODE_HASH_FORM
+    phant::FlatSide code_side{nullptr, nullptr, nullptr};
+    uint32_t code_form = 0;
 };
 
 namespace {
@@ -237,6 +244,10 @@ void phant_ctx_destroy(phant_ctx* c) {
     if (c->side.fork) (void)hipEventDestroy(c->side.fork);
     if (c->side.join) (void)hipEventDestroy(c->side.join);
     if (c->side.join2) (void)hipEventDestroy(c->side.join2);
+    if (c->code_side.stream) (void)hipStreamSynchronize(c->code_side.stream);
+    if (c->code_side.fork) (void)hipEventDestroy(c->code_side.fork);
+    if (c->code_side.join) (void)hipEventDestroy(c->code_side.join);
+    if (c->code_side.stream) (void)hipStreamDestroy(c->code_side.stream);
     if (c->side.stream) (void)hipStreamDestroy(c->side.stream);
     if (c->side.stream2) (void)hipStreamDestroy(c->side.stream2);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -393,6 +404,7 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_SORT_REPAIR_BITS: t.sort_repair_bits = value; return PHANT_OK;
         case PHANT_DIAG_NODESET_WAVE_MAX: c->ns_tune.wave_max = (uint32_t)(value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : value); return PHANT_OK;
         case PHANT_DIAG_TRIE_SMALL_MAX_KEYS: t.small_max_keys = value; return PHANT_OK;
+        case PHANT_DIAG_CODE_HASH_FORM: c->code_form = value == 1 ? 1u : 0u; return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }
@@ -841,9 +853,8 @@ int32_t phant_mpt_verify_batch(phant_ctx* c, const uint8_t* roots, uint32_t n_ro
 
 /* -------------------------------------------------------------- node-set witnesses */
 
-// Runs the node-set pipeline on device-resident arguments on stream `st` with the workspace `sp` (a.fail_count given: the verdict).
-static int32_t nodeset_resident_on(phant_ctx* c, const phant::VerifyArgs& a, uint32_t total_nodes, hipStream_t st, NodesetSpace& sp,
-                                   bool timed) {
+// The workspace `sp` sized for total_nodes and the epoch of the next launch on it (stream `st`).
+static int32_t nodeset_prepare(phant_ctx* c, uint32_t total_nodes, hipStream_t st, NodesetSpace& sp) {
     if (total_nodes > sp.cap_nodes || !sp.dv.base) {
         const uint32_t cap = phant::verify_nodeset_capacity(total_nodes);
         HIP_TRY(c, hipStreamSynchronize(st));
@@ -860,6 +871,16 @@ static int32_t nodeset_resident_on(phant_ctx* c, const phant::VerifyArgs& a, uin
     }
     ++sp.epoch;
     if (&sp == &c->ns) c->last_was_nodeset = true;
+    return PHANT_OK;
+}
+
+// Runs the node-set pipeline on device-resident arguments on stream `st` with the workspace `sp` (a.fail_count given: the verdict).
+static int32_t nodeset_resident_on(phant_ctx* c, const phant::VerifyArgs& a, uint32_t total_nodes, hipStream_t st, NodesetSpace& sp,
+                                   bool timed) {
+    {
+        const int32_t rc = nodeset_prepare(c, total_nodes, st, sp);
+        if (rc) return rc;
+    }
     hipError_t e;
     if (timed) {
         TimedRegion t(c);
@@ -1302,6 +1323,187 @@ int32_t phant_witness_verify(phant_ctx* c, const phant_witness* pw, const uint8_
         for (uint32_t i = 0; i < n; ++i) bad += !(status[i] == PHANT_PROOF_PRESENT || status[i] == PHANT_PROOF_ABSENT);
         *n_failed = bad;
     }
+    return PHANT_OK;
+}
+
+/* ------------------------------------------------------- execution witness -> pre-state */
+
+int32_t phant_exec_witness_parse_json(const char* json, uint64_t len, phant_exec_witness** out, char* err, uint32_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (!out || (!json && len)) return PHANT_E_INVALID_ARG;
+    *out = nullptr;
+    std::unique_ptr<phant_exec_witness> w(new (std::nothrow) phant_exec_witness());
+    if (!w) return PHANT_E_OOM;
+    std::string msg;
+    if (!phant::exec_witness_parse_json(json, (size_t)len, w->w, msg)) {
+        if (err && err_cap) {
+            std::strncpy(err, msg.c_str(), err_cap - 1);
+            err[err_cap - 1] = 0;
+        }
+        return PHANT_E_INVALID_ARG;
+    }
+    *out = w.release();
+    return PHANT_OK;
+}
+
+void phant_exec_witness_free(phant_exec_witness* w) { delete w; }
+
+int32_t phant_exec_witness_get(const phant_exec_witness* pw, phant_exec_witness_info* info) {
+    if (!pw || !info || info->struct_size < sizeof(phant_exec_witness_info)) return PHANT_E_INVALID_ARG;
+    const phant::ExecWitness& w = pw->w;
+    info->n_accounts = w.n_accounts;
+    info->n_slots = w.n_slots;
+    info->n_codes = (uint32_t)(w.code_off.size() - 1);
+    info->total_nodes = (uint32_t)(w.node_off.size() - 1);
+    info->nodes_len = (uint64_t)w.nodes.size();
+    info->code_bytes = (uint64_t)w.codes.size();
+    info->addresses = w.preimages.data();
+    info->slot_first = w.slot_first.data();
+    info->slots = w.preimages.data() + 20 * (size_t)w.n_accounts;
+    info->codes = w.codes.data();
+    info->code_off = w.code_off.data();
+    info->nodes = w.nodes.data();
+    info->node_off = w.node_off.data();
+    return PHANT_OK;
+}
+
+// helper stream + events of the code hashing (created on first use)
+static int32_t ensure_code_side(phant_ctx* c) {
+    if (c->code_side.stream) return PHANT_OK;
+    HIP_TRY(c, hipStreamCreateWithFlags(&c->code_side.stream, hipStreamNonBlocking));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->code_side.fork, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->code_side.join, hipEventDisableTiming));
+    return PHANT_OK;
+}
+
+// Everything on the device, one synchronisation at the end:
+//   ctx stream   copies -> fork --------------------------------------------------------------------------- join -> code_match -> copies
+//                              \-> trie keys -> node-set hash -> account walk -> account decode -> slot walk -> slot decode /
+//   helper stream               `-> table clear -> code hash ------------------------------------------------------------'
+int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, const uint8_t* state_root, phant_prestate* out) {
+    if (!c || !pw || !out) return PHANT_E_INVALID_ARG;
+    if (out->struct_size < sizeof(phant_prestate)) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_prestate: struct_size too small");
+    if (!state_root) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_prestate: the trusted state root is required");
+    const phant::ExecWitness& w = pw->w;
+    const uint32_t na = w.n_accounts, ns = w.n_slots, nc = (uint32_t)(w.code_off.size() - 1);
+    const uint32_t total_nodes = (uint32_t)(w.node_off.size() - 1);
+    const size_t nodes_len = w.nodes.size(), code_bytes = w.codes.size(), pre_len = w.preimages.size();
+    const uint32_t slots_t = phant::code_table_slots(nc);
+    out->n_failed = out->n_missing_code = out->n_unused_codes = 0;
+    DeviceGuard g(c->device);
+    hipStream_t s = c->stream;
+    const size_t nk = (size_t)na + ns;
+    const size_t need = ws_round(pre_len + 16) + ws_round((nk + 1) * 8) + ws_round(nk * 32) + ws_round(32) + ws_round((size_t)na * 32) +
+                        ws_round((size_t)ns * 4) + ws_round(nodes_len + 16) + ws_round(((size_t)total_nodes + 1) * 8) +
+                        ws_round(code_bytes + 16) + ws_round(((size_t)nc + 1) * 8) + ws_round(na) + ws_round((size_t)na * 8) +
+                        ws_round((size_t)na * 4) + ws_round(ns) + ws_round((size_t)ns * 8) + ws_round((size_t)ns * 4) +
+                        ws_round((size_t)na * 8) + ws_round((size_t)na * 32) * 2 + ws_round((size_t)na * 4) + ws_round((size_t)ns * 32) +
+                        ws_round((size_t)nc * 32) + ws_round((size_t)nc * 4) + ws_round((size_t)slots_t * 4) * 2 + ws_round(16);
+    int32_t rc = ws_reset(c, need);
+    if (rc) return rc;
+    uint8_t* d_pre = ws_take<uint8_t>(c, pre_len + 16);
+    uint64_t* d_poff = ws_take<uint64_t>(c, nk + 1);
+    uint8_t* d_keys = ws_take<uint8_t>(c, nk * 32);
+    uint8_t* d_root = ws_take<uint8_t>(c, 32);
+    phant::PrestateArgs p{};
+    p.storage_roots = ws_take<uint8_t>(c, (size_t)na * 32);
+    uint32_t* d_sacc = ws_take<uint32_t>(c, ns);
+    uint8_t* d_nodes = ws_take<uint8_t>(c, nodes_len + 16);
+    uint64_t* d_noff = ws_take<uint64_t>(c, (size_t)total_nodes + 1);
+    uint8_t* d_codes = ws_take<uint8_t>(c, code_bytes + 16);
+    uint64_t* d_coff = ws_take<uint64_t>(c, (size_t)nc + 1);
+    p.acc_status = ws_take<uint8_t>(c, na);
+    uint64_t* d_avoff = ws_take<uint64_t>(c, na);
+    uint32_t* d_avlen = ws_take<uint32_t>(c, na);
+    p.slot_status = ws_take<uint8_t>(c, ns);
+    uint64_t* d_svoff = ws_take<uint64_t>(c, ns);
+    uint32_t* d_svlen = ws_take<uint32_t>(c, ns);
+    p.nonces = ws_take<uint64_t>(c, na);
+    p.balances = ws_take<uint8_t>(c, (size_t)na * 32);
+    p.code_hashes = ws_take<uint8_t>(c, (size_t)na * 32);
+    p.code_index = ws_take<uint32_t>(c, na);
+    p.slot_vals = ws_take<uint8_t>(c, (size_t)ns * 32);
+    p.code_dig = ws_take<uint32_t>(c, (size_t)nc * 8);
+    p.code_slot = ws_take<uint32_t>(c, nc);
+    p.table = ws_take<uint32_t>(c, slots_t);
+    p.table_used = ws_take<uint32_t>(c, slots_t);
+    p.counters = ws_take<uint32_t>(c, 4);
+    p.nodes = d_nodes;
+    p.na = na;
+    p.ns = ns;
+    p.nc = nc;
+    p.acc_voff = d_avoff;
+    p.acc_vlen = d_avlen;
+    p.slot_voff = d_svoff;
+    p.slot_vlen = d_svlen;
+    p.slot_account = d_sacc;
+    p.codes = d_codes;
+    p.code_off = d_coff;
+    p.mask = slots_t - 1u;
+    p.salt0 = c->ns_salt[0];
+    p.salt1 = c->ns_salt[1];
+    if (c->ws.io.overflowed) return fail(c, PHANT_E_DEVICE, "exec_witness_prestate: staging arena undersized");
+    rc = ensure_code_side(c);
+    if (rc) return rc;
+    if (na) {  // (the node-set workspace sized and its epoch taken before anything is queued: sizing it may wait for the stream)
+        rc = nodeset_prepare(c, total_nodes, s, c->ns);
+        if (rc) return rc;
+    }
+    if (code_bytes) HIP_TRY(c, hipMemcpyAsync(d_codes, w.codes.data(), code_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_coff, w.code_off.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
+    if (pre_len) HIP_TRY(c, hipMemcpyAsync(d_pre, w.preimages.data(), pre_len, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_poff, w.preimage_off.data(), (nk + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_root, state_root, 32, hipMemcpyHostToDevice, s));
+    if (ns) HIP_TRY(c, hipMemcpyAsync(d_sacc, w.slot_account.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+    if (nodes_len) HIP_TRY(c, hipMemcpyAsync(d_nodes, w.nodes.data(), nodes_len, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_noff, w.node_off.data(), ((size_t)total_nodes + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(p.counters, 0, 16, s));
+    {
+        TimedRegion t(c);  // (phant_timing: the kernels of both streams, the copies in and out left out)
+        HIP_TRY(c, hipEventRecord(c->code_side.fork, s));
+        hipStream_t h = c->code_side.stream;
+        HIP_TRY(c, hipStreamWaitEvent(h, c->code_side.fork, 0));
+        HIP_TRY(c, hipMemsetAsync(p.table, 0, (size_t)slots_t * 4, h));
+        HIP_TRY(c, hipMemsetAsync(p.table_used, 0, (size_t)slots_t * 4, h));
+        HIP_TRY(c, phant::launch_code_hash(p, c->code_form, h));
+        HIP_TRY(c, hipEventRecord(c->code_side.join, h));
+        if (na) {
+            HIP_TRY(c, phant::launch_keccak256_var(d_pre, d_poff, (uint32_t)nk, d_keys, s));
+            // the set is hashed ONCE; the accounts walk from the trusted root, the slots from the storage roots the account leaves prove
+            phant::VerifyArgs acc{d_root, 1, nullptr, d_keys, 32, d_nodes, nodes_len, d_noff, nullptr, na, p.acc_status, d_avoff, d_avlen};
+            phant::VerifyArgs sto{p.storage_roots, na, d_sacc, d_keys + 32ull * na, 32, d_nodes, nodes_len, d_noff, nullptr, ns,
+                                  p.slot_status, d_svoff, d_svlen};
+            hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s, c->ns_tune);
+            if (e == hipSuccess) e = phant::launch_nodeset_walk(acc, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+            if (e == hipSuccess) e = phant::launch_prestate_accounts(p, s);
+            if (e == hipSuccess) e = phant::launch_nodeset_walk(sto, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+            if (e != hipSuccess) {
+                c->ns.dirty = true;  // (whatever part of the launch ran: the next one starts from zeroed memory)
+                (void)hipStreamSynchronize(h);
+                return fail(c, PHANT_E_DEVICE, "exec_witness_prestate: node-set launch", e);
+            }
+            HIP_TRY(c, phant::launch_prestate_slots(p, s));
+        }
+        HIP_TRY(c, hipStreamWaitEvent(s, c->code_side.join, 0));
+        HIP_TRY(c, phant::launch_code_match(p, s));
+    }
+    uint32_t cnt[4] = {0, 0, 0, 0};
+    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(c, back(out->account_status, p.acc_status, na));
+    HIP_TRY(c, back(out->nonces, p.nonces, (size_t)na * 8));
+    HIP_TRY(c, back(out->balances, p.balances, (size_t)na * 32));
+    HIP_TRY(c, back(out->storage_roots, p.storage_roots, (size_t)na * 32));
+    HIP_TRY(c, back(out->code_hashes, p.code_hashes, (size_t)na * 32));
+    HIP_TRY(c, back(out->code_index, p.code_index, (size_t)na * 4));
+    HIP_TRY(c, back(out->slot_status, p.slot_status, ns));
+    HIP_TRY(c, back(out->slot_vals, p.slot_vals, (size_t)ns * 32));
+    HIP_TRY(c, back(cnt, p.counters, 12));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    out->n_failed = cnt[phant::PRE_CNT_FAILED];
+    out->n_missing_code = cnt[phant::PRE_CNT_MISSING_CODE];
+    out->n_unused_codes = cnt[phant::PRE_CNT_UNUSED_CODES];
     return PHANT_OK;
 }
 

@@ -128,6 +128,48 @@ hipError_t launch_mpt_verify_nodeset(const VerifyArgs& a, uint32_t total_nodes, 
 // nodes hashed per rate-block class by the launch of `epoch`, from a host copy of the workspace's first VERIFY_HEADER_WORDS
 // words; *overflow (may be null): nodes that went through the second table
 void verify_nodeset_stats_from_header(const uint32_t* hdr, uint32_t epoch, uint32_t hashed[8], uint32_t* overflow);
+// prestate.hip.h (included by mpt_verify_nodeset.hip): the pre-state of an execution witness between and behind the two walks of
+// the node-set pipeline (phant_exec_witness_prestate).  Every pointer is device memory of the call.
+struct PrestateArgs {
+    const uint8_t* nodes;
+    uint32_t na, ns, nc;
+    uint8_t* acc_status;          // na: the account walk's statuses, decoded in place
+    const uint64_t* acc_voff;
+    const uint32_t* acc_vlen;
+    uint64_t* nonces;             // na
+    uint8_t* balances;            // na x 32, big-endian
+    uint8_t* storage_roots;       // na x 32: the storage walk's root table
+    uint8_t* code_hashes;         // na x 32
+    uint32_t* code_index;         // na
+    uint8_t* slot_status;         // ns: the storage walk's statuses, decoded in place
+    const uint64_t* slot_voff;
+    const uint32_t* slot_vlen;
+    const uint32_t* slot_account; // ns
+    uint8_t* slot_vals;           // ns x 32, big-endian
+    uint32_t* counters;           // PRE_CNT_*: zeroed by the caller
+    const uint8_t* codes;
+    const uint64_t* code_off;     // nc + 1
+    uint32_t* code_dig;           // nc x 8 words
+    uint32_t* code_slot;          // nc: the table slot a code's digest lives in
+    uint32_t* table;              // mask + 1: 1 + the lowest code index with the slot's digest, 0 = free (zeroed by the caller)
+    uint32_t* table_used;         // mask + 1: an account matched the slot's digest (zeroed by the caller)
+    uint32_t mask;
+    uint32_t salt0, salt1;
+};
+enum : uint32_t { PRE_CNT_FAILED = 0, PRE_CNT_MISSING_CODE = 1, PRE_CNT_UNUSED_CODES = 2 };  // PrestateArgs::counters
+hipError_t launch_prestate_accounts(const PrestateArgs& a, hipStream_t st);  // account_decode_kernel
+hipError_t launch_prestate_slots(const PrestateArgs& a, hipStream_t st);     // slot_decode_kernel
+// code_hash_kernel (form 0: a half wave per code) or code_hash_lane_kernel (form 1: a lane per code); table / table_used zeroed
+hipError_t launch_code_hash(const PrestateArgs& a, uint32_t form, hipStream_t st);
+hipError_t launch_code_match(const PrestateArgs& a, hipStream_t st);         // code_match_kernel + code_unused_kernel
+uint32_t code_table_slots(uint32_t n_codes);
+// The node-set launch in its two phases: the HASH phase (classify + set_hash_kernel, or set_hash_wave_kernel for a small set) fills the
+// record table of `epoch`; the WALK phase (set_walk_kernel) may then run any number of times against that table, with keys, roots and
+// outputs of its own.  a.n == 0 in the hash phase: only the clearing (nothing will walk).  launch_mpt_verify_nodeset = both, once.
+hipError_t launch_nodeset_hash(const VerifyArgs& a, uint32_t total_nodes, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch,
+                               const uint32_t salt[2], hipStream_t st, const NodesetTune& tune);
+hipError_t launch_nodeset_walk(const VerifyArgs& a, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2],
+                               hipStream_t st);
 hipError_t launch_mpt_verdict(const uint8_t* d_status, const uint32_t* d_root_idx, uint32_t n,
                               uint32_t n_roots, uint32_t* d_fail_count, hipStream_t st);
 

@@ -31,6 +31,8 @@
 //                        WAVE per node, the sponge of coop_sponge.hip.h's one-state-per-wave form (3.8-5.2 us a permutation where a
 //                        lane takes 9: a set of a few hundred nodes is as long as ONE node's four permutations), no class lists;
 //                        the wave's first lane puts the node into the record table; the kernel also does the clearing.)
+//   (launch_nodeset_hash runs the kernels above, launch_nodeset_walk the one below: a set hashed once can be walked more than once --
+//   the accounts of an execution witness, then its slots from the storage roots their leaves prove: prestate.hip.h)
 //   set_walk_kernel      one lane per key, from its root: a reference costs ONE 48-byte record fetch (digest compared in
 //                        full, the node's place and form in the same line), a canonical full branch one 32-byte fetch of the
 //                        child reference for the key's nibble, anything else is staged into LDS and decoded (mpt_walk.hip.h,
@@ -618,17 +620,16 @@ uint32_t verify_nodeset_capacity(uint32_t total_nodes) {  // a power of two (the
 }
 size_t verify_nodeset_workspace_bytes(uint32_t cap_nodes) { return ns::layout(cap_nodes).end; }
 
-hipError_t launch_mpt_verify_nodeset(const VerifyArgs& v, uint32_t total_nodes, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch,
-                                     const uint32_t salt[2], hipStream_t st, const NodesetTune& tune) {
+static ns::Args nodeset_args(const VerifyArgs& v, uint32_t total_nodes, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch,
+                             const uint32_t salt[2], uint32_t order) {
     using namespace ns;
-    if (total_nodes > cap_nodes) return hipErrorInvalidValue;
     Args a;
     a.v = v;
     a.total_nodes = total_nodes;
     a.epoch = epoch;
     a.salt0 = salt[0];
     a.salt1 = salt[1];
-    a.order = tune.order;
+    a.order = order;
     const Layout l = layout(cap_nodes);
     a.hdr = reinterpret_cast<uint32_t*>(ws);
     a.ent = reinterpret_cast<uint4*>(ws + l.ent);
@@ -640,6 +641,14 @@ hipError_t launch_mpt_verify_nodeset(const VerifyArgs& v, uint32_t total_nodes, 
     a.ov_dig = reinterpret_cast<uint4*>(ws + l.ov_dig);
     a.thin = reinterpret_cast<unsigned long long*>(ws + l.thin);
     a.thin_mask = l.slots - 1u;
+    return a;
+}
+
+hipError_t launch_nodeset_hash(const VerifyArgs& v, uint32_t total_nodes, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch,
+                               const uint32_t salt[2], hipStream_t st, const NodesetTune& tune) {
+    using namespace ns;
+    if (total_nodes > cap_nodes) return hipErrorInvalidValue;
+    const Args a = nodeset_args(v, total_nodes, cap_nodes, ws, epoch, salt, tune.order);
     const uint32_t ng = total_nodes ? (total_nodes + 255u) / 256u : 1u;
     if (v.n != 0 && total_nodes != 0 && total_nodes <= tune.wave_max) {
         // a wave per node (up to two waves per CU the workgroups are single waves, which the dispatcher spreads over the CUs:
@@ -660,8 +669,24 @@ hipError_t launch_mpt_verify_nodeset(const VerifyArgs& v, uint32_t total_nodes, 
             else hipLaunchKernelGGL(set_hash_kernel<0>, dim3(wgs), dim3(256), tune.hash_lds, st, a);
         }
     }
+    return hipGetLastError();
+}
+
+// (the walk reads the table and the header's overflow count of `epoch`; it writes nothing but its outputs and the verdict)
+hipError_t launch_nodeset_walk(const VerifyArgs& v, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2],
+                               hipStream_t st) {
+    using namespace ns;
+    if (v.n == 0) return hipGetLastError();
+    const Args a = nodeset_args(v, 0, cap_nodes, ws, epoch, salt, 0);
     hipLaunchKernelGGL(set_walk_kernel, dim3((v.n + WALK_LANES - 1u) / WALK_LANES), dim3(WALK_LANES), 0, st, a);
     return hipGetLastError();
+}
+
+hipError_t launch_mpt_verify_nodeset(const VerifyArgs& v, uint32_t total_nodes, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch,
+                                     const uint32_t salt[2], hipStream_t st, const NodesetTune& tune) {
+    const hipError_t e = launch_nodeset_hash(v, total_nodes, cap_nodes, ws, epoch, salt, st, tune);
+    if (e != hipSuccess || v.n == 0) return e;
+    return launch_nodeset_walk(v, cap_nodes, ws, epoch, salt, st);
 }
 
 // nodes hashed per rate-block class by the launch of `epoch` on this workspace (host copy of its header)
@@ -678,3 +703,5 @@ void verify_nodeset_stats_from_header(const uint32_t* hdr, uint32_t epoch, uint3
 }
 
 }  // namespace phant
+
+#include "prestate.hip.h"

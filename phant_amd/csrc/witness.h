@@ -73,6 +73,23 @@ struct Witness {
     std::vector<uint64_t> node_src;         // total_nodes
 };
 
+// An execution witness as stateless clients exchange it (phant_exec_witness_parse_json): nothing is declared, every value comes out
+// of the proofs.  { "state": [node, ...], "codes": [bytecode, ...], "keys": [20-byte address | 52-byte address ++ slot, ...] }
+// Accounts are the distinct addresses in order of first appearance, slots grouped under their account in order of first
+// appearance (duplicates collapse): the slot_first layout of phant_state_root.
+struct ExecWitness {
+    ByteBlob nodes;                      // the "state" set, every node once, any order
+    std::vector<uint64_t> node_off;      // total_nodes + 1
+    ByteBlob codes;
+    std::vector<uint64_t> code_off;      // n_codes + 1
+    std::vector<uint8_t> preimages;      // n_accounts x 20 addresses, then n_slots x 32 slots: what the trie keys hash
+    std::vector<uint64_t> preimage_off;  // n_accounts + n_slots + 1
+    std::vector<uint32_t> slot_first;    // n_accounts + 1
+    std::vector<uint32_t> slot_account;  // n_slots
+    uint32_t n_accounts = 0, n_slots = 0;
+};
+bool exec_witness_parse_json(const char* json, size_t len, ExecWitness& out, std::string& err);
+
 bool witness_parse_json(const char* json, size_t len, Witness& out, std::string& err);
 // the same result with the accounts parsed on `threads` host threads (0 = as many as the host has, at most 32)
 bool witness_parse_json_mt(const char* json, size_t len, unsigned threads, Witness& out, std::string& err);

@@ -30,14 +30,20 @@
 // (20-byte address / 32-byte big-endian slot): the secure-trie keys keccak256(preimage) are computed on
 // the GPU by phant_witness_verify, batched, like every other hash of this library.
 //
+// The execution witness of stateless clients -- { "state": [..], "codes": [..], "keys": [..] }, nothing declared -- has a parser
+// of its own at the end of this file (exec_witness_parse_json, phant_exec_witness_parse_json).
+//
 // Pure host code (no HIP calls): parsing is testable without a GPU.
 #include <cstdint>
 #include <cstddef>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
+#include <array>
 #include <cstring>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <thread>
 #include <vector>
 
@@ -847,6 +853,155 @@ bool witness_parse_json_mt(const char* json, size_t len, unsigned threads, Witne
 
 bool witness_index_json(const char* json, size_t len, unsigned threads, Witness& w, std::string& err) {
     return threads == 1 ? parse_single(json, len, w, err, true) : parse_mt(json, len, threads, w, err, true);
+}
+
+// ---- the execution witness: { "state": [..], "codes": [..], "keys": [..] } (exec_witness_parse_json) ----
+namespace {
+
+// an array of hex data strings appended to `blob`, one offset per string
+bool parse_hex_array(Parser& ps, ByteBlob& blob, std::vector<uint64_t>& off, const char* what) {
+    if (!ps.expect('[')) return false;
+    if (ps.lit(']')) return true;
+    for (;;) {
+        Parser::View v;
+        if (!ps.view(v)) return false;
+        if (v.escaped || !hex_append(v.b, v.e, blob)) return ps.fail(what);
+        off.push_back((uint64_t)blob.size());
+        if (ps.lit(',')) continue;
+        return ps.expect(']');
+    }
+}
+
+struct KeyTable {
+    std::vector<std::array<uint8_t, 20>> addrs;
+    std::vector<std::vector<std::array<uint8_t, 32>>> slots;  // per account, in order of first appearance
+    std::unordered_map<std::string, uint32_t> account_of;     // address -> account index
+    std::unordered_set<std::string> seen_slot;                // address ++ slot
+    uint32_t account(const uint8_t* a) {
+        const std::string k(reinterpret_cast<const char*>(a), 20);
+        const auto it = account_of.find(k);
+        if (it != account_of.end()) return it->second;
+        const uint32_t i = (uint32_t)addrs.size();
+        account_of.emplace(k, i);
+        std::array<uint8_t, 20> x;
+        std::memcpy(x.data(), a, 20);
+        addrs.push_back(x);
+        slots.emplace_back();
+        return i;
+    }
+};
+
+bool parse_keys(Parser& ps, KeyTable& t) {
+    if (!ps.expect('[')) return false;
+    if (ps.lit(']')) return true;
+    ByteBlob buf;
+    for (size_t idx = 0;; ++idx) {
+        Parser::View v;
+        if (!ps.view(v)) return false;
+        buf.clear();
+        if (v.escaped || !hex_append(v.b, v.e, buf)) return ps.fail(("key " + std::to_string(idx) + " is not hex data").c_str());
+        if (buf.size() == 20) {
+            t.account(buf.data());
+        } else if (buf.size() == 52) {
+            const uint32_t a = t.account(buf.data());
+            if (t.seen_slot.emplace(reinterpret_cast<const char*>(buf.data()), 52).second) {
+                std::array<uint8_t, 32> sl;
+                std::memcpy(sl.data(), buf.data() + 20, 32);
+                t.slots[a].push_back(sl);
+            }
+        } else if (buf.size() == 32) {
+            return ps.fail(("key " + std::to_string(idx) +
+                            " is a 32-byte slot without its address (unpaired slot keys are not supported; send address ++ slot)")
+                               .c_str());
+        } else {
+            return ps.fail(("key " + std::to_string(idx) + " is " + std::to_string(buf.size()) +
+                            " bytes: a key is a 20-byte address or a 52-byte address ++ slot")
+                               .c_str());
+        }
+        if (ps.lit(',')) continue;
+        return ps.expect(']');
+    }
+}
+
+}  // namespace
+
+bool exec_witness_parse_json(const char* json, size_t len, ExecWitness& w, std::string& err) {
+    w = ExecWitness();
+    w.node_off.push_back(0);
+    w.code_off.push_back(0);
+    w.nodes.reserve(len / 2);
+    Parser ps{json, json + len, std::string(), json};
+    KeyTable keys;
+    bool have_state = false, have_codes = false, have_keys = false;
+    bool ok = ps.expect('{');
+    if (ok && !ps.lit('}')) {
+        for (;;) {
+            Parser::View name;
+            if (!(ok = ps.view(name) && ps.expect(':'))) break;
+            if (name.is("state")) {
+                if (have_state) {
+                    ok = ps.fail("duplicate \"state\"");
+                    break;
+                }
+                have_state = true;
+                if (!(ok = parse_hex_array(ps, w.nodes, w.node_off, "state node is not hex data"))) break;
+            } else if (name.is("codes")) {
+                if (have_codes) {
+                    ok = ps.fail("duplicate \"codes\"");
+                    break;
+                }
+                have_codes = true;
+                if (!(ok = parse_hex_array(ps, w.codes, w.code_off, "code is not hex data"))) break;
+            } else if (name.is("keys")) {
+                if (have_keys) {
+                    ok = ps.fail("duplicate \"keys\"");
+                    break;
+                }
+                have_keys = true;
+                if (!(ok = parse_keys(ps, keys))) break;
+            } else if (!(ok = ps.skip_value())) {
+                break;
+            }
+            if (ps.lit(',')) continue;
+            ok = ps.expect('}');
+            break;
+        }
+    }
+    if (ok) {
+        ps.ws();
+        if (ps.p != ps.end) ok = ps.fail("trailing characters");
+    }
+    if (ok && !have_state) ok = ps.fail("missing \"state\"");
+    if (ok && !have_keys) ok = ps.fail("missing \"keys\"");
+    if (!ok) {
+        err = ps.err;
+        w = ExecWitness();
+        return false;
+    }
+    // accounts in order of first appearance, their slots behind each other: what the trie keys are hashed from
+    w.n_accounts = (uint32_t)keys.addrs.size();
+    size_t m = 0;
+    for (const auto& s : keys.slots) m += s.size();
+    w.n_slots = (uint32_t)m;
+    w.preimages.resize(20 * (size_t)w.n_accounts + 32 * m);
+    w.preimage_off.resize((size_t)w.n_accounts + m + 1);
+    w.slot_first.resize((size_t)w.n_accounts + 1);
+    w.slot_account.resize(m);
+    size_t k = 0;
+    for (uint32_t a = 0; a < w.n_accounts; ++a) {
+        std::memcpy(w.preimages.data() + 20 * (size_t)a, keys.addrs[a].data(), 20);
+        w.preimage_off[a] = 20 * (uint64_t)a;
+        w.slot_first[a] = (uint32_t)k;
+        for (const auto& sl : keys.slots[a]) {
+            std::memcpy(w.preimages.data() + 20 * (size_t)w.n_accounts + 32 * k, sl.data(), 32);
+            w.preimage_off[w.n_accounts + k] = 20 * (uint64_t)w.n_accounts + 32 * (uint64_t)k;
+            w.slot_account[k] = a;
+            ++k;
+        }
+    }
+    w.slot_first[w.n_accounts] = (uint32_t)k;
+    w.preimage_off[w.n_accounts + m] = (uint64_t)w.preimages.size();
+    return true;
 }
 
 }  // namespace phant

@@ -1,0 +1,195 @@
+"""The pre-state of a block out of an execution witness as stateless clients exchange it -- the step phant's
+newPayloadV2Handler (src/engine_api/execution_payload.zig:175-181) leaves open before `runBlock`, which needs
+`StateDB.init(allocator, accounts)` (src/state/statedb.zig:32).
+
+The document declares nothing; every value comes out of the proofs (include/phant_gpu.h, execution-witness section):
+
+    { "state": ["0x<rlp node>", ...], "codes": ["0x<bytecode>", ...], "keys": ["0x<address>" | "0x<address ++ slot>", ...] }
+
+    w = StatelessWitness.parse_json(text)                # host-only (no GPU needed)
+    pre = w.prestate(ctx, parent_state_root)            # the GPU: one call, one synchronisation
+    pre.ok, pre.accounts                                # -> state.AccountState list for StateDB.init
+    pre = new_payload_prestate(text, parent_state_root) # the hook: raises unless every proof holds
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib as L
+from .context import Context, default_context
+from .state import AccountState
+
+PROOF_BAD_VALUE = L.PROOF_BAD_VALUE
+CODE_NONE = L.CODE_NONE
+
+
+class ExecWitnessInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_accounts", C.c_uint32), ("n_slots", C.c_uint32), ("n_codes", C.c_uint32),
+                ("total_nodes", C.c_uint32), ("nodes_len", C.c_uint64), ("code_bytes", C.c_uint64),
+                ("addresses", C.c_void_p), ("slot_first", C.c_void_p), ("slots", C.c_void_p), ("codes", C.c_void_p),
+                ("code_off", C.c_void_p), ("nodes", C.c_void_p), ("node_off", C.c_void_p)]
+
+
+class PrestateOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("account_status", C.c_void_p), ("nonces", C.c_void_p), ("balances", C.c_void_p),
+                ("storage_roots", C.c_void_p), ("code_hashes", C.c_void_p), ("code_index", C.c_void_p),
+                ("slot_status", C.c_void_p), ("slot_vals", C.c_void_p), ("n_failed", C.c_uint32),
+                ("n_missing_code", C.c_uint32), ("n_unused_codes", C.c_uint32)]
+
+
+class WitnessFormatError(ValueError):
+    pass
+
+
+class PrestateError(RuntimeError):
+    def __init__(self, msg: str, prestate: "PreState"):
+        super().__init__(msg)
+        self.prestate = prestate
+
+
+def _view(ptr, count, dtype):
+    if not count or not ptr:
+        return np.zeros(0, dtype)
+    n = count * np.dtype(dtype).itemsize
+    return np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=dtype, count=count)
+
+
+@dataclass
+class PreState:
+    """What phant_exec_witness_prestate proved.  accounts: the PRESENT accounts as state.AccountState (code by code_index,
+    only the non-zero slots in storage), in witness order; absent: the addresses proven absent."""
+    accounts: list
+    absent: list
+    addresses: list
+    account_status: np.ndarray
+    slot_status: np.ndarray
+    nonces: np.ndarray
+    balances: np.ndarray
+    storage_roots: np.ndarray
+    code_hashes: np.ndarray
+    code_index: np.ndarray
+    slot_vals: np.ndarray
+    n_failed: int
+    n_missing_code: int
+    n_unused_codes: int
+    missing_code: list = field(default_factory=list)  # addresses of PRESENT accounts whose code the witness does not carry
+
+    @property
+    def ok(self) -> bool:
+        return self.n_failed == 0
+
+
+class StatelessWitness:
+    def __init__(self, handle):
+        self._h = handle
+        self._lib = L.lib()
+
+    @staticmethod
+    def parse_json(text: str | bytes) -> "StatelessWitness":
+        lib = L.lib()
+        data = text.encode() if isinstance(text, str) else bytes(text)
+        h = C.c_void_p()
+        err = C.create_string_buffer(256)
+        rc = lib.phant_exec_witness_parse_json(data, len(data), C.byref(h), err, 256)
+        if rc != L.OK:
+            raise WitnessFormatError(err.value.decode() or f"phant_exec_witness_parse_json rc={rc}")
+        return StatelessWitness(h)
+
+    def info(self) -> dict:
+        """numpy views (valid while this object lives) of the parsed arrays + counts."""
+        wi = ExecWitnessInfo()
+        wi.struct_size = C.sizeof(ExecWitnessInfo)
+        rc = self._lib.phant_exec_witness_get(self._h, C.byref(wi))
+        if rc != L.OK:
+            raise L.PhantError(rc, "phant_exec_witness_get")
+        return {"n_accounts": wi.n_accounts, "n_slots": wi.n_slots, "n_codes": wi.n_codes, "total_nodes": wi.total_nodes,
+                "nodes_len": wi.nodes_len, "code_bytes": wi.code_bytes,
+                "addresses": _view(wi.addresses, wi.n_accounts * 20, np.uint8).reshape(-1, 20),
+                "slot_first": _view(wi.slot_first, wi.n_accounts + 1, np.uint32),
+                "slots": _view(wi.slots, wi.n_slots * 32, np.uint8).reshape(-1, 32),
+                "codes": _view(wi.codes, wi.code_bytes, np.uint8), "code_off": _view(wi.code_off, wi.n_codes + 1, np.uint64),
+                "nodes": _view(wi.nodes, wi.nodes_len, np.uint8), "node_off": _view(wi.node_off, wi.total_nodes + 1, np.uint64)}
+
+    def prestate_arrays(self, ctx: Context | None, state_root: bytes) -> dict:
+        """The raw outputs of phant_exec_witness_prestate (numpy arrays + the three counts)."""
+        ctx = ctx or default_context()
+        if state_root is None or len(state_root) != 32:
+            raise ValueError("state_root must be the 32-byte state root the caller trusts")
+        i = self.info()
+        na, ns = i["n_accounts"], i["n_slots"]
+        r = {"account_status": np.zeros(max(na, 1), np.uint8), "nonces": np.zeros(max(na, 1), np.uint64),
+             "balances": np.zeros((max(na, 1), 32), np.uint8), "storage_roots": np.zeros((max(na, 1), 32), np.uint8),
+             "code_hashes": np.zeros((max(na, 1), 32), np.uint8), "code_index": np.zeros(max(na, 1), np.uint32),
+             "slot_status": np.zeros(max(ns, 1), np.uint8), "slot_vals": np.zeros((max(ns, 1), 32), np.uint8)}
+        o = PrestateOut()
+        o.struct_size = C.sizeof(PrestateOut)
+        for k, a in r.items():
+            setattr(o, k, a.ctypes.data)
+        root = C.create_string_buffer(bytes(state_root), 32)
+        ctx.check(self._lib.phant_exec_witness_prestate(ctx.handle, self._h, root, C.byref(o)))
+        out = {k: a[:na] if k not in ("slot_status", "slot_vals") else a[:ns] for k, a in r.items()}
+        out.update(n_failed=int(o.n_failed), n_missing_code=int(o.n_missing_code), n_unused_codes=int(o.n_unused_codes))
+        return out
+
+    def prestate(self, ctx: Context | None, state_root: bytes) -> PreState:
+        r = self.prestate_arrays(ctx, state_root)
+        i = self.info()
+        addrs = [bytes(a) for a in i["addresses"]]
+        first, slots = i["slot_first"], i["slots"]
+        codes, code_off = i["codes"], i["code_off"]
+        accounts, absent, missing = [], [], []
+        for k, addr in enumerate(addrs):
+            st = int(r["account_status"][k])
+            if st == L.PROOF_ABSENT:
+                absent.append(addr)
+                continue
+            if st != L.PROOF_PRESENT:
+                continue
+            ci = int(r["code_index"][k])
+            code = b"" if ci == CODE_NONE else codes[int(code_off[ci]):int(code_off[ci + 1])].tobytes()
+            if ci == CODE_NONE and r["code_hashes"][k].tobytes() != _EMPTY_CODE:
+                missing.append(addr)
+            storage = {}
+            for j in range(int(first[k]), int(first[k + 1])):
+                v = int.from_bytes(r["slot_vals"][j].tobytes(), "big")
+                if r["slot_status"][j] == L.PROOF_PRESENT and v:
+                    storage[int.from_bytes(slots[j].tobytes(), "big")] = v
+            accounts.append(AccountState(addr=addr, nonce=int(r["nonces"][k]),
+                                         balance=int.from_bytes(r["balances"][k].tobytes(), "big"), code=code, storage=storage))
+        return PreState(accounts=accounts, absent=absent, addresses=addrs, account_status=r["account_status"],
+                        slot_status=r["slot_status"], nonces=r["nonces"], balances=r["balances"],
+                        storage_roots=r["storage_roots"], code_hashes=r["code_hashes"], code_index=r["code_index"],
+                        slot_vals=r["slot_vals"], n_failed=r["n_failed"], n_missing_code=r["n_missing_code"],
+                        n_unused_codes=r["n_unused_codes"], missing_code=missing)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.phant_exec_witness_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_EMPTY_CODE = bytes.fromhex("c5d2460186f7233c927e7db2dcc703c0e500b653ca82273b7bfad8045d85a470")
+
+
+def new_payload_prestate(witness_json: str | bytes, parent_state_root: bytes, ctx: Context | None = None) -> PreState:
+    """The hook newPayloadV2Handler (execution_payload.zig:175-181) would call before `runBlock`: the pre-state the block runs
+    on, proven against `parent_state_root` -- the parent header's state root the node already trusts.  Raises
+    WitnessFormatError for a malformed document and PrestateError (carrying the PreState) when any proof fails; a code the
+    witness does not carry is not a failure here (pre.missing_code: the caller decides)."""
+    w = StatelessWitness.parse_json(witness_json)
+    try:
+        pre = w.prestate(ctx, parent_state_root)
+    finally:
+        w.close()
+    if not pre.ok:
+        raise PrestateError(f"execution witness: {pre.n_failed} account / slot proofs failed against the parent state root", pre)
+    return pre
