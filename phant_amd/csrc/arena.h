@@ -57,6 +57,17 @@ struct DevArena {
     }
 };
 
+// Stands in for a DevArena to count what a list of take<T>() calls needs: the size to reset() the arena to before the same
+// list runs against it.
+struct ArenaSizer {
+    size_t bytes = 0;
+    template <class T>
+    T* take(size_t count) {
+        bytes += DevArena::round(count * sizeof(T));
+        return nullptr;
+    }
+};
+
 // Switches of the trie hasher and of the state root's key sort (per ctx; set through include/phant_gpu_diag.h's phant_diag_set by
 // tests and tools, never read from the environment).  -1 / 0 / false = the library's own choice (the constants in trie_build.hip).
 struct TrieTune {

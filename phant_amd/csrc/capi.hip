@@ -107,29 +107,28 @@ int32_t fail(phant_ctx* c, int32_t code, const char* what, hipError_t e = hipSuc
         if (e_ != hipSuccess) return fail((c), PHANT_E_DEVICE, #call, e_); \
     } while (0)
 
-// Reserve `total` bytes of staging workspace (drops previous contents).
-int32_t ws_reset(phant_ctx* c, size_t total) {
-    if (total > c->ws.io.cap) {
-        hipError_t s = hipStreamSynchronize(c->stream);
-        if (s != hipSuccess) return fail(c, PHANT_E_DEVICE, "hipStreamSynchronize", s);
-    }
-    hipError_t e = c->ws.io.reset(total);
+// Lay out a call's staging arrays in `io` (drops its previous contents).  `lay(arena)` makes the call's take<T>() calls: it runs
+// once against a counter, which sizes the arena (stream `s` synchronised before it grows: a kernel may still read the old
+// one), then against the arena itself.  Afterwards io.used is the counted total.
+template <class Lay>
+int32_t lay_out(phant_ctx* c, hipStream_t s, phant::DevArena& io, const Lay& lay) {
+    phant::ArenaSizer size;
+    lay(size);
+    if (size.bytes > io.cap) HIP_TRY(c, hipStreamSynchronize(s));
+    hipError_t e = io.reset(size.bytes);
     if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(workspace)", e);
+    lay(io);
+    if (io.overflowed) return fail(c, PHANT_E_DEVICE, "staging arena undersized");
     return PHANT_OK;
-}
-size_t ws_round(size_t n) { return phant::DevArena::round(n); }
-template <class T>
-T* ws_take(phant_ctx* c, size_t count) {
-    return c->ws.io.take<T>(count);
 }
 
 struct TimedRegion {
-    phant_ctx* c;
-    explicit TimedRegion(phant_ctx* ctx) : c(ctx) {
-        if (c->timing) (void)hipEventRecord(c->ev0, c->stream);
+    phant_ctx* c;  // null: not timed
+    explicit TimedRegion(phant_ctx* ctx, bool timed = true) : c(timed && ctx->timing ? ctx : nullptr) {
+        if (c) (void)hipEventRecord(c->ev0, c->stream);
     }
     ~TimedRegion() {
-        if (c->timing) {
+        if (c) {
             (void)hipEventRecord(c->ev1, c->stream);
             c->ev_pending = true;
         }
@@ -424,9 +423,9 @@ int32_t phant_keccak_rate(phant_ctx* c, uint32_t waves_per_simd, uint32_t perms,
     int cus = 0;
     HIP_TRY(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     const uint32_t blocks = (uint32_t)cus * waves_per_simd;  // a 256-lane workgroup = one wave on each of a CU's four SIMDs
-    const int32_t rc = ws_reset(c, (size_t)blocks * 256 * 4 + 256);
+    uint32_t* d_out = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) { d_out = io.template take<uint32_t>((size_t)blocks * 256); });
     if (rc) return rc;
-    uint32_t* d_out = ws_take<uint32_t>(c, (size_t)blocks * 256);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(c, hipEventCreate(&e0));
     hipError_t e = hipEventCreate(&e1);
@@ -480,11 +479,14 @@ int32_t phant_keccak256_batch(phant_ctx* c, const uint8_t* blob, const uint64_t*
     const size_t blob_len = (size_t)(hi - lo);
     if (blob_len && !blob) return fail(c, PHANT_E_INVALID_ARG, "keccak256_batch: null blob");
     DeviceGuard g(c->device);
-    int32_t rc = ws_reset(c, ws_round(blob_len + 16) + ws_round((size_t)(n + 1) * 8) + ws_round((size_t)n * 32));
+    uint8_t *d_blob = nullptr, *d_out = nullptr;
+    uint64_t* d_off = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        d_blob = io.template take<uint8_t>(blob_len + 16);
+        d_off = io.template take<uint64_t>((size_t)n + 1);
+        d_out = io.template take<uint8_t>((size_t)n * 32);
+    });
     if (rc) return rc;
-    uint8_t* d_blob = ws_take<uint8_t>(c, blob_len + 16);
-    uint64_t* d_off = ws_take<uint64_t>(c, (size_t)n + 1);
-    uint8_t* d_out = ws_take<uint8_t>(c, (size_t)n * 32);
     std::vector<uint64_t> rel((size_t)n + 1);
     for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
     if (blob_len) HIP_TRY(c, hipMemcpyAsync(d_blob, blob + lo, blob_len, hipMemcpyHostToDevice, c->stream));
@@ -541,13 +543,16 @@ int32_t phant_logs_bloom(phant_ctx* c, const uint8_t* items, const uint64_t* ite
     const size_t blob_len = (size_t)(hi - lo);
     if (blob_len && !items) return fail(c, PHANT_E_INVALID_ARG, "logs_bloom: null items");
     DeviceGuard g(c->device);
-    int32_t rc = ws_reset(c, ws_round(blob_len + 16) + ws_round(((size_t)n_items + 1) * 8) + ws_round((size_t)n_items * 4 + 4) +
-                                 ws_round((size_t)n_receipts * 256));
+    uint8_t *d_items = nullptr, *d_blooms = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_rcpt = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        d_items = io.template take<uint8_t>(blob_len + 16);
+        d_off = io.template take<uint64_t>((size_t)n_items + 1);
+        d_rcpt = io.template take<uint32_t>((size_t)n_items + 1);
+        d_blooms = io.template take<uint8_t>((size_t)n_receipts * 256);
+    });
     if (rc) return rc;
-    uint8_t* d_items = ws_take<uint8_t>(c, blob_len + 16);
-    uint64_t* d_off = ws_take<uint64_t>(c, (size_t)n_items + 1);
-    uint32_t* d_rcpt = ws_take<uint32_t>(c, (size_t)n_items + 1);
-    uint8_t* d_blooms = ws_take<uint8_t>(c, (size_t)n_receipts * 256);
     std::vector<uint64_t> rel((size_t)n_items + 1, 0);
     for (uint32_t i = 0; i <= n_items && n_items; ++i) rel[i] = item_off[i] - lo;
     if (blob_len) HIP_TRY(c, hipMemcpyAsync(d_items, items + lo, blob_len, hipMemcpyHostToDevice, c->stream));
@@ -575,10 +580,12 @@ int32_t phant_sender_addresses(phant_ctx* c, const uint8_t* pubkeys, uint64_t st
     if (n == 0) return PHANT_OK;
     if (!pubkeys || !out20 || stride < 64) return fail(c, PHANT_E_INVALID_ARG, "sender_addresses: bad argument");
     DeviceGuard g(c->device);
-    int32_t rc = ws_reset(c, ws_round((size_t)n * 64 + 16) + ws_round((size_t)n * 20));
+    uint8_t *d_pk = nullptr, *d_out = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        d_pk = io.template take<uint8_t>((size_t)n * 64 + 16);
+        d_out = io.template take<uint8_t>((size_t)n * 20);
+    });
     if (rc) return rc;
-    uint8_t* d_pk = ws_take<uint8_t>(c, (size_t)n * 64 + 16);
-    uint8_t* d_out = ws_take<uint8_t>(c, (size_t)n * 20);
     if (stride == 64) {
         HIP_TRY(c, hipMemcpyAsync(d_pk, pubkeys, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
     } else {  // pack: only the 64 key bytes travel
@@ -608,41 +615,81 @@ static int32_t ensure_side(phant_ctx* c) {
     return PHANT_OK;
 }
 
-// Runs the verify pipeline on device-resident arguments (shared by all forms) on stream `st` with the
-// workspace arena `dv`; `side` = helper stream of the two-tier pipeline or nullptr (then its tiers run one after the other).
-static int32_t verify_resident_on(phant_ctx* c, const phant::VerifyArgs& a_in, uint32_t total_nodes, hipStream_t st,
-                                  phant::DevArena& dv, const phant::FlatSide* side, bool timed) {
-    phant::VerifyArgs a = a_in;
-    a.total_nodes = total_nodes;
-    const size_t need = phant::verify_workspace_bytes(total_nodes);
-    if (need > dv.cap) {
+// The workspace `sp` sized for total_nodes and the epoch of the next launch on it (stream `st`).
+static int32_t nodeset_prepare(phant_ctx* c, uint32_t total_nodes, hipStream_t st, NodesetSpace& sp) {
+    if (total_nodes > sp.cap_nodes || !sp.dv.base) {
+        const uint32_t cap = phant::verify_nodeset_capacity(total_nodes);
         HIP_TRY(c, hipStreamSynchronize(st));
-        hipError_t e = dv.reset(need);
-        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(verify workspace)", e);
-        // (the pipeline validates whatever its group table holds -- it never clears it --, so this is not needed for
-        // correctness; it keeps the first launch on fresh memory deterministic)
-        HIP_TRY(c, hipMemsetAsync(dv.base, 0, dv.cap, st));
+        sp.cap_nodes = 0;
+        hipError_t e = sp.dv.reset(phant::verify_nodeset_workspace_bytes(cap));
+        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(node-set workspace)", e);
+        sp.cap_nodes = cap;
+        sp.dirty = true;
     }
-    if (&dv == &c->dv) c->last_was_nodeset = false;
-    auto launch = [&]() { return phant::launch_mpt_verify(a, total_nodes, dv.base, c->dedup_levels, st, side, c->tune); };
-    if (timed) {
-        TimedRegion t(c);
-        HIP_TRY(c, launch());
-    } else {
-        HIP_TRY(c, launch());
+    if (sp.dirty || sp.epoch >= 0xfffffff0u) {
+        HIP_TRY(c, hipMemsetAsync(sp.dv.base, 0, sp.dv.cap, st));
+        sp.epoch = 0;
+        sp.dirty = false;
     }
-    // phant_verify_kernel_ms reads the per-kernel events of THIS launch or nothing: a launch that took the S = 0 form (or ran
-    // the tiers next to each other) recorded none
-    if (&dv == &c->dv) c->kev_valid = c->tune.serial && c->tune.kernel_ev && c->last_shallow != 0u;
+    ++sp.epoch;
+    if (&sp == &c->ns) c->last_was_nodeset = true;
     return PHANT_OK;
 }
 
-static int32_t verify_resident(phant_ctx* c, const phant::VerifyArgs& a, uint32_t total_nodes) {
-    {
-        const int32_t src = ensure_side(c);
-        if (src) return src;
+// Where a verify call runs: a stream and the workspaces that go with it, the ctx's own or a streaming slot's.
+struct Lane {
+    hipStream_t stream;
+    phant::DevArena& io;          // staging of the host forms
+    phant::DevArena& dv;          // workspace of the per-proof pipeline
+    NodesetSpace& ns;             // ... of the node-set pipeline
+    const phant::FlatSide* side;  // per-proof form: the ctx's helper stream (null: the two tiers one after the other)
+    bool timed;                   // inside phant_timing's events
+};
+static Lane ctx_lane(phant_ctx* c, bool timed) { return {c->stream, c->ws.io, c->dv, c->ns, &c->side, timed}; }
+static Lane slot_lane(phant_ctx::Slot& sl) { return {sl.stream, sl.io, sl.dv, sl.ns, nullptr, false}; }
+
+// Runs the pipeline of a's form (a.proof_first_node == nullptr: the node-set one) on device-resident arguments, on w's stream
+// with w's workspaces.  What phant_verify_stats and phant_verify_kernel_ms report follows the ctx's own workspaces only.
+static int32_t run_verify(phant_ctx* c, const Lane& w, phant::VerifyArgs a, uint32_t total_nodes) {
+    if (!a.proof_first_node) {
+        const int32_t rc = nodeset_prepare(c, total_nodes, w.stream, w.ns);
+        if (rc) return rc;
+        hipError_t e;
+        {
+            TimedRegion t(c, w.timed);
+            e = phant::launch_mpt_verify_nodeset(a, total_nodes, w.ns.cap_nodes, w.ns.dv.base, w.ns.epoch, c->ns_salt, w.stream,
+                                                 c->ns_tune);
+        }
+        if (e != hipSuccess) {
+            w.ns.dirty = true;  // (whatever part of the launch ran: the next one starts from zeroed memory)
+            return fail(c, PHANT_E_DEVICE, "launch_mpt_verify_nodeset", e);
+        }
+        return PHANT_OK;
     }
-    return verify_resident_on(c, a, total_nodes, c->stream, c->dv, &c->side, true);
+    if (w.side) {
+        const int32_t rc = ensure_side(c);
+        if (rc) return rc;
+    }
+    a.total_nodes = total_nodes;
+    const size_t need = phant::verify_workspace_bytes(total_nodes);
+    if (need > w.dv.cap) {
+        HIP_TRY(c, hipStreamSynchronize(w.stream));
+        hipError_t e = w.dv.reset(need);
+        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(verify workspace)", e);
+        // (the pipeline validates whatever its group table holds -- it never clears it --, so this is not needed for
+        // correctness; it keeps the first launch on fresh memory deterministic)
+        HIP_TRY(c, hipMemsetAsync(w.dv.base, 0, w.dv.cap, w.stream));
+    }
+    const bool own = &w.dv == &c->dv;
+    if (own) c->last_was_nodeset = false;
+    {
+        TimedRegion t(c, w.timed);
+        HIP_TRY(c, phant::launch_mpt_verify(a, total_nodes, w.dv.base, c->dedup_levels, w.stream, w.side, c->tune));
+    }
+    // phant_verify_kernel_ms reads the per-kernel events of THIS launch or nothing: a launch that took the S = 0 form (or ran
+    // the tiers next to each other) recorded none
+    if (own) c->kev_valid = c->tune.serial && c->tune.kernel_ev && c->last_shallow != 0u;
+    return PHANT_OK;
 }
 
 // Results of a call that went through the pinned staging buffer: where they wait for the stream to finish
@@ -656,89 +703,153 @@ static void deliver_staged(const StagedResults& r, uint32_t n, uint8_t* status, 
     if (value_len) std::memcpy(value_len, r.value_len, (size_t)n * 4);
 }
 
-// Stage a host witness into `io` on stream `s`, run the pipeline there and queue the copies of the results
-// back into the caller's buffers (or, staged_out given and the call small, leave them in the pinned buffer).  Does NOT wait.
-static int32_t verify_host_async(phant_ctx* c, hipStream_t s, phant::DevArena& io, phant::DevArena& dv,
-                                 const phant::FlatSide* side, bool timed, const uint8_t* roots, uint32_t n_roots,
-                                 const uint32_t* root_idx, const uint8_t* keys, uint32_t key_len, const uint8_t* nodes,
-                                 uint64_t nodes_len, const uint64_t* node_off, const uint32_t* proof_first_node,
-                                 uint32_t n, uint8_t* status, uint64_t* value_off, uint32_t* value_len,
-                                 uint32_t** d_fail_out = nullptr /* != null: the per-root verdict, left on the device */,
-                                 StagedResults* staged_out = nullptr /* != null: small batches may go through c->ws.stage; the
-                                 caller then synchronises the stream and calls deliver_staged() */) {
+// Stage a host witness `h` (arrays in host memory; h.proof_first_node == nullptr: a node set of h.total_nodes nodes) into w.io,
+// run the pipeline there and queue the copies of the results back into the caller's buffers.  Does NOT wait; after a failure
+// nothing of the call stays in flight.  d_fail_out != null: the per-root verdict, left on the device.  staged_out != null:
+// small batches on the ctx's own arena may go through c->ws.stage; the caller then synchronises the stream and calls
+// deliver_staged().
+static int32_t stage_and_verify(phant_ctx* c, const Lane& w, const phant::VerifyArgs& h, uint32_t** d_fail_out = nullptr,
+                                 StagedResults* staged_out = nullptr) {
+    const bool nodeset = !h.proof_first_node;
+    const uint32_t n = h.n, n_roots = h.n_roots;
     // The number of node offsets the caller provided is what the LAST entry of proof_first_node says
     // (include/phant_gpu.h): node_off has proof_first_node[n] + 1 entries.  An earlier entry that points
     // beyond it makes its proofs BAD_INPUT on the device; it never widens what is read from the caller.
-    const uint32_t total_nodes = proof_first_node[n];
-    const size_t need = ws_round((size_t)n_roots * 32) + ws_round((size_t)n * 4) +
-                        ws_round((size_t)n * key_len + 4) + ws_round((size_t)nodes_len + 16) +
-                        ws_round(((size_t)total_nodes + 1) * 8) + ws_round(((size_t)n + 1) * 4) +
-                        ws_round(n) + ws_round((size_t)n * 8) + ws_round((size_t)n * 4) + ws_round((size_t)n_roots * 4);
-    if (need > io.cap) HIP_TRY(c, hipStreamSynchronize(s));
-    {
-        hipError_t e = io.reset(need);
-        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(workspace)", e);
-    }
-    uint8_t* d_roots = io.take<uint8_t>((size_t)n_roots * 32);
-    uint32_t* d_ridx = io.take<uint32_t>(n);
-    uint8_t* d_keys = io.take<uint8_t>((size_t)n * key_len + 4);
-    uint8_t* d_nodes = io.take<uint8_t>((size_t)nodes_len + 16);
-    uint64_t* d_noff = io.take<uint64_t>((size_t)total_nodes + 1);
-    uint32_t* d_pfn = io.take<uint32_t>((size_t)n + 1);
-    uint8_t* d_status = io.take<uint8_t>(n);
-    uint64_t* d_voff = io.take<uint64_t>(n);
-    uint32_t* d_vlen = io.take<uint32_t>(n);
-    uint32_t* d_fail = io.take<uint32_t>(n_roots);
-    // Small batches (the witness of an ordinary block): the arena's layout mirrored in pinned memory, one copy in, one out
-    const bool staged = staged_out != nullptr && &io == &c->ws.io && need <= phant::Workspaces::STAGE_BYTES;
-    if (staged) {
-        hipError_t e = c->ws.ensure_stage();
-        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipHostMalloc(staging)", e);
-    }
-    auto put = [&](void* d_dst, const void* src, size_t bytes) -> hipError_t {
-        if (!bytes) return hipSuccess;
-        if (!staged) return hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, s);
-        uint8_t* const h = c->ws.staged(static_cast<uint8_t*>(d_dst));
-        std::memcpy(h, src, bytes);
-        // (sanitizer test builds poison the arena's padding: array by array there)
-        return PHANT_ARENA_POISONS ? hipMemcpyAsync(d_dst, h, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    const uint32_t total_nodes = nodeset ? h.total_nodes : h.proof_first_node[n];
+    uint8_t *d_roots = nullptr, *d_keys = nullptr, *d_nodes = nullptr, *d_status = nullptr;
+    uint32_t *d_ridx = nullptr, *d_pfn = nullptr, *d_vlen = nullptr, *d_fail = nullptr;
+    uint64_t *d_noff = nullptr, *d_voff = nullptr;
+    const auto lay = [&](auto& io) {
+        d_roots = io.template take<uint8_t>((size_t)n_roots * 32);
+        d_ridx = io.template take<uint32_t>(n);
+        d_keys = io.template take<uint8_t>((size_t)n * h.key_len + 4);
+        d_nodes = io.template take<uint8_t>((size_t)h.nodes_len + 16);
+        d_noff = io.template take<uint64_t>((size_t)total_nodes + 1);
+        if (!nodeset) d_pfn = io.template take<uint32_t>((size_t)n + 1);
+        d_status = io.template take<uint8_t>(n);
+        d_voff = io.template take<uint64_t>(n);
+        d_vlen = io.template take<uint32_t>(n);
+        d_fail = io.template take<uint32_t>(n_roots);
     };
-    HIP_TRY(c, put(d_roots, roots, (size_t)n_roots * 32));
-    if (root_idx) HIP_TRY(c, put(d_ridx, root_idx, (size_t)n * 4));
-    if (key_len) HIP_TRY(c, put(d_keys, keys, (size_t)n * key_len));
-    if (nodes_len) HIP_TRY(c, put(d_nodes, nodes, (size_t)nodes_len));
-    HIP_TRY(c, put(d_noff, node_off, ((size_t)total_nodes + 1) * 8));
-    HIP_TRY(c, put(d_pfn, proof_first_node, ((size_t)n + 1) * 4));
-    if (staged && !PHANT_ARENA_POISONS)  // [roots .. proof_first_node]: consecutive allocations of the arena
-        HIP_TRY(c, hipMemcpyAsync(io.base, c->ws.stage, (size_t)(reinterpret_cast<uint8_t*>(d_pfn + n + 1) - io.base), hipMemcpyHostToDevice, s));
-    phant::VerifyArgs a{d_roots, n_roots, root_idx ? d_ridx : nullptr, d_keys, key_len, d_nodes, nodes_len,
-                        d_noff, d_pfn, n, d_status, d_voff, d_vlen};
-    if (staged) {
-        // the results are written straight into the pinned buffer (hipHostMalloc memory is mapped into the device's address
-        // space and coherent): no copy back, the caller's stream synchronisation makes them visible
-        a.status = c->ws.staged(d_status);
-        a.value_off = c->ws.staged(d_voff);
-        a.value_len = c->ws.staged(d_vlen);
-    }
-    if (d_fail_out) {
-        *d_fail_out = d_fail;
-        a.fail_count = d_fail;
-    }
-    {
-        const int32_t vrc = verify_resident_on(c, a, total_nodes, s, dv, side, timed);
-        if (vrc) return vrc;
-    }
-    if (staged) {  // [status .. value_len]: consecutive as well
-        staged_out->status = a.status;
-        staged_out->value_off = reinterpret_cast<const uint8_t*>(a.value_off);
-        staged_out->value_len = reinterpret_cast<const uint8_t*>(a.value_len);
+    const int32_t rc = [&]() -> int32_t {
+        {
+            const int32_t lrc = lay_out(c, w.stream, w.io, lay);
+            if (lrc) return lrc;
+        }
+        // Small batches (the witness of an ordinary block): the arena's layout mirrored in pinned memory, one copy in, one out
+        const bool staged = staged_out != nullptr && &w.io == &c->ws.io && w.io.used <= phant::Workspaces::STAGE_BYTES;
+        if (staged) {
+            hipError_t e = c->ws.ensure_stage();
+            if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipHostMalloc(staging)", e);
+        }
+        auto put = [&](void* d_dst, const void* src, size_t bytes) -> hipError_t {
+            if (!bytes) return hipSuccess;
+            if (!staged) return hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, w.stream);
+            uint8_t* const hp = c->ws.staged(static_cast<uint8_t*>(d_dst));
+            std::memcpy(hp, src, bytes);
+            // (sanitizer test builds poison the arena's padding: array by array there)
+            return PHANT_ARENA_POISONS ? hipMemcpyAsync(d_dst, hp, bytes, hipMemcpyHostToDevice, w.stream) : hipSuccess;
+        };
+        HIP_TRY(c, put(d_roots, h.roots, (size_t)n_roots * 32));
+        if (h.root_idx) HIP_TRY(c, put(d_ridx, h.root_idx, (size_t)n * 4));
+        if (h.key_len) HIP_TRY(c, put(d_keys, h.keys, (size_t)n * h.key_len));
+        if (h.nodes_len) HIP_TRY(c, put(d_nodes, h.nodes, (size_t)h.nodes_len));
+        HIP_TRY(c, put(d_noff, h.node_off, ((size_t)total_nodes + 1) * 8));
+        if (!nodeset) HIP_TRY(c, put(d_pfn, h.proof_first_node, ((size_t)n + 1) * 4));
+        if (staged && !PHANT_ARENA_POISONS)  // [roots .. proof_first_node]: consecutive allocations of the arena
+            HIP_TRY(c, hipMemcpyAsync(w.io.base, c->ws.stage, (size_t)(reinterpret_cast<uint8_t*>(d_pfn + n + 1) - w.io.base),
+                                      hipMemcpyHostToDevice, w.stream));
+        phant::VerifyArgs a{d_roots, n_roots, h.root_idx ? d_ridx : nullptr, d_keys, h.key_len, d_nodes, h.nodes_len,
+                            d_noff, d_pfn, n, d_status, d_voff, d_vlen};
+        if (staged) {
+            // the results are written straight into the pinned buffer (hipHostMalloc memory is mapped into the device's address
+            // space and coherent): no copy back, the caller's stream synchronisation makes them visible
+            a.status = c->ws.staged(d_status);
+            a.value_off = c->ws.staged(d_voff);
+            a.value_len = c->ws.staged(d_vlen);
+        }
+        if (d_fail_out) {
+            *d_fail_out = d_fail;
+            a.fail_count = d_fail;
+        }
+        {
+            const int32_t vrc = run_verify(c, w, a, total_nodes);
+            if (vrc) return vrc;
+        }
+        if (staged) {  // [status .. value_len]: consecutive as well
+            staged_out->status = a.status;
+            staged_out->value_off = reinterpret_cast<const uint8_t*>(a.value_off);
+            staged_out->value_len = reinterpret_cast<const uint8_t*>(a.value_len);
+            return PHANT_OK;
+        }
+        HIP_TRY(c, hipMemcpyAsync(h.status, d_status, n, hipMemcpyDeviceToHost, w.stream));
+        if (h.value_off) HIP_TRY(c, hipMemcpyAsync(h.value_off, d_voff, (size_t)n * 8, hipMemcpyDeviceToHost, w.stream));
+        if (h.value_len) HIP_TRY(c, hipMemcpyAsync(h.value_len, d_vlen, (size_t)n * 4, hipMemcpyDeviceToHost, w.stream));
         return PHANT_OK;
+    }();
+    if (rc) (void)hipStreamSynchronize(w.stream);  // nothing of a failed call stays in flight
+    return rc;
+}
+
+// The argument contract of the verify entry points, both forms (nodeset: no proof_first_node).  host: the arrays are the
+// caller's, so the node blob must be there whenever nodes_len says so.  verdict: a _verdict_dev call, which owes its counts
+// even for n == 0 -- the per-proof form insists on them, the node-set form zeroes them when it has them.
+// -> PHANT_OK (run it), NOTHING_TO_DO (n == 0) or the error.
+constexpr int32_t NOTHING_TO_DO = 1;
+static int32_t check_verify_args(phant_ctx* c, const phant::VerifyArgs& a, bool nodeset, bool host, bool verdict, const char* what) {
+    auto refuse = [&]() { return fail(c, PHANT_E_INVALID_ARG, (std::string(what) + ": bad argument").c_str()); };
+    if (verdict && !nodeset && (!a.fail_count || a.n_roots == 0)) return refuse();
+    if (a.n == 0) {
+        if (verdict && a.fail_count && a.n_roots)
+            HIP_TRY(c, hipMemsetAsync(a.fail_count, 0, sizeof(uint32_t) * (size_t)a.n_roots, c->stream));
+        return NOTHING_TO_DO;
     }
-    HIP_TRY(c, hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, s));
-    if (value_off) HIP_TRY(c, hipMemcpyAsync(value_off, d_voff, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    if (value_len) HIP_TRY(c, hipMemcpyAsync(value_len, d_vlen, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (!a.roots || a.n_roots == 0 || !a.node_off || !a.status || (a.key_len && !a.keys) || a.key_len > 0x3fffffffu ||
+        (!nodeset && !a.proof_first_node) || (host && a.nodes_len && !a.nodes))
+        return refuse();
     return PHANT_OK;
 }
+
+// The device forms: on the ctx's own stream, arrays already on the device.
+static int32_t verify_dev(phant_ctx* c, const phant::VerifyArgs& a, uint32_t total_nodes, bool nodeset, bool verdict,
+                          const char* what) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    const int32_t rc = check_verify_args(c, a, nodeset, false, verdict, what);
+    if (rc != PHANT_OK) return rc == NOTHING_TO_DO ? PHANT_OK : rc;
+    return run_verify(c, ctx_lane(c, true), a, total_nodes);
+}
+
+// The host forms: staged through the ctx's own arena, waited for.
+static int32_t verify_host(phant_ctx* c, const phant::VerifyArgs& h, bool nodeset, const char* what) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    int32_t rc = check_verify_args(c, h, nodeset, true, false, what);
+    if (rc != PHANT_OK) return rc == NOTHING_TO_DO ? PHANT_OK : rc;
+    StagedResults staged;  // (the per-proof form only: pinned staging for node sets is not measured)
+    rc = stage_and_verify(c, ctx_lane(c, true), h, nullptr, nodeset ? nullptr : &staged);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    deliver_staged(staged, h.n, h.status, h.value_off, h.value_len);
+    return PHANT_OK;
+}
+
+// The streaming forms: staged and queued on the slot's own stream; phant_wait collects them.
+static int32_t verify_submit(phant_ctx* c, uint32_t slot, const phant::VerifyArgs& h, bool nodeset, const char* what) {
+    if (!c || slot >= PHANT_MAX_SLOTS) return PHANT_E_INVALID_ARG;
+    phant_ctx::Slot& sl = c->slots[slot];
+    if (sl.busy) return fail(c, PHANT_E_INVALID_ARG, (std::string(what) + ": slot still in flight (phant_wait it first)").c_str());
+    DeviceGuard g(c->device);
+    int32_t rc = check_verify_args(c, h, nodeset, true, false, what);
+    if (rc != PHANT_OK) return rc == NOTHING_TO_DO ? PHANT_OK : rc;
+    if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
+    rc = stage_and_verify(c, slot_lane(sl), h);
+    if (rc) return rc;
+    sl.busy = true;
+    return PHANT_OK;
+}
+
+constexpr bool PROOFS = false, NODESET = true;
 
 int32_t phant_mpt_verify_batch_dev(phant_ctx* c, const uint8_t* d_roots, uint32_t n_roots,
                                    const uint32_t* d_root_idx, const uint8_t* d_keys,
@@ -746,15 +857,9 @@ int32_t phant_mpt_verify_batch_dev(phant_ctx* c, const uint8_t* d_roots, uint32_
                                    const uint64_t* d_node_off, uint32_t total_nodes,
                                    const uint32_t* d_proof_first_node, uint32_t n, uint8_t* d_status,
                                    uint64_t* d_value_off, uint32_t* d_value_len) {
-    if (!c) return PHANT_E_INVALID_ARG;
-    if (n == 0) return PHANT_OK;
-    if (!d_roots || n_roots == 0 || !d_node_off || !d_proof_first_node || !d_status || (key_len && !d_keys) ||
-        key_len > 0x3fffffffu)
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_batch_dev: bad argument");
-    phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len,
-                        d_node_off, d_proof_first_node, n, d_status, d_value_off, d_value_len};
-    DeviceGuard g(c->device);
-    return verify_resident(c, a, total_nodes);
+    const phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len,
+                              d_node_off, d_proof_first_node, n, d_status, d_value_off, d_value_len};
+    return verify_dev(c, a, total_nodes, PROOFS, false, "mpt_verify_batch_dev");
 }
 
 int32_t phant_verify_bound_experiment(phant_ctx* c, const uint8_t* d_roots, uint32_t n_roots, const uint32_t* d_root_idx,
@@ -801,19 +906,9 @@ int32_t phant_mpt_verify_verdict_dev(phant_ctx* c, const uint8_t* d_roots, uint3
                                      const uint64_t* d_node_off, uint32_t total_nodes,
                                      const uint32_t* d_proof_first_node, uint32_t n, uint8_t* d_status,
                                      uint64_t* d_value_off, uint32_t* d_value_len, uint32_t* d_fail_count) {
-    if (!c) return PHANT_E_INVALID_ARG;
-    if (!d_fail_count || n_roots == 0) return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_verdict_dev: bad argument");
-    DeviceGuard g(c->device);
-    if (n == 0) {
-        HIP_TRY(c, hipMemsetAsync(d_fail_count, 0, sizeof(uint32_t) * (size_t)n_roots, c->stream));
-        return PHANT_OK;
-    }
-    if (!d_roots || !d_node_off || !d_proof_first_node || !d_status || (key_len && !d_keys) || key_len > 0x3fffffffu)
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_verdict_dev: bad argument");
-    phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len,
-                        d_node_off, d_proof_first_node, n, d_status, d_value_off, d_value_len};
-    a.fail_count = d_fail_count;
-    return verify_resident(c, a, total_nodes);
+    const phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len,
+                              d_node_off, d_proof_first_node, n, d_status, d_value_off, d_value_len, d_fail_count};
+    return verify_dev(c, a, total_nodes, PROOFS, true, "mpt_verify_verdict_dev");
 }
 
 int32_t phant_mpt_verdict_dev(phant_ctx* c, const uint8_t* d_status, const uint32_t* d_root_idx,
@@ -831,161 +926,38 @@ int32_t phant_mpt_verify_batch(phant_ctx* c, const uint8_t* roots, uint32_t n_ro
                                const uint8_t* nodes, uint64_t nodes_len, const uint64_t* node_off,
                                const uint32_t* proof_first_node, uint32_t n, uint8_t* status,
                                uint64_t* value_off, uint32_t* value_len) {
-    if (!c) return PHANT_E_INVALID_ARG;
-    if (n == 0) return PHANT_OK;
-    if (!roots || n_roots == 0 || !node_off || !proof_first_node || !status || (key_len && !keys) ||
-        (nodes_len && !nodes) || key_len > 0x3fffffffu)
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_batch: bad argument");
-    DeviceGuard g(c->device);
-    {
-        const int32_t src = ensure_side(c);
-        if (src) return src;
-    }
-    StagedResults staged;
-    const int32_t rc = verify_host_async(c, c->stream, c->ws.io, c->dv, &c->side, true, roots, n_roots, root_idx, keys,
-                                         key_len, nodes, nodes_len, node_off, proof_first_node, n, status, value_off,
-                                         value_len, nullptr, &staged);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    deliver_staged(staged, n, status, value_off, value_len);
-    return PHANT_OK;
+    const phant::VerifyArgs h{roots, n_roots, root_idx, keys, key_len, nodes, nodes_len,
+                              node_off, proof_first_node, n, status, value_off, value_len};
+    return verify_host(c, h, PROOFS, "mpt_verify_batch");
 }
 
 /* -------------------------------------------------------------- node-set witnesses */
-
-// The workspace `sp` sized for total_nodes and the epoch of the next launch on it (stream `st`).
-static int32_t nodeset_prepare(phant_ctx* c, uint32_t total_nodes, hipStream_t st, NodesetSpace& sp) {
-    if (total_nodes > sp.cap_nodes || !sp.dv.base) {
-        const uint32_t cap = phant::verify_nodeset_capacity(total_nodes);
-        HIP_TRY(c, hipStreamSynchronize(st));
-        sp.cap_nodes = 0;
-        hipError_t e = sp.dv.reset(phant::verify_nodeset_workspace_bytes(cap));
-        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(node-set workspace)", e);
-        sp.cap_nodes = cap;
-        sp.dirty = true;
-    }
-    if (sp.dirty || sp.epoch >= 0xfffffff0u) {
-        HIP_TRY(c, hipMemsetAsync(sp.dv.base, 0, sp.dv.cap, st));
-        sp.epoch = 0;
-        sp.dirty = false;
-    }
-    ++sp.epoch;
-    if (&sp == &c->ns) c->last_was_nodeset = true;
-    return PHANT_OK;
-}
-
-// Runs the node-set pipeline on device-resident arguments on stream `st` with the workspace `sp` (a.fail_count given: the verdict).
-static int32_t nodeset_resident_on(phant_ctx* c, const phant::VerifyArgs& a, uint32_t total_nodes, hipStream_t st, NodesetSpace& sp,
-                                   bool timed) {
-    {
-        const int32_t rc = nodeset_prepare(c, total_nodes, st, sp);
-        if (rc) return rc;
-    }
-    hipError_t e;
-    if (timed) {
-        TimedRegion t(c);
-        e = phant::launch_mpt_verify_nodeset(a, total_nodes, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, st, c->ns_tune);
-    } else {
-        e = phant::launch_mpt_verify_nodeset(a, total_nodes, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, st, c->ns_tune);
-    }
-    if (e != hipSuccess) {
-        sp.dirty = true;  // (whatever part of the launch ran: the next one starts from zeroed memory)
-        return fail(c, PHANT_E_DEVICE, "launch_mpt_verify_nodeset", e);
-    }
-    return PHANT_OK;
-}
-
-static bool nodeset_args_ok(const uint8_t* roots, uint32_t n_roots, const uint8_t* keys, uint32_t key_len, const uint64_t* node_off,
-                            const uint8_t* status) {
-    return roots && n_roots != 0 && node_off && status && (!key_len || keys) && key_len <= 0x3fffffffu;
-}
 
 int32_t phant_mpt_verify_nodeset_verdict_dev(phant_ctx* c, const uint8_t* d_roots, uint32_t n_roots, const uint32_t* d_root_idx,
                                              const uint8_t* d_keys, uint32_t key_len, const uint8_t* d_nodes, uint64_t nodes_len,
                                              const uint64_t* d_node_off, uint32_t total_nodes, uint32_t n, uint8_t* d_status,
                                              uint64_t* d_value_off, uint32_t* d_value_len, uint32_t* d_fail_count) {
-    if (!c) return PHANT_E_INVALID_ARG;
-    DeviceGuard g(c->device);
-    if (n == 0) {
-        if (d_fail_count && n_roots) HIP_TRY(c, hipMemsetAsync(d_fail_count, 0, sizeof(uint32_t) * (size_t)n_roots, c->stream));
-        return PHANT_OK;
-    }
-    if (!nodeset_args_ok(d_roots, n_roots, d_keys, key_len, d_node_off, d_status))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_nodeset_dev: bad argument");
-    phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len, d_node_off, nullptr, n,
-                        d_status, d_value_off, d_value_len};
-    a.fail_count = d_fail_count;
-    return nodeset_resident_on(c, a, total_nodes, c->stream, c->ns, true);
+    const phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len, d_node_off, nullptr, n,
+                              d_status, d_value_off, d_value_len, d_fail_count};
+    return verify_dev(c, a, total_nodes, NODESET, true, "mpt_verify_nodeset_verdict_dev");
 }
 
 int32_t phant_mpt_verify_nodeset_dev(phant_ctx* c, const uint8_t* d_roots, uint32_t n_roots, const uint32_t* d_root_idx,
                                      const uint8_t* d_keys, uint32_t key_len, const uint8_t* d_nodes, uint64_t nodes_len,
                                      const uint64_t* d_node_off, uint32_t total_nodes, uint32_t n, uint8_t* d_status,
                                      uint64_t* d_value_off, uint32_t* d_value_len) {
-    return phant_impl::phant_mpt_verify_nodeset_verdict_dev(c, d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len,
-                                                            d_node_off, total_nodes, n, d_status, d_value_off, d_value_len, nullptr);
-}
-
-// Stage a host node set into `io` on stream `s`, run the pipeline there with the workspace `sp` and queue the copies of the results
-// back into the caller's buffers.  Does NOT wait.  d_fail_out (may be null): where the per-root verdict is left on the device.
-static int32_t nodeset_host_async(phant_ctx* c, hipStream_t s, phant::DevArena& io, NodesetSpace& sp, bool timed, const uint8_t* roots,
-                                  uint32_t n_roots, const uint32_t* root_idx, const uint8_t* keys, uint32_t key_len,
-                                  const uint8_t* nodes, uint64_t nodes_len, const uint64_t* node_off, uint32_t total_nodes, uint32_t n,
-                                  uint8_t* status, uint64_t* value_off, uint32_t* value_len, uint32_t** d_fail_out) {
-    const size_t need = ws_round((size_t)n_roots * 32) + ws_round((size_t)n * 4) + ws_round((size_t)n * key_len + 4) +
-                        ws_round((size_t)nodes_len + 16) + ws_round(((size_t)total_nodes + 1) * 8) + ws_round(n) +
-                        ws_round((size_t)n * 8) + ws_round((size_t)n * 4) + ws_round((size_t)n_roots * 4);
-    if (need > io.cap) HIP_TRY(c, hipStreamSynchronize(s));
-    {
-        hipError_t e = io.reset(need);
-        if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(workspace)", e);
-    }
-    uint8_t* d_roots = io.take<uint8_t>((size_t)n_roots * 32);
-    uint32_t* d_ridx = io.take<uint32_t>(n);
-    uint8_t* d_keys = io.take<uint8_t>((size_t)n * key_len + 4);
-    uint8_t* d_nodes = io.take<uint8_t>((size_t)nodes_len + 16);
-    uint64_t* d_noff = io.take<uint64_t>((size_t)total_nodes + 1);
-    uint8_t* d_status = io.take<uint8_t>(n);
-    uint64_t* d_voff = io.take<uint64_t>(n);
-    uint32_t* d_vlen = io.take<uint32_t>(n);
-    uint32_t* d_fail = io.take<uint32_t>(n_roots);
-    if (io.overflowed) return fail(c, PHANT_E_DEVICE, "node-set staging arena undersized");
-    HIP_TRY(c, hipMemcpyAsync(d_roots, roots, (size_t)n_roots * 32, hipMemcpyHostToDevice, s));
-    if (root_idx) HIP_TRY(c, hipMemcpyAsync(d_ridx, root_idx, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (key_len) HIP_TRY(c, hipMemcpyAsync(d_keys, keys, (size_t)n * key_len, hipMemcpyHostToDevice, s));
-    if (nodes_len) HIP_TRY(c, hipMemcpyAsync(d_nodes, nodes, (size_t)nodes_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_noff, node_off, ((size_t)total_nodes + 1) * 8, hipMemcpyHostToDevice, s));
-    phant::VerifyArgs a{d_roots, n_roots, root_idx ? d_ridx : nullptr, d_keys, key_len, d_nodes, nodes_len, d_noff, nullptr, n,
-                        d_status, d_voff, d_vlen};
-    if (d_fail_out) {
-        a.fail_count = d_fail;
-        *d_fail_out = d_fail;
-    }
-    const int32_t rc = nodeset_resident_on(c, a, total_nodes, s, sp, timed);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, s));
-    if (value_off) HIP_TRY(c, hipMemcpyAsync(value_off, d_voff, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    if (value_len) HIP_TRY(c, hipMemcpyAsync(value_len, d_vlen, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    return PHANT_OK;
+    const phant::VerifyArgs a{d_roots, n_roots, d_root_idx, d_keys, key_len, d_nodes, nodes_len, d_node_off, nullptr, n,
+                              d_status, d_value_off, d_value_len};
+    return verify_dev(c, a, total_nodes, NODESET, false, "mpt_verify_nodeset_dev");
 }
 
 int32_t phant_mpt_verify_nodeset(phant_ctx* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
                                  const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
                                  const uint64_t* node_off, uint32_t total_nodes, uint32_t n, uint8_t* status,
                                  uint64_t* value_off, uint32_t* value_len) {
-    if (!c) return PHANT_E_INVALID_ARG;
-    if (n == 0) return PHANT_OK;
-    if (!nodeset_args_ok(roots, n_roots, keys, key_len, node_off, status) || (nodes_len && !nodes))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_nodeset: null pointer");
-    DeviceGuard g(c->device);
-    const int32_t rc = nodeset_host_async(c, c->stream, c->ws.io, c->ns, true, roots, n_roots, root_idx, keys, key_len, nodes, nodes_len,
-                                          node_off, total_nodes, n, status, value_off, value_len, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PHANT_OK;
+    phant::VerifyArgs h{roots, n_roots, root_idx, keys, key_len, nodes, nodes_len, node_off, nullptr, n, status, value_off, value_len};
+    h.total_nodes = total_nodes;
+    return verify_host(c, h, NODESET, "mpt_verify_nodeset");
 }
 
 /* ------------------------------------------------------------------ streaming */
@@ -1012,46 +984,18 @@ int32_t phant_mpt_verify_submit(phant_ctx* c, uint32_t slot, const uint8_t* root
                                 const uint8_t* nodes, uint64_t nodes_len, const uint64_t* node_off,
                                 const uint32_t* proof_first_node, uint32_t n, uint8_t* status,
                                 uint64_t* value_off, uint32_t* value_len) {
-    if (!c || slot >= PHANT_MAX_SLOTS) return PHANT_E_INVALID_ARG;
-    phant_ctx::Slot& sl = c->slots[slot];
-    if (sl.busy) return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_submit: slot still in flight (phant_wait it first)");
-    if (n == 0) return PHANT_OK;
-    if (!roots || n_roots == 0 || !node_off || !proof_first_node || !status || (key_len && !keys) ||
-        (nodes_len && !nodes) || key_len > 0x3fffffffu)
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_submit: bad argument");
-    DeviceGuard g(c->device);
-    if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    const int32_t rc = verify_host_async(c, sl.stream, sl.io, sl.dv, nullptr, false, roots, n_roots, root_idx, keys,
-                                         key_len, nodes, nodes_len, node_off, proof_first_node, n, status, value_off,
-                                         value_len);
-    if (rc) {
-        (void)hipStreamSynchronize(sl.stream);  // nothing of a failed submission stays in flight
-        return rc;
-    }
-    sl.busy = true;
-    return PHANT_OK;
+    const phant::VerifyArgs h{roots, n_roots, root_idx, keys, key_len, nodes, nodes_len,
+                              node_off, proof_first_node, n, status, value_off, value_len};
+    return verify_submit(c, slot, h, PROOFS, "mpt_verify_submit");
 }
 
 int32_t phant_mpt_verify_nodeset_submit(phant_ctx* c, uint32_t slot, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
                                         const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
                                         const uint64_t* node_off, uint32_t total_nodes, uint32_t n, uint8_t* status,
                                         uint64_t* value_off, uint32_t* value_len) {
-    if (!c || slot >= PHANT_MAX_SLOTS) return PHANT_E_INVALID_ARG;
-    phant_ctx::Slot& sl = c->slots[slot];
-    if (sl.busy) return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_nodeset_submit: slot still in flight (phant_wait it first)");
-    if (n == 0) return PHANT_OK;
-    if (!nodeset_args_ok(roots, n_roots, keys, key_len, node_off, status) || (nodes_len && !nodes))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_verify_nodeset_submit: bad argument");
-    DeviceGuard g(c->device);
-    if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    const int32_t rc = nodeset_host_async(c, sl.stream, sl.io, sl.ns, false, roots, n_roots, root_idx, keys, key_len, nodes, nodes_len,
-                                          node_off, total_nodes, n, status, value_off, value_len, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(sl.stream);  // nothing of a failed submission stays in flight
-        return rc;
-    }
-    sl.busy = true;
-    return PHANT_OK;
+    phant::VerifyArgs h{roots, n_roots, root_idx, keys, key_len, nodes, nodes_len, node_off, nullptr, n, status, value_off, value_len};
+    h.total_nodes = total_nodes;
+    return verify_submit(c, slot, h, NODESET, "mpt_verify_nodeset_submit");
 }
 
 int32_t phant_wait(phant_ctx* c, uint32_t slot) {
@@ -1069,35 +1013,17 @@ int32_t phant_wait(phant_ctx* c, uint32_t slot) {
 /* ------------------------------------------------- internal: what comm.hip (several devices in one process) builds on */
 namespace phant {
 
-// Stage a host witness on the ctx's own stream, verify it there (helper stream included) with the per-root verdict left
-// in a device array of the ctx, queue the copies of statuses / values back to the caller's buffers.  Does NOT wait.
-int32_t ctx_verify_host_async_verdict(phant_ctx* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
-                                      const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
-                                      const uint64_t* node_off, const uint32_t* proof_first_node, uint32_t n,
-                                      uint8_t* status, uint64_t* value_off, uint32_t* value_len, uint32_t** d_fail) {
+// Stage a host witness of either form (stage_and_verify) on the ctx's own stream, verify it there with the per-root verdict
+// left in a device array of the ctx, queue the copies of statuses / values back to the caller's buffers.  Does NOT wait.
+int32_t ctx_stage_and_verify(phant_ctx* c, const VerifyArgs& h, uint32_t** d_fail) {
     DeviceGuard g(c->device);
-    {
-        const int32_t src = phant_impl::ensure_side(c);
-        if (src) return src;
-    }
-    return phant_impl::verify_host_async(c, c->stream, c->ws.io, c->dv, &c->side, false, roots, n_roots, root_idx, keys, key_len, nodes,
-                             nodes_len, node_off, proof_first_node, n, status, value_off, value_len, d_fail);
-}
-// the same for a node-set witness
-int32_t ctx_nodeset_host_async_verdict(phant_ctx* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
-                                       const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
-                                       const uint64_t* node_off, uint32_t total_nodes, uint32_t n, uint8_t* status,
-                                       uint64_t* value_off, uint32_t* value_len, uint32_t** d_fail) {
-    DeviceGuard g(c->device);
-    return phant_impl::nodeset_host_async(c, c->stream, c->ws.io, c->ns, false, roots, n_roots, root_idx, keys, key_len, nodes,
-                                          nodes_len, node_off, total_nodes, n, status, value_off, value_len, d_fail);
+    return phant_impl::stage_and_verify(c, phant_impl::ctx_lane(c, false), h, d_fail);
 }
 // a device array of n_roots zeroed counters owned by the ctx (a rank without proofs still takes part in the reduction)
 int32_t ctx_zero_verdict(phant_ctx* c, uint32_t n_roots, uint32_t** d_fail) {
     DeviceGuard g(c->device);
-    const int32_t rc = ws_reset(c, ws_round((size_t)n_roots * 4));
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) { *d_fail = io.template take<uint32_t>(n_roots); });
     if (rc) return rc;
-    *d_fail = ws_take<uint32_t>(c, n_roots);
     HIP_TRY(c, hipMemsetAsync(*d_fail, 0, (size_t)n_roots * 4, c->stream));
     return PHANT_OK;
 }
@@ -1200,26 +1126,29 @@ int32_t phant_witness_verify(phant_ctx* c, const phant_witness* pw, const uint8_
     if (deferred && total_nodes && !w.json) return fail(c, PHANT_E_INVALID_ARG, "witness_verify: index-form witness without its JSON text");
     DeviceGuard g(c->device);
     hipStream_t s = c->stream;
-    const size_t need = ws_round(pre_len + 16) + ws_round(((size_t)n + 1) * 8) + ws_round((size_t)n * 32) +
-                        ws_round((size_t)n_roots * 32) + ws_round((size_t)n * 4) + ws_round(nodes_len + 16) +
-                        ws_round(((size_t)total_nodes + 1) * 8) + ws_round(((size_t)n + 1) * 4) + ws_round(n) +
-                        ws_round((size_t)n * 8) + ws_round((size_t)n * 4) +
-                        (deferred ? ws_round(w.json_len + 16) + ws_round((size_t)total_nodes * 8 + 8) + ws_round(16) +
-                                        ws_round((size_t)n * VAL_CAP)
-                                  : 0);
-    int32_t rc = ws_reset(c, need);
+    uint8_t *d_pre, *d_keys, *d_roots, *d_nodes, *d_status, *d_json = nullptr, *d_vals = nullptr;
+    uint64_t *d_poff, *d_noff, *d_voff, *d_src = nullptr;
+    uint32_t *d_ridx, *d_pfn, *d_vlen, *d_err = nullptr;
+    int32_t rc = lay_out(c, s, c->ws.io, [&](auto& io) {
+        d_pre = io.template take<uint8_t>(pre_len + 16);
+        d_poff = io.template take<uint64_t>((size_t)n + 1);
+        d_keys = io.template take<uint8_t>((size_t)n * 32);
+        d_roots = io.template take<uint8_t>((size_t)n_roots * 32);
+        d_ridx = io.template take<uint32_t>(n);
+        d_nodes = io.template take<uint8_t>(nodes_len + 16);
+        d_noff = io.template take<uint64_t>((size_t)total_nodes + 1);
+        d_pfn = io.template take<uint32_t>((size_t)n + 1);
+        d_status = io.template take<uint8_t>(n);
+        d_voff = io.template take<uint64_t>(n);
+        d_vlen = io.template take<uint32_t>(n);
+        if (deferred) {
+            d_json = io.template take<uint8_t>(w.json_len + 16);
+            d_src = io.template take<uint64_t>((size_t)total_nodes + 1);
+            d_err = io.template take<uint32_t>(4);
+            d_vals = io.template take<uint8_t>((size_t)n * VAL_CAP);
+        }
+    });
     if (rc) return rc;
-    uint8_t* d_pre = ws_take<uint8_t>(c, pre_len + 16);
-    uint64_t* d_poff = ws_take<uint64_t>(c, (size_t)n + 1);
-    uint8_t* d_keys = ws_take<uint8_t>(c, (size_t)n * 32);
-    uint8_t* d_roots = ws_take<uint8_t>(c, (size_t)n_roots * 32);
-    uint32_t* d_ridx = ws_take<uint32_t>(c, n);
-    uint8_t* d_nodes = ws_take<uint8_t>(c, nodes_len + 16);
-    uint64_t* d_noff = ws_take<uint64_t>(c, (size_t)total_nodes + 1);
-    uint32_t* d_pfn = ws_take<uint32_t>(c, (size_t)n + 1);
-    uint8_t* d_status = ws_take<uint8_t>(c, n);
-    uint64_t* d_voff = ws_take<uint64_t>(c, n);
-    uint32_t* d_vlen = ws_take<uint32_t>(c, n);
     std::vector<uint64_t> poff64(w.preimage_off.begin(), w.preimage_off.end());
     HIP_TRY(c, hipMemcpyAsync(d_pre, w.preimages.data(), pre_len, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_poff, poff64.data(), poff64.size() * 8, hipMemcpyHostToDevice, s));
@@ -1229,32 +1158,19 @@ int32_t phant_witness_verify(phant_ctx* c, const phant_witness* pw, const uint8_
     HIP_TRY(c, hipMemcpyAsync(d_ridx, w.root_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_noff, w.node_off.data(), ((size_t)total_nodes + 1) * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_pfn, w.proof_first_node.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
-    uint32_t* d_err = nullptr;
-    uint8_t* d_vals = nullptr;
     if (!deferred) {
         if (nodes_len) HIP_TRY(c, hipMemcpyAsync(d_nodes, w.nodes.data(), nodes_len, hipMemcpyHostToDevice, s));
     } else {
-        uint8_t* d_json = ws_take<uint8_t>(c, w.json_len + 16);
-        uint64_t* d_src = ws_take<uint64_t>(c, (size_t)total_nodes + 1);
-        d_err = ws_take<uint32_t>(c, 4);
-        d_vals = ws_take<uint8_t>(c, (size_t)n * VAL_CAP);
         HIP_TRY(c, hipMemcpyAsync(d_json, w.json, w.json_len, hipMemcpyHostToDevice, s));
         if (total_nodes) HIP_TRY(c, hipMemcpyAsync(d_src, w.node_src.data(), (size_t)total_nodes * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(c, phant::launch_hex_decode(d_json, d_src, d_noff, total_nodes, d_nodes, d_err, s));
     }
     // secure-trie keys: keccak256(address) / keccak256(slot), one batched launch
     HIP_TRY(c, phant::launch_keccak256_var(d_pre, d_poff, n, d_keys, s));
-    phant::VerifyArgs a{d_roots, n_roots, d_ridx, d_keys, 32, d_nodes, nodes_len, d_noff, d_pfn, n, d_status, d_voff, d_vlen};
-    {
-        const int32_t src = ensure_side(c);
-        if (src) return src;
-    }
-    if (w.node_set) {  // the document's "state" array: every node once, references resolved by hash
-        a.proof_first_node = nullptr;
-        rc = nodeset_resident_on(c, a, total_nodes, s, c->ns, true);
-    } else {
-        rc = verify_resident_on(c, a, total_nodes, s, c->dv, &c->side, true);
-    }
+    // the document's "state" array (w.node_set): every node once, references resolved by hash
+    phant::VerifyArgs a{d_roots, n_roots, d_ridx, d_keys, 32, d_nodes, nodes_len, d_noff, w.node_set ? nullptr : d_pfn, n,
+                        d_status, d_voff, d_vlen};
+    rc = run_verify(c, ctx_lane(c, true), a, total_nodes);
     if (rc) return rc;
     std::vector<uint64_t> voff(n);
     std::vector<uint32_t> vlen(n);
@@ -1393,41 +1309,39 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
     DeviceGuard g(c->device);
     hipStream_t s = c->stream;
     const size_t nk = (size_t)na + ns;
-    const size_t need = ws_round(pre_len + 16) + ws_round((nk + 1) * 8) + ws_round(nk * 32) + ws_round(32) + ws_round((size_t)na * 32) +
-                        ws_round((size_t)ns * 4) + ws_round(nodes_len + 16) + ws_round(((size_t)total_nodes + 1) * 8) +
-                        ws_round(code_bytes + 16) + ws_round(((size_t)nc + 1) * 8) + ws_round(na) + ws_round((size_t)na * 8) +
-                        ws_round((size_t)na * 4) + ws_round(ns) + ws_round((size_t)ns * 8) + ws_round((size_t)ns * 4) +
-                        ws_round((size_t)na * 8) + ws_round((size_t)na * 32) * 2 + ws_round((size_t)na * 4) + ws_round((size_t)ns * 32) +
-                        ws_round((size_t)nc * 32) + ws_round((size_t)nc * 4) + ws_round((size_t)slots_t * 4) * 2 + ws_round(16);
-    int32_t rc = ws_reset(c, need);
-    if (rc) return rc;
-    uint8_t* d_pre = ws_take<uint8_t>(c, pre_len + 16);
-    uint64_t* d_poff = ws_take<uint64_t>(c, nk + 1);
-    uint8_t* d_keys = ws_take<uint8_t>(c, nk * 32);
-    uint8_t* d_root = ws_take<uint8_t>(c, 32);
+    uint8_t *d_pre, *d_keys, *d_root, *d_nodes, *d_codes;
+    uint64_t *d_poff, *d_noff, *d_coff, *d_avoff, *d_svoff;
+    uint32_t *d_sacc, *d_avlen, *d_svlen;
     phant::PrestateArgs p{};
-    p.storage_roots = ws_take<uint8_t>(c, (size_t)na * 32);
-    uint32_t* d_sacc = ws_take<uint32_t>(c, ns);
-    uint8_t* d_nodes = ws_take<uint8_t>(c, nodes_len + 16);
-    uint64_t* d_noff = ws_take<uint64_t>(c, (size_t)total_nodes + 1);
-    uint8_t* d_codes = ws_take<uint8_t>(c, code_bytes + 16);
-    uint64_t* d_coff = ws_take<uint64_t>(c, (size_t)nc + 1);
-    p.acc_status = ws_take<uint8_t>(c, na);
-    uint64_t* d_avoff = ws_take<uint64_t>(c, na);
-    uint32_t* d_avlen = ws_take<uint32_t>(c, na);
-    p.slot_status = ws_take<uint8_t>(c, ns);
-    uint64_t* d_svoff = ws_take<uint64_t>(c, ns);
-    uint32_t* d_svlen = ws_take<uint32_t>(c, ns);
-    p.nonces = ws_take<uint64_t>(c, na);
-    p.balances = ws_take<uint8_t>(c, (size_t)na * 32);
-    p.code_hashes = ws_take<uint8_t>(c, (size_t)na * 32);
-    p.code_index = ws_take<uint32_t>(c, na);
-    p.slot_vals = ws_take<uint8_t>(c, (size_t)ns * 32);
-    p.code_dig = ws_take<uint32_t>(c, (size_t)nc * 8);
-    p.code_slot = ws_take<uint32_t>(c, nc);
-    p.table = ws_take<uint32_t>(c, slots_t);
-    p.table_used = ws_take<uint32_t>(c, slots_t);
-    p.counters = ws_take<uint32_t>(c, 4);
+    int32_t rc = lay_out(c, s, c->ws.io, [&](auto& io) {
+        d_pre = io.template take<uint8_t>(pre_len + 16);
+        d_poff = io.template take<uint64_t>(nk + 1);
+        d_keys = io.template take<uint8_t>(nk * 32);
+        d_root = io.template take<uint8_t>(32);
+        p.storage_roots = io.template take<uint8_t>((size_t)na * 32);
+        d_sacc = io.template take<uint32_t>(ns);
+        d_nodes = io.template take<uint8_t>(nodes_len + 16);
+        d_noff = io.template take<uint64_t>((size_t)total_nodes + 1);
+        d_codes = io.template take<uint8_t>(code_bytes + 16);
+        d_coff = io.template take<uint64_t>((size_t)nc + 1);
+        p.acc_status = io.template take<uint8_t>(na);
+        d_avoff = io.template take<uint64_t>(na);
+        d_avlen = io.template take<uint32_t>(na);
+        p.slot_status = io.template take<uint8_t>(ns);
+        d_svoff = io.template take<uint64_t>(ns);
+        d_svlen = io.template take<uint32_t>(ns);
+        p.nonces = io.template take<uint64_t>(na);
+        p.balances = io.template take<uint8_t>((size_t)na * 32);
+        p.code_hashes = io.template take<uint8_t>((size_t)na * 32);
+        p.code_index = io.template take<uint32_t>(na);
+        p.slot_vals = io.template take<uint8_t>((size_t)ns * 32);
+        p.code_dig = io.template take<uint32_t>((size_t)nc * 8);
+        p.code_slot = io.template take<uint32_t>(nc);
+        p.table = io.template take<uint32_t>(slots_t);
+        p.table_used = io.template take<uint32_t>(slots_t);
+        p.counters = io.template take<uint32_t>(4);
+    });
+    if (rc) return rc;
     p.nodes = d_nodes;
     p.na = na;
     p.ns = ns;
@@ -1442,7 +1356,6 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
     p.mask = slots_t - 1u;
     p.salt0 = c->ns_salt[0];
     p.salt1 = c->ns_salt[1];
-    if (c->ws.io.overflowed) return fail(c, PHANT_E_DEVICE, "exec_witness_prestate: staging arena undersized");
     rc = ensure_code_side(c);
     if (rc) return rc;
     if (na) {  // (the node-set workspace sized and its epoch taken before anything is queued: sizing it may wait for the stream)

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/phant_gpu.h"
+#include "launch.h"
 
 // RCCL's names and entry points (resolved at run time) and one host thread per device: comm_host.h (the CPU test suite's
 // phant_platform.h names a stand-in: an in-process sum, devices one after the other).
@@ -32,14 +33,7 @@
 
 struct phant_ctx;
 namespace phant {
-int32_t ctx_verify_host_async_verdict(phant_ctx* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
-                                      const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
-                                      const uint64_t* node_off, const uint32_t* proof_first_node, uint32_t n,
-                                      uint8_t* status, uint64_t* value_off, uint32_t* value_len, uint32_t** d_fail);
-int32_t ctx_nodeset_host_async_verdict(phant_ctx* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
-                                       const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
-                                       const uint64_t* node_off, uint32_t total_nodes, uint32_t n, uint8_t* status,
-                                       uint64_t* value_off, uint32_t* value_len, uint32_t** d_fail);
+int32_t ctx_stage_and_verify(phant_ctx* c, const VerifyArgs& h, uint32_t** d_fail);
 int32_t ctx_zero_verdict(phant_ctx* c, uint32_t n_roots, uint32_t** d_fail);
 hipStream_t ctx_stream(phant_ctx* c);
 int ctx_device(const phant_ctx* c);
@@ -352,41 +346,23 @@ int32_t phant_comm_allreduce_verdict(phant_comm* c, uint32_t* const* d_fail_coun
     return all_reduce_u32(c, bufs, n_roots);
 }
 
-int32_t phant_mpt_verify_sharded(phant_comm* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
-                                 const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
-                                 const uint64_t* node_off, const uint32_t* proof_first_node, uint32_t n, uint8_t* status,
-                                 uint64_t* value_off, uint32_t* value_len, uint32_t* fail_count) {
-    if (!c) return PHANT_E_INVALID_ARG;
-    if (fail_count)
-        for (uint32_t r = 0; r < n_roots; ++r) fail_count[r] = 0;
-    if (n == 0) return PHANT_OK;
-    if (!roots || n_roots == 0 || !node_off || !proof_first_node || !status || (key_len && !keys) ||
-        (nodes_len && !nodes) || key_len > 0x3fffffffu)
-        return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: bad argument");
-    const uint32_t W = (uint32_t)c->ctx.size();
-    const uint32_t total_nodes = proof_first_node[n];  // node_off has proof_first_node[n] + 1 entries (as in the batch form)
-    // This form reads the index arrays on the HOST (it re-packs the witness per device), so unlike the single-device
-    // forms -- where a bad entry costs its proof a BAD_INPUT on the device -- it insists on consistent ones.
-    for (uint32_t i = 0; i < n; ++i)
-        if (proof_first_node[i + 1] < proof_first_node[i] || proof_first_node[i + 1] > total_nodes)
-            return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: proof_first_node is not monotone");
-    for (uint32_t j = 0; j < total_nodes; ++j)
-        if (node_off[j + 1] < node_off[j] || node_off[j + 1] > nodes_len || node_off[j + 1] - node_off[j] > 0x7fffffffull)
-            return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: node_off is inconsistent");
-    if (root_idx)
-        for (uint32_t i = 0; i < n; ++i)
-            if (root_idx[i] >= n_roots) return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: root_idx out of range");
-
-    // ---- deal the proofs out ----
+// The sharded verify forms past their own checks (h: the caller's arguments; nodeset: h has no proof_first_node).  The proofs are
+// dealt out by phant_comm_owner; every device, on a host thread of its own, gathers its shard's keys and root indices, lets
+// `pack(s)` gather its nodes (the form's part: s.nodes, s.node_off and, per proof, s.pfn) and stages and verifies it
+// (asynchronous).  Then the one exchange, the verdict copy-back, the syncs and the results back into the caller's order, value
+// offsets through `value_at(s, k, i)`: where the value of proof i (the k-th of shard s, PRESENT) lies in the caller's node blob.
+template <class Pack, class ValueAt>
+int32_t verify_sharded(phant_comm* c, const char* what, const phant::VerifyArgs& h, bool nodeset, uint32_t* fail_count,
+                       const Pack& pack, const ValueAt& value_at) {
+    const uint32_t W = (uint32_t)c->ctx.size(), n = h.n, n_roots = h.n_roots, key_len = h.key_len;
     for (Shard& s : c->shards) {
         s.proofs.clear();
         s.d_fail = nullptr;
         s.rc = PHANT_OK;
     }
     for (uint32_t i = 0; i < n; ++i)
-        c->shards[phant_impl::phant_comm_owner(c, keys ? keys + (size_t)key_len * i : nullptr, key_len)].proofs.push_back(i);
+        c->shards[phant_impl::phant_comm_owner(c, h.keys ? h.keys + (size_t)key_len * i : nullptr, key_len)].proofs.push_back(i);
 
-    // ---- per device, on a host thread of its own: gather the shard, stage it, verify (asynchronous) ----
     auto work = [&](uint32_t r) {
         Shard& s = c->shards[r];
         const uint32_t m = (uint32_t)s.proofs.size();
@@ -395,36 +371,27 @@ int32_t phant_mpt_verify_sharded(phant_comm* c, const uint8_t* roots, uint32_t n
             return;
         }
         s.keys.resize((size_t)m * key_len);
-        s.root_idx.resize(root_idx ? m : 0);
-        s.pfn.assign((size_t)m + 1, 0);
-        s.node_off.clear();
-        s.nodes.clear();
+        s.root_idx.resize(h.root_idx ? m : 0);
         s.status.assign(m, 0);
         s.value_off.assign(m, 0);
         s.value_len.assign(m, 0);
-        s.node_off.push_back(0);
         for (uint32_t k = 0; k < m; ++k) {
             const uint32_t i = s.proofs[k];
-            if (key_len) std::memcpy(s.keys.data() + (size_t)k * key_len, keys + (size_t)i * key_len, key_len);
-            if (root_idx) s.root_idx[k] = root_idx[i];
-            const uint32_t f = proof_first_node[i], l = proof_first_node[i + 1];
-            s.pfn[k] = (uint32_t)(s.node_off.size() - 1);
-            for (uint32_t j = f; j < l; ++j) {
-                const uint64_t b = node_off[j], e = node_off[j + 1];
-                s.nodes.insert(s.nodes.end(), nodes + b, nodes + e);
-                s.node_off.push_back(s.nodes.size());
-            }
-            s.pfn[k + 1] = (uint32_t)(s.node_off.size() - 1);
+            if (key_len) std::memcpy(s.keys.data() + (size_t)k * key_len, h.keys + (size_t)i * key_len, key_len);
+            if (h.root_idx) s.root_idx[k] = h.root_idx[i];
         }
-        s.rc = phant::ctx_verify_host_async_verdict(
-            c->ctx[r], roots, n_roots, root_idx ? s.root_idx.data() : nullptr, s.keys.data(), key_len, s.nodes.data(),
-            s.nodes.size(), s.node_off.data(), s.pfn.data(), m, s.status.data(), s.value_off.data(), s.value_len.data(), &s.d_fail);
+        pack(s);
+        phant::VerifyArgs sh{h.roots, n_roots, h.root_idx ? s.root_idx.data() : nullptr, s.keys.data(), key_len, s.nodes.data(),
+                             s.nodes.size(), s.node_off.data(), nodeset ? nullptr : s.pfn.data(), m, s.status.data(),
+                             s.value_off.data(), s.value_len.data()};
+        sh.total_nodes = (uint32_t)(s.node_off.size() - 1);
+        s.rc = phant::ctx_stage_and_verify(c->ctx[r], sh, &s.d_fail);
     };
     for_each_device(W, work);
     for (uint32_t r = 0; r < W; ++r)
         if (c->shards[r].rc != PHANT_OK) {
             for (phant_ctx* x : c->ctx) (void)phant_stream_sync(x);  // nothing of a failed call stays in flight
-            return cfail(c, c->shards[r].rc, std::string("mpt_verify_sharded: device ") + std::to_string(c->devices[r]) + ": " +
+            return cfail(c, c->shards[r].rc, std::string(what) + ": device " + std::to_string(c->devices[r]) + ": " +
                                                  phant_last_error(c->ctx[r]));
         }
 
@@ -438,11 +405,11 @@ int32_t phant_mpt_verify_sharded(phant_comm* c, const uint8_t* roots, uint32_t n
         hipError_t e = hipSetDevice(c->devices[0]);
         if (e == hipSuccess) e = hipMemcpyAsync(fail_count, bufs[0], (size_t)n_roots * 4, hipMemcpyDeviceToHost, phant::ctx_stream(c->ctx[0]));
         if (prev >= 0) (void)hipSetDevice(prev);
-        if (e != hipSuccess) rc = cfail(c, PHANT_E_DEVICE, "mpt_verify_sharded: copying the verdict back");
+        if (e != hipSuccess) rc = cfail(c, PHANT_E_DEVICE, std::string(what) + ": copying the verdict back");
     }
     for (phant_ctx* x : c->ctx) {
         const int32_t src = phant_stream_sync(x);
-        if (rc == PHANT_OK && src != PHANT_OK) rc = cfail(c, src, std::string("mpt_verify_sharded: ") + phant_last_error(x));
+        if (rc == PHANT_OK && src != PHANT_OK) rc = cfail(c, src, std::string(what) + ": " + phant_last_error(x));
     }
     if (rc != PHANT_OK) return rc;
 
@@ -451,23 +418,67 @@ int32_t phant_mpt_verify_sharded(phant_comm* c, const uint8_t* roots, uint32_t n
         const Shard& s = c->shards[r];
         for (uint32_t k = 0; k < (uint32_t)s.proofs.size(); ++k) {
             const uint32_t i = s.proofs[k];
-            status[i] = s.status[k];
-            if (value_len) value_len[i] = s.value_len[k];
-            if (value_off) {
-                uint64_t vo = 0;
-                if (s.status[k] == PHANT_PROOF_PRESENT) {
-                    // the value lies in this proof's last node: shard offset - shard node start + caller's node start
-                    const uint32_t f = proof_first_node[i], l = proof_first_node[i + 1];
-                    const uint32_t sf = s.pfn[k];
-                    uint32_t j = 0;
-                    while (j + 1 < l - f && s.node_off[sf + j + 1] <= s.value_off[k]) ++j;
-                    vo = s.value_off[k] - s.node_off[sf + j] + node_off[f + j];
-                }
-                value_off[i] = vo;
-            }
+            h.status[i] = s.status[k];
+            if (h.value_len) h.value_len[i] = s.value_len[k];
+            if (h.value_off) h.value_off[i] = s.status[k] == PHANT_PROOF_PRESENT ? value_at(s, k, i) : 0;
         }
     }
     return PHANT_OK;
+}
+
+int32_t phant_mpt_verify_sharded(phant_comm* c, const uint8_t* roots, uint32_t n_roots, const uint32_t* root_idx,
+                                 const uint8_t* keys, uint32_t key_len, const uint8_t* nodes, uint64_t nodes_len,
+                                 const uint64_t* node_off, const uint32_t* proof_first_node, uint32_t n, uint8_t* status,
+                                 uint64_t* value_off, uint32_t* value_len, uint32_t* fail_count) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (fail_count)
+        for (uint32_t r = 0; r < n_roots; ++r) fail_count[r] = 0;
+    if (n == 0) return PHANT_OK;
+    if (!roots || n_roots == 0 || !node_off || !proof_first_node || !status || (key_len && !keys) ||
+        (nodes_len && !nodes) || key_len > 0x3fffffffu)
+        return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: bad argument");
+    const uint32_t total_nodes = proof_first_node[n];  // node_off has proof_first_node[n] + 1 entries (as in the batch form)
+    // This form reads the index arrays on the HOST (it re-packs the witness per device), so unlike the single-device
+    // forms -- where a bad entry costs its proof a BAD_INPUT on the device -- it insists on consistent ones.
+    for (uint32_t i = 0; i < n; ++i)
+        if (proof_first_node[i + 1] < proof_first_node[i] || proof_first_node[i + 1] > total_nodes)
+            return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: proof_first_node is not monotone");
+    for (uint32_t j = 0; j < total_nodes; ++j)
+        if (node_off[j + 1] < node_off[j] || node_off[j + 1] > nodes_len || node_off[j + 1] - node_off[j] > 0x7fffffffull)
+            return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: node_off is inconsistent");
+    if (root_idx)
+        for (uint32_t i = 0; i < n; ++i)
+            if (root_idx[i] >= n_roots) return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_sharded: root_idx out of range");
+
+    // every proof's nodes, in proof order
+    auto pack = [&](Shard& s) {
+        const uint32_t m = (uint32_t)s.proofs.size();
+        s.pfn.assign((size_t)m + 1, 0);
+        s.node_off.clear();
+        s.nodes.clear();
+        s.node_off.push_back(0);
+        for (uint32_t k = 0; k < m; ++k) {
+            const uint32_t f = proof_first_node[s.proofs[k]], l = proof_first_node[s.proofs[k] + 1];
+            s.pfn[k] = (uint32_t)(s.node_off.size() - 1);
+            for (uint32_t j = f; j < l; ++j) {
+                const uint64_t b = node_off[j], e = node_off[j + 1];
+                s.nodes.insert(s.nodes.end(), nodes + b, nodes + e);
+                s.node_off.push_back(s.nodes.size());
+            }
+            s.pfn[k + 1] = (uint32_t)(s.node_off.size() - 1);
+        }
+    };
+    // the value lies in this proof's last node: shard offset - shard node start + caller's node start
+    auto value_at = [&](const Shard& s, uint32_t k, uint32_t i) -> uint64_t {
+        const uint32_t f = proof_first_node[i], l = proof_first_node[i + 1];
+        const uint32_t sf = s.pfn[k];
+        uint32_t j = 0;
+        while (j + 1 < l - f && s.node_off[sf + j + 1] <= s.value_off[k]) ++j;
+        return s.value_off[k] - s.node_off[sf + j] + node_off[f + j];
+    };
+    const phant::VerifyArgs h{roots, n_roots, root_idx, keys, key_len, nodes, nodes_len, node_off, proof_first_node, n,
+                              status, value_off, value_len};
+    return verify_sharded(c, "mpt_verify_sharded", h, false, fail_count, pack, value_at);
 }
 
 // The node-set form over the comm's devices.  A flat set cannot be cut without knowing where its nodes sit in their tries --
@@ -486,14 +497,7 @@ int32_t phant_mpt_verify_nodeset_sharded(phant_comm* c, const uint8_t* roots, ui
     if (!roots || n_roots == 0 || !node_off || !status || (key_len && !keys) || (nodes_len && !nodes) || key_len > 0x3fffffffu)
         return cfail(c, PHANT_E_INVALID_ARG, "mpt_verify_nodeset_sharded: bad argument");
     const uint32_t W = (uint32_t)c->ctx.size();
-    for (Shard& s : c->shards) {
-        s.proofs.clear();
-        s.members.clear();
-        s.d_fail = nullptr;
-        s.rc = PHANT_OK;
-    }
-    for (uint32_t i = 0; i < n; ++i)
-        c->shards[phant_impl::phant_comm_owner(c, keys ? keys + (size_t)key_len * i : nullptr, key_len)].proofs.push_back(i);
+    for (Shard& s : c->shards) s.members.clear();
     // (an entry of node_off that goes backwards, ends beyond the blob or is absurdly long is not a member of the set -- as on one
     // device --: it is simply not shipped)
     for (uint32_t j = 0; j < total_nodes; ++j) {
@@ -506,23 +510,8 @@ int32_t phant_mpt_verify_nodeset_sharded(phant_comm* c, const uint8_t* roots, ui
             for (Shard& s : c->shards) s.members.push_back(j);
         }
     }
-    auto work = [&](uint32_t r) {
-        Shard& s = c->shards[r];
-        const uint32_t m = (uint32_t)s.proofs.size();
-        if (m == 0) {
-            s.rc = phant::ctx_zero_verdict(c->ctx[r], n_roots, &s.d_fail);
-            return;
-        }
-        s.keys.resize((size_t)m * key_len);
-        s.root_idx.resize(root_idx ? m : 0);
-        s.status.assign(m, 0);
-        s.value_off.assign(m, 0);
-        s.value_len.assign(m, 0);
-        for (uint32_t k = 0; k < m; ++k) {
-            const uint32_t i = s.proofs[k];
-            if (key_len) std::memcpy(s.keys.data() + (size_t)k * key_len, keys + (size_t)i * key_len, key_len);
-            if (root_idx) s.root_idx[k] = root_idx[i];
-        }
+    // the members this device was dealt
+    auto pack = [&](Shard& s) {
         size_t bytes = 0;
         for (uint32_t j : s.members) bytes += (size_t)(node_off[j + 1] - node_off[j]);
         s.nodes.resize(bytes);
@@ -536,61 +525,23 @@ int32_t phant_mpt_verify_nodeset_sharded(phant_comm* c, const uint8_t* roots, ui
             at += len;
         }
         s.node_off[s.members.size()] = at;
-        s.rc = phant::ctx_nodeset_host_async_verdict(c->ctx[r], roots, n_roots, root_idx ? s.root_idx.data() : nullptr, s.keys.data(),
-                                                     key_len, s.nodes.data(), s.nodes.size(), s.node_off.data(),
-                                                     (uint32_t)s.members.size(), m, s.status.data(), s.value_off.data(),
-                                                     s.value_len.data(), &s.d_fail);
     };
-    for_each_device(W, work);
-    for (uint32_t r = 0; r < W; ++r)
-        if (c->shards[r].rc != PHANT_OK) {
-            for (phant_ctx* x : c->ctx) (void)phant_stream_sync(x);  // nothing of a failed call stays in flight
-            return cfail(c, c->shards[r].rc, std::string("mpt_verify_nodeset_sharded: device ") + std::to_string(c->devices[r]) + ": " +
-                                                 phant_last_error(c->ctx[r]));
+    auto value_at = [&](const Shard& s, uint32_t k, uint32_t) -> uint64_t {
+        if (s.members.empty()) return 0;
+        // the shard node the value lies in: the last one that starts at or before it
+        size_t lo = 0, hi = s.members.size();
+        while (hi - lo > 1) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (s.node_off[mid] <= s.value_off[k]) lo = mid;
+            else hi = mid;
         }
-    // ---- the one exchange: per-root failure counts, summed over the devices (RCCL over xGMI) ----
-    std::vector<uint32_t*> bufs(W);
-    for (uint32_t r = 0; r < W; ++r) bufs[r] = c->shards[r].d_fail;
-    int32_t rc = all_reduce_u32(c, bufs, n_roots);
-    if (rc == PHANT_OK && fail_count) {
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        hipError_t e = hipSetDevice(c->devices[0]);
-        if (e == hipSuccess) e = hipMemcpyAsync(fail_count, bufs[0], (size_t)n_roots * 4, hipMemcpyDeviceToHost, phant::ctx_stream(c->ctx[0]));
-        if (prev >= 0) (void)hipSetDevice(prev);
-        if (e != hipSuccess) rc = cfail(c, PHANT_E_DEVICE, "mpt_verify_nodeset_sharded: copying the verdict back");
-    }
-    for (phant_ctx* x : c->ctx) {
-        const int32_t src = phant_stream_sync(x);
-        if (rc == PHANT_OK && src != PHANT_OK) rc = cfail(c, src, std::string("mpt_verify_nodeset_sharded: ") + phant_last_error(x));
-    }
-    if (rc != PHANT_OK) return rc;
-    // ---- results back into the caller's order; value offsets back into the caller's node blob ----
-    for (uint32_t r = 0; r < W; ++r) {
-        const Shard& s = c->shards[r];
-        for (uint32_t k = 0; k < (uint32_t)s.proofs.size(); ++k) {
-            const uint32_t i = s.proofs[k];
-            status[i] = s.status[k];
-            if (value_len) value_len[i] = s.value_len[k];
-            if (value_off) {
-                uint64_t vo = 0;
-                if (s.status[k] == PHANT_PROOF_PRESENT && !s.members.empty()) {
-                    // the shard node the value lies in: the last one that starts at or before it
-                    size_t lo = 0, hi = s.members.size();
-                    while (hi - lo > 1) {
-                        const size_t mid = lo + (hi - lo) / 2;
-                        if (s.node_off[mid] <= s.value_off[k]) lo = mid;
-                        else hi = mid;
-                    }
-                    // (empty nodes share their start with the next one: step to the node that really holds the byte)
-                    while (lo + 1 < s.members.size() && s.node_off[lo + 1] <= s.value_off[k]) ++lo;
-                    vo = s.value_off[k] - s.node_off[lo] + node_off[s.members[lo]];
-                }
-                value_off[i] = vo;
-            }
-        }
-    }
-    return PHANT_OK;
+        // (empty nodes share their start with the next one: step to the node that really holds the byte)
+        while (lo + 1 < s.members.size() && s.node_off[lo + 1] <= s.value_off[k]) ++lo;
+        return s.value_off[k] - s.node_off[lo] + node_off[s.members[lo]];
+    };
+    phant::VerifyArgs h{roots, n_roots, root_idx, keys, key_len, nodes, nodes_len, node_off, nullptr, n, status, value_off, value_len};
+    h.total_nodes = total_nodes;
+    return verify_sharded(c, "mpt_verify_nodeset_sharded", h, true, fail_count, pack, value_at);
 }
 
 // mptize (src/mpt/mpt.zig:38-45) with the work spread over the comm's devices by the top key nibble:

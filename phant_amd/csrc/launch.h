@@ -46,7 +46,7 @@ struct VerifyArgs {
                                      // produced by the pipeline's last kernel (phant_mpt_verify_verdict_dev)
     uint32_t total_nodes = 0;        // node_off has total_nodes + 1 entries: a proof whose node range reaches
                                      // beyond it is BAD_INPUT before node_off is touched (set by the launchers'
-                                     // caller, capi.hip::verify_resident_on)
+                                     // caller, capi.hip::run_verify)
 };
 // Two-tier pipeline (mpt_verify_v3.hip): the trie levels that repeat across proofs are deduplicated (propose ->
 // dedup -> class-sorted hashing of the distinct nodes), the deeper ones hashed in place next to that, then walk.

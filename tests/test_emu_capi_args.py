@@ -125,3 +125,125 @@ def test_plain_c_caller(L, tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "c binding OK" in r.stdout, r.stdout + r.stderr
+
+
+MAX_SLOTS = 4  # PHANT_MAX_SLOTS
+
+
+def _verify_entry_points(h, comm, oracle):
+    """name -> (valid arguments, indices of the pointers it refuses to go without, index of n, index of the slot or None,
+    index of the fail counts or None) for the ten verify entry points; the arrays behind the pointers; the fail counts."""
+    root, keys, nodes, node_off, pfn = _small_batch(oracle)
+    rng = np.random.default_rng(5)
+    k2, v2 = random_kv(rng, 40, 32, 1, 60)
+    t = oracle.Trie(k2, v2)
+    from tests.witness_util import node_set
+    snodes, soff = node_set([t.prove(k) for k in k2[:10]])
+    sroot, skeys = np.frombuffer(t.root(), np.uint8).copy(), np.frombuffer(b"".join(k2[:10]), np.uint8).copy()
+    st, vo, vl, fail = np.zeros(10, np.uint8), np.zeros(10, np.uint64), np.zeros(10, np.uint32), np.zeros(1, np.uint32)
+    m, total = soff.size - 1, node_off.size - 1
+    keep = (root, keys, nodes, node_off, pfn, snodes, soff, sroot, skeys, st, vo, vl, fail)
+    proof = [_p(root), 1, None, _p(keys), 32, _p(nodes), nodes.size, _p(node_off)]
+    nset = [_p(sroot), 1, None, _p(skeys), 32, _p(snodes), snodes.size, _p(soff)]
+    outs = [_p(st), _p(vo), _p(vl)]
+    E = {
+        "phant_mpt_verify_batch": ([h, *proof, _p(pfn), 10, *outs], (1, 4, 6, 8, 9, 11), 10, None, None),
+        "phant_mpt_verify_batch_dev": ([h, *proof, total, _p(pfn), 10, *outs], (1, 4, 8, 10, 12), 11, None, None),
+        "phant_mpt_verify_verdict_dev": ([h, *proof, total, _p(pfn), 10, *outs, _p(fail)], (1, 4, 8, 10, 12, 15), 11, None, 15),
+        "phant_mpt_verify_nodeset": ([h, *nset, m, 10, *outs], (1, 4, 6, 8, 11), 10, None, None),
+        "phant_mpt_verify_nodeset_dev": ([h, *nset, m, 10, *outs], (1, 4, 8, 11), 10, None, None),
+        "phant_mpt_verify_nodeset_verdict_dev": ([h, *nset, m, 10, *outs, _p(fail)], (1, 4, 8, 11), 10, None, 14),
+        "phant_mpt_verify_submit": ([h, 2, *proof, _p(pfn), 10, *outs], (2, 5, 7, 9, 10, 12), 11, 1, None),
+        "phant_mpt_verify_nodeset_submit": ([h, 2, *nset, m, 10, *outs], (2, 5, 7, 9, 12), 11, 1, None),
+        "phant_mpt_verify_sharded": ([comm, *proof, _p(pfn), 10, *outs, _p(fail)], (1, 4, 6, 8, 9, 11), 10, None, 14),
+        # (node_group null: every node shared)
+        "phant_mpt_verify_nodeset_sharded": ([comm, *nset, m, None, 10, *outs, _p(fail)], (1, 4, 6, 8, 12), 11, None, 15),
+    }
+    return E, keep, fail
+
+
+@pytest.fixture()
+def comm1(L):
+    h = C.c_void_p()
+    assert L.phant_comm_create(None, 1, 0, C.byref(h)) == OK
+    yield h
+    L.phant_comm_destroy(h)
+
+
+def test_verify_entry_point_contracts(L, ctx, comm1, oracle):
+    """The argument contract of every verify entry point, table-driven: what each refuses (with a message of its own) and
+    what it accepts as a no-op, including where the forms differ (the _verdict_dev forms with n == 0)."""
+    E, _keep, fail = _verify_entry_points(ctx.handle, comm1, oracle)
+    assert len(E) == 10
+
+    def refused(name, args, fresh_message=True):
+        f = getattr(L, name)
+        sharded = name.endswith("_sharded")
+        # a message nothing of the call under test writes, so that the one read afterwards is the refusal's own
+        if sharded:
+            assert L.phant_comm_allreduce_verdict(comm1, (C.c_void_p * 1)(None), 1) == E_INVALID_ARG
+            before = L.phant_comm_last_error(comm1)
+        else:
+            assert L.phant_diag_set(ctx.handle, 0xFFFF, 0) == E_INVALID_ARG
+            before = L.phant_last_error(ctx.handle)
+        assert f(*args) == E_INVALID_ARG, (name, args)
+        msg = L.phant_comm_last_error(comm1) if sharded else L.phant_last_error(ctx.handle)
+        assert msg, name
+        if fresh_message:
+            assert msg != before and b"mpt_verify" in msg, (name, msg)
+
+    for name, (args, required, n_at, slot_at, fail_at) in E.items():
+        f = getattr(L, name)
+        handle_at = 0
+        n_roots_at, key_len_at = (3, 6) if slot_at is not None else (2, 5)
+        # the valid call
+        fail[:] = 7
+        assert f(*args) == OK, (name, L.phant_last_error(ctx.handle))
+        if slot_at is not None:
+            assert L.phant_wait(ctx.handle, args[slot_at]) == OK
+        # a null handle
+        bad = list(args)
+        bad[handle_at] = None
+        assert f(*bad) == E_INVALID_ARG, name
+        # each required pointer missing, one at a time
+        for hole in required:
+            bad = list(args)
+            bad[hole] = None
+            refused(name, bad)
+        # no roots; a key length beyond 2^30 - 1
+        bad = list(args)
+        bad[n_roots_at] = 0
+        refused(name, bad)
+        bad = list(args)
+        bad[key_len_at] = 0x40000000
+        refused(name, bad)
+        # n == 0 with every array null: a no-op -- except for phant_mpt_verify_verdict_dev, which insists on its counts
+        empty = [a if i == handle_at or i == slot_at or not (a is None or isinstance(a, C.c_void_p)) else None
+                 for i, a in enumerate(args)]
+        empty[n_at], empty[n_roots_at] = 0, 0
+        if name == "phant_mpt_verify_verdict_dev":
+            refused(name, empty)
+        else:
+            assert f(*empty) == OK, name
+        # n == 0 with counts to fill: zeroed by every form that takes them
+        if fail_at is not None:
+            zero = list(empty)
+            zero[n_roots_at], zero[fail_at] = 1, _p(fail)
+            fail[:] = 7
+            assert f(*zero) == OK, name
+            assert fail[0] == 0, name
+            if name == "phant_mpt_verify_verdict_dev":
+                zero[n_roots_at] = 0
+                refused(name, zero)
+        # the streaming forms: a slot in flight (of either form) and a slot that does not exist
+        if slot_at is not None:
+            assert f(*args) == OK
+            for other in ("phant_mpt_verify_submit", "phant_mpt_verify_nodeset_submit"):
+                refused(other, E[other][0])
+                busy_empty = list(E[other][0])
+                busy_empty[11] = 0
+                refused(other, busy_empty)
+            assert L.phant_wait(ctx.handle, args[slot_at]) == OK
+            bad = list(args)
+            bad[slot_at] = MAX_SLOTS
+            refused(name, bad, fresh_message=False)
