@@ -452,6 +452,61 @@ PHANT_API int32_t phant_exec_witness_get(const phant_exec_witness *w, phant_exec
 PHANT_API int32_t phant_exec_witness_prestate(phant_ctx *ctx, const phant_exec_witness *w, const uint8_t *state_root,
                                               phant_prestate *out);
 
+/* phant_exec_witness_poststate: the state root AFTER the block, from the same witness and the block's writes -- the check of
+ * blockchain.zig:83-85 for a client that does not have the state.  The contract:
+ *  - Pre-state proof: the call proves the pre-state itself, exactly as phant_exec_witness_prestate does, with the same kernels:
+ *    the set is hashed once, the accounts are walked from parent_state_root (required), the slots from the proven storage roots;
+ *    the statuses carry the same meaning.
+ *  - Failed keys: a key that is neither PRESENT nor ABSENT counts in n_failed.  When n_failed != 0, state_root and storage_roots
+ *    are zero-filled.  The call still returns PHANT_OK: an invalid witness is a result, not an error.
+ *  - KEEP accounts: the body is unchanged, except that the storage root follows its slot writes.  A KEEP account that is ABSENT
+ *    and has a slot write gets PHANT_PROOF_MISMATCH; a slot write under an ABSENT account is valid only with op == SET, which
+ *    creates the account with a storage trie that starts empty.
+ *  - SET accounts: the leaf becomes rlp([nonce, balance, post storage root, code_hash]) (src/state/types.zig:13-20).
+ *  - DELETE accounts: the leaf is removed and the slot writes are ignored.  Deleting an ABSENT account is a no-op.
+ *  - Slot writes: a non-zero write sets rlp(minimal big-endian); a zero write removes the slot (statedb.zig:112-119); a zero
+ *    write to an ABSENT slot is a no-op.
+ *  - The result is the root of the canonical trie over (old key set - removals + inserts): an insert into an empty branch slot,
+ *    beside a leaf or inside an extension splits nodes as mptize would build them; a removal that leaves a branch with one child
+ *    collapses it and the surviving child merges upward (a leaf takes the longer path, an extension merges with the extension
+ *    above it, a branch hangs under an extension).
+ *  - Too-thin witnesses: collapsing needs to know what the surviving child is.  If that child is a 32-byte reference that nothing
+ *    in the set hashes to, every removed key under that branch gets PHANT_PROOF_MISSING_SIBLING and counts in n_failed; the
+ *    child's type is never guessed.  A reference that is the child of an extension in the authenticated old trie is a branch and
+ *    needs no lookup.  An inserted key whose path runs into an unresolved reference: PHANT_PROOF_MISSING_NODE.
+ *  - Soundness: every byte that enters the new root is a post value the caller passed or a byte of a node reached from
+ *    parent_state_root through references resolved by Keccak; nodes of the set not reachable from the trusted root are never read
+ *    for content, and the declared order of the set is irrelevant.
+ *  - Arguments: NULL ctx, w, io or root, a wrong struct_size, an op outside 0..2 or a NULL input array whose count is non-zero:
+ *    PHANT_E_INVALID_ARG.  An array that the ops make unread may be NULL: nonces / balances / code_hashes when no account is SET,
+ *    slot_vals when slot_write is NULL.  n_accounts == 0 leaves the root equal to the parent root.
+ *  - storage_roots of an account that does not exist afterwards (deleted, or absent and not created): empty_mpt_root.
+ *  - One host synchronisation (a second run of the call's kernels only when the device's key order is undecided or the item list
+ *    outgrows its estimate: DESIGN.md section 7c). */
+#define PHANT_PROOF_MISSING_SIBLING 24  /* poststate only: the key's proof holds, but re-rooting after a removal needs a node
+                                           the witness does not carry */
+#define PHANT_POST_KEEP 0
+#define PHANT_POST_SET 1
+#define PHANT_POST_DELETE 2
+typedef struct phant_poststate {
+    uint32_t struct_size; /* = sizeof(phant_poststate) */
+    /* in: the block's writes, in the witness's own account / slot order (phant_exec_witness_info) */
+    const uint8_t *account_op;   /* n_accounts: KEEP / SET / DELETE */
+    const uint64_t *nonces;      /* n_accounts, read where op == SET */
+    const uint8_t *balances;     /* n_accounts x 32 big-endian, read where op == SET */
+    const uint8_t *code_hashes;  /* n_accounts x 32, read where op == SET */
+    const uint8_t *slot_write;   /* n_slots: != 0 -> slot j's post value is slot_vals[j]; NULL = no slot is written */
+    const uint8_t *slot_vals;    /* n_slots x 32 big-endian; an all-zero value removes the slot */
+    /* out (NULL: not wanted) */
+    uint8_t *state_root;         /* 32 */
+    uint8_t *storage_roots;      /* n_accounts x 32: post storage roots */
+    uint8_t *account_status;     /* n_accounts */
+    uint8_t *slot_status;        /* n_slots */
+    uint32_t n_failed;
+} phant_poststate;
+PHANT_API int32_t phant_exec_witness_poststate(phant_ctx *ctx, const phant_exec_witness *w,
+                                               const uint8_t *parent_state_root, phant_poststate *io);
+
 /* ---------------------------------------------------------------- trie root
  * Replaces src/mpt/mpt.zig:38 `mptize(arena, list: []const KeyVal) !Hash32`
  * (KeyVal = mpt.zig:13-34: key bytes expanded to nibbles, value borrowed).

@@ -35,6 +35,8 @@ PROOF_MISSING_NODE = 20
 PROOF_BAD_INPUT = 21
 PROOF_MISMATCH = 22
 PROOF_BAD_VALUE = 23
+PROOF_MISSING_SIBLING = 24
+POST_KEEP, POST_SET, POST_DELETE = 0, 1, 2
 CODE_NONE = 0xFFFFFFFF
 
 # every symbol include/phant_gpu.h declares: (name, restype, argtypes)
@@ -82,6 +84,7 @@ SYMBOLS = {
     "phant_exec_witness_free": (None, [_vp]),
     "phant_exec_witness_get": (_i32, [_vp, _vp]),
     "phant_exec_witness_prestate": (_i32, [_vp, _vp, _vp, _vp]),
+    "phant_exec_witness_poststate": (_i32, [_vp, _vp, _vp, _vp]),
     "phant_mpt_root": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "phant_mpt_root_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_strip_first_nibble": (_i32, [_vp, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),

@@ -5,6 +5,7 @@
 // without a gfx950 device phant_ctx_create fails.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +74,7 @@ struct phant_ctx {
     // first use); code_form: PHANT_DIAG_CODE_HASH_FORM
     phant::FlatSide code_side{nullptr, nullptr, nullptr};
     uint32_t code_form = 0;
+    bool post_raw_slot_keys = false;  // PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS
 };
 
 namespace {
@@ -404,6 +406,7 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_NODESET_WAVE_MAX: c->ns_tune.wave_max = (uint32_t)(value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : value); return PHANT_OK;
         case PHANT_DIAG_TRIE_SMALL_MAX_KEYS: t.small_max_keys = value; return PHANT_OK;
         case PHANT_DIAG_CODE_HASH_FORM: c->code_form = value == 1 ? 1u : 0u; return PHANT_OK;
+        case PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS: c->post_raw_slot_keys = value != 0; return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }
@@ -1417,6 +1420,231 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
     out->n_failed = cnt[phant::PRE_CNT_FAILED];
     out->n_missing_code = cnt[phant::PRE_CNT_MISSING_CODE];
     out->n_unused_codes = cnt[phant::PRE_CNT_UNUSED_CODES];
+    return PHANT_OK;
+}
+
+/* ------------------------------------------------------- execution witness + writes -> post-state root */
+
+// One run of the whole pipeline on the ctx stream, one synchronisation at its end:
+//   copies -> trie keys -> node-set hash -> account walk -> account decode -> slot walk -> slot decode      (the pre-state's kernels)
+//          -> actions -> key order -> count / scan / emit -> link -> storage tries, level by level -> state trie -> finish -> copies
+// host_order (may be null): the keys' order when the device sort left it undecided.  *need_items: the length of the item list;
+// *undecided: the device sort's flag; keys_back: the hashed keys.
+static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const uint8_t* parent_root, phant_poststate* io,
+                             const uint32_t* host_order, uint32_t cap_items, uint32_t* need_items, uint32_t* undecided,
+                             std::vector<uint8_t>& keys_back, uint32_t cnt[8]) {
+    const uint32_t na = w.n_accounts, ns = w.n_slots, total_nodes = (uint32_t)(w.node_off.size() - 1);
+    const size_t nodes_len = w.nodes.size(), pre_len = w.preimages.size(), nk = (size_t)na + ns;
+    hipStream_t s = c->stream;
+    uint8_t *d_pre, *d_keys, *d_root, *d_nodes, *d_sort, *d_op, *d_pbal, *d_pch, *d_swr, *d_sval;
+    uint64_t *d_poff, *d_noff, *d_avoff, *d_svoff, *d_pnonce;
+    uint32_t *d_sacc, *d_avlen, *d_svlen, *d_sfirst, *d_order_host;
+    phant::PrestateArgs p{};
+    phant::PoststateArgs q{};
+    const size_t sort_ws = phant::order_workspace_bytes((uint32_t)nk);
+    int32_t rc = lay_out(c, s, c->ws.io, [&](auto& a) {
+        d_pre = a.template take<uint8_t>(pre_len + 16);
+        d_poff = a.template take<uint64_t>(nk + 1);
+        d_keys = a.template take<uint8_t>(nk * 32);
+        d_root = a.template take<uint8_t>(32);
+        p.storage_roots = a.template take<uint8_t>((size_t)na * 32);
+        d_sacc = a.template take<uint32_t>(ns);
+        d_nodes = a.template take<uint8_t>(nodes_len + 16);
+        d_noff = a.template take<uint64_t>((size_t)total_nodes + 1);
+        p.acc_status = a.template take<uint8_t>(na);
+        d_avoff = a.template take<uint64_t>(na);
+        d_avlen = a.template take<uint32_t>(na);
+        p.slot_status = a.template take<uint8_t>(ns);
+        d_svoff = a.template take<uint64_t>(ns);
+        d_svlen = a.template take<uint32_t>(ns);
+        p.nonces = a.template take<uint64_t>(na);
+        p.balances = a.template take<uint8_t>((size_t)na * 32);
+        p.code_hashes = a.template take<uint8_t>((size_t)na * 32);
+        p.slot_vals = a.template take<uint8_t>((size_t)ns * 32);
+        p.counters = a.template take<uint32_t>(8);
+        d_sfirst = a.template take<uint32_t>((size_t)na + 1);
+        d_op = a.template take<uint8_t>(na);
+        d_pnonce = a.template take<uint64_t>(na);
+        d_pbal = a.template take<uint8_t>((size_t)na * 32);
+        d_pch = a.template take<uint8_t>((size_t)na * 32);
+        d_swr = a.template take<uint8_t>(ns);
+        d_sval = a.template take<uint8_t>((size_t)ns * 32);
+        q.post_sroots = a.template take<uint8_t>((size_t)na * 32);
+        q.state_root = a.template take<uint8_t>(32);
+        q.acc_flag = a.template take<uint32_t>(na);
+        q.act = a.template take<uint8_t>(nk);
+        q.seg_of = a.template take<uint32_t>(nk);
+        d_order_host = a.template take<uint32_t>(nk);
+        q.key_bad = a.template take<uint8_t>(nk);
+        q.cnt = a.template take<uint32_t>(nk + 4);
+        q.scan_scratch = a.template take<uint32_t>(phant::scan_scratch_entries((uint32_t)nk + 1) + 4);
+        q.items_raw = a.template take<uint8_t>((size_t)cap_items * phant::POSTSTATE_ITEM_BYTES);
+        d_sort = a.template take<uint8_t>(sort_ws + 256);
+    });
+    if (rc) return rc;
+    p.nodes = d_nodes;
+    p.na = na;
+    p.ns = ns;
+    p.nc = 0;
+    p.acc_voff = d_avoff;
+    p.acc_vlen = d_avlen;
+    p.slot_voff = d_svoff;
+    p.slot_vlen = d_svlen;
+    p.slot_account = d_sacc;
+    q.nodes = d_nodes;
+    q.nodes_len = nodes_len;
+    q.na = na;
+    q.ns = ns;
+    q.keys = d_keys;
+    q.parent_root = d_root;
+    q.acc_status = p.acc_status;
+    q.slot_status = p.slot_status;
+    q.acc_voff = d_avoff;
+    q.acc_vlen = d_avlen;
+    q.slot_voff = d_svoff;
+    q.slot_vlen = d_svlen;
+    q.pre_nonces = p.nonces;
+    q.pre_balances = p.balances;
+    q.pre_sroots = p.storage_roots;
+    q.pre_code_hashes = p.code_hashes;
+    q.slot_account = d_sacc;
+    q.slot_first = d_sfirst;
+    q.op = d_op;
+    q.post_nonces = d_pnonce;
+    q.post_balances = d_pbal;
+    q.post_code_hashes = d_pch;
+    q.slot_write = io->slot_write ? d_swr : nullptr;
+    q.post_slot_vals = d_sval;
+    q.cap_items = cap_items;
+    q.counters = p.counters;
+    rc = nodeset_prepare(c, total_nodes, s, c->ns);
+    if (rc) return rc;
+    auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(c, up(d_pre, w.preimages.data(), pre_len));
+    HIP_TRY(c, up(d_poff, w.preimage_off.data(), (nk + 1) * 8));
+    HIP_TRY(c, up(d_root, parent_root, 32));
+    HIP_TRY(c, up(d_sacc, w.slot_account.data(), (size_t)ns * 4));
+    HIP_TRY(c, up(d_nodes, w.nodes.data(), nodes_len));
+    HIP_TRY(c, up(d_noff, w.node_off.data(), ((size_t)total_nodes + 1) * 8));
+    HIP_TRY(c, up(d_sfirst, w.slot_first.data(), ((size_t)na + 1) * 4));
+    HIP_TRY(c, up(d_op, io->account_op, na));
+    // (the post arrays are only read where op == SET; an all-KEEP / DELETE call may leave them out)
+    if (io->nonces) HIP_TRY(c, up(d_pnonce, io->nonces, (size_t)na * 8));
+    if (io->balances) HIP_TRY(c, up(d_pbal, io->balances, (size_t)na * 32));
+    if (io->code_hashes) HIP_TRY(c, up(d_pch, io->code_hashes, (size_t)na * 32));
+    if (io->slot_write) {
+        HIP_TRY(c, up(d_swr, io->slot_write, ns));
+        HIP_TRY(c, up(d_sval, io->slot_vals, (size_t)ns * 32));
+    }
+    if (host_order) HIP_TRY(c, up(d_order_host, host_order, nk * 4));
+    HIP_TRY(c, hipMemsetAsync(p.counters, 0, 32, s));
+    HIP_TRY(c, hipMemsetAsync(q.acc_flag, 0, (size_t)na * 4, s));
+    HIP_TRY(c, hipMemsetAsync(q.key_bad, 0, nk, s));
+    uint32_t* d_flag = nullptr;
+    {
+        TimedRegion t(c);
+        HIP_TRY(c, phant::launch_keccak256_var(d_pre, d_poff, (uint32_t)nk, d_keys, s));
+        if (c->post_raw_slot_keys && ns)  // (tests: the slots' 32 bytes verbatim as their trie keys)
+            HIP_TRY(c, hipMemcpyAsync(d_keys + 32ull * na, d_pre + 20ull * na, (size_t)ns * 32, hipMemcpyDeviceToDevice, s));
+        phant::VerifyArgs acc{d_root, 1, nullptr, d_keys, 32, d_nodes, nodes_len, d_noff, nullptr, na, p.acc_status, d_avoff, d_avlen};
+        phant::VerifyArgs sto{p.storage_roots, na, d_sacc, d_keys + 32ull * na, 32, d_nodes, nodes_len, d_noff, nullptr, ns,
+                              p.slot_status, d_svoff, d_svlen};
+        hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s, c->ns_tune);
+        if (e == hipSuccess) e = phant::launch_nodeset_walk(acc, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+        if (e == hipSuccess) e = phant::launch_prestate_accounts(p, s);
+        if (e == hipSuccess) e = phant::launch_nodeset_walk(sto, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+        if (e == hipSuccess) e = phant::launch_prestate_slots(p, s);
+        if (e == hipSuccess) e = phant::launch_poststate_actions(q, s);
+        if (e == hipSuccess) {
+            if (host_order) {
+                q.order = d_order_host;
+            } else {
+                uint32_t* d_order = nullptr;
+                e = phant::launch_order_digests(d_keys, q.seg_of, (uint32_t)nk, na + 1u, d_sort, &d_order, &d_flag, 0, s);
+                q.order = d_order;
+            }
+        }
+        if (e == hipSuccess) e = phant::launch_poststate_build(q, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+        if (e != hipSuccess) {
+            c->ns.dirty = true;
+            return fail(c, PHANT_E_DEVICE, "exec_witness_poststate: launch", e);
+        }
+    }
+    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    keys_back.resize(nk * 32);
+    *undecided = 0;
+    HIP_TRY(c, back(io->account_status, p.acc_status, na));
+    HIP_TRY(c, back(io->slot_status, p.slot_status, ns));
+    HIP_TRY(c, back(io->storage_roots, q.post_sroots, (size_t)na * 32));
+    HIP_TRY(c, back(io->state_root, q.state_root, 32));
+    HIP_TRY(c, back(keys_back.data(), d_keys, nk * 32));
+    HIP_TRY(c, back(cnt, p.counters, 32));
+    if (d_flag) HIP_TRY(c, back(undecided, d_flag, 4));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    *need_items = cnt[phant::POST_CNT_ITEMS];
+    return PHANT_OK;
+}
+
+int32_t phant_exec_witness_poststate(phant_ctx* c, const phant_exec_witness* pw, const uint8_t* parent_state_root, phant_poststate* io) {
+    if (!c || !pw || !io) return PHANT_E_INVALID_ARG;
+    if (io->struct_size != sizeof(phant_poststate)) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: wrong struct_size");
+    if (!parent_state_root) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: the trusted parent state root is required");
+    const phant::ExecWitness& w = pw->w;
+    const uint32_t na = w.n_accounts, ns = w.n_slots;
+    io->n_failed = 0;
+    if (na && !io->account_op) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: account_op is null");
+    bool any_set = false;
+    for (uint32_t i = 0; i < na; ++i) {
+        if (io->account_op[i] > PHANT_POST_DELETE) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: an account op outside 0..2");
+        any_set = any_set || io->account_op[i] == PHANT_POST_SET;
+    }
+    if (any_set && (!io->nonces || !io->balances || !io->code_hashes))
+        return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: an account is SET but nonces / balances / code_hashes is null");
+    if (ns && io->slot_write && !io->slot_vals) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: slot_write without slot_vals");
+    if (na == 0) {  // nothing is touched: the root stays
+        if (io->state_root) std::memcpy(io->state_root, parent_state_root, 32);
+        return PHANT_OK;
+    }
+    DeviceGuard g(c->device);
+    const size_t nk = (size_t)na + ns;
+    // the item list: a leaf per key and the other children of the branches on their paths -- at most one per reference the set's
+    // bytes can hold in the usual case; a list that outgrows this is counted exactly and the call's kernels run again
+    uint64_t cap = nk + w.nodes.size() / 16u + 1024u;
+    std::vector<uint32_t> order;
+    std::vector<uint8_t> keys;
+    uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int attempt = 0;; ++attempt) {
+        if (cap >= 0x40000000ull) return fail(c, PHANT_E_OOM, "exec_witness_poststate: item list too long");
+        uint32_t need = 0, undecided = 0;
+        const int32_t rc = poststate_run(c, w, parent_state_root, io, order.empty() ? nullptr : order.data(), (uint32_t)cap, &need,
+                                         &undecided, keys, cnt);
+        if (rc) return rc;
+        const bool again_order = undecided != 0 && order.empty(), again_cap = need > cap && cnt[phant::PRE_CNT_FAILED] + cnt[phant::POST_CNT_EMIT_FAILED] == 0;
+        if ((!again_order && !again_cap) || attempt == 2) {
+            if (again_order || again_cap) return fail(c, PHANT_E_DEVICE, "exec_witness_poststate: the item list did not settle");
+            break;
+        }
+        if (again_order) {  // (duplicate keys or a long run of equal prefixes: ordered here, as the state root does)
+            order.resize(nk);
+            for (uint32_t k = 0; k < nk; ++k) order[k] = k;
+            auto seg = [&](uint32_t k) { return k < na ? na : w.slot_account[k - na]; };
+            std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+                if (seg(x) != seg(y)) return seg(x) < seg(y);
+                const int m = std::memcmp(keys.data() + 32ull * x, keys.data() + 32ull * y, 32);
+                return m != 0 ? m < 0 : x < y;
+            });
+        }
+        if (need > cap) cap = need;
+    }
+    io->n_failed = cnt[phant::PRE_CNT_FAILED] + cnt[phant::POST_CNT_INTERNAL] + cnt[phant::POST_CNT_EMIT_FAILED];
+    if (io->n_failed != 0) {
+        if (io->state_root) std::memset(io->state_root, 0, 32);
+        if (io->storage_roots) std::memset(io->storage_roots, 0, (size_t)na * 32);
+    }
     return PHANT_OK;
 }
 

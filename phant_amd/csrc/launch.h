@@ -170,6 +170,52 @@ hipError_t launch_nodeset_hash(const VerifyArgs& a, uint32_t total_nodes, uint32
                                const uint32_t salt[2], hipStream_t st, const NodesetTune& tune);
 hipError_t launch_nodeset_walk(const VerifyArgs& a, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2],
                                hipStream_t st);
+// poststate.hip.h (included by mpt_verify_nodeset.hip): the post-state root behind the pre-state kernels
+// (phant_exec_witness_poststate).  Every pointer is device memory of the call; keys 0 .. na are the accounts, na .. na + ns the slots.
+struct PoststateArgs {
+    const uint8_t* nodes;
+    uint64_t nodes_len;
+    uint32_t na, ns;
+    const uint8_t* keys;            // (na + ns) x 32: the hashed keys
+    const uint8_t* parent_root;     // 32
+    uint8_t* acc_status;            // as the pre-state kernels left them; failures of this phase are added
+    uint8_t* slot_status;
+    const uint64_t* acc_voff;
+    const uint32_t* acc_vlen;
+    const uint64_t* slot_voff;
+    const uint32_t* slot_vlen;
+    const uint64_t* pre_nonces;
+    const uint8_t* pre_balances;
+    const uint8_t* pre_sroots;      // na x 32: the proven storage roots (the roots the storage tries are walked from)
+    const uint8_t* pre_code_hashes;
+    const uint32_t* slot_account;   // ns
+    const uint32_t* slot_first;     // na + 1
+    const uint8_t* op;              // na: PHANT_POST_*
+    const uint64_t* post_nonces;
+    const uint8_t* post_balances;
+    const uint8_t* post_code_hashes;
+    const uint8_t* slot_write;      // ns, may be null
+    const uint8_t* post_slot_vals;  // ns x 32
+    uint8_t* post_sroots;           // na x 32, out
+    uint8_t* state_root;            // 32, out
+    uint32_t* acc_flag;             // na, zeroed by the caller
+    uint8_t* act;                   // na + ns
+    uint32_t* seg_of;               // na + ns: the trie a key lives in (a slot: its account; an account: na)
+    const uint32_t* order;          // na + ns: the keys by (trie, hashed key)
+    uint8_t* key_bad;               // na + ns, zeroed by the caller
+    uint32_t* cnt;                  // na + ns + 1 (16-byte aligned): items per key, then their offsets
+    uint32_t* scan_scratch;         // scan_scratch_entries(na + ns + 1)
+    void* items_raw;                // cap_items x POSTSTATE_ITEM_BYTES
+    uint32_t cap_items;
+    uint32_t* counters;             // the pre-state's PRE_CNT_*, then POST_CNT_*: zeroed by the caller
+};
+constexpr size_t POSTSTATE_ITEM_BYTES = 96;
+// the list's length (may exceed cap_items: run again), what cannot happen, keys whose emit walk failed (counted apart from PRE_CNT_FAILED,
+// which the lanes of that launch read)
+enum : uint32_t { POST_CNT_ITEMS = 3, POST_CNT_INTERNAL = 4, POST_CNT_EMIT_FAILED = 5 };
+hipError_t launch_poststate_actions(const PoststateArgs& p, hipStream_t st);
+hipError_t launch_poststate_build(const PoststateArgs& p, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2],
+                                  hipStream_t st);
 hipError_t launch_mpt_verdict(const uint8_t* d_status, const uint32_t* d_root_idx, uint32_t n,
                               uint32_t n_roots, uint32_t* d_fail_count, hipStream_t st);
 

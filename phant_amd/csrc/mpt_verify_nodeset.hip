@@ -705,3 +705,4 @@ void verify_nodeset_stats_from_header(const uint32_t* hdr, uint32_t epoch, uint3
 }  // namespace phant
 
 #include "prestate.hip.h"
+#include "poststate.hip.h"

@@ -23,6 +23,8 @@ from .context import Context, default_context
 from .state import AccountState
 
 PROOF_BAD_VALUE = L.PROOF_BAD_VALUE
+PROOF_MISSING_SIBLING = L.PROOF_MISSING_SIBLING
+POST_KEEP, POST_SET, POST_DELETE = L.POST_KEEP, L.POST_SET, L.POST_DELETE
 CODE_NONE = L.CODE_NONE
 
 
@@ -193,3 +195,125 @@ def new_payload_prestate(witness_json: str | bytes, parent_state_root: bytes, ct
     if not pre.ok:
         raise PrestateError(f"execution witness: {pre.n_failed} account / slot proofs failed against the parent state root", pre)
     return pre
+
+
+# ------------------------------------------------------------------------------------------------ the post-state root
+class PoststateIO(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("account_op", C.c_void_p), ("nonces", C.c_void_p), ("balances", C.c_void_p),
+                ("code_hashes", C.c_void_p), ("slot_write", C.c_void_p), ("slot_vals", C.c_void_p), ("state_root", C.c_void_p),
+                ("storage_roots", C.c_void_p), ("account_status", C.c_void_p), ("slot_status", C.c_void_p),
+                ("n_failed", C.c_uint32)]
+
+
+class PoststateError(RuntimeError):
+    def __init__(self, msg: str, poststate: "PostState"):
+        super().__init__(msg)
+        self.poststate = poststate
+
+
+@dataclass
+class PostState:
+    """What phant_exec_witness_poststate computed: the state root after the block's writes (zero when a proof failed), the post
+    storage roots and the statuses, in witness order."""
+    root: bytes
+    storage_roots: np.ndarray
+    account_status: np.ndarray
+    slot_status: np.ndarray
+    n_failed: int
+
+    @property
+    def ok(self) -> bool:
+        return self.n_failed == 0
+
+
+def _poststate_arrays(self, ctx: Context | None, parent_root: bytes, writes: dict) -> dict:
+    """The raw call.  writes: account_op (n_accounts, POST_KEEP / POST_SET / POST_DELETE), nonces, balances (n x 32), code_hashes
+    (n x 32) -- read where op == SET --, slot_write (n_slots, or None) and slot_vals (n_slots x 32), all in witness order."""
+    ctx = ctx or default_context()
+    if parent_root is None or len(parent_root) != 32:
+        raise ValueError("parent_root must be the 32-byte state root the caller trusts")
+    i = self.info()
+    na, ns = i["n_accounts"], i["n_slots"]
+
+    def arr(name, dtype, shape):
+        a = writes.get(name)
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.size != int(np.prod(shape)):
+            raise ValueError(f"{name}: expected {shape}, got {a.shape}")
+        return a
+
+    ins = {"account_op": arr("account_op", np.uint8, (na,)), "nonces": arr("nonces", np.uint64, (na,)),
+           "balances": arr("balances", np.uint8, (na, 32)), "code_hashes": arr("code_hashes", np.uint8, (na, 32)),
+           "slot_write": arr("slot_write", np.uint8, (ns,)), "slot_vals": arr("slot_vals", np.uint8, (ns, 32))}
+    outs = {"state_root": np.zeros(32, np.uint8), "storage_roots": np.zeros((max(na, 1), 32), np.uint8),
+            "account_status": np.zeros(max(na, 1), np.uint8), "slot_status": np.zeros(max(ns, 1), np.uint8)}
+    o = PoststateIO()
+    o.struct_size = C.sizeof(PoststateIO)
+    for k, a in ins.items():
+        setattr(o, k, a.ctypes.data if a is not None and a.size else None)
+    for k, a in outs.items():
+        setattr(o, k, a.ctypes.data)
+    root = C.create_string_buffer(bytes(parent_root), 32)
+    ctx.check(self._lib.phant_exec_witness_poststate(ctx.handle, self._h, root, C.byref(o)))
+    return {"state_root": outs["state_root"].tobytes(), "storage_roots": outs["storage_roots"][:na],
+            "account_status": outs["account_status"][:na], "slot_status": outs["slot_status"][:ns], "n_failed": int(o.n_failed)}
+
+
+def writes_of(info: dict, accounts_after: dict, ctx: Context | None = None) -> dict:
+    """The write arrays for a witness from address -> AccountState (the account after the block; every slot of it among the
+    witness's keys is written, with zero where its storage does not hold it) or None (deleted); other addresses are kept."""
+    from .state import code_hashes
+    na, ns = info["n_accounts"], info["n_slots"]
+    w = {"account_op": np.zeros(na, np.uint8), "nonces": np.zeros(na, np.uint64), "balances": np.zeros((na, 32), np.uint8),
+         "code_hashes": np.zeros((na, 32), np.uint8), "slot_write": np.zeros(ns, np.uint8), "slot_vals": np.zeros((ns, 32), np.uint8)}
+    first, slots = info["slot_first"], info["slots"]
+    setters = []
+    for k, addr in enumerate(bytes(a) for a in info["addresses"]):
+        if addr not in accounts_after:
+            continue
+        a = accounts_after[addr]
+        if a is None:
+            w["account_op"][k] = L.POST_DELETE
+            continue
+        w["account_op"][k] = L.POST_SET
+        w["nonces"][k] = a.nonce
+        w["balances"][k] = np.frombuffer(int(a.balance).to_bytes(32, "big"), np.uint8)
+        setters.append((k, a))
+        for j in range(int(first[k]), int(first[k + 1])):
+            v = int(a.storage.get(int.from_bytes(slots[j].tobytes(), "big"), 0))
+            w["slot_write"][j] = 1
+            w["slot_vals"][j] = np.frombuffer(v.to_bytes(32, "big"), np.uint8)
+    if setters:
+        h = code_hashes([a.code for _, a in setters], ctx)
+        for (k, _), d in zip(setters, h):
+            w["code_hashes"][k] = d
+    return w
+
+
+def _poststate(self, ctx: Context | None, parent_root: bytes, accounts_after: dict) -> PostState:
+    r = self.poststate_arrays(ctx, parent_root, writes_of(self.info(), accounts_after, ctx))
+    return PostState(root=r["state_root"], storage_roots=r["storage_roots"], account_status=r["account_status"],
+                     slot_status=r["slot_status"], n_failed=r["n_failed"])
+
+
+StatelessWitness.poststate_arrays = _poststate_arrays
+StatelessWitness.poststate = _poststate
+
+
+def new_payload_poststate(witness_json: str | bytes, parent_state_root: bytes, accounts_after: dict, header_state_root: bytes,
+                          ctx: Context | None = None) -> PostState:
+    """The hook behind `runBlock` (src/blockchain/blockchain.zig:83-85): the state root after the block's writes, proven from the
+    witness alone, must be the header's.  accounts_after: address -> AccountState, or None for a deleted account.  Raises
+    PoststateError when a proof fails, the witness is too thin to re-root, or the root is not header_state_root."""
+    w = StatelessWitness.parse_json(witness_json)
+    try:
+        post = w.poststate(ctx, parent_state_root, accounts_after)
+    finally:
+        w.close()
+    if not post.ok:
+        raise PoststateError(f"execution witness: {post.n_failed} keys failed (proofs, or nodes missing for the new root)", post)
+    if post.root != bytes(header_state_root):
+        raise PoststateError(f"state root after the block is {post.root.hex()}, the header says {bytes(header_state_root).hex()}", post)
+    return post
