@@ -525,6 +525,66 @@ PHANT_API int32_t phant_mpt_root_dev(phant_ctx *ctx, const uint8_t *d_keys, cons
                                      const uint8_t *d_vals, const uint64_t *d_val_off, uint64_t val_bytes, uint32_t n,
                                      uint8_t *d_root);
 
+/* ------------------------------------------------------- witness generation
+ * The nodes a verifier needs for a set of queried keys, cut from the tries of a forest: the producing half of
+ * phant_mpt_verify_nodeset.  What this call emits, phant_mpt_verify_nodeset accepts under the emitted roots with the statuses
+ * reported here.
+ *
+ * 1. The forest: keys / key_off / vals / val_off / n as phant_mpt_root (sorted inside every trie, keys <= 255 bytes; the same
+ *    errors), trie t owning keys [seg_first[t], seg_first[t + 1]) as in phant_mpt_root_nodes.  seg_first == NULL with
+ *    n_tries == 1: one trie.
+ * 2. The queries: key j = qkeys[qkey_off[j] .. qkey_off[j + 1]) (any length), against trie q_trie[j] (NULL: trie 0; an index >=
+ *    n_tries is PHANT_E_INVALID_ARG), with q_flags[j] (NULL: all zero).  Queries may repeat and come in any order.
+ * 3. For trie t the call emits the union over its queries of the hashed nodes from the root node down to where the walk of the
+ *    verifier ends: at the key's leaf or branch value, at the leaf or extension whose path diverges from the key (that node
+ *    included), or at the branch whose slot for the key's next nibble is empty.  A node shorter than 32 bytes lives inside its
+ *    parent and is never a member; an extension and the branch under it are two nodes.  An empty trie and a trie without queries
+ *    contribute nothing (their roots are still written).
+ * 4. Every node POSITION is written once, however many queries pass through it; byte-identical nodes of two tries may both
+ *    appear.  Nodes come grouped by trie in trie order: trie t's are nodes [trie_first_node[t], trie_first_node[t + 1]).  The
+ *    order inside a trie is the implementation's, and the same inputs give the same bytes.
+ * 5. PHANT_PROVE_MAY_REMOVE (bit 0 of q_flags[j]): the caller may remove this key, and phant_exec_witness_poststate must then
+ *    be able to collapse a branch on its path.  Every flagged query that is PRESENT marks the position (nibble, or the value) it
+ *    passes through in each branch on its path.  A branch of which exactly ONE occupied position is unmarked, that position
+ *    holding a 32-byte reference, has the node under that position added to the set (that node only).  A branch collapses only if
+ *    all but one of its positions vanish, and a position vanishes only through flagged keys: so this covers every set of
+ *    removals among the flagged keys.
+ * 6. Capacity.  total_nodes and nodes_len are always written.  If total_nodes > max_nodes or nodes_len > nodes_cap the call
+ *    still returns PHANT_OK, and nodes / node_off are left untouched: call again with the reported sizes.
+ *    Every output pointer may be NULL (not wanted).  struct_size must be sizeof(phant_prove_out), else PHANT_E_INVALID_ARG. */
+#define PHANT_PROVE_MAY_REMOVE 1u
+typedef struct phant_prove_out {
+    uint32_t struct_size;      /* = sizeof(phant_prove_out) */
+    uint32_t max_nodes;        /* node_off holds max_nodes + 1 entries */
+    uint64_t nodes_cap;        /* bytes of nodes */
+    uint8_t *nodes;            /* node bytes back to back */
+    uint64_t *node_off;        /* total_nodes + 1 */
+    uint32_t *trie_first_node; /* n_tries + 1 */
+    uint8_t *roots;            /* n_tries x 32: the mptize roots */
+    uint8_t *q_status;         /* n_queries: PHANT_PROOF_PRESENT / PHANT_PROOF_ABSENT */
+    /* results */
+    uint64_t nodes_len;
+    uint32_t total_nodes;
+    uint32_t reserved;
+} phant_prove_out;
+PHANT_API int32_t phant_mpt_prove_nodeset(phant_ctx *ctx, const uint8_t *keys, const uint32_t *key_off,
+                                          const uint8_t *vals, const uint64_t *val_off, uint32_t n,
+                                          const uint32_t *seg_first /* n_tries + 1, or NULL */, uint32_t n_tries,
+                                          const uint8_t *qkeys, const uint32_t *qkey_off /* n_queries + 1 */,
+                                          const uint32_t *q_trie /* or NULL */, const uint8_t *q_flags /* or NULL */,
+                                          uint32_t n_queries, phant_prove_out *out);
+/* The same over DEVICE-resident tries and queries (offsets relative to their blobs, key_bytes / val_bytes / qkey_bytes the blobs'
+ * totals as in phant_mpt_root_dev).  `out` itself is host memory; the buffers it points to are device memory (roots 4-byte
+ * aligned, node_off 8-byte aligned); an out-of-range q_trie entry is found on the device.  d_qkey_off is TRUSTED: the caller who packed
+ * the queries guarantees n_queries + 1 ascending entries from 0 to qkey_bytes; the locate lanes read d_qkeys through it unchecked
+ * (the forest's own offsets are checked on the device as in phant_mpt_root_dev).  The call synchronises the ctx stream. */
+PHANT_API int32_t phant_mpt_prove_nodeset_dev(phant_ctx *ctx, const uint8_t *d_keys, const uint32_t *d_key_off, uint64_t key_bytes,
+                                              const uint8_t *d_vals, const uint64_t *d_val_off, uint64_t val_bytes, uint32_t n,
+                                              const uint32_t *d_seg_first /* n_tries + 1, or NULL */, uint32_t n_tries,
+                                              const uint8_t *d_qkeys, const uint32_t *d_qkey_off, uint64_t qkey_bytes,
+                                              const uint32_t *d_q_trie /* or NULL */, const uint8_t *d_q_flags /* or NULL */,
+                                              uint32_t n_queries, phant_prove_out *out);
+
 /* Callers of mptize ("next" rows):
  * src/blockchain/blockchain.zig:209-235 calculateMPTRoot -- key rlp(index) */
 PHANT_API int32_t phant_index_root_rlp(phant_ctx *ctx, const uint8_t *items,
@@ -588,6 +648,31 @@ PHANT_API int32_t phant_state_root_dev(phant_ctx *ctx, const uint8_t *d_addrs, c
                                        const uint8_t *d_balances, const uint8_t *d_code, const uint64_t *d_code_off,
                                        uint64_t code_bytes, const uint8_t *d_slot_keys, const uint8_t *d_slot_vals,
                                        const uint32_t *d_slot_first, uint32_t n_slots, uint32_t n, uint8_t *d_root);
+/* phant_state_witness: the execution witness a node that HOLDS the state ships with a payload
+ * (src/engine_api/execution_payload.zig:121) -- the producing half of phant_exec_witness_prestate / _poststate.  The contract:
+ *  - The state: the struct-of-arrays of phant_state_root (host memory), every address once.
+ *  - The keys: key k = wkeys[wkey_off[k] .. wkey_off[k + 1]) is a 20-byte address or a 52-byte address ++ slot, under the rules
+ *    of phant_exec_witness_parse_json: accounts are the distinct addresses in order of first appearance, slots grouped under their
+ *    account in order of first appearance, duplicates collapse (their flags are ORed).  Any other length: PHANT_E_INVALID_ARG,
+ *    the key's index in phant_last_error.
+ *  - The result is a phant_exec_witness, the object the parser returns: phant_exec_witness_get / _prestate / _poststate / _free
+ *    work on it unchanged.  "state" holds the state-trie nodes on the paths of every touched address (an exclusion proof for an
+ *    address the state does not hold), followed by the storage-trie nodes on the paths of every touched slot of an account the
+ *    state holds (a zero-valued slot is not in the trie, statedb.zig:112-119: an exclusion proof; an account without live slots
+ *    has the empty root and contributes nothing) -- each set as phant_mpt_prove_nodeset emits it, every node position once.
+ *    "codes" holds each distinct non-empty bytecode of a touched account the state holds once, in order of first appearance,
+ *    told apart by the code hash the state pass computes.  "keys" are the caller's keys, grouped as above.
+ *  - state_root_out (required): the state root, equal to phant_state_root on the same arrays; the root to hand to _prestate.
+ *  - wkey_flags (NULL: all zero): bit 0 = PHANT_PROVE_MAY_REMOVE.  On a 52-byte key it flags the slot in its account's storage
+ *    trie, on a 20-byte key the account in the state trie: the siblings a collapse would need join the set (rule 5 above).
+ *  - The storage forest is proven while its tables stand, the state trie behind it; the touched keys are hashed on the device.
+ *    Host form only.  A call without keys returns a witness without nodes. */
+PHANT_API int32_t phant_state_witness(phant_ctx *ctx, const uint8_t *addrs, const uint64_t *nonces, const uint8_t *balances,
+                                      const uint8_t *code, const uint64_t *code_off, const uint8_t *slot_keys,
+                                      const uint8_t *slot_vals, const uint32_t *slot_first, uint32_t n, const uint8_t *wkeys,
+                                      const uint32_t *wkey_off /* n_wkeys + 1 */, const uint8_t *wkey_flags /* or NULL */,
+                                      uint32_t n_wkeys, phant_exec_witness **out, uint8_t state_root_out[32]);
+
 /* One rank's share of a SHARDED state root (arguments as phant_state_root): the sub-tries of its accounts by the top nibble x
  * of the hashed address, in one pass -- roots[32 x] = that sub-trie's mptize root, root_enc[root_enc_cap x ..] = the RLP of its
  * root NODE (what phant_mpt_strip_first_nibble re-roots one nibble lower), root_enc_len[x] its length, 0 when the rank has no

@@ -37,6 +37,7 @@ PROOF_MISMATCH = 22
 PROOF_BAD_VALUE = 23
 PROOF_MISSING_SIBLING = 24
 POST_KEEP, POST_SET, POST_DELETE = 0, 1, 2
+PROVE_MAY_REMOVE = 1
 CODE_NONE = 0xFFFFFFFF
 
 # every symbol include/phant_gpu.h declares: (name, restype, argtypes)
@@ -87,11 +88,14 @@ SYMBOLS = {
     "phant_exec_witness_poststate": (_i32, [_vp, _vp, _vp, _vp]),
     "phant_mpt_root": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "phant_mpt_root_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "phant_mpt_prove_nodeset": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "phant_mpt_prove_nodeset_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "phant_mpt_strip_first_nibble": (_i32, [_vp, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "phant_index_root_rlp": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "phant_block_roots": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_index_root_be32": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "phant_state_root": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "phant_state_witness": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, C.POINTER(_vp), _vp]),
     "phant_state_trie_leaves": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp]),
     "phant_state_root_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_state_subtrie_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
@@ -125,6 +129,13 @@ SYMBOLS = {
 
 class PhantOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("stream", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class PhantProveOut(C.Structure):
+    """phant_prove_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_nodes", C.c_uint32), ("nodes_cap", C.c_uint64), ("nodes", C.c_void_p),
+                ("node_off", C.c_void_p), ("trie_first_node", C.c_void_p), ("roots", C.c_void_p), ("q_status", C.c_void_p),
+                ("nodes_len", C.c_uint64), ("total_nodes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PhantError(RuntimeError):

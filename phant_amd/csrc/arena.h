@@ -93,6 +93,8 @@ struct Workspaces {
     DevArena io;  // staged inputs / outputs of the current call
     DevArena t1;  // trie builder: per-key / per-boundary arrays
     DevArena t2;  // trie builder: slot tables + encoding scratch
+    DevArena pv;  // prover (trie_prove.hip.h): marks, sizes, offsets -- next to t1 / t2, which hold the build it reads
+    DevArena pvo; // prover, host form: the node blob and its offsets on their way out
     // Pinned mirror of the first STAGE_BYTES of `io` for SMALL host-form calls: the caller's pageable arrays are packed into
     // it at the offsets their device copies have in the arena and cross the bus in ONE copy (a pageable hipMemcpyAsync costs
     // ~25 us a piece, and a call has five to nine); it is mapped into the device's address space, so small results can be
@@ -143,6 +145,8 @@ struct Workspaces {
         io.release();
         t1.release();
         t2.release();
+        pv.release();
+        pvo.release();
         if (stage) (void)hipHostFree(stage);
         stage = nullptr;
         if (mailbox) (void)hipHostFree(mailbox);

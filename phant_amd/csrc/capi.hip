@@ -1698,6 +1698,84 @@ int32_t phant_mpt_root_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* 
     return PHANT_OK;
 }
 
+/* ---------------------------------------------------------------- witness generation */
+
+static void prove_args_of(const phant_prove_out* out, phant::ProveArgs& a) {
+    a.nodes = out->nodes;
+    a.node_off = out->node_off;
+    a.trie_first_node = out->trie_first_node;
+    a.roots = out->roots;
+    a.q_status = out->q_status;
+    // (a buffer nobody wants has no capacity to exceed: the other one is then written under its own bound alone)
+    a.nodes_cap = out->nodes ? out->nodes_cap : ~0ull;
+    a.max_nodes = out->node_off ? out->max_nodes : 0xffffffffu;
+}
+
+int32_t phant_mpt_prove_nodeset(phant_ctx* c, const uint8_t* keys, const uint32_t* key_off, const uint8_t* vals,
+                                const uint64_t* val_off, uint32_t n, const uint32_t* seg_first, uint32_t n_tries,
+                                const uint8_t* qkeys, const uint32_t* qkey_off, const uint32_t* q_trie, const uint8_t* q_flags,
+                                uint32_t n_queries, phant_prove_out* out) {
+    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: out is null") : PHANT_E_INVALID_ARG;
+    if (out->struct_size != sizeof(phant_prove_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: wrong struct_size");
+    if (n_tries == 0 || (!seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: seg_first is null, or no trie");
+    if (n && (!key_off || !val_off)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: null pointer");
+    if (n_queries && !qkey_off) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: qkey_off is null");
+    if (n_queries && !q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: q_trie is null with several tries");
+    out->total_nodes = 0;
+    out->nodes_len = 0;
+    DeviceGuard g(c->device);
+    std::string err;
+    const uint32_t zero32[1] = {0};
+    const uint64_t zero64[1] = {0};
+    phant::ProveArgs a;
+    prove_args_of(out, a);
+    a.qkeys = qkeys;
+    a.qkey_off = n_queries ? qkey_off : zero32;
+    a.q_trie = q_trie;
+    a.q_flags = q_flags;
+    a.n_queries = n_queries;
+    const int32_t rc = phant::prove_nodeset_host(c->ws, c->stream, keys, n ? key_off : zero32, vals, n ? val_off : zero64, n, seg_first,
+                                                 n_tries, a, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->total_nodes = a.total_nodes;
+    out->nodes_len = a.nodes_len;
+    return PHANT_OK;
+}
+
+int32_t phant_mpt_prove_nodeset_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
+                                    const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n,
+                                    const uint32_t* d_seg_first, uint32_t n_tries, const uint8_t* d_qkeys, const uint32_t* d_qkey_off,
+                                    uint64_t qkey_bytes, const uint32_t* d_q_trie, const uint8_t* d_q_flags, uint32_t n_queries,
+                                    phant_prove_out* out) {
+    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: out is null") : PHANT_E_INVALID_ARG;
+    if (out->struct_size != sizeof(phant_prove_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: wrong struct_size");
+    if (n_tries == 0 || (!d_seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: d_seg_first is null, or no trie");
+    if (n && (!d_key_off || !d_val_off || (key_bytes && !d_keys) || (val_bytes && !d_vals)))
+        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: null pointer");
+    if (n_queries && (!d_qkey_off || (qkey_bytes && !d_qkeys))) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: null query pointer");
+    if (n_queries && !d_q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: d_q_trie is null with several tries");
+    if (((uintptr_t)out->roots & 3u) || ((uintptr_t)out->node_off & 7u) || ((uintptr_t)out->trie_first_node & 3u))
+        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: roots / trie_first_node 4-byte, node_off 8-byte aligned");
+    out->total_nodes = 0;
+    out->nodes_len = 0;
+    DeviceGuard g(c->device);
+    TimedRegion t(c);
+    std::string err;
+    phant::ProveArgs a;
+    prove_args_of(out, a);
+    a.qkeys = d_qkeys;
+    a.qkey_off = d_qkey_off;
+    a.q_trie = d_q_trie;
+    a.q_flags = d_q_flags;
+    a.n_queries = n_queries;
+    const int32_t rc = phant::prove_nodeset_dev(c->ws, c->stream, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first,
+                                                n_tries, a, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->total_nodes = a.total_nodes;
+    out->nodes_len = a.nodes_len;
+    return PHANT_OK;
+}
+
 int32_t phant_index_root_rlp(phant_ctx* c, const uint8_t* items, const uint64_t* item_off,
                              uint32_t n, uint8_t out[32]) {
     if (!c || !out) return PHANT_E_INVALID_ARG;
@@ -1752,6 +1830,26 @@ int32_t phant_state_root(phant_ctx* c, const uint8_t* addrs, const uint64_t* non
     int32_t rc = phant::state_root_host(c->ws, c->stream, addrs, nonces, balances, code, code_off, slot_keys,
                                         slot_vals, slot_first, n, out, err);
     if (rc) return fail(c, rc, err.c_str());
+    return PHANT_OK;
+}
+
+int32_t phant_state_witness(phant_ctx* c, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances, const uint8_t* code,
+                            const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals, const uint32_t* slot_first,
+                            uint32_t n, const uint8_t* wkeys, const uint32_t* wkey_off, const uint8_t* wkey_flags, uint32_t n_wkeys,
+                            phant_exec_witness** out, uint8_t state_root_out[32]) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!out || !state_root_out) return fail(c, PHANT_E_INVALID_ARG, "state_witness: out / state_root_out is null");
+    if (n && (!addrs || !nonces || !balances || !code_off || !slot_first)) return fail(c, PHANT_E_INVALID_ARG, "state_witness: null pointer");
+    if (n_wkeys && (!wkeys || !wkey_off)) return fail(c, PHANT_E_INVALID_ARG, "state_witness: wkeys / wkey_off is null");
+    std::unique_ptr<phant_exec_witness> w(new (std::nothrow) phant_exec_witness());
+    if (!w) return fail(c, PHANT_E_OOM, "state_witness: out of host memory");
+    DeviceGuard g(c->device);
+    std::string err;
+    const int32_t rc = phant::state_witness_host(c->ws, c->stream, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first,
+                                                 n, wkeys, wkey_off, wkey_flags, n_wkeys, w->w, state_root_out, err);
+    if (rc) return fail(c, rc, err.c_str());
+    *out = w.release();
     return PHANT_OK;
 }
 

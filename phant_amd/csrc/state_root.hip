@@ -21,12 +21,17 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <array>
 #include <numeric>
+#include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/phant_gpu.h"
 #include "launch.h"
 #include "trie_build.h"
+#include "witness.h"
 
 namespace phant {
 namespace {
@@ -240,7 +245,37 @@ struct DevLeaves {
     uint64_t val_bytes = 0;
     uint32_t* seg = nullptr;      // {0, n}: the one trie's segment table
     uint8_t* root = nullptr;      // 32 bytes for the caller's forest pass
+    uint8_t* code_hash = nullptr; // n x 32, in the caller's account order
 };
+
+// phant_state_witness: the slot queries the storage forest is proven for while its tables stand (the state trie's pass reuses
+// them).  Trie t of that forest is the caller's account t.  The nodes come back in host memory.
+struct StateProve {
+    std::vector<uint8_t> slot_pre;    // ns x 32 slot preimages
+    std::vector<uint32_t> slot_trie;  // ns
+    std::vector<uint8_t> slot_flags;  // ns
+    std::vector<uint8_t> nodes;
+    std::vector<uint64_t> node_off{0};
+    static size_t io_bytes(size_t ns, size_t na) {  // what the queries take of ws.io on top of the state pass
+        auto R = [](size_t b) { return DevArena::round(b); };
+        return 2 * R(32 * ns + 16) + 2 * R(4 * ns + 4) + R(ns + 1) + R(20 * na + 16) + R(32 * na + 16) + R(4 * na + 4) + R(na + 1) +
+               R(4 * na + 4) + R(32 * na + 16) + 4096;
+    }
+};
+
+// the queries' trie keys: 32-byte digests back to back
+__global__ void __launch_bounds__(256) query_offsets_kernel(uint32_t nq, uint32_t* __restrict__ off) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i <= nq) off[i] = 32u * i;
+}
+
+// dst[32 j ..] = src[32 idx[j] ..]: the code hashes of the touched accounts
+__global__ void __launch_bounds__(256) gather32_kernel(const uint8_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t cnt,
+                                                       uint8_t* __restrict__ dst) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= 32ull * cnt) return;
+    dst[i] = src[32ull * idx[i >> 5] + (i & 31u)];
+}
 
 // the AccountState fields as device-resident struct-of-arrays, offsets relative (code_off[0] == 0, slot_first[0] == 0)
 struct StateIn {
@@ -273,7 +308,7 @@ size_t state_scratch_bytes(uint32_t n, uint32_t m) {
 
 // device-resident inputs -> the state trie's leaves in device memory (scratch from ws.io, which the caller has reset to
 // hold state_scratch_bytes on top of whatever it staged there)
-int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, DevLeaves& out, std::string& err) {
+int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, DevLeaves& out, std::string& err, StateProve* pv = nullptr) {
     const uint32_t n = in.n, m = in.m;
     if ((uint64_t)n * 112u > 0xffffffffull || (uint64_t)m * 33u > 0xffffffffull) {  // (leaf offsets are scanned as 32-bit counters)
         err = "state root: more than 4 GiB of leaves in one call";
@@ -342,7 +377,28 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, Dev
             SR_TRY(hipMemsetAsync(d_flag, 0, 4, st));
         }
     }
-    int32_t rc = trie_forest_dev(ws, st, d_lkeys, d_lkoff, 32ull * L, d_lvals, d_lvoff, leaf_bytes, L, d_acc_first, n, d_sroots, err);
+    int32_t rc;
+    const uint32_t ns = pv ? (uint32_t)pv->slot_trie.size() : 0u;
+    if (ns && L) {  // the same pass with its tables kept, and the touched slots' paths cut from it (no live slot: no storage node)
+        uint8_t* d_qpre = ws.io.take<uint8_t>(32 * (size_t)ns + 16);
+        uint8_t* d_qkeys = ws.io.take<uint8_t>(32 * (size_t)ns + 16);
+        uint32_t* d_qoff = ws.io.take<uint32_t>((size_t)ns + 1);
+        uint32_t* d_qtrie = ws.io.take<uint32_t>((size_t)ns + 1);
+        uint8_t* d_qflags = ws.io.take<uint8_t>((size_t)ns + 1);
+        if (ws.io.overflowed) {
+            err = "state-witness arena sized too small (internal)";
+            return PHANT_E_DEVICE;
+        }
+        SR_TRY(hipMemcpyAsync(d_qpre, pv->slot_pre.data(), 32 * (size_t)ns, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(d_qtrie, pv->slot_trie.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(d_qflags, pv->slot_flags.data(), ns, hipMemcpyHostToDevice, st));
+        SR_TRY(launch_keccak256_fixed(d_qpre, 32, 32, ns, d_qkeys, st));
+        hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)ns + 1)), dim3(256), 0, st, ns, d_qoff);
+        rc = prove_forest_collect(ws, st, d_lkeys, d_lkoff, 32ull * L, d_lvals, d_lvoff, leaf_bytes, L, d_acc_first, n, d_sroots, d_qkeys, d_qoff,
+                                  d_qtrie, d_qflags, ns, pv->nodes, pv->node_off, err);
+    } else {
+        rc = trie_forest_dev(ws, st, d_lkeys, d_lkoff, 32ull * L, d_lvals, d_lvoff, leaf_bytes, L, d_acc_first, n, d_sroots, err);
+    }
     if (rc) return rc;
 
     // ---- accounts: hashed addresses in order, code hashes, leaves ----
@@ -361,6 +417,7 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, Dev
     }
     SR_TRY(launch_keccak256_fixed(d_addrs, 20, 20, n, d_ha, st));
     SR_TRY(launch_keccak256_var(d_code, d_code_off, n, d_hc, st));
+    out.code_hash = d_hc;
     uint32_t* d_aorder = nullptr;
     uint32_t* d_aflag = nullptr;
     rc = order_digests_async(ws.tune, st, d_ha, nullptr, n, 1, d_sort, &d_aorder, &d_aflag, err);
@@ -387,7 +444,8 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, Dev
 // the caller's HOST arrays -> staged once -> state_leaves_core
 int32_t state_leaves_dev(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances,
                          const uint8_t* code, const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals,
-                         const uint32_t* slot_first, uint32_t n, DevLeaves& out, std::string& err) {
+                         const uint32_t* slot_first, uint32_t n, DevLeaves& out, std::string& err, StateProve* pv = nullptr,
+                         size_t extra_io = 0) {
     for (uint32_t a = 0; a < n; ++a) {
         if (slot_first[a + 1] < slot_first[a]) {
             err = "slot_first not monotone";
@@ -403,7 +461,7 @@ int32_t state_leaves_dev(Workspaces& ws, hipStream_t st, const uint8_t* addrs, c
     const size_t n1 = (size_t)n + 1;
     auto R = [](size_t b) { return DevArena::round(b); };
     SR_TRY(ws.io.reset(R(20 * (size_t)n + 16) + R(8 * (size_t)n) + R(32 * (size_t)n) + R(code_bytes + 16) + R(8 * n1) + 2 * R(32 * (size_t)m + 16) +
-                       R(4 * n1) + state_scratch_bytes(n, m)));
+                       R(4 * n1) + state_scratch_bytes(n, m) + extra_io));
     // ---- the caller's arrays, once ----
     uint8_t* d_addrs = ws.io.take<uint8_t>(20 * (size_t)n + 16);
     uint64_t* d_nonces = ws.io.take<uint64_t>(n);
@@ -435,7 +493,7 @@ int32_t state_leaves_dev(Workspaces& ws, hipStream_t st, const uint8_t* addrs, c
     }
     SR_TRY(hipStreamSynchronize(st));  // (the rel_* vectors may go; the core synchronises within microseconds anyway)
     const StateIn in{d_addrs, d_nonces, d_bal, d_code, d_code_off, d_skeys_in, d_svals_in, d_slot_first, n, m, code_bytes};
-    return state_leaves_core(ws, st, in, out, err);
+    return state_leaves_core(ws, st, in, out, err, pv);
 }
 
 // device form: what only the device can see -- offsets that go backwards or do not span what the caller says
@@ -559,6 +617,134 @@ int32_t state_root_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, co
     if (rc) return rc;
     SR_TRY(hipMemcpyAsync(out, l.root, 32, hipMemcpyDeviceToHost, st));
     SR_TRY(hipStreamSynchronize(st));
+    return PHANT_OK;
+}
+
+// phant_state_witness: the state pass with both of its forests proven -- the touched slots against the storage forest while its
+// tables stand, the touched addresses against the state trie behind it -- and the result laid out as the parser lays out a
+// document: accounts and slots in order of first appearance, "state" = the state-trie nodes, then the storage nodes.
+int32_t state_witness_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances,
+                           const uint8_t* code, const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals,
+                           const uint32_t* slot_first, uint32_t n, const uint8_t* wkeys, const uint32_t* wkey_off, const uint8_t* wkey_flags,
+                           uint32_t n_wkeys, ExecWitness& w, uint8_t root_out[32], std::string& err) {
+    w = ExecWitness();
+    w.node_off.push_back(0);
+    w.code_off.push_back(0);
+    // ---- the keys, grouped as exec_witness_parse_json groups them ----
+    std::vector<std::array<uint8_t, 20>> t_addr;
+    std::vector<std::vector<std::array<uint8_t, 32>>> t_slots;
+    std::vector<std::vector<uint8_t>> t_slot_flags;
+    std::vector<uint8_t> t_flags;
+    std::unordered_map<std::string, uint32_t> touched_of;
+    std::unordered_map<std::string, uint32_t> slot_of;  // address ++ slot -> its index under the account
+    for (uint32_t k = 0; k < n_wkeys; ++k) {
+        if (wkey_off[k + 1] < wkey_off[k]) {
+            err = "state_witness: wkey_off not monotone";
+            return PHANT_E_INVALID_ARG;
+        }
+        const uint32_t len = wkey_off[k + 1] - wkey_off[k];
+        if (len != 20 && len != 52) {
+            err = "state_witness: key " + std::to_string(k) + " is " + std::to_string(len) +
+                  " bytes: a key is a 20-byte address or a 52-byte address ++ slot";
+            return PHANT_E_INVALID_ARG;
+        }
+        const uint8_t* p = wkeys + wkey_off[k];
+        const uint8_t fl = wkey_flags ? (uint8_t)(wkey_flags[k] & PHANT_PROVE_MAY_REMOVE) : (uint8_t)0;
+        const auto ins = touched_of.emplace(std::string(reinterpret_cast<const char*>(p), 20), (uint32_t)t_addr.size());
+        const uint32_t a = ins.first->second;
+        if (ins.second) {
+            std::array<uint8_t, 20> x;
+            std::memcpy(x.data(), p, 20);
+            t_addr.push_back(x);
+            t_slots.emplace_back();
+            t_slot_flags.emplace_back();
+            t_flags.push_back(0);
+        }
+        if (len == 20) {
+            t_flags[a] |= fl;
+            continue;
+        }
+        const auto si = slot_of.emplace(std::string(reinterpret_cast<const char*>(p), 52), (uint32_t)t_slots[a].size());
+        if (si.second) {
+            std::array<uint8_t, 32> sl;
+            std::memcpy(sl.data(), p + 20, 32);
+            t_slots[a].push_back(sl);
+            t_slot_flags[a].push_back(0);
+        }
+        t_slot_flags[a][si.first->second] |= fl;
+    }
+    exec_witness_layout_keys(w, t_addr, t_slots);
+    if (n == 0) return trie_root_host(ws, st, nullptr, nullptr, nullptr, nullptr, 0, root_out, err);  // (every key absent under the empty root)
+
+    // ---- which touched addresses the state holds: their slots are queries against that account's storage trie ----
+    std::unordered_map<std::string, uint32_t> index_of;
+    index_of.reserve((size_t)n * 2);
+    for (uint32_t i = 0; i < n; ++i) index_of.emplace(std::string(reinterpret_cast<const char*>(addrs + 20ull * i), 20), i);
+    const uint32_t na = (uint32_t)t_addr.size();
+    std::vector<uint32_t> held_idx;  // the state's index of every touched account it holds, in touched order
+    StateProve pv;
+    for (uint32_t a = 0; a < na; ++a) {
+        const auto it = index_of.find(std::string(reinterpret_cast<const char*>(t_addr[a].data()), 20));
+        if (it == index_of.end()) continue;
+        held_idx.push_back(it->second);
+        for (size_t j = 0; j < t_slots[a].size(); ++j) {
+            pv.slot_pre.insert(pv.slot_pre.end(), t_slots[a][j].begin(), t_slots[a][j].end());
+            pv.slot_trie.push_back(it->second);
+            pv.slot_flags.push_back(t_slot_flags[a][j]);
+        }
+    }
+    DevLeaves l;
+    int32_t rc = state_leaves_dev(ws, st, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n, l, err, &pv,
+                                  StateProve::io_bytes(pv.slot_trie.size(), na));
+    if (rc) return rc;
+
+    // ---- the state trie: the touched addresses' paths, exclusion proofs included ----
+    uint8_t* d_apre = ws.io.take<uint8_t>(20 * (size_t)na + 16);
+    uint8_t* d_akeys = ws.io.take<uint8_t>(32 * (size_t)na + 16);
+    uint32_t* d_aoff = ws.io.take<uint32_t>((size_t)na + 1);
+    uint8_t* d_aflags = ws.io.take<uint8_t>((size_t)na + 1);
+    uint32_t* d_held = ws.io.take<uint32_t>((size_t)na + 1);
+    uint8_t* d_hc = ws.io.take<uint8_t>(32 * (size_t)na + 16);
+    if (ws.io.overflowed) {
+        err = "state-witness arena sized too small (internal)";
+        return PHANT_E_DEVICE;
+    }
+    if (na) {
+        SR_TRY(hipMemcpyAsync(d_apre, w.preimages.data(), 20 * (size_t)na, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(d_aflags, t_flags.data(), na, hipMemcpyHostToDevice, st));
+        SR_TRY(launch_keccak256_fixed(d_apre, 20, 20, na, d_akeys, st));
+    }
+    hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)na + 1)), dim3(256), 0, st, na, d_aoff);
+    std::vector<uint8_t> hc(32 * held_idx.size());
+    if (!held_idx.empty()) {  // (before the forest pass: the copy rides on its synchronisations)
+        SR_TRY(hipMemcpyAsync(d_held, held_idx.data(), 4 * held_idx.size(), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * held_idx.size())), dim3(256), 0, st, l.code_hash, d_held,
+                           (uint32_t)held_idx.size(), d_hc);
+        SR_TRY(hipMemcpyAsync(hc.data(), d_hc, hc.size(), hipMemcpyDeviceToHost, st));
+    }
+    std::vector<uint8_t> nodes;
+    rc = prove_forest_collect(ws, st, l.keys, l.key_off, 32ull * n, l.vals, l.val_off, l.val_bytes, n, l.seg, 1, l.root, d_akeys, d_aoff, nullptr,
+                              d_aflags, na, nodes, w.node_off, err);
+    if (rc) return rc;
+    SR_TRY(hipMemcpyAsync(root_out, l.root, 32, hipMemcpyDeviceToHost, st));
+    SR_TRY(hipStreamSynchronize(st));
+    // "state": the state-trie nodes, then the storage nodes
+    const uint64_t b0 = nodes.size();
+    w.nodes.resize(b0 + pv.nodes.size());
+    if (b0) std::memcpy(w.nodes.data(), nodes.data(), b0);
+    if (!pv.nodes.empty()) std::memcpy(w.nodes.data() + b0, pv.nodes.data(), pv.nodes.size());
+    for (size_t i = 1; i < pv.node_off.size(); ++i) w.node_off.push_back(b0 + pv.node_off[i]);
+    // "codes": every distinct non-empty code of a touched account the state holds, once, by the hash the pass computed
+    std::unordered_set<std::string> seen_code;
+    for (size_t h = 0; h < held_idx.size(); ++h) {
+        const uint32_t i = held_idx[h];
+        const uint64_t len = code_off[i + 1] - code_off[i];
+        if (!len || !seen_code.emplace(reinterpret_cast<const char*>(hc.data() + 32 * h), 32).second) continue;
+        const size_t c0 = w.codes.size();
+        w.codes.resize(c0 + len);
+        std::memcpy(w.codes.data() + c0, code + code_off[i], len);
+        w.code_off.push_back((uint64_t)w.codes.size());
+    }
     return PHANT_OK;
 }
 

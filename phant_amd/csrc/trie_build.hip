@@ -1628,6 +1628,8 @@ __global__ void __launch_bounds__(256) fill_empty_roots_kernel(uint8_t* roots, u
     if (i < n_tries) store_empty_root(roots + 32ull * i);
 }
 
+#include "trie_prove.hip.h"
+
 // ---- host driver ----
 #define TB_TRY(call)                                    \
     do {                                                \
@@ -1651,7 +1653,8 @@ constexpr uint32_t SIDE_LEAF_LDS = 20480;     // bytes of unused dynamic LDS per
 constexpr uint32_t FALLBACK_GRID = 1024;           // workgroups of a bin's fallback pass (its count is on the device)
 
 // The small pass (small_head_kernel, small_climb_kernel): t holds the inputs, the outputs and the t1 arena's arrays.
-static int32_t small_forest(Workspaces& ws, hipStream_t st, TrieDev t, uint64_t total_key_bytes, uint64_t total_val_bytes, std::string& err) {
+static int32_t small_forest(Workspaces& ws, hipStream_t st, TrieDev t, uint64_t total_key_bytes, uint64_t total_val_bytes, std::string& err,
+                            TrieDev* keep) {
     const uint32_t n = t.n;
     TB_TRY(ws.ensure_small(SS_WORDS * 4u));
     {   // slot tables by boundary (a node's dense id is its boundary: < n) + the scratch blob of the nodes that take the general way
@@ -1715,16 +1718,19 @@ static int32_t small_forest(Workspaces& ws, hipStream_t st, TrieDev t, uint64_t 
         err = "trie scratch overflow (internal bound too small)";
         return PHANT_E_DEVICE;
     }
+    if (keep) *keep = t;
     return PHANT_OK;
 }
 
 // Device-side forest build; all pointers device memory, except roots_host.
+// keep (optional): the pass's view of its tables as they stand when it returns -- the prover's input (trie_prove.hip.h); they
+// live in the t1 / t2 arenas until the next call resets those.
 static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off,
                              const uint8_t* d_vals, const uint64_t* d_val_off, uint32_t n,
                              uint64_t total_key_bytes, uint64_t total_val_bytes,
                              const uint32_t* d_seg_first, uint32_t n_tries, uint8_t* d_roots,
                              std::string& err, uint8_t* d_root_enc = nullptr, uint32_t* d_root_enc_len = nullptr,
-                             uint32_t root_enc_cap = 0) {
+                             uint32_t root_enc_cap = 0, TrieDev* keep = nullptr) {
     TB_TRY(ws.ensure_mailbox());
     TrieDev t{};
     t.root_enc = d_root_enc;
@@ -1745,6 +1751,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     if (n == 0) {
         hipLaunchKernelGGL(fill_empty_roots_kernel, dim3(blocks(n_tries)), dim3(256), 0, st, d_roots, n_tries);
         TB_TRY(hipGetLastError());
+        if (keep) *keep = t;
         return PHANT_OK;
     }
 
@@ -1803,7 +1810,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
         const bool fits = n <= SMALL_MAX_KEYS && (size_t)t.lvl_size[0] + tree_ints + FAN <= SMALL_LCP_INTS;  // (the first kernel's LDS)
         const bool by_default = fits && (n <= SMALL_SURE_KEYS || total_val_bytes >= (uint64_t)RATE * n);
         const bool small = ws.tune.small_max_keys >= 0 ? fits && n <= (uint64_t)ws.tune.small_max_keys : by_default;
-        if (small) return small_forest(ws, st, t, total_key_bytes, total_val_bytes, err);
+        if (small) return small_forest(ws, st, t, total_key_bytes, total_val_bytes, err, keep);
     }
     if (n_tries == 1) t.first_flag = nullptr;
     {
@@ -2037,6 +2044,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
         return PHANT_E_DEVICE;
     }
     main_guard.armed = false;
+    if (keep) *keep = t;
     return PHANT_OK;
 }
 
@@ -2208,6 +2216,297 @@ int32_t trie_root_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, cons
     const uint64_t zero64[1] = {0};
     return trie_forest_host(ws, st, keys, n ? key_off : zero32, vals, n ? val_off : zero64, n, seg, 1, out, err, nullptr,
                             0, nullptr);
+}
+
+// ---- witness generation (trie_prove.hip.h): the nodes on the paths of queried keys ----
+namespace {
+struct ProveRun {
+    TrieDev t;
+    ProveDev p;
+    uint32_t total_nodes = 0;
+    uint64_t nodes_len = 0;
+};
+}  // namespace
+
+// The build with its tables kept, then locate / mark, sizes and offsets.  Every pointer is device memory; d_seg_first and d_roots
+// are required here.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the emit pass would write.
+static int32_t prove_plan(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
+                          const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first,
+                          uint32_t n_tries, uint8_t* d_roots, const uint8_t* d_qkeys, const uint32_t* d_qkey_off, const uint32_t* d_q_trie,
+                          const uint8_t* d_q_flags, uint32_t n_queries, uint8_t* d_q_status, ProveRun& run, std::string& err) {
+    int32_t rc = forest_device(ws, st, d_keys, d_key_off, d_vals, d_val_off, n, key_bytes, val_bytes, d_seg_first, n_tries, d_roots, err,
+                               nullptr, nullptr, 0, &run.t);
+    if (rc) return rc;
+    const size_t n1 = (size_t)n + 1;
+    const uint32_t tiles = n ? (uint32_t)((n1 + PV_TILE - 1u) / PV_TILE) : 0u;
+    ProveDev& p = run.p;
+    p = ProveDev{};
+    auto carve = [&](auto& a) {
+        p.nmark = a.template take<uint32_t>(n1);
+        p.lmark = a.template take<uint8_t>(n1);
+        p.members = a.template take<uint8_t>(n1);
+        p.nbase = a.template take<uint32_t>(n1);
+        p.bbase = a.template take<unsigned long long>(n1);
+        p.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
+        p.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
+        p.flags = a.template take<uint32_t>(4);
+    };
+    {
+        ArenaSizer sz;
+        carve(sz);
+        TB_TRY(ws.pv.reset(sz.bytes + 1024));
+        carve(ws.pv);
+        if (ws.pv.overflowed || !p.flags) {
+            err = "prover workspace sized too small (internal)";
+            return PHANT_E_DEVICE;
+        }
+    }
+    p.tiles = tiles;
+    p.qkeys = d_qkeys;
+    p.qkey_off = d_qkey_off;
+    p.q_trie = d_q_trie;
+    p.q_flags = d_q_flags;
+    p.n_queries = n_queries;
+    p.q_status = d_q_status;
+    p.mailbox = ws.mailbox;
+    run.t.n_tries = n_tries;
+    run.t.seg_first = d_seg_first;
+    if (n) {
+        TB_TRY(hipMemsetAsync(p.nmark, 0, n1 * 4, st));
+        TB_TRY(hipMemsetAsync(p.lmark, 0, n1, st));
+    }
+    hipLaunchKernelGGL(prove_reset_kernel, dim3(1), dim3(64), 0, st, run.t, p);
+    if (n_queries) hipLaunchKernelGGL(prove_locate_kernel, dim3(blocks(n_queries)), dim3(256), 0, st, run.t, p);
+    if (n) {
+        if (d_q_flags && n_queries) hipLaunchKernelGGL(prove_sibling_kernel, dim3(blocks(n)), dim3(256), 0, st, run.t, p);
+        hipLaunchKernelGGL(prove_size_kernel, dim3(tiles), dim3(PV_TILE), 0, st, run.t, p);
+    }
+    hipLaunchKernelGGL(prove_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, p);
+    if (n) hipLaunchKernelGGL(prove_base_kernel, dim3(blocks(n1)), dim3(256), 0, st, run.t, p);
+    TB_TRY(hipGetLastError());
+    TB_TRY(hipStreamSynchronize(st));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    const volatile uint32_t* const mb = ws.mailbox + MAILBOX_PROVE;
+    run.total_nodes = mb[0];
+    run.nodes_len = (uint64_t)mb[1] | ((uint64_t)mb[2] << 32);
+    if (mb[3] & PV_ERR_TRIE) {
+        err = "prove_nodeset: a q_trie index is not below n_tries";
+        return PHANT_E_INVALID_ARG;
+    }
+    return PHANT_OK;
+}
+
+// The writing pass: node bytes, node offsets (total_nodes + 1) and the tries' first nodes (n_tries + 1) into DEVICE buffers; any
+// may be null.  The caller has checked that the blob and the offsets hold run.nodes_len / run.total_nodes.  Synchronises.
+static int32_t prove_emit(hipStream_t st, ProveRun& run, uint8_t* d_nodes, uint64_t* d_node_off, uint32_t* d_first, std::string& err) {
+    const uint32_t n = run.t.n;
+    ProveDev& p = run.p;
+    p.nodes = d_nodes;
+    p.node_off = reinterpret_cast<unsigned long long*>(d_node_off);
+    p.trie_first_node = d_first;
+    if (d_first) {
+        if (n) hipLaunchKernelGGL(prove_first_kernel, dim3(blocks((uint64_t)run.t.n_tries + 1)), dim3(256), 0, st, run.t, p);
+        else TB_TRY(hipMemsetAsync(d_first, 0, ((size_t)run.t.n_tries + 1) * 4, st));
+    }
+    if (d_nodes || d_node_off) {
+        if (n) hipLaunchKernelGGL(prove_emit_kernel, dim3((uint32_t)(((uint64_t)n + 1 + 63u) / 64u)), dim3(64), 0, st, run.t, p);
+        else if (d_node_off) TB_TRY(hipMemsetAsync(d_node_off, 0, 8, st));
+    }
+    TB_TRY(hipGetLastError());
+    uint32_t flags = 0;
+    TB_TRY(hipMemcpyAsync(&flags, p.flags, 4, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipStreamSynchronize(st));
+    if (flags & PV_ERR_SCRATCH) {
+        err = "prove_nodeset: scratch overflow (internal bound too small)";
+        return PHANT_E_DEVICE;
+    }
+    return PHANT_OK;
+}
+
+int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
+                          const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first,
+                          uint32_t n_tries, ProveArgs& a, std::string& err) {
+    // what the caller left out: the one trie's segment table, roots nobody wants
+    TB_TRY(ws.io.reset(DevArena::round((size_t)n_tries * 32) + 1024));
+    uint32_t* d_seg = ws.io.take<uint32_t>(2);
+    uint8_t* d_roots = a.roots ? a.roots : ws.io.take<uint8_t>((size_t)n_tries * 32);
+    if (ws.io.overflowed) {
+        err = "prover staging arena sized too small (internal)";
+        return PHANT_E_DEVICE;
+    }
+    if (!d_seg_first) {
+        const uint32_t seg[2] = {0, n};
+        TB_TRY(hipMemcpyAsync(d_seg, seg, sizeof seg, hipMemcpyHostToDevice, st));
+        d_seg_first = d_seg;
+    }
+    ProveRun run;
+    int32_t rc = prove_plan(ws, st, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries, d_roots, a.qkeys,
+                            a.qkey_off, a.q_trie, a.q_flags, a.n_queries, a.q_status, run, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    a.total_nodes = run.total_nodes;
+    a.nodes_len = run.nodes_len;
+    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
+    rc = prove_emit(st, run, fits ? a.nodes : nullptr, fits ? a.node_off : nullptr, a.trie_first_node, err);
+    if (rc) (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// The forest pass of a caller that owns ws.io (phant_state_witness): everything device-resident, d_seg_first and d_roots required.
+// The emitted nodes are APPENDED to the host vectors (node_off holds one entry per node so far + 1), so two forests that reuse
+// t1 / t2 / pv / pvo one after the other end up in one set.
+int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
+                             const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first,
+                             uint32_t n_tries, uint8_t* d_roots, const uint8_t* d_qkeys, const uint32_t* d_qkey_off, const uint32_t* d_q_trie,
+                             const uint8_t* d_q_flags, uint32_t n_queries, std::vector<uint8_t>& nodes, std::vector<uint64_t>& node_off,
+                             std::string& err) {
+    ProveRun run;
+    int32_t rc = prove_plan(ws, st, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries, d_roots, d_qkeys,
+                            d_qkey_off, d_q_trie, d_q_flags, n_queries, nullptr, run, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (!run.total_nodes) return PHANT_OK;
+    TB_TRY(ws.pvo.reset(DevArena::round(run.nodes_len + 16) + DevArena::round(((size_t)run.total_nodes + 1) * 8) + 1024));
+    uint8_t* d_nodes = ws.pvo.take<uint8_t>(run.nodes_len + 16);
+    uint64_t* d_noff = ws.pvo.take<uint64_t>((size_t)run.total_nodes + 1);
+    if (ws.pvo.overflowed || !d_noff) {
+        err = "prover output arena sized too small (internal)";
+        return PHANT_E_DEVICE;
+    }
+    rc = prove_emit(st, run, d_nodes, d_noff, nullptr, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    const size_t b0 = nodes.size(), k0 = node_off.size();  // (node_off[k0 - 1] == b0)
+    nodes.resize(b0 + run.nodes_len);
+    node_off.resize(k0 + run.total_nodes);
+    std::vector<uint64_t> rel((size_t)run.total_nodes + 1);
+    TB_TRY(hipMemcpyAsync(nodes.data() + b0, d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipMemcpyAsync(rel.data(), d_noff, rel.size() * 8, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < run.total_nodes; ++i) node_off[k0 + i] = b0 + rel[i + 1];
+    return PHANT_OK;
+}
+
+int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, const uint32_t* key_off, const uint8_t* vals,
+                           const uint64_t* val_off, uint32_t n, const uint32_t* seg_first, uint32_t n_tries, ProveArgs& a, std::string& err) {
+    const uint32_t one[2] = {0, n};
+    if (!seg_first) seg_first = one;
+    const uint32_t nq = a.n_queries;
+    const uint64_t kb = n ? key_off[n] - key_off[0] : 0;
+    const uint64_t vb = n ? val_off[n] - val_off[0] : 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (key_off[i + 1] < key_off[i] || val_off[i + 1] < val_off[i]) {
+            err = "offsets not monotone";
+            return PHANT_E_INVALID_ARG;
+        }
+        if (key_off[i + 1] - key_off[i] > 255) {
+            err = "key longer than 255 bytes";
+            return PHANT_E_UNSUPPORTED;
+        }
+    }
+    for (uint32_t s = 0; s < n_tries; ++s)
+        if (seg_first[s] > seg_first[s + 1] || seg_first[s + 1] > n) {
+            err = "seg_first not monotone";
+            return PHANT_E_INVALID_ARG;
+        }
+    if (seg_first[0] != 0 || seg_first[n_tries] != n) {
+        err = "seg_first must span [0, n]";
+        return PHANT_E_INVALID_ARG;
+    }
+    for (uint32_t j = 0; j < nq; ++j) {
+        if (a.qkey_off[j + 1] < a.qkey_off[j]) {
+            err = "query key offsets not monotone";
+            return PHANT_E_INVALID_ARG;
+        }
+        if (a.q_trie && a.q_trie[j] >= n_tries) {
+            err = "prove_nodeset: q_trie[" + std::to_string(j) + "] is not below n_tries";
+            return PHANT_E_INVALID_ARG;
+        }
+    }
+    const uint64_t qb = nq ? a.qkey_off[nq] - a.qkey_off[0] : 0;
+    uint8_t *d_keys, *d_vals, *d_roots, *d_qkeys, *d_qflags, *d_qstatus;
+    uint32_t *d_koff, *d_seg, *d_qoff, *d_qtrie, *d_first;
+    uint64_t* d_voff;
+    auto carve = [&](auto& ar) {
+        d_keys = ar.template take<uint8_t>(kb + 16);
+        d_koff = ar.template take<uint32_t>((size_t)n + 1);
+        d_vals = ar.template take<uint8_t>(vb + 16);
+        d_voff = ar.template take<uint64_t>((size_t)n + 1);
+        d_seg = ar.template take<uint32_t>((size_t)n_tries + 1);
+        d_roots = ar.template take<uint8_t>((size_t)n_tries * 32);
+        d_qkeys = ar.template take<uint8_t>(qb + 16);
+        d_qoff = ar.template take<uint32_t>((size_t)nq + 1);
+        d_qtrie = ar.template take<uint32_t>((size_t)nq + 1);
+        d_qflags = ar.template take<uint8_t>((size_t)nq + 1);
+        d_qstatus = ar.template take<uint8_t>((size_t)nq + 1);
+        d_first = ar.template take<uint32_t>((size_t)n_tries + 1);
+    };
+    {
+        ArenaSizer sz;
+        carve(sz);
+        TB_TRY(ws.io.reset(sz.bytes + 1024));
+        carve(ws.io);
+        if (ws.io.overflowed || !d_first) {
+            err = "prover staging arena sized too small (internal)";
+            return PHANT_E_DEVICE;
+        }
+    }
+    std::vector<uint32_t> ko((size_t)n + 1, 0), qo((size_t)nq + 1, 0);
+    std::vector<uint64_t> vo((size_t)n + 1, 0);
+    for (uint32_t i = 0; i <= n && n; ++i) {
+        ko[i] = key_off[i] - key_off[0];
+        vo[i] = val_off[i] - val_off[0];
+    }
+    for (uint32_t j = 0; j <= nq && nq; ++j) qo[j] = a.qkey_off[j] - a.qkey_off[0];
+    if (kb) TB_TRY(hipMemcpyAsync(d_keys, keys + key_off[0], kb, hipMemcpyHostToDevice, st));
+    if (vb) TB_TRY(hipMemcpyAsync(d_vals, vals + val_off[0], vb, hipMemcpyHostToDevice, st));
+    TB_TRY(hipMemcpyAsync(d_koff, ko.data(), ko.size() * 4, hipMemcpyHostToDevice, st));
+    TB_TRY(hipMemcpyAsync(d_voff, vo.data(), vo.size() * 8, hipMemcpyHostToDevice, st));
+    TB_TRY(hipMemcpyAsync(d_seg, seg_first, ((size_t)n_tries + 1) * 4, hipMemcpyHostToDevice, st));
+    if (qb) TB_TRY(hipMemcpyAsync(d_qkeys, a.qkeys + a.qkey_off[0], qb, hipMemcpyHostToDevice, st));
+    TB_TRY(hipMemcpyAsync(d_qoff, qo.data(), qo.size() * 4, hipMemcpyHostToDevice, st));
+    if (a.q_trie && nq) TB_TRY(hipMemcpyAsync(d_qtrie, a.q_trie, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    if (a.q_flags && nq) TB_TRY(hipMemcpyAsync(d_qflags, a.q_flags, nq, hipMemcpyHostToDevice, st));
+    // (pageable sources: hipMemcpyAsync has taken its copy when it returns)
+    ProveRun run;
+    int32_t rc = prove_plan(ws, st, d_keys, d_koff, kb, d_vals, d_voff, vb, n, d_seg, n_tries, d_roots, d_qkeys, d_qoff,
+                            a.q_trie ? d_qtrie : nullptr, a.q_flags ? d_qflags : nullptr, nq, d_qstatus, run, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    a.total_nodes = run.total_nodes;
+    a.nodes_len = run.nodes_len;
+    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
+    uint8_t* d_nodes = nullptr;
+    uint64_t* d_noff = nullptr;
+    if (fits && (a.nodes || a.node_off)) {  // the blob and its offsets at their exact sizes, in an arena of their own
+        TB_TRY(ws.pvo.reset(DevArena::round(run.nodes_len + 16) + DevArena::round(((size_t)run.total_nodes + 1) * 8) + 1024));
+        if (a.nodes) d_nodes = ws.pvo.take<uint8_t>(run.nodes_len + 16);
+        if (a.node_off) d_noff = ws.pvo.take<uint64_t>((size_t)run.total_nodes + 1);
+        if (ws.pvo.overflowed) {
+            err = "prover output arena sized too small (internal)";
+            return PHANT_E_DEVICE;
+        }
+    }
+    rc = prove_emit(st, run, d_nodes, d_noff, a.trie_first_node ? d_first : nullptr, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (d_nodes && run.nodes_len) TB_TRY(hipMemcpyAsync(a.nodes, d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
+    if (d_noff) TB_TRY(hipMemcpyAsync(a.node_off, d_noff, ((size_t)run.total_nodes + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (a.trie_first_node) TB_TRY(hipMemcpyAsync(a.trie_first_node, d_first, ((size_t)n_tries + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (a.roots) TB_TRY(hipMemcpyAsync(a.roots, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
+    if (a.q_status && nq) TB_TRY(hipMemcpyAsync(a.q_status, d_qstatus, nq, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipStreamSynchronize(st));
+    return PHANT_OK;
 }
 
 // rlp.serialize(usize, i) as used at blockchain.zig:226-229

@@ -1,5 +1,6 @@
 // witness.h -- a parsed block witness (witness_json.cpp) in the packed layout of phant_mpt_verify_batch.
 #pragma once
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -89,6 +90,10 @@ struct ExecWitness {
     uint32_t n_accounts = 0, n_slots = 0;
 };
 bool exec_witness_parse_json(const char* json, size_t len, ExecWitness& out, std::string& err);
+// the key tables of `w` from the accounts (in order of first appearance) and each account's slots: what the parser and
+// phant_state_witness both end with
+void exec_witness_layout_keys(ExecWitness& w, const std::vector<std::array<uint8_t, 20>>& addrs,
+                              const std::vector<std::vector<std::array<uint8_t, 32>>>& slots);
 
 bool witness_parse_json(const char* json, size_t len, Witness& out, std::string& err);
 // the same result with the accounts parsed on `threads` host threads (0 = as many as the host has, at most 32)

@@ -925,6 +925,33 @@ bool parse_keys(Parser& ps, KeyTable& t) {
 
 }  // namespace
 
+void exec_witness_layout_keys(ExecWitness& w, const std::vector<std::array<uint8_t, 20>>& addrs,
+                              const std::vector<std::vector<std::array<uint8_t, 32>>>& slots) {
+    // accounts in order of first appearance, their slots behind each other: what the trie keys are hashed from
+    w.n_accounts = (uint32_t)addrs.size();
+    size_t m = 0;
+    for (const auto& s : slots) m += s.size();
+    w.n_slots = (uint32_t)m;
+    w.preimages.resize(20 * (size_t)w.n_accounts + 32 * m);
+    w.preimage_off.resize((size_t)w.n_accounts + m + 1);
+    w.slot_first.resize((size_t)w.n_accounts + 1);
+    w.slot_account.resize(m);
+    size_t k = 0;
+    for (uint32_t a = 0; a < w.n_accounts; ++a) {
+        std::memcpy(w.preimages.data() + 20 * (size_t)a, addrs[a].data(), 20);
+        w.preimage_off[a] = 20 * (uint64_t)a;
+        w.slot_first[a] = (uint32_t)k;
+        for (const auto& sl : slots[a]) {
+            std::memcpy(w.preimages.data() + 20 * (size_t)w.n_accounts + 32 * k, sl.data(), 32);
+            w.preimage_off[w.n_accounts + k] = 20 * (uint64_t)w.n_accounts + 32 * (uint64_t)k;
+            w.slot_account[k] = a;
+            ++k;
+        }
+    }
+    w.slot_first[w.n_accounts] = (uint32_t)k;
+    w.preimage_off[w.n_accounts + m] = (uint64_t)w.preimages.size();
+}
+
 bool exec_witness_parse_json(const char* json, size_t len, ExecWitness& w, std::string& err) {
     w = ExecWitness();
     w.node_off.push_back(0);
@@ -978,29 +1005,7 @@ bool exec_witness_parse_json(const char* json, size_t len, ExecWitness& w, std::
         w = ExecWitness();
         return false;
     }
-    // accounts in order of first appearance, their slots behind each other: what the trie keys are hashed from
-    w.n_accounts = (uint32_t)keys.addrs.size();
-    size_t m = 0;
-    for (const auto& s : keys.slots) m += s.size();
-    w.n_slots = (uint32_t)m;
-    w.preimages.resize(20 * (size_t)w.n_accounts + 32 * m);
-    w.preimage_off.resize((size_t)w.n_accounts + m + 1);
-    w.slot_first.resize((size_t)w.n_accounts + 1);
-    w.slot_account.resize(m);
-    size_t k = 0;
-    for (uint32_t a = 0; a < w.n_accounts; ++a) {
-        std::memcpy(w.preimages.data() + 20 * (size_t)a, keys.addrs[a].data(), 20);
-        w.preimage_off[a] = 20 * (uint64_t)a;
-        w.slot_first[a] = (uint32_t)k;
-        for (const auto& sl : keys.slots[a]) {
-            std::memcpy(w.preimages.data() + 20 * (size_t)w.n_accounts + 32 * k, sl.data(), 32);
-            w.preimage_off[w.n_accounts + k] = 20 * (uint64_t)w.n_accounts + 32 * (uint64_t)k;
-            w.slot_account[k] = a;
-            ++k;
-        }
-    }
-    w.slot_first[w.n_accounts] = (uint32_t)k;
-    w.preimage_off[w.n_accounts + m] = (uint64_t)w.preimages.size();
+    exec_witness_layout_keys(w, keys.addrs, keys.slots);
     return true;
 }
 

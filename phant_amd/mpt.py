@@ -8,6 +8,7 @@ verifier the reference only has as a TODO
     index_root_rlp / index_root_be32   blockchain.zig:209-235 /
                                        execution_payload.zig:125-158
     verify_batch / verify_batch_dev    DESIGN.md section 3
+    prove_nodeset / _packed / _dev     DESIGN.md section 7d (witness generation)
 """
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ PROOF_BAD_NODE = L.PROOF_BAD_NODE
 PROOF_EXTRA_NODES = L.PROOF_EXTRA_NODES
 PROOF_MISSING_NODE = L.PROOF_MISSING_NODE
 PROOF_BAD_INPUT = L.PROOF_BAD_INPUT
+PROVE_MAY_REMOVE = L.PROVE_MAY_REMOVE
 
 
 class UnsortedError(ValueError):
@@ -435,3 +437,101 @@ def verify_nodeset_submit(hw: HostNodeSet, slot: int, ctx: Context | None = None
         None if hw.root_idx is None else hw.root_idx.data_ptr(), hw.keys.data_ptr(), key_len, hw.nodes.data_ptr(),
         hw.nodes.numel(), hw.node_off.data_ptr(), hw.node_off.numel() - 1, hw.n, hw.status.data_ptr(),
         hw.value_off.data_ptr(), hw.value_len.data_ptr()))
+
+
+# ---------------------------------------------------------------------------- witness generation
+@dataclass
+class ProvenNodeSet:
+    """What phant_mpt_prove_nodeset emits (numpy, host): the hashed nodes on the paths of the queried keys, every position once,
+    grouped by trie.  roots / nodes / node_off are what verify_nodeset takes; with root_idx = q_trie the queries verify against it.
+
+    roots (n_tries, 32) u8 | nodes u8[nodes_len] | node_off u64[total_nodes + 1] | trie_first_node u32[n_tries + 1] |
+    q_status u8[n_queries] (PROOF_PRESENT / PROOF_ABSENT)
+    """
+    roots: np.ndarray
+    nodes: np.ndarray
+    node_off: np.ndarray
+    trie_first_node: np.ndarray
+    q_status: np.ndarray
+
+    @property
+    def total_nodes(self) -> int:
+        return len(self.node_off) - 1
+
+    def node(self, j: int) -> bytes:
+        return self.nodes[int(self.node_off[j]):int(self.node_off[j + 1])].tobytes()
+
+    def trie_nodes(self, t: int) -> list[bytes]:
+        """the nodes of trie t, in the order they were emitted"""
+        return [self.node(j) for j in range(int(self.trie_first_node[t]), int(self.trie_first_node[t + 1]))]
+
+
+def prove_nodeset_packed(keys, key_off, vals, val_off, seg_first, qkeys, qkey_off, q_trie=None, q_flags=None,
+                         ctx: Context | None = None) -> ProvenNodeSet:
+    """phant_mpt_prove_nodeset over packed arrays: the forest as mptize_packed takes a trie plus seg_first (u32[n_tries + 1], or
+    None: one trie), the queries as a blob with offsets, q_trie (u32 per query, None with one trie) and q_flags (u8 per query,
+    PROVE_MAY_REMOVE).  The first call guesses the capacities; if the set is larger the call is made once more with the sizes the
+    first one reported."""
+    ctx = ctx or default_context()
+    keys = np.ascontiguousarray(keys, np.uint8)
+    key_off = np.ascontiguousarray(key_off, np.uint32)
+    vals = np.ascontiguousarray(vals, np.uint8)
+    val_off = np.ascontiguousarray(val_off, np.uint64)
+    n = len(key_off) - 1
+    seg = None if seg_first is None else np.ascontiguousarray(seg_first, np.uint32)
+    n_tries = 1 if seg is None else len(seg) - 1
+    qkeys = np.ascontiguousarray(qkeys, np.uint8)
+    qkey_off = np.ascontiguousarray(qkey_off, np.uint32)
+    nq = len(qkey_off) - 1
+    qt = None if q_trie is None else np.ascontiguousarray(q_trie, np.uint32)
+    qf = None if q_flags is None else np.ascontiguousarray(q_flags, np.uint8)
+    roots = np.zeros((max(n_tries, 1), 32), np.uint8)
+    first = np.zeros(n_tries + 1, np.uint32)
+    status = np.zeros(max(nq, 1), np.uint8)
+    max_nodes, nodes_cap = 8 * nq + 64, (8 * nq + 64) * 256
+    for attempt in (0, 1):
+        nodes = np.zeros(max(nodes_cap, 1), np.uint8)
+        node_off = np.zeros(max_nodes + 1, np.uint64)
+        o = L.PhantProveOut(C.sizeof(L.PhantProveOut), max_nodes, nodes_cap, _np_ptr(nodes), _np_ptr(node_off), _np_ptr(first),
+                            _np_ptr(roots), _np_ptr(status), 0, 0, 0)
+        rc = ctx._lib.phant_mpt_prove_nodeset(ctx.handle, _np_ptr(keys), _np_ptr(key_off), _np_ptr(vals), _np_ptr(val_off), n,
+                                              None if seg is None else _np_ptr(seg), n_tries, _np_ptr(qkeys), _np_ptr(qkey_off),
+                                              None if qt is None else _np_ptr(qt), None if qf is None else _np_ptr(qf), nq, C.byref(o))
+        if rc == L.E_UNSORTED:
+            raise UnsortedError("prove_nodeset: keys must be strictly increasing inside every trie")
+        ctx.check(rc)
+        if o.total_nodes <= max_nodes and o.nodes_len <= nodes_cap:
+            return ProvenNodeSet(roots[:n_tries], nodes[:o.nodes_len], node_off[:o.total_nodes + 1], first, status[:nq])
+        max_nodes, nodes_cap = int(o.total_nodes), int(o.nodes_len)
+    raise RuntimeError("prove_nodeset: the reported sizes did not hold on the second call")
+
+
+def prove_nodeset(keyvals, queries, q_trie=None, q_flags=None, seg_first=None, ctx: Context | None = None) -> ProvenNodeSet:
+    """The node set that proves `queries` (an iterable of key bytes) against the trie holding `keyvals` (sorted KeyVals) -- or, with
+    seg_first, against a forest of tries laid end to end (q_trie says which).  -> ProvenNodeSet."""
+    kb, ko = _pack([kv.key for kv in keyvals], np.uint32)
+    vb, vo = _pack([kv.value for kv in keyvals], np.uint64)
+    qb, qo = _pack([bytes(q) for q in queries], np.uint32)
+    return prove_nodeset_packed(kb, ko, vb, vo, seg_first, qb, qo, q_trie, q_flags, ctx)
+
+
+def prove_nodeset_dev(keys: torch.Tensor, key_off: torch.Tensor, vals: torch.Tensor, val_off: torch.Tensor,
+                      seg_first: torch.Tensor | None, qkeys: torch.Tensor, qkey_off: torch.Tensor, q_trie: torch.Tensor | None,
+                      q_flags: torch.Tensor | None, nodes: torch.Tensor | None, node_off: torch.Tensor | None,
+                      trie_first_node: torch.Tensor | None = None, roots: torch.Tensor | None = None,
+                      q_status: torch.Tensor | None = None, ctx: Context | None = None) -> tuple[int, int]:
+    """phant_mpt_prove_nodeset_dev: every tensor device-resident (keys u8, key_off i32[n + 1], vals u8, val_off i64[n + 1],
+    seg_first i32[n_tries + 1] or None, qkeys u8, qkey_off i32[nq + 1], q_trie i32[nq] or None, q_flags u8[nq] or None; outputs
+    nodes u8[cap], node_off i64[max_nodes + 1], trie_first_node i32, roots u8, q_status u8, each optional).
+    -> (total_nodes, nodes_len); nodes / node_off are valid only if both fit."""
+    ctx = ctx or default_context(keys.device.index)
+    n, nq = key_off.numel() - 1, qkey_off.numel() - 1
+    n_tries = 1 if seg_first is None else seg_first.numel() - 1
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    o = L.PhantProveOut(C.sizeof(L.PhantProveOut), 0 if node_off is None else node_off.numel() - 1,
+                        0 if nodes is None else nodes.numel(), ptr(nodes), ptr(node_off), ptr(trie_first_node), ptr(roots),
+                        ptr(q_status), 0, 0, 0)
+    ctx.check(ctx._lib.phant_mpt_prove_nodeset_dev(ctx.handle, keys.data_ptr(), key_off.data_ptr(), keys.numel(), vals.data_ptr(),
+                                                   val_off.data_ptr(), vals.numel(), n, ptr(seg_first), n_tries, qkeys.data_ptr(),
+                                                   qkey_off.data_ptr(), qkeys.numel(), ptr(q_trie), ptr(q_flags), nq, C.byref(o)))
+    return int(o.total_nodes), int(o.nodes_len)

@@ -167,6 +167,20 @@ class StatelessWitness:
                         slot_vals=r["slot_vals"], n_failed=r["n_failed"], n_missing_code=r["n_missing_code"],
                         n_unused_codes=r["n_unused_codes"], missing_code=missing)
 
+    def to_json(self) -> str:
+        """The document parse_json reads back to the same object: state / codes / keys, each account's address followed by its
+        address ++ slot keys, in this object's own order."""
+        import json
+        i = self.info()
+        nodes, off = i["nodes"].tobytes(), i["node_off"]
+        codes, coff = i["codes"].tobytes(), i["code_off"]
+        keys = []
+        for k, addr in enumerate(bytes(a) for a in i["addresses"]):
+            keys.append("0x" + addr.hex())
+            keys += ["0x" + (addr + i["slots"][j].tobytes()).hex() for j in range(int(i["slot_first"][k]), int(i["slot_first"][k + 1]))]
+        return json.dumps({"state": ["0x" + nodes[int(off[j]):int(off[j + 1])].hex() for j in range(i["total_nodes"])],
+                           "codes": ["0x" + codes[int(coff[j]):int(coff[j + 1])].hex() for j in range(i["n_codes"])], "keys": keys})
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.phant_exec_witness_free(self._h)
@@ -177,6 +191,30 @@ class StatelessWitness:
             self.close()
         except Exception:
             pass
+
+
+def build_witness(accounts, keys, may_remove=(), ctx: Context | None = None) -> StatelessWitness:
+    """phant_state_witness: the execution witness of `keys` (20-byte addresses, 52-byte address ++ slot) cut from the state
+    `accounts` (AccountState list) on the GPU; keys also in `may_remove` carry PHANT_PROVE_MAY_REMOVE, so that the witness holds
+    what phant_exec_witness_poststate needs when the block removes them.  The state root is left in `.state_root`."""
+    from .context import _np_ptr
+    from .state import _soa
+    ctx = ctx or default_context()
+    n, arrays = _soa(accounts)
+    keys = [bytes(k) for k in keys]
+    flagged = {bytes(k) for k in may_remove}
+    blob = np.frombuffer(b"".join(keys), np.uint8).copy() if keys and sum(map(len, keys)) else np.zeros(1, np.uint8)
+    off = np.zeros(len(keys) + 1, np.uint32)
+    if keys:
+        off[1:] = np.cumsum([len(k) for k in keys])
+    flags = np.array([L.PROVE_MAY_REMOVE if k in flagged else 0 for k in keys] or [0], np.uint8)
+    h = C.c_void_p()
+    root = np.zeros(32, np.uint8)
+    ctx.check(ctx._lib.phant_state_witness(ctx.handle, *[_np_ptr(a) for a in arrays], n, _np_ptr(blob), _np_ptr(off),
+                                           _np_ptr(flags) if flagged else None, len(keys), C.byref(h), _np_ptr(root)))
+    w = StatelessWitness(h)
+    w.state_root = root.tobytes()
+    return w
 
 
 _EMPTY_CODE = bytes.fromhex("c5d2460186f7233c927e7db2dcc703c0e500b653ca82273b7bfad8045d85a470")
