@@ -507,6 +507,38 @@ typedef struct phant_poststate {
 PHANT_API int32_t phant_exec_witness_poststate(phant_ctx *ctx, const phant_exec_witness *w,
                                                const uint8_t *parent_state_root, phant_poststate *io);
 
+/* phant_exec_witness_advance: phant_exec_witness_poststate, and the nodes of the post-state it built as the witness of the NEXT
+ * block -- what lets one witness over the keys of blocks N+1 .. N+k, proven against the root of block N, be checked block by
+ * block, and what a client that keeps nodes by hash commits after the block (the "dirty set").  Host form only.  The contract:
+ *  - io: arguments, ops, statuses, state_root, storage_roots and n_failed behave exactly as in phant_exec_witness_poststate, with
+ *    the same errors; an io passed to both calls gives the same outputs.  next == NULL or a flag bit other than
+ *    PHANT_ADVANCE_KEEP_OLD: PHANT_E_INVALID_ARG.
+ *  - Failure: when n_failed != 0 (the call reports no root) *next = NULL, and the return is still PHANT_OK.
+ *  - Result: otherwise *next is a phant_exec_witness: phant_exec_witness_get / _prestate / _poststate / _advance / _free work on it
+ *    unchanged.  It has the keys of w, in the same account and slot order, and the codes of w: a contract the block creates has no
+ *    code in it (phant_exec_witness_prestate counts it in n_missing_code), the code of a deleted account becomes unused.
+ *  - Its "state" is the set of post-state nodes the call constructs: every node of 32 bytes or more, and every root node, of the
+ *    post storage tries of the accounts that exist afterwards and have a slot among the keys, and then of the state trie.  It
+ *    holds every node on the post-trie walk of every key of the witness, written or only read -- the walk ends as in rule 3 of
+ *    phant_mpt_prove_nodeset; a removed key ends at the node it now diverges from or at an empty slot -- and the new nodes beside
+ *    those paths that the writes reshaped: the shortened leaf or extension a split leaves, the survivor of a collapse merged
+ *    upward.  Every position appears once; a node under 32 bytes lives inside its parent and is never a member.  Nothing is
+ *    emitted for the storage trie of a deleted or never-created account or for a trie that is empty afterwards.  With
+ *    n_accounts == 0 there are no nodes.
+ *  - Determinism: the same inputs give the same bytes in the same order.  The order is the implementation's: the storage tries by
+ *    account index, then the state trie; inside a trie by the position in path order of the list item that carries the node,
+ *    deeper nodes first.
+ *  - PHANT_ADVANCE_KEEP_OLD: all nodes of w follow the new ones, in w's order, nothing filtered.  This carries the siblings a
+ *    producer added under PHANT_PROVE_MAY_REMOVE on to the next block; nodes that nothing reaches any more are harmless to every
+ *    verifier here ("Soundness").
+ *  - One host synchronisation, plus the second runs phant_exec_witness_poststate has and a rare third kind: the room for the nodes
+ *    is estimated before the launch (the witness's own node bytes, a leaf per key, slack); nodes beyond it are counted, not
+ *    written, and the call's kernels run again with the counted sizes. */
+#define PHANT_ADVANCE_KEEP_OLD 1u
+PHANT_API int32_t phant_exec_witness_advance(phant_ctx *ctx, const phant_exec_witness *w,
+                                             const uint8_t *parent_state_root, phant_poststate *io, uint32_t flags,
+                                             phant_exec_witness **next);
+
 /* ---------------------------------------------------------------- trie root
  * Replaces src/mpt/mpt.zig:38 `mptize(arena, list: []const KeyVal) !Hash32`
  * (KeyVal = mpt.zig:13-34: key bytes expanded to nibbles, value borrowed).

@@ -89,10 +89,13 @@ enum {
     PHANT_DIAG_NODESET_WAVE_MAX,      /* node-set witnesses of up to this many nodes are hashed a node per wave (default 2 048; 0: never) */
     PHANT_DIAG_TRIE_SMALL_MAX_KEYS,   /* trie hasher: up to this many keys a call takes the two-launch pass for small tries (-1: the default, 0: never) */
     PHANT_DIAG_CODE_HASH_FORM,        /* phant_exec_witness_prestate: the codes hashed 0 = a half wave per code (the default), 1 = a lane per code */
-    PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS /* phant_exec_witness_poststate: != 0: a slot's 32 bytes ARE its storage-trie key, not hashed (tests: tries
+    PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS,/* phant_exec_witness_poststate: != 0: a slot's 32 bytes ARE its storage-trie key, not hashed (tests: tries
                                           with chosen keys -- 63 shared nibbles, nodes small enough to embed; the accounts stay hashed).
                                           A TEST HOOK ONLY: it changes what the entry point computes (the root is no state root any
                                           more), so a client never sets it; it holds for the context it was set on until set back to 0 */
+    PHANT_DIAG_ADVANCE_ESTIMATE_BYTES  /* phant_exec_witness_advance: > 0: the room estimated for the emitted nodes is this many bytes (and a
+                                          node descriptor per 64 of them), so that a test reaches the run with the counted sizes; 0: the
+                                          call's own estimate.  A TEST HOOK ONLY: the result does not depend on it */
 };
 PHANT_API int32_t phant_diag_set(phant_ctx *ctx, uint32_t knob, int64_t value);
 

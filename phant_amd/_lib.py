@@ -38,6 +38,7 @@ PROOF_BAD_VALUE = 23
 PROOF_MISSING_SIBLING = 24
 POST_KEEP, POST_SET, POST_DELETE = 0, 1, 2
 PROVE_MAY_REMOVE = 1
+ADVANCE_KEEP_OLD = 1
 CODE_NONE = 0xFFFFFFFF
 
 # every symbol include/phant_gpu.h declares: (name, restype, argtypes)
@@ -86,6 +87,7 @@ SYMBOLS = {
     "phant_exec_witness_get": (_i32, [_vp, _vp]),
     "phant_exec_witness_prestate": (_i32, [_vp, _vp, _vp, _vp]),
     "phant_exec_witness_poststate": (_i32, [_vp, _vp, _vp, _vp]),
+    "phant_exec_witness_advance": (_i32, [_vp, _vp, _vp, _vp, _u32, C.POINTER(_vp)]),
     "phant_mpt_root": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "phant_mpt_root_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_prove_nodeset": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),

@@ -75,6 +75,7 @@ struct phant_ctx {
     phant::FlatSide code_side{nullptr, nullptr, nullptr};
     uint32_t code_form = 0;
     bool post_raw_slot_keys = false;  // PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS
+    uint64_t advance_estimate = 0;    // PHANT_DIAG_ADVANCE_ESTIMATE_BYTES (0: the call's own estimate)
 };
 
 namespace {
@@ -407,6 +408,7 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_TRIE_SMALL_MAX_KEYS: t.small_max_keys = value; return PHANT_OK;
         case PHANT_DIAG_CODE_HASH_FORM: c->code_form = value == 1 ? 1u : 0u; return PHANT_OK;
         case PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS: c->post_raw_slot_keys = value != 0; return PHANT_OK;
+        case PHANT_DIAG_ADVANCE_ESTIMATE_BYTES: c->advance_estimate = value > 0 ? (uint64_t)value : 0u; return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }
@@ -1430,9 +1432,20 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
 //          -> actions -> key order -> count / scan / emit -> link -> storage tries, level by level -> state trie -> finish -> copies
 // host_order (may be null): the keys' order when the device sort left it undecided.  *need_items: the length of the item list;
 // *undecided: the device sort's flag; keys_back: the hashed keys.
+// sink (null: phant_exec_witness_poststate, which allocates and copies nothing of it): phant_exec_witness_advance's room for the nodes
+// the build hashes.  The whole room comes back with the other copies, in front of the one synchronisation; need_* say what the
+// run would have filled.
+struct AdvanceSink {
+    uint64_t cap_bytes = 0;
+    uint32_t cap_desc = 0;
+    std::vector<uint8_t> blob;
+    std::vector<phant::PoststateNodeDesc> desc;
+    uint64_t need_bytes = 0;
+    uint32_t need_desc = 0, overflow = 0;
+};
 static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const uint8_t* parent_root, phant_poststate* io,
                              const uint32_t* host_order, uint32_t cap_items, uint32_t* need_items, uint32_t* undecided,
-                             std::vector<uint8_t>& keys_back, uint32_t cnt[8]) {
+                             std::vector<uint8_t>& keys_back, uint32_t cnt[8], AdvanceSink* sink) {
     const uint32_t na = w.n_accounts, ns = w.n_slots, total_nodes = (uint32_t)(w.node_off.size() - 1);
     const size_t nodes_len = w.nodes.size(), pre_len = w.preimages.size(), nk = (size_t)na + ns;
     hipStream_t s = c->stream;
@@ -1480,8 +1493,18 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
         q.scan_scratch = a.template take<uint32_t>(phant::scan_scratch_entries((uint32_t)nk + 1) + 4);
         q.items_raw = a.template take<uint8_t>((size_t)cap_items * phant::POSTSTATE_ITEM_BYTES);
         d_sort = a.template take<uint8_t>(sort_ws + 256);
+        if (sink) {
+            q.sink_blob = a.template take<uint8_t>(sink->cap_bytes + 16);
+            q.sink_desc = a.template take<phant::PoststateNodeDesc>(sink->cap_desc);
+            q.sink_bytes = a.template take<unsigned long long>(1);
+            q.sink_cnt = a.template take<uint32_t>(2);
+        }
     });
     if (rc) return rc;
+    if (sink) {
+        q.sink_cap_bytes = sink->cap_bytes;
+        q.sink_cap_desc = sink->cap_desc;
+    }
     p.nodes = d_nodes;
     p.na = na;
     p.ns = ns;
@@ -1542,6 +1565,10 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
     HIP_TRY(c, hipMemsetAsync(p.counters, 0, 32, s));
     HIP_TRY(c, hipMemsetAsync(q.acc_flag, 0, (size_t)na * 4, s));
     HIP_TRY(c, hipMemsetAsync(q.key_bad, 0, nk, s));
+    if (sink) {
+        HIP_TRY(c, hipMemsetAsync(q.sink_bytes, 0, 8, s));
+        HIP_TRY(c, hipMemsetAsync(q.sink_cnt, 0, 8, s));
+    }
     uint32_t* d_flag = nullptr;
     {
         TimedRegion t(c);
@@ -1564,6 +1591,7 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
                 uint32_t* d_order = nullptr;
                 e = phant::launch_order_digests(d_keys, q.seg_of, (uint32_t)nk, na + 1u, d_sort, &d_order, &d_flag, 0, s);
                 q.order = d_order;
+                if (sink) q.sink_undecided = d_flag;
             }
         }
         if (e == hipSuccess) e = phant::launch_poststate_build(q, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
@@ -1584,12 +1612,30 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
     HIP_TRY(c, back(keys_back.data(), d_keys, nk * 32));
     HIP_TRY(c, back(cnt, p.counters, 32));
     if (d_flag) HIP_TRY(c, back(undecided, d_flag, 4));
+    uint32_t sink_cnt[2] = {0, 0};
+    unsigned long long sink_bytes = 0;
+    if (sink) {
+        sink->blob.resize(sink->cap_bytes);
+        sink->desc.resize(sink->cap_desc);
+        HIP_TRY(c, back(sink->blob.data(), q.sink_blob, sink->cap_bytes));
+        HIP_TRY(c, back(sink->desc.data(), q.sink_desc, (size_t)sink->cap_desc * sizeof(phant::PoststateNodeDesc)));
+        HIP_TRY(c, back(&sink_bytes, q.sink_bytes, 8));
+        HIP_TRY(c, back(sink_cnt, q.sink_cnt, 8));
+    }
     HIP_TRY(c, hipStreamSynchronize(s));
     *need_items = cnt[phant::POST_CNT_ITEMS];
+    if (sink) {
+        sink->need_bytes = sink_bytes;
+        sink->need_desc = sink_cnt[phant::POST_SINK_NODES];
+        sink->overflow = sink_cnt[phant::POST_SINK_OVERFLOW];
+    }
     return PHANT_OK;
 }
 
-int32_t phant_exec_witness_poststate(phant_ctx* c, const phant_exec_witness* pw, const uint8_t* parent_state_root, phant_poststate* io) {
+// The call behind both entry points.  sink null: phant_exec_witness_poststate.  Otherwise the nodes of the last run are left in it
+// (sink->need_desc of them) unless the call failed or reports no root.
+static int32_t poststate_call(phant_ctx* c, const phant_exec_witness* pw, const uint8_t* parent_state_root, phant_poststate* io,
+                              AdvanceSink* sink) {
     if (!c || !pw || !io) return PHANT_E_INVALID_ARG;
     if (io->struct_size != sizeof(phant_poststate)) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: wrong struct_size");
     if (!parent_state_root) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_poststate: the trusted parent state root is required");
@@ -1621,12 +1667,19 @@ int32_t phant_exec_witness_poststate(phant_ctx* c, const phant_exec_witness* pw,
         if (cap >= 0x40000000ull) return fail(c, PHANT_E_OOM, "exec_witness_poststate: item list too long");
         uint32_t need = 0, undecided = 0;
         const int32_t rc = poststate_run(c, w, parent_state_root, io, order.empty() ? nullptr : order.data(), (uint32_t)cap, &need,
-                                         &undecided, keys, cnt);
+                                         &undecided, keys, cnt, sink);
         if (rc) return rc;
         const bool again_order = undecided != 0 && order.empty(), again_cap = need > cap && cnt[phant::PRE_CNT_FAILED] + cnt[phant::POST_CNT_EMIT_FAILED] == 0;
-        if ((!again_order && !again_cap) || attempt == 2) {
-            if (again_order || again_cap) return fail(c, PHANT_E_DEVICE, "exec_witness_poststate: the item list did not settle");
+        // (the nodes outgrew their estimate: only a run that would otherwise have been the last is worth repeating for them)
+        const bool again_sink = sink && sink->overflow != 0 && !again_order && !again_cap &&
+                                cnt[phant::PRE_CNT_FAILED] + cnt[phant::POST_CNT_INTERNAL] + cnt[phant::POST_CNT_EMIT_FAILED] == 0;
+        if ((!again_order && !again_cap && !again_sink) || attempt == (sink ? 3 : 2)) {
+            if (again_order || again_cap || again_sink) return fail(c, PHANT_E_DEVICE, "exec_witness_poststate: the item list did not settle");
             break;
+        }
+        if (again_sink) {
+            sink->cap_bytes = sink->need_bytes;
+            sink->cap_desc = sink->need_desc;
         }
         if (again_order) {  // (duplicate keys or a long run of equal prefixes: ordered here, as the state root does)
             order.resize(nk);
@@ -1645,6 +1698,75 @@ int32_t phant_exec_witness_poststate(phant_ctx* c, const phant_exec_witness* pw,
         if (io->state_root) std::memset(io->state_root, 0, 32);
         if (io->storage_roots) std::memset(io->storage_roots, 0, (size_t)na * 32);
     }
+    return PHANT_OK;
+}
+
+int32_t phant_exec_witness_poststate(phant_ctx* c, const phant_exec_witness* pw, const uint8_t* parent_state_root, phant_poststate* io) {
+    return poststate_call(c, pw, parent_state_root, io, nullptr);
+}
+
+/* ------------------------------------------------------- execution witness + writes -> the next block's witness */
+
+// The post-state call with a sink behind node_ref (poststate.hip.h): the nodes come back in the order the lanes reserved their room,
+// which no two runs share, so they are ordered here by what they ARE -- trie (the storage tries by account, then the state trie),
+// the item that carries them in the call's sorted list (path order), deepest first, a child before the branch over it.
+int32_t phant_exec_witness_advance(phant_ctx* c, const phant_exec_witness* pw, const uint8_t* parent_state_root, phant_poststate* io,
+                                   uint32_t flags, phant_exec_witness** next) {
+    if (!c || !pw || !io) return PHANT_E_INVALID_ARG;
+    if (!next) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_advance: next is null");
+    *next = nullptr;
+    if (flags & ~PHANT_ADVANCE_KEEP_OLD) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_advance: unknown flag");
+    const phant::ExecWitness& w = pw->w;
+    const uint64_t nk = (uint64_t)w.n_accounts + w.n_slots, total_nodes = w.node_off.size() - 1;
+    AdvanceSink sink;
+    // the nodes on the touched paths are about the ones the witness came with, plus a leaf per key and what the writes reshape
+    sink.cap_bytes = c->advance_estimate ? c->advance_estimate : (uint64_t)w.nodes.size() + 256u * nk + 4096u;
+    const uint64_t cap_desc = c->advance_estimate ? c->advance_estimate / 64u + 1u : total_nodes + 3u * nk + 64u;
+    if (cap_desc >= 0x40000000ull) return fail(c, PHANT_E_OOM, "exec_witness_advance: too many nodes");
+    sink.cap_desc = (uint32_t)cap_desc;
+    const int32_t rc = poststate_call(c, pw, parent_state_root, io, &sink);
+    if (rc) return rc;
+    if (io->n_failed != 0) return PHANT_OK;
+    std::unique_ptr<phant_exec_witness> out(new (std::nothrow) phant_exec_witness());
+    if (!out) return fail(c, PHANT_E_OOM, "exec_witness_advance: out of host memory");
+    phant::ExecWitness& x = out->w;
+    x.codes = w.codes;
+    x.code_off = w.code_off;
+    x.preimages = w.preimages;
+    x.preimage_off = w.preimage_off;
+    x.slot_first = w.slot_first;
+    x.slot_account = w.slot_account;
+    x.n_accounts = w.n_accounts;
+    x.n_slots = w.n_slots;
+    x.node_off.push_back(0);
+    if (w.n_accounts != 0) {  // (without accounts nothing ran)
+        if (sink.overflow || sink.need_desc > sink.desc.size()) return fail(c, PHANT_E_DEVICE, "exec_witness_advance: the node list did not settle");
+        std::vector<uint32_t> by(sink.need_desc);
+        for (uint32_t i = 0; i < sink.need_desc; ++i) by[i] = i;
+        const phant::PoststateNodeDesc* d = sink.desc.data();
+        std::sort(by.begin(), by.end(), [&](uint32_t a, uint32_t b) {
+            if (d[a].trie != d[b].trie) return d[a].trie < d[b].trie;
+            if (d[a].item != d[b].item) return d[a].item < d[b].item;
+            return d[a].where > d[b].where;
+        });
+        x.nodes.resize(sink.need_bytes);
+        uint64_t at = 0;
+        for (uint32_t i : by) {
+            if (d[i].off + d[i].len > sink.blob.size() || at + d[i].len > sink.need_bytes)
+                return fail(c, PHANT_E_DEVICE, "exec_witness_advance: a node descriptor out of range");
+            std::memcpy(x.nodes.data() + at, sink.blob.data() + d[i].off, d[i].len);
+            at += d[i].len;
+            x.node_off.push_back(at);
+        }
+        x.nodes.resize(at);
+    }
+    if (flags & PHANT_ADVANCE_KEEP_OLD) {
+        const uint64_t b0 = x.nodes.size();
+        x.nodes.resize(b0 + w.nodes.size());
+        if (!w.nodes.empty()) std::memcpy(x.nodes.data() + b0, w.nodes.data(), w.nodes.size());
+        for (size_t i = 1; i < w.node_off.size(); ++i) x.node_off.push_back(b0 + w.node_off[i]);
+    }
+    *next = out.release();
     return PHANT_OK;
 }
 

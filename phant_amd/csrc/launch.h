@@ -172,6 +172,13 @@ hipError_t launch_nodeset_walk(const VerifyArgs& a, uint32_t cap_nodes, uint8_t*
                                hipStream_t st);
 // poststate.hip.h (included by mpt_verify_nodeset.hip): the post-state root behind the pre-state kernels
 // (phant_exec_witness_poststate).  Every pointer is device memory of the call; keys 0 .. na are the accounts, na .. na + ns the slots.
+// a node the post-state build emitted: its bytes in the sink's blob and the position it was built for -- the trie (an account's
+// index, n_accounts = the state trie), the item of the call's list that carries it, the branch depth d + 1 it was built at (0: the
+// trie's root) and whether it is that branch itself (1) or the child attached to it (0).  No two nodes of a call share all four.
+struct PoststateNodeDesc {
+    uint64_t off;
+    uint32_t len, trie, item, where;  // where = (d + 1) << 1 | branch
+};
 struct PoststateArgs {
     const uint8_t* nodes;
     uint64_t nodes_len;
@@ -208,8 +215,17 @@ struct PoststateArgs {
     void* items_raw;                // cap_items x POSTSTATE_ITEM_BYTES
     uint32_t cap_items;
     uint32_t* counters;             // the pre-state's PRE_CNT_*, then POST_CNT_*: zeroed by the caller
+    // phant_exec_witness_advance: where the lanes leave every hashed node they build (all null / zero: phant_exec_witness_poststate)
+    uint8_t* sink_blob;             // sink_cap_bytes: the nodes back to back, in the order the lanes reserved their room
+    PoststateNodeDesc* sink_desc;   // sink_cap_desc: which position of which trie each of them is
+    unsigned long long* sink_bytes; // bytes reserved so far (beyond sink_cap_bytes: counted, not written); zeroed by the caller
+    uint32_t* sink_cnt;             // POST_SINK_*: zeroed by the caller
+    const uint32_t* sink_undecided; // may be null: the device sort's flag -- != 0: this run's key order is not one, it will be discarded
+    uint64_t sink_cap_bytes;
+    uint32_t sink_cap_desc;
 };
 constexpr size_t POSTSTATE_ITEM_BYTES = 96;
+enum : uint32_t { POST_SINK_NODES = 0, POST_SINK_OVERFLOW = 1 };  // PoststateArgs::sink_cnt
 // the list's length (may exceed cap_items: run again), what cannot happen, keys whose emit walk failed (counted apart from PRE_CNT_FAILED,
 // which the lanes of that launch read)
 enum : uint32_t { POST_CNT_ITEMS = 3, POST_CNT_INTERNAL = 4, POST_CNT_EMIT_FAILED = 5 };

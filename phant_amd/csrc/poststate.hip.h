@@ -22,6 +22,9 @@
 //   post_root_kernel       a lane per trie: the last item standing is the root node (always hashed)
 //   post_finish_kernel     MISSING_SIBLING into the statuses, the post storage roots of accounts that do not exist afterwards
 //
+// phant_exec_witness_advance runs the same kernels with a sink behind node_ref: every hashed node the build constructs leaves the
+// lane's private buffer for a device blob, with a descriptor of its position.  Without a sink nothing changes.
+//
 // Soundness: a byte enters a node built here from (a) a post value of the caller or (b) a node that the emit walk reached from the
 // trusted root (or a storage root proven under it) through references resolved by Keccak in the record table, or such a node's
 // child reference resolved the same way.  Nodes of the set that nothing reachable refers to are never looked at.
@@ -487,11 +490,40 @@ PHANT_DEV uint32_t put_minimal(uint8_t* out, const uint8_t* be, uint32_t n) {  /
     return put_string(out, be + z, n - z);
 }
 // a node's reference: itself below 32 bytes (mpt.zig:104 / :112), else -- or when `force` (the root, :42) -- its Keccak-256
-PHANT_DEV uint32_t node_ref(const uint8_t* node, uint32_t len, bool force, uint8_t* ref) {
+// -- the single place a built node is hashed, and therefore where phant_exec_witness_advance takes its nodes from: a hashed node
+// goes to the sink (`at.p` null: there is none) with the position it was built for.  A lane reserves its room with one atomicAdd on the
+// byte cursor and one on the node count; what does not fit is counted and not written (the host runs the call again with the
+// counted sizes).  Nothing is emitted for the storage trie of an account that does not exist afterwards (the build still walks
+// it; its root is overwritten by post_finish_kernel) nor in a run whose key order the device sort left undecided.
+struct NodeAt {
+    const PoststateArgs* p;
+    uint32_t trie, item, where;  // PoststateNodeDesc
+};
+PHANT_DEV void sink_put(const NodeAt& at, const uint8_t* node, uint32_t len) {
+    const PoststateArgs& p = *at.p;
+    if (at.trie < p.na && (p.act[at.trie] == ACT_REMOVE || p.act[at.trie] == ACT_NONE)) return;
+    if (p.sink_undecided && *p.sink_undecided != 0u) return;
+    const unsigned long long off = atomicAdd(p.sink_bytes, (unsigned long long)len);
+    const uint32_t idx = atomicAdd(&p.sink_cnt[POST_SINK_NODES], 1u);
+    if (off + len > p.sink_cap_bytes || idx >= p.sink_cap_desc) {
+        atomicOr(&p.sink_cnt[POST_SINK_OVERFLOW], 1u);
+        return;
+    }
+    uint8_t* const out = p.sink_blob + off;
+    for (uint32_t t = 0; t < len; ++t) out[t] = node[t];
+    PoststateNodeDesc& d = p.sink_desc[idx];
+    d.off = off;
+    d.len = len;
+    d.trie = at.trie;
+    d.item = at.item;
+    d.where = at.where;
+}
+PHANT_DEV uint32_t node_ref(const uint8_t* node, uint32_t len, bool force, uint8_t* ref, const NodeAt& at) {
     if (len < 32u && !force) {
         for (uint32_t t = 0; t < len; ++t) ref[t] = node[t];
         return len;
     }
+    if (at.p) sink_put(at, node, len);
     Sponge s;
     keccak256_global(s, node, len);
     for (uint32_t k = 0; k < 4u; ++k) {
@@ -546,6 +578,7 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
     uint8_t vb[MAX_VALUE + 8];
     uint8_t nibs[64];
     uint32_t n = 0;
+    const NodeAt here{p.sink_blob ? &p : nullptr, c->trie, (uint32_t)(c - post_items(p)), (uint32_t)(d + 1) << 1};
     for (uint32_t j = (uint32_t)(d + 1); j < c->plen; ++j) nibs[n++] = (uint8_t)nib_of(c->path, j);
     const uint32_t kind = c->kind;
     if (kind <= IK_LEAF_ACC) {
@@ -575,7 +608,7 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
             for (uint32_t t = 0; t < q; ++t) acc[h + t] = body[t];
             vl = put_string(vb, acc, h + q);
         }
-        return node_ref(node, put_short_node(node, nibs, n, true, vb, vl), force, ref);
+        return node_ref(node, put_short_node(node, nibs, n, true, vb, vl), force, ref, here);
     }
     if (n == 0u) {  // the reference fills the slot as it is (the root: the hash of a branch built here)
         if (force && c->reflen != 32u) {  // (over 32-byte keys a root branch is never small enough to embed)
@@ -587,7 +620,7 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
     }
     if (kind == IK_BUILT || kind == IK_REF_BRANCH) {  // known to be a branch: it hangs under an extension
         const uint32_t il = put_ref_item(vb, c->ref, c->reflen);
-        return node_ref(node, put_short_node(node, nibs, n, false, vb, il), force, ref);
+        return node_ref(node, put_short_node(node, nibs, n, false, vb, il), force, ref, here);
     }
     // what the reference points to decides: never guessed
     const uint8_t* nd = c->ref;
@@ -607,7 +640,7 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
     decode_node(nd, nd_len, m);
     if (m.cnt == 17u) {
         const uint32_t il = put_ref_item(vb, c->ref, c->reflen);
-        return node_ref(node, put_short_node(node, nibs, n, false, vb, il), force, ref);
+        return node_ref(node, put_short_node(node, nibs, n, false, vb, il), force, ref, here);
     }
     if (m.cnt != 2u || n + m.plen > 64u || m.it[1].total > MAX_VALUE) {
         mark_removed_under(p, c->trie, c->path, c->plen - 1u);
@@ -617,7 +650,7 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
     for (uint32_t j = 0; j < m.plen; ++j) nibs[n++] = (uint8_t)hp_nibble(nd, m, j);
     const uint32_t at = m.it[1].pay - (m.it[1].total - m.it[1].len);
     for (uint32_t t = 0; t < m.it[1].total; ++t) vb[t] = nd[at + t];
-    return node_ref(node, put_short_node(node, nibs, n, m.leaf != 0u, vb, m.it[1].total), force, ref);
+    return node_ref(node, put_short_node(node, nibs, n, m.leaf != 0u, vb, m.it[1].total), force, ref, here);
 }
 
 // ---------------------------------------------------------------- build
@@ -654,7 +687,8 @@ __global__ void __launch_bounds__(64) post_level_kernel(const Args a, const int3
     const uint32_t pl = pos - 3u, hdr = pl < 56u ? 1u : pl < 256u ? 2u : 3u;
     uint8_t* const node = buf + 3u - hdr;
     put_list_header(node, pl);
-    me->reflen = (uint8_t)node_ref(node, hdr + pl, false, me->ref);
+    const NodeAt at{p.sink_blob ? &p : nullptr, me->trie, i, ((uint32_t)(d + 1) << 1) | 1u};
+    me->reflen = (uint8_t)node_ref(node, hdr + pl, false, me->ref, at);
     me->kind = IK_BUILT;
     me->plen = (uint8_t)d;
     me->nxt = c;

@@ -10,6 +10,9 @@ The document declares nothing; every value comes out of the proofs (include/phan
     pre = w.prestate(ctx, parent_state_root)            # the GPU: one call, one synchronisation
     pre.ok, pre.accounts                                # -> state.AccountState list for StateDB.init
     pre = new_payload_prestate(text, parent_state_root) # the hook: raises unless every proof holds
+    post = w.poststate(ctx, parent_state_root, accounts_after)         # the state root after the block's writes
+    post, nxt = w.advance(ctx, parent_state_root, accounts_after)      # ... and the witness of the NEXT block (its nodes: the post-state's)
+    posts = new_payload_chain(text, parent_state_root, [(accounts_after, header_state_root), ...])  # k blocks, one witness
 """
 from __future__ import annotations
 
@@ -264,8 +267,8 @@ class PostState:
         return self.n_failed == 0
 
 
-def _poststate_arrays(self, ctx: Context | None, parent_root: bytes, writes: dict) -> dict:
-    """The raw call.  writes: account_op (n_accounts, POST_KEEP / POST_SET / POST_DELETE), nonces, balances (n x 32), code_hashes
+def _poststate_arrays(self, ctx: Context | None, parent_root: bytes, writes: dict, advance: int | None = None):
+    """The raw call (advance = the flags of phant_exec_witness_advance: that call instead, -> (dict, next witness or None)).  writes: account_op (n_accounts, POST_KEEP / POST_SET / POST_DELETE), nonces, balances (n x 32), code_hashes
     (n x 32) -- read where op == SET --, slot_write (n_slots, or None) and slot_vals (n_slots x 32), all in witness order."""
     ctx = ctx or default_context()
     if parent_root is None or len(parent_root) != 32:
@@ -294,9 +297,16 @@ def _poststate_arrays(self, ctx: Context | None, parent_root: bytes, writes: dic
     for k, a in outs.items():
         setattr(o, k, a.ctypes.data)
     root = C.create_string_buffer(bytes(parent_root), 32)
-    ctx.check(self._lib.phant_exec_witness_poststate(ctx.handle, self._h, root, C.byref(o)))
-    return {"state_root": outs["state_root"].tobytes(), "storage_roots": outs["storage_roots"][:na],
-            "account_status": outs["account_status"][:na], "slot_status": outs["slot_status"][:ns], "n_failed": int(o.n_failed)}
+    nxt = None
+    if advance is None:
+        ctx.check(self._lib.phant_exec_witness_poststate(ctx.handle, self._h, root, C.byref(o)))
+    else:
+        h = C.c_void_p()
+        ctx.check(self._lib.phant_exec_witness_advance(ctx.handle, self._h, root, C.byref(o), int(advance), C.byref(h)))
+        nxt = StatelessWitness(h) if h.value else None
+    out = {"state_root": outs["state_root"].tobytes(), "storage_roots": outs["storage_roots"][:na],
+           "account_status": outs["account_status"][:na], "slot_status": outs["slot_status"][:ns], "n_failed": int(o.n_failed)}
+    return out if advance is None else (out, nxt)
 
 
 def writes_of(info: dict, accounts_after: dict, ctx: Context | None = None) -> dict:
@@ -336,8 +346,24 @@ def _poststate(self, ctx: Context | None, parent_root: bytes, accounts_after: di
                      slot_status=r["slot_status"], n_failed=r["n_failed"])
 
 
+def _advance_arrays(self, ctx: Context | None, parent_root: bytes, writes: dict, keep_old: bool = False):
+    """phant_exec_witness_advance, raw: poststate_arrays' dict and the witness of the next block (None when the call failed)."""
+    return _poststate_arrays(self, ctx, parent_root, writes, L.ADVANCE_KEEP_OLD if keep_old else 0)
+
+
+def _advance(self, ctx: Context | None, parent_root: bytes, accounts_after: dict, keep_old: bool = False):
+    """-> (PostState, StatelessWitness | None): the post-state of the block and the witness to check the NEXT block with -- the
+    same keys and codes over the nodes of the post-state (keep_old: this witness's own nodes behind them, which carries the
+    siblings a producer shipped for later removals).  None when a proof failed; the caller closes the witness it gets."""
+    r, nxt = self.advance_arrays(ctx, parent_root, writes_of(self.info(), accounts_after, ctx), keep_old)
+    return PostState(root=r["state_root"], storage_roots=r["storage_roots"], account_status=r["account_status"],
+                     slot_status=r["slot_status"], n_failed=r["n_failed"]), nxt
+
+
 StatelessWitness.poststate_arrays = _poststate_arrays
 StatelessWitness.poststate = _poststate
+StatelessWitness.advance_arrays = _advance_arrays
+StatelessWitness.advance = _advance
 
 
 def new_payload_poststate(witness_json: str | bytes, parent_state_root: bytes, accounts_after: dict, header_state_root: bytes,
@@ -355,3 +381,28 @@ def new_payload_poststate(witness_json: str | bytes, parent_state_root: bytes, a
     if post.root != bytes(header_state_root):
         raise PoststateError(f"state root after the block is {post.root.hex()}, the header says {bytes(header_state_root).hex()}", post)
     return post
+
+
+def new_payload_chain(witness_json: str | bytes, parent_state_root: bytes, blocks, ctx: Context | None = None) -> list:
+    """k payloads under ONE witness: the document covers the keys of all of `blocks` -- a list of (accounts_after,
+    header_state_root), as new_payload_poststate takes them -- and is proven against parent_state_root, the root before the first.
+    Every block is checked against the witness the block before it left (StatelessWitness.advance with keep_old, so that siblings
+    shipped for a later block's removals stay).  -> the PostState of every block; PoststateError at the first block that fails or
+    whose root is not its header's."""
+    w = StatelessWitness.parse_json(witness_json)
+    out, root = [], bytes(parent_state_root)
+    try:
+        for n, (accounts_after, header_root) in enumerate(blocks):
+            post, nxt = w.advance(ctx, root, accounts_after, keep_old=True)
+            w.close()
+            w = nxt
+            if not post.ok or w is None:
+                raise PoststateError(f"block {n}: {post.n_failed} keys failed (proofs, or nodes missing for the new root)", post)
+            if post.root != bytes(header_root):
+                raise PoststateError(f"block {n}: state root after the block is {post.root.hex()}, the header says {bytes(header_root).hex()}", post)
+            out.append(post)
+            root = post.root
+    finally:
+        if w is not None:
+            w.close()
+    return out

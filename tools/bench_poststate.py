@@ -6,6 +6,8 @@ shuffled, every key); the block writes 60 % of the keys, one write in ten a remo
   poststate_device_ms  phant_timing's region of the call: the pre-state's node-set kernels and the post-state passes behind them
   prestate_device_ms   phant_exec_witness_prestate on the same document (without codes: the post-state call hashes none)
   oracle_state_root_ms the oracle's state_root over the FULL post-state on one core
+  advance_device_ms    phant_exec_witness_advance on the same document and writes: the same kernels with the sink behind node_ref
+                       (read against poststate_device_ms of the same run: advance_over_post), with the nodes and bytes it emitted
 Needs a GPU.  python tools/bench_poststate.py [--reps 20] [--warmup 3]
 """
 import argparse
@@ -82,6 +84,18 @@ def main():
 
     post_ms, got = measure(lambda: w.poststate_arrays(ctx, root, arrays))
     pre_ms, pre = measure(lambda: w.prestate_arrays(ctx, root))
+    emitted = {}
+
+    def advance():
+        out, nxt = w.advance_arrays(ctx, root, arrays)
+        if nxt is not None:
+            i = nxt.info()
+            emitted.update(nodes=int(i["total_nodes"]), bytes=int(i["nodes_len"]))
+            nxt.close()
+        return out
+
+    adv_ms, adv = measure(advance)
+    assert adv["n_failed"] == 0 and adv["state_root"] == got["state_root"] and emitted, "the benchmark witness must advance"
     after = Q.apply_writes(accounts, writes)
     t = []
     for _ in range(3):
@@ -93,7 +107,9 @@ def main():
     print(json.dumps({"bench": "exec_witness_poststate", "accounts": args.accounts, "slots": info["n_slots"], "nodes": info["total_nodes"],
                       "writes": n_writes, "removals": int(n_removed), "poststate_device_ms": round(post_ms, 4),
                       "prestate_device_ms": round(pre_ms, 4), "oracle_state_root_ms": round(float(np.median(t)), 3),
-                      "post_over_pre": round(post_ms / pre_ms, 2), "reps": args.reps}))
+                      "post_over_pre": round(post_ms / pre_ms, 2), "advance_device_ms": round(adv_ms, 4),
+                      "advance_over_post": round(adv_ms / post_ms, 3), "advance_nodes": emitted["nodes"],
+                      "advance_bytes": emitted["bytes"], "reps": args.reps}))
 
 
 if __name__ == "__main__":
