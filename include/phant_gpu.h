@@ -148,8 +148,8 @@ PHANT_API int32_t phant_logs_bloom_dev(phant_ctx *ctx, const uint8_t *d_items, c
                                        uint32_t n_receipts, uint8_t *d_blooms);
 /* Sender addresses -- the hashing half of src/signer/signer.zig:77-78 `keccak256(pubkey[1..])[12..]` for a
  * block's recovered public keys: key i = 64 bytes at pubkeys + i * stride (stride >= 64; pass pk + 1 and
- * stride 65 for 0x04-tagged keys), out20 = n x 20 bytes.  (The recovery itself stays libsecp256k1's,
- * src/crypto/ecdsa.zig.)  Device form: d_out20 4-byte aligned.
+ * stride 65 for 0x04-tagged keys), out20 = n x 20 bytes.  (For keys recovered elsewhere; phant_ecrecover_batch
+ * below recovers and hashes in one launch.)  Device form: d_out20 4-byte aligned.
  *
  * Transaction hashes (src/types/transaction.zig:183-187,223-228,256-261 = keccak256 of the EIP-2718 bytes) and
  * code hashes (src/blockchain/vm.zig:284-298; keccak256("") is its `empty_hash`) are phant_keccak256_batch
@@ -158,6 +158,45 @@ PHANT_API int32_t phant_sender_addresses(phant_ctx *ctx, const uint8_t *pubkeys,
                                          uint32_t n, uint8_t *out20);
 PHANT_API int32_t phant_sender_addresses_dev(phant_ctx *ctx, const uint8_t *d_pubkeys, uint64_t stride,
                                              uint32_t n, uint8_t *d_out20);
+
+/* ------------------------------------------------- sender recovery (secp256k1)
+ * src/signer/signer.zig:40-79 `get_sender` / src/crypto/ecdsa.zig:19-21 `erecover` for a block's transactions in one
+ * launch: one lane per signature does SEC 1 section 4.1.6 and hashes the key it found.  Status byte per item: */
+#define PHANT_SIG_OK 0
+#define PHANT_SIG_BAD_RANGE 1     /* r or s is 0 or >= n */
+#define PHANT_SIG_HIGH_S 2        /* PHANT_RECOVER_LOW_S: s > n / 2 */
+#define PHANT_SIG_BAD_RECID 3     /* recid > 3, or r + n (recid & 2) is no field element */
+#define PHANT_SIG_NOT_ON_CURVE 4  /* no curve point has that x */
+#define PHANT_SIG_INFINITY 5      /* the recovered key is the point at infinity */
+#define PHANT_SIG_BAD_TX 6        /* phant_tx_senders: undecodable, non-canonical or unknown transaction type */
+#define PHANT_SIG_BAD_V 7         /* phant_tx_senders: v is neither 27 / 28 nor 35 + 2 chain_id + {0, 1}; y_parity > 1 */
+#define PHANT_RECOVER_LOW_S 1u    /* src/crypto/ecdsa.zig:28-36 validateSignatureFields: reject s > n / 2 */
+/* hashes, r, s: n x 32 bytes, big-endian; recid: n bytes.  The checks run in this order, so a tuple that is wrong in two
+ * ways has ONE status: recid > 3 -> BAD_RECID; r == 0, r >= n, s == 0 or s >= n -> BAD_RANGE; with PHANT_RECOVER_LOW_S,
+ * s > n / 2 -> HIGH_S; x = r + (recid & 2 ? n : 0), x >= p -> BAD_RECID; x on no curve point -> NOT_ON_CURVE; y's parity =
+ * recid & 1; Q = (-z / r) G + (s / r) R; Q at infinity -> INFINITY; else OK.  pubkeys64 (n x 64 bytes, x || y big-endian),
+ * addresses20 (n x 20 bytes) and status (n bytes) may each be NULL, not all three; a failed item's outputs are zeroed.
+ * n == 0 is PHANT_OK.  NULL inputs with n > 0 or unknown flag bits: PHANT_E_INVALID_ARG.  Device form: every array is
+ * device memory (no alignment asked), nothing is synchronised; the first call on a context also computes the context's
+ * table of multiples of G (one 16 KiB allocation and one launch). */
+PHANT_API int32_t phant_ecrecover_batch(phant_ctx *ctx, const uint8_t *hashes, const uint8_t *r, const uint8_t *s,
+                                        const uint8_t *recid, uint32_t n, uint32_t flags, uint8_t *pubkeys64,
+                                        uint8_t *addresses20, uint8_t *status);
+PHANT_API int32_t phant_ecrecover_batch_dev(phant_ctx *ctx, const uint8_t *d_hashes, const uint8_t *d_r,
+                                            const uint8_t *d_s, const uint8_t *d_recid, uint32_t n, uint32_t flags,
+                                            uint8_t *d_pubkeys64, uint8_t *d_addresses20, uint8_t *d_status);
+/* `get_sender` for raw transactions: transaction i = txs[tx_off[i] .. tx_off[i+1]), a legacy RLP list, 0x01 || rlp or
+ * 0x02 || rlp.  One call, one synchronisation: the host decodes each transaction strictly (canonical RLP, the field count
+ * of its type, integers without leading zeros and within their width, `to` empty or 20 bytes, a well-formed access list;
+ * anything else, or another type byte: BAD_TX) and builds its signing preimage by putting the item bytes, verbatim and
+ * without v / r / s, under a new list header (EIP-155: followed by chain_id, 0, 0); the device hashes the preimages and
+ * recovers with PHANT_RECOVER_LOW_S.  Legacy v: 27 / 28 -> the pre-EIP-155 preimage; 35 + 2 chain_id + {0, 1} -> the
+ * EIP-155 preimage; anything else BAD_V (signer.zig:52-59).  Typed: recid = y_parity, > 1 -> BAD_V.
+ * ONE DEVIATION from the reference: signer.zig:87 hashes every legacy transaction with the EIP-155 preimage whenever
+ * the signer's chain id is non-zero, also for v = 27 / 28; this call hashes what was signed.
+ * addresses20 (n x 20) or status (n) may be NULL, not both; a failed item's address is zeroed. */
+PHANT_API int32_t phant_tx_senders(phant_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, uint32_t n,
+                                   uint64_t chain_id, uint8_t *addresses20, uint8_t *status);
 
 /* ------------------------------------------------------- proof verification
  * ABSENT in the reference: this is the call the TODO at

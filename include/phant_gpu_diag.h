@@ -62,6 +62,16 @@ PHANT_API int32_t phant_keccak_rate(phant_ctx *ctx, uint32_t waves_per_simd, uin
 PHANT_API int32_t phant_nodeset_tune(phant_ctx *ctx, int32_t form, uint32_t order, uint32_t hash_lds_bytes,
                                      uint32_t resident_wgs);
 
+/* One primitive of the secp256k1 arithmetic (phant_amd/csrc/secp256k1.hip.h) per lane, host arrays in and out, so that a carry
+ * bug shows at the primitive and not as a wrong address 3 000 multiplications later.  Numbers are 32 big-endian bytes.
+ *   op 0 field mul, 1 field sqr, 2 field inverse (0 -> 0), 4 scalar mul, 5 scalar inverse: rows of 32 bytes in a (and b for
+ *        0 and 4; b is ignored otherwise), 32 out.  The field ops take ANY 256-bit operands, the scalar ops too.
+ *   op 3 field square root: 32 in, 33 out: x^((p+1)/4), then 1 if that is a root of x, else 0.
+ *   op 6 point double, 7 point add (the general formula), 8 point add (the formula for an affine second operand): rows of 65
+ *        bytes, x || y || flag (flag != 0: the point at infinity, x and y ignored; else x, y < p on the curve), 65 out. */
+#define PHANT_DIAG_SECP_OPS 9
+PHANT_API int32_t phant_diag_secp_op(phant_ctx *ctx, uint32_t op, const uint8_t *a, const uint8_t *b, uint32_t n, uint8_t *out);
+
 /* Per-ctx switches of measured alternatives and test hooks (phant_diag_set(ctx, knob, value)).  The library's defaults are what
  * the measurements in profiles/ chose; nothing here changes a result, only how it is computed. */
 enum {

@@ -40,6 +40,8 @@ POST_KEEP, POST_SET, POST_DELETE = 0, 1, 2
 PROVE_MAY_REMOVE = 1
 ADVANCE_KEEP_OLD = 1
 CODE_NONE = 0xFFFFFFFF
+SIG_OK, SIG_BAD_RANGE, SIG_HIGH_S, SIG_BAD_RECID, SIG_NOT_ON_CURVE, SIG_INFINITY, SIG_BAD_TX, SIG_BAD_V = range(8)
+RECOVER_LOW_S = 1
 
 # every symbol include/phant_gpu.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
@@ -60,6 +62,10 @@ SYMBOLS = {
     "phant_logs_bloom_dev": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_sender_addresses": (_i32, [_vp, _vp, _u64, _u32, _vp]),
     "phant_sender_addresses_dev": (_i32, [_vp, _vp, _u64, _u32, _vp]),
+    "phant_ecrecover_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "phant_ecrecover_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "phant_tx_senders": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp]),
+    "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_verify_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_mpt_verify_batch_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
                                           _vp, _vp]),

@@ -7,10 +7,13 @@
 //   sender address  src/signer/signer.zig:77-78  one lane per 64-byte public key: the last 20 digest bytes
 //
 // Transaction hashes (src/types/transaction.zig:183-187,223-228,256-261: keccak256 of the EIP-2718 bytes) and
+//   sender recovery  src/signer/signer.zig:40-79 / src/crypto/ecdsa.zig:19-21  one lane per signature: the public key
+//                   (secp256k1.hip.h), hashed while it is in registers
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
 #include "launch.h"
+#include "secp256k1.hip.h"
 
 namespace phant {
 
@@ -54,6 +57,111 @@ sender_address_kernel(const uint8_t* __restrict__ pubkeys, uint64_t stride, uint
     o[2] = s.hi[2];
     o[3] = s.lo[3];
     o[4] = s.hi[3];
+}
+
+// ---- secp256k1 (secp256k1.hip.h) ----
+// entry j of the table = j G, affine, as 16 little-endian limbs; one lane per entry, once per context
+__global__ void __launch_bounds__(64)
+secp_gtable_kernel(uint32_t* __restrict__ gtable) {
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= secp::GTABLE_ENTRIES) return;
+    uint32_t* e = gtable + 16u * j;
+    if (j == 0) {
+        for (int i = 0; i < 16; ++i) e[i] = 0u;
+        return;
+    }
+    const secp::Jac g = secp::jac_from_affine(secp::const_gx(), secp::const_gy());
+    secp::Jac acc = secp::jac_infinity();
+    for (int bit = 7; bit >= 0; --bit) {
+        acc = secp::jac_double(acc);
+        if ((j >> bit) & 1u) acc = secp::jac_add(acc, g, true);
+    }
+    secp::U256 x, y;
+    secp::jac_to_affine(acc, x, y);
+    for (int i = 0; i < 8; ++i) e[i] = x.v[i], e[8 + i] = y.v[i];
+}
+
+// One lane per signature.  pre_status (may be null): a non-zero byte is the lane's verdict already (phant_tx_senders: a
+// transaction the host could not decode).  A lane that fails leaves zeroed outputs.  Rows are read and written byte by byte: no
+// alignment is asked of any array.
+__global__ void __launch_bounds__(64)
+ecrecover_kernel(const uint8_t* __restrict__ hashes, const uint8_t* __restrict__ r, const uint8_t* __restrict__ s,
+                 const uint8_t* __restrict__ recid, const uint8_t* __restrict__ pre_status, uint32_t n, uint32_t flags,
+                 const uint32_t* __restrict__ gtable, uint8_t* __restrict__ pubkeys, uint8_t* __restrict__ addresses,
+                 uint8_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    uint8_t st = pre_status ? pre_status[i] : secp::SIG_OK;
+    secp::U256 qx = secp::u256_zero(), qy = secp::u256_zero();
+    if (st == secp::SIG_OK) {
+        st = secp::recover(secp::load_be32(hashes + 32ull * i), secp::load_be32(r + 32ull * i), secp::load_be32(s + 32ull * i),
+                           recid[i], flags, gtable, qx, qy);
+        if (st != secp::SIG_OK) qx = secp::u256_zero(), qy = secp::u256_zero();
+    }
+    if (status) status[i] = st;
+    if (pubkeys) {
+        secp::store_be32(pubkeys + 64ull * i, qx);
+        secp::store_be32(pubkeys + 64ull * i + 32, qy);
+    }
+    if (addresses) {
+        uint8_t* a = addresses + 20ull * i;
+        if (st != secp::SIG_OK) {
+            for (int k = 0; k < 20; ++k) a[k] = 0;
+        } else {
+            Sponge sp;
+            secp::pubkey_digest(sp, qx, qy);
+            const uint32_t w[5] = {sp.hi[1], sp.lo[2], sp.hi[2], sp.lo[3], sp.hi[3]};  // digest bytes 12..31
+            for (int k = 0; k < 20; ++k) a[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+}
+
+// phant_diag_secp_op (include/phant_gpu_diag.h): one primitive per lane.  A point row is x || y || flag (65 bytes); the point
+// operations lift their affine inputs to Jacobian coordinates with Z = 3 (and Z = 2 for the second operand of the general
+// addition), so that the formulas see the denominators they see in the ladder.
+PHANT_DEV secp::Jac diag_point(const uint8_t* __restrict__ row, uint32_t z) {
+    if (row[64]) return secp::jac_infinity();
+    const secp::U256 zz = secp::u256_small(z * z), zzz = secp::u256_small(z * z * z);
+    secp::Jac p;
+    p.x = secp::fe_mul(secp::load_be32(row), zz);
+    p.y = secp::fe_mul(secp::load_be32(row + 32), zzz);
+    p.z = secp::u256_small(z);
+    return p;
+}
+
+__global__ void __launch_bounds__(64)
+secp_op_kernel(uint32_t op, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint32_t n, uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    if (op <= 5u) {
+        const secp::U256 x = secp::load_be32(a + 32ull * i);
+        const secp::U256 y = (op == 0u || op == 4u) ? secp::load_be32(b + 32ull * i) : x;
+        secp::U256 res;
+        if (op == 0u) res = secp::fe_mul(x, y);
+        else if (op == 1u) res = secp::fe_sqr(x);
+        else if (op == 2u) res = secp::fe_inv(x);
+        else if (op == 3u) {
+            const bool sq = secp::fe_sqrt(res, x);
+            out[33ull * i + 32] = sq ? 1 : 0;
+            secp::store_be32(out + 33ull * i, res);
+            return;
+        } else if (op == 4u) res = secp::sc_mul(x, y);
+        else res = secp::sc_inv(x);
+        secp::store_be32(out + 32ull * i, res);
+        return;
+    }
+    const secp::Jac p = diag_point(a + 65ull * i, 3u);
+    secp::Jac q;
+    if (op == 6u) q = secp::jac_double(p);
+    else if (op == 7u) q = secp::jac_add(p, diag_point(b + 65ull * i, 2u), false);
+    else q = b[65ull * i + 64] ? p : secp::jac_add(p, diag_point(b + 65ull * i, 1u), true);  // (the mixed form takes no infinity)
+    uint8_t* o = out + 65ull * i;
+    secp::U256 x = secp::u256_zero(), y = secp::u256_zero();
+    const bool inf = secp::jac_is_infinity(q);
+    if (!inf) secp::jac_to_affine(q, x, y);
+    secp::store_be32(o, x);
+    secp::store_be32(o + 32, y);
+    o[64] = inf ? 1 : 0;
 }
 
 // ---- a witness in its "index" form (witness.h): the proof nodes' hex digits still sit in the JSON text ----
@@ -130,6 +238,26 @@ hipError_t launch_sender_addresses(const uint8_t* d_pubkeys, uint64_t stride, ui
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(sender_address_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, d_pubkeys, stride, n,
                        reinterpret_cast<uint32_t*>(d_out));
+    return hipGetLastError();
+}
+
+hipError_t launch_secp_gtable(uint32_t* d_gtable, hipStream_t st) {
+    hipLaunchKernelGGL(secp_gtable_kernel, dim3(secp::GTABLE_ENTRIES / 64u), dim3(64), 0, st, d_gtable);
+    return hipGetLastError();
+}
+
+hipError_t launch_ecrecover(const uint8_t* d_hashes, const uint8_t* d_r, const uint8_t* d_s, const uint8_t* d_recid,
+                            const uint8_t* d_pre_status, uint32_t n, uint32_t flags, const uint32_t* d_gtable,
+                            uint8_t* d_pubkeys, uint8_t* d_addresses, uint8_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(ecrecover_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, d_hashes, d_r, d_s, d_recid, d_pre_status, n,
+                       flags, d_gtable, d_pubkeys, d_addresses, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, uint32_t n, uint8_t* d_out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(secp_op_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, op, d_a, d_b, n, d_out);
     return hipGetLastError();
 }
 

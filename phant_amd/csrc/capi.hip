@@ -76,6 +76,7 @@ struct phant_ctx {
     uint32_t code_form = 0;
     bool post_raw_slot_keys = false;  // PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS
     uint64_t advance_estimate = 0;    // PHANT_DIAG_ADVANCE_ESTIMATE_BYTES (0: the call's own estimate)
+    uint32_t* secp_gtable = nullptr;  // phant_ecrecover_batch: 1 G .. 255 G, computed on the device by the first call that needs it
 };
 
 namespace {
@@ -228,6 +229,7 @@ void phant_ctx_destroy(phant_ctx* c) {
     c->ws.release();
     c->dv.release();
     c->ns.dv.release();
+    if (c->secp_gtable) (void)hipFree(c->secp_gtable);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->kev)
@@ -601,6 +603,143 @@ int32_t phant_sender_addresses(phant_ctx* c, const uint8_t* pubkeys, uint64_t st
     }
     HIP_TRY(c, phant::launch_sender_addresses(d_pk, 64, n, d_out, c->stream));
     HIP_TRY(c, hipMemcpyAsync(out20, d_out, (size_t)n * 20, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PHANT_OK;
+}
+
+/* --------------------------------------------------------- sender recovery */
+
+// the context's table of multiples of G: allocated and computed (on the ctx stream, in front of the launch that reads it)
+// by the first call that needs it
+static int32_t ensure_gtable(phant_ctx* c) {
+    if (c->secp_gtable) return PHANT_OK;
+    uint32_t* t = nullptr;
+    hipError_t e = hipMalloc((void**)&t, (size_t)phant::SECP_GTABLE_BYTES);
+    if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(secp256k1 table)", e);
+    e = phant::launch_secp_gtable(t, c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(t);
+        return fail(c, PHANT_E_DEVICE, "launch_secp_gtable", e);
+    }
+    c->secp_gtable = t;
+    return PHANT_OK;
+}
+
+int32_t phant_ecrecover_batch_dev(phant_ctx* c, const uint8_t* d_hashes, const uint8_t* d_r, const uint8_t* d_s,
+                                  const uint8_t* d_recid, uint32_t n, uint32_t flags, uint8_t* d_pubkeys64,
+                                  uint8_t* d_addresses20, uint8_t* d_status) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (flags & ~PHANT_RECOVER_LOW_S) return fail(c, PHANT_E_INVALID_ARG, "ecrecover_batch_dev: unknown flag");
+    if (!d_pubkeys64 && !d_addresses20 && !d_status) return fail(c, PHANT_E_INVALID_ARG, "ecrecover_batch_dev: no output");
+    if (n == 0) return PHANT_OK;
+    if (!d_hashes || !d_r || !d_s || !d_recid) return fail(c, PHANT_E_INVALID_ARG, "ecrecover_batch_dev: null input");
+    DeviceGuard g(c->device);
+    if (const int32_t rc = ensure_gtable(c)) return rc;
+    TimedRegion t(c);
+    HIP_TRY(c, phant::launch_ecrecover(d_hashes, d_r, d_s, d_recid, nullptr, n, flags, c->secp_gtable, d_pubkeys64, d_addresses20,
+                                       d_status, c->stream));
+    return PHANT_OK;
+}
+
+int32_t phant_ecrecover_batch(phant_ctx* c, const uint8_t* hashes, const uint8_t* r, const uint8_t* s, const uint8_t* recid,
+                              uint32_t n, uint32_t flags, uint8_t* pubkeys64, uint8_t* addresses20, uint8_t* status) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (flags & ~PHANT_RECOVER_LOW_S) return fail(c, PHANT_E_INVALID_ARG, "ecrecover_batch: unknown flag");
+    if (!pubkeys64 && !addresses20 && !status) return fail(c, PHANT_E_INVALID_ARG, "ecrecover_batch: no output");
+    if (n == 0) return PHANT_OK;
+    if (!hashes || !r || !s || !recid) return fail(c, PHANT_E_INVALID_ARG, "ecrecover_batch: null input");
+    DeviceGuard g(c->device);
+    if (const int32_t rc = ensure_gtable(c)) return rc;
+    uint8_t *d_h = nullptr, *d_r = nullptr, *d_s = nullptr, *d_id = nullptr, *d_pk = nullptr, *d_ad = nullptr, *d_st = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        d_h = io.template take<uint8_t>((size_t)n * 32);
+        d_r = io.template take<uint8_t>((size_t)n * 32);
+        d_s = io.template take<uint8_t>((size_t)n * 32);
+        d_id = io.template take<uint8_t>(n);
+        if (pubkeys64) d_pk = io.template take<uint8_t>((size_t)n * 64);
+        if (addresses20) d_ad = io.template take<uint8_t>((size_t)n * 20);
+        if (status) d_st = io.template take<uint8_t>(n);
+    });
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_h, hashes, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_r, r, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_s, s, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_id, recid, n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, phant::launch_ecrecover(d_h, d_r, d_s, d_id, nullptr, n, flags, c->secp_gtable, d_pk, d_ad, d_st, c->stream));
+    if (pubkeys64) HIP_TRY(c, hipMemcpyAsync(pubkeys64, d_pk, (size_t)n * 64, hipMemcpyDeviceToHost, c->stream));
+    if (addresses20) HIP_TRY(c, hipMemcpyAsync(addresses20, d_ad, (size_t)n * 20, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIP_TRY(c, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PHANT_OK;
+}
+
+int32_t phant_tx_senders(phant_ctx* c, const uint8_t* txs, const uint64_t* tx_off, uint32_t n, uint64_t chain_id,
+                         uint8_t* addresses20, uint8_t* status) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!addresses20 && !status) return fail(c, PHANT_E_INVALID_ARG, "tx_senders: no output");
+    if (n == 0) return PHANT_OK;
+    if (!tx_off) return fail(c, PHANT_E_INVALID_ARG, "tx_senders: null offsets");
+    for (uint32_t i = 0; i < n; ++i)
+        if (tx_off[i + 1] < tx_off[i]) return fail(c, PHANT_E_INVALID_ARG, "tx_senders: offsets not monotone");
+    if (tx_off[n] != tx_off[0] && !txs) return fail(c, PHANT_E_INVALID_ARG, "tx_senders: null transactions");
+    // host: decode, split off the signature, splice the preimages (one blob, hashed by the variable-length Keccak launch)
+    std::vector<uint8_t> pre, rs((size_t)n * 64), ids((size_t)n * 2);  // rs: all r, then all s; ids: all recid, then the host's verdicts
+    std::vector<uint64_t> off((size_t)n + 1);
+    uint8_t *r = rs.data(), *s = rs.data() + (size_t)n * 32, *recid = ids.data(), *pre_st = ids.data() + n;
+    for (uint32_t i = 0; i < n; ++i) {
+        off[i] = pre.size();
+        recid[i] = 0;
+        pre_st[i] = phant::tx_signing_parts(txs + tx_off[i], (size_t)(tx_off[i + 1] - tx_off[i]), chain_id, pre, r + 32 * (size_t)i,
+                                            s + 32 * (size_t)i, recid + i);
+    }
+    off[n] = pre.size();
+    DeviceGuard g(c->device);
+    if (const int32_t rc = ensure_gtable(c)) return rc;
+    uint8_t *d_pre = nullptr, *d_h = nullptr, *d_rs = nullptr, *d_ids = nullptr, *d_ad = nullptr, *d_st = nullptr;
+    uint64_t* d_off = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        d_pre = io.template take<uint8_t>(pre.size() + 16);
+        d_off = io.template take<uint64_t>((size_t)n + 1);
+        d_h = io.template take<uint8_t>((size_t)n * 32);
+        d_rs = io.template take<uint8_t>((size_t)n * 64);
+        d_ids = io.template take<uint8_t>((size_t)n * 2);
+        if (addresses20) d_ad = io.template take<uint8_t>((size_t)n * 20);
+        if (status) d_st = io.template take<uint8_t>(n);
+    });
+    if (rc) return rc;
+    if (!pre.empty()) HIP_TRY(c, hipMemcpyAsync(d_pre, pre.data(), pre.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_rs, rs.data(), rs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_ids, ids.data(), ids.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, phant::launch_keccak256_var(d_pre, d_off, n, d_h, c->stream));
+    const uint32_t low_s = PHANT_RECOVER_LOW_S;  // validateSignatureFields
+    HIP_TRY(c, phant::launch_ecrecover(d_h, d_rs, d_rs + (size_t)n * 32, d_ids, d_ids + n, n, low_s, c->secp_gtable,
+                                       nullptr, d_ad, d_st, c->stream));
+    if (addresses20) HIP_TRY(c, hipMemcpyAsync(addresses20, d_ad, (size_t)n * 20, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIP_TRY(c, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the host vectors above live until here)
+    return PHANT_OK;
+}
+
+int32_t phant_diag_secp_op(phant_ctx* c, uint32_t op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (op >= PHANT_DIAG_SECP_OPS) return fail(c, PHANT_E_INVALID_ARG, "diag_secp_op: unknown op");
+    if (n == 0) return PHANT_OK;
+    const bool two = op == 0 || op == 4 || op == 7 || op == 8;
+    if (!a || !out || (two && !b)) return fail(c, PHANT_E_INVALID_ARG, "diag_secp_op: null pointer");
+    const size_t in_row = op >= 6 ? 65 : 32, out_row = op >= 6 ? 65 : op == 3 ? 33 : 32;
+    DeviceGuard g(c->device);
+    uint8_t *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        d_a = io.template take<uint8_t>(n * in_row);
+        d_b = io.template take<uint8_t>(n * in_row);
+        d_out = io.template take<uint8_t>(n * out_row);
+    });
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_a, a, n * in_row, hipMemcpyHostToDevice, c->stream));
+    if (two) HIP_TRY(c, hipMemcpyAsync(d_b, b, n * in_row, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, phant::launch_secp_op(op, d_a, d_b, n, d_out, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, n * out_row, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PHANT_OK;
 }

@@ -172,4 +172,148 @@ int32_t strip_first_nibble(const uint8_t* node, uint32_t len, uint8_t* out, uint
     return PHANT_OK;
 }
 
+// ---- transactions (src/types/transaction.zig, src/signer/signer.zig:81-188) ----
+namespace {
+
+struct TxItem {
+    const uint8_t* full;  // the item with its header
+    size_t total;
+    const uint8_t* pay;
+    size_t len;
+    bool is_list;
+};
+
+// a big-endian integer of at most `max_bytes` bytes without a leading zero
+bool tx_uint(const TxItem& it, size_t max_bytes) { return !it.is_list && it.len <= max_bytes && (it.len == 0 || it.pay[0] != 0); }
+
+// [[address, [key, ...]], ...]
+bool tx_access_list(const TxItem& al) {
+    if (!al.is_list) return false;
+    const uint8_t* p = al.pay;
+    size_t left = al.len;
+    while (left) {
+        size_t pay, len, total;
+        bool is_list;
+        if (!host_rlp_item(p, left, pay, len, total, is_list) || !is_list) return false;
+        const uint8_t* q = p + pay;
+        size_t qleft = len, ip, il, it;
+        bool ilist;
+        if (!host_rlp_item(q, qleft, ip, il, it, ilist) || ilist || il != 20) return false;  // the address
+        q += it, qleft -= it;
+        if (!host_rlp_item(q, qleft, ip, il, it, ilist) || !ilist || it != qleft) return false;  // the keys, and nothing after
+        const uint8_t* k = q + ip;
+        size_t kleft = il;
+        while (kleft) {
+            size_t kp, kl, kt;
+            bool klist;
+            if (!host_rlp_item(k, kleft, kp, kl, kt, klist) || klist || kl != 32) return false;
+            k += kt, kleft -= kt;
+        }
+        p += total, left -= total;
+    }
+    return true;
+}
+
+void put_list_header(std::vector<uint8_t>& out, size_t len) {
+    if (len <= 55) {
+        out.push_back((uint8_t)(0xc0 + len));
+        return;
+    }
+    uint8_t be[8];
+    size_t ll = 0;
+    for (size_t l = len; l; l >>= 8) be[ll++] = (uint8_t)l;
+    out.push_back((uint8_t)(0xf7 + ll));
+    for (size_t q = 0; q < ll; ++q) out.push_back(be[ll - 1 - q]);
+}
+
+void pad32(uint8_t out[32], const TxItem& it) {
+    std::memset(out, 0, 32);
+    if (it.len) std::memcpy(out + 32 - it.len, it.pay, it.len);
+}
+
+}  // namespace
+
+uint8_t tx_signing_parts(const uint8_t* tx, size_t len, uint64_t chain_id, std::vector<uint8_t>& preimage, uint8_t r[32],
+                         uint8_t s[32], uint8_t* recid) {
+    if (!tx || len == 0) return PHANT_SIG_BAD_TX;
+    uint8_t type = 0;
+    if (tx[0] < 0x80) {  // EIP-2718: a type byte in front of the list
+        type = tx[0];
+        if (type != 1 && type != 2) return PHANT_SIG_BAD_TX;
+        ++tx, --len;
+    }
+    size_t pay, plen, total;
+    bool is_list;
+    if (!host_rlp_item(tx, len, pay, plen, total, is_list) || !is_list || total != len) return PHANT_SIG_BAD_TX;
+    const size_t want = type == 0 ? 9 : type == 1 ? 11 : 12;
+    TxItem it[12];
+    size_t count = 0;
+    const uint8_t* p = tx + pay;
+    size_t left = plen;
+    while (left) {
+        size_t ip, il, tot;
+        bool ilist;
+        if (count == want || !host_rlp_item(p, left, ip, il, tot, ilist)) return PHANT_SIG_BAD_TX;
+        it[count++] = TxItem{p, tot, p + ip, il, ilist};
+        p += tot, left -= tot;
+    }
+    if (count != want) return PHANT_SIG_BAD_TX;
+    // the fields of each type: widths as in src/types/transaction.zig; `to` empty (creation) or an address; data any string
+    size_t to_i, data_i;
+    if (type == 0) {  // nonce, gas_price, gas_limit, to, value, data, v, r, s
+        if (!tx_uint(it[0], 8) || !tx_uint(it[1], 32) || !tx_uint(it[2], 8) || !tx_uint(it[4], 32)) return PHANT_SIG_BAD_TX;
+        to_i = 3, data_i = 5;
+    } else if (type == 1) {  // chain_id, nonce, gas_price, gas, to, value, data, access_list, y_parity, r, s
+        if (!tx_uint(it[0], 8) || !tx_uint(it[1], 8) || !tx_uint(it[2], 32) || !tx_uint(it[3], 8) || !tx_uint(it[5], 32) ||
+            !tx_access_list(it[7]))
+            return PHANT_SIG_BAD_TX;
+        to_i = 4, data_i = 6;
+    } else {  // chain_id, nonce, max_priority_fee_per_gas, max_fee_per_gas, gas, to, value, data, access_list, y_parity, r, s
+        if (!tx_uint(it[0], 8) || !tx_uint(it[1], 8) || !tx_uint(it[2], 32) || !tx_uint(it[3], 32) || !tx_uint(it[4], 8) ||
+            !tx_uint(it[6], 32) || !tx_access_list(it[8]))
+            return PHANT_SIG_BAD_TX;
+        to_i = 5, data_i = 7;
+    }
+    if (it[to_i].is_list || (it[to_i].len != 0 && it[to_i].len != 20) || it[data_i].is_list) return PHANT_SIG_BAD_TX;
+    const TxItem &v = it[want - 3], &ri = it[want - 2], &si = it[want - 1];
+    if (!tx_uint(v, 32) || !tx_uint(ri, 32) || !tx_uint(si, 32)) return PHANT_SIG_BAD_TX;
+    // v: a value of more than 9 bytes matches nothing below (35 + 2 chain_id + 1 < 2^66)
+    unsigned __int128 vv = 0;
+    if (v.len > 9) return PHANT_SIG_BAD_V;
+    for (size_t k = 0; k < v.len; ++k) vv = vv << 8 | v.pay[k];
+    bool eip155 = false;
+    if (type == 0) {
+        const unsigned __int128 base = (unsigned __int128)35 + 2 * (unsigned __int128)chain_id;
+        if (vv == 27 || vv == 28) *recid = (uint8_t)(vv - 27);
+        else if (vv == base || vv == base + 1) *recid = (uint8_t)(vv - base), eip155 = true;
+        else return PHANT_SIG_BAD_V;
+    } else {
+        if (vv > 1) return PHANT_SIG_BAD_V;
+        *recid = (uint8_t)vv;
+    }
+    pad32(r, ri);
+    pad32(s, si);
+    // the signed list: the items in front of v, verbatim, (chain_id, 0, 0 for EIP-155,) under a header of their own
+    const size_t body = (size_t)(v.full - (tx + pay));
+    uint8_t tail[12];
+    size_t tail_len = 0;
+    if (eip155) {
+        uint8_t be[8];
+        size_t ll = 0;
+        for (uint64_t cid = chain_id; cid; cid >>= 8) be[ll++] = (uint8_t)cid;
+        if (ll == 1 && be[0] < 0x80) tail[tail_len++] = be[0];
+        else {
+            tail[tail_len++] = (uint8_t)(0x80 + ll);
+            for (size_t q = 0; q < ll; ++q) tail[tail_len++] = be[ll - 1 - q];
+        }
+        tail[tail_len++] = 0x80;
+        tail[tail_len++] = 0x80;
+    }
+    if (type) preimage.push_back(type);
+    put_list_header(preimage, body + tail_len);
+    preimage.insert(preimage.end(), tx + pay, tx + pay + body);
+    preimage.insert(preimage.end(), tail, tail + tail_len);
+    return PHANT_SIG_OK;
+}
+
 }  // namespace phant

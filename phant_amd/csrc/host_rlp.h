@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include <vector>
+
 #include "witness.h"
 
 namespace phant {
@@ -20,5 +22,10 @@ bool account_absent_consistent(const WitnessAccount& a);
 // phant_mpt_strip_first_nibble (include/phant_gpu.h): returns PHANT_OK / PHANT_E_*
 int32_t strip_first_nibble(const uint8_t* node, uint32_t len, uint8_t* out, uint32_t cap, uint32_t* out_len,
                            uint32_t* is_ref);
+
+// phant_tx_senders (include/phant_gpu.h): one raw transaction -> PHANT_SIG_OK with its signing preimage APPENDED to `preimage`,
+// r and s padded to 32 bytes and the recovery id, or PHANT_SIG_BAD_TX / PHANT_SIG_BAD_V (nothing appended).  Untrusted bytes in.
+uint8_t tx_signing_parts(const uint8_t* tx, size_t len, uint64_t chain_id, std::vector<uint8_t>& preimage, uint8_t r[32],
+                         uint8_t s[32], uint8_t* recid);
 
 }  // namespace phant

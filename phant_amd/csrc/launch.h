@@ -21,6 +21,15 @@ hipError_t launch_logs_bloom(const uint8_t* d_items, const uint64_t* d_item_off,
 hipError_t launch_sender_addresses(const uint8_t* d_pubkeys, uint64_t stride, uint32_t n, uint8_t* d_out,
                                    hipStream_t st);
 
+// secp256k1 (secp256k1.hip.h): the table of G's multiples (256 x 64 bytes), a lane per signature (rows of 32 / 1 bytes in, 64 /
+// 20 / 1 bytes out; d_pre_status, d_pubkeys, d_addresses, d_status may be null), and one arithmetic primitive per lane
+constexpr size_t SECP_GTABLE_BYTES = 256 * 64;
+hipError_t launch_secp_gtable(uint32_t* d_gtable, hipStream_t st);
+hipError_t launch_ecrecover(const uint8_t* d_hashes, const uint8_t* d_r, const uint8_t* d_s, const uint8_t* d_recid,
+                            const uint8_t* d_pre_status, uint32_t n, uint32_t flags, const uint32_t* d_gtable,
+                            uint8_t* d_pubkeys, uint8_t* d_addresses, uint8_t* d_status, hipStream_t st);
+hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, uint32_t n, uint8_t* d_out, hipStream_t st);
+
 // index-form witnesses: decode the nodes' hex digits out of the JSON text on the device (d_err: 2 dwords, [0] != 0
 // when some digit was not hex, [1] = the first such node), and compact the proven values for the host
 hipError_t launch_hex_decode(const uint8_t* d_json, const uint64_t* d_node_src, const uint64_t* d_node_off,
