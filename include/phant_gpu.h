@@ -159,6 +159,79 @@ PHANT_API int32_t phant_sender_addresses(phant_ctx *ctx, const uint8_t *pubkeys,
 PHANT_API int32_t phant_sender_addresses_dev(phant_ctx *ctx, const uint8_t *d_pubkeys, uint64_t stride,
                                              uint32_t n, uint8_t *d_out20);
 
+/* ------------------------------------------------- a block's receipts
+ * What src/blockchain/blockchain.zig:76-90 `runBlock` compares with the header once a block has executed, from the receipts'
+ * FIELDS in one call and one synchronisation: every receipt's bloom (receipt.zig:37-63), its encoding
+ *     [tx_type, when != 0] ++ rlp([status, cumulative_gas_used, bloom, [ [address, [topics...], data] ... ]])
+ * (receipt.zig:13-35; EIP-658: status 1 encodes as 0x01, 0 as 0x80; EIP-2718: the type byte in front -- the reference's
+ * Receipt.encode has no prefix yet, tx_type 0 reproduces it), the receipts root (calculateMPTRoot over the encodings, key
+ * rlp(index) as phant_index_root_rlp) and the block's logs bloom (the OR of all rows).  Nothing is encoded on the host.
+ *
+ * Input, struct-of-arrays: receipt i has tx_type[i] (0 = legacy, 1 .. 0x7f), status[i] (0 / 1), cum_gas[i] and the logs
+ * [log_first[i], log_first[i+1]); log l has address[20 l .. 20 l + 20), the topics [topic_first[l], topic_first[l+1]) of 32
+ * bytes each (any count) and the data bytes [data_off[l], data_off[l+1]).  log_first runs from 0 to n_logs, topic_first from
+ * 0 to n_topics, data_off from 0 to data_bytes.  An array whose count is zero may be NULL.
+ *
+ * Lists that ride along (optional): n_lists lists of already encoded items as in phant_block_roots (list l = lists[l][list_off
+ * [l][0] .. list_off[l][list_n[l]])), hashed in the SAME forest pass; receipts_at (<= n_lists) is the receipts' place among
+ * them.  roots_out = (n_lists + 1) x 32 bytes in that order: transactions, receipts and withdrawals give transactions_root,
+ * receipts_root and withdrawals_root from one call.  An empty list (or n_receipts == 0) gives mpt.zig:10 empty_mpt_root; no
+ * receipts give a zero bloom.
+ *
+ * Output, any pointer may be NULL (not wanted): receipts_root[32]; logs_bloom[256]; blooms = n_receipts x 256; roots_out;
+ * encoded / encoded_off = the encodings back to back in index order and their n_receipts + 1 offsets.  encoded_len is always
+ * written; if it exceeds encoded_cap, or n_receipts + 1 exceeds encoded_off_cap, the call still returns PHANT_OK and neither
+ * buffer is touched (a NULL buffer has no capacity to exceed): call again with the reported size.
+ *
+ * PHANT_E_INVALID_ARG: a wrong struct_size, a NULL array with a non-zero count, status > 1, tx_type > 0x7f, receipts_at >
+ * n_lists, offsets that go backwards or do not run from 0 to the stated totals.  PHANT_E_UNSUPPORTED: a receipt longer than
+ * 2^32 - 1 bytes, or more than 4 GiB of trie values in one call.  The host form checks before anything is copied.
+ *
+ * Device form: every array (and every list, with list_off[l] running from 0 to list_bytes[l]) is device memory, cum_gas /
+ * data_off / list_off[l] / encoded_off 8-byte and log_first / topic_first 4-byte aligned (kernels read and write them as
+ * words; the other outputs are copied as bytes and need no alignment); `lists`, `list_off`, `list_n`, `list_bytes` and both
+ * structs themselves are host memory.  The caller's
+ * offsets and flags are checked on the device before any kernel indexes with them.  Outputs stay in device memory; the call
+ * synchronises the ctx stream on the way (encoded_len is valid when it returns), the copies into the output buffers are in
+ * stream order behind it. */
+typedef struct phant_receipts_in {
+    uint32_t struct_size; /* = sizeof(phant_receipts_in) */
+    uint32_t n_receipts;
+    uint32_t n_logs;
+    uint32_t n_topics;
+    uint64_t data_bytes;
+    const uint8_t *tx_type;      /* n_receipts */
+    const uint8_t *status;       /* n_receipts */
+    const uint64_t *cum_gas;     /* n_receipts */
+    const uint32_t *log_first;   /* n_receipts + 1 */
+    const uint8_t *address;      /* n_logs x 20 */
+    const uint32_t *topic_first; /* n_logs + 1 */
+    const uint64_t *data_off;    /* n_logs + 1 */
+    const uint8_t *topics;       /* n_topics x 32 */
+    const uint8_t *data;         /* data_bytes */
+    const uint8_t *const *lists;     /* n_lists */
+    const uint64_t *const *list_off; /* n_lists, list_n[l] + 1 entries each */
+    const uint32_t *list_n;          /* n_lists */
+    const uint64_t *list_bytes;      /* n_lists; device form only */
+    uint32_t n_lists;
+    uint32_t receipts_at;
+} phant_receipts_in;
+typedef struct phant_receipts_out {
+    uint32_t struct_size;     /* = sizeof(phant_receipts_out) */
+    uint32_t encoded_off_cap; /* entries of encoded_off */
+    uint64_t encoded_cap;     /* bytes of encoded */
+    uint8_t *receipts_root;
+    uint8_t *logs_bloom;
+    uint8_t *blooms;
+    uint8_t *encoded;
+    uint64_t *encoded_off;
+    uint8_t *roots_out;
+    /* result */
+    uint64_t encoded_len;
+} phant_receipts_out;
+PHANT_API int32_t phant_block_receipts(phant_ctx *ctx, const phant_receipts_in *in, phant_receipts_out *out);
+PHANT_API int32_t phant_block_receipts_dev(phant_ctx *ctx, const phant_receipts_in *in, phant_receipts_out *out);
+
 /* ------------------------------------------------- sender recovery (secp256k1)
  * src/signer/signer.zig:40-79 `get_sender` / src/crypto/ecdsa.zig:19-21 `erecover` for a block's transactions in one
  * launch: one lane per signature does SEC 1 section 4.1.6 and hashes the key it found.  Status byte per item: */

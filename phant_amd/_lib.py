@@ -62,6 +62,8 @@ SYMBOLS = {
     "phant_logs_bloom_dev": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_sender_addresses": (_i32, [_vp, _vp, _u64, _u32, _vp]),
     "phant_sender_addresses_dev": (_i32, [_vp, _vp, _u64, _u32, _vp]),
+    "phant_block_receipts": (_i32, [_vp, _vp, _vp]),
+    "phant_block_receipts_dev": (_i32, [_vp, _vp, _vp]),
     "phant_ecrecover_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_ecrecover_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_tx_senders": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp]),
@@ -137,6 +139,22 @@ SYMBOLS = {
 
 class PhantOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("stream", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class PhantReceiptsIn(C.Structure):
+    """phant_receipts_in (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_receipts", C.c_uint32), ("n_logs", C.c_uint32), ("n_topics", C.c_uint32),
+                ("data_bytes", C.c_uint64), ("tx_type", C.c_void_p), ("status", C.c_void_p), ("cum_gas", C.c_void_p),
+                ("log_first", C.c_void_p), ("address", C.c_void_p), ("topic_first", C.c_void_p), ("data_off", C.c_void_p),
+                ("topics", C.c_void_p), ("data", C.c_void_p), ("lists", C.c_void_p), ("list_off", C.c_void_p),
+                ("list_n", C.c_void_p), ("list_bytes", C.c_void_p), ("n_lists", C.c_uint32), ("receipts_at", C.c_uint32)]
+
+
+class PhantReceiptsOut(C.Structure):
+    """phant_receipts_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("encoded_off_cap", C.c_uint32), ("encoded_cap", C.c_uint64),
+                ("receipts_root", C.c_void_p), ("logs_bloom", C.c_void_p), ("blooms", C.c_void_p), ("encoded", C.c_void_p),
+                ("encoded_off", C.c_void_p), ("roots_out", C.c_void_p), ("encoded_len", C.c_uint64)]
 
 
 class PhantProveOut(C.Structure):

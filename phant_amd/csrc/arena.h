@@ -109,6 +109,11 @@ struct Workspaces {
     // Coherent (fine-grained) whatever HIP_HOST_COHERENT says: the trie builder's host side reads what a kernel stored here
     // WHILE that kernel runs (order_kernel).
     static constexpr size_t MAILBOX_WORDS = 2048;
+    // Who owns which words: the trie builder and its prover everything below MAILBOX_RECEIPTS (trie_prove.hip.h asserts that
+    // they end in front of it), block_receipts the MAILBOX_RECEIPTS_WORDS behind it -- so the builder's passes, which rewrite
+    // their own window on every call, never touch the control words a receipts call has read or is about to read.
+    static constexpr size_t MAILBOX_RECEIPTS = 1536, MAILBOX_RECEIPTS_WORDS = 8;
+    static_assert(MAILBOX_RECEIPTS + MAILBOX_RECEIPTS_WORDS <= MAILBOX_WORDS, "the receipts' control words fit the pinned mailbox");
     uint32_t* mailbox = nullptr;
     hipError_t ensure_mailbox() {
         if (mailbox) return hipSuccess;

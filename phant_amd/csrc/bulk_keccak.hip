@@ -9,11 +9,14 @@
 // Transaction hashes (src/types/transaction.zig:183-187,223-228,256-261: keccak256 of the EIP-2718 bytes) and
 //   sender recovery  src/signer/signer.zig:40-79 / src/crypto/ecdsa.zig:19-21  one lane per signature: the public key
 //                   (secp256k1.hip.h), hashed while it is in registers
+//   receipts        src/types/receipt.zig:13-63 + src/blockchain/blockchain.zig:76-90  blooms, encodings, the block's bloom and
+//                   the receipts root of a block in one call (receipts.hip.h)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
 #include "launch.h"
 #include "secp256k1.hip.h"
+#include "receipts.hip.h"
 
 namespace phant {
 
@@ -28,20 +31,7 @@ logs_bloom_kernel(const uint8_t* __restrict__ items, const uint64_t* __restrict_
     const uint64_t b = item_off[k], e = item_off[k + 1];
     Sponge s;
     keccak256_global(s, items + b, e >= b ? e - b : 0, items + item_off[n_items]);
-    // digest bytes 0..5 = the three big-endian 16-bit words (receipt.zig:53-55); lo[0] holds bytes 0..3
-    // little-endian, hi[0] bytes 4..7
-    const uint32_t w0 = ((s.lo[0] & 0xffu) << 8) | ((s.lo[0] >> 8) & 0xffu);
-    const uint32_t w1 = (((s.lo[0] >> 16) & 0xffu) << 8) | (s.lo[0] >> 24);
-    const uint32_t w2 = ((s.hi[0] & 0xffu) << 8) | ((s.hi[0] >> 8) & 0xffu);
-    uint32_t* const bloom = blooms + 64ull * r;
-    const uint32_t w[3] = {w0, w1, w2};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const uint32_t bit_index = 0x07FFu - (w[i] & 0x07FFu);          // receipt.zig:56-57
-        const uint32_t byte_index = bit_index >> 3;
-        const uint32_t bit_value = 1u << (7u - (bit_index & 7u));       // receipt.zig:60
-        atomicOr(&bloom[byte_index >> 2], bit_value << (8u * (byte_index & 3u)));  // byte -> its dword, little-endian
-    }
+    bloom_add_digest(s, blooms + 64ull * r);  // (receipts.hip.h)
 }
 
 __global__ void __launch_bounds__(256)

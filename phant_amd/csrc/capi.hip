@@ -19,6 +19,7 @@
 #include "../../include/phant_gpu_diag.h"
 #include "arena.h"
 #include "launch.h"
+#include "receipts.h"
 #include "trie_build.h"
 #include "witness.h"
 #include "host_rlp.h"
@@ -606,6 +607,56 @@ int32_t phant_sender_addresses(phant_ctx* c, const uint8_t* pubkeys, uint64_t st
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PHANT_OK;
 }
+
+/* ------------------------------------------------- a block's receipts (receipts.hip.h) */
+
+static int32_t block_receipts_impl(phant_ctx* c, const phant_receipts_in* in, phant_receipts_out* out, bool dev) {
+    const char* const who = dev ? "block_receipts_dev" : "block_receipts";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_receipts_in) || out->struct_size != sizeof(phant_receipts_out)) return bad("wrong struct_size");
+    out->encoded_len = 0;
+    const uint32_t n = in->n_receipts, nl = in->n_logs;
+    if (n && (!in->tx_type || !in->status || !in->cum_gas || !in->log_first)) return bad("null receipt array");
+    if (nl && (!n || !in->address || !in->topic_first || !in->data_off)) return bad("null log array, or logs without receipts");
+    if ((in->n_topics && (!nl || !in->topics)) || (in->data_bytes && (!nl || !in->data))) return bad("null topics / data, or topics / data without logs");
+    if (in->receipts_at > in->n_lists) return bad("receipts_at > n_lists");
+    if (in->n_lists && (!in->lists || !in->list_off || !in->list_n || (dev && !in->list_bytes))) return bad("null list table");
+    for (uint32_t l = 0; l < in->n_lists; ++l)
+        if (in->list_n[l] && (!in->list_off[l] || (!in->lists[l] && (!dev || in->list_bytes[l])))) return bad("null list");
+    if (dev) {
+        // (what a kernel reads or writes as words; roots, rows and the block's bloom arrive by device-to-device copies of bytes)
+        bool mis = ((uintptr_t)in->cum_gas & 7u) || ((uintptr_t)in->data_off & 7u) || ((uintptr_t)out->encoded_off & 7u) || ((uintptr_t)in->log_first & 3u) ||
+                   ((uintptr_t)in->topic_first & 3u);
+        for (uint32_t l = 0; l < in->n_lists; ++l) mis = mis || ((uintptr_t)in->list_off[l] & 7u);
+        if (mis) return bad("misaligned array");
+    }
+    phant::ReceiptsArgs a;
+    a.tx_type = in->tx_type, a.status = in->status, a.cum_gas = in->cum_gas, a.log_first = in->log_first, a.address = in->address;
+    a.topic_first = in->topic_first, a.data_off = in->data_off, a.topics = in->topics, a.data = in->data;
+    a.n = n, a.n_logs = nl, a.n_topics = in->n_topics, a.data_bytes = in->data_bytes;
+    a.lists = in->lists, a.list_off = in->list_off, a.list_n = in->list_n, a.list_bytes = in->list_bytes, a.n_lists = in->n_lists;
+    a.receipts_at = in->receipts_at;
+    a.receipts_root = out->receipts_root, a.logs_bloom = out->logs_bloom, a.blooms = out->blooms, a.encoded = out->encoded;
+    a.encoded_off = out->encoded_off, a.roots_out = out->roots_out, a.encoded_cap = out->encoded_cap, a.encoded_off_cap = out->encoded_off_cap;
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    const int32_t rc = phant::block_receipts(c->ws, c->stream, a, dev, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->encoded_len = a.encoded_len;
+    return PHANT_OK;
+}
+
+int32_t phant_block_receipts(phant_ctx* c, const phant_receipts_in* in, phant_receipts_out* out) {
+    return block_receipts_impl(c, in, out, false);
+}
+
+int32_t phant_block_receipts_dev(phant_ctx* c, const phant_receipts_in* in, phant_receipts_out* out) {
+    return block_receipts_impl(c, in, out, true);
+}
+
 
 /* --------------------------------------------------------- sender recovery */
 

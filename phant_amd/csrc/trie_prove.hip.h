@@ -34,6 +34,7 @@ constexpr uint32_t PV_ERR_TRIE = 1u, PV_ERR_SCRATCH = 2u;
 // the mailbox words behind the build's own: total nodes, total bytes (two words), error flags
 constexpr uint32_t MAILBOX_PROVE = N_COUNTERS + 8u;
 static_assert(MAILBOX_PROVE + 4u <= Workspaces::MAILBOX_WORDS, "the prover's totals fit the pinned mailbox");
+static_assert(MAILBOX_PROVE + 4u <= Workspaces::MAILBOX_RECEIPTS, "the builder's and the prover's words end in front of the receipts'");
 
 struct ProveDev {
     const uint8_t* qkeys;
