@@ -232,6 +232,110 @@ typedef struct phant_receipts_out {
 PHANT_API int32_t phant_block_receipts(phant_ctx *ctx, const phant_receipts_in *in, phant_receipts_out *out);
 PHANT_API int32_t phant_block_receipts_dev(phant_ctx *ctx, const phant_receipts_in *in, phant_receipts_out *out);
 
+/* ------------------------------------------------- block headers: encode, hash, validate chain segments
+ * src/blockchain/blockchain.zig:100-145 `validateBlockHeader` for n headers in one call: every header's fork-aware RLP
+ * encoding (src/types/block.zig:51-69), its hash, and for every header but a segment's first the checks of the header
+ * against the one before it.  Nothing is encoded or hashed on the host.
+ *
+ * Input, struct-of-arrays in the field order of block.zig:15-36; header i has parent_hash[32 i ..), fee_recipient[20 i ..),
+ * logs_bloom[256 i ..), nonce[8 i ..), base_fee[32 i ..) (big-endian u256), the uint64_t fields, extra_data[extra_off[i] ..
+ * extra_off[i+1]) (extra_off runs from 0, never backwards) and n_fields[i] = how many list items it encodes: 15, 16 (+ base
+ * fee), 17 (+ withdrawals root), 19 (+ blob gas used, excess blob gas), 20 (+ parent beacon root) or 21 (+ requests hash).
+ * An array that no header of the call encodes may be NULL, and so may extra_data when every header's is empty.
+ * seg_first (NULL: one segment): n_segs + 1 strictly increasing indices from 0 to n; the first header of a segment is its
+ * ANCHOR (the reference's prev_block): it is hashed, no rule is applied to it.  expected_hash (NULL: none): n x 32.
+ *
+ * Encoding: one RLP list of the first n_fields items; hashes, address, bloom, prev_randao and nonce as strings of their
+ * full width, the integers and base_fee minimal big-endian (zero is 0x80), extra_data by RLP's string rules, any length.
+ *
+ * flags[i], bit k = the k-th check of validateBlockHeader failed (p = the header before; integers are exact, nothing wraps):
+ * the lowest set bit is the error the reference returns, and all failed checks are reported. */
+#define PHANT_HDR_GAS_LIMIT_TOO_HIGH 0x0001u /* gas_limit >= p.gas_limit + p.gas_limit / 1024 */
+#define PHANT_HDR_GAS_LIMIT_TOO_LOW 0x0002u  /* gas_limit <= p.gas_limit - p.gas_limit / 1024 */
+#define PHANT_HDR_GAS_LIMIT_MINIMUM 0x0004u  /* gas_limit < 5000 */
+#define PHANT_HDR_GAS_LIMIT_EXCEEDED 0x0008u /* gas_used > gas_limit */
+#define PHANT_HDR_BASE_FEE 0x0010u           /* base_fee is not the EIP-1559 value that follows from p (see below) */
+#define PHANT_HDR_TIMESTAMP 0x0020u          /* timestamp <= p.timestamp */
+#define PHANT_HDR_NUMBER 0x0040u             /* number != p.number + 1 */
+#define PHANT_HDR_EXTRA_DATA 0x0080u         /* more than 32 bytes of extra_data */
+#define PHANT_HDR_DIFFICULTY 0x0100u         /* difficulty != 0 */
+#define PHANT_HDR_NONCE 0x0200u              /* nonce is not eight zero bytes */
+#define PHANT_HDR_UNCLE_HASH 0x0400u         /* uncle_hash != keccak256(0xc0) */
+#define PHANT_HDR_PARENT_HASH 0x0800u        /* parent_hash != hash(p) */
+#define PHANT_HDR_EXPECTED_HASH 0x1000u      /* expected_hash given and != hash(header): the one bit an anchor can have */
+/* Expected base fee, t = p.gas_limit / 2, all divisions floor: p.gas_used == t: p.base_fee; above: p.base_fee +
+ * max(p.base_fee (p.gas_used - t) / t / 8, 1); below: p.base_fee - p.base_fee (t - p.gas_used) / t / 8.  Where the reference
+ * would panic -- t == 0 with p.gas_used != 0, or exactly one of the two headers without a base fee (n_fields 15) -- the bit
+ * is set; two headers without one skip the rule; an expected value beyond 2^256 - 1 equals no field: the bit is set.
+ *
+ * Output, any pointer may be NULL: hashes = n x 32; flags = n words; enc / enc_off = the encodings back to back in index
+ * order and their n + 1 offsets.  first_bad (the least i with flags[i] != 0, n if none) and enc_len are always written; if
+ * enc_len exceeds enc_cap the call still returns PHANT_OK, neither enc nor enc_off is touched (a NULL enc has no capacity to
+ * exceed) and the other outputs arrive: call again with the reported size.
+ *
+ * A bad header is a flag, never an error.  PHANT_E_INVALID_ARG: a wrong struct_size, a NULL array that a header needs, an
+ * n_fields outside the six values, extra_off or seg_first as not described above.  PHANT_E_UNSUPPORTED: 700 n + the
+ * extra data's bytes, the call's bound on its encodings, is 4 GiB or more.  n == 0 is PHANT_OK with first_bad = 0.  The host
+ * form checks before anything is copied.
+ *
+ * Device form: every array is device memory, the uint64_t arrays and enc_off 8-byte, extra_off / seg_first / flags 4-byte
+ * aligned; both structs are host memory.  n_fields, extra_off and seg_first are checked on the device before any kernel
+ * indexes with them.  Outputs stay in device memory; the call synchronises the ctx stream on the way (enc_len and first_bad
+ * are valid when it returns), the copies into hashes are in stream order behind it. */
+typedef struct phant_headers_in {
+    uint32_t struct_size; /* = sizeof(phant_headers_in) */
+    uint32_t n;
+    uint32_t n_segs;      /* with seg_first */
+    uint32_t reserved;    /* 0 */
+    const uint8_t *parent_hash;        /* n x 32 */
+    const uint8_t *uncle_hash;         /* n x 32 */
+    const uint8_t *fee_recipient;      /* n x 20 */
+    const uint8_t *state_root;         /* n x 32 */
+    const uint8_t *transactions_root;  /* n x 32 */
+    const uint8_t *receipts_root;      /* n x 32 */
+    const uint8_t *logs_bloom;         /* n x 256 */
+    const uint64_t *difficulty;        /* n */
+    const uint64_t *number;            /* n */
+    const uint64_t *gas_limit;         /* n */
+    const uint64_t *gas_used;          /* n */
+    const uint64_t *timestamp;         /* n */
+    const uint8_t *extra_data;
+    const uint32_t *extra_off;         /* n + 1 */
+    const uint8_t *prev_randao;        /* n x 32 */
+    const uint8_t *nonce;              /* n x 8 */
+    const uint8_t *base_fee;           /* n x 32, big-endian; n_fields >= 16 */
+    const uint8_t *withdrawals_root;   /* n x 32; n_fields >= 17 */
+    const uint64_t *blob_gas_used;     /* n; n_fields >= 19 */
+    const uint64_t *excess_blob_gas;   /* n; n_fields >= 19 */
+    const uint8_t *parent_beacon_root; /* n x 32; n_fields >= 20 */
+    const uint8_t *requests_hash;      /* n x 32; n_fields == 21 */
+    const uint8_t *n_fields;           /* n */
+    const uint32_t *seg_first;         /* n_segs + 1, or NULL */
+    const uint8_t *expected_hash;      /* n x 32, or NULL */
+} phant_headers_in;
+typedef struct phant_headers_out {
+    uint32_t struct_size; /* = sizeof(phant_headers_out) */
+    uint32_t first_bad;   /* result */
+    uint64_t enc_cap;     /* bytes of enc */
+    uint8_t *hashes;
+    uint32_t *flags;
+    uint8_t *enc;
+    uint64_t *enc_off;
+    uint64_t enc_len;     /* result */
+} phant_headers_out;
+PHANT_API int32_t phant_header_chain(phant_ctx *ctx, const phant_headers_in *in, phant_headers_out *out);
+PHANT_API int32_t phant_header_chain_dev(phant_ctx *ctx, const phant_headers_in *in, phant_headers_out *out);
+/* Host only, strict: header i = blob[off[i] .. off[i+1]), or with PHANT_HEADERS_FROM_BLOCKS the first item of the block
+ * encoding there.  Writes the caller's arrays behind fields_out (ALL of them non-NULL and sized for n; extra_data sized by
+ * the input bytes; seg_first / expected_hash are not touched) and sets fields_out->n, so that fields_out can go straight into
+ * phant_header_chain.
+ * Strict: canonical RLP, one of the six field counts, exact widths, minimal integers that fit their field, nothing behind
+ * the item -- so encode(decode(x)) == x.  status[i] != 0: refused; its n_fields is 0 (which phant_header_chain refuses) and
+ * its other fields are zero.  Returns PHANT_E_INVALID_ARG for NULL arguments, offsets that go backwards or unknown flags. */
+#define PHANT_HEADERS_FROM_BLOCKS 1u
+PHANT_API int32_t phant_headers_decode_rlp(const uint8_t *blob, const uint64_t *off, uint32_t n, uint32_t flags,
+                                           phant_headers_in *fields_out, uint8_t *status);
+
 /* ------------------------------------------------- sender recovery (secp256k1)
  * src/signer/signer.zig:40-79 `get_sender` / src/crypto/ecdsa.zig:19-21 `erecover` for a block's transactions in one
  * launch: one lane per signature does SEC 1 section 4.1.6 and hashes the key it found.  Status byte per item: */

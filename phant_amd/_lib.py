@@ -64,6 +64,9 @@ SYMBOLS = {
     "phant_sender_addresses_dev": (_i32, [_vp, _vp, _u64, _u32, _vp]),
     "phant_block_receipts": (_i32, [_vp, _vp, _vp]),
     "phant_block_receipts_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_header_chain": (_i32, [_vp, _vp, _vp]),
+    "phant_header_chain_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_headers_decode_rlp": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "phant_ecrecover_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_ecrecover_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_tx_senders": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp]),
@@ -155,6 +158,25 @@ class PhantReceiptsOut(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("encoded_off_cap", C.c_uint32), ("encoded_cap", C.c_uint64),
                 ("receipts_root", C.c_void_p), ("logs_bloom", C.c_void_p), ("blooms", C.c_void_p), ("encoded", C.c_void_p),
                 ("encoded_off", C.c_void_p), ("roots_out", C.c_void_p), ("encoded_len", C.c_uint64)]
+
+
+HEADER_ARRAYS = ("parent_hash", "uncle_hash", "fee_recipient", "state_root", "transactions_root", "receipts_root", "logs_bloom", "difficulty",
+                 "number", "gas_limit", "gas_used", "timestamp", "extra_data", "extra_off", "prev_randao", "nonce", "base_fee",
+                 "withdrawals_root", "blob_gas_used", "excess_blob_gas", "parent_beacon_root", "requests_hash", "n_fields", "seg_first",
+                 "expected_hash")
+HEADERS_FROM_BLOCKS = 1
+
+
+class PhantHeadersIn(C.Structure):
+    """phant_headers_in (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_uint32), ("n_segs", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(name, C.c_void_p) for name in HEADER_ARRAYS]
+
+
+class PhantHeadersOut(C.Structure):
+    """phant_headers_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("first_bad", C.c_uint32), ("enc_cap", C.c_uint64), ("hashes", C.c_void_p),
+                ("flags", C.c_void_p), ("enc", C.c_void_p), ("enc_off", C.c_void_p), ("enc_len", C.c_uint64)]
 
 
 class PhantProveOut(C.Structure):

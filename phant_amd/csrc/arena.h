@@ -113,7 +113,9 @@ struct Workspaces {
     // they end in front of it), block_receipts the MAILBOX_RECEIPTS_WORDS behind it -- so the builder's passes, which rewrite
     // their own window on every call, never touch the control words a receipts call has read or is about to read.
     static constexpr size_t MAILBOX_RECEIPTS = 1536, MAILBOX_RECEIPTS_WORDS = 8;
-    static_assert(MAILBOX_RECEIPTS + MAILBOX_RECEIPTS_WORDS <= MAILBOX_WORDS, "the receipts' control words fit the pinned mailbox");
+    // ... and header_chain (headers.hip.h) the MAILBOX_HEADERS_WORDS behind those
+    static constexpr size_t MAILBOX_HEADERS = MAILBOX_RECEIPTS + MAILBOX_RECEIPTS_WORDS, MAILBOX_HEADERS_WORDS = 8;
+    static_assert(MAILBOX_HEADERS + MAILBOX_HEADERS_WORDS <= MAILBOX_WORDS, "the receipts' and the headers' control words fit the pinned mailbox");
     uint32_t* mailbox = nullptr;
     hipError_t ensure_mailbox() {
         if (mailbox) return hipSuccess;

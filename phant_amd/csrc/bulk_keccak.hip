@@ -11,12 +11,15 @@
 //                   (secp256k1.hip.h), hashed while it is in registers
 //   receipts        src/types/receipt.zig:13-63 + src/blockchain/blockchain.zig:76-90  blooms, encodings, the block's bloom and
 //                   the receipts root of a block in one call (receipts.hip.h)
+//   block headers   src/types/block.zig:51-69 + src/blockchain/blockchain.zig:100-145  encodings, hashes and validateBlockHeader of
+//                   whole chain segments in one call (headers.hip.h)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
 #include "launch.h"
 #include "secp256k1.hip.h"
 #include "receipts.hip.h"
+#include "headers.hip.h"
 
 namespace phant {
 

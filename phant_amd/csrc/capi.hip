@@ -20,6 +20,7 @@
 #include "arena.h"
 #include "launch.h"
 #include "receipts.h"
+#include "headers.h"
 #include "trie_build.h"
 #include "witness.h"
 #include "host_rlp.h"
@@ -657,6 +658,73 @@ int32_t phant_block_receipts_dev(phant_ctx* c, const phant_receipts_in* in, phan
     return block_receipts_impl(c, in, out, true);
 }
 
+
+/* ------------------------------------------------- block headers (headers.hip.h) */
+
+static int32_t header_chain_impl(phant_ctx* c, const phant_headers_in* in, phant_headers_out* out, bool dev) {
+    const char* const who = dev ? "header_chain_dev" : "header_chain";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_headers_in) || out->struct_size != sizeof(phant_headers_out)) return bad("wrong struct_size");
+    const uint32_t n = in->n;
+    if (n == 0) {
+        out->first_bad = 0, out->enc_len = 0;
+        return PHANT_OK;
+    }
+    if (!in->parent_hash || !in->uncle_hash || !in->fee_recipient || !in->state_root || !in->transactions_root || !in->receipts_root ||
+        !in->logs_bloom || !in->difficulty || !in->number || !in->gas_limit || !in->gas_used || !in->timestamp || !in->extra_off ||
+        !in->prev_randao || !in->nonce || !in->n_fields)
+        return bad("a NULL array that every header needs");
+    if (in->seg_first && (in->n_segs == 0 || in->n_segs > n)) return bad("n_segs is 0 or beyond n");
+    if (dev) {  // (what a kernel reads or writes as words; digests, flags and encodings arrive by device-to-device copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->difficulty | (uintptr_t)in->number | (uintptr_t)in->gas_limit | (uintptr_t)in->gas_used |
+                             (uintptr_t)in->timestamp | (uintptr_t)in->blob_gas_used | (uintptr_t)in->excess_blob_gas | (uintptr_t)out->enc_off;
+        const uintptr_t w4 = (uintptr_t)in->extra_off | (uintptr_t)in->seg_first | (uintptr_t)out->flags;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_headers_out res = *out;
+    const int32_t rc = phant::header_chain(c->ws, c->stream, *in, res, dev, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->first_bad = res.first_bad, out->enc_len = res.enc_len;
+    return PHANT_OK;
+}
+
+int32_t phant_header_chain(phant_ctx* c, const phant_headers_in* in, phant_headers_out* out) { return header_chain_impl(c, in, out, false); }
+
+int32_t phant_header_chain_dev(phant_ctx* c, const phant_headers_in* in, phant_headers_out* out) { return header_chain_impl(c, in, out, true); }
+
+int32_t phant_headers_decode_rlp(const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t flags, phant_headers_in* fields_out,
+                                 uint8_t* status) {
+    if (flags & ~PHANT_HEADERS_FROM_BLOCKS) return PHANT_E_INVALID_ARG;
+    if (n == 0) return PHANT_OK;
+    const phant_headers_in* f = fields_out;
+    if (!off || !f || !status || f->struct_size != sizeof(phant_headers_in)) return PHANT_E_INVALID_ARG;
+    if (!f->parent_hash || !f->uncle_hash || !f->fee_recipient || !f->state_root || !f->transactions_root || !f->receipts_root || !f->logs_bloom ||
+        !f->difficulty || !f->number || !f->gas_limit || !f->gas_used || !f->timestamp || !f->extra_data || !f->extra_off || !f->prev_randao ||
+        !f->nonce || !f->base_fee || !f->withdrawals_root || !f->blob_gas_used || !f->excess_blob_gas || !f->parent_beacon_root ||
+        !f->requests_hash || !f->n_fields)
+        return PHANT_E_INVALID_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return PHANT_E_INVALID_ARG;
+    if (off[n] != off[0] && !blob) return PHANT_E_INVALID_ARG;
+    auto w8 = [](const uint8_t* p) { return const_cast<uint8_t*>(p); };
+    auto w64 = [](const uint64_t* p) { return const_cast<uint64_t*>(p); };
+    const phant::HeaderArrays a{w8(f->parent_hash), w8(f->uncle_hash), w8(f->fee_recipient), w8(f->state_root), w8(f->transactions_root),
+                                w8(f->receipts_root), w8(f->logs_bloom), w64(f->difficulty), w64(f->number), w64(f->gas_limit), w64(f->gas_used),
+                                w64(f->timestamp), w8(f->extra_data), const_cast<uint32_t*>(f->extra_off), w8(f->prev_randao), w8(f->nonce),
+                                w8(f->base_fee), w8(f->withdrawals_root), w64(f->blob_gas_used), w64(f->excess_blob_gas),
+                                w8(f->parent_beacon_root), w8(f->requests_hash), w8(f->n_fields)};
+    uint32_t extra_at = 0;
+    a.extra_off[0] = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        status[i] = phant::header_decode(blob ? blob + off[i] : nullptr, (size_t)(off[i + 1] - off[i]), (flags & PHANT_HEADERS_FROM_BLOCKS) != 0, a, i, &extra_at) ? 0 : 1;
+    fields_out->n = n;
+    return PHANT_OK;
+}
 
 /* --------------------------------------------------------- sender recovery */
 

@@ -316,4 +316,74 @@ uint8_t tx_signing_parts(const uint8_t* tx, size_t len, uint64_t chain_id, std::
     return PHANT_SIG_OK;
 }
 
+// ---- block headers (src/types/block.zig:15-69) ----
+bool header_decode(const uint8_t* p, size_t len, bool from_block, const HeaderArrays& f, uint32_t i, uint32_t* extra_at) {
+    uint8_t* const rows32[9] = {f.parent_hash, f.uncle_hash, f.state_root, f.transactions_root, f.receipts_root, f.prev_randao, f.withdrawals_root,
+                                f.parent_beacon_root, f.requests_hash};
+    uint64_t* const ints[7] = {f.difficulty, f.number, f.gas_limit, f.gas_used, f.timestamp, f.blob_gas_used, f.excess_blob_gas};
+    for (uint8_t* r : rows32) std::memset(r + 32 * (size_t)i, 0, 32);
+    for (uint64_t* v : ints) v[i] = 0;
+    std::memset(f.fee_recipient + 20 * (size_t)i, 0, 20);
+    std::memset(f.logs_bloom + 256 * (size_t)i, 0, 256);
+    std::memset(f.nonce + 8 * (size_t)i, 0, 8);
+    std::memset(f.base_fee + 32 * (size_t)i, 0, 32);
+    f.n_fields[i] = 0;
+    f.extra_off[i + 1] = *extra_at;
+    if (!p) return false;
+    size_t pay, plen, total;
+    bool is_list;
+    if (!host_rlp_item(p, len, pay, plen, total, is_list) || !is_list || total != len) return false;
+    if (from_block) {  // [header, transactions, uncles, (withdrawals)]: the first item, the rest only walked
+        const uint8_t* q = p + pay;
+        size_t left = plen, hp = 0, hl = 0, ht = 0, count = 0;
+        while (left) {
+            size_t ip, il, it;
+            bool ilist;
+            if (!host_rlp_item(q, left, ip, il, it, ilist) || !ilist) return false;
+            if (count == 0) hp = ip, hl = il, ht = it;
+            ++count, q += it, left -= it;
+        }
+        if (count != 3 && count != 4) return false;
+        p += pay, pay = hp, plen = hl, total = ht;
+    }
+    // the items: widths as in block.zig:15-36
+    const uint8_t* item[21];
+    size_t ilen[21], count = 0;
+    const uint8_t* q = p + pay;
+    size_t left = plen;
+    while (left) {
+        size_t ip, il, it;
+        bool ilist;
+        if (count == 21 || !host_rlp_item(q, left, ip, il, it, ilist) || ilist) return false;
+        item[count] = q + ip, ilen[count] = il;
+        ++count, q += it, left -= it;
+    }
+    if (count != 15 && count != 16 && count != 17 && count != 19 && count != 20 && count != 21) return false;
+    static const uint16_t width[21] = {32, 32, 20, 32, 32, 32, 256, 0, 0, 0, 0, 0, 0, 32, 8, 0, 32, 0, 0, 32, 32};
+    for (size_t k = 0; k < count; ++k) {
+        const bool integer = (k >= 7 && k <= 11) || k == 15 || k == 17 || k == 18;
+        if (integer ? (ilen[k] > (k == 15 ? 32u : 8u) || (ilen[k] && item[k][0] == 0)) : (k != 12 && ilen[k] != width[k])) return false;
+    }
+    if (ilen[12] > 0xffffffffull - *extra_at) return false;
+    auto u64 = [&](size_t k) {
+        uint64_t v = 0;
+        for (size_t b = 0; b < ilen[k]; ++b) v = v << 8 | item[k][b];
+        return v;
+    };
+    const size_t at32[9] = {0, 1, 3, 4, 5, 13, 16, 19, 20};
+    for (size_t r = 0; r < 9; ++r)
+        if (at32[r] < count) std::memcpy(rows32[r] + 32 * (size_t)i, item[at32[r]], 32);
+    std::memcpy(f.fee_recipient + 20 * (size_t)i, item[2], 20);
+    std::memcpy(f.logs_bloom + 256 * (size_t)i, item[6], 256);
+    for (size_t k = 0; k < 5; ++k) ints[k][i] = u64(7 + k);
+    if (ilen[12]) std::memcpy(f.extra_data + *extra_at, item[12], ilen[12]);
+    *extra_at += (uint32_t)ilen[12];
+    f.extra_off[i + 1] = *extra_at;
+    std::memcpy(f.nonce + 8 * (size_t)i, item[14], 8);
+    if (count >= 16 && ilen[15]) std::memcpy(f.base_fee + 32 * (size_t)i + 32 - ilen[15], item[15], ilen[15]);
+    if (count >= 19) f.blob_gas_used[i] = u64(17), f.excess_blob_gas[i] = u64(18);
+    f.n_fields[i] = (uint8_t)count;
+    return true;
+}
+
 }  // namespace phant

@@ -28,4 +28,18 @@ int32_t strip_first_nibble(const uint8_t* node, uint32_t len, uint8_t* out, uint
 uint8_t tx_signing_parts(const uint8_t* tx, size_t len, uint64_t chain_id, std::vector<uint8_t>& preimage, uint8_t r[32],
                          uint8_t s[32], uint8_t* recid);
 
+// phant_headers_decode_rlp (include/phant_gpu.h): header i of the call, strictly decoded from `len` bytes at `p` (from_block: the
+// first item of the block encoding there) into row i of the caller's arrays behind `f`; extra_data is appended at *extra_at.
+// false = refused: row i is zeroed, its n_fields is 0 and *extra_at stays.  Untrusted bytes in.
+struct HeaderArrays {
+    uint8_t *parent_hash, *uncle_hash, *fee_recipient, *state_root, *transactions_root, *receipts_root, *logs_bloom;
+    uint64_t *difficulty, *number, *gas_limit, *gas_used, *timestamp;
+    uint8_t* extra_data;
+    uint32_t* extra_off;
+    uint8_t *prev_randao, *nonce, *base_fee, *withdrawals_root;
+    uint64_t *blob_gas_used, *excess_blob_gas;
+    uint8_t *parent_beacon_root, *requests_hash, *n_fields;
+};
+bool header_decode(const uint8_t* p, size_t len, bool from_block, const HeaderArrays& f, uint32_t i, uint32_t* extra_at);
+
 }  // namespace phant

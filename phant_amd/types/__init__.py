@@ -1,2 +1,2 @@
-"""phant_amd.types <-> the keccak256 users of src/types/ (receipt.zig logs bloom, transaction.zig hashes)."""
-from . import receipt, transaction  # noqa: F401
+"""phant_amd.types <-> the keccak256 users of src/types/ (receipt.zig logs bloom, transaction.zig hashes, block.zig headers)."""
+from . import block, receipt, transaction  # noqa: F401

@@ -1,0 +1,260 @@
+"""Block headers <-> src/types/block.zig:15-69 (`BlockHeader`, `encodeToRLP`) and src/blockchain/blockchain.zig:100-145
+(`validateBlockHeader`): encodings, hashes and the header rules of whole chain segments in ONE call (phant_header_chain), strict
+decoding of raw headers on the host (phant_headers_decode_rlp).  Through the C-ABI; no CPU fallback.
+
+Two deviations from the reference, both where it would panic: a header pair of which exactly one has a base fee, and a parent
+whose gas target is zero while it used gas, set the InvalidBaseFee flag instead."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, fields as _dc_fields
+
+import numpy as np
+
+from .. import _lib as L
+from ..context import Context, default_context
+
+EMPTY_UNCLE_HASH = bytes.fromhex("1dcc4de8dec75d7aab85b567b6ccd41ad312451b948a7413f0a142fd40d49347")  # block.zig:13
+
+
+class Flags:
+    """flags[i] of validate_chain: bit k = the k-th check of validateBlockHeader failed"""
+    GasLimitTooHigh = 1 << 0
+    GasLimitTooLow = 1 << 1
+    GasLimitLessThanMinimum = 1 << 2
+    GasLimitExceeded = 1 << 3
+    InvalidBaseFee = 1 << 4
+    InvalidTimestamp = 1 << 5
+    InvalidBlockNumber = 1 << 6
+    ExtraDataTooLong = 1 << 7
+    InvalidDifficulty = 1 << 8
+    InvalidNonce = 1 << 9
+    InvalidUnclesHash = 1 << 10
+    InvalidParentHash = 1 << 11
+    ExpectedHashMismatch = 1 << 12  # not one of the reference's: the caller's expected hash (a payload's blockHash) differs
+    NAMES = ("GasLimitTooHigh", "GasLimitTooLow", "GasLimitLessThanMinimum", "GasLimitExceeded", "InvalidBaseFee", "InvalidTimestamp",
+             "InvalidBlockNumber", "ExtraDataTooLong", "InvalidDifficulty", "InvalidNonce", "InvalidUnclesHash", "InvalidParentHash",
+             "ExpectedHashMismatch")
+
+
+def first_error(flags: int):
+    """the error validateBlockHeader would return for this flag word (its lowest set bit), or None"""
+    flags = int(flags)
+    return None if not flags else Flags.NAMES[(flags & -flags).bit_length() - 1]
+
+
+@dataclass
+class BlockHeader:
+    """block.zig:15-36 `BlockHeader`"""
+    parent_hash: bytes
+    uncle_hash: bytes
+    fee_recipient: bytes
+    state_root: bytes
+    transactions_root: bytes
+    receipts_root: bytes
+    logs_bloom: bytes
+    difficulty: int
+    block_number: int
+    gas_limit: int
+    gas_used: int
+    timestamp: int
+    extra_data: bytes
+    prev_randao: bytes
+    nonce: bytes
+    base_fee_per_gas: int | None = None
+    withdrawals_root: bytes | None = None
+    blob_gas_used: int | None = None
+    excess_blob_gas: int | None = None
+    parent_beacon_root: bytes | None = None
+    request_hash: bytes | None = None
+
+    @property
+    def n_fields(self) -> int:
+        """block.zig:51-68: the last field that is set decides how many items are encoded"""
+        if self.request_hash is not None:
+            n = 21
+        elif self.parent_beacon_root is not None:
+            n = 20
+        elif self.blob_gas_used is not None or self.excess_blob_gas is not None:
+            n = 19
+        elif self.withdrawals_root is not None:
+            n = 17
+        elif self.base_fee_per_gas is not None:
+            n = 16
+        else:
+            n = 15
+        if any(getattr(self, f.name) is None for f in _dc_fields(self)[:n]):
+            raise ValueError("a field in front of the header's last one is None")
+        return n
+
+    def encode(self, ctx: Context | None = None) -> bytes:
+        """block.zig:51 `encodeToRLP`"""
+        return header_chain([self], want_encodings=True, ctx=ctx).encoded[0]
+
+    def hash(self, ctx: Context | None = None) -> bytes:
+        """common.encodeToRLPAndHash(BlockHeader, ...)"""
+        return header_chain([self], ctx=ctx).hashes[0]
+
+    @classmethod
+    def decode(cls, raw: bytes) -> "BlockHeader":
+        """strict; ValueError for anything encode() would not have produced"""
+        return decode_headers([raw])[0]
+
+
+_ROWS = (("parent_hash", 32), ("uncle_hash", 32), ("fee_recipient", 20), ("state_root", 32), ("transactions_root", 32), ("receipts_root", 32),
+         ("logs_bloom", 256), ("prev_randao", 32), ("nonce", 8), ("withdrawals_root", 32), ("parent_beacon_root", 32), ("requests_hash", 32))
+_INTS = ("difficulty", "number", "gas_limit", "gas_used", "timestamp", "blob_gas_used", "excess_blob_gas")
+_ATTR = {"number": "block_number", "requests_hash": "request_hash"}  # C-ABI array -> the reference's field name
+
+
+def _empty_arrays(n, extra_bytes):
+    m = max(n, 1)
+    a = {name: np.zeros((m, w), np.uint8) for name, w in _ROWS}
+    a.update({name: np.zeros(m, np.uint64) for name in _INTS})
+    a["base_fee"] = np.zeros((m, 32), np.uint8)
+    a["extra_data"] = np.zeros(max(extra_bytes, 1), np.uint8)
+    a["extra_off"] = np.zeros(n + 1, np.uint32)
+    a["n_fields"] = np.zeros(m, np.uint8)
+    return a
+
+
+def pack_headers(headers):
+    """-> the struct-of-arrays of phant_headers_in as numpy arrays (never empty: a zero count gets one spare element)"""
+    headers = list(headers)
+    n = len(headers)
+    a = _empty_arrays(n, sum(len(h.extra_data) for h in headers))
+    at = 0
+    for i, h in enumerate(headers):
+        a["n_fields"][i] = h.n_fields
+        for name, w in _ROWS:
+            v = getattr(h, _ATTR.get(name, name))
+            if v is not None:
+                if len(v) != w:
+                    raise ValueError(f"{name} is {w} bytes")
+                a[name][i] = np.frombuffer(bytes(v), np.uint8)
+        for name in _INTS:
+            v = getattr(h, _ATTR.get(name, name))
+            if v is not None:
+                if not 0 <= v < 1 << 64:
+                    raise ValueError(f"{name} does not fit 64 bits")
+                a[name][i] = v
+        if h.base_fee_per_gas is not None:
+            a["base_fee"][i] = np.frombuffer(int(h.base_fee_per_gas).to_bytes(32, "big"), np.uint8)
+        x = bytes(h.extra_data)
+        a["extra_data"][at:at + len(x)] = np.frombuffer(x, np.uint8)
+        at += len(x)
+        a["extra_off"][i + 1] = at
+    return a
+
+
+def _struct(a, n, seg_first=None, expected=None):
+    ptr = {k: v.ctypes.data for k, v in a.items()}
+    return L.PhantHeadersIn(C.sizeof(L.PhantHeadersIn), n, 0 if seg_first is None else len(seg_first) - 1, 0,
+                            *[ptr.get(k) for k in L.HEADER_ARRAYS[:-2]], None if seg_first is None else seg_first.ctypes.data,
+                            None if expected is None else expected.ctypes.data)
+
+
+@dataclass
+class HeaderChain:
+    hashes: list          # n 32-byte hashes
+    flags: np.ndarray     # n uint32 (Flags)
+    first_bad: int        # the least index with a flag, n if none
+    encoded: list | None  # n byte strings where asked for
+
+
+def header_chain(headers, seg_first=None, expected_hashes=None, want_encodings=False, ctx: Context | None = None, arrays=None) -> HeaderChain:
+    """phant_header_chain over BlockHeader objects (or over `arrays` as pack_headers / decode_arrays made them)."""
+    ctx = ctx or default_context()
+    a = pack_headers(headers) if arrays is None else arrays
+    n = len(a["extra_off"]) - 1
+    seg = None if seg_first is None else np.asarray(seg_first, np.uint32)
+    exp = None
+    if expected_hashes is not None:
+        exp = np.frombuffer(b"".join(bytes(x) for x in expected_hashes) or bytes(32), np.uint8).copy()
+        if exp.size != 32 * max(n, 1):
+            raise ValueError("one 32-byte expected hash per header")
+    arg = _struct(a, n, seg, exp)
+    hashes = np.zeros((max(n, 1), 32), np.uint8)
+    flags = np.zeros(max(n, 1), np.uint32)
+    cap = (700 * n + int(a["extra_off"][-1]) + 16) if want_encodings else 0
+    enc = np.zeros(max(cap, 1), np.uint8)
+    enc_off = np.zeros(n + 1, np.uint64)
+    out = L.PhantHeadersOut(C.sizeof(L.PhantHeadersOut), 0, cap, hashes.ctypes.data, flags.ctypes.data,
+                            enc.ctypes.data if want_encodings else None, enc_off.ctypes.data if want_encodings else None, 0)
+    ctx.check(ctx._lib.phant_header_chain(ctx.handle, C.byref(arg), C.byref(out)))
+    if want_encodings and out.enc_len > cap:
+        raise RuntimeError("header_chain: the encodings exceed their bound (internal)")
+    encoded = [enc[int(enc_off[i]):int(enc_off[i + 1])].tobytes() for i in range(n)] if want_encodings else None
+    return HeaderChain([hashes[i].tobytes() for i in range(n)], flags[:n], int(out.first_bad), encoded)
+
+
+def validate_chain(headers, seg_first=None, expected_hashes=None, ctx: Context | None = None):
+    """validateBlockHeader of every header against the one before it, for whole segments: seg_first (None: one segment) are the
+    n_segs + 1 increasing indices of the segments' first headers, from 0 to n; the first header of a segment is the trusted
+    prev_block and only hashed.  expected_hashes: one per header, compared with its hash.  -> (hashes, flags, first_bad)"""
+    r = header_chain(headers, seg_first, expected_hashes, ctx=ctx)
+    return r.hashes, r.flags, r.first_bad
+
+
+def decode_arrays(raws, from_blocks=False):
+    """phant_headers_decode_rlp -> (arrays as pack_headers makes them, status uint8[n]); host only"""
+    raws = [bytes(r) for r in raws]
+    n = len(raws)
+    blob = np.frombuffer(b"".join(raws) or b"\x00", np.uint8).copy()
+    off = np.cumsum([0] + [len(r) for r in raws]).astype(np.uint64)
+    a = _empty_arrays(n, int(off[-1]))
+    status = np.zeros(max(n, 1), np.uint8)
+    arg = _struct(a, n)
+    rc = L.lib().phant_headers_decode_rlp(blob.ctypes.data, off.ctypes.data, n, L.HEADERS_FROM_BLOCKS if from_blocks else 0, C.byref(arg),
+                                          status.ctypes.data)
+    if rc != L.OK:
+        raise L.PhantError(rc, "phant_headers_decode_rlp")
+    return a, status[:n]
+
+
+def unpack_headers(a):
+    """arrays -> BlockHeader objects"""
+    out = []
+    for i in range(len(a["extra_off"]) - 1):
+        k = int(a["n_fields"][i])
+        row = lambda name: a[name][i].tobytes()  # noqa: E731
+        out.append(BlockHeader(
+            row("parent_hash"), row("uncle_hash"), row("fee_recipient"), row("state_root"), row("transactions_root"), row("receipts_root"),
+            row("logs_bloom"), int(a["difficulty"][i]), int(a["number"][i]), int(a["gas_limit"][i]), int(a["gas_used"][i]), int(a["timestamp"][i]),
+            a["extra_data"][int(a["extra_off"][i]):int(a["extra_off"][i + 1])].tobytes(), row("prev_randao"), row("nonce"),
+            int.from_bytes(row("base_fee"), "big") if k >= 16 else None, row("withdrawals_root") if k >= 17 else None,
+            int(a["blob_gas_used"][i]) if k >= 19 else None, int(a["excess_blob_gas"][i]) if k >= 19 else None,
+            row("parent_beacon_root") if k >= 20 else None, row("requests_hash") if k >= 21 else None))
+    return out
+
+
+def decode_headers(raws, from_blocks=False):
+    """strict decoding of raw headers (from_blocks: of the first item of raw blocks); ValueError names the first refused one"""
+    a, status = decode_arrays(raws, from_blocks)
+    if status.any():
+        raise ValueError(f"header {int(np.flatnonzero(status)[0])} is not a canonical header encoding")
+    return unpack_headers(a)
+
+
+def payload_block_hash(payload_fields: dict, raw_txs, withdrawals, ctx: Context | None = None, keys: str = "be32"):
+    """The check newPayloadV2Handler leaves out (execution_payload.zig:115,175-181): the header ExecutionPayload.toBlock builds
+    (:125-166) from the payload's fields and the two roots it computes, hashed and compared with the payload's `blockHash`.
+    payload_fields: parentHash, feeRecipient, stateRoot, receiptsRoot, logsBloom, prevRandao, blockNumber, gasLimit, gasUsed,
+    timestamp, extraData, baseFeePerGas, blockHash (bytes / ints) and optionally blobGasUsed, excessBlobGas; raw_txs / withdrawals:
+    the encoded items.  keys: "be32" = 32-byte big-endian index keys as toBlock has them, "rlp" = rlp(index) as a block's header
+    commits to.  Two calls: the roots, then one header.  -> (matches, hash, header)"""
+    from .. import mpt
+    p = payload_fields
+    if keys == "be32":
+        tx_root, wd_root = mpt.index_root_be32(raw_txs, ctx), mpt.index_root_be32(withdrawals, ctx)
+    elif keys == "rlp":
+        tx_root, wd_root = mpt.block_roots([raw_txs, withdrawals], ctx)
+    else:
+        raise ValueError("keys is 'be32' or 'rlp'")
+    blob = p.get("blobGasUsed")
+    h = BlockHeader(bytes(p["parentHash"]), EMPTY_UNCLE_HASH, bytes(p["feeRecipient"]), bytes(p["stateRoot"]), tx_root, bytes(p["receiptsRoot"]),
+                    bytes(p["logsBloom"]), 0, int(p["blockNumber"]), int(p["gasLimit"]), int(p["gasUsed"]), int(p["timestamp"]),
+                    bytes(p["extraData"]), bytes(p["prevRandao"]), bytes(8), int(p["baseFeePerGas"]), wd_root,
+                    None if blob is None else int(blob), None if blob is None else int(p["excessBlobGas"]))
+    r = header_chain([h], expected_hashes=[bytes(p["blockHash"])], ctx=ctx)
+    return r.first_bad == 1, r.hashes[0], h
