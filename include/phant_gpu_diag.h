@@ -54,6 +54,25 @@ PHANT_API int32_t phant_verify_bound_experiment(phant_ctx *ctx, const uint8_t *d
  * library is measured against (bench.py: roofline.valu.peak). */
 PHANT_API int32_t phant_keccak_rate(phant_ctx *ctx, uint32_t waves_per_simd, uint32_t perms, double *perms_per_s);
 
+/* What the trie hasher's last call on this ctx did (phant_mpt_root*, phant_index_root*, phant_block_roots, the forests of the
+ * state root and of the prover ...): the choices its launcher made from the node counts of the depth bins, the key count and free
+ * memory, so that a test that forces one of them can tell that the call took it.  Host integers the launcher has anyway; only
+ * out[10] and out[15] are read from the device, when this is called.  Synchronises the ctx stream.
+ *   out[0]  the pass: 0 = none (no call yet, no keys), 1 = the two-launch pass for small tries, 2 = the general pass
+ * the rest is about the general pass (0, deep_from -1, after the small one):
+ *   out[1]  1 = the leaves were queued ahead of the host's sizing, with worst-case tables
+ *   out[2]  (int32_t) the depth from which the bins ran on the helper stream beside the leaves, -1 = no helper stream
+ *   out[3]  non-empty depth bins                    out[4]  nodes of the largest
+ *   out[5 .. 9]  bins launched a wave per node, a node per half wave, a lane per node in slots of 1, 2, 4 rate blocks
+ *   out[10] nodes that did not fit their bin's slot class and went through its fallback list (all bins)
+ *   out[11] 1 = the kernel for leaves of 136 .. 543 bytes ran
+ *   out[12] branch nodes                            out[13] keys
+ *   out[14] of the bins of out[5 .. 9], those launched on the helper stream
+ *   out[15] bytes of the scratch blob taken by the nodes that fit no LDS slot (4-byte rounded; branches: with their extension's
+ *           room; leaves of 544 bytes and more in the general pass), both passes, saturating */
+#define PHANT_TRIE_STATS 16
+PHANT_API int32_t phant_trie_stats(phant_ctx *ctx, uint32_t out[PHANT_TRIE_STATS]);
+
 /* A/B of the node-set pipeline's hash kernel (tools/probe_nodeset*.py): form = how a wave hashes 532-byte nodes (0 plain,
  * 1 its issue priority falls block by block -- the default --, 2 every rate block requested a permutation ahead into
  * registers); order = 0: class lists by falling rate-block count (default), 1: rising; hash_lds_bytes = idle dynamic LDS per

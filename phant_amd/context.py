@@ -135,6 +135,20 @@ class Context:
         self.check(self._lib.phant_verify_tier_stats(self._h, C.byref(out)))
         return dict(zip(("dedup_levels", "list_nodes", "list_keccak_f", "deep_nodes", "deep_keccak_f"), [int(x) for x in out]))
 
+    TRIE_PASSES = {0: "none", 1: "small", 2: "general"}
+
+    def trie_stats(self) -> dict:
+        """What the trie hasher's last call on this ctx did (phant_trie_stats): the pass ("none", "small", "general"), whether
+        the leaves were queued ahead, deep_from (-1: no helper stream), the depth bins and how many went through each kernel
+        class, the nodes that took a fallback list, whether the kernel for 136 .. 543-byte leaves ran, branch nodes, keys and the bytes
+        of the scratch blob taken by nodes that fit no LDS slot."""
+        out = (C.c_uint32 * 16)()
+        self.check(self._lib.phant_trie_stats(self._h, C.byref(out)))
+        v = [int(x) for x in out]
+        return {"pass": self.TRIE_PASSES.get(v[0], "?"), "leaves_ahead": bool(v[1]), "deep_from": v[2] - (1 << 32) if v[2] >> 31 else v[2],
+                "bins": v[3], "max_bin": v[4], "wave": v[5], "half_wave": v[6], "blocks1": v[7], "blocks2": v[8], "blocks4": v[9],
+                "misfits": v[10], "leaf_big": bool(v[11]), "n_rep": v[12], "n": v[13], "side_bins": v[14], "scratch_bytes": v[15]}
+
     def verify_path_stats(self) -> tuple[int, int]:
         """(proofs verified from scratch by their walk lane, nodes decoded by walks that decoded more than one)."""
         out = (C.c_uint32 * 2)()

@@ -87,9 +87,29 @@ struct TrieTune {
     int64_t small_max_keys = -1;     // up to this many keys a call takes the two-launch pass (trie_build.hip: small_head_kernel; 0: never)
 };
 
+// What the trie hasher's last call on a ctx did (include/phant_gpu_diag.h: phant_trie_stats): host integers the launcher had in its
+// hands anyway, written as it goes; nothing on the device is touched for them.  The misfit counters stay where the kernels count
+// them (the t1 arena, at misfit_off), like the scratch blob's cursor, and are read when somebody asks.
+struct TrieStats {
+    uint32_t pass = 0;          // 0: no kernel pass (no call yet, no keys, or refused before one was chosen), 1: the small pass, 2: the general one
+    uint32_t ahead = 0;         // the leaves were queued ahead of the host's sizing
+    int32_t deep_from = -1;     // the depth from which the bins ran on the helper stream (-1: none did)
+    uint32_t bins = 0;          // non-empty depth bins
+    uint32_t max_bin = 0;       // nodes of the largest
+    uint32_t by_class[5] = {};  // bins launched a wave per node, a node per half wave, a lane per node in 1- / 2- / 4-block slots
+    uint32_t side_bins = 0;     // ... of all those, on the helper stream
+    uint32_t leaf_big = 0;      // leaf_big_kernel ran
+    uint32_t n_rep = 0;         // branch nodes (the general pass; the small pass does not count them)
+    uint32_t n = 0;             // keys
+    bool has_misfit = false, has_cursor = false;
+    size_t misfit_off = 0;      // of the 512 per-depth misfit counters inside t1
+    size_t cursor_off = 0;      // of the scratch blob's cursor (the bytes the nodes that did not fit an LDS slot took there) inside t1
+};
+
 // The arenas a ctx lends to the host-form entry points.
 struct Workspaces {
     TrieTune tune;
+    TrieStats trie_stats;
     DevArena io;  // staged inputs / outputs of the current call
     DevArena t1;  // trie builder: per-key / per-boundary arrays
     DevArena t2;  // trie builder: slot tables + encoding scratch

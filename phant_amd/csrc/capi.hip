@@ -344,6 +344,41 @@ int32_t phant_verify_path_stats(phant_ctx* c, uint32_t out[2]) {
     return PHANT_OK;
 }
 
+int32_t phant_trie_stats(phant_ctx* c, uint32_t out[PHANT_TRIE_STATS]) {
+    if (!c || !out) return PHANT_E_INVALID_ARG;
+    const phant::TrieStats& s = c->ws.trie_stats;
+    for (int i = 0; i < PHANT_TRIE_STATS; ++i) out[i] = 0;
+    out[0] = s.pass;
+    out[1] = s.ahead;
+    out[2] = (uint32_t)s.deep_from;
+    out[3] = s.bins;
+    out[4] = s.max_bin;
+    for (int k = 0; k < 5; ++k) out[5 + k] = s.by_class[k];
+    out[11] = s.leaf_big;
+    out[12] = s.n_rep;
+    out[13] = s.n;
+    out[14] = s.side_bins;
+    DeviceGuard g(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->ws.side) HIP_TRY(c, hipStreamSynchronize(c->ws.side));
+    // the per-depth misfit counters, where the last general pass left them (an offset, not a pointer: whatever has happened to
+    // the arena since, the copy stays inside it)
+    constexpr size_t MISFIT_BYTES = 512 * sizeof(uint32_t);
+    if (s.has_misfit && c->ws.t1.base && s.misfit_off + MISFIT_BYTES <= c->ws.t1.cap) {
+        std::vector<uint32_t> mis(512);
+        HIP_TRY(c, hipMemcpy(mis.data(), c->ws.t1.base + s.misfit_off, MISFIT_BYTES, hipMemcpyDeviceToHost));
+        uint64_t tot = 0;
+        for (const uint32_t m : mis) tot += m;
+        out[10] = (uint32_t)std::min<uint64_t>(tot, 0xffffffffull);
+    }
+    if (s.has_cursor && c->ws.t1.base && s.cursor_off + sizeof(unsigned long long) <= c->ws.t1.cap) {
+        unsigned long long used = 0;
+        HIP_TRY(c, hipMemcpy(&used, c->ws.t1.base + s.cursor_off, sizeof used, hipMemcpyDeviceToHost));
+        out[15] = (uint32_t)std::min<unsigned long long>(used, 0xffffffffull);
+    }
+    return PHANT_OK;
+}
+
 int32_t phant_verify_kernel_ms(phant_ctx* c, float ms[PHANT_VERIFY_KERNEL_STAGES]) {
     if (!c || !ms) return PHANT_E_INVALID_ARG;
     if (!c->tune.kernel_ev) return fail(c, PHANT_E_UNSUPPORTED, "verify_kernel_ms: the tiers are not serialised on this ctx (phant_diag_set: the verify-serial knob)");

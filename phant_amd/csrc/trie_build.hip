@@ -1744,6 +1744,9 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     t.seg_first = d_seg_first;
     t.n_tries = n_tries;
     t.roots = d_roots;
+    ws.trie_stats = TrieStats{};  // (phant_trie_stats: what THIS call did)
+    TrieStats& stats = ws.trie_stats;
+    stats.n = n;
     if (n >= 0x7fffffffu) {  // (identify_element keeps a bit of a boundary index for itself)
         err = "more than 2^31 - 2 keys in one call";
         return PHANT_E_UNSUPPORTED;
@@ -1799,6 +1802,8 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
             err = "trie workspace sized too small (internal)";
             return PHANT_E_DEVICE;
         }
+        stats.cursor_off = (size_t)(reinterpret_cast<const uint8_t*>(t.cursor) - ws.t1.base);
+        stats.has_cursor = true;
     }
 
     // head (roots, counters, a forest's start flags) -> [first_flag] -> lcp (+ markers, + the min-tree's padding): three or two
@@ -1810,7 +1815,11 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
         const bool fits = n <= SMALL_MAX_KEYS && (size_t)t.lvl_size[0] + tree_ints + FAN <= SMALL_LCP_INTS;  // (the first kernel's LDS)
         const bool by_default = fits && (n <= SMALL_SURE_KEYS || total_val_bytes >= (uint64_t)RATE * n);
         const bool small = ws.tune.small_max_keys >= 0 ? fits && n <= (uint64_t)ws.tune.small_max_keys : by_default;
-        if (small) return small_forest(ws, st, t, total_key_bytes, total_val_bytes, err, keep);
+        if (small) {
+            stats.pass = 1u;
+            return small_forest(ws, st, t, total_key_bytes, total_val_bytes, err, keep);
+        }
+        stats.pass = 2u;
     }
     if (n_tries == 1) t.first_flag = nullptr;
     {
@@ -1929,7 +1938,14 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     for (int d = 0; d < MAX_DEPTH_BINS; ++d) {
         depth_begin[d] = acc;
         acc += cnt[8 + d];
+        if (cnt[8 + d]) ++stats.bins;
+        stats.max_bin = std::max(stats.max_bin, cnt[8 + d]);
     }
+    stats.n_rep = n_rep;
+    stats.ahead = ahead ? 1u : 0u;
+    stats.deep_from = deep_from;
+    stats.misfit_off = (size_t)(reinterpret_cast<const uint8_t*>(t.misfit) - ws.t1.base);
+    stats.has_misfit = true;
 
     if (!ahead) {
         const int32_t rc = size_tables(n_rep);
@@ -1943,13 +1959,16 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     auto launch_bin = [&](int d, hipStream_t on) {
         const uint32_t c = cnt[8 + d];
         if (!c) return;
+        if (on != st) ++stats.side_bins;
         const bool no_coop = ws.tune.no_coop;
         const uint32_t coop_max = ws.tune.coop_max >= 0 ? (uint32_t)std::min<int64_t>(ws.tune.coop_max, 1 << 20) : COOP_MAX_NODES;
         if (c <= coop_max && !no_coop && !force_blocks) {
             // (the sponge's fetches share the CU's LDS pipeline: with one wave on a CU a permutation takes 4.9 us, with four 5.7 --
             // up to two waves per CU the workgroups are single waves, which the dispatcher spreads over the CUs)
             const bool no_wave = ws.tune.no_wave;  // (A/B: the half-wave kernel for every thin bin)
-            if (c <= WAVE_MAX_NODES && !no_wave) {  // a wave per node
+            const bool wave = c <= WAVE_MAX_NODES && !no_wave;
+            ++stats.by_class[wave ? 0 : 1];
+            if (wave) {  // a wave per node
                 if (c <= 512u) hipLaunchKernelGGL(branch_wave_kernel, dim3(c), dim3(64), 0, on, t, depth_begin[d], c);
                 else hipLaunchKernelGGL(branch_wave_kernel, dim3((c + 3u) / 4u), dim3(256), 0, on, t, depth_begin[d], c);
             } else if (c <= 1024u) {
@@ -1967,6 +1986,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
         }
         if (force_blocks == 1 || force_blocks == 2 || force_blocks == 4) blocks = (uint32_t)force_blocks;
         uint32_t* const mis = t.misfit + d;
+        ++stats.by_class[blocks == 1 ? 2 : blocks == 2 ? 3 : 4];
         if (blocks == 1)
             hipLaunchKernelGGL(branch_kernel<1>, dim3((c + 255u) / 256u), dim3(256), 0, on, t, t.order, depth_begin[d], c, nullptr, mis);
         else if (blocks == 2)
@@ -2026,8 +2046,10 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
         if (!ahead) hipLaunchKernelGGL(leaf_kernel, dim3(blocks(n)), dim3(256), 0, st, t, nullptr, nullptr);
         // (leaves of 136 .. 543 bytes: identify_kernel said whether there can be any -- a grid of lanes that only find out that
         // their leaf is small was 24 us per million keys)
-        if (cnt[3])
+        if (cnt[3]) {
+            stats.leaf_big = 1u;
             hipLaunchKernelGGL(leaf_big_kernel, dim3((n + BRANCH_LANES - 1u) / BRANCH_LANES), dim3(BRANCH_LANES), 0, st, t);
+        }
         for (int d = MAX_DEPTH_BINS - 1; d >= 0; --d) launch_bin(d, st);
     }
     // The end of the call the same way: finish_kernel, last in the stream, puts the overflow flag into the mailbox and raises
