@@ -375,6 +375,105 @@ PHANT_API int32_t phant_ecrecover_batch_dev(phant_ctx *ctx, const uint8_t *d_has
 PHANT_API int32_t phant_tx_senders(phant_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, uint32_t n,
                                    uint64_t chain_id, uint8_t *addresses20, uint8_t *status);
 
+/* ------------------------------------------------- a block's transactions: decode, hash, pre-execution checks
+ * Everything src/blockchain/blockchain.zig `applyBody` needs of a transaction before it touches state, for n raw transactions in
+ * one call: the decoded fields (src/types/transaction.zig:152-273), Tx.hash, the signing hash and the sender
+ * (src/signer/signer.zig:40-188), `calculateIntrinsicCost` (blockchain.zig:355-381) and the state-free rules of
+ * `checkTransaction` / `validateTransaction` (:237-260, :345-353).  The raw bytes are uploaded once and read by kernels only;
+ * nothing is decoded, spliced or hashed on the host.
+ *
+ * Input: transaction i = txs[tx_off[i] .. tx_off[i+1]) (n + 1 offsets from 0, never backwards; device form: up to tx_bytes), a
+ * legacy RLP list, 0x01 || rlp or 0x02 || rlp, decoded exactly as strictly as phant_tx_senders decodes; chain_id; base_fee
+ * (32 bytes big-endian, HOST memory in both forms; NULL skips the two fee rules); block_gas_limit, read with
+ * PHANT_TXS_HAVE_GAS_LIMIT.  PHANT_TXS_NO_RECOVERY skips the secp256k1 launch: sender and sig_status must then be NULL.
+ *
+ * Output, struct-of-arrays of n rows, any pointer may be NULL.  Integers of 32 bytes are big-endian.
+ *   tx_hash (32)       keccak256 of the raw bytes; always defined (a zero-length transaction: the hash of the empty string)
+ *   sig_hash (32)      what was signed: the items in front of v under a list header of their own (EIP-155: + chain_id, 0, 0)
+ *   sender (20), sig_status (1)   value for value what phant_tx_senders writes for the same input (PHANT_SIG_*)
+ *   sig (65)           r || s || recid
+ *   type (1), chain_id, nonce, gas_limit (uint64_t)   chain_id of a legacy transaction: (v - 35) >> 1, 0 for v = 27 / 28
+ *   gas_price (32)     getGasPrice(): max_fee_per_gas for type 2
+ *   priority_fee (32)  max_priority_fee_per_gas; the gas price for types 0 and 1
+ *   value (32), to (20; zero for a creation, which is a flag bit)
+ *   data_off (uint64_t, into txs), data_len (uint32_t); al_off / al_len: the access list's payload span in txs (0, 0 for a
+ *   legacy transaction); al_addresses, al_keys (uint32_t): its tuples and its storage keys
+ *   intrinsic_gas (uint64_t) = 21000 + 4 (zero data bytes) + 16 (non-zero data bytes) + 2400 al_addresses + 1900 al_keys, for a
+ *                      creation + 32000 + 2 ceil(data_len / 32)   (src/blockchain/params.zig:7-15)
+ *   effective_gas_price (32)  type 2: min(priority_fee, gas_price - base_fee) + base_fee, else gas_price; zero when base_fee is NULL
+ *                      or a fee rule fails
+ *   upfront_cost (32) = gas_limit x gas_price + value, what blockchain.zig:268-274 compares with the sender's balance
+ *   flags (uint32_t)   below; every failed rule is reported, and the lowest set error bit is the error the reference returns first
+ * A transaction that does not decode (PHANT_TX_UNDECODABLE) has zero rows except tx_hash, flags and sig_status (PHANT_SIG_BAD_TX);
+ * none of the other rules is evaluated for it.  With PHANT_TX_BAD_V the fields and rules are there, sig_hash, sig and sender are zero.
+ * first_bad (always written): the least i whose flags carry an error bit, n if none. */
+#define PHANT_TXS_HAVE_GAS_LIMIT 1u
+#define PHANT_TXS_NO_RECOVERY 2u
+#define PHANT_TX_UNDECODABLE 0x001u        /* what phant_tx_senders calls PHANT_SIG_BAD_TX */
+#define PHANT_TX_BAD_V 0x002u              /* as PHANT_SIG_BAD_V */
+#define PHANT_TX_SIGNATURE 0x004u          /* the recovery failed; sig_status says how */
+#define PHANT_TX_CHAIN_ID 0x008u           /* a typed transaction whose chain_id field is not the call's.  AN ADDITION: the reference never
+                                            * checks it (signer.zig:149,176 sign with the transaction's own id) */
+#define PHANT_TX_PRIORITY_ABOVE_MAX 0x010u /* InvalidMaxFeePerGas: type 2, max_fee_per_gas < max_priority_fee_per_gas */
+#define PHANT_TX_FEE_BELOW_BASE 0x020u     /* MaxFeePerGasLowerThanBaseFee / GasPriceLowerThanBaseFee */
+#define PHANT_TX_GAS_ABOVE_BLOCK 0x040u    /* gas_limit > block_gas_limit: the state-free part of InsufficientGas; the running
+                                            * gas_available needs execution and stays with the caller */
+#define PHANT_TX_INTRINSIC_GAS 0x080u      /* intrinsic_gas > gas_limit */
+#define PHANT_TX_NONCE_MAX 0x100u          /* nonce == 2^64 - 1 (EIP-2681).  A DEVIATION: the reference's constant (2 << 64) - 1 at
+                                            * blockchain.zig:348 can never trigger for a u64 */
+#define PHANT_TX_INITCODE_SIZE 0x200u      /* a creation with more than 2 x 0x6000 bytes of data */
+#define PHANT_TX_COST_OVERFLOW 0x400u      /* upfront_cost exceeds 2^256 - 1; its row is zero */
+#define PHANT_TX_IS_CREATE 0x800u          /* no error: `to` is empty */
+/* A bad transaction is a flag, never an error.  PHANT_E_INVALID_ARG: a wrong struct_size, NULL txs / tx_off with n > 0, offsets
+ * that go backwards or do not run from 0 (device form: to tx_bytes), unknown flag bits, sender or sig_status together with
+ * PHANT_TXS_NO_RECOVERY.  PHANT_E_UNSUPPORTED: a single transaction of 2^32 bytes or more.  n == 0 is PHANT_OK with first_bad =
+ * 0.  The host form checks before anything is copied: one staged upload, the launches, one synchronisation.
+ *
+ * Device form: txs, tx_off and every output are device memory, the uint64_t arrays 8-byte, the uint32_t arrays 4-byte aligned,
+ * byte arrays not at all; both structs and base_fee are host memory.  tx_off is checked on the device before any kernel
+ * indexes with it.  The call synchronises the ctx stream (first_bad is valid when it returns). */
+typedef struct phant_txs_in {
+    uint32_t struct_size; /* = sizeof(phant_txs_in) */
+    uint32_t n;
+    uint32_t flags;       /* PHANT_TXS_* */
+    uint32_t reserved;    /* 0 */
+    const uint8_t *txs;
+    const uint64_t *tx_off;  /* n + 1 */
+    uint64_t tx_bytes;       /* device form: tx_off[n] as the caller states it */
+    uint64_t chain_id;
+    const uint8_t *base_fee; /* 32 bytes, host memory, or NULL */
+    uint64_t block_gas_limit;
+} phant_txs_in;
+typedef struct phant_txs_out {
+    uint32_t struct_size; /* = sizeof(phant_txs_out) */
+    uint32_t first_bad;   /* result */
+    uint8_t *tx_hash;
+    uint8_t *sig_hash;
+    uint8_t *sender;
+    uint8_t *sig_status;
+    uint8_t *sig;
+    uint8_t *type;
+    uint64_t *chain_id;
+    uint64_t *nonce;
+    uint64_t *gas_limit;
+    uint8_t *gas_price;
+    uint8_t *priority_fee;
+    uint8_t *value;
+    uint8_t *to;
+    uint64_t *data_off;
+    uint32_t *data_len;
+    uint64_t *al_off;
+    uint32_t *al_len;
+    uint32_t *al_addresses;
+    uint32_t *al_keys;
+    uint64_t *intrinsic_gas;
+    uint8_t *effective_gas_price;
+    uint8_t *upfront_cost;
+    uint32_t *flags;
+} phant_txs_out;
+PHANT_API int32_t phant_block_transactions(phant_ctx *ctx, const phant_txs_in *in, phant_txs_out *out);
+PHANT_API int32_t phant_block_transactions_dev(phant_ctx *ctx, const phant_txs_in *in, phant_txs_out *out);
+
 /* ------------------------------------------------------- proof verification
  * ABSENT in the reference: this is the call the TODO at
  * src/engine_api/execution_payload.zig:177-178 asks for (witness field

@@ -70,6 +70,8 @@ SYMBOLS = {
     "phant_ecrecover_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_ecrecover_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_tx_senders": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp]),
+    "phant_block_transactions": (_i32, [_vp, _vp, _vp]),
+    "phant_block_transactions_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_verify_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_mpt_verify_batch_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
@@ -178,6 +180,31 @@ class PhantHeadersOut(C.Structure):
     """phant_headers_out (include/phant_gpu.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("first_bad", C.c_uint32), ("enc_cap", C.c_uint64), ("hashes", C.c_void_p),
                 ("flags", C.c_void_p), ("enc", C.c_void_p), ("enc_off", C.c_void_p), ("enc_len", C.c_uint64)]
+
+
+TXS_HAVE_GAS_LIMIT, TXS_NO_RECOVERY = 1, 2
+# phant_txs_out's arrays in the struct's order: (name, numpy dtype, elements per transaction)
+TX_OUTPUTS = (("tx_hash", "u1", 32), ("sig_hash", "u1", 32), ("sender", "u1", 20), ("sig_status", "u1", 1), ("sig", "u1", 65), ("type", "u1", 1),
+              ("chain_id", "u8", 1), ("nonce", "u8", 1), ("gas_limit", "u8", 1), ("gas_price", "u1", 32), ("priority_fee", "u1", 32),
+              ("value", "u1", 32), ("to", "u1", 20), ("data_off", "u8", 1), ("data_len", "u4", 1), ("al_off", "u8", 1), ("al_len", "u4", 1),
+              ("al_addresses", "u4", 1), ("al_keys", "u4", 1), ("intrinsic_gas", "u8", 1), ("effective_gas_price", "u1", 32),
+              ("upfront_cost", "u1", 32), ("flags", "u4", 1))
+# PHANT_TX_*: bit k of flags[i]; every bit below IsCreate is an error
+TX_FLAG_NAMES = ("Undecodable", "BadV", "Signature", "ChainId", "PriorityAboveMax", "FeeBelowBase", "GasAboveBlock", "IntrinsicGas", "NonceMax",
+                 "InitcodeSize", "CostOverflow", "IsCreate")
+TX_ERROR_BITS = 0x7FF
+
+
+class PhantTxsIn(C.Structure):
+    """phant_txs_in (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("txs", C.c_void_p),
+                ("tx_off", C.c_void_p), ("tx_bytes", C.c_uint64), ("chain_id", C.c_uint64), ("base_fee", C.c_void_p),
+                ("block_gas_limit", C.c_uint64)]
+
+
+class PhantTxsOut(C.Structure):
+    """phant_txs_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("first_bad", C.c_uint32)] + [(name, C.c_void_p) for name, _, _ in TX_OUTPUTS]
 
 
 class PhantProveOut(C.Structure):

@@ -13,6 +13,9 @@
 //                   the receipts root of a block in one call (receipts.hip.h)
 //   block headers   src/types/block.zig:51-69 + src/blockchain/blockchain.zig:100-145  encodings, hashes and validateBlockHeader of
 //                   whole chain segments in one call (headers.hip.h)
+//   transactions    src/types/transaction.zig:152-273 + src/blockchain/blockchain.zig:237-260,345-381  decode, both hashes, senders,
+//                   intrinsic gas and the state-free rules of a block's transactions in one call (transactions.hip.h, behind
+//                   ecrecover_kernel below, which it launches)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
@@ -255,3 +258,5 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 }
 
 }  // namespace phant
+
+#include "transactions.hip.h"

@@ -21,6 +21,7 @@
 #include "launch.h"
 #include "receipts.h"
 #include "headers.h"
+#include "transactions.h"
 #include "trie_build.h"
 #include "witness.h"
 #include "host_rlp.h"
@@ -874,6 +875,45 @@ int32_t phant_tx_senders(phant_ctx* c, const uint8_t* txs, const uint64_t* tx_of
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the host vectors above live until here)
     return PHANT_OK;
 }
+
+/* ------------------------------------------------- a block's transactions (transactions.hip.h) */
+
+static int32_t block_transactions_impl(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out, bool dev) {
+    const char* const who = dev ? "block_transactions_dev" : "block_transactions";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_txs_in) || out->struct_size != sizeof(phant_txs_out)) return bad("wrong struct_size");
+    if (in->flags & ~(PHANT_TXS_HAVE_GAS_LIMIT | PHANT_TXS_NO_RECOVERY)) return bad("unknown flag");
+    if ((in->flags & PHANT_TXS_NO_RECOVERY) && (out->sender || out->sig_status)) return bad("sender / sig_status asked for together with the no-recovery flag");
+    const uint32_t n = in->n;
+    if (n == 0) {
+        out->first_bad = 0;
+        return PHANT_OK;
+    }
+    if (!in->tx_off || !in->txs) return bad("null txs / tx_off");
+    if (dev) {  // (tx_off is read by kernels as words; the outputs arrive by device-to-device copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->tx_off | (uintptr_t)out->chain_id | (uintptr_t)out->nonce | (uintptr_t)out->gas_limit |
+                             (uintptr_t)out->data_off | (uintptr_t)out->al_off | (uintptr_t)out->intrinsic_gas;
+        const uintptr_t w4 = (uintptr_t)out->data_len | (uintptr_t)out->al_len | (uintptr_t)out->al_addresses | (uintptr_t)out->al_keys |
+                             (uintptr_t)out->flags;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    DeviceGuard g(c->device);
+    if (!(in->flags & PHANT_TXS_NO_RECOVERY))
+        if (const int32_t rc = ensure_gtable(c)) return rc;
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_txs_out res = *out;
+    const int32_t rc = phant::block_transactions(c->ws, c->stream, *in, res, dev, c->secp_gtable, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->first_bad = res.first_bad;
+    return PHANT_OK;
+}
+
+int32_t phant_block_transactions(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out) { return block_transactions_impl(c, in, out, false); }
+
+int32_t phant_block_transactions_dev(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out) { return block_transactions_impl(c, in, out, true); }
 
 int32_t phant_diag_secp_op(phant_ctx* c, uint32_t op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out) {
     if (!c) return PHANT_E_INVALID_ARG;

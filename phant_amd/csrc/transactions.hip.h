@@ -1,0 +1,714 @@
+// transactions.hip.h -- a block's transactions end to end on the device (included by bulk_keccak.hip): the strict decode of
+// src/types/transaction.zig:152-273, both hashes of every transaction (Tx.hash and the signing hash of src/signer/signer.zig:81-188),
+// the sender (secp256k1.hip.h), src/blockchain/blockchain.zig:355-381 `calculateIntrinsicCost` and the state-free rules of
+// `checkTransaction` / `validateTransaction` (:237-260, :345-353).  The raw bytes are read by kernels only, and no signing preimage is
+// ever written anywhere: the signing sponge takes it from where it lies in the transaction.
+//
+//   tx_check_args_kernel  device form only: tx_off runs from 0 to tx_bytes, never backwards, no transaction of 4 GiB; a lane per
+//                         entry, and the host reads the verdict before any other kernel indexes with the offsets
+//   tx_decode_kernel      a lane per transaction: tx::decode (below; its access-list walk is serial in its lane), the field rows, r / s /
+//                         recid for the recovery, and the PLAN of the signing preimage:
+//                             prefix (type byte, new list header: <= 10 bytes)  ||  raw[body_begin, body_end)  ||  suffix (EIP-155: rlp(chain_id),
+//                             0x80, 0x80: <= 11 bytes)
+//   tx_hash_kernel        a lane per transaction, two runs of one sponge loop: the raw bytes (with the calldata's non-zero bytes counted
+//                         on the dwords the sponge has loaded anyway), then the plan.  Block k of the signing sponge starts at raw offset
+//                         body_begin + 136 k - prefix_len: its first and last blocks mix bytes from registers with bytes from memory
+//   (ecrecover_kernel)    bulk_keccak.hip's, with PHANT_RECOVER_LOW_S; a transaction the decode refused arrives with its verdict in
+//                         pre_status and never reaches the curve arithmetic
+//   tx_rules_kernel       a lane per transaction: intrinsic gas, the fee rules, gas_limit x gas_price + value in 320 bits, flags, and the
+//                         least flagged index by one atomic
+//
+// Plain C++ plus the builtins the sponge uses: tests/emu.py compiles this file for the host.  With PHANT_TX_DECODE_ONLY defined only
+// tx::decode and what it needs are declared, without any HIP header: tests/native/tx_decode_main.cpp builds it as a program of its own.
+#pragma once
+#include <stdint.h>
+
+#ifdef PHANT_TX_DECODE_ONLY
+#define TX_HD inline
+#else
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "../../include/phant_gpu.h"
+#include "absorb.hip.h"
+#include "launch.h"
+#include "secp256k1.hip.h"
+#include "transactions.h"
+#define TX_HD __host__ __device__ inline
+#endif
+
+namespace phant {
+namespace tx {
+
+// the decode's verdicts: PHANT_SIG_OK, PHANT_SIG_BAD_TX, PHANT_SIG_BAD_V (include/phant_gpu.h)
+enum : uint8_t { ST_OK = 0, ST_BAD_TX = 6, ST_BAD_V = 7 };
+
+// a string item's payload inside the transaction
+struct Span {
+    uint32_t at, len;
+};
+
+// What one transaction decodes to.  Positions are relative to the transaction's first byte (a transaction is shorter than 4 GiB).
+struct Decoded {
+    uint8_t status;  // ST_*; with ST_BAD_TX nothing else is defined
+    uint8_t type;    // 0, 1, 2
+    uint8_t recid;   // ST_OK only
+    uint8_t eip155;  // legacy, v = 35 + 2 chain_id + {0, 1}
+    uint8_t create;  // `to` is empty
+    uint64_t chain_id_field, nonce, gas_limit;  // chain_id_field: typed transactions
+    Span priority, gas_price, value, to, data, al, r, s;  // al: the access list's payload; priority = gas_price for types 0 and 1
+    uint32_t al_addresses, al_keys;
+    // the signing preimage = prefix || raw[body_begin, body_end) || suffix (ST_OK only)
+    uint32_t body_begin, body_end;
+    uint8_t prefix_len, suffix_len;
+    uint8_t prefix[12], suffix[12];  // 10 and 11 bytes used
+};
+
+// One canonical RLP item at p[pos ..) with everything up to `end` left: its payload [pay, pend), which ends the item.  Every length is
+// compared with what is left BEFORE it is added to a position (a declared length can be 2^64 - 1).  The strictness is
+// host_rlp.cpp::host_rlp_item's.
+TX_HD bool rlp_item(const uint8_t* p, uint32_t pos, uint32_t end, uint32_t& pay, uint32_t& pend, bool& is_list) {
+    if (pos >= end) return false;
+    const uint32_t avail = end - pos, b = p[pos];
+    if (b < 0x80u) {
+        pay = pos, pend = pos + 1u, is_list = false;
+        return true;
+    }
+    if (b <= 0xb7u || (b >= 0xc0u && b <= 0xf7u)) {
+        is_list = b >= 0xc0u;
+        const uint32_t len = b - (is_list ? 0xc0u : 0x80u);
+        if (len > avail - 1u) return false;
+        if (!is_list && len == 1u && p[pos + 1u] < 0x80u) return false;
+        pay = pos + 1u, pend = pay + len;
+        return true;
+    }
+    is_list = b >= 0xf8u;
+    const uint32_t ll = b - (is_list ? 0xf7u : 0xb7u);  // 1 .. 8
+    if (ll > avail - 1u || p[pos + 1u] == 0u) return false;
+    uint64_t l = 0;
+    for (uint32_t k = 0; k < ll; ++k) l = l << 8 | p[pos + 1u + k];
+    if (l <= 55u || l > (uint64_t)(avail - 1u - ll)) return false;
+    pay = pos + 1u + ll, pend = pay + (uint32_t)l;
+    return true;
+}
+
+// a string of at most max_bytes bytes without a leading zero
+TX_HD bool uint_ok(const uint8_t* p, uint32_t pay, uint32_t pend, bool is_list, uint32_t max_bytes) {
+    return !is_list && pend - pay <= max_bytes && (pend == pay || p[pay] != 0u);
+}
+TX_HD uint64_t be_u64(const uint8_t* p, uint32_t pay, uint32_t pend) {
+    uint64_t v = 0;
+    for (uint32_t k = pay; k < pend; ++k) v = v << 8 | p[k];
+    return v;
+}
+
+// [[address20, [key32, ...]], ...] inside [pay, pend), nothing else inside a tuple; serial in its lane
+TX_HD bool access_list(const uint8_t* p, uint32_t pay, uint32_t pend, uint32_t& addresses, uint32_t& keys) {
+    addresses = keys = 0;
+    uint32_t pos = pay;
+    while (pos < pend) {
+        uint32_t tp, te, ip, ie;
+        bool list;
+        if (!rlp_item(p, pos, pend, tp, te, list) || !list) return false;  // the tuple
+        if (!rlp_item(p, tp, te, ip, ie, list) || list || ie - ip != 20u) return false;  // the address
+        uint32_t kp, ke;
+        if (!rlp_item(p, ie, te, kp, ke, list) || !list || ke != te) return false;  // the keys, and nothing after
+        ++addresses;
+        while (kp < ke) {
+            if (!rlp_item(p, kp, ke, ip, ie, list) || list || ie - ip != 32u) return false;
+            ++keys;
+            kp = ie;
+        }
+        pos = te;
+    }
+    return true;
+}
+
+// a list header for `len` payload bytes -> bytes written (at most 9)
+TX_HD uint32_t put_list_header(uint8_t* o, uint64_t len) {
+    if (len <= 55u) return o[0] = (uint8_t)(0xc0u + len), 1u;
+    uint32_t ll = 0;
+    for (uint64_t l = len; l; l >>= 8) ++ll;
+    o[0] = (uint8_t)(0xf7u + ll);
+    for (uint32_t q = 0; q < ll; ++q) o[1u + q] = (uint8_t)(len >> (8u * (ll - 1u - q)));
+    return 1u + ll;
+}
+
+// The item kinds of a transaction in the order of a type-2 list; type 1 has no PRIORITY, type 0 neither CHAIN_ID nor ACCESS_LIST.
+enum : uint32_t { K_CHAIN_ID, K_NONCE, K_PRIORITY, K_GAS_PRICE, K_GAS, K_TO, K_VALUE, K_DATA, K_ACCESS_LIST, K_V, K_R, K_S, K_END };
+TX_HD uint32_t kind_of(uint32_t type, uint32_t idx) {
+    if (type == 2u) return idx;
+    if (type == 1u) return idx < 2u ? idx : idx + 1u;
+    return idx == 0u ? (uint32_t)K_NONCE : idx <= 5u ? idx + 2u : idx + 3u;
+}
+
+// Transaction p[0, len) -> d, with exactly the verdicts of host_rlp.cpp::tx_signing_parts (which phant_tx_senders decodes with):
+// canonical RLP, the item count of the type, integers without leading zeros and within their widths, `to` empty or 20 bytes, a
+// well-formed access list, nothing behind the list.  Every read stays inside p[0, len).
+TX_HD void decode(const uint8_t* p, uint32_t len, uint64_t chain_id, Decoded& d) {
+    d.status = ST_BAD_TX;
+    d.type = d.recid = d.eip155 = d.create = 0;
+    d.chain_id_field = d.nonce = d.gas_limit = 0;
+    d.al_addresses = d.al_keys = 0;
+    d.body_begin = d.body_end = 0;
+    d.prefix_len = d.suffix_len = 0;
+    const Span none = {0u, 0u};
+    d.priority = d.gas_price = d.value = d.to = d.data = d.al = d.r = d.s = none;
+    if (len == 0u) return;
+    uint32_t start = 0;
+    if (p[0] < 0x80u) {  // EIP-2718: a type byte in front of the list
+        d.type = p[0];
+        if (d.type != 1u && d.type != 2u) return;
+        start = 1u;
+    }
+    uint32_t pay, pend;
+    bool is_list;
+    if (!rlp_item(p, start, len, pay, pend, is_list) || !is_list || pend != len) return;
+    Span v = none;
+    uint32_t v_full = 0, idx = 0, pos = pay;
+    while (pos < pend) {
+        const uint32_t kind = kind_of(d.type, idx);
+        uint32_t ip, ie;
+        bool il;
+        if (kind >= K_END || !rlp_item(p, pos, pend, ip, ie, il)) return;
+        const Span sp = {ip, ie - ip};
+        switch (kind) {
+        case K_CHAIN_ID:
+            if (!uint_ok(p, ip, ie, il, 8u)) return;
+            d.chain_id_field = be_u64(p, ip, ie);
+            break;
+        case K_NONCE:
+            if (!uint_ok(p, ip, ie, il, 8u)) return;
+            d.nonce = be_u64(p, ip, ie);
+            break;
+        case K_GAS:
+            if (!uint_ok(p, ip, ie, il, 8u)) return;
+            d.gas_limit = be_u64(p, ip, ie);
+            break;
+        case K_PRIORITY:
+            if (!uint_ok(p, ip, ie, il, 32u)) return;
+            d.priority = sp;
+            break;
+        case K_GAS_PRICE:
+            if (!uint_ok(p, ip, ie, il, 32u)) return;
+            d.gas_price = sp;
+            break;
+        case K_VALUE:
+            if (!uint_ok(p, ip, ie, il, 32u)) return;
+            d.value = sp;
+            break;
+        case K_TO:
+            if (il || (sp.len != 0u && sp.len != 20u)) return;
+            d.to = sp, d.create = sp.len == 0u;
+            break;
+        case K_DATA:
+            if (il) return;
+            d.data = sp;
+            break;
+        case K_ACCESS_LIST:
+            if (!il || !access_list(p, ip, ie, d.al_addresses, d.al_keys)) return;
+            d.al = sp;
+            break;
+        case K_V:
+            if (!uint_ok(p, ip, ie, il, 32u)) return;
+            v = sp, v_full = pos;
+            break;
+        case K_R:
+            if (!uint_ok(p, ip, ie, il, 32u)) return;
+            d.r = sp;
+            break;
+        default:  // K_S
+            if (!uint_ok(p, ip, ie, il, 32u)) return;
+            d.s = sp;
+            break;
+        }
+        pos = ie, ++idx;
+    }
+    if (kind_of(d.type, idx) != K_END) return;  // too few items
+    if (d.type != 2u) d.priority = d.gas_price;
+    // v: a value of more than 9 bytes matches nothing below (35 + 2 chain_id + 1 < 2^66); 72 bits as (hi, lo)
+    d.status = ST_BAD_V;
+    if (v.len > 9u) return;
+    const uint32_t v_hi = v.len == 9u ? p[v.at] : 0u;
+    const uint64_t v_lo = be_u64(p, v.len == 9u ? v.at + 1u : v.at, v.at + v.len);
+    if (d.type == 0u) {
+        const uint64_t twice = chain_id << 1, b_lo = twice + 35u;
+        const uint32_t b_hi = (uint32_t)(chain_id >> 63) + (b_lo < twice ? 1u : 0u);
+        const uint64_t c_lo = b_lo + 1u;
+        const uint32_t c_hi = b_hi + (c_lo == 0u ? 1u : 0u);
+        if (v_hi == 0u && (v_lo == 27u || v_lo == 28u)) d.recid = (uint8_t)(v_lo - 27u);
+        else if (v_hi == b_hi && v_lo == b_lo) d.recid = 0, d.eip155 = 1;
+        else if (v_hi == c_hi && v_lo == c_lo) d.recid = 1, d.eip155 = 1;
+        else return;
+    } else {
+        if (v_hi != 0u || v_lo > 1u) return;
+        d.recid = (uint8_t)v_lo;
+    }
+    d.status = ST_OK;
+    // the signed list: the items in front of v, verbatim, (chain_id, 0, 0 for EIP-155,) under a header of their own
+    d.body_begin = pay, d.body_end = v_full;
+    if (d.eip155) {
+        uint32_t ll = 0;
+        for (uint64_t c = chain_id; c; c >>= 8) ++ll;
+        uint32_t t = 0;
+        if (ll == 1u && chain_id < 0x80u) d.suffix[t++] = (uint8_t)chain_id;
+        else {
+            d.suffix[t++] = (uint8_t)(0x80u + ll);
+            for (uint32_t q = 0; q < ll; ++q) d.suffix[t++] = (uint8_t)(chain_id >> (8u * (ll - 1u - q)));
+        }
+        d.suffix[t++] = 0x80u, d.suffix[t++] = 0x80u;
+        d.suffix_len = (uint8_t)t;
+    }
+    uint32_t h = 0;
+    if (d.type) d.prefix[h++] = d.type;
+    h += put_list_header(d.prefix + h, (uint64_t)(d.body_end - d.body_begin) + d.suffix_len);
+    d.prefix_len = (uint8_t)h;
+}
+
+}  // namespace tx
+}  // namespace phant
+
+#ifndef PHANT_TX_DECODE_ONLY
+namespace phant {
+namespace tx {
+
+using In = phant_txs_in;
+using Out = phant_txs_out;
+
+enum : uint32_t { F_INVALID = 1u, F_TOO_LONG = 2u };
+// the call's control words (32-bit, device memory, zeroed): [0] = F_*, [1] = n - (the least flagged index) or 0
+constexpr size_t CTL_WORDS = 8;
+constexpr uint32_t ERROR_BITS = PHANT_TX_IS_CREATE - 1u;
+
+// the call's outputs in the order they lie in the arena, the ones most callers want first (the host form fetches one span that ends
+// behind the last wanted one): X(member, element type, elements per transaction)
+#define TX_OUTPUTS(X)                                                                                                              \
+    X(flags, uint32_t, 1) X(tx_hash, uint8_t, 32) X(sender, uint8_t, 20) X(sig_status, uint8_t, 1) X(sig_hash, uint8_t, 32)           \
+    X(intrinsic_gas, uint64_t, 1) X(effective_gas_price, uint8_t, 32) X(upfront_cost, uint8_t, 32) X(type, uint8_t, 1)                 \
+    X(nonce, uint64_t, 1) X(gas_limit, uint64_t, 1) X(chain_id, uint64_t, 1) X(gas_price, uint8_t, 32) X(priority_fee, uint8_t, 32)    \
+    X(value, uint8_t, 32) X(to, uint8_t, 20) X(data_off, uint64_t, 1) X(data_len, uint32_t, 1) X(al_off, uint64_t, 1)                  \
+    X(al_len, uint32_t, 1) X(al_addresses, uint32_t, 1) X(al_keys, uint32_t, 1) X(sig, uint8_t, 65)
+
+// what tx_decode_kernel leaves for tx_hash_kernel: 48 bytes a transaction, read as three 16-byte loads
+struct __attribute__((aligned(16))) Plan {
+    uint32_t body_begin, body_end, lens;  // lens = prefix_len | suffix_len << 8 | (the decode's verdict) << 16
+    uint32_t data_at, data_len;           // the calldata inside the transaction (0, 0 when it did not decode)
+    uint32_t prefix[3], suffix[3];
+    uint32_t pad;
+};
+static_assert(sizeof(Plan) == 48, "three 16-byte loads");
+
+// the device arrays of a call (Out's members point into the arena), r / s / recid / the decode's verdicts for ecrecover_kernel
+struct Dev {
+    Out o;
+    Plan* plan;
+    uint8_t *r, *s, *recid, *pre_status;
+    uint32_t* ctl;
+};
+struct Rules {
+    uint32_t base_fee[8];  // little-endian limbs
+    uint32_t have_base_fee, have_gas_limit;
+    uint64_t block_gas_limit;
+};
+
+// Device form only: what a caller can lie about, a lane per entry, before any kernel indexes with it.
+__global__ void __launch_bounds__(256) tx_check_args_kernel(const uint64_t* __restrict__ tx_off, uint32_t n, uint64_t tx_bytes, uint32_t* __restrict__ ctl) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = tx_off[i], e = tx_off[i + 1u];
+    uint32_t f = 0;
+    if (e < b || (i == 0u && b != 0u) || (i + 1u == n && e != tx_bytes)) f |= F_INVALID;
+    else if (e - b > 0xffffffffull) f |= F_TOO_LONG;
+    if (f) atomicOr(ctl, f);
+}
+
+TX_HD void put_be32(uint8_t* row, const uint8_t* p, Span sp) {
+    for (uint32_t k = 0; k < 32u; ++k) row[k] = k < 32u - sp.len ? (uint8_t)0 : p[sp.at + k - (32u - sp.len)];
+}
+TX_HD uint32_t pack4(const uint8_t* b) { return (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; }
+
+__global__ void __launch_bounds__(64) tx_decode_kernel(const uint8_t* __restrict__ txs, const uint64_t* __restrict__ tx_off, uint32_t n,
+                                                        uint64_t chain_id, Dev dv) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = tx_off[i];
+    const uint32_t len = (uint32_t)(tx_off[i + 1u] - b);  // (checked: below 4 GiB)
+    const uint8_t* const p = txs + b;
+    Decoded d;
+    decode(p, len, chain_id, d);
+    const bool dec = d.status != ST_BAD_TX, ok = d.status == ST_OK;
+    const Span none = {0u, 0u};
+    const Out& o = dv.o;
+    o.flags[i] = !dec ? PHANT_TX_UNDECODABLE
+                      : (ok ? 0u : PHANT_TX_BAD_V) | (d.create ? PHANT_TX_IS_CREATE : 0u) | (d.type && d.chain_id_field != chain_id ? PHANT_TX_CHAIN_ID : 0u);
+    o.type[i] = dec ? d.type : (uint8_t)0;
+    o.nonce[i] = dec ? d.nonce : 0u;
+    o.gas_limit[i] = dec ? d.gas_limit : 0u;
+    o.chain_id[i] = !dec ? 0u : d.type ? d.chain_id_field : d.eip155 ? chain_id : 0u;
+    put_be32(o.gas_price + 32ull * i, p, dec ? d.gas_price : none);
+    put_be32(o.priority_fee + 32ull * i, p, dec ? d.priority : none);
+    put_be32(o.value + 32ull * i, p, dec ? d.value : none);
+    for (uint32_t k = 0; k < 20u; ++k) o.to[20ull * i + k] = dec && d.to.len ? p[d.to.at + k] : (uint8_t)0;
+    o.data_off[i] = dec ? b + d.data.at : 0u;
+    o.data_len[i] = dec ? d.data.len : 0u;
+    o.al_off[i] = dec && d.type ? b + d.al.at : 0u;
+    o.al_len[i] = dec ? d.al.len : 0u;
+    o.al_addresses[i] = dec ? d.al_addresses : 0u;
+    o.al_keys[i] = dec ? d.al_keys : 0u;
+    // r, s, recid: for ecrecover_kernel (rows of 32 / 32 / 1) and as the caller's 65-byte row
+    put_be32(dv.r + 32ull * i, p, ok ? d.r : none);
+    put_be32(dv.s + 32ull * i, p, ok ? d.s : none);
+    dv.recid[i] = ok ? d.recid : (uint8_t)0;
+    dv.pre_status[i] = d.status;
+    uint8_t* const sg = o.sig + 65ull * i;
+    for (uint32_t k = 0; k < 32u; ++k) sg[k] = dv.r[32ull * i + k], sg[32u + k] = dv.s[32ull * i + k];
+    sg[64] = dv.recid[i];
+    Plan pl;
+    pl.body_begin = d.body_begin, pl.body_end = d.body_end;
+    pl.lens = (uint32_t)d.prefix_len | (uint32_t)d.suffix_len << 8 | (uint32_t)d.status << 16;
+    pl.data_at = dec ? d.data.at : 0u, pl.data_len = dec ? d.data.len : 0u;
+    for (uint32_t k = 0; k < 12u; ++k) {
+        if (k >= d.prefix_len) d.prefix[k] = 0;
+        if (k >= d.suffix_len) d.suffix[k] = 0;
+    }
+    for (uint32_t k = 0; k < 3u; ++k) pl.prefix[k] = pack4(d.prefix + 4u * k), pl.suffix[k] = pack4(d.suffix + 4u * k);
+    pl.pad = 0;
+    dv.plan[i] = pl;
+}
+
+// ---- the two hashes: one sponge loop over   prefix (registers) || body (memory) || suffix (registers)
+struct __attribute__((packed, aligned(1))) PackedU32 { uint32_t x; };
+PHANT_DEV uint32_t load32(const uint8_t* __restrict__ p) { return reinterpret_cast<const PackedU32*>(p)->x; }
+// byte q (< 12) of three dwords, without indexing registers by a variable
+PHANT_DEV uint32_t byte_of(const uint32_t (&w)[3], uint32_t q) {
+    const uint32_t d = q < 4u ? w[0] : q < 8u ? w[1] : w[2];
+    return (d >> (8u * (q & 3u))) & 0xffu;
+}
+struct Message {
+    const uint8_t* body;  // message byte j, pl <= j < pl + bl, is body[j - pl]
+    uint32_t pl, bl;
+    uint64_t total;       // pl + bl + the suffix's bytes (64 bits: a transaction may be a few bytes short of 4 GiB)
+    uint32_t prefix[3], suffix[3];
+};
+PHANT_DEV uint32_t message_byte(const Message& m, uint64_t j) {
+    if (j < m.pl) return byte_of(m.prefix, (uint32_t)j);
+    if (j - m.pl < m.bl) return m.body[j - m.pl];
+    return j < m.total ? byte_of(m.suffix, (uint32_t)(j - m.pl - m.bl)) : 0u;
+}
+// the dword at message offset j (a multiple of 4): one load where it lies in the body, else byte by byte; zero behind the message
+PHANT_DEV uint32_t message_dword(const Message& m, uint64_t j) {
+    if (j >= m.total) return 0u;
+    if (j >= m.pl && m.bl >= 4u && j - m.pl <= m.bl - 4u) return load32(m.body + (j - m.pl));
+    return message_byte(m, j) | message_byte(m, j + 1u) << 8 | message_byte(m, j + 2u) << 16 | message_byte(m, j + 3u) << 24;
+}
+// bit 7 of every non-zero byte
+PHANT_DEV uint32_t nonzero_bytes(uint32_t d) { return (((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u; }
+// the non-zero bytes of the block d (which starts `rel` bytes behind the calldata's first byte, modulo 2^32) that are calldata
+PHANT_DEV uint32_t count_nonzero(const uint32_t (&d)[RATE_DWORDS], uint32_t rel, uint32_t data_len) {
+    uint32_t c = 0;
+    if (rel < data_len && data_len - rel >= RATE) {  // the whole block is calldata
+#pragma unroll
+        for (int i = 0; i < (int)RATE_DWORDS; ++i) c += (uint32_t)__popc(nonzero_bytes(d[i]));
+    } else if (rel < data_len || rel > 0u - RATE) {  // it begins or ends inside this block
+#pragma unroll
+        for (int i = 0; i < (int)RATE_DWORDS; ++i) {
+            const uint32_t q = rel + 4u * (uint32_t)i;
+            const uint32_t mask = (q < data_len ? 0x80u : 0u) | (q + 1u < data_len ? 0x8000u : 0u) | (q + 2u < data_len ? 0x800000u : 0u) |
+                                  (q + 3u < data_len ? 0x80000000u : 0u);
+            c += (uint32_t)__popc(nonzero_bytes(d[i]) & mask);
+        }
+    }
+    return c;
+}
+
+// the Keccak-256 of message m in s; -> the non-zero bytes of the calldata, which starts at message offset data_at
+PHANT_DEV uint32_t hash_message(Sponge& s, const Message& m, uint32_t data_at, uint32_t data_len) {
+    sponge_zero(s);
+    uint32_t nonzero = 0;
+    for (uint64_t j = 0;; j += RATE) {
+        const uint64_t left = m.total - j;
+        uint32_t d[RATE_DWORDS];
+        if (j >= m.pl && m.bl >= RATE && j - m.pl <= m.bl - RATE) {
+            load_block_wide(d, m.body + (j - m.pl));
+        } else {
+#pragma unroll
+            for (int i = 0; i < (int)RATE_DWORDS; ++i) d[i] = message_dword(m, j + 4u * (uint64_t)i);
+        }
+        if (data_len) nonzero += count_nonzero(d, (uint32_t)j - data_at, data_len);
+        if (left >= RATE) xor_block(s, d);
+        else absorb_loaded_final(s, d, (uint32_t)left);
+        keccak_f1600(s);
+        if (left < RATE) break;
+    }
+    return nonzero;
+}
+
+__global__ void __launch_bounds__(64) tx_hash_kernel(const uint8_t* __restrict__ txs, const uint64_t* __restrict__ tx_off, uint32_t n,
+                                                      const Plan* __restrict__ plan, uint8_t* __restrict__ tx_hash, uint8_t* __restrict__ sig_hash,
+                                                      uint64_t* __restrict__ nonzero_out) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = tx_off[i];
+    const Plan pl = plan[i];
+    Message m;
+    m.body = txs + b, m.pl = 0u, m.bl = (uint32_t)(tx_off[i + 1u] - b), m.total = m.bl;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m.prefix[k] = m.suffix[k] = 0u;
+    Sponge s;
+    nonzero_out[i] = hash_message(s, m, pl.data_at, pl.data_len);  // (the rules kernel turns the count into the intrinsic gas)
+    store_digest(s, tx_hash + 32ull * i);
+    if ((pl.lens >> 16) == ST_OK) {
+        m.body = txs + b + pl.body_begin, m.pl = pl.lens & 0xffu, m.bl = pl.body_end - pl.body_begin;
+        m.total = (uint64_t)m.pl + m.bl + ((pl.lens >> 8) & 0xffu);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m.prefix[k] = pl.prefix[k], m.suffix[k] = pl.suffix[k];
+        (void)hash_message(s, m, 0u, 0u);
+    } else {
+        sponge_zero(s);
+    }
+    store_digest(s, sig_hash + 32ull * i);
+}
+
+// ---- the rules: 256-bit integers as eight 32-bit limbs, little-endian
+TX_HD void load_u256(const uint8_t* be, uint32_t w[8]) {
+    for (int k = 0; k < 8; ++k) {
+        const uint8_t* p = be + 28 - 4 * k;
+        w[k] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+    }
+}
+TX_HD void store_u256(uint8_t* be, const uint32_t w[8]) {
+    for (int k = 0; k < 8; ++k) {
+        uint8_t* p = be + 28 - 4 * k;
+        p[0] = (uint8_t)(w[k] >> 24), p[1] = (uint8_t)(w[k] >> 16), p[2] = (uint8_t)(w[k] >> 8), p[3] = (uint8_t)w[k];
+    }
+}
+TX_HD bool less_u256(const uint32_t a[8], const uint32_t b[8]) {
+    for (int k = 7; k >= 0; --k)
+        if (a[k] != b[k]) return a[k] < b[k];
+    return false;
+}
+
+// sig_status: the recovery's verdicts, or null (PHANT_TXS_NO_RECOVERY)
+__global__ void __launch_bounds__(64) tx_rules_kernel(uint32_t n, Rules ru, Dev dv, const uint8_t* __restrict__ sig_status) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const Out& o = dv.o;
+    uint32_t f = o.flags[i];
+    uint32_t eff[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cost[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t intrinsic = 0;
+    if (!(f & PHANT_TX_UNDECODABLE)) {
+        const bool create = (f & PHANT_TX_IS_CREATE) != 0u;
+        const uint32_t type = o.type[i], data_len = o.data_len[i];
+        const uint64_t gas_limit = o.gas_limit[i], nonzero = o.intrinsic_gas[i];  // (the hash kernel's count)
+        if (sig_status && sig_status[i] != PHANT_SIG_OK && sig_status[i] != PHANT_SIG_BAD_V) f |= PHANT_TX_SIGNATURE;
+        intrinsic = 21000u + 4u * ((uint64_t)data_len - nonzero) + 16u * nonzero + 2400u * (uint64_t)o.al_addresses[i] + 1900u * (uint64_t)o.al_keys[i];
+        if (create) intrinsic += 32000u + 2u * (((uint64_t)data_len + 31u) / 32u);
+        uint32_t price[8], prio[8], value[8];
+        load_u256(o.gas_price + 32ull * i, price);
+        load_u256(o.priority_fee + 32ull * i, prio);
+        load_u256(o.value + 32ull * i, value);
+        if (ru.have_base_fee) {
+            if (type == 2u && less_u256(price, prio)) f |= PHANT_TX_PRIORITY_ABOVE_MAX;
+            if (less_u256(price, ru.base_fee)) f |= PHANT_TX_FEE_BELOW_BASE;
+            if (!(f & (PHANT_TX_PRIORITY_ABOVE_MAX | PHANT_TX_FEE_BELOW_BASE))) {
+                if (type == 2u) {  // min(priority, max_fee - base_fee) + base_fee
+                    uint32_t room[8];
+                    uint64_t c = 0;
+                    for (int k = 0; k < 8; ++k) {
+                        const uint64_t t = (uint64_t)price[k] - ru.base_fee[k] - c;
+                        room[k] = (uint32_t)t, c = (t >> 32) & 1u;
+                    }
+                    const bool take_prio = less_u256(prio, room);
+                    c = 0;
+                    for (int k = 0; k < 8; ++k) {
+                        c += (uint64_t)(take_prio ? prio[k] : room[k]) + ru.base_fee[k];
+                        eff[k] = (uint32_t)c, c >>= 32;
+                    }
+                } else {
+                    for (int k = 0; k < 8; ++k) eff[k] = price[k];
+                }
+            }
+        }
+        if (ru.have_gas_limit && gas_limit > ru.block_gas_limit) f |= PHANT_TX_GAS_ABOVE_BLOCK;
+        if (intrinsic > gas_limit) f |= PHANT_TX_INTRINSIC_GAS;
+        if (o.nonce[i] == ~0ull) f |= PHANT_TX_NONCE_MAX;
+        if (create && data_len > 2u * 0x6000u) f |= PHANT_TX_INITCODE_SIZE;
+        // gas_limit x getGasPrice() + value: column k of the schoolbook product is price[k] g0 + price[k - 1] g1
+        const uint32_t g0 = (uint32_t)gas_limit, g1 = (uint32_t)(gas_limit >> 32);
+        uint64_t carry = 0;
+        uint32_t over = 0;
+        for (int k = 0; k < 10; ++k) {
+            const uint64_t a = k < 8 ? (uint64_t)price[k] * g0 : 0ull, b = (k >= 1 && k <= 8) ? (uint64_t)price[k - 1] * g1 : 0ull;
+            const uint64_t lo = (carry & 0xffffffffull) + (a & 0xffffffffull) + (b & 0xffffffffull) + (k < 8 ? value[k] : 0u);
+            if (k < 8) cost[k] = (uint32_t)lo;
+            else over |= (uint32_t)lo;
+            carry = (carry >> 32) + (a >> 32) + (b >> 32) + (lo >> 32);
+        }
+        if (over || carry) {
+            f |= PHANT_TX_COST_OVERFLOW;
+            for (int k = 0; k < 8; ++k) cost[k] = 0u;
+        }
+    }
+    o.flags[i] = f;
+    o.intrinsic_gas[i] = intrinsic;
+    store_u256(o.effective_gas_price + 32ull * i, eff);
+    store_u256(o.upfront_cost + 32ull * i, cost);
+    if (f & ERROR_BITS) atomicMax(dv.ctl + 1, n - i);
+}
+
+#define TX_TRY(call)                                                              \
+    do {                                                                          \
+        const hipError_t e_ = (call);                                             \
+        if (e_ != hipSuccess) {                                                   \
+            err = std::string("block_transactions: " #call ": ") + hipGetErrorString(e_); \
+            return PHANT_E_DEVICE;                                                \
+        }                                                                         \
+    } while (0)
+
+// what the host form refuses before anything is copied
+inline int32_t check_host(const In& in, std::string& err) {
+    if (in.tx_off[0] != 0u) return err = "block_transactions: tx_off does not run from 0", PHANT_E_INVALID_ARG;
+    for (uint32_t i = 0; i < in.n; ++i)
+        if (in.tx_off[i + 1u] < in.tx_off[i]) return err = "block_transactions: tx_off goes backwards", PHANT_E_INVALID_ARG;
+    for (uint32_t i = 0; i < in.n; ++i)
+        if (in.tx_off[i + 1u] - in.tx_off[i] > 0xffffffffull) return err = "block_transactions: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
+    return PHANT_OK;
+}
+
+}  // namespace tx
+
+int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_in& in, phant_txs_out& out, bool dev, const uint32_t* gtable,
+                           std::string& err) {
+    using namespace tx;
+    const uint32_t n = in.n;
+    const bool recover = !(in.flags & PHANT_TXS_NO_RECOVERY);
+    TX_TRY(ws.ensure_mailbox());
+    static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXS_WORDS, "the control words fit their part of the mailbox");
+    volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXS;
+    auto read_ctl = [&](const uint32_t* d_ctl) -> hipError_t {
+        hipError_t e = hipMemcpyAsync(const_cast<uint32_t*>(mb), d_ctl, 4 * CTL_WORDS, hipMemcpyDeviceToHost, st);
+        return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    };
+    uint64_t bytes = in.tx_bytes;
+    if (!dev) {
+        const int32_t rc = check_host(in, err);
+        if (rc) return rc;
+        bytes = in.tx_off[n];
+    }
+
+    // ---- the arena: control words and outputs in front (one span goes back), the internal arrays, (host form) offsets and bytes last
+    Dev d;
+    const uint8_t* d_txs = in.txs;
+    const uint64_t* d_off = in.tx_off;
+    auto carve = [&](auto& io) {
+        d.ctl = io.template take<uint32_t>(CTL_WORDS);
+#define X(m, T, e) d.o.m = io.template take<T>((size_t)n * e);
+        TX_OUTPUTS(X)
+#undef X
+        d.plan = io.template take<Plan>((size_t)n);
+        d.r = io.template take<uint8_t>(32 * (size_t)n);
+        d.s = io.template take<uint8_t>(32 * (size_t)n);
+        d.recid = io.template take<uint8_t>((size_t)n);
+        d.pre_status = io.template take<uint8_t>((size_t)n);
+        if (!dev) {
+            d_off = io.template take<uint64_t>((size_t)n + 1);
+            d_txs = io.template take<uint8_t>((size_t)bytes + 16);
+        }
+    };
+    {
+        ArenaSizer size;
+        carve(size);
+        if (size.bytes > ws.io.cap) TX_TRY(hipStreamSynchronize(st));  // (a kernel may still read the arena that is about to go)
+        const hipError_t e = ws.io.reset(size.bytes);
+        if (e != hipSuccess) return err = std::string("block_transactions: hipMalloc(workspace): ") + hipGetErrorString(e), PHANT_E_OOM;
+        carve(ws.io);
+        if (ws.io.overflowed) return err = "block_transactions: arena sized too small (internal)", PHANT_E_DEVICE;
+    }
+    TX_TRY(hipMemsetAsync(d.ctl, 0, 4 * CTL_WORDS, st));
+
+    // ---- in: (host form) offsets and bytes in ONE copy through the pinned stage where they fit it; (device form) the offsets' check
+    const uint32_t grid256 = (n + 255u) / 256u, grid64 = (n + 63u) / 64u;
+    if (!dev) {
+        uint8_t* const in_begin = reinterpret_cast<uint8_t*>(const_cast<uint64_t*>(d_off));
+        const size_t in_end = (size_t)(d_txs + bytes - ws.io.base);
+        const bool staged = !PHANT_ARENA_POISONS && in_end <= Workspaces::STAGE_BYTES;
+        if (staged) {
+            TX_TRY(ws.ensure_stage());
+            std::memcpy(ws.staged(in_begin), in.tx_off, 8 * ((size_t)n + 1));
+            if (bytes) std::memcpy(ws.staged(const_cast<uint8_t*>(d_txs)), in.txs, (size_t)bytes);
+            TX_TRY(hipMemcpyAsync(in_begin, ws.staged(in_begin), (size_t)(d_txs + bytes - in_begin), hipMemcpyHostToDevice, st));
+        } else {
+            TX_TRY(hipMemcpyAsync(in_begin, in.tx_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+            if (bytes) TX_TRY(hipMemcpyAsync(const_cast<uint8_t*>(d_txs), in.txs, (size_t)bytes, hipMemcpyHostToDevice, st));
+        }
+    } else {
+        hipLaunchKernelGGL(tx_check_args_kernel, dim3(grid256), dim3(256), 0, st, d_off, n, bytes, d.ctl);
+        TX_TRY(hipGetLastError());
+        TX_TRY(read_ctl(d.ctl));
+        if (mb[0] & F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
+        if (mb[0] & F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
+    }
+
+    // ---- decode, hash, recover, rules
+    Rules ru;
+    std::memset(&ru, 0, sizeof ru);
+    if (in.base_fee) load_u256(in.base_fee, ru.base_fee), ru.have_base_fee = 1u;
+    ru.have_gas_limit = (in.flags & PHANT_TXS_HAVE_GAS_LIMIT) ? 1u : 0u;
+    ru.block_gas_limit = in.block_gas_limit;
+    hipLaunchKernelGGL(tx_decode_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, in.chain_id, d);
+    TX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tx_hash_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, d.plan, d.o.tx_hash, d.o.sig_hash, d.o.intrinsic_gas);
+    TX_TRY(hipGetLastError());
+    const uint32_t low_s = PHANT_RECOVER_LOW_S;  // validateSignatureFields
+    if (recover) TX_TRY(launch_ecrecover(d.o.sig_hash, d.r, d.s, d.recid, d.pre_status, n, low_s, gtable, nullptr, d.o.sender, d.o.sig_status, st));
+    hipLaunchKernelGGL(tx_rules_kernel, dim3(grid64), dim3(64), 0, st, n, ru, d, recover ? d.o.sig_status : nullptr);
+    TX_TRY(hipGetLastError());
+
+    // ---- out
+    if (dev) {
+#define X(m, T, e) \
+    if (out.m) TX_TRY(hipMemcpyAsync(out.m, d.o.m, (size_t)n * e * sizeof(T), hipMemcpyDeviceToDevice, st));
+        TX_OUTPUTS(X)
+#undef X
+        TX_TRY(read_ctl(d.ctl));
+        out.first_bad = n - mb[1];
+        return PHANT_OK;
+    }
+    // host form: the control words and everything up to the last wanted output cross the bus as ONE copy into the pinned stage when they
+    // fit there (a copy into pageable memory is ~25 us a piece, and a call has up to 23)
+    size_t last = 0;
+#define X(m, T, e) \
+    if (out.m) last = (size_t)(reinterpret_cast<uint8_t*>(d.o.m) - ws.io.base) + (size_t)n * e * sizeof(T);
+    TX_OUTPUTS(X)
+#undef X
+    if (!last) last = (size_t)(reinterpret_cast<uint8_t*>(d.ctl + CTL_WORDS) - ws.io.base);
+    const bool staged_out = !PHANT_ARENA_POISONS && last <= Workspaces::STAGE_BYTES;
+    uint32_t first_bad_word = 0;
+    if (staged_out) {
+        TX_TRY(ws.ensure_stage());
+        TX_TRY(hipMemcpyAsync(ws.staged(d.ctl), d.ctl, last - (size_t)(reinterpret_cast<uint8_t*>(d.ctl) - ws.io.base), hipMemcpyDeviceToHost, st));
+        TX_TRY(hipStreamSynchronize(st));
+        first_bad_word = ws.staged(d.ctl)[1];
+#define X(m, T, e) \
+    if (out.m && n) std::memcpy(out.m, ws.staged(d.o.m), (size_t)n * e * sizeof(T));
+        TX_OUTPUTS(X)
+#undef X
+    } else {
+#define X(m, T, e) \
+    if (out.m && n) TX_TRY(hipMemcpyAsync(out.m, d.o.m, (size_t)n * e * sizeof(T), hipMemcpyDeviceToHost, st));
+        TX_OUTPUTS(X)
+#undef X
+        TX_TRY(read_ctl(d.ctl));
+        first_bad_word = mb[1];
+    }
+    out.first_bad = n - first_bad_word;
+    return PHANT_OK;
+}
+
+#undef TX_TRY
+#undef TX_OUTPUTS
+
+}  // namespace phant
+#endif  // PHANT_TX_DECODE_ONLY
+#undef TX_HD
