@@ -390,7 +390,8 @@ PHANT_API int32_t phant_tx_senders(phant_ctx *ctx, const uint8_t *txs, const uin
  * Output, struct-of-arrays of n rows, any pointer may be NULL.  Integers of 32 bytes are big-endian.
  *   tx_hash (32)       keccak256 of the raw bytes; always defined (a zero-length transaction: the hash of the empty string)
  *   sig_hash (32)      what was signed: the items in front of v under a list header of their own (EIP-155: + chain_id, 0, 0)
- *   sender (20), sig_status (1)   value for value what phant_tx_senders writes for the same input (PHANT_SIG_*)
+ *   sender (20), sig_status (1)   value for value what phant_tx_senders writes for the same input (PHANT_SIG_*; types 0 - 2, the only
+ *                      ones either call decodes -- phant_block_transactions_ex below goes further)
  *   sig (65)           r || s || recid
  *   type (1), chain_id, nonce, gas_limit (uint64_t)   chain_id of a legacy transaction: (v - 35) >> 1, 0 for v = 27 / 28
  *   gas_price (32)     getGasPrice(): max_fee_per_gas for type 2
@@ -473,6 +474,92 @@ typedef struct phant_txs_out {
 } phant_txs_out;
 PHANT_API int32_t phant_block_transactions(phant_ctx *ctx, const phant_txs_in *in, phant_txs_out *out);
 PHANT_API int32_t phant_block_transactions_dev(phant_ctx *ctx, const phant_txs_in *in, phant_txs_out *out);
+
+/* ------------------------------------------------- a block's transactions, the forks after London: blob (type 3) and set-code (type 4)
+ * phant_block_transactions_ex is phant_block_transactions with a fork: which typed transactions decode, and which rules hold.
+ *   PHANT_TXS_FORK_LONDON   types 0 - 2: answer for answer phant_block_transactions (which is this call with that fork)
+ *   PHANT_TXS_FORK_CANCUN   + type 3 (EIP-4844)
+ *   PHANT_TXS_FORK_PRAGUE   + type 4 (EIP-7702), + the EIP-7623 floor for every type
+ * A type the fork does not enable is PHANT_TX_UNDECODABLE.  None of this is in the reference (its transaction.zig stops at
+ * FeeMarketTx): the EIPs are the specification, written out here.  sender / sig_status equal phant_tx_senders' value for value
+ * for types 0 - 2 only: that call (and the host decode behind it) does not know types 3 and 4.
+ *
+ * Type 3 = 0x03 || rlp([chain_id, nonce, max_priority_fee_per_gas, max_fee_per_gas, gas_limit, to, value, data, access_list,
+ * max_fee_per_blob_gas, blob_versioned_hashes, y_parity, r, s]): 14 items, max_fee_per_blob_gas of at most 32 bytes, the hashes a
+ * list of strings of exactly 32 bytes (anything else: undecodable).  Signing hash: keccak256(0x03 || rlp(the first 11 items)).
+ * Type 4 = 0x04 || rlp([chain_id, nonce, max_priority_fee_per_gas, max_fee_per_gas, gas_limit, to, value, data, access_list,
+ * authorization_list, y_parity, r, s]): 13 items, authorization_list = [[chain_id, address, nonce, y_parity, r, s], ...] with
+ * chain_id <= 32 bytes, address exactly 20, nonce <= 8, y_parity <= 1, r and s <= 32, canonical integers, exactly six items in
+ * a tuple and nothing else inside it; any violation makes the TRANSACTION undecodable.  Signing hash: keccak256(0x04 ||
+ * rlp(the first 10 items)).  Both: the strictness of types 1 and 2; `to` empty or 20 bytes (empty: PHANT_TX_NO_TO and
+ * PHANT_TX_IS_CREATE, not a decode failure); the fee rules, effective_gas_price and PHANT_TX_CHAIN_ID of type 2.
+ *
+ * Rules.  Type 4: intrinsic_gas gains 25000 per tuple.  Type 3: upfront_cost = gas_limit x max_fee_per_gas + value + blobs x
+ * 131072 x max_fee_per_blob_gas; beyond 2^256 - 1: PHANT_TX_COST_OVERFLOW and a zero row, as for the other types.  PRAGUE, every
+ * type: floor_gas = 21000 + 10 x (zero bytes + 4 x non-zero bytes of the calldata), PHANT_TX_FLOOR_GAS when gas_limit <
+ * floor_gas (PHANT_TX_INTRINSIC_GAS is what it was).  blob_base_fee (32 bytes big-endian, HOST memory in both forms; NULL skips
+ * the rule): PHANT_TX_BLOB_FEE_BELOW_BASE when a type-3 transaction's max_fee_per_blob_gas is below it; the caller computes it
+ * from the parent header's excess_blob_gas (EIP-4844 fake_exponential).  blob_gas_used is a RESULT, which the caller compares with
+ * the header's field and the fork's maximum.
+ *
+ * Authorization tuples: row j of the per-authorization outputs is tuple j - auth_first[i] of transaction i, auth_first (n + 1
+ * entries) being the exclusive prefix sums of the tuples per decodable type-4 transaction.  auth_hash = keccak256(0x05 ||
+ * rlp([chain_id, address, nonce])), auth_sig = r || s || y_parity as decoded; authority = the recovered signer (low s enforced:
+ * PHANT_RECOVER_LOW_S), zero unless auth_status is PHANT_SIG_OK.  auth_status is, in this order: PHANT_AUTH_CHAIN_ID (the tuple's
+ * chain id is neither 0 nor the call's), PHANT_AUTH_NONCE_MAX (its nonce is 2^64 - 1), PHANT_SIG_BAD_V (y_parity > 1) -- none of
+ * which reaches the curve arithmetic -- or the recovery's PHANT_SIG_*.  A tuple whose status is not PHANT_SIG_OK is skipped by the
+ * caller, as EIP-7702 says: it does NOT flag its transaction.  auth_cap = the rows the per-authorization arrays hold: n_auth and
+ * auth_first are always complete, rows from auth_cap on are not written, and the call still returns PHANT_OK.  A tuple takes at
+ * least 27 bytes (a list header of 1, then 1 + 21 + 1 + 1 + 1 + 1), so n_auth <= (bytes of the type-4 transactions) / 27.
+ * PHANT_TXS_NO_RECOVERY also skips the authorities' recovery: authority and auth_status must then be NULL.
+ *
+ * Refusals as for phant_block_transactions (PHANT_E_INVALID_ARG, nothing touched), and: a wrong outer struct_size, fork >
+ * PHANT_TXS_FORK_PRAGUE, reserved != 0.  Device form: as phant_block_transactions_dev; blob_off, floor_gas and auth_nonce 8-byte,
+ * blobs and auth_first 4-byte aligned.  A PRAGUE call that may hold a tuple (device form: every one; host form: one with a
+ * transaction that begins with 0x04) synchronises once more in its middle to learn how many there are. */
+#define PHANT_TXS_FORK_LONDON 0u
+#define PHANT_TXS_FORK_CANCUN 1u
+#define PHANT_TXS_FORK_PRAGUE 2u
+#define PHANT_AUTH_CHAIN_ID 8u  /* auth_status, beside PHANT_SIG_* */
+#define PHANT_AUTH_NONCE_MAX 9u
+#define PHANT_TX_NO_TO 0x01000u               /* type 3 or 4 with an empty `to` (PHANT_TX_IS_CREATE is set as well) */
+#define PHANT_TX_BLOB_NONE 0x02000u           /* type 3 without a versioned hash */
+#define PHANT_TX_BLOB_VERSION 0x04000u        /* some versioned hash's first byte is not 0x01 */
+#define PHANT_TX_BLOB_FEE_BELOW_BASE 0x08000u /* type 3: max_fee_per_blob_gas < blob_base_fee */
+#define PHANT_TX_AUTH_NONE 0x10000u           /* type 4 with an empty authorization list */
+#define PHANT_TX_FLOOR_GAS 0x20000u           /* PRAGUE: gas_limit < floor_gas */
+/* (0x40000 stays free: the blob term is part of upfront_cost, and PHANT_TX_COST_OVERFLOW covers it) */
+#define PHANT_TX_ERROR_BITS_EX (0x7ffu | 0x7f000u) /* the error bits of the _ex call; first_bad counts these */
+typedef struct phant_txs_ex_in {
+    uint32_t struct_size; /* = sizeof(phant_txs_ex_in) */
+    uint32_t fork;        /* PHANT_TXS_FORK_* */
+    phant_txs_in base;    /* base.struct_size = sizeof(phant_txs_in) */
+    const uint8_t *blob_base_fee; /* 32 bytes big-endian, host memory, or NULL */
+    uint32_t auth_cap;    /* rows the per-authorization outputs hold */
+    uint32_t reserved;    /* 0 */
+} phant_txs_ex_in;
+typedef struct phant_txs_ex_out {
+    uint32_t struct_size;   /* = sizeof(phant_txs_ex_out) */
+    uint32_t n_auth;        /* result: the authorization tuples of all decodable type-4 transactions */
+    uint64_t blob_gas_used; /* result: 131072 x the versioned hashes of all decodable type-3 transactions */
+    phant_txs_out base;     /* base.first_bad counts the new error bits too */
+    /* per transaction, n rows; any may be NULL */
+    uint8_t *max_fee_per_blob_gas; /* 32, zero unless type 3 */
+    uint64_t *blob_off;            /* into txs: the first byte of the versioned-hash list's payload; 0 unless type 3 */
+    uint32_t *blobs;               /* its hashes (33 RLP bytes each) */
+    uint32_t *auth_first;          /* n + 1; auth_first[n] == n_auth */
+    uint64_t *floor_gas;           /* EIP-7623; 0 below PRAGUE and for undecodable rows */
+    /* per authorization, in (transaction, position) order, min(n_auth, auth_cap) rows written; any may be NULL */
+    uint8_t *auth_chain_id; /* 32 big-endian */
+    uint8_t *auth_address;  /* 20 */
+    uint64_t *auth_nonce;
+    uint8_t *auth_hash;     /* 32 */
+    uint8_t *auth_sig;      /* 65: r || s || y_parity */
+    uint8_t *authority;     /* 20, zero unless auth_status == PHANT_SIG_OK */
+    uint8_t *auth_status;   /* PHANT_SIG_* or PHANT_AUTH_* */
+} phant_txs_ex_out;
+PHANT_API int32_t phant_block_transactions_ex(phant_ctx *ctx, const phant_txs_ex_in *in, phant_txs_ex_out *out);
+PHANT_API int32_t phant_block_transactions_ex_dev(phant_ctx *ctx, const phant_txs_ex_in *in, phant_txs_ex_out *out);
 
 /* ------------------------------------------------------- proof verification
  * ABSENT in the reference: this is the call the TODO at

@@ -72,6 +72,8 @@ SYMBOLS = {
     "phant_tx_senders": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _vp]),
     "phant_block_transactions": (_i32, [_vp, _vp, _vp]),
     "phant_block_transactions_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_block_transactions_ex": (_i32, [_vp, _vp, _vp]),
+    "phant_block_transactions_ex_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_verify_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_mpt_verify_batch_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
@@ -205,6 +207,35 @@ class PhantTxsIn(C.Structure):
 class PhantTxsOut(C.Structure):
     """phant_txs_out (include/phant_gpu.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("first_bad", C.c_uint32)] + [(name, C.c_void_p) for name, _, _ in TX_OUTPUTS]
+
+
+TXS_FORK_LONDON, TXS_FORK_CANCUN, TXS_FORK_PRAGUE = 0, 1, 2
+AUTH_CHAIN_ID, AUTH_NONCE_MAX = 8, 9  # auth_status, beside SIG_*
+# phant_txs_ex_out's arrays in the struct's order: a row per transaction (auth_first: n + 1 entries) ...
+TX_EX_OUTPUTS = (("max_fee_per_blob_gas", "u1", 32), ("blob_off", "u8", 1), ("blobs", "u4", 1), ("auth_first", "u4", 1), ("floor_gas", "u8", 1))
+# ... and a row per authorization tuple
+TX_AUTH_OUTPUTS = (("auth_chain_id", "u1", 32), ("auth_address", "u1", 20), ("auth_nonce", "u8", 1), ("auth_hash", "u1", 32), ("auth_sig", "u1", 65),
+                   ("authority", "u1", 20), ("auth_status", "u1", 1))
+# PHANT_TX_* of phant_block_transactions_ex: bit k of flags[i] (bits 12 .. 18 are errors too)
+TX_FLAG_NAMES_EX = TX_FLAG_NAMES + ("NoTo", "BlobNone", "BlobVersion", "BlobFeeBelowBase", "AuthNone", "FloorGas")
+TX_ERROR_BITS_EX = 0x7FF | 0x7F000
+
+
+def tx_error_bits(fork=None):
+    """the error bits of a call's flags: fork None = phant_block_transactions"""
+    return TX_ERROR_BITS if fork is None else TX_ERROR_BITS_EX
+
+
+class PhantTxsExIn(C.Structure):
+    """phant_txs_ex_in (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("fork", C.c_uint32), ("base", PhantTxsIn), ("blob_base_fee", C.c_void_p), ("auth_cap", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PhantTxsExOut(C.Structure):
+    """phant_txs_ex_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_auth", C.c_uint32), ("blob_gas_used", C.c_uint64), ("base", PhantTxsOut)] + \
+               [(name, C.c_void_p) for name, _, _ in TX_EX_OUTPUTS + TX_AUTH_OUTPUTS]
 
 
 class PhantProveOut(C.Structure):

@@ -115,6 +115,7 @@ struct Workspaces {
     DevArena t2;  // trie builder: slot tables + encoding scratch
     DevArena pv;  // prover (trie_prove.hip.h): marks, sizes, offsets -- next to t1 / t2, which hold the build it reads
     DevArena pvo; // prover, host form: the node blob and its offsets on their way out
+    DevArena txa; // block_transactions: the rows of the authorization tuples, sized in the middle of a call (whose other arrays stay in `io`)
     // Pinned mirror of the first STAGE_BYTES of `io` for SMALL host-form calls: the caller's pageable arrays are packed into
     // it at the offsets their device copies have in the arena and cross the bus in ONE copy (a pageable hipMemcpyAsync costs
     // ~25 us a piece, and a call has five to nine); it is mapped into the device's address space, so small results can be
@@ -176,6 +177,7 @@ struct Workspaces {
         t2.release();
         pv.release();
         pvo.release();
+        txa.release();
         if (stage) (void)hipHostFree(stage);
         stage = nullptr;
         if (mailbox) (void)hipHostFree(mailbox);

@@ -878,42 +878,85 @@ int32_t phant_tx_senders(phant_ctx* c, const uint8_t* txs, const uint64_t* tx_of
 
 /* ------------------------------------------------- a block's transactions (transactions.hip.h) */
 
-static int32_t block_transactions_impl(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out, bool dev) {
-    const char* const who = dev ? "block_transactions_dev" : "block_transactions";
+// xin / xout: the new structs of phant_block_transactions_ex; null for phant_block_transactions, which is the same path with
+// PHANT_TXS_FORK_LONDON and none of the new outputs
+static int32_t block_transactions_impl(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out, const phant_txs_ex_in* xin, phant_txs_ex_out* xout,
+                                       bool dev) {
+    const char* const who = xin ? (dev ? "block_transactions_ex_dev" : "block_transactions_ex") : dev ? "block_transactions_dev" : "block_transactions";
     auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
     if (!c) return PHANT_E_INVALID_ARG;
     if (!in || !out) return bad("in / out is null");
+    if (xin && (xin->struct_size != sizeof(phant_txs_ex_in) || xout->struct_size != sizeof(phant_txs_ex_out))) return bad("wrong struct_size");
     if (in->struct_size != sizeof(phant_txs_in) || out->struct_size != sizeof(phant_txs_out)) return bad("wrong struct_size");
+    if (xin && xin->fork > PHANT_TXS_FORK_PRAGUE) return bad("unknown fork");
+    if (xin && xin->reserved != 0u) return bad("reserved is not 0");
+    if (xin && (in->flags & PHANT_TXS_NO_RECOVERY) && (xout->authority || xout->auth_status))
+        return bad("authority / auth_status asked for together with the no-recovery flag");
     if (in->flags & ~(PHANT_TXS_HAVE_GAS_LIMIT | PHANT_TXS_NO_RECOVERY)) return bad("unknown flag");
     if ((in->flags & PHANT_TXS_NO_RECOVERY) && (out->sender || out->sig_status)) return bad("sender / sig_status asked for together with the no-recovery flag");
     const uint32_t n = in->n;
+    if (dev) {  // (tx_off is read by kernels as words; the outputs arrive by device-to-device copies of bytes)
+        uintptr_t w8 = (uintptr_t)in->tx_off | (uintptr_t)out->chain_id | (uintptr_t)out->nonce | (uintptr_t)out->gas_limit |
+                       (uintptr_t)out->data_off | (uintptr_t)out->al_off | (uintptr_t)out->intrinsic_gas;
+        uintptr_t w4 = (uintptr_t)out->data_len | (uintptr_t)out->al_len | (uintptr_t)out->al_addresses | (uintptr_t)out->al_keys |
+                       (uintptr_t)out->flags;
+        if (xout) {
+            w8 |= (uintptr_t)xout->blob_off | (uintptr_t)xout->floor_gas | (uintptr_t)xout->auth_nonce;
+            w4 |= (uintptr_t)xout->blobs | (uintptr_t)xout->auth_first;
+        }
+        if (n != 0 && ((w8 & 7u) || (w4 & 3u))) return bad("misaligned array");
+    }
     if (n == 0) {
         out->first_bad = 0;
+        if (xout) {
+            xout->n_auth = 0, xout->blob_gas_used = 0;
+            if (xout->auth_first) {  // its one entry
+                const uint32_t zero = 0;
+                if (dev) {
+                    DeviceGuard g(c->device);
+                    HIP_TRY(c, hipMemcpyAsync(xout->auth_first, &zero, 4, hipMemcpyHostToDevice, c->stream));
+                    HIP_TRY(c, hipStreamSynchronize(c->stream));
+                } else {
+                    xout->auth_first[0] = zero;
+                }
+            }
+        }
         return PHANT_OK;
     }
     if (!in->tx_off || !in->txs) return bad("null txs / tx_off");
-    if (dev) {  // (tx_off is read by kernels as words; the outputs arrive by device-to-device copies of bytes)
-        const uintptr_t w8 = (uintptr_t)in->tx_off | (uintptr_t)out->chain_id | (uintptr_t)out->nonce | (uintptr_t)out->gas_limit |
-                             (uintptr_t)out->data_off | (uintptr_t)out->al_off | (uintptr_t)out->intrinsic_gas;
-        const uintptr_t w4 = (uintptr_t)out->data_len | (uintptr_t)out->al_len | (uintptr_t)out->al_addresses | (uintptr_t)out->al_keys |
-                             (uintptr_t)out->flags;
-        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
-    }
     DeviceGuard g(c->device);
     if (!(in->flags & PHANT_TXS_NO_RECOVERY))
         if (const int32_t rc = ensure_gtable(c)) return rc;
     TimedRegion t(c, dev);
     std::string err;
-    phant_txs_out res = *out;
-    const int32_t rc = phant::block_transactions(c->ws, c->stream, *in, res, dev, c->secp_gtable, err);
+    phant_txs_ex_in call;
+    phant_txs_ex_out res;
+    std::memset(&call, 0, sizeof call);
+    std::memset(&res, 0, sizeof res);
+    if (xin) call = *xin, res = *xout;
+    else call.fork = PHANT_TXS_FORK_LONDON, call.base = *in, res.base = *out;
+    const int32_t rc = phant::block_transactions(c->ws, c->stream, call, res, dev, c->secp_gtable, err);
     if (rc) return fail(c, rc, err.c_str());
-    out->first_bad = res.first_bad;
+    out->first_bad = res.base.first_bad;
+    if (xout) xout->n_auth = res.n_auth, xout->blob_gas_used = res.blob_gas_used;
     return PHANT_OK;
 }
 
-int32_t phant_block_transactions(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out) { return block_transactions_impl(c, in, out, false); }
+int32_t phant_block_transactions(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out) { return block_transactions_impl(c, in, out, nullptr, nullptr, false); }
 
-int32_t phant_block_transactions_dev(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out) { return block_transactions_impl(c, in, out, true); }
+int32_t phant_block_transactions_dev(phant_ctx* c, const phant_txs_in* in, phant_txs_out* out) { return block_transactions_impl(c, in, out, nullptr, nullptr, true); }
+
+int32_t phant_block_transactions_ex(phant_ctx* c, const phant_txs_ex_in* in, phant_txs_ex_out* out) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return fail(c, PHANT_E_INVALID_ARG, "block_transactions_ex: in / out is null");
+    return block_transactions_impl(c, &in->base, &out->base, in, out, false);
+}
+
+int32_t phant_block_transactions_ex_dev(phant_ctx* c, const phant_txs_ex_in* in, phant_txs_ex_out* out) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return fail(c, PHANT_E_INVALID_ARG, "block_transactions_ex_dev: in / out is null");
+    return block_transactions_impl(c, &in->base, &out->base, in, out, true);
+}
 
 int32_t phant_diag_secp_op(phant_ctx* c, uint32_t op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out) {
     if (!c) return PHANT_E_INVALID_ARG;

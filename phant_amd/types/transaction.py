@@ -29,14 +29,31 @@ def hashes(encoded_txs, ctx: Context | None = None) -> np.ndarray:
 
 FLAG_NAMES = L.TX_FLAG_NAMES
 ERROR_BITS = L.TX_ERROR_BITS
+FLAG_NAMES_EX = L.TX_FLAG_NAMES_EX
+ERROR_BITS_EX = L.TX_ERROR_BITS_EX
+FORK_LONDON, FORK_CANCUN, FORK_PRAGUE = L.TXS_FORK_LONDON, L.TXS_FORK_CANCUN, L.TXS_FORK_PRAGUE
+GAS_PER_BLOB = 131072
+_BLOB_FEE_UPDATE_FRACTION = {FORK_CANCUN: 3338477, FORK_PRAGUE: 5007716}
+
+
+def blob_base_fee(excess_blob_gas, fork=FORK_PRAGUE) -> int:
+    """EIP-4844's fake_exponential(1, excess_blob_gas, BLOB_BASE_FEE_UPDATE_FRACTION) with the fork's fraction (EIP-7691 raised it for
+    Prague): what `block_transactions(..., blob_base_fee=)` takes.  Computed on the host: one number a block."""
+    denominator = _BLOB_FEE_UPDATE_FRACTION[fork]
+    i, output, accum = 1, 0, denominator  # factor = 1
+    while accum > 0:
+        output += accum
+        accum = accum * int(excess_blob_gas) // (denominator * i)
+        i += 1
+    return output // denominator
 
 
 class BlockTransactions:
     """What phant_block_transactions answers: one numpy array per output of include/phant_gpu.h's phant_txs_out (rows of 32 / 20 / 65
     bytes as (n, width) uint8, big-endian), `first_bad`, and views of the calldata and the access lists inside the blob."""
 
-    def __init__(self, blob, arrays, first_bad):
-        self.blob, self.first_bad = blob, first_bad
+    def __init__(self, blob, arrays, first_bad, fork=None, n_auth=0, blob_gas_used=0):
+        self.blob, self.first_bad, self.fork, self.n_auth, self.blob_gas_used = blob, first_bad, fork, n_auth, blob_gas_used
         self.__dict__.update(arrays)
         self.n = len(self.flags)
 
@@ -50,7 +67,18 @@ class BlockTransactions:
 
     def errors(self, i):
         """the names of transaction i's failed rules, the one the reference returns first in front"""
-        return [name for k, name in enumerate(FLAG_NAMES) if (int(self.flags[i]) & ERROR_BITS) >> k & 1]
+        names = FLAG_NAMES if self.fork is None else FLAG_NAMES_EX
+        return [name for k, name in enumerate(names) if (int(self.flags[i]) & L.tx_error_bits(self.fork)) >> k & 1]
+
+    def versioned_hashes(self, i) -> np.ndarray:
+        """transaction i's blob versioned hashes, (blobs, 32): a view into the blob (calls with a fork)"""
+        at, k = int(self.blob_off[i]), int(self.blobs[i])
+        return self.blob[at:at + 33 * k].reshape(k, 33)[:, 1:]
+
+    def authorizations(self, i) -> dict:
+        """the rows of transaction i's authorization tuples: {output of phant_txs_ex_out: its slice} (calls with a fork)"""
+        rows = slice(int(self.auth_first[i]), int(self.auth_first[i + 1]))
+        return {name: getattr(self, name)[rows] for name, _, _ in L.TX_AUTH_OUTPUTS if hasattr(self, name)}
 
 
 def pack(raw_txs):
@@ -63,9 +91,14 @@ def pack(raw_txs):
     return blob, off
 
 
-def block_transactions(raw_txs, chain_id, base_fee=None, block_gas_limit=None, recover=True, ctx: Context | None = None) -> BlockTransactions:
+def block_transactions(raw_txs, chain_id, base_fee=None, block_gas_limit=None, recover=True, ctx: Context | None = None, fork=None,
+                       blob_base_fee=None) -> BlockTransactions:
     """raw transactions (legacy list, 0x01 || rlp, 0x02 || rlp) -> BlockTransactions.  base_fee (int) None: the two fee rules are
-    skipped; block_gas_limit None: GasAboveBlock is not evaluated; recover=False: no secp256k1 launch, no `sender` / `sig_status`."""
+    skipped; block_gas_limit None: GasAboveBlock is not evaluated; recover=False: no secp256k1 launch, no `sender` / `sig_status`.
+    fork None: phant_block_transactions.  FORK_LONDON / FORK_CANCUN (+ 0x03 || rlp) / FORK_PRAGUE (+ 0x04 || rlp, the EIP-7623 floor):
+    phant_block_transactions_ex, whose result also has the arrays of phant_txs_ex_out (one row per authorization tuple of the whole
+    call for the auth_* ones; without `authority` / `auth_status` when recover=False), `n_auth` and `blob_gas_used`; blob_base_fee
+    (int, `blob_base_fee()` of the parent's excess blob gas) None: BlobFeeBelowBase is not evaluated."""
     ctx = ctx or default_context()
     blob, off = pack(raw_txs)
     n = len(off) - 1
@@ -75,5 +108,18 @@ def block_transactions(raw_txs, chain_id, base_fee=None, block_gas_limit=None, r
     arg = L.PhantTxsIn(C.sizeof(L.PhantTxsIn), n, flags, 0, blob.ctypes.data, off.ctypes.data, int(off[-1]), int(chain_id),
                        None if fee is None else fee.ctypes.data, int(block_gas_limit or 0))
     out = L.PhantTxsOut(C.sizeof(L.PhantTxsOut), 0, *[arrays[name].ctypes.data if name in arrays else None for name, _, _ in L.TX_OUTPUTS])
-    ctx.check(ctx._lib.phant_block_transactions(ctx.handle, C.byref(arg), C.byref(out)))
-    return BlockTransactions(blob, arrays, int(out.first_bad))
+    if fork is None:
+        ctx.check(ctx._lib.phant_block_transactions(ctx.handle, C.byref(arg), C.byref(out)))
+        return BlockTransactions(blob, arrays, int(out.first_bad))
+    # a tuple takes at least 27 bytes: the rows that the transactions beginning with 0x04 can need
+    cap = sum(int(off[i + 1] - off[i]) for i in range(n) if off[i + 1] > off[i] and blob[int(off[i])] == 4) // 27 if fork >= FORK_PRAGUE else 0
+    for name, dtype, k in L.TX_EX_OUTPUTS:
+        arrays[name] = np.zeros((n, k) if k > 1 else n + (name == "auth_first"), dtype)
+    auth = {name: np.zeros((cap, k) if k > 1 else cap, dtype) for name, dtype, k in L.TX_AUTH_OUTPUTS if recover or name not in ("authority", "auth_status")}
+    blob_fee = None if blob_base_fee is None else np.frombuffer(int(blob_base_fee).to_bytes(32, "big"), np.uint8).copy()
+    xarg = L.PhantTxsExIn(C.sizeof(L.PhantTxsExIn), int(fork), arg, None if blob_fee is None else blob_fee.ctypes.data, cap, 0)
+    xout = L.PhantTxsExOut(C.sizeof(L.PhantTxsExOut), 0, 0, out, *[arrays[name].ctypes.data for name, _, _ in L.TX_EX_OUTPUTS],
+                           *[auth[name].ctypes.data if name in auth and cap else None for name, _, _ in L.TX_AUTH_OUTPUTS])
+    ctx.check(ctx._lib.phant_block_transactions_ex(ctx.handle, C.byref(xarg), C.byref(xout)))
+    arrays.update({name: a[:int(xout.n_auth)] for name, a in auth.items()})
+    return BlockTransactions(blob, arrays, int(xout.base.first_bad), int(fork), int(xout.n_auth), int(xout.blob_gas_used))
