@@ -561,6 +561,122 @@ typedef struct phant_txs_ex_out {
 PHANT_API int32_t phant_block_transactions_ex(phant_ctx *ctx, const phant_txs_ex_in *in, phant_txs_ex_out *out);
 PHANT_API int32_t phant_block_transactions_ex_dev(phant_ctx *ctx, const phant_txs_ex_in *in, phant_txs_ex_out *out);
 
+/* ------------------------------------------------- a block's transactions against the pre-state: nonces, EOA and witness rows
+ * phant_block_txs_prestate joins the rows phant_block_transactions[_ex] answers (keyed by transaction) with the rows
+ * phant_exec_witness_prestate answers (keyed by witness row), and decides what `processTransaction` checks first
+ * (src/blockchain/blockchain.zig:270-276: InvalidTxNonce, NotEnoughBalance, SenderIsNotEOA) as far as it can be decided for the whole
+ * block before any transaction runs.  tests/txstate_ref.py is the same definition in Python integers.
+ *
+ * row_of(a) = the LOWEST j with addresses[j] == a over all 20 bytes, else PHANT_ROW_NONE.  A row j is PROVEN when account_status[j] is
+ * PHANT_PROOF_PRESENT or PHANT_PROOF_ABSENT (the empty account, by phant_exec_witness_prestate's contract); the account arrays are read
+ * as they are.
+ *
+ * Transaction i PARTICIPATES when sig_status[i] == PHANT_SIG_OK and tx_flags[i] has none of PHANT_TX_UNDECODABLE, PHANT_TX_BAD_V,
+ * PHANT_TX_SIGNATURE.  Any other row has no sender: sender_row = to_row = PHANT_ROW_NONE, expected_nonce = 0, spent_before = 0,
+ * state_flags = PHANT_TXST_SKIPPED, which is no error bit here (the transactions call has reported the row).  A participating row:
+ *   sender_row = s = row_of(sender).  s is NONE or not proven: PHANT_TXST_SENDER_UNKNOWN; the row joins no sequence, expected_nonce and
+ *     spent_before are 0 and no further sender rule is evaluated (the block cannot be executed from this witness).
+ *   Otherwise the row joins the SEQUENCE of s: the participating rows with that sender row, in block order.  rank = the rows of the
+ *     sequence before i.  expected_nonce = nonces[s] + rank, saturating at 2^64 - 1: a sender's nonce moves by exactly one for each of
+ *     its transactions, whatever the EVM does with them, and every verdict assumes that every earlier row was included.
+ *     spent_before = the sum of upfront_cost over the rows of the sequence before i, a row with PHANT_TX_COST_OVERFLOW counting as 2^256;
+ *     written clamped to 2^256 - 1, with PHANT_TXST_SPENT_SATURATED when it was clamped.
+ *   UNDETERMINED rows, fork >= PHANT_TXS_FORK_PRAGUE only: (1) the sender's code is a delegation designator -- code_hashes[s] is not
+ *     the empty code hash, code_index[s] names a code of exactly 23 bytes, and that code begins ef 01 00 --, or (2) the sender is the
+ *     `authority` of a tuple with auth_status == PHANT_SIG_OK in a participating transaction j < i (not j == i).  Delegated code may
+ *     CREATE and a set-code tuple may bump the nonce: the row gets PHANT_TXST_UNDETERMINED, is counted in n_undetermined, the nonce, EOA
+ *     and balance rules are NOT evaluated for it -- deciding it needs the full EIP-7702 tuple processing and stays with the CALLER --,
+ *     and expected_nonce and spent_before are still written.
+ *   A determined row: PHANT_TXST_NONCE_LOW when nonce[i] < expected_nonce, PHANT_TXST_NONCE_HIGH when nonce[i] > expected_nonce (A
+ *     DEVIATION: the two split the reference's one InvalidTxNonce).  EIP-3607: a code hash that is not the empty one is
+ *     PHANT_TXST_NOT_EOA below PRAGUE; from PRAGUE on PHANT_TXST_CODE_MISSING when code_index[s] == PHANT_CODE_NONE (nobody can tell
+ *     statelessly whether it is a designator), else PHANT_TXST_NOT_EOA (A DEVIATION: the designator exemption is newer than the
+ *     reference's SenderIsNotEOA).  PHANT_TXST_NEEDS_INFLOW (advisory): balances[s] < spent_before + the row's own cost, in full
+ *     width; when the bit is clear the reference's balance check for this row cannot fail, because an undelegated EOA loses at most
+ *     its upfront costs.  PHANT_TXST_BALANCE_SHORT: NEEDS_INFLOW and i == 0 (nothing ran before the block's first transaction).
+ *   Recipient, unless PHANT_TX_IS_CREATE (then to_row = NONE): to_row = row_of(to); PHANT_TXST_TO_UNKNOWN when that is NONE or not proven.
+ * Tuple k belongs to transaction j when auth_first[j] <= k < auth_first[j + 1]; auth_first NULL: the call has no tuples.
+ * Per account: sends[j] = the length of row j's sequence; roles[j] = who named the row (PHANT_ROLE_*: the sender or recipient of a
+ * participating transaction, the authority of a PHANT_SIG_OK tuple of one, a probe).  Per probe (any further address the caller wants
+ * located: coinbase, withdrawal recipients, access-list and delegation targets): probe_row = row_of(probe).
+ * first_bad (always written): the least i whose state_flags carry an error bit, n if none (0 for n == 0); n_undetermined.
+ *
+ * Any output pointer may be NULL.  PHANT_E_INVALID_ARG, before anything is indexed with the offending value: a wrong struct_size, an
+ * unknown fork, reserved != 0, a NULL input whose count is not zero (auth_first may be NULL, code_off may not when n_codes > 0), auth_first
+ * not non-decreasing within [0, n_auth], code_off not non-decreasing within [0, code_bytes], a code_index that is neither < n_codes
+ * nor PHANT_CODE_NONE.  Nothing outside the stated extents is read; of `codes` only the first three bytes of the codes of 23 bytes.
+ * Host form: checked on the host before anything is copied; one staged upload, the launches, one copy back of the wanted outputs,
+ * one synchronisation.  Device form: every array is device memory (uint64_t arrays 8-byte, uint32_t arrays 4-byte aligned), both
+ * structs host memory; the offsets and indices are checked by a kernel whose verdict the host reads before any other kernel uses
+ * them; the call synchronises the ctx stream. */
+#define PHANT_ROW_NONE 0xffffffffu
+#define PHANT_TXST_SENDER_UNKNOWN 0x001u  /* the witness lacks the sender, or its row is not proven */
+#define PHANT_TXST_TO_UNKNOWN 0x002u      /* ... the recipient */
+#define PHANT_TXST_NONCE_LOW 0x004u       /* InvalidTxNonce: nonce < expected_nonce */
+#define PHANT_TXST_NONCE_HIGH 0x008u      /* InvalidTxNonce: nonce > expected_nonce */
+#define PHANT_TXST_BALANCE_SHORT 0x010u   /* NotEnoughBalance, certain: the block's first transaction */
+#define PHANT_TXST_NOT_EOA 0x020u         /* SenderIsNotEOA (EIP-3607) */
+#define PHANT_TXST_CODE_MISSING 0x040u    /* PRAGUE: the sender has code the witness does not carry */
+#define PHANT_TXST_ERROR_BITS 0x07fu      /* first_bad counts these */
+#define PHANT_TXST_SKIPPED 0x100u         /* no error: the row does not participate */
+#define PHANT_TXST_UNDETERMINED 0x200u    /* advisory: the sender rules were not evaluated */
+#define PHANT_TXST_NEEDS_INFLOW 0x400u    /* advisory: the balance does not cover spent_before + the row's cost */
+#define PHANT_TXST_SPENT_SATURATED 0x800u /* advisory: spent_before was clamped to 2^256 - 1 */
+#define PHANT_ROLE_SENDER 1u
+#define PHANT_ROLE_RECIPIENT 2u
+#define PHANT_ROLE_AUTHORITY 4u
+#define PHANT_ROLE_PROBE 8u
+typedef struct phant_txstate_in {
+    uint32_t struct_size; /* = sizeof(phant_txstate_in) */
+    uint32_t fork;        /* PHANT_TXS_FORK_* */
+    uint32_t n;           /* transaction rows */
+    uint32_t n_auth;      /* authorization rows */
+    uint32_t n_accounts;  /* pre-state rows */
+    uint32_t n_codes;
+    uint32_t n_probe;
+    uint32_t reserved;    /* 0 */
+    /* per transaction, straight from phant_txs_out / phant_txs_ex_out */
+    const uint8_t *sender;       /* n x 20 */
+    const uint8_t *sig_status;   /* n */
+    const uint32_t *tx_flags;    /* n: phant_txs_out.flags */
+    const uint64_t *nonce;       /* n */
+    const uint8_t *upfront_cost; /* n x 32 */
+    const uint8_t *to;           /* n x 20 */
+    const uint32_t *auth_first;  /* n + 1, or NULL */
+    const uint8_t *authority;    /* n_auth x 20 */
+    const uint8_t *auth_status;  /* n_auth */
+    /* per pre-state row, straight from phant_exec_witness_info / phant_prestate */
+    const uint8_t *addresses;      /* n_accounts x 20 */
+    const uint8_t *account_status; /* n_accounts */
+    const uint64_t *nonces;        /* n_accounts */
+    const uint8_t *balances;       /* n_accounts x 32 */
+    const uint8_t *code_hashes;    /* n_accounts x 32 */
+    const uint32_t *code_index;    /* n_accounts */
+    const uint64_t *code_off;      /* n_codes + 1 */
+    const uint8_t *codes;
+    uint64_t code_bytes;
+    const uint8_t *probe;          /* n_probe x 20 */
+} phant_txstate_in;
+typedef struct phant_txstate_out {
+    uint32_t struct_size;    /* = sizeof(phant_txstate_out) */
+    uint32_t first_bad;      /* result */
+    uint32_t n_undetermined; /* result */
+    uint32_t reserved;
+    /* per transaction */
+    uint32_t *sender_row;
+    uint32_t *to_row;
+    uint64_t *expected_nonce;
+    uint8_t *spent_before;   /* 32 big-endian */
+    uint32_t *state_flags;   /* PHANT_TXST_* */
+    /* per pre-state row */
+    uint32_t *sends;
+    uint8_t *roles;          /* PHANT_ROLE_* */
+    /* per probe */
+    uint32_t *probe_row;
+} phant_txstate_out;
+PHANT_API int32_t phant_block_txs_prestate(phant_ctx *ctx, const phant_txstate_in *in, phant_txstate_out *out);
+PHANT_API int32_t phant_block_txs_prestate_dev(phant_ctx *ctx, const phant_txstate_in *in, phant_txstate_out *out);
+
 /* ------------------------------------------------------- proof verification
  * ABSENT in the reference: this is the call the TODO at
  * src/engine_api/execution_payload.zig:177-178 asks for (witness field

@@ -74,6 +74,8 @@ SYMBOLS = {
     "phant_block_transactions_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_transactions_ex": (_i32, [_vp, _vp, _vp]),
     "phant_block_transactions_ex_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
+    "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_verify_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_mpt_verify_batch_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
@@ -236,6 +238,33 @@ class PhantTxsExOut(C.Structure):
     """phant_txs_ex_out (include/phant_gpu.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("n_auth", C.c_uint32), ("blob_gas_used", C.c_uint64), ("base", PhantTxsOut)] + \
                [(name, C.c_void_p) for name, _, _ in TX_EX_OUTPUTS + TX_AUTH_OUTPUTS]
+
+
+ROW_NONE = 0xFFFFFFFF
+# phant_txstate_in's arrays in the struct's order (code_bytes sits between codes and probe)
+TXSTATE_INPUTS = ("sender", "sig_status", "tx_flags", "nonce", "upfront_cost", "to", "auth_first", "authority", "auth_status", "addresses",
+                  "account_status", "nonces", "balances", "code_hashes", "code_index", "code_off", "codes")
+# phant_txstate_out's arrays in the struct's order: (name, numpy dtype, elements per row, the count its rows follow)
+TXSTATE_OUTPUTS = (("sender_row", "u4", 1, "n"), ("to_row", "u4", 1, "n"), ("expected_nonce", "u8", 1, "n"), ("spent_before", "u1", 32, "n"),
+                   ("state_flags", "u4", 1, "n"), ("sends", "u4", 1, "n_accounts"), ("roles", "u1", 1, "n_accounts"), ("probe_row", "u4", 1, "n_probe"))
+# PHANT_TXST_*: bit k of state_flags[i]; the bits below 0x80 are errors
+TXST_FLAG_NAMES = ("SenderUnknown", "ToUnknown", "NonceLow", "NonceHigh", "BalanceShort", "NotEOA", "CodeMissing", None, "Skipped", "Undetermined",
+                   "NeedsInflow", "SpentSaturated")
+TXST_ERROR_BITS = 0x7F
+TXST_SKIPPED, TXST_UNDETERMINED, TXST_NEEDS_INFLOW, TXST_SPENT_SATURATED = 0x100, 0x200, 0x400, 0x800
+ROLE_SENDER, ROLE_RECIPIENT, ROLE_AUTHORITY, ROLE_PROBE = 1, 2, 4, 8
+
+
+class PhantTxstateIn(C.Structure):
+    """phant_txstate_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "fork", "n", "n_auth", "n_accounts", "n_codes", "n_probe", "reserved")] + \
+               [(name, C.c_void_p) for name in TXSTATE_INPUTS] + [("code_bytes", C.c_uint64), ("probe", C.c_void_p)]
+
+
+class PhantTxstateOut(C.Structure):
+    """phant_txstate_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "first_bad", "n_undetermined", "reserved")] + \
+               [(name, C.c_void_p) for name, _, _, _ in TXSTATE_OUTPUTS]
 
 
 class PhantProveOut(C.Structure):

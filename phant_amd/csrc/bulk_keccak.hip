@@ -260,3 +260,4 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 }  // namespace phant
 
 #include "transactions.hip.h"
+#include "txstate.hip.h"

@@ -22,6 +22,7 @@
 #include "receipts.h"
 #include "headers.h"
 #include "transactions.h"
+#include "txstate.h"
 #include "trie_build.h"
 #include "witness.h"
 #include "host_rlp.h"
@@ -957,6 +958,42 @@ int32_t phant_block_transactions_ex_dev(phant_ctx* c, const phant_txs_ex_in* in,
     if (!in || !out) return fail(c, PHANT_E_INVALID_ARG, "block_transactions_ex_dev: in / out is null");
     return block_transactions_impl(c, &in->base, &out->base, in, out, true);
 }
+
+/* ------------------------------------------------- a block's transactions against the pre-state (txstate.hip.h) */
+
+static int32_t block_txs_prestate_impl(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out, bool dev) {
+    const char* const who = dev ? "block_txs_prestate_dev" : "block_txs_prestate";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_txstate_in) || out->struct_size != sizeof(phant_txstate_out)) return bad("wrong struct_size");
+    if (in->fork > PHANT_TXS_FORK_PRAGUE) return bad("unknown fork");
+    if (in->reserved != 0u) return bad("reserved is not 0");
+    if (in->n && (!in->sender || !in->sig_status || !in->tx_flags || !in->nonce || !in->upfront_cost || !in->to)) return bad("null transaction array");
+    if (in->n_auth && (!in->authority || !in->auth_status)) return bad("null authority / auth_status");
+    if (in->n_accounts && (!in->addresses || !in->account_status || !in->nonces || !in->balances || !in->code_hashes || !in->code_index))
+        return bad("null pre-state array");
+    if (in->n_codes && !in->code_off) return bad("null code_off");
+    if (in->code_bytes && !in->codes) return bad("null codes");
+    if (in->n_probe && !in->probe) return bad("null probe");
+    if (in->n_accounts > 0x7fffffffu) return fail(c, PHANT_E_UNSUPPORTED, (std::string(who) + ": 2^31 pre-state rows or more").c_str());
+    if (dev) {  // (kernels read these as words; the outputs arrive by device-to-device copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->nonce | (uintptr_t)in->nonces | (uintptr_t)in->code_off | (uintptr_t)out->expected_nonce;
+        const uintptr_t w4 = (uintptr_t)in->tx_flags | (uintptr_t)in->auth_first | (uintptr_t)in->code_index | (uintptr_t)out->sender_row |
+                             (uintptr_t)out->to_row | (uintptr_t)out->state_flags | (uintptr_t)out->sends | (uintptr_t)out->probe_row;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    const int32_t rc = phant::block_txs_prestate(c->ws, c->stream, *in, *out, dev, c->ns_salt, err);
+    if (rc) return fail(c, rc, err.c_str());
+    return PHANT_OK;
+}
+
+int32_t phant_block_txs_prestate(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out) { return block_txs_prestate_impl(c, in, out, false); }
+
+int32_t phant_block_txs_prestate_dev(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out) { return block_txs_prestate_impl(c, in, out, true); }
 
 int32_t phant_diag_secp_op(phant_ctx* c, uint32_t op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out) {
     if (!c) return PHANT_E_INVALID_ARG;

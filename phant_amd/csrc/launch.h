@@ -250,6 +250,13 @@ size_t order_workspace_bytes(uint32_t n);
 hipError_t launch_order_digests(const uint8_t* d_digests, const uint32_t* d_seg_of, uint32_t n, uint32_t n_seg, uint8_t* ws,
                                 uint32_t** d_order_out, uint32_t** d_flag_out, uint32_t prefix_bits, hipStream_t st);
 
+// radix_sort.hip: the stable sort of n (64-bit key, 32-bit value) pairs by the low `bits` key bits (rounded up to whole bytes; three
+// launches per byte).  The pairs end up in *keys_out / *vals_out, which are the given buffers or their alternates; hist:
+// sort_hist_entries(n) counters, digit_totals: 512 counters the caller has zeroed.
+size_t sort_hist_entries(uint32_t n);
+hipError_t launch_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt, uint32_t n, uint32_t bits, uint32_t* hist,
+                             uint32_t* digit_totals, uint64_t** keys_out, uint32_t** vals_out, hipStream_t st);
+
 // exclusive prefix sum of d[0 .. n) in place; d 16-byte aligned, scratch = scan_scratch_entries(n) counters of device memory
 size_t scan_scratch_entries(uint32_t n);
 hipError_t launch_exclusive_scan_u32(uint32_t* d, uint32_t n, uint32_t* scratch, hipStream_t st);

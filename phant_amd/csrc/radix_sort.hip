@@ -410,6 +410,17 @@ hipError_t launch_order_digests(const uint8_t* d_digests, const uint32_t* d_seg_
     return hipGetLastError();
 }
 
+// The stable sort by itself (txstate.hip.h: a block's transactions by their sender's witness row): n pairs by the low `bits` bits of
+// their keys, three launches per 8 bits.  hist: sort_hist_entries(n) counters; digit_totals: 512 counters the caller has zeroed.
+size_t sort_hist_entries(uint32_t n) { return (size_t)256 * sort_tiles(n); }
+hipError_t launch_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt, uint32_t n, uint32_t bits, uint32_t* hist,
+                             uint32_t* digit_totals, uint64_t** keys_out, uint32_t** vals_out, hipStream_t st) {
+    uint32_t cur = 0;
+    const hipError_t e = n ? sort_pairs(keys, vals, keys_alt, vals_alt, n, 0u, (bits + 7u) / 8u * 8u, hist, digit_totals, cur, st) : hipSuccess;
+    *keys_out = keys, *vals_out = vals;
+    return e;
+}
+
 // exclusive prefix sum of d[0 .. n) in place (d 16-byte aligned; scratch: scan_scratch_entries(n) counters).  With n + 1
 // entries and d[n] = 0 on entry, d[n] is the total on exit.
 hipError_t launch_exclusive_scan_u32(uint32_t* d, uint32_t n, uint32_t* scratch, hipStream_t st) { return exclusive_scan(d, n, scratch, st); }

@@ -123,3 +123,58 @@ def block_transactions(raw_txs, chain_id, base_fee=None, block_gas_limit=None, r
     ctx.check(ctx._lib.phant_block_transactions_ex(ctx.handle, C.byref(xarg), C.byref(xout)))
     arrays.update({name: a[:int(xout.n_auth)] for name, a in auth.items()})
     return BlockTransactions(blob, arrays, int(xout.base.first_bad), int(fork), int(xout.n_auth), int(xout.blob_gas_used))
+
+
+class TransactionsAgainstPrestate:
+    """What phant_block_txs_prestate answers: one numpy array per output of include/phant_gpu.h's phant_txstate_out (spent_before as
+    (n, 32) uint8, big-endian), `first_bad` and `n_undetermined`."""
+    FLAG_NAMES = L.TXST_FLAG_NAMES
+    ERROR_BITS = L.TXST_ERROR_BITS
+
+    def __init__(self, arrays, first_bad, n_undetermined):
+        self.first_bad, self.n_undetermined = first_bad, n_undetermined
+        self.__dict__.update(arrays)
+        self.n = len(self.state_flags)
+
+    def errors(self, i):
+        """the names of transaction i's failed rules"""
+        return [name for k, name in enumerate(self.FLAG_NAMES) if name and (int(self.state_flags[i]) & self.ERROR_BITS) >> k & 1]
+
+    def undetermined(self, i) -> bool:
+        return bool(int(self.state_flags[i]) & L.TXST_UNDETERMINED)
+
+
+def against_prestate(bt: BlockTransactions, prestate, witness_info, fork, probe=(), ctx: Context | None = None) -> TransactionsAgainstPrestate:
+    """A block's transactions against the pre-state its witness proves <-> phant_block_txs_prestate: which witness row every sender,
+    recipient, authority and probe is, the nonce every transaction must carry, EIP-3607, and what a sender can have spent before each of
+    its transactions (blockchain.zig:270-276, for the whole block before any transaction runs).  bt: `block_transactions` of the block
+    (with its senders); prestate, witness_info: `StatelessWitness.prestate()` and `.info()` of phant_amd/stateless.py (anything with
+    their arrays will do); fork: FORK_*; probe: further 20-byte addresses to locate."""
+    ctx = ctx or default_context()
+    if not hasattr(bt, "sender"):
+        raise ValueError("against_prestate needs the senders: block_transactions(..., recover=True)")
+    u8 = lambda a, width: np.ascontiguousarray(np.asarray(a, np.uint8).reshape(-1, width))  # noqa: E731
+    n, na, nc = bt.n, int(witness_info["n_accounts"]), int(witness_info["n_codes"])
+    has_auth = hasattr(bt, "authority") and hasattr(bt, "auth_first")
+    n_auth = len(bt.auth_status) if has_auth else 0
+    probes = u8(np.frombuffer(b"".join(bytes(p) for p in probe), np.uint8), 20)
+    ins = {"sender": u8(bt.sender, 20), "sig_status": np.ascontiguousarray(bt.sig_status, np.uint8), "tx_flags": np.ascontiguousarray(bt.flags, np.uint32),
+           "nonce": np.ascontiguousarray(bt.nonce, np.uint64), "upfront_cost": u8(bt.upfront_cost, 32), "to": u8(bt.to, 20),
+           "auth_first": np.ascontiguousarray(bt.auth_first, np.uint32) if has_auth else None,
+           "authority": u8(bt.authority, 20) if has_auth else None, "auth_status": np.ascontiguousarray(bt.auth_status, np.uint8) if has_auth else None,
+           "addresses": u8(witness_info["addresses"], 20), "account_status": np.ascontiguousarray(prestate.account_status, np.uint8),
+           "nonces": np.ascontiguousarray(prestate.nonces, np.uint64), "balances": u8(prestate.balances, 32), "code_hashes": u8(prestate.code_hashes, 32),
+           "code_index": np.ascontiguousarray(prestate.code_index, np.uint32), "code_off": np.ascontiguousarray(witness_info["code_off"], np.uint64),
+           "codes": np.ascontiguousarray(witness_info["codes"], np.uint8)}
+    if len(ins["account_status"]) < na or len(ins["addresses"]) < na:
+        raise ValueError("the pre-state has fewer rows than the witness has accounts")
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rows = {"n": n, "n_accounts": na, "n_probe": len(probes)}
+    arrays = {name: np.zeros((rows[r], k) if k > 1 else rows[r], dtype) for name, dtype, k, r in L.TXSTATE_OUTPUTS}
+    arg = L.PhantTxstateIn(C.sizeof(L.PhantTxstateIn), int(fork), n, n_auth, na, nc, len(probes), 0, *[ptr(ins[name]) for name in L.TXSTATE_INPUTS],
+                           int(witness_info["code_bytes"]), ptr(probes))
+    if has_auth:
+        arg.auth_first = ins["auth_first"].ctypes.data
+    out = L.PhantTxstateOut(C.sizeof(L.PhantTxstateOut), 0, 0, 0, *[ptr(arrays[name]) for name, _, _, _ in L.TXSTATE_OUTPUTS])
+    ctx.check(ctx._lib.phant_block_txs_prestate(ctx.handle, C.byref(arg), C.byref(out)))
+    return TransactionsAgainstPrestate(arrays, int(out.first_bad), int(out.n_undetermined))
