@@ -25,6 +25,7 @@
 
 #include "../../include/phant_gpu.h"
 #include "launch.h"
+#include "rlp.h"
 
 // RCCL's names and entry points (resolved at run time) and one host thread per device: comm_host.h (the CPU test suite's
 // phant_platform.h names a stand-in: an in-process sum, devices one after the other).
@@ -228,20 +229,8 @@ int32_t root_from_parts(phant_comm* c, const std::vector<Part>& parts, uint8_t o
         }
     }
     b[body++] = 0x80;  // no value at the root (every key has at least one byte)
-    uint8_t* start;
-    if (body <= 55) {
-        start = node + 2;
-        start[0] = (uint8_t)(0xc0 + body);
-    } else if (body <= 255) {
-        start = node + 1;
-        start[0] = 0xf8;
-        start[1] = (uint8_t)body;
-    } else {
-        start = node;
-        start[0] = 0xf9;
-        start[1] = (uint8_t)(body >> 8);
-        start[2] = (uint8_t)body;
-    }
+    uint8_t* const start = b - phant::hdr_len(body);  // (at most three bytes: the body is below 64 KiB)
+    (void)phant::put_hdr(start, 0xc0u, body);
     return phant_keccak256(c->ctx[0], start, (uint64_t)(b + body - start), out);
 }
 

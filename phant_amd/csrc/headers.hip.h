@@ -27,7 +27,9 @@
 #include "../../include/phant_gpu.h"
 #include "headers.h"
 #include "launch.h"
-#include "receipts.hip.h"
+#include "rlp.h"
+#include "trie_build.h"
+#include "wave_util.hip.h"
 
 namespace phant {
 namespace hd {
@@ -68,43 +70,26 @@ HD_HD bool seg_args_ok(const In& in, uint32_t j) {
     return j != 0u || (in.seg_first[0] == 0u && in.seg_first[in.n_segs] == in.n);
 }
 
-// a 32-byte big-endian integer's significant bytes
-HD_HD uint32_t be32_bytes(const uint8_t* v) {
-    uint32_t z = 0;
-    while (z < 32u && v[z] == 0u) ++z;
-    return 32u - z;
-}
-HD_HD uint32_t fee_len(const uint8_t* v) {
-    const uint32_t nb = be32_bytes(v);
-    return nb == 0u ? 1u : (nb == 1u && v[31] < 0x80u) ? 1u : 1u + nb;
-}
 // the payload of header i's list (its arguments are sound: header_args_ok)
 HD_HD uint64_t payload_len(const In& in, uint32_t i) {
     const uint32_t nf = in.n_fields[i];
     const uint64_t xl = in.extra_off[i + 1u] - in.extra_off[i];
-    uint64_t p = STATIC_BYTES + rc::gas_len(in.difficulty[i]) + rc::gas_len(in.number[i]) + rc::gas_len(in.gas_limit[i]) + rc::gas_len(in.gas_used[i]) +
-                 rc::gas_len(in.timestamp[i]) + rc::str_len(xl, xl == 1u ? in.extra_data[in.extra_off[i]] : 0u) + 33u + 9u;
-    if (nf >= 16u) p += fee_len(in.base_fee + 32ull * i);
+    uint64_t p = STATIC_BYTES + uint_len(in.difficulty[i]) + uint_len(in.number[i]) + uint_len(in.gas_limit[i]) + uint_len(in.gas_used[i]) +
+                 uint_len(in.timestamp[i]) + str_len(xl, xl == 1u ? in.extra_data[in.extra_off[i]] : 0u) + 33u + 9u;
+    if (nf >= 16u) {
+        const uint8_t* const f = in.base_fee + 32ull * i;
+        p += str_len(be_bytes(f, 32u), f[31]);
+    }
     if (nf >= 17u) p += 33u;
-    if (nf >= 19u) p += rc::gas_len(in.blob_gas_used[i]) + rc::gas_len(in.excess_blob_gas[i]);
+    if (nf >= 19u) p += uint_len(in.blob_gas_used[i]) + uint_len(in.excess_blob_gas[i]);
     if (nf >= 20u) p += 33u;
     if (nf >= 21u) p += 33u;
     return p;
 }
 HD_HD uint64_t header_len(const In& in, uint32_t i) {
     const uint64_t p = payload_len(in, i);
-    return rc::hdr_len(p) + p;
+    return hdr_len(p) + p;
 }
-// an integer by RLP's rules -> bytes written
-HD_HD uint32_t put_int(uint8_t* o, uint64_t v) {
-    if (v == 0u) return o[0] = 0x80u, 1u;
-    if (v < 0x80u) return o[0] = (uint8_t)v, 1u;
-    const uint32_t nb = rc::be_bytes(v);
-    o[0] = (uint8_t)(0x80u + nb);
-    for (uint32_t k = 0; k < nb; ++k) o[1u + k] = (uint8_t)(v >> (8u * (nb - 1u - k)));
-    return 1u + nb;
-}
-
 // ---- the expected base fee (EIP-1559, blockchain.zig:105-119) in exact arithmetic: 32-bit limbs, little-endian
 struct Wide {
     uint32_t w[10];  // 320 bits: a 256-bit fee times a 64-bit gas delta
@@ -277,13 +262,13 @@ __global__ void __launch_bounds__(256) hdr_encode_kernel(In in, const uint32_t* 
             if (i + 1u == in.n) enc_off[in.n] = end;
         }
         const uint64_t payload = payload_len(in, i);
-        if (end > enc_cap || end - at != rc::hdr_len(payload) + payload) continue;  // (cannot happen: sized from the same rules)
+        if (end > enc_cap || end - at != hdr_len(payload) + payload) continue;  // (cannot happen: sized from the same rules)
         const uint32_t nf = in.n_fields[i];
-        uint8_t* const s = enc + at + rc::hdr_len(payload);  // the static part: 5 hashes, the address, the bloom
+        uint8_t* const s = enc + at + hdr_len(payload);  // the static part: 5 hashes, the address, the bloom
         const uint8_t* const h32[5] = {in.parent_hash, in.uncle_hash, in.state_root, in.transactions_root, in.receipts_root};
         const uint32_t h_at[5] = {0u, 33u, 87u, 120u, 153u};
         if (lane == 0u) {
-            (void)rc::put_hdr(enc + at, 0xc0u, payload);
+            (void)put_hdr(enc + at, 0xc0u, payload);
 #pragma unroll
             for (int k = 0; k < 5; ++k) s[h_at[k]] = 0xa0u;
             s[66] = 0x94u;
@@ -302,16 +287,16 @@ __global__ void __launch_bounds__(256) hdr_encode_kernel(In in, const uint32_t* 
         if (lane == 0u) {
             uint8_t* o = t;
 #pragma unroll
-            for (int k = 0; k < 5; ++k) o += put_int(o, ints[k]);
+            for (int k = 0; k < 5; ++k) o += put_uint(o, ints[k]);
         }
 #pragma unroll
-        for (int k = 0; k < 5; ++k) t += rc::gas_len(ints[k]);
+        for (int k = 0; k < 5; ++k) t += uint_len(ints[k]);
         const uint64_t xl = in.extra_off[i + 1u] - in.extra_off[i];
         const uint8_t* const x = in.extra_data + in.extra_off[i];
         const bool bare = xl == 1u && x[0] < 0x80u;  // a single byte below 0x80 is its own encoding
-        const uint32_t xh = bare ? 0u : rc::hdr_len(xl);
-        if (lane == 0u && !bare) (void)rc::put_hdr(t, 0x80u, xl);
-        rc::wave_copy(t + xh, x, xl, lane);
+        const uint32_t xh = bare ? 0u : hdr_len(xl);
+        if (lane == 0u && !bare) (void)put_hdr(t, 0x80u, xl);
+        wave_copy(t + xh, x, xl, lane);
         t += xh + xl;
         if (lane == 0u) t[0] = 0xa0u, t[33] = 0x88u;
         if (lane < 32u) t[1u + lane] = in.prev_randao[32ull * i + lane];
@@ -319,7 +304,7 @@ __global__ void __launch_bounds__(256) hdr_encode_kernel(In in, const uint32_t* 
         t += 42u;
         if (nf >= 16u) {
             const uint8_t* const f = in.base_fee + 32ull * i;
-            const uint32_t nb = be32_bytes(f), fl = fee_len(f);
+            const uint32_t nb = be_bytes(f, 32u), fl = (uint32_t)str_len(nb, f[31]);
             if (lane == 0u) {
                 if (nb == 0u) t[0] = 0x80u;
                 else if (fl == 1u) t[0] = f[31];
@@ -334,8 +319,8 @@ __global__ void __launch_bounds__(256) hdr_encode_kernel(In in, const uint32_t* 
             t += 33u;
         }
         if (nf >= 19u) {
-            if (lane == 0u) (void)put_int(t + put_int(t, in.blob_gas_used[i]), in.excess_blob_gas[i]);
-            t += rc::gas_len(in.blob_gas_used[i]) + rc::gas_len(in.excess_blob_gas[i]);
+            if (lane == 0u) (void)put_uint(t + put_uint(t, in.blob_gas_used[i]), in.excess_blob_gas[i]);
+            t += uint_len(in.blob_gas_used[i]) + uint_len(in.excess_blob_gas[i]);
         }
         if (nf >= 20u) {
             if (lane == 0u) t[0] = 0xa0u;
@@ -356,7 +341,7 @@ __global__ void __launch_bounds__(256) hdr_check_kernel(In in, const uint8_t* __
     if (i >= in.n) return;
     if (i == 0u) ctl[2] = (uint32_t)enc_off[in.n], ctl[3] = (uint32_t)(enc_off[in.n] >> 32);
     bool anchor = i == 0u;
-    if (in.seg_first && i) anchor = in.seg_first[rc::upper_bound(in.seg_first, in.n_segs + 1u, i) - 1u] == i;
+    if (in.seg_first && i) anchor = in.seg_first[upper_bound(in.seg_first, in.n_segs + 1u, i) - 1u] == i;
     uint32_t f = anchor ? 0u : check_pair(in, i, hashes + 32ull * (i - 1u));
     if (in.expected_hash && !same32(in.expected_hash + 32ull * i, hashes + 32ull * i)) f |= PHANT_HDR_EXPECTED_HASH;
     if (flags) flags[i] = f;
@@ -400,7 +385,7 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
     const uint32_t n = hin.n, nulls = null_mask(hin);
     const bool small = n < SMALL_MAX;  // (n + 1 offsets, eight a lane)
     const bool want_enc = out.enc || out.enc_off;
-    const uint32_t grid = rc::blocks_of((uint64_t)n, 256);
+    const uint32_t grid = blocks_of((uint64_t)n, 256);
     HD_TRY(ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_HEADERS_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_HEADERS;
@@ -504,7 +489,7 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
         HD_TRY(hipMemsetAsync(d_len + n, 0, 4, st));
         HD_TRY(launch_exclusive_scan_u32(d_len, n + 1u, d_scan, st));
     }
-    const uint32_t waves = 4u * std::min(rc::blocks_of(n, 4), 4096u);
+    const uint32_t waves = 4u * std::min(blocks_of(n, 4), 4096u);
     hipLaunchKernelGGL(hdr_encode_kernel, dim3(waves / 4u), dim3(256), 0, st, d, small ? nullptr : d_len, d_enc_off, d_enc, enc_bound, waves);
     HD_TRY(hipGetLastError());
     HD_TRY(launch_keccak256_var(d_enc, d_enc_off, n, d_hashes, st));

@@ -5,33 +5,16 @@
 #include <vector>
 
 #include "../../include/phant_gpu.h"
+#include "rlp.h"
 
 namespace phant {
 
 
-// one canonical RLP item of `avail` bytes at p: payload offset / length, or false
+// one canonical RLP item of `avail` bytes at p: payload offset / length, or false (rlp.h's decoder over size_t offsets)
 bool host_rlp_item(const uint8_t* p, size_t avail, size_t& pay, size_t& len, size_t& total, bool& is_list) {
-    if (avail == 0) return false;
-    const uint8_t b = p[0];
-    if (b < 0x80) {
-        pay = 0, len = 1, total = 1, is_list = false;
-        return true;
-    }
-    if (b <= 0xb7 || (b >= 0xc0 && b <= 0xf7)) {
-        is_list = b >= 0xc0;
-        len = b - (is_list ? 0xc0 : 0x80);
-        pay = 1, total = 1 + len;
-        if (total > avail) return false;
-        if (!is_list && len == 1 && p[1] < 0x80) return false;
-        return true;
-    }
-    is_list = b >= 0xf8;
-    const size_t ll = b - (is_list ? 0xf7 : 0xb7);
-    if (1 + ll > avail || p[1] == 0) return false;
-    size_t l = 0;
-    for (size_t i = 0; i < ll; ++i) l = l << 8 | p[1 + i];
-    if (l <= 55 || l > avail - 1 - ll) return false;
-    pay = 1 + ll, len = l, total = 1 + ll + l;
+    RlpItemOf<size_t> it;
+    if (!rlp_decode(MemBytes{p}, 0, avail, it)) return false;
+    pay = it.pay, len = it.len, total = it.total, is_list = it.is_list != 0;
     return true;
 }
 
@@ -138,32 +121,11 @@ int32_t strip_first_nibble(const uint8_t* node, uint32_t len, uint8_t* out, uint
     if (nib.size() & 1) h.push_back((uint8_t)(f << 4 | nib[k++]));
     else h.push_back((uint8_t)(f << 4));
     for (; k + 1 < nib.size(); k += 2) h.push_back((uint8_t)(nib[k] << 4 | nib[k + 1]));
-    std::vector<uint8_t> body;
-    if (h.size() == 1 && h[0] < 0x80) body.push_back(h[0]);
-    else {
-        // canonical RLP string header: keys go up to 255 bytes (128 path bytes), beyond the 55-byte short form
-        if (h.size() <= 55) {
-            body.push_back((uint8_t)(0x80 + h.size()));
-        } else {
-            body.push_back((uint8_t)(0xb7 + (h.size() > 0xff ? 2 : 1)));
-            if (h.size() > 0xff) body.push_back((uint8_t)(h.size() >> 8));
-            body.push_back((uint8_t)h.size());
-        }
-        body.insert(body.end(), h.begin(), h.end());
-    }
+    uint8_t hdr[9];
+    std::vector<uint8_t> body(str_len(h.size(), h[0]));  // (keys go up to 255 bytes, 128 path bytes: beyond the short form)
+    (void)put_str(body.data(), h.data(), (uint32_t)h.size());
     body.insert(body.end(), rest, rest + rest_len);
-    std::vector<uint8_t> enc;
-    if (body.size() <= 55) enc.push_back((uint8_t)(0xc0 + body.size()));
-    else {
-        size_t l = body.size(), ll = 0;
-        uint8_t be[8];
-        while (l) {
-            be[ll++] = (uint8_t)l;
-            l >>= 8;
-        }
-        enc.push_back((uint8_t)(0xf7 + ll));
-        for (size_t q = 0; q < ll; ++q) enc.push_back(be[ll - 1 - q]);
-    }
+    std::vector<uint8_t> enc(hdr, hdr + put_hdr(hdr, 0xc0u, body.size()));
     enc.insert(enc.end(), body.begin(), body.end());
     *is_ref = 0;
     *out_len = (uint32_t)enc.size();
@@ -215,15 +177,8 @@ bool tx_access_list(const TxItem& al) {
 }
 
 void put_list_header(std::vector<uint8_t>& out, size_t len) {
-    if (len <= 55) {
-        out.push_back((uint8_t)(0xc0 + len));
-        return;
-    }
-    uint8_t be[8];
-    size_t ll = 0;
-    for (size_t l = len; l; l >>= 8) be[ll++] = (uint8_t)l;
-    out.push_back((uint8_t)(0xf7 + ll));
-    for (size_t q = 0; q < ll; ++q) out.push_back(be[ll - 1 - q]);
+    uint8_t hdr[9];
+    out.insert(out.end(), hdr, hdr + put_hdr(hdr, 0xc0u, len));
 }
 
 void pad32(uint8_t out[32], const TxItem& it) {
@@ -298,14 +253,7 @@ uint8_t tx_signing_parts(const uint8_t* tx, size_t len, uint64_t chain_id, std::
     uint8_t tail[12];
     size_t tail_len = 0;
     if (eip155) {
-        uint8_t be[8];
-        size_t ll = 0;
-        for (uint64_t cid = chain_id; cid; cid >>= 8) be[ll++] = (uint8_t)cid;
-        if (ll == 1 && be[0] < 0x80) tail[tail_len++] = be[0];
-        else {
-            tail[tail_len++] = (uint8_t)(0x80 + ll);
-            for (size_t q = 0; q < ll; ++q) tail[tail_len++] = be[ll - 1 - q];
-        }
+        tail_len = put_uint(tail, chain_id);
         tail[tail_len++] = 0x80;
         tail[tail_len++] = 0x80;
     }

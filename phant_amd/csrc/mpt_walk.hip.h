@@ -13,19 +13,13 @@
 // tile kernel share it.
 #pragma once
 #include "absorb.hip.h"
+#include "rlp.h"
 #include "../../include/phant_gpu.h"
 
 namespace phant {
 
-struct RlpItem {
-    uint32_t pay;    // payload offset from the start of the current node
-    uint32_t len;    // payload length
-    uint32_t total;  // header + payload
-    uint32_t is_list;
-};
-
 // Byte access to the node currently being decoded.  All offsets handed to it
-// are < node length (the decoder bounds-checks first).
+// are < node length (the decoder, rlp.h's rlp_decode, bounds-checks first).
 struct GlobalBytes {
     const uint8_t* p;
     PHANT_DEV uint32_t byte(uint32_t o) const { return p[o]; }
@@ -39,45 +33,6 @@ struct GlobalBytes {
         return alignbyte(b, a, sh);
     }
 };
-
-// One canonical RLP item at node offset `at` with `avail` bytes left.
-template <class Bytes>
-PHANT_DEV bool rlp_decode(const Bytes& nd, uint32_t at, uint32_t avail, RlpItem& it) {
-    if (avail == 0) return false;
-    const uint32_t b = nd.byte(at);
-    if (b < 0x80u) {
-        it.pay = at;
-        it.len = 1;
-        it.total = 1;
-        it.is_list = 0;
-        return true;
-    }
-    if (b <= 0xb7u || (b >= 0xc0u && b <= 0xf7u)) {
-        const uint32_t list = b >= 0xc0u;
-        const uint32_t len = b - (list ? 0xc0u : 0x80u);
-        if (1u + len > avail) return false;
-        if (!list && len == 1u && nd.byte(at + 1) < 0x80u) return false;
-        it.pay = at + 1;
-        it.len = len;
-        it.total = 1u + len;
-        it.is_list = list;
-        return true;
-    }
-    const uint32_t list = b >= 0xf8u;
-    const uint32_t ll = b - (list ? 0xf7u : 0xb7u);  // 1..8
-    if (1u + ll > avail) return false;
-    if (nd.byte(at + 1) == 0) return false;  // leading zero in the length
-    uint64_t len = 0;
-    for (uint32_t i = 0; i < ll; ++i) len = (len << 8) | nd.byte(at + 1 + i);
-    if (len <= 55) return false;  // short form was mandatory
-    const uint32_t hdr = 1u + ll;
-    if (len > (uint64_t)(avail - hdr)) return false;
-    it.pay = at + hdr;
-    it.len = (uint32_t)len;
-    it.total = hdr + (uint32_t)len;
-    it.is_list = list;
-    return true;
-}
 
 enum : uint32_t { REF_EMPTY = 0, REF_HASH = 1, REF_EMBED = 2, REF_BAD = 3 };
 PHANT_DEV uint32_t ref_kind(const RlpItem& it) {

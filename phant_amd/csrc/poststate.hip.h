@@ -439,55 +439,17 @@ __global__ void __launch_bounds__(256) post_link_kernel(const PoststateArgs p) {
 }
 
 // ---------------------------------------------------------------- encoding
-PHANT_DEV uint32_t put_list_header(uint8_t* out, uint32_t pl) {
-    if (pl < 56u) {
-        out[0] = (uint8_t)(0xc0u + pl);
-        return 1;
-    }
-    if (pl < 256u) {
-        out[0] = 0xf8;
-        out[1] = (uint8_t)pl;
-        return 2;
-    }
-    out[0] = 0xf9;
-    out[1] = (uint8_t)(pl >> 8);
-    out[2] = (uint8_t)pl;
-    return 3;
-}
-PHANT_DEV uint32_t put_string(uint8_t* out, const uint8_t* v, uint32_t n) {
-    uint32_t p = 0;
-    if (n == 1u && v[0] < 0x80u) {
-        out[0] = v[0];
-        return 1;
-    }
-    if (n < 56u) {
-        out[p++] = (uint8_t)(0x80u + n);
-    } else if (n < 256u) {
-        out[p++] = 0xb8;
-        out[p++] = (uint8_t)n;
-    } else {
-        out[p++] = 0xb9;
-        out[p++] = (uint8_t)(n >> 8);
-        out[p++] = (uint8_t)n;
-    }
-    for (uint32_t t = 0; t < n; ++t) out[p + t] = v[t];
-    return p + n;
-}
+// (headers, strings and integers: rlp.h's writers)
 // rlp([hex-prefix(nibs[0 .. n), leaf), item]) -- mpt.zig:187-193 / :254-261 / :285-314; `item` is RLP already
 PHANT_DEV uint32_t put_short_node(uint8_t* out, const uint8_t* nibs, uint32_t n, bool leaf, const uint8_t* item, uint32_t ilen) {
     const uint32_t hl = n / 2u + 1u, hpl = hl == 1u ? 1u : 1u + hl, pl = hpl + ilen;
-    uint32_t p = put_list_header(out, pl);
+    uint32_t p = put_hdr(out, 0xc0u, pl);
     if (hl != 1u) out[p++] = (uint8_t)(0x80u + hl);
     const uint32_t flag = (leaf ? 2u : 0u) + (n & 1u);
     out[p++] = (uint8_t)((flag << 4) | ((n & 1u) ? nibs[0] : 0u));
     for (uint32_t j = n & 1u; j < n; j += 2u) out[p++] = (uint8_t)((nibs[j] << 4) | nibs[j + 1]);
     for (uint32_t t = 0; t < ilen; ++t) out[p + t] = item[t];
     return p + ilen;
-}
-PHANT_DEV uint32_t put_minimal(uint8_t* out, const uint8_t* be, uint32_t n) {  // rlp of a big-endian integer
-    uint32_t z = 0;
-    while (z < n && be[z] == 0u) ++z;
-    return put_string(out, be + z, n - z);
 }
 // a node's reference: itself below 32 bytes (mpt.zig:104 / :112), else -- or when `force` (the root, :42) -- its Keccak-256
 // -- the single place a built node is hashed, and therefore where phant_exec_witness_advance takes its nodes from: a hashed node
@@ -588,25 +550,23 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
                 atomicAdd(&p.counters[POST_CNT_INTERNAL], 1u);
                 return 0;
             }
-            vl = put_string(vb, p.nodes + c->src, c->vlen);
+            vl = put_str(vb, p.nodes + c->src, c->vlen);
         } else if (kind == IK_LEAF_SLOT) {
             uint8_t v[36];
             const uint32_t l = put_minimal(v, p.post_slot_vals + 32ull * c->key, 32);
-            vl = put_string(vb, v, l);
+            vl = put_str(vb, v, l);
         } else {  // rlp([nonce, balance, storageRoot, codeHash]), types.zig:13-20
             const uint32_t i = c->key;
             const bool set = p.op[i] == PHANT_POST_SET;
-            uint8_t body[120], nb[8];
-            const uint64_t nonce = set ? p.post_nonces[i] : p.pre_nonces[i];
-            for (uint32_t t = 0; t < 8u; ++t) nb[t] = (uint8_t)(nonce >> (56u - 8u * t));
-            uint32_t q = put_minimal(body, nb, 8);
+            uint8_t body[120];
+            uint32_t q = put_uint(body, set ? p.post_nonces[i] : p.pre_nonces[i]);
             q += put_minimal(body + q, (set ? p.post_balances : p.pre_balances) + 32ull * i, 32);
-            q += put_string(body + q, p.post_sroots + 32ull * i, 32);
-            q += put_string(body + q, (set ? p.post_code_hashes : p.pre_code_hashes) + 32ull * i, 32);
+            q += put_str(body + q, p.post_sroots + 32ull * i, 32);
+            q += put_str(body + q, (set ? p.post_code_hashes : p.pre_code_hashes) + 32ull * i, 32);
             uint8_t acc[124];
-            const uint32_t h = put_list_header(acc, q);
+            const uint32_t h = put_hdr(acc, 0xc0u, q);
             for (uint32_t t = 0; t < q; ++t) acc[h + t] = body[t];
-            vl = put_string(vb, acc, h + q);
+            vl = put_str(vb, acc, h + q);
         }
         return node_ref(node, put_short_node(node, nibs, n, true, vb, vl), force, ref, here);
     }
@@ -684,9 +644,9 @@ __global__ void __launch_bounds__(64) post_level_kernel(const Args a, const int3
         buf[pos++] = 0x80;
         ++slot;
     }
-    const uint32_t pl = pos - 3u, hdr = pl < 56u ? 1u : pl < 256u ? 2u : 3u;
+    const uint32_t pl = pos - 3u, hdr = hdr_len(pl);  // (at most 3: a branch is below 64 KiB)
     uint8_t* const node = buf + 3u - hdr;
-    put_list_header(node, pl);
+    (void)put_hdr(node, 0xc0u, pl);
     const NodeAt at{p.sink_blob ? &p : nullptr, me->trie, i, ((uint32_t)(d + 1) << 1) | 1u};
     me->reflen = (uint8_t)node_ref(node, hdr + pl, false, me->ref, at);
     me->kind = IK_BUILT;

@@ -20,6 +20,7 @@
 
 #include "coop_sponge.hip.h"
 #include "launch.h"
+#include "rlp.h"
 #include "../../include/phant_gpu.h"
 
 namespace phant {
@@ -43,28 +44,6 @@ PHANT_DEV uint32_t get_word(const uint8_t* p, uint32_t w) {
     return v;
 }
 
-// One canonical RLP string at v[p .. len): its content [cb, cb + cl), p behind it.  Only the short forms (< 56 bytes): nothing
-// of an account body or a slot value is longer, so a long string or a list is not what is asked for.
-PHANT_DEV bool rlp_short_string(const uint8_t* v, uint32_t len, uint32_t& p, uint32_t& cb, uint32_t& cl) {
-    if (p >= len) return false;
-    const uint32_t b = v[p];
-    if (b < 0x80u) {
-        cb = p;
-        cl = 1;
-        p += 1;
-        return true;
-    }
-    if (b > 0xb7u) return false;
-    const uint32_t l = b - 0x80u;
-    if (l > len - p - 1u) return false;
-    if (l == 1u && v[p + 1u] < 0x80u) return false;  // (a single byte below 0x80 is its own encoding)
-    cb = p + 1u;
-    cl = l;
-    p += 1u + l;
-    return true;
-}
-
-
 __global__ void __launch_bounds__(256) account_decode_kernel(const phant::PrestateArgs a) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= a.na) return;
@@ -77,23 +56,17 @@ __global__ void __launch_bounds__(256) account_decode_kernel(const phant::Presta
     if (st == PHANT_PROOF_PRESENT) {
         const uint8_t* const v = a.nodes + a.acc_voff[i];
         const uint32_t len = a.acc_vlen[i];
-        uint32_t p = 0, pay = 0;
-        bool ok = len >= 1u;
-        if (ok) {
-            const uint32_t b = v[0];
-            if (b >= 0xc0u && b <= 0xf7u) {
-                pay = b - 0xc0u;
-                p = 1;
-            } else if (b == 0xf8u && len >= 2u && v[1] >= 56u) {
-                pay = v[1];
-                p = 2;
-            } else {
-                ok = false;
-            }
-        }
-        ok = ok && p + pay == len;
+        // the body: one list that is the whole value (rlp.h's decoder: canonical or refused), four strings inside it
+        const MemBytes vb{v};
+        RlpItem body;
+        bool ok = rlp_decode(vb, 0u, len, body) && body.is_list && body.total == len;
+        uint32_t p = ok ? body.pay : 0u;
         uint32_t cb[4] = {0, 0, 0, 0}, cl[4] = {0, 0, 0, 0};
-        for (uint32_t k = 0; k < 4u && ok; ++k) ok = rlp_short_string(v, len, p, cb[k], cl[k]);
+        for (uint32_t k = 0; k < 4u && ok; ++k) {
+            RlpItem it;
+            ok = rlp_decode(vb, p, len - p, it) && !it.is_list;
+            if (ok) cb[k] = it.pay, cl[k] = it.len, p += it.total;
+        }
         ok = ok && p == len;                                               // nothing behind the fourth item
         ok = ok && cl[0] <= 8u && (cl[0] == 0u || v[cb[0]] != 0u);         // nonce: u64, minimal
         ok = ok && cl[1] <= 32u && (cl[1] == 0u || v[cb[1]] != 0u);        // balance: u256, minimal
@@ -135,12 +108,10 @@ __global__ void __launch_bounds__(256) slot_decode_kernel(const phant::PrestateA
     } else if (st == PHANT_PROOF_PRESENT) {
         v = a.nodes + a.slot_voff[j];
         const uint32_t len = a.slot_vlen[j];
-        uint32_t p = 0;
-        const bool ok = rlp_short_string(v, len, p, cb, cl) && p == len && cl >= 1u && cl <= 32u && v[cb] != 0u;
-        if (!ok) {
-            st = PHANT_PROOF_BAD_VALUE;
-            cl = 0;
-        }
+        RlpItem it;
+        const bool ok = rlp_decode(MemBytes{v}, 0u, len, it) && !it.is_list && it.total == len && it.len >= 1u && it.len <= 32u && v[it.pay] != 0u;
+        if (ok) cb = it.pay, cl = it.len;
+        else st = PHANT_PROOF_BAD_VALUE;
     }
     if (st != PHANT_PROOF_PRESENT) cl = 0;
     for (uint32_t t = 0; t < 32u; ++t) out[t] = t < 32u - cl ? 0u : v[cb + t - (32u - cl)];

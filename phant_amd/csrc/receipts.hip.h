@@ -28,7 +28,9 @@
 #include "absorb.hip.h"
 #include "launch.h"
 #include "receipts.h"
+#include "rlp.h"
 #include "trie_build.h"
+#include "wave_util.hip.h"
 
 namespace phant {
 
@@ -92,30 +94,7 @@ RC_HD uint32_t key_bytes_before(uint32_t p) {
     return (uint32_t)b;
 }
 
-// ---- RLP's rules (Yellow Paper appendix B)
-RC_HD uint32_t be_bytes(uint64_t v) {
-    uint32_t n = 0;
-    while (v) {
-        ++n;
-        v >>= 8;
-    }
-    return n;
-}
-RC_HD uint32_t hdr_len(uint64_t payload) { return payload < 56u ? 1u : 1u + be_bytes(payload); }
-RC_HD uint32_t gas_len(uint64_t g) { return g < 0x80u ? 1u : 1u + be_bytes(g); }
-// a string of d bytes (first: its first byte, read only when d == 1)
-RC_HD uint64_t str_len(uint64_t d, uint32_t first) { return d == 1u ? (first < 0x80u ? 1u : 2u) : hdr_len(d) + d; }
-// base 0x80 (string) or 0xc0 (list)
-RC_HD uint32_t put_hdr(uint8_t* o, uint32_t base, uint64_t payload) {
-    if (payload < 56u) {
-        o[0] = (uint8_t)(base + payload);
-        return 1u;
-    }
-    const uint32_t nb = be_bytes(payload);
-    o[0] = (uint8_t)(base + 55u + nb);
-    for (uint32_t k = 0; k < nb; ++k) o[1u + k] = (uint8_t)(payload >> (8u * (nb - 1u - k)));
-    return 1u + nb;
-}
+// ---- lengths, from rlp.h's rules
 constexpr uint32_t BLOOM_FIELD = 3u + 256u;  // 0xb9 0x01 0x00 ++ bloom
 
 struct LogLen {
@@ -138,28 +117,12 @@ RC_HD uint64_t receipt_len(const In& in, uint32_t i, uint64_t& logs_payload, uin
         lp += log_len(in, l).total;
     }
     logs_payload = lp;
-    const uint64_t payload = 1u + gas_len(in.cum_gas[i]) + BLOOM_FIELD + hdr_len(lp) + lp;
+    const uint64_t payload = 1u + uint_len(in.cum_gas[i]) + BLOOM_FIELD + hdr_len(lp) + lp;
     return (in.tx_type[i] ? 1u : 0u) + hdr_len(payload) + payload;
 }
 // most bytes the receipts of a block of this shape can take
 inline uint64_t encoded_bound(uint32_t n, uint32_t n_logs, uint32_t n_topics, uint64_t data_bytes) {
     return (uint64_t)n * (1u + 9u + 1u + 9u + BLOOM_FIELD + 9u) + (uint64_t)n_logs * (9u + 21u + 9u + 9u) + 33ull * n_topics + data_bytes;
-}
-
-// first j in [0, cnt) with a[j] > v (a ascending, a[cnt - 1] > v)
-PHANT_DEV uint32_t upper_bound(const uint32_t* __restrict__ a, uint32_t cnt, uint32_t v) {
-    uint32_t lo = 0, hi = cnt - 1u;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] > v) hi = mid;
-        else lo = mid + 1u;
-    }
-    return lo;
-}
-
-// lanes of a wave copy len bytes (any alignment on either side)
-PHANT_DEV void wave_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t len, uint32_t lane) {
-    for (uint64_t k = lane; k < len; k += 64u) dst[k] = src[k];
 }
 
 __global__ void __launch_bounds__(256) rc_check_kernel(In in, uint32_t* __restrict__ ctl) {
@@ -249,13 +212,7 @@ PHANT_DEV void write_key(const uint32_t* __restrict__ meta, uint32_t n_tries, ui
     const uint32_t p = g - meta[t], n = meta[t + 1u] - meta[t], idx = index_of_pos(p, n);
     const uint32_t ko = meta[n_tries + 1u + t] + key_bytes_before(p);
     key_off[g] = ko;
-    if (idx == 0u) keys[ko] = 0x80u;
-    else if (idx < 0x80u) keys[ko] = (uint8_t)idx;
-    else {
-        const uint32_t nb = be_bytes(idx);
-        keys[ko] = (uint8_t)(0x80u + nb);
-        for (uint32_t k = 0; k < nb; ++k) keys[ko + 1u + k] = (uint8_t)(idx >> (8u * (nb - 1u - k)));
-    }
+    (void)put_uint(keys + ko, idx);
 }
 
 // len = the scanned lengths
@@ -339,23 +296,16 @@ __global__ void __launch_bounds__(256) rc_encode_kernel(In in, const uint32_t* _
         if (val_off[pos + 1u] > val_cap) continue;  // (cannot happen: the array is sized from the same rules)
         uint8_t* const out = vals + val_off[pos];
         const uint64_t lp = logs_payload[i];
-        const uint64_t payload = 1u + gas_len(in.cum_gas[i]) + BLOOM_FIELD + hdr_len(lp) + lp;
+        const uint64_t payload = 1u + uint_len(in.cum_gas[i]) + BLOOM_FIELD + hdr_len(lp) + lp;
         const uint32_t at_status = (in.tx_type[i] ? 1u : 0u) + hdr_len(payload);
-        const uint32_t at_bloom = at_status + 1u + gas_len(in.cum_gas[i]) + 3u;
+        const uint32_t at_bloom = at_status + 1u + uint_len(in.cum_gas[i]) + 3u;
         if (head) {
             if (lane == 0u) {
                 uint8_t* o = out;
                 if (in.tx_type[i]) *o++ = in.tx_type[i];
                 o += put_hdr(o, 0xc0u, payload);
                 *o++ = in.status[i] ? 0x01u : 0x80u;  // EIP-658: the integer 1 or 0
-                const uint64_t g = in.cum_gas[i];
-                if (g == 0u) *o++ = 0x80u;
-                else if (g < 0x80u) *o++ = (uint8_t)g;
-                else {
-                    const uint32_t nb = be_bytes(g);
-                    *o++ = (uint8_t)(0x80u + nb);
-                    for (uint32_t k = 0; k < nb; ++k) *o++ = (uint8_t)(g >> (8u * (nb - 1u - k)));
-                }
+                o += put_uint(o, in.cum_gas[i]);
                 o[0] = 0xb9u;
                 o[1] = 0x01u;
                 o[2] = 0x00u;
@@ -423,7 +373,6 @@ __global__ void __launch_bounds__(256) rc_gather_kernel(const uint8_t* __restric
     if (out) wave_copy(out + at, vals + val_off[p], val_off[p + 1u] - val_off[p], lane);
 }
 
-inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1u) / per); }
 
 #define RC_TRY(call)                                                        \
     do {                                                                    \

@@ -30,6 +30,7 @@
 
 #include "../../include/phant_gpu.h"
 #include "launch.h"
+#include "rlp.h"
 #include "trie_build.h"
 #include "witness.h"
 
@@ -48,7 +49,8 @@ namespace {
 inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 
 // ------------------------------------------------------------------ kernels
-// bytes of the minimal big-endian form of a 32-byte value (0 for zero); v is 4-byte aligned
+// bytes of the minimal big-endian form of a 32-byte value (0 for zero); v is 4-byte aligned.  rlp.h's be_bytes(v, 32) says the same
+// byte by byte; this dword form relies on the alignment, which that one must not assume, and stays here.
 __device__ __forceinline__ uint32_t be_len32(const uint8_t* v) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(v);
     for (uint32_t i = 0; i < 8u; ++i) {
@@ -57,17 +59,8 @@ __device__ __forceinline__ uint32_t be_len32(const uint8_t* v) {
     }
     return 0u;
 }
-// canonical RLP of a byte string of <= 32 bytes at `o`; returns its length
-__device__ __forceinline__ uint32_t put_rlp_short(uint8_t* o, const uint8_t* s, uint32_t len) {
-    if (len == 1u && s[0] < 0x80u) {
-        o[0] = s[0];
-        return 1u;
-    }
-    o[0] = (uint8_t)(0x80u + len);
-    for (uint32_t i = 0; i < len; ++i) o[1u + i] = s[i];
-    return 1u + len;
-}
-__device__ __forceinline__ uint32_t rlp_short_len(const uint8_t* s, uint32_t len) { return (len == 1u && s[0] < 0x80u) ? 1u : 1u + len; }
+// length of rlp(the integer in the 32 bytes at v), whose minimal form has vl bytes
+__device__ __forceinline__ uint32_t rlp_be32_len(const uint8_t* v, uint32_t vl) { return (uint32_t)str_len(vl, vl == 1u ? v[31] : 0u); }
 
 // live[s] = 1 iff slot s holds a non-zero value (statedb.zig:112-119: zero = absent); live[m] = 0 (the scan's total lands there)
 __global__ void __launch_bounds__(256) slot_live_kernel(const uint8_t* __restrict__ slot_vals, uint32_t m, uint32_t* __restrict__ live) {
@@ -115,7 +108,7 @@ __global__ void __launch_bounds__(256) slot_leaf_len_kernel(const uint32_t* __re
     if (j < L) {
         const uint8_t* v = slot_vals + 32ull * live_src[order[j]];
         const uint32_t vl = be_len32(v);
-        l = rlp_short_len(v + (32u - vl), vl);
+        l = rlp_be32_len(v, vl);
     }
     len[j] = l;
 }
@@ -137,17 +130,7 @@ __global__ void __launch_bounds__(256) slot_leaf_write_kernel(const uint32_t* __
     o[1] = k[1];
     const uint8_t* v = slot_vals + 32ull * live_src[src];
     const uint32_t vl = be_len32(v);
-    put_rlp_short(svals + off[j], v + (32u - vl), vl);
-}
-
-// minimal big-endian bytes of a u64 (0 bytes for zero) into b[8]; returns the count
-__device__ __forceinline__ uint32_t be_u64(uint64_t x, uint8_t (&b)[8]) {
-    uint32_t n = 0;
-    for (int sh = 56; sh >= 0; sh -= 8) {
-        const uint8_t t = (uint8_t)(x >> sh);
-        if (n || t) b[n++] = t;
-    }
-    return n;
+    (void)put_str(svals + off[j], v + (32u - vl), vl);
 }
 
 // account leaf i (key order): length of rlp([nonce, balance, storageRoot, codeHash]); len[n] = 0
@@ -158,12 +141,9 @@ __global__ void __launch_bounds__(256) account_len_kernel(const uint32_t* __rest
     uint32_t l = 0;
     if (i < n) {
         const uint32_t a = order[i];
-        uint8_t nb[8];
-        const uint32_t nl = be_u64(nonces[a], nb);
         const uint8_t* bv = balances + 32ull * a;
-        const uint32_t bl = be_len32(bv);
-        const uint32_t payload = rlp_short_len(nb, nl) + rlp_short_len(bv + (32u - bl), bl) + 33u + 33u;
-        l = payload <= 55u ? 1u + payload : 2u + payload;  // (<= 108 bytes: at most one length byte)
+        const uint32_t payload = uint_len(nonces[a]) + rlp_be32_len(bv, be_len32(bv)) + 33u + 33u;
+        l = hdr_len(payload) + payload;
     }
     len[i] = l;
 }
@@ -184,22 +164,15 @@ __global__ void __launch_bounds__(256) account_write_kernel(const uint32_t* __re
     uint4* ko = reinterpret_cast<uint4*>(akeys + 32ull * i);
     ko[0] = k[0];
     ko[1] = k[1];
-    uint8_t nb[8];
-    const uint32_t nl = be_u64(nonces[a], nb);
     const uint8_t* bv = balances + 32ull * a;
     const uint32_t bl = be_len32(bv);
-    const uint32_t payload = rlp_short_len(nb, nl) + rlp_short_len(bv + (32u - bl), bl) + 33u + 33u;
+    const uint32_t payload = uint_len(nonces[a]) + rlp_be32_len(bv, bl) + 33u + 33u;
     uint8_t* o = avals + off[i];
-    if (payload <= 55u) {
-        *o++ = (uint8_t)(0xc0u + payload);
-    } else {
-        *o++ = 0xf8;
-        *o++ = (uint8_t)payload;
-    }
-    o += put_rlp_short(o, nb, nl);
-    o += put_rlp_short(o, bv + (32u - bl), bl);
-    o += put_rlp_short(o, sroots + 32ull * a, 32u);
-    put_rlp_short(o, hc + 32ull * a, 32u);
+    o += put_hdr(o, 0xc0u, payload);
+    o += put_uint(o, nonces[a]);
+    o += put_str(o, bv + (32u - bl), bl);
+    o += put_str(o, sroots + 32ull * a, 32u);
+    (void)put_str(o, hc + 32ull * a, 32u);
 }
 
 // ------------------------------------------------------------------ host side

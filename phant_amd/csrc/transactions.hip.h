@@ -29,6 +29,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rlp.h"
+
 #ifdef PHANT_TX_DECODE_ONLY
 #define TX_HD inline
 #else
@@ -76,31 +78,11 @@ struct Decoded {
     uint8_t prefix[12], suffix[12];  // 10 and 11 bytes used
 };
 
-// One canonical RLP item at p[pos ..) with everything up to `end` left: its payload [pay, pend), which ends the item.  Every length is
-// compared with what is left BEFORE it is added to a position (a declared length can be 2^64 - 1).  The strictness is
-// host_rlp.cpp::host_rlp_item's.
+// One canonical RLP item (rlp.h's decoder) at p[pos ..) with everything up to `end` left: its payload [pay, pend), which ends the item.
 TX_HD bool rlp_item(const uint8_t* p, uint32_t pos, uint32_t end, uint32_t& pay, uint32_t& pend, bool& is_list) {
-    if (pos >= end) return false;
-    const uint32_t avail = end - pos, b = p[pos];
-    if (b < 0x80u) {
-        pay = pos, pend = pos + 1u, is_list = false;
-        return true;
-    }
-    if (b <= 0xb7u || (b >= 0xc0u && b <= 0xf7u)) {
-        is_list = b >= 0xc0u;
-        const uint32_t len = b - (is_list ? 0xc0u : 0x80u);
-        if (len > avail - 1u) return false;
-        if (!is_list && len == 1u && p[pos + 1u] < 0x80u) return false;
-        pay = pos + 1u, pend = pay + len;
-        return true;
-    }
-    is_list = b >= 0xf8u;
-    const uint32_t ll = b - (is_list ? 0xf7u : 0xb7u);  // 1 .. 8
-    if (ll > avail - 1u || p[pos + 1u] == 0u) return false;
-    uint64_t l = 0;
-    for (uint32_t k = 0; k < ll; ++k) l = l << 8 | p[pos + 1u + k];
-    if (l <= 55u || l > (uint64_t)(avail - 1u - ll)) return false;
-    pay = pos + 1u + ll, pend = pay + (uint32_t)l;
+    RlpItem it;
+    if (pos >= end || !rlp_decode(MemBytes{p}, pos, end - pos, it)) return false;
+    pay = it.pay, pend = it.pay + it.len, is_list = it.is_list != 0u;
     return true;
 }
 
@@ -180,16 +162,6 @@ TX_HD bool auth_list(const uint8_t* p, uint32_t pay, uint32_t pend, uint32_t& tu
         if (!auth_tuple(p, pos, pend, a, pos)) return false;
     }
     return true;
-}
-
-// a list header for `len` payload bytes -> bytes written (at most 9)
-TX_HD uint32_t put_list_header(uint8_t* o, uint64_t len) {
-    if (len <= 55u) return o[0] = (uint8_t)(0xc0u + len), 1u;
-    uint32_t ll = 0;
-    for (uint64_t l = len; l; l >>= 8) ++ll;
-    o[0] = (uint8_t)(0xf7u + ll);
-    for (uint32_t q = 0; q < ll; ++q) o[1u + q] = (uint8_t)(len >> (8u * (ll - 1u - q)));
-    return 1u + ll;
 }
 
 // The item kinds of a transaction in the order of a type-2 list; type 1 has no PRIORITY, type 0 neither CHAIN_ID nor ACCESS_LIST.
@@ -331,20 +303,13 @@ TX_HD void decode(const uint8_t* p, uint32_t len, uint64_t chain_id, uint32_t fo
     // the signed list: the items in front of v, verbatim, (chain_id, 0, 0 for EIP-155,) under a header of their own
     d.body_begin = pay, d.body_end = v_full;
     if (d.eip155) {
-        uint32_t ll = 0;
-        for (uint64_t c = chain_id; c; c >>= 8) ++ll;
-        uint32_t t = 0;
-        if (ll == 1u && chain_id < 0x80u) d.suffix[t++] = (uint8_t)chain_id;
-        else {
-            d.suffix[t++] = (uint8_t)(0x80u + ll);
-            for (uint32_t q = 0; q < ll; ++q) d.suffix[t++] = (uint8_t)(chain_id >> (8u * (ll - 1u - q)));
-        }
+        uint32_t t = put_uint(d.suffix, chain_id);
         d.suffix[t++] = 0x80u, d.suffix[t++] = 0x80u;
         d.suffix_len = (uint8_t)t;
     }
     uint32_t h = 0;
     if (d.type) d.prefix[h++] = d.type;
-    h += put_list_header(d.prefix + h, (uint64_t)(d.body_end - d.body_begin) + d.suffix_len);
+    h += put_hdr(d.prefix + h, 0xc0u, (uint64_t)(d.body_end - d.body_begin) + d.suffix_len);
     d.prefix_len = (uint8_t)h;
 }
 // types 0 - 2 only: what phant_block_transactions decodes
@@ -629,6 +594,8 @@ struct AuthMessage {
     uint32_t cl, nl;           // the significant bytes of chain_id and of nonce
     uint32_t ce, ne, hl, pay;  // the bytes of their encodings, of the list header, of the list's payload
 };
+// Byte j of that message.  The encoding is never written anywhere, so rlp.h's writers do not apply: this states the layout a second
+// time, for the lengths rlp.h has computed (tx_auth_hash_kernel), and stays here.
 PHANT_DEV uint32_t auth_message_byte(const AuthMessage& m, uint32_t j) {
     if (j == 0u) return 0x05u;
     if (j <= m.hl) return m.hl == 1u ? 0xc0u + m.pay : j == 1u ? 0xf8u : m.pay;
@@ -651,15 +618,12 @@ __global__ void __launch_bounds__(64) tx_auth_hash_kernel(AuthDev ad, uint32_t n
     if (j >= n_auth) return;
     AuthMessage m;
     m.chain_id = ad.x.auth_chain_id + 32ull * j, m.address = ad.x.auth_address + 20ull * j, m.nonce = ad.x.auth_nonce[j];
-    m.cl = 0u;
-    for (uint32_t k = 0; k < 32u; ++k)
-        if (m.cl == 0u && m.chain_id[k] != 0u) m.cl = 32u - k;
-    m.nl = 0u;
-    for (uint64_t v = m.nonce; v; v >>= 8) ++m.nl;
-    m.ce = m.cl == 0u || (m.cl == 1u && m.chain_id[31] < 0x80u) ? 1u : 1u + m.cl;
-    m.ne = m.nl == 0u || (m.nl == 1u && m.nonce < 0x80u) ? 1u : 1u + m.nl;
+    m.cl = be_bytes(m.chain_id, 32u);
+    m.nl = uint_bytes(m.nonce);
+    m.ce = (uint32_t)str_len(m.cl, m.chain_id[31]);
+    m.ne = uint_len(m.nonce);
     m.pay = m.ce + 21u + m.ne;
-    m.hl = m.pay <= 55u ? 1u : 2u;  // (above 55 only with a chain id of 24 bytes or more)
+    m.hl = hdr_len(m.pay);  // (two bytes only with a chain id of 24 bytes or more)
     const uint32_t total = 1u + m.hl + m.pay;
     uint32_t d[RATE_DWORDS];
 #pragma unroll

@@ -35,6 +35,7 @@
 #include "absorb.hip.h"
 #include "coop_sponge.hip.h"
 #include "launch.h"
+#include "rlp.h"
 
 namespace phant {
 namespace {
@@ -513,36 +514,10 @@ __global__ void __launch_bounds__(COUNT_BLOCK) order_kernel(TrieDev t) {
     }
 }
 
-// ---- RLP helpers (row a10: canonical subset used at mpt.zig:127,198,236,268) ----
-PHANT_DEV uint32_t be_len_bytes(uint64_t v) {
-    uint32_t n = 0;
-    while (v) {
-        ++n;
-        v >>= 8;
-    }
-    return n;
-}
-// encoded size of a byte string of `len` bytes whose first byte is b0
-PHANT_DEV uint64_t rlp_str_size(uint64_t len, uint32_t b0) {
-    if (len == 1 && b0 < 0x80u) return 1;
-    if (len <= 55) return 1 + len;
-    return 1 + be_len_bytes(len) + len;
-}
-PHANT_DEV uint32_t rlp_list_hdr_size(uint64_t payload) {
-    return payload <= 55 ? 1u : 1u + be_len_bytes(payload);
-}
-PHANT_DEV uint8_t* put_hdr(uint8_t* w, uint64_t len, uint32_t short_base, uint32_t long_base) {
-    if (len <= 55) {
-        *w++ = (uint8_t)(short_base + len);
-        return w;
-    }
-    const uint32_t ll = be_len_bytes(len);
-    *w++ = (uint8_t)(long_base + ll);
-    for (int s = 8 * ((int)ll - 1); s >= 0; s -= 8) *w++ = (uint8_t)(len >> s);
-    return w;
-}
-PHANT_DEV uint8_t* put_str(uint8_t* w, const uint8_t* s, uint64_t len) {
-    if (!(len == 1 && s[0] < 0x80u)) w = put_hdr(w, len, 0x80u, 0xb7u);
+// ---- RLP (row a10: canonical subset used at mpt.zig:127,198,236,268): the rules are rlp.h's.  What stays here is put_str_wide's
+// payload copy, which is a tuned copy (dword loads, eight in flight) and no rule of RLP; its header is rlp.h's put_hdr_to.
+PHANT_DEV uint8_t* put_str_wide(uint8_t* w, const uint8_t* s, uint64_t len) {
+    if (!(len == 1 && s[0] < 0x80u)) w = put_hdr_to(w, 0x80u, len);
     // the payload: byte by byte up to a 4-byte boundary of the source, then a dword per load (a transaction or a receipt is
     // hundreds of bytes: one load instruction per byte was most of the leaf kernel for such items), never beyond s + len
     uint64_t k = 0;
@@ -611,7 +586,7 @@ PHANT_DEV uint32_t trie_of(const TrieDev& t, uint32_t key) {
 // hex-prefix of nibbles [ps, pe) of key k (mpt.zig:285-314), as an RLP string
 PHANT_DEV uint64_t hp_rlp_size(uint32_t plen) {
     const uint32_t hp = plen / 2u + 1u;
-    return hp == 1 ? 1 : rlp_str_size(hp, 0xffu);  // a 1-byte HP is 0x00..0x3f: encodes as itself
+    return hp == 1 ? 1 : str_len(hp, 0xffu);  // a 1-byte HP is 0x00..0x3f: encodes as itself
 }
 PHANT_DEV uint8_t* put_hp(uint8_t* w, const TrieDev& t, uint32_t k, uint32_t ps, uint32_t pe,
                           bool is_leaf) {
@@ -619,7 +594,7 @@ PHANT_DEV uint8_t* put_hp(uint8_t* w, const TrieDev& t, uint32_t k, uint32_t ps,
     const uint32_t hp = plen / 2u + 1u;
     const bool odd = plen & 1u;
     const uint32_t b0 = ((is_leaf ? 2u : 0u) + (odd ? 1u : 0u)) << 4 | (odd ? nib_at(t, k, ps) : 0u);
-    if (hp > 1) w = put_hdr(w, hp, 0x80u, 0xb7u);
+    if (hp > 1) w = put_hdr_to(w, 0x80u, hp);
     *w++ = (uint8_t)b0;
     // nibbles [s, pe), an even number, two per byte.  The key bytes are loaded eight (nine) at a time BEFORE any is stored: one
     // load per nibble, each waited for in turn, was 10-15 us of a leaf's latency (57 nibbles of a 32-byte key).
@@ -728,8 +703,8 @@ PHANT_DEV LeafPlan leaf_plan(const TrieDev& t, const uint32_t i) {
         p.nl = nib_len(t, i);
         p.v = t.vals + t.val_off[i];
         p.vlen = t.val_off[i + 1] - t.val_off[i];
-        p.payload = hp_rlp_size(p.nl - p.ps) + rlp_str_size(p.vlen, p.vlen ? p.v[0] : 0u);
-        p.total = (uint32_t)(rlp_list_hdr_size(p.payload) + p.payload);
+        p.payload = hp_rlp_size(p.nl - p.ps) + str_len(p.vlen, p.vlen ? p.v[0] : 0u);
+        p.total = (uint32_t)(hdr_len(p.payload) + p.payload);
     }
     return p;
 }
@@ -742,9 +717,9 @@ PHANT_DEV void leaf_emit_staged(const TrieDev& t, const uint32_t i, const LeafPl
     Sponge s;
     stage_clear<STAGE_DW>(slot);
     uint8_t* enc = reinterpret_cast<uint8_t*>(slot);
-    uint8_t* w = put_hdr(enc, p.payload, 0xc0u, 0xf7u);
+    uint8_t* w = put_hdr_to(enc, 0xc0u, p.payload);
     w = put_hp(w, t, i, p.ps, p.nl, true);
-    w = put_str(w, p.v, p.vlen);
+    w = put_str_wide(w, p.v, p.vlen);
     if (hashed) keccak256_staged(s, slot, p.total);
     deliver(t, parent, p.ps ? nib_at(t, i, p.ps - 1) : 0u, i, enc, p.total, s, hashed);
 }
@@ -758,9 +733,9 @@ PHANT_DEV void leaf_emit_scratch(const TrieDev& t, const uint32_t i, const LeafP
     const bool hashed = p.total >= 32u || parent == NONE;
     Sponge s;
     uint8_t* enc = t.scratch + at;
-    uint8_t* w = put_hdr(enc, p.payload, 0xc0u, 0xf7u);
+    uint8_t* w = put_hdr_to(enc, 0xc0u, p.payload);
     w = put_hp(w, t, i, p.ps, p.nl, true);
-    w = put_str(w, p.v, p.vlen);
+    w = put_str_wide(w, p.v, p.vlen);
     if (hashed) keccak256_global(s, enc, p.total);
     deliver(t, parent, p.ps ? nib_at(t, i, p.ps - 1) : 0u, i, enc, p.total, s, hashed);
 }
@@ -802,7 +777,7 @@ __global__ void __launch_bounds__(256) leaf_kernel(TrieDev t, const uint32_t* li
 // it when the parent is more than one nibble up (mpt.zig:83-106, :187-193).
 // Writes the 17-item list into `enc` (LDS slot or scratch blob: the caller's pointer decides what the stores are).
 PHANT_DEV uint8_t* put_branch(uint8_t* enc, const TrieDev& t, uint32_t dn, uint64_t payload, const uint8_t* v, uint64_t vlen) {
-    uint8_t* w = put_hdr(enc, payload, 0xc0u, 0xf7u);
+    uint8_t* w = put_hdr_to(enc, 0xc0u, payload);
     // the 16 slot lengths: one aligned 16-byte load; the slots' bytes four children at a time, all eight 16-byte loads issued
     // before the first byte is stored (the table has all 32 bytes of every slot, whatever its length says is used): sixteen
     // load-wait-store rounds were 15-25 us of EVERY branch node's latency, which is what a depth bin with few nodes costs
@@ -839,7 +814,7 @@ PHANT_DEV uint8_t* put_branch(uint8_t* enc, const TrieDev& t, uint32_t dn, uint6
         }
     }
     if (vlen)
-        w = put_str(w, v, vlen);
+        w = put_str_wide(w, v, vlen);
     else
         *w++ = 0x80;
     return w;
@@ -850,7 +825,7 @@ PHANT_DEV uint32_t put_extension(uint8_t* xenc, const TrieDev& t, uint32_t l, ui
                                  const Sponge& s, const uint8_t* inner, uint32_t total) {
     const uint32_t ref_size = inner_hashed ? 33u : total;
     const uint64_t xpayload = hp_rlp_size(pe - ps) + ref_size;
-    uint8_t* x = put_hdr(xenc, xpayload, 0xc0u, 0xf7u);
+    uint8_t* x = put_hdr_to(xenc, 0xc0u, xpayload);
     x = put_hp(x, t, l, ps, pe, false);
     if (inner_hashed) {
         *x++ = 0xa0;
@@ -908,8 +883,8 @@ PHANT_DEV BranchPlan branch_plan_node(const TrieDev& t, const uint32_t node, con
             p.v = t.vals + t.val_off[vk];
             p.vlen = t.val_off[vk + 1] - t.val_off[vk];
         }
-        p.payload += rlp_str_size(p.vlen, p.vlen ? p.v[0] : 0u);
-        p.total = (uint32_t)(rlp_list_hdr_size(p.payload) + p.payload);
+        p.payload += str_len(p.vlen, p.vlen ? p.v[0] : 0u);
+        p.total = (uint32_t)(hdr_len(p.payload) + p.payload);
     }
     p.d = live ? t.lcp[p.i] : 0;
     p.pd = live ? t.nd_pd[p.i] : 0;
@@ -1202,7 +1177,7 @@ __global__ void __launch_bounds__(256) branch_coop_kernel(TrieDev t, uint32_t be
     }
     const uint32_t children = __shfl(incl, (int)(base + 15u), 64);
     const uint32_t payload = children + 1u;  // (+ the empty value slot)
-    const uint32_t hdr = rlp_list_hdr_size(payload), total = hdr + payload;
+    const uint32_t hdr = hdr_len(payload), total = hdr + payload;
     // A value in the branch, a root whose bytes the caller wants, an extension over a branch too short to be hashed, an extension
     // longer than the buffer: the general way, on the half wave's first lane -- for BOTH halves of the wave (a wave that takes both
     // ways takes them one after the other).
@@ -1215,7 +1190,7 @@ __global__ void __launch_bounds__(256) branch_coop_kernel(TrieDev t, uint32_t be
         return;
     }
     if (live && l == 16u) {
-        (void)put_hdr(b, payload, 0xc0u, 0xf7u);
+        (void)put_hdr_to(b, 0xc0u, payload);
         b[hdr + children] = 0x80;
     }
     if (live && l < 16u) {
@@ -1324,7 +1299,7 @@ PHANT_DEV void branch_wave_node(const TrieDev& t, const uint32_t node, const int
     }
     const uint32_t children = __shfl(incl, 15, 64);
     const uint32_t payload = children + 1u;  // (+ the empty value slot)
-    const uint32_t hdr = rlp_list_hdr_size(payload), total = hdr + payload;
+    const uint32_t hdr = hdr_len(payload), total = hdr + payload;
     // A value in the branch, a root whose bytes the caller wants, an extension over a branch too short to be hashed, an extension
     // longer than the buffer: the general way, on the wave's first lane.
     const bool plain = vk == NONE && !(is_root && t.root_enc) && (ext_len == 0u || (total >= 32u && 44u + ext_len / 2u < BRANCH_STAGE_BYTES));
@@ -1336,7 +1311,7 @@ PHANT_DEV void branch_wave_node(const TrieDev& t, const uint32_t node, const int
         return;
     }
     if (l == 16u) {
-        (void)put_hdr(b, payload, 0xc0u, 0xf7u);
+        (void)put_hdr_to(b, 0xc0u, payload);
         b[hdr + children] = 0x80;
     }
     if (l < 16u) {
@@ -1459,9 +1434,9 @@ PHANT_DEV void leaf_wave_node(const TrieDev& t, const uint32_t i, uint32_t* cons
     uint8_t* const b = reinterpret_cast<uint8_t*>(buf);
     const uint32_t total = p.total, off = total - (uint32_t)p.vlen;  // (what stands in front of the value's bytes)
     if (l == 0) {
-        uint8_t* w = put_hdr(pre, p.payload, 0xc0u, 0xf7u);
+        uint8_t* w = put_hdr_to(pre, 0xc0u, p.payload);
         w = put_hp(w, t, i, p.ps, p.nl, true);
-        if (!(p.vlen == 1 && p.v[0] < 0x80u)) (void)put_hdr(w, p.vlen, 0x80u, 0xb7u);
+        if (!(p.vlen == 1 && p.v[0] < 0x80u)) (void)put_hdr_to(w, 0x80u, p.vlen);
     }
     const uint32_t tr = is_root ? trie_of(t, i) : 0u;
     const bool want_enc = is_root && t.root_enc;

@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(256) prove_sibling_kernel(TrieDev t, ProveDev 
 // the length of the extension over branch plan b (put_extension's arithmetic)
 PHANT_DEV uint32_t pv_ext_size(const BranchPlan& b, bool inner_hashed) {
     const uint64_t xpayload = hp_rlp_size(b.ext_len) + (inner_hashed ? 33u : b.total);
-    return (uint32_t)(rlp_list_hdr_size(xpayload) + xpayload);
+    return (uint32_t)(hdr_len(xpayload) + xpayload);
 }
 // which nodes of index i are members, and their lengths
 PHANT_DEV uint32_t pv_members(const TrieDev& t, const ProveDev& p, uint32_t i, uint32_t& xlen, uint32_t& blen, unsigned long long& llen) {
@@ -219,7 +219,7 @@ PHANT_DEV uint32_t pv_members(const TrieDev& t, const ProveDev& p, uint32_t i, u
         const LeafPlan lp = leaf_plan(t, i);
         if (lp.live && (lp.total >= 32u || t.leaf_parent[i] == NONE)) {
             mem |= PV_M_LEAF;
-            llen = rlp_list_hdr_size(lp.payload) + lp.payload;
+            llen = hdr_len(lp.payload) + lp.payload;
         }
     }
     return mem;
@@ -359,9 +359,9 @@ __global__ void __launch_bounds__(64) prove_emit_kernel(TrieDev t, ProveDev p) {
         const LeafPlan lp = leaf_plan(t, i);
         if (p.node_off) p.node_off[j] = at;
         if (p.nodes) {
-            uint8_t* w = put_hdr(p.nodes + at, lp.payload, 0xc0u, 0xf7u);
+            uint8_t* w = put_hdr_to(p.nodes + at, 0xc0u, lp.payload);
             w = put_hp(w, t, i, lp.ps, lp.nl, true);
-            (void)put_str(w, lp.v, lp.vlen);
+            (void)put_str_wide(w, lp.v, lp.vlen);
         }
     }
 }
