@@ -149,6 +149,12 @@ struct Workspaces {
             for (size_t i = 0; i < MAILBOX_WORDS; ++i) mailbox[i] = 0u;
         return e;
     }
+    // A call's control words into its part of the mailbox (`at`: one of the MAILBOX_* offsets above): one copy and a stream
+    // synchronisation, behind which mailbox[at ..] holds them.
+    hipError_t read_words(size_t at, const uint32_t* d_words, size_t words, hipStream_t st) {
+        const hipError_t e = hipMemcpyAsync(mailbox + at, d_words, 4 * words, hipMemcpyDeviceToHost, st);
+        return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    }
     // a helper stream + events for the trie builder's deepest bins, which run next to the bulk of the leaves
     hipStream_t side = nullptr;
     hipEvent_t side_fork = nullptr, side_join = nullptr;

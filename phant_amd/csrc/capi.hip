@@ -18,6 +18,7 @@
 #include "../../include/phant_gpu.h"
 #include "../../include/phant_gpu_diag.h"
 #include "arena.h"
+#include "staging.h"
 #include "launch.h"
 #include "receipts.h"
 #include "headers.h"
@@ -115,19 +116,14 @@ int32_t fail(phant_ctx* c, int32_t code, const char* what, hipError_t e = hipSuc
         if (e_ != hipSuccess) return fail((c), PHANT_E_DEVICE, #call, e_); \
     } while (0)
 
-// Lay out a call's staging arrays in `io` (drops its previous contents).  `lay(arena)` makes the call's take<T>() calls: it runs
-// once against a counter, which sizes the arena (stream `s` synchronised before it grows: a kernel may still read the old
-// one), then against the arena itself.  Afterwards io.used is the counted total.
+// Lay out a call's staging arrays in `io` (staging.h: phant::lay_out_arena; afterwards io.used is the counted total), a failure as this
+// file reports one.
 template <class Lay>
 int32_t lay_out(phant_ctx* c, hipStream_t s, phant::DevArena& io, const Lay& lay) {
-    phant::ArenaSizer size;
-    lay(size);
-    if (size.bytes > io.cap) HIP_TRY(c, hipStreamSynchronize(s));
-    hipError_t e = io.reset(size.bytes);
-    if (e != hipSuccess) return fail(c, PHANT_E_OOM, "hipMalloc(workspace)", e);
-    lay(io);
-    if (io.overflowed) return fail(c, PHANT_E_DEVICE, "staging arena undersized");
-    return PHANT_OK;
+    const phant::LaidOut r = phant::lay_out_arena(io, s, lay);
+    if (r.what == phant::LaidOut::SYNC_FAILED) return fail(c, PHANT_E_DEVICE, "hipStreamSynchronize(s)", r.e);
+    if (r.what == phant::LaidOut::OOM) return fail(c, PHANT_E_OOM, "hipMalloc(workspace)", r.e);
+    return r.what == phant::LaidOut::UNDERSIZED ? fail(c, PHANT_E_DEVICE, "staging arena undersized") : PHANT_OK;
 }
 
 struct TimedRegion {

@@ -28,6 +28,7 @@
 #include "headers.h"
 #include "launch.h"
 #include "rlp.h"
+#include "staging.h"
 #include "trie_build.h"
 #include "wave_util.hip.h"
 
@@ -384,15 +385,10 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
     using namespace hd;
     const uint32_t n = hin.n, nulls = null_mask(hin);
     const bool small = n < SMALL_MAX;  // (n + 1 offsets, eight a lane)
-    const bool want_enc = out.enc || out.enc_off;
     const uint32_t grid = blocks_of((uint64_t)n, 256);
     HD_TRY(ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_HEADERS_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_HEADERS;
-    auto read_ctl = [&](const uint32_t* d_ctl) -> hipError_t {
-        hipError_t e = hipMemcpyAsync(const_cast<uint32_t*>(mb), d_ctl, 4 * CTL_WORDS, hipMemcpyDeviceToHost, st);
-        return e == hipSuccess ? hipStreamSynchronize(st) : e;
-    };
 
     // ---- the arguments: the host form checks before anything is copied, the device form on the device -- and reads the verdict
     // before any kernel indexes with the caller's offsets.  Either way the extra data's bytes are known afterwards.
@@ -405,17 +401,12 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
     } else {
         // (the control words alone, in the trie builder's first arena, which this call does not use otherwise: the call's own
         // arena is sized from what this launch reports)
-        ArenaSizer size;
-        (void)size.take<uint32_t>(CTL_WORDS);
-        if (size.bytes > ws.t1.cap) HD_TRY(hipStreamSynchronize(st));
-        const hipError_t e = ws.t1.reset(size.bytes);
-        if (e != hipSuccess) return err = std::string("header_chain_dev: hipMalloc(workspace): ") + hipGetErrorString(e), PHANT_E_OOM;
-        d_ctl = ws.t1.take<uint32_t>(CTL_WORDS);
-        if (!d_ctl) return err = "header_chain_dev: arena sized too small (internal)", PHANT_E_DEVICE;
+        auto carve_ctl = [&](auto& t1) { d_ctl = t1.template take<uint32_t>(CTL_WORDS); };
+        if (const int32_t rc = lay_out_status(lay_out_arena(ws.t1, st, carve_ctl), "header_chain_dev", "workspace", err)) return rc;
         HD_TRY(hipMemsetAsync(d_ctl, 0, 4 * CTL_WORDS, st));
         hipLaunchKernelGGL(hdr_check_args_kernel, dim3(grid), dim3(256), 0, st, hin, nulls, d_ctl);
         HD_TRY(hipGetLastError());
-        HD_TRY(read_ctl(d_ctl));
+        HD_TRY(ws.read_words(Workspaces::MAILBOX_HEADERS, d_ctl, CTL_WORDS, st));
         if (mb[0] & F_INVALID)
             return err = "header_chain_dev: an n_fields outside 15, 16, 17, 19, 20, 21, a NULL array that a header needs, extra_off not running up from 0, "
                          "or seg_first not increasing from 0 to n",
@@ -450,35 +441,18 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
             d_scan = io.template take<uint32_t>(scan_scratch_entries(n + 1u) + 4);
         }
     };
-    {
-        ArenaSizer size;
-        carve(size);
-        if (size.bytes > ws.io.cap) HD_TRY(hipStreamSynchronize(st));  // (a kernel may still read the arena that is about to go)
-        const hipError_t e = ws.io.reset(size.bytes);
-        if (e != hipSuccess) return err = std::string("header_chain: hipMalloc(workspace): ") + hipGetErrorString(e), PHANT_E_OOM;
-        carve(ws.io);
-        if (ws.io.overflowed) return err = "header_chain: arena sized too small (internal)", PHANT_E_DEVICE;
-    }
+    if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "header_chain", "workspace", err)) return rc;
 
     // ---- in
     if (!dev) {
-        const size_t in_span = (size_t)(reinterpret_cast<const uint8_t*>(d_ctl) - ws.io.base);
-        const bool staged = !PHANT_ARENA_POISONS && in_span <= Workspaces::STAGE_BYTES;
-        if (staged) HD_TRY(ws.ensure_stage());
-        hipError_t ce = hipSuccess;
-        auto put = [&](const void* dst, const void* src, size_t bytes) {
-            if (!bytes || !src || ce != hipSuccess) return;
-            if (staged) std::memcpy(ws.staged(const_cast<uint8_t*>(static_cast<const uint8_t*>(dst))), src, bytes);
-            else ce = hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, st);
-        };
-#define X(m, T, k) put(d.m, hin.m, (size_t)n * k * sizeof(T));
+        StagedInputs ins(ws, st, ws.io.base, d_ctl);
+#define X(m, T, k) ins.put(d.m, hin.m, (size_t)n * k * sizeof(T));
         HD_ARRAYS(X)
 #undef X
-        put(d.extra_data, hin.extra_data, (size_t)extra_bytes);
-        put(d.extra_off, hin.extra_off, 4 * ((size_t)n + 1));
-        if (hin.seg_first) put(d.seg_first, hin.seg_first, 4 * ((size_t)hin.n_segs + 1));
-        HD_TRY(ce);
-        if (staged) HD_TRY(hipMemcpyAsync(ws.io.base, ws.stage, in_span, hipMemcpyHostToDevice, st));
+        ins.put(d.extra_data, hin.extra_data, (size_t)extra_bytes);
+        ins.put(d.extra_off, hin.extra_off, 4 * ((size_t)n + 1));
+        ins.put(d.seg_first, hin.seg_first, 4 * ((size_t)hin.n_segs + 1));
+        HD_TRY(ins.finish());
         HD_TRY(hipMemsetAsync(d_ctl, 0, 4 * CTL_WORDS, st));
     }
 
@@ -496,49 +470,22 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
     hipLaunchKernelGGL(hdr_check_kernel, dim3(grid), dim3(256), 0, st, d, d_hashes, d_enc_off, d_flags, d_ctl);
     HD_TRY(hipGetLastError());
 
-    // ---- out
-    if (dev) {
-        HD_TRY(read_ctl(d_ctl));
-        const uint64_t total = (uint64_t)mb[2] | ((uint64_t)mb[3] << 32);
-        out.first_bad = n - mb[1];
-        out.enc_len = total;
-        const bool fits = !out.enc || total <= out.enc_cap;  // (a buffer nobody wants has no capacity to exceed)
-        if (out.hashes) HD_TRY(hipMemcpyAsync(out.hashes, d_hashes, 32 * (size_t)n, hipMemcpyDeviceToDevice, st));
-        if (out.flags) HD_TRY(hipMemcpyAsync(out.flags, d_flags, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
-        if (fits && out.enc && total) HD_TRY(hipMemcpyAsync(out.enc, d_enc, (size_t)total, hipMemcpyDeviceToDevice, st));
-        if (fits && out.enc_off) HD_TRY(hipMemcpyAsync(out.enc_off, d_enc_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToDevice, st));
-        return PHANT_OK;
-    }
-    // host form: control words, digests, flags and offsets cross the bus as ONE copy into the pinned stage when they fit there (a
-    // copy into pageable memory is ~25 us a piece); the encodings, whose size only the control words tell, follow when wanted
-    const uint8_t *h_ctl = reinterpret_cast<const uint8_t*>(d_ctl), *h_hashes = d_hashes, *h_flags = reinterpret_cast<const uint8_t*>(d_flags),
-                  *h_enc_off = reinterpret_cast<const uint8_t*>(d_enc_off);
-    const uint8_t* const head_end = reinterpret_cast<const uint8_t*>(d_enc_off + n + 1);
-    const bool staged_out = !PHANT_ARENA_POISONS && (size_t)(head_end - ws.io.base) <= Workspaces::STAGE_BYTES;
-    uint32_t ctl_host[CTL_WORDS] = {0};
-    if (staged_out) {
-        HD_TRY(ws.ensure_stage());
-        HD_TRY(hipMemcpyAsync(ws.staged(d_ctl), d_ctl, (size_t)(head_end - h_ctl), hipMemcpyDeviceToHost, st));
-        HD_TRY(hipStreamSynchronize(st));
-        h_ctl = ws.staged(h_ctl), h_hashes = ws.staged(h_hashes), h_flags = ws.staged(h_flags), h_enc_off = ws.staged(h_enc_off);
-        std::memcpy(ctl_host, h_ctl, sizeof ctl_host);
-    } else {
-        HD_TRY(read_ctl(d_ctl));
-        for (size_t k = 0; k < CTL_WORDS; ++k) ctl_host[k] = mb[k];
-    }
-    const uint64_t total = (uint64_t)ctl_host[2] | ((uint64_t)ctl_host[3] << 32);
+    // ---- out: the control words, digests, flags and offsets lie next to each other (one span in the host form while it fits the pinned
+    // stage); the control words first, since only they tell the encodings' size, which follow by a copy of their own when wanted
+    CallOutputs outs(ws, st, dev, d_ctl, d_ctl, Workspaces::MAILBOX_HEADERS, CTL_WORDS);
+    outs.cover(d_enc_off + n + 1);
+    HD_TRY(outs.deliver());
+    const uint32_t bad_from_end = outs.ctl()[1];
+    const uint64_t total = (uint64_t)outs.ctl()[2] | ((uint64_t)outs.ctl()[3] << 32);
     const bool fits = !out.enc || total <= out.enc_cap;  // (a buffer nobody wants has no capacity to exceed)
-    auto give = [&](void* dst, const uint8_t* src, size_t bytes) -> hipError_t {
-        if (!dst || !bytes) return hipSuccess;
-        if (staged_out) return std::memcpy(dst, src, bytes), hipSuccess;
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-    };
-    HD_TRY(give(out.hashes, h_hashes, 32 * (size_t)n));
-    HD_TRY(give(out.flags, h_flags, 4 * (size_t)n));
-    if (want_enc && fits) HD_TRY(give(out.enc_off, h_enc_off, 8 * ((size_t)n + 1)));
-    if (out.enc && fits && total) HD_TRY(hipMemcpyAsync(out.enc, d_enc, (size_t)total, hipMemcpyDeviceToHost, st));
-    if (!staged_out || (out.enc && fits && total)) HD_TRY(hipStreamSynchronize(st));
-    out.first_bad = n - ctl_host[1];
+    outs.add(out.hashes, d_hashes, 32 * (size_t)n);
+    outs.add(out.flags, d_flags, 4 * (size_t)n);
+    if (fits) {
+        outs.add(out.enc_off, d_enc_off, 8 * ((size_t)n + 1));
+        outs.add(out.enc, d_enc, (size_t)total);
+    }
+    HD_TRY(outs.deliver());
+    out.first_bad = n - bad_from_end;
     out.enc_len = total;
     return PHANT_OK;
 }

@@ -29,6 +29,7 @@
 #include "launch.h"
 #include "receipts.h"
 #include "rlp.h"
+#include "staging.h"
 #include "trie_build.h"
 #include "wave_util.hip.h"
 
@@ -457,7 +458,6 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
     uint8_t *d_zero = nullptr, *d_keys = nullptr, *d_vals = nullptr, *d_roots = nullptr, *d_enc = nullptr;
     const size_t zero_bytes = 256 * (size_t)n + 256 + 8 * CTL_WORDS + 4 * ((size_t)total + 1);
     const bool want_enc = a.encoded || a.encoded_off;
-    size_t in_span = 0;
     auto carve = [&](auto& io) {
         if (!dev) {
             d.tx_type = io.template take<uint8_t>((size_t)n + 16);
@@ -490,16 +490,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
         d_keys = io.template take<uint8_t>((size_t)key_total + 16);
         d_vals = io.template take<uint8_t>((size_t)val_cap + 16);
     };
-    {
-        ArenaSizer size;
-        carve(size);
-        if (size.bytes > ws.io.cap) RC_TRY(hipStreamSynchronize(st));  // (a kernel may still read the arena that is about to go)
-        const hipError_t e = ws.io.reset(size.bytes);
-        if (e != hipSuccess) return err = std::string("block_receipts: hipMalloc(workspace): ") + hipGetErrorString(e), PHANT_E_OOM;
-        carve(ws.io);
-        if (ws.io.overflowed) return err = "block_receipts: arena sized too small (internal)", PHANT_E_DEVICE;
-        if (!dev) in_span = (size_t)(reinterpret_cast<const uint8_t*>(d_meta + meta.size()) - d.tx_type);
-    }
+    if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_receipts", "workspace", err)) return rc;
     if (dev) {
         d_list.assign(a.lists, a.lists + a.n_lists);
         d_loff.assign(a.list_off, a.list_off + a.n_lists);
@@ -515,34 +506,26 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
     // ---- in
     if (!dev) {
         std::vector<std::vector<uint64_t>> rel(a.n_lists);
-        const bool staged = !PHANT_ARENA_POISONS && in_span <= Workspaces::STAGE_BYTES;
-        if (staged) RC_TRY(ws.ensure_stage());
-        hipError_t ce = hipSuccess;
-        auto put = [&](const void* dst, const void* src, size_t bytes) {
-            if (!bytes || ce != hipSuccess) return;
-            if (staged) std::memcpy(ws.staged(const_cast<uint8_t*>(static_cast<const uint8_t*>(dst))), src, bytes);
-            else ce = hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, st);
-        };
-        put(d.tx_type, a.tx_type, n);
-        put(d.status, a.status, n);
-        put(d.cum_gas, a.cum_gas, 8 * (size_t)n);
-        if (n) put(d.log_first, a.log_first, 4 * ((size_t)n + 1));
-        put(d.address, a.address, 20 * (size_t)nl);
-        if (nl) put(d.topic_first, a.topic_first, 4 * ((size_t)nl + 1));
-        if (nl) put(d.data_off, a.data_off, 8 * ((size_t)nl + 1));
-        put(d.topics, a.topics, 32 * (size_t)nt);
-        put(d.data, a.data, (size_t)a.data_bytes);
+        StagedInputs ins(ws, st, d.tx_type, d_meta + meta.size());
+        ins.put(d.tx_type, a.tx_type, n);
+        ins.put(d.status, a.status, n);
+        ins.put(d.cum_gas, a.cum_gas, 8 * (size_t)n);
+        if (n) ins.put(d.log_first, a.log_first, 4 * ((size_t)n + 1));
+        ins.put(d.address, a.address, 20 * (size_t)nl);
+        if (nl) ins.put(d.topic_first, a.topic_first, 4 * ((size_t)nl + 1));
+        if (nl) ins.put(d.data_off, a.data_off, 8 * ((size_t)nl + 1));
+        ins.put(d.topics, a.topics, 32 * (size_t)nt);
+        ins.put(d.data, a.data, (size_t)a.data_bytes);
         for (uint32_t l = 0; l < a.n_lists; ++l) {
             if (!a.list_n[l]) continue;
             rel[l].resize((size_t)a.list_n[l] + 1);
             for (size_t k = 0; k < rel[l].size(); ++k) rel[l][k] = a.list_off[l][k] - lfirst[l];
-            put(d_list[l], a.lists[l] + lfirst[l], (size_t)lbytes[l]);
-            put(d_loff[l], rel[l].data(), 8 * rel[l].size());
+            ins.put(d_list[l], a.lists[l] + lfirst[l], (size_t)lbytes[l]);
+            ins.put(d_loff[l], rel[l].data(), 8 * rel[l].size());
         }
-        put(d_meta, meta.data(), 4 * meta.size());
-        RC_TRY(ce);
-        if (staged) RC_TRY(hipMemcpyAsync(const_cast<uint8_t*>(d.tx_type), ws.staged(const_cast<uint8_t*>(d.tx_type)), in_span, hipMemcpyHostToDevice, st));
-        else RC_TRY(hipStreamSynchronize(st));  // (`rel` and `meta` may go)
+        ins.put(d_meta, meta.data(), 4 * meta.size());
+        RC_TRY(ins.finish());
+        if (!ins.staged) RC_TRY(hipStreamSynchronize(st));  // (the copies read `rel`, which goes at the end of this block)
     } else {
         RC_TRY(hipMemcpyAsync(d_meta, meta.data(), 4 * meta.size(), hipMemcpyHostToDevice, st));
     }
@@ -551,10 +534,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
     // a small block: one workgroup sizes, scans and keys (the device form still checks its lists first, a launch each)
     const bool small = total < SMALL_PLAN_MAX && a.n_lists <= SMALL_PLAN_LISTS;
     // ---- lengths; the device form reads its verdict before any kernel indexes with the caller's offsets
-    auto read_ctl = [&]() -> hipError_t {
-        hipError_t e = hipMemcpyAsync(const_cast<uint32_t*>(mb), d_ctl, 8 * CTL_WORDS, hipMemcpyDeviceToHost, st);
-        return e == hipSuccess ? hipStreamSynchronize(st) : e;
-    };
+    auto read_ctl = [&]() { return ws.read_words(Workspaces::MAILBOX_RECEIPTS, d_ctl, 2 * CTL_WORDS, st); };
     if (dev && (n || nl)) hipLaunchKernelGGL(rc_check_kernel, dim3(blocks_of((uint64_t)(n > nl ? n : nl) + 1, 256)), dim3(256), 0, st, d, d_ctl);
     for (uint32_t l = 0; l < a.n_lists; ++l) {
         const uint32_t t = l < a.receipts_at ? l : l + 1u;
@@ -621,33 +601,19 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
         else if (oo) RC_TRY(hipMemsetAsync(oo, 0, 8, st));
         RC_TRY(hipGetLastError());
     }
-    const uint8_t *h_roots = d_roots, *h_block = reinterpret_cast<const uint8_t*>(d_block), *h_rows = reinterpret_cast<const uint8_t*>(d_rows),
-                  *h_enc = d_enc, *h_enc_off = reinterpret_cast<const uint8_t*>(d_enc_off);
-    const uint8_t* const out_end = d_enc ? d_enc + rbytes : d_zero + zero_bytes;
-    // host form, a small block: everything that goes back crosses the bus as ONE copy into the pinned stage (a copy into
-    // pageable memory is ~25 us a piece, and there are up to six)
-    const bool staged_out = !dev && !PHANT_ARENA_POISONS && (size_t)(out_end - ws.io.base) <= Workspaces::STAGE_BYTES;
-    if (staged_out) {
-        RC_TRY(ws.ensure_stage());
-        RC_TRY(hipMemcpyAsync(ws.staged(d_roots), d_roots, (size_t)(out_end - d_roots), hipMemcpyDeviceToHost, st));
-        RC_TRY(hipStreamSynchronize(st));
-        h_roots = ws.staged(h_roots), h_block = ws.staged(h_block), h_rows = ws.staged(h_rows);
-        if (d_enc) h_enc = ws.staged(h_enc), h_enc_off = ws.staged(h_enc_off);
-    }
-    auto give = [&](void* dst, const uint8_t* src, size_t bytes) -> hipError_t {
-        if (!dst || !bytes) return hipSuccess;
-        if (staged_out) return std::memcpy(dst, src, bytes), hipSuccess;
-        return hipMemcpyAsync(dst, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
-    };
-    RC_TRY(give(a.receipts_root, h_roots + 32 * (size_t)a.receipts_at, 32));
-    RC_TRY(give(a.roots_out, h_roots, 32 * (size_t)n_tries));
-    RC_TRY(give(a.logs_bloom, h_block, 256));
-    RC_TRY(give(a.blooms, h_rows, 256 * (size_t)n));
+    // roots, rows and the block's bloom (inside d_zero) and the host form's encodings lie next to each other: one span in the host form
+    // while it fits the pinned stage.  No control words go back: the device form has read them above, the host form needs none.
+    CallOutputs outs(ws, st, dev, d_roots);
+    outs.cover(d_enc ? d_enc + rbytes : d_zero + zero_bytes);
+    outs.add(a.receipts_root, d_roots + 32 * (size_t)a.receipts_at, 32);
+    outs.add(a.roots_out, d_roots, 32 * (size_t)n_tries);
+    outs.add(a.logs_bloom, d_block, 256);
+    outs.add(a.blooms, d_rows, 256 * (size_t)n);
     if (!dev && want_enc && fits) {
-        RC_TRY(give(a.encoded, h_enc, (size_t)rbytes));
-        RC_TRY(give(a.encoded_off, h_enc_off, 8 * ((size_t)n + 1)));
+        outs.add(a.encoded, d_enc, (size_t)rbytes);
+        outs.add(a.encoded_off, d_enc_off, 8 * ((size_t)n + 1));
     }
-    if (!dev && !staged_out) RC_TRY(hipStreamSynchronize(st));
+    RC_TRY(outs.deliver());
     return PHANT_OK;
 }
 

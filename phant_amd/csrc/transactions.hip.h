@@ -42,6 +42,7 @@
 #include "absorb.hip.h"
 #include "launch.h"
 #include "secp256k1.hip.h"
+#include "staging.h"
 #include "transactions.h"
 #define TX_HD __host__ __device__ inline
 #endif
@@ -772,10 +773,6 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
     TX_TRY(ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXS_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXS;
-    auto read_ctl = [&](const uint32_t* d_ctl) -> hipError_t {
-        hipError_t e = hipMemcpyAsync(const_cast<uint32_t*>(mb), d_ctl, 4 * CTL_WORDS, hipMemcpyDeviceToHost, st);
-        return e == hipSuccess ? hipStreamSynchronize(st) : e;
-    };
     uint64_t bytes = in.tx_bytes;
     // can the call hold an authorization tuple?  The host form sees every transaction's first byte; the device form cannot know
     bool maybe_tuples = fork >= FORK_PRAGUE && dev;
@@ -816,36 +813,20 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
             d_txs = io.template take<uint8_t>((size_t)bytes + 16);
         }
     };
-    {
-        ArenaSizer size;
-        carve(size);
-        if (size.bytes > ws.io.cap) TX_TRY(hipStreamSynchronize(st));  // (a kernel may still read the arena that is about to go)
-        const hipError_t e = ws.io.reset(size.bytes);
-        if (e != hipSuccess) return err = std::string("block_transactions: hipMalloc(workspace): ") + hipGetErrorString(e), PHANT_E_OOM;
-        carve(ws.io);
-        if (ws.io.overflowed) return err = "block_transactions: arena sized too small (internal)", PHANT_E_DEVICE;
-    }
+    if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_transactions", "workspace", err)) return rc;
     TX_TRY(hipMemsetAsync(d.ctl, 0, 4 * CTL_WORDS, st));
 
     // ---- in: (host form) offsets and bytes in ONE copy through the pinned stage where they fit it; (device form) the offsets' check
     const uint32_t grid256 = (n + 255u) / 256u, grid64 = (n + 63u) / 64u;
     if (!dev) {
-        uint8_t* const in_begin = reinterpret_cast<uint8_t*>(const_cast<uint64_t*>(d_off));
-        const size_t in_end = (size_t)(d_txs + bytes - ws.io.base);
-        const bool staged = !PHANT_ARENA_POISONS && in_end <= Workspaces::STAGE_BYTES;
-        if (staged) {
-            TX_TRY(ws.ensure_stage());
-            std::memcpy(ws.staged(in_begin), in.tx_off, 8 * ((size_t)n + 1));
-            if (bytes) std::memcpy(ws.staged(const_cast<uint8_t*>(d_txs)), in.txs, (size_t)bytes);
-            TX_TRY(hipMemcpyAsync(in_begin, ws.staged(in_begin), (size_t)(d_txs + bytes - in_begin), hipMemcpyHostToDevice, st));
-        } else {
-            TX_TRY(hipMemcpyAsync(in_begin, in.tx_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
-            if (bytes) TX_TRY(hipMemcpyAsync(const_cast<uint8_t*>(d_txs), in.txs, (size_t)bytes, hipMemcpyHostToDevice, st));
-        }
+        StagedInputs ins(ws, st, d_off, d_txs + bytes);
+        ins.put(d_off, in.tx_off, 8 * ((size_t)n + 1));
+        ins.put(d_txs, in.txs, (size_t)bytes);
+        TX_TRY(ins.finish());
     } else {
         hipLaunchKernelGGL(tx_check_args_kernel, dim3(grid256), dim3(256), 0, st, d_off, n, bytes, d.ctl);
         TX_TRY(hipGetLastError());
-        TX_TRY(read_ctl(d.ctl));
+        TX_TRY(ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
         if (mb[0] & F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
         if (mb[0] & F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
     }
@@ -867,7 +848,7 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
     AuthDev ad;
     std::memset(&ad, 0, sizeof ad);
     if (maybe_tuples) {
-        TX_TRY(read_ctl(d.ctl));
+        TX_TRY(ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
         n_auth = mb[2];
     }
     if (n_auth) {
@@ -881,12 +862,8 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
             ad.recid = io.template take<uint8_t>((size_t)n_auth);
             ad.pre_status = io.template take<uint8_t>((size_t)n_auth);
         };
-        ArenaSizer size;
-        carve_auth(size);
-        const hipError_t e = ws.txa.reset(size.bytes);  // (the stream is idle: the control words were just read)
-        if (e != hipSuccess) return err = std::string("block_transactions: hipMalloc(authorizations): ") + hipGetErrorString(e), PHANT_E_OOM;
-        carve_auth(ws.txa);
-        if (ws.txa.overflowed) return err = "block_transactions: arena sized too small (internal)", PHANT_E_DEVICE;
+        // (no synchronisation before the arena grows -- the stream is idle: the control words were just read)
+        if (const int32_t rc = lay_out_status(lay_out_arena(ws.txa, st, carve_auth, true), "block_transactions", "authorizations", err)) return rc;
         TX_TRY(launch_exclusive_scan_u32(d.x.auth_first, n + 1u, d_scan, st));
         hipLaunchKernelGGL(tx_auth_rows_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, in.chain_id, d, ad, n_auth);
         TX_TRY(hipGetLastError());
@@ -899,73 +876,28 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
     hipLaunchKernelGGL(tx_rules_kernel, dim3(grid64), dim3(64), 0, st, n, ru, d, recover ? d.o.sig_status : nullptr);
     TX_TRY(hipGetLastError());
 
-    // ---- out: the rows of the tuples (at most auth_cap of them) by copies of their own in both forms
+    // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage);
+    // the rows of the tuples (at most auth_cap of them), which lie in their own arena, by copies of their own in both forms
+    CallOutputs outs(ws, st, dev, d.ctl, d.ctl, Workspaces::MAILBOX_TXS, CTL_WORDS);
     const size_t auth_rows = std::min(n_auth, xin.auth_cap);
-    const hipMemcpyKind back = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-#define X(m, T, e) \
-    if (xout.m && auth_rows) TX_TRY(hipMemcpyAsync(xout.m, ad.x.m, auth_rows * e * sizeof(T), back, st));
+#define X(m, T, e) +1
+    static_assert(0 TX_AUTH_OUTPUTS(X) TX_OUTPUTS(X) TX_EX_OUTPUTS(X) + 1 <= CallOutputs::CAP, "the longest list of outputs fits");
+#undef X
+#define X(m, T, e) outs.add(xout.m, ad.x.m, auth_rows * e * sizeof(T));
     TX_AUTH_OUTPUTS(X)
 #undef X
-    auto results = [&](const volatile uint32_t* ctl) {
-        out.first_bad = n - ctl[1];
-        xout.n_auth = ctl[2];
-        xout.blob_gas_used = GAS_PER_BLOB * ((uint64_t)ctl[4] | (uint64_t)ctl[5] << 32);
-    };
-    if (dev) {
-#define X(m, T, e) \
-    if (out.m) TX_TRY(hipMemcpyAsync(out.m, d.o.m, (size_t)n * e * sizeof(T), hipMemcpyDeviceToDevice, st));
-        TX_OUTPUTS(X)
-#undef X
-#define X(m, T, e) \
-    if (xout.m) TX_TRY(hipMemcpyAsync(xout.m, d.x.m, (size_t)n * e * sizeof(T), hipMemcpyDeviceToDevice, st));
-        TX_EX_OUTPUTS(X)
-#undef X
-        if (xout.auth_first) TX_TRY(hipMemcpyAsync(xout.auth_first, d.x.auth_first, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, st));
-        TX_TRY(read_ctl(d.ctl));
-        results(mb);
-        return PHANT_OK;
-    }
-    // host form: the control words and everything up to the last wanted output cross the bus as ONE copy into the pinned stage when they
-    // fit there (a copy into pageable memory is ~25 us a piece, and a call has up to 28)
-    size_t last = 0;
-#define X(m, T, e) \
-    if (out.m) last = (size_t)(reinterpret_cast<uint8_t*>(d.o.m) - ws.io.base) + (size_t)n * e * sizeof(T);
+#define X(m, T, e) outs.add(out.m, d.o.m, (size_t)n * e * sizeof(T));
     TX_OUTPUTS(X)
 #undef X
-    if (xout.auth_first) last = (size_t)(reinterpret_cast<uint8_t*>(d.x.auth_first) - ws.io.base) + 4 * ((size_t)n + 1);
-#define X(m, T, e) \
-    if (xout.m) last = (size_t)(reinterpret_cast<uint8_t*>(d.x.m) - ws.io.base) + (size_t)n * e * sizeof(T);
+    outs.add(xout.auth_first, d.x.auth_first, 4 * ((size_t)n + 1));
+#define X(m, T, e) outs.add(xout.m, d.x.m, (size_t)n * e * sizeof(T));
     TX_EX_OUTPUTS(X)
 #undef X
-    if (!last) last = (size_t)(reinterpret_cast<uint8_t*>(d.ctl + CTL_WORDS) - ws.io.base);
-    const bool staged_out = !PHANT_ARENA_POISONS && last <= Workspaces::STAGE_BYTES;
-    if (staged_out) {
-        TX_TRY(ws.ensure_stage());
-        TX_TRY(hipMemcpyAsync(ws.staged(d.ctl), d.ctl, last - (size_t)(reinterpret_cast<uint8_t*>(d.ctl) - ws.io.base), hipMemcpyDeviceToHost, st));
-        TX_TRY(hipStreamSynchronize(st));
-        results(ws.staged(d.ctl));
-#define X(m, T, e) \
-    if (out.m && n) std::memcpy(out.m, ws.staged(d.o.m), (size_t)n * e * sizeof(T));
-        TX_OUTPUTS(X)
-#undef X
-#define X(m, T, e) \
-    if (xout.m && n) std::memcpy(xout.m, ws.staged(d.x.m), (size_t)n * e * sizeof(T));
-        TX_EX_OUTPUTS(X)
-#undef X
-        if (xout.auth_first) std::memcpy(xout.auth_first, ws.staged(d.x.auth_first), 4 * ((size_t)n + 1));
-    } else {
-#define X(m, T, e) \
-    if (out.m && n) TX_TRY(hipMemcpyAsync(out.m, d.o.m, (size_t)n * e * sizeof(T), hipMemcpyDeviceToHost, st));
-        TX_OUTPUTS(X)
-#undef X
-#define X(m, T, e) \
-    if (xout.m && n) TX_TRY(hipMemcpyAsync(xout.m, d.x.m, (size_t)n * e * sizeof(T), hipMemcpyDeviceToHost, st));
-        TX_EX_OUTPUTS(X)
-#undef X
-        if (xout.auth_first) TX_TRY(hipMemcpyAsync(xout.auth_first, d.x.auth_first, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
-        TX_TRY(read_ctl(d.ctl));
-        results(mb);
-    }
+    TX_TRY(outs.deliver());
+    const volatile uint32_t* const ctl = outs.ctl();
+    out.first_bad = n - ctl[1];
+    xout.n_auth = ctl[2];
+    xout.blob_gas_used = GAS_PER_BLOB * ((uint64_t)ctl[4] | (uint64_t)ctl[5] << 32);
     return PHANT_OK;
 }
 

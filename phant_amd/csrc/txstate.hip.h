@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "launch.h"
+#include "staging.h"
 #include "txstate.h"
 #define TXST_HD __host__ __device__ inline
 #endif
@@ -591,10 +592,6 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
     TXST_TRY(ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXST_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXST;
-    auto read_ctl = [&](const uint32_t* d_ctl) -> hipError_t {
-        hipError_t e = hipMemcpyAsync(const_cast<uint32_t*>(mb), d_ctl, 4 * CTL_WORDS, hipMemcpyDeviceToHost, st);
-        return e == hipSuccess ? hipStreamSynchronize(st) : e;
-    };
     std::vector<uint8_t> kind;
     if (!dev)
         if (const char* what = check_host(in, kind)) return err = std::string("block_txs_prestate: ") + what, PHANT_E_INVALID_ARG;
@@ -611,7 +608,7 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
     a.mask = slots - 1u, a.salt0 = salt[0], a.salt1 = salt[1];
     uint32_t *zero = nullptr, *ones = nullptr, *digit_totals = nullptr, *hist = nullptr, *vals_alt = nullptr;
     uint64_t* keys_alt = nullptr;
-    uint8_t *in_begin = nullptr, *in_end = nullptr;
+    uint8_t* in_end = nullptr;
     auto carve = [&](auto& io) {
         zero = io.template take<uint32_t>(zero_words);
 #define X(m, T, e) a.o.m = io.template take<T>(e);
@@ -635,47 +632,30 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
         a.agg = io.template take<uint32_t>((size_t)SEG_WORDS * tiles);
         a.tp = io.template take<uint32_t>((size_t)SEG_WORDS * (tiles ? tiles : 1u));
     };
-    {
-        ArenaSizer size;
-        carve(size);
-        if (size.bytes > ws.io.cap) TXST_TRY(hipStreamSynchronize(st));  // (a kernel may still read the arena that is about to go)
-        const hipError_t e = ws.io.reset(size.bytes);
-        if (e != hipSuccess) return err = std::string("block_txs_prestate: hipMalloc(workspace): ") + hipGetErrorString(e), PHANT_E_OOM;
-        carve(ws.io);
-        if (ws.io.overflowed) return err = "block_txs_prestate: arena sized too small (internal)", PHANT_E_DEVICE;
-    }
+    if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_txs_prestate", "workspace", err)) return rc;
     if (!in.auth_first) a.in.auth_first = nullptr;
     a.ctl = zero, digit_totals = zero + CTL_WORDS;
     a.o.sends = digit_totals + 512;
     a.o.roles = reinterpret_cast<uint8_t*>(a.o.sends + na);
     a.table = ones, a.first_auth = ones + slots;
-    in_begin = reinterpret_cast<uint8_t*>(const_cast<uint8_t*>(a.in.sender));
     TXST_TRY(hipMemsetAsync(zero, 0, 4 * zero_words, st));
     const bool small = n != 0u && n <= SMALL_ROWS && na <= SMALL_ACCOUNTS;  // (its table and first-tuple words are in LDS)
     if (!small) TXST_TRY(hipMemsetAsync(ones, 0xff, 4 * ((size_t)slots + na), st));
 
     // ---- in: (host form) every array and the codes' kinds in ONE copy through the pinned stage where they fit it; (device form) the check
     if (!dev) {
-        const bool staged = !PHANT_ARENA_POISONS && (size_t)(in_end - ws.io.base) <= Workspaces::STAGE_BYTES;
-        if (staged) TXST_TRY(ws.ensure_stage());
-#define X(m, T, e)                                                                                                          \
-    if ((e) != 0) {                                                                                                         \
-        if (staged) std::memcpy(ws.staged(const_cast<T*>(a.in.m)), in.m, (size_t)(e) * sizeof(T));                          \
-        else TXST_TRY(hipMemcpyAsync(const_cast<T*>(a.in.m), in.m, (size_t)(e) * sizeof(T), hipMemcpyHostToDevice, st));   \
-    }
+        StagedInputs ins(ws, st, a.in.sender, in_end);
+#define X(m, T, e) ins.put(a.in.m, in.m, (size_t)(e) * sizeof(T));
         TXST_INPUTS(X)
 #undef X
-        if (nc) {
-            if (staged) std::memcpy(ws.staged(a.code_kind), kind.data(), nc);
-            else TXST_TRY(hipMemcpyAsync(a.code_kind, kind.data(), nc, hipMemcpyHostToDevice, st));
-        }
-        if (staged && in_end > in_begin) TXST_TRY(hipMemcpyAsync(in_begin, ws.staged(in_begin), (size_t)(in_end - in_begin), hipMemcpyHostToDevice, st));
+        ins.put(a.code_kind, kind.data(), nc);  // (`kind` outlives the call's last synchronisation)
+        TXST_TRY(ins.finish());
         a.in.code_off = nullptr, a.in.codes = nullptr;  // (no kernel of the host form reads them: the kinds are there)
     } else {
         const uint64_t lanes = std::max<uint64_t>(std::max<uint64_t>((uint64_t)n + 1u, nc), na);
         hipLaunchKernelGGL(txst_check_args_kernel, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, st, a);
         TXST_TRY(hipGetLastError());
-        TXST_TRY(read_ctl(a.ctl));
+        TXST_TRY(ws.read_words(Workspaces::MAILBOX_TXST, a.ctl, CTL_WORDS, st));
         if (mb[0] & BAD_AUTH_FIRST) return err = "block_txs_prestate_dev: auth_first does not run within [0, n_auth] without going backwards", PHANT_E_INVALID_ARG;
         if (mb[0] & BAD_CODE_OFF) return err = "block_txs_prestate_dev: code_off does not run within [0, code_bytes] without going backwards", PHANT_E_INVALID_ARG;
         if (mb[0] & BAD_CODE_INDEX) return err = "block_txs_prestate_dev: a code_index names no code", PHANT_E_INVALID_ARG;
@@ -708,48 +688,15 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
         TXST_TRY(hipGetLastError());
     }
 
-    // ---- out
-    auto results = [&](const volatile uint32_t* ctl) { out.first_bad = n - ctl[1], out.n_undetermined = ctl[2]; };
-    if (dev) {
-        if (out.sends && na) TXST_TRY(hipMemcpyAsync(out.sends, a.o.sends, 4 * (size_t)na, hipMemcpyDeviceToDevice, st));
-        if (out.roles && na) TXST_TRY(hipMemcpyAsync(out.roles, a.o.roles, na, hipMemcpyDeviceToDevice, st));
-#define X(m, T, e) \
-    if (out.m && (e) != 0) TXST_TRY(hipMemcpyAsync(out.m, a.o.m, (size_t)(e) * sizeof(T), hipMemcpyDeviceToDevice, st));
-        TXST_OUTPUTS(X)
-#undef X
-        TXST_TRY(read_ctl(a.ctl));
-        results(mb);
-        return PHANT_OK;
-    }
-    // host form: the control words and everything up to the last wanted output as ONE copy into the pinned stage when they fit there
-    size_t last = 4 * (size_t)CTL_WORDS;
-    if (out.sends && na) last = (size_t)(reinterpret_cast<uint8_t*>(a.o.sends + na) - ws.io.base);
-    if (out.roles && na) last = (size_t)(a.o.roles + na - ws.io.base);
-#define X(m, T, e) \
-    if (out.m && (e) != 0) last = (size_t)(reinterpret_cast<uint8_t*>(a.o.m) - ws.io.base) + (size_t)(e) * sizeof(T);
+    // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage)
+    CallOutputs outs(ws, st, dev, a.ctl, a.ctl, Workspaces::MAILBOX_TXST, CTL_WORDS);
+    outs.add(out.sends, a.o.sends, 4 * (size_t)na);
+    outs.add(out.roles, a.o.roles, na);
+#define X(m, T, e) outs.add(out.m, a.o.m, (size_t)(e) * sizeof(T));
     TXST_OUTPUTS(X)
 #undef X
-    if (!PHANT_ARENA_POISONS && last <= Workspaces::STAGE_BYTES) {
-        TXST_TRY(ws.ensure_stage());
-        TXST_TRY(hipMemcpyAsync(ws.staged(a.ctl), a.ctl, last, hipMemcpyDeviceToHost, st));
-        TXST_TRY(hipStreamSynchronize(st));
-        results(ws.staged(a.ctl));
-        if (out.sends && na) std::memcpy(out.sends, ws.staged(a.o.sends), 4 * (size_t)na);
-        if (out.roles && na) std::memcpy(out.roles, ws.staged(a.o.roles), na);
-#define X(m, T, e) \
-    if (out.m && (e) != 0) std::memcpy(out.m, ws.staged(a.o.m), (size_t)(e) * sizeof(T));
-        TXST_OUTPUTS(X)
-#undef X
-    } else {
-        if (out.sends && na) TXST_TRY(hipMemcpyAsync(out.sends, a.o.sends, 4 * (size_t)na, hipMemcpyDeviceToHost, st));
-        if (out.roles && na) TXST_TRY(hipMemcpyAsync(out.roles, a.o.roles, na, hipMemcpyDeviceToHost, st));
-#define X(m, T, e) \
-    if (out.m && (e) != 0) TXST_TRY(hipMemcpyAsync(out.m, a.o.m, (size_t)(e) * sizeof(T), hipMemcpyDeviceToHost, st));
-        TXST_OUTPUTS(X)
-#undef X
-        TXST_TRY(read_ctl(a.ctl));
-        results(mb);
-    }
+    TXST_TRY(outs.deliver());
+    out.first_bad = n - outs.ctl()[1], out.n_undetermined = outs.ctl()[2];
     return PHANT_OK;
 }
 

@@ -11,6 +11,15 @@ extern "C" __attribute__((visibility("default"))) void hipemu_counters(unsigned 
     out[2] = hipemu::M.divergent_ops;  // ... of which with an active mask smaller than the wave's live lanes
 }
 
+// hipMemcpyAsync calls host to device, device to host and device to device, hipMemsetAsync calls, hipStreamSynchronize calls
+extern "C" __attribute__((visibility("default"))) void hipemu_bus_counters(unsigned long long out[5]) {
+    out[0] = hipemu::M.h2d;
+    out[1] = hipemu::M.d2h;
+    out[2] = hipemu::M.d2d;
+    out[3] = hipemu::M.memsets;
+    out[4] = hipemu::M.stream_syncs;
+}
+
 // radix_sort.hip's prefix sum over caller-supplied counters (test hook: the C-ABI reaches it only through the state root).
 #include "../../phant_amd/csrc/launch.h"
 extern "C" __attribute__((visibility("default"))) int hipemu_test_exclusive_scan(unsigned* counters, unsigned n) {

@@ -166,6 +166,8 @@ struct Machine {
     Lane* cur = nullptr;
     std::function<void()> body;
     unsigned long long launches = 0, wave_ops = 0, divergent_ops = 0, graph_launches = 0;
+    // what crosses the bus, as the host asks for it: hipMemcpyAsync by kind, hipMemsetAsync, hipStreamSynchronize
+    unsigned long long h2d = 0, d2h = 0, d2d = 0, memsets = 0, stream_syncs = 0;
     const char* kernel = "";
     std::vector<std::function<void()>>* capture = nullptr;  // stream capture in progress: work is recorded, not run
 };
@@ -562,7 +564,8 @@ static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKi
     if (n) std::memmove(d, s, n);
     return hipSuccess;
 }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) {
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t = nullptr) {
+    ++(kind == hipMemcpyHostToDevice ? hipemu::M.h2d : kind == hipMemcpyDeviceToHost ? hipemu::M.d2h : hipemu::M.d2d);
     if (hipemu::M.capture) {
         hipemu::M.capture->push_back([=]() { if (n) std::memmove(d, s, n); });
         return hipSuccess;
@@ -571,6 +574,7 @@ static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMem
     return hipSuccess;
 }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) {
+    ++hipemu::M.memsets;
     if (hipemu::M.capture) {
         hipemu::M.capture->push_back([=]() { if (n) std::memset(d, v, n); });
         return hipSuccess;
@@ -588,7 +592,7 @@ static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
 }
 static inline hipError_t hipStreamCreate(hipStream_t* s) { return hipStreamCreateWithFlags(s, 0); }
 static inline hipError_t hipStreamDestroy(hipStream_t s) { std::free(s); return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t) { ++hipemu::M.stream_syncs; return hipSuccess; }
 static inline hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }  // (a launch has run when it returns)
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hipemu_event(); return hipSuccess; }

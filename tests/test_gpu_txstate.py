@@ -310,6 +310,28 @@ def test_subsets_of_the_outputs(P):
     assert (rc, fb, nu) == (OK, 0, 0)
 
 
+@pytest.mark.parametrize("n, na", [(64, 90000), (170000, 2048)])
+def test_a_call_beyond_the_pinned_stage(P, n, na):
+    """The smallest shapes that cross the 8 MiB pinned stage, whose arena holds the outputs in front of the inputs.  90 000 pre-state rows
+    (97 input bytes and 5 output bytes each): the inputs end beyond the stage and cross the bus array by array, the outputs still come
+    back as one span.  170 000 transactions (85 input bytes and 52 output bytes each) against 2 048 rows: both directions go array by
+    array.  Row for row against the definition, in both forms."""
+    rng = np.random.default_rng(41)
+    accounts = make_accounts(na, rng)
+    txs = make_block(n, accounts, "distinct", rng)
+    probes = [addr(3), addr(10**7), accounts[na // 3]["address"]]
+    in_bytes = sum(a.nbytes for a in R.inputs(txs, accounts, probes=probes).values() if a is not None)
+    rows = {"n": n, "n_accounts": na, "n_probe": len(probes)}
+    out_bytes = sum(np.dtype(dt).itemsize * k * rows[r] for _, dt, k, r in R.OUTPUTS)
+    assert in_bytes > 8 << 20  # (the inputs lie behind the outputs: whatever those take, they end beyond the stage)
+    if n < na:  # the outputs with the control words, the sort's 512 digit totals and every array's padding in front of and between them
+        assert out_bytes + 4 * (8 + 512) + 256 * (len(R.OUTPUTS) + 2) < 8 << 20
+    else:
+        assert out_bytes > 8 << 20
+    flags = check(P, R.LONDON, txs, accounts, probes=probes)
+    assert len(set(flags.tolist())) >= 3
+
+
 def test_refused_arguments(P):
     """one refusal per rule of the header, in both forms; nothing is written"""
     rng = np.random.default_rng(6)
