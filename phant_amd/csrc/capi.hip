@@ -1050,6 +1050,111 @@ static int32_t nodeset_prepare(phant_ctx* c, uint32_t total_nodes, hipStream_t s
     return PHANT_OK;
 }
 
+namespace {
+
+// A copy in of an array that may be empty, and a copy back that the caller may not want (a NULL destination): neither is a copy.
+hipError_t up(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+hipError_t back(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+}
+
+// The pre-state stage of the execution-witness calls, once for phant_exec_witness_prestate and poststate_run:
+//   copies -> trie keys -> node-set hash -> account walk -> account decode -> slot walk -> slot decode
+// The set is hashed ONCE; the accounts walk from the trusted root, the slots from the storage roots the account leaves prove.  A
+// caller carves inside its own lay_out, calls nodeset_prepare(c->ns) before it queues anything, and may put work of its own between
+// the two launch steps.  `p`'s code side (nc, code_index, codes .. salt1) is the pre-state call's own.
+struct PrestateStage {
+    uint32_t na = 0, ns = 0, total_nodes = 0, n_counters = 0;
+    size_t nk = 0, pre_len = 0, nodes_len = 0;
+    uint8_t *pre = nullptr, *keys = nullptr, *root = nullptr, *nodes = nullptr;
+    uint64_t *poff = nullptr, *noff = nullptr, *avoff = nullptr, *svoff = nullptr;
+    uint32_t *sacc = nullptr, *avlen = nullptr, *svlen = nullptr;
+    phant::PrestateArgs p{};
+
+    // the stage's part of the call's layout; counters: the words behind p.counters (PRE_CNT_*, then the caller's own)
+    template <class Arena>
+    void carve(Arena& a, const phant::ExecWitness& w, uint32_t counters) {
+        p.na = na = w.n_accounts;
+        p.ns = ns = w.n_slots;
+        total_nodes = (uint32_t)(w.node_off.size() - 1);
+        n_counters = counters;
+        nk = (size_t)na + ns;
+        pre_len = w.preimages.size();
+        nodes_len = w.nodes.size();
+        pre = a.template take<uint8_t>(pre_len + 16);
+        poff = a.template take<uint64_t>(nk + 1);
+        keys = a.template take<uint8_t>(nk * 32);
+        root = a.template take<uint8_t>(32);
+        p.storage_roots = a.template take<uint8_t>((size_t)na * 32);
+        p.slot_account = sacc = a.template take<uint32_t>(ns);
+        p.nodes = nodes = a.template take<uint8_t>(nodes_len + 16);
+        noff = a.template take<uint64_t>((size_t)total_nodes + 1);
+        p.acc_status = a.template take<uint8_t>(na);
+        p.acc_voff = avoff = a.template take<uint64_t>(na);
+        p.acc_vlen = avlen = a.template take<uint32_t>(na);
+        p.slot_status = a.template take<uint8_t>(ns);
+        p.slot_voff = svoff = a.template take<uint64_t>(ns);
+        p.slot_vlen = svlen = a.template take<uint32_t>(ns);
+        p.nonces = a.template take<uint64_t>(na);
+        p.balances = a.template take<uint8_t>((size_t)na * 32);
+        p.code_hashes = a.template take<uint8_t>((size_t)na * 32);
+        p.slot_vals = a.template take<uint8_t>((size_t)ns * 32);
+        p.counters = a.template take<uint32_t>(counters);
+    }
+    // the witness and the root the caller trusts on their way in (an empty array is no copy), the counters zeroed
+    hipError_t upload(const phant::ExecWitness& w, const uint8_t* trusted_root, hipStream_t s) const {
+        hipError_t e = up(pre, w.preimages.data(), pre_len, s);
+        if (e == hipSuccess) e = up(poff, w.preimage_off.data(), (nk + 1) * 8, s);
+        if (e == hipSuccess) e = up(root, trusted_root, 32, s);
+        if (e == hipSuccess) e = up(sacc, w.slot_account.data(), (size_t)ns * 4, s);
+        if (e == hipSuccess) e = up(nodes, w.nodes.data(), nodes_len, s);
+        if (e == hipSuccess) e = up(noff, w.node_off.data(), ((size_t)total_nodes + 1) * 8, s);
+        return e == hipSuccess ? hipMemsetAsync(p.counters, 0, (size_t)n_counters * 4, s) : e;
+    }
+    // secure-trie keys: keccak256(address) / keccak256(slot), one batched launch
+    hipError_t hash_keys(hipStream_t s) const { return phant::launch_keccak256_var(pre, poff, (uint32_t)nk, keys, s); }
+    // ... and everything behind them, on c->ns at the epoch nodeset_prepare took.  A failure (the first one is returned) leaves the
+    // workspace dirty, whatever part of the launch ran: the next one starts from zeroed memory.
+    hipError_t resolve(phant_ctx* c, hipStream_t s) const {
+        NodesetSpace& sp = c->ns;
+        const phant::VerifyArgs acc{root, 1, nullptr, keys, 32, nodes, nodes_len, noff, nullptr, na, p.acc_status, avoff, avlen};
+        const phant::VerifyArgs sto{p.storage_roots, na, sacc, keys + 32ull * na, 32, nodes, nodes_len, noff, nullptr, ns,
+                                    p.slot_status, svoff, svlen};
+        hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s, c->ns_tune);
+        if (e == hipSuccess) e = phant::launch_nodeset_walk(acc, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s);
+        if (e == hipSuccess) e = phant::launch_prestate_accounts(p, s);
+        if (e == hipSuccess) e = phant::launch_nodeset_walk(sto, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s);
+        if (e == hipSuccess) e = phant::launch_prestate_slots(p, s);
+        if (e != hipSuccess) sp.dirty = true;
+        return e;
+    }
+    // the pre-state fields of the post-state build's arguments
+    void fill(phant::PoststateArgs& q) const {
+        q.nodes = nodes;
+        q.nodes_len = nodes_len;
+        q.na = na;
+        q.ns = ns;
+        q.keys = keys;
+        q.parent_root = root;
+        q.acc_status = p.acc_status;
+        q.slot_status = p.slot_status;
+        q.acc_voff = avoff;
+        q.acc_vlen = avlen;
+        q.slot_voff = svoff;
+        q.slot_vlen = svlen;
+        q.pre_nonces = p.nonces;
+        q.pre_balances = p.balances;
+        q.pre_sroots = p.storage_roots;
+        q.pre_code_hashes = p.code_hashes;
+        q.slot_account = sacc;
+        q.counters = p.counters;
+    }
+};
+
+}  // namespace
+
 // Where a verify call runs: a stream and the workspaces that go with it, the ctx's own or a streaming slot's.
 struct Lane {
     hipStream_t stream;
@@ -1716,55 +1821,27 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
     if (!state_root) return fail(c, PHANT_E_INVALID_ARG, "exec_witness_prestate: the trusted state root is required");
     const phant::ExecWitness& w = pw->w;
     const uint32_t na = w.n_accounts, ns = w.n_slots, nc = (uint32_t)(w.code_off.size() - 1);
-    const uint32_t total_nodes = (uint32_t)(w.node_off.size() - 1);
-    const size_t nodes_len = w.nodes.size(), code_bytes = w.codes.size(), pre_len = w.preimages.size();
+    const size_t code_bytes = w.codes.size();
     const uint32_t slots_t = phant::code_table_slots(nc);
     out->n_failed = out->n_missing_code = out->n_unused_codes = 0;
     DeviceGuard g(c->device);
     hipStream_t s = c->stream;
-    const size_t nk = (size_t)na + ns;
-    uint8_t *d_pre, *d_keys, *d_root, *d_nodes, *d_codes;
-    uint64_t *d_poff, *d_noff, *d_coff, *d_avoff, *d_svoff;
-    uint32_t *d_sacc, *d_avlen, *d_svlen;
-    phant::PrestateArgs p{};
+    uint8_t* d_codes;
+    uint64_t* d_coff;
+    PrestateStage st;
+    phant::PrestateArgs& p = st.p;
     int32_t rc = lay_out(c, s, c->ws.io, [&](auto& io) {
-        d_pre = io.template take<uint8_t>(pre_len + 16);
-        d_poff = io.template take<uint64_t>(nk + 1);
-        d_keys = io.template take<uint8_t>(nk * 32);
-        d_root = io.template take<uint8_t>(32);
-        p.storage_roots = io.template take<uint8_t>((size_t)na * 32);
-        d_sacc = io.template take<uint32_t>(ns);
-        d_nodes = io.template take<uint8_t>(nodes_len + 16);
-        d_noff = io.template take<uint64_t>((size_t)total_nodes + 1);
+        st.carve(io, w, 4);
         d_codes = io.template take<uint8_t>(code_bytes + 16);
         d_coff = io.template take<uint64_t>((size_t)nc + 1);
-        p.acc_status = io.template take<uint8_t>(na);
-        d_avoff = io.template take<uint64_t>(na);
-        d_avlen = io.template take<uint32_t>(na);
-        p.slot_status = io.template take<uint8_t>(ns);
-        d_svoff = io.template take<uint64_t>(ns);
-        d_svlen = io.template take<uint32_t>(ns);
-        p.nonces = io.template take<uint64_t>(na);
-        p.balances = io.template take<uint8_t>((size_t)na * 32);
-        p.code_hashes = io.template take<uint8_t>((size_t)na * 32);
         p.code_index = io.template take<uint32_t>(na);
-        p.slot_vals = io.template take<uint8_t>((size_t)ns * 32);
         p.code_dig = io.template take<uint32_t>((size_t)nc * 8);
         p.code_slot = io.template take<uint32_t>(nc);
         p.table = io.template take<uint32_t>(slots_t);
         p.table_used = io.template take<uint32_t>(slots_t);
-        p.counters = io.template take<uint32_t>(4);
     });
     if (rc) return rc;
-    p.nodes = d_nodes;
-    p.na = na;
-    p.ns = ns;
     p.nc = nc;
-    p.acc_voff = d_avoff;
-    p.acc_vlen = d_avlen;
-    p.slot_voff = d_svoff;
-    p.slot_vlen = d_svlen;
-    p.slot_account = d_sacc;
     p.codes = d_codes;
     p.code_off = d_coff;
     p.mask = slots_t - 1u;
@@ -1773,18 +1850,12 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
     rc = ensure_code_side(c);
     if (rc) return rc;
     if (na) {  // (the node-set workspace sized and its epoch taken before anything is queued: sizing it may wait for the stream)
-        rc = nodeset_prepare(c, total_nodes, s, c->ns);
+        rc = nodeset_prepare(c, st.total_nodes, s, c->ns);
         if (rc) return rc;
     }
     if (code_bytes) HIP_TRY(c, hipMemcpyAsync(d_codes, w.codes.data(), code_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_coff, w.code_off.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
-    if (pre_len) HIP_TRY(c, hipMemcpyAsync(d_pre, w.preimages.data(), pre_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_poff, w.preimage_off.data(), (nk + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_root, state_root, 32, hipMemcpyHostToDevice, s));
-    if (ns) HIP_TRY(c, hipMemcpyAsync(d_sacc, w.slot_account.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-    if (nodes_len) HIP_TRY(c, hipMemcpyAsync(d_nodes, w.nodes.data(), nodes_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_noff, w.node_off.data(), ((size_t)total_nodes + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(p.counters, 0, 16, s));
+    HIP_TRY(c, st.upload(w, state_root, s));
     {
         TimedRegion t(c);  // (phant_timing: the kernels of both streams, the copies in and out left out)
         HIP_TRY(c, hipEventRecord(c->code_side.fork, s));
@@ -1795,38 +1866,26 @@ int32_t phant_exec_witness_prestate(phant_ctx* c, const phant_exec_witness* pw, 
         HIP_TRY(c, phant::launch_code_hash(p, c->code_form, h));
         HIP_TRY(c, hipEventRecord(c->code_side.join, h));
         if (na) {
-            HIP_TRY(c, phant::launch_keccak256_var(d_pre, d_poff, (uint32_t)nk, d_keys, s));
-            // the set is hashed ONCE; the accounts walk from the trusted root, the slots from the storage roots the account leaves prove
-            phant::VerifyArgs acc{d_root, 1, nullptr, d_keys, 32, d_nodes, nodes_len, d_noff, nullptr, na, p.acc_status, d_avoff, d_avlen};
-            phant::VerifyArgs sto{p.storage_roots, na, d_sacc, d_keys + 32ull * na, 32, d_nodes, nodes_len, d_noff, nullptr, ns,
-                                  p.slot_status, d_svoff, d_svlen};
-            hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s, c->ns_tune);
-            if (e == hipSuccess) e = phant::launch_nodeset_walk(acc, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
-            if (e == hipSuccess) e = phant::launch_prestate_accounts(p, s);
-            if (e == hipSuccess) e = phant::launch_nodeset_walk(sto, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+            HIP_TRY(c, st.hash_keys(s));
+            const hipError_t e = st.resolve(c, s);
             if (e != hipSuccess) {
-                c->ns.dirty = true;  // (whatever part of the launch ran: the next one starts from zeroed memory)
                 (void)hipStreamSynchronize(h);
                 return fail(c, PHANT_E_DEVICE, "exec_witness_prestate: node-set launch", e);
             }
-            HIP_TRY(c, phant::launch_prestate_slots(p, s));
         }
         HIP_TRY(c, hipStreamWaitEvent(s, c->code_side.join, 0));
         HIP_TRY(c, phant::launch_code_match(p, s));
     }
     uint32_t cnt[4] = {0, 0, 0, 0};
-    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    HIP_TRY(c, back(out->account_status, p.acc_status, na));
-    HIP_TRY(c, back(out->nonces, p.nonces, (size_t)na * 8));
-    HIP_TRY(c, back(out->balances, p.balances, (size_t)na * 32));
-    HIP_TRY(c, back(out->storage_roots, p.storage_roots, (size_t)na * 32));
-    HIP_TRY(c, back(out->code_hashes, p.code_hashes, (size_t)na * 32));
-    HIP_TRY(c, back(out->code_index, p.code_index, (size_t)na * 4));
-    HIP_TRY(c, back(out->slot_status, p.slot_status, ns));
-    HIP_TRY(c, back(out->slot_vals, p.slot_vals, (size_t)ns * 32));
-    HIP_TRY(c, back(cnt, p.counters, 12));
+    HIP_TRY(c, back(out->account_status, p.acc_status, na, s));
+    HIP_TRY(c, back(out->nonces, p.nonces, (size_t)na * 8, s));
+    HIP_TRY(c, back(out->balances, p.balances, (size_t)na * 32, s));
+    HIP_TRY(c, back(out->storage_roots, p.storage_roots, (size_t)na * 32, s));
+    HIP_TRY(c, back(out->code_hashes, p.code_hashes, (size_t)na * 32, s));
+    HIP_TRY(c, back(out->code_index, p.code_index, (size_t)na * 4, s));
+    HIP_TRY(c, back(out->slot_status, p.slot_status, ns, s));
+    HIP_TRY(c, back(out->slot_vals, p.slot_vals, (size_t)ns * 32, s));
+    HIP_TRY(c, back(cnt, p.counters, 12, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     out->n_failed = cnt[phant::PRE_CNT_FAILED];
     out->n_missing_code = cnt[phant::PRE_CNT_MISSING_CODE];
@@ -1855,35 +1914,17 @@ struct AdvanceSink {
 static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const uint8_t* parent_root, phant_poststate* io,
                              const uint32_t* host_order, uint32_t cap_items, uint32_t* need_items, uint32_t* undecided,
                              std::vector<uint8_t>& keys_back, uint32_t cnt[8], AdvanceSink* sink) {
-    const uint32_t na = w.n_accounts, ns = w.n_slots, total_nodes = (uint32_t)(w.node_off.size() - 1);
-    const size_t nodes_len = w.nodes.size(), pre_len = w.preimages.size(), nk = (size_t)na + ns;
+    const uint32_t na = w.n_accounts, ns = w.n_slots;
+    const size_t nk = (size_t)na + ns;
     hipStream_t s = c->stream;
-    uint8_t *d_pre, *d_keys, *d_root, *d_nodes, *d_sort, *d_op, *d_pbal, *d_pch, *d_swr, *d_sval;
-    uint64_t *d_poff, *d_noff, *d_avoff, *d_svoff, *d_pnonce;
-    uint32_t *d_sacc, *d_avlen, *d_svlen, *d_sfirst, *d_order_host;
-    phant::PrestateArgs p{};
+    uint8_t *d_sort, *d_op, *d_pbal, *d_pch, *d_swr, *d_sval;
+    uint64_t* d_pnonce;
+    uint32_t *d_sfirst, *d_order_host;
+    PrestateStage st;
     phant::PoststateArgs q{};
     const size_t sort_ws = phant::order_workspace_bytes((uint32_t)nk);
     int32_t rc = lay_out(c, s, c->ws.io, [&](auto& a) {
-        d_pre = a.template take<uint8_t>(pre_len + 16);
-        d_poff = a.template take<uint64_t>(nk + 1);
-        d_keys = a.template take<uint8_t>(nk * 32);
-        d_root = a.template take<uint8_t>(32);
-        p.storage_roots = a.template take<uint8_t>((size_t)na * 32);
-        d_sacc = a.template take<uint32_t>(ns);
-        d_nodes = a.template take<uint8_t>(nodes_len + 16);
-        d_noff = a.template take<uint64_t>((size_t)total_nodes + 1);
-        p.acc_status = a.template take<uint8_t>(na);
-        d_avoff = a.template take<uint64_t>(na);
-        d_avlen = a.template take<uint32_t>(na);
-        p.slot_status = a.template take<uint8_t>(ns);
-        d_svoff = a.template take<uint64_t>(ns);
-        d_svlen = a.template take<uint32_t>(ns);
-        p.nonces = a.template take<uint64_t>(na);
-        p.balances = a.template take<uint8_t>((size_t)na * 32);
-        p.code_hashes = a.template take<uint8_t>((size_t)na * 32);
-        p.slot_vals = a.template take<uint8_t>((size_t)ns * 32);
-        p.counters = a.template take<uint32_t>(8);
+        st.carve(a, w, 8);
         d_sfirst = a.template take<uint32_t>((size_t)na + 1);
         d_op = a.template take<uint8_t>(na);
         d_pnonce = a.template take<uint64_t>(na);
@@ -1914,32 +1955,7 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
         q.sink_cap_bytes = sink->cap_bytes;
         q.sink_cap_desc = sink->cap_desc;
     }
-    p.nodes = d_nodes;
-    p.na = na;
-    p.ns = ns;
-    p.nc = 0;
-    p.acc_voff = d_avoff;
-    p.acc_vlen = d_avlen;
-    p.slot_voff = d_svoff;
-    p.slot_vlen = d_svlen;
-    p.slot_account = d_sacc;
-    q.nodes = d_nodes;
-    q.nodes_len = nodes_len;
-    q.na = na;
-    q.ns = ns;
-    q.keys = d_keys;
-    q.parent_root = d_root;
-    q.acc_status = p.acc_status;
-    q.slot_status = p.slot_status;
-    q.acc_voff = d_avoff;
-    q.acc_vlen = d_avlen;
-    q.slot_voff = d_svoff;
-    q.slot_vlen = d_svlen;
-    q.pre_nonces = p.nonces;
-    q.pre_balances = p.balances;
-    q.pre_sroots = p.storage_roots;
-    q.pre_code_hashes = p.code_hashes;
-    q.slot_account = d_sacc;
+    st.fill(q);
     q.slot_first = d_sfirst;
     q.op = d_op;
     q.post_nonces = d_pnonce;
@@ -1948,30 +1964,20 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
     q.slot_write = io->slot_write ? d_swr : nullptr;
     q.post_slot_vals = d_sval;
     q.cap_items = cap_items;
-    q.counters = p.counters;
-    rc = nodeset_prepare(c, total_nodes, s, c->ns);
+    rc = nodeset_prepare(c, st.total_nodes, s, c->ns);
     if (rc) return rc;
-    auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(c, up(d_pre, w.preimages.data(), pre_len));
-    HIP_TRY(c, up(d_poff, w.preimage_off.data(), (nk + 1) * 8));
-    HIP_TRY(c, up(d_root, parent_root, 32));
-    HIP_TRY(c, up(d_sacc, w.slot_account.data(), (size_t)ns * 4));
-    HIP_TRY(c, up(d_nodes, w.nodes.data(), nodes_len));
-    HIP_TRY(c, up(d_noff, w.node_off.data(), ((size_t)total_nodes + 1) * 8));
-    HIP_TRY(c, up(d_sfirst, w.slot_first.data(), ((size_t)na + 1) * 4));
-    HIP_TRY(c, up(d_op, io->account_op, na));
+    HIP_TRY(c, st.upload(w, parent_root, s));
+    HIP_TRY(c, up(d_sfirst, w.slot_first.data(), ((size_t)na + 1) * 4, s));
+    HIP_TRY(c, up(d_op, io->account_op, na, s));
     // (the post arrays are only read where op == SET; an all-KEEP / DELETE call may leave them out)
-    if (io->nonces) HIP_TRY(c, up(d_pnonce, io->nonces, (size_t)na * 8));
-    if (io->balances) HIP_TRY(c, up(d_pbal, io->balances, (size_t)na * 32));
-    if (io->code_hashes) HIP_TRY(c, up(d_pch, io->code_hashes, (size_t)na * 32));
+    if (io->nonces) HIP_TRY(c, up(d_pnonce, io->nonces, (size_t)na * 8, s));
+    if (io->balances) HIP_TRY(c, up(d_pbal, io->balances, (size_t)na * 32, s));
+    if (io->code_hashes) HIP_TRY(c, up(d_pch, io->code_hashes, (size_t)na * 32, s));
     if (io->slot_write) {
-        HIP_TRY(c, up(d_swr, io->slot_write, ns));
-        HIP_TRY(c, up(d_sval, io->slot_vals, (size_t)ns * 32));
+        HIP_TRY(c, up(d_swr, io->slot_write, ns, s));
+        HIP_TRY(c, up(d_sval, io->slot_vals, (size_t)ns * 32, s));
     }
-    if (host_order) HIP_TRY(c, up(d_order_host, host_order, nk * 4));
-    HIP_TRY(c, hipMemsetAsync(p.counters, 0, 32, s));
+    if (host_order) HIP_TRY(c, up(d_order_host, host_order, nk * 4, s));
     HIP_TRY(c, hipMemsetAsync(q.acc_flag, 0, (size_t)na * 4, s));
     HIP_TRY(c, hipMemsetAsync(q.key_bad, 0, nk, s));
     if (sink) {
@@ -1981,55 +1987,45 @@ static int32_t poststate_run(phant_ctx* c, const phant::ExecWitness& w, const ui
     uint32_t* d_flag = nullptr;
     {
         TimedRegion t(c);
-        HIP_TRY(c, phant::launch_keccak256_var(d_pre, d_poff, (uint32_t)nk, d_keys, s));
+        HIP_TRY(c, st.hash_keys(s));
         if (c->post_raw_slot_keys && ns)  // (tests: the slots' 32 bytes verbatim as their trie keys)
-            HIP_TRY(c, hipMemcpyAsync(d_keys + 32ull * na, d_pre + 20ull * na, (size_t)ns * 32, hipMemcpyDeviceToDevice, s));
-        phant::VerifyArgs acc{d_root, 1, nullptr, d_keys, 32, d_nodes, nodes_len, d_noff, nullptr, na, p.acc_status, d_avoff, d_avlen};
-        phant::VerifyArgs sto{p.storage_roots, na, d_sacc, d_keys + 32ull * na, 32, d_nodes, nodes_len, d_noff, nullptr, ns,
-                              p.slot_status, d_svoff, d_svlen};
-        hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s, c->ns_tune);
-        if (e == hipSuccess) e = phant::launch_nodeset_walk(acc, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
-        if (e == hipSuccess) e = phant::launch_prestate_accounts(p, s);
-        if (e == hipSuccess) e = phant::launch_nodeset_walk(sto, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
-        if (e == hipSuccess) e = phant::launch_prestate_slots(p, s);
+            HIP_TRY(c, hipMemcpyAsync(st.keys + 32ull * na, st.pre + 20ull * na, (size_t)ns * 32, hipMemcpyDeviceToDevice, s));
+        hipError_t e = st.resolve(c, s);
         if (e == hipSuccess) e = phant::launch_poststate_actions(q, s);
         if (e == hipSuccess) {
             if (host_order) {
                 q.order = d_order_host;
             } else {
                 uint32_t* d_order = nullptr;
-                e = phant::launch_order_digests(d_keys, q.seg_of, (uint32_t)nk, na + 1u, d_sort, &d_order, &d_flag, 0, s);
+                e = phant::launch_order_digests(st.keys, q.seg_of, (uint32_t)nk, na + 1u, d_sort, &d_order, &d_flag, 0, s);
                 q.order = d_order;
                 if (sink) q.sink_undecided = d_flag;
             }
         }
         if (e == hipSuccess) e = phant::launch_poststate_build(q, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
         if (e != hipSuccess) {
-            c->ns.dirty = true;
+            c->ns.dirty = true;  // (the build's launches write the same workspace)
             return fail(c, PHANT_E_DEVICE, "exec_witness_poststate: launch", e);
         }
     }
-    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
     keys_back.resize(nk * 32);
     *undecided = 0;
-    HIP_TRY(c, back(io->account_status, p.acc_status, na));
-    HIP_TRY(c, back(io->slot_status, p.slot_status, ns));
-    HIP_TRY(c, back(io->storage_roots, q.post_sroots, (size_t)na * 32));
-    HIP_TRY(c, back(io->state_root, q.state_root, 32));
-    HIP_TRY(c, back(keys_back.data(), d_keys, nk * 32));
-    HIP_TRY(c, back(cnt, p.counters, 32));
-    if (d_flag) HIP_TRY(c, back(undecided, d_flag, 4));
+    HIP_TRY(c, back(io->account_status, q.acc_status, na, s));
+    HIP_TRY(c, back(io->slot_status, q.slot_status, ns, s));
+    HIP_TRY(c, back(io->storage_roots, q.post_sroots, (size_t)na * 32, s));
+    HIP_TRY(c, back(io->state_root, q.state_root, 32, s));
+    HIP_TRY(c, back(keys_back.data(), st.keys, nk * 32, s));
+    HIP_TRY(c, back(cnt, q.counters, 32, s));
+    if (d_flag) HIP_TRY(c, back(undecided, d_flag, 4, s));
     uint32_t sink_cnt[2] = {0, 0};
     unsigned long long sink_bytes = 0;
     if (sink) {
         sink->blob.resize(sink->cap_bytes);
         sink->desc.resize(sink->cap_desc);
-        HIP_TRY(c, back(sink->blob.data(), q.sink_blob, sink->cap_bytes));
-        HIP_TRY(c, back(sink->desc.data(), q.sink_desc, (size_t)sink->cap_desc * sizeof(phant::PoststateNodeDesc)));
-        HIP_TRY(c, back(&sink_bytes, q.sink_bytes, 8));
-        HIP_TRY(c, back(sink_cnt, q.sink_cnt, 8));
+        HIP_TRY(c, back(sink->blob.data(), q.sink_blob, sink->cap_bytes, s));
+        HIP_TRY(c, back(sink->desc.data(), q.sink_desc, (size_t)sink->cap_desc * sizeof(phant::PoststateNodeDesc), s));
+        HIP_TRY(c, back(&sink_bytes, q.sink_bytes, 8, s));
+        HIP_TRY(c, back(sink_cnt, q.sink_cnt, 8, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     *need_items = cnt[phant::POST_CNT_ITEMS];

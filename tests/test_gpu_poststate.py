@@ -411,6 +411,103 @@ def test_one_context_small_large_small(P, oracle):
         ctx.close()
 
 
+def _contract(rng, code):
+    return _acc(rng, {int(s): int(s) + 7 for s in rng.integers(1, 1 << 40, 2)}, code)
+
+
+def small_case(oracle, rng):
+    """3 accounts and 4 slots among the keys of a state of ten: a KEEP with two slot writes, a SET with two, a DELETE.
+    -> (doc, parent root, accounts, writes)"""
+    accounts = [_contract(rng, b"\x01"), _contract(rng, b"\x02")] + [_acc(rng) for _ in range(8)]
+    a, b = accounts[0], accounts[1]
+    writes = {a["addr"]: ("keep", {list(a["storage"])[0]: 99, 12345: 6}),
+              b["addr"]: {"nonce": b["nonce"] + 1, "balance": 5, "code": b["code"], "storage": {list(b["storage"])[1]: 3, 777: 8}},
+              accounts[2]["addr"]: None}
+    doc, root = Q.witness_doc(oracle, accounts, writes, rng)
+    return doc, root, accounts, writes
+
+
+def test_one_context_prestate_poststate_advance_interleaved(P, oracle):
+    """The calls that share the pre-state stage (capi.hip: PrestateStage), interleaved on ONE private context over one witness of
+    3 accounts, 4 slots and 2 codes: pre-state, post-state, advance, pre-state, post-state, with a witness of 40 accounts in between
+    that grows the arena and the node-set workspace once.  Every result is what the same call gives on a fresh context (and what
+    the references say); the second pre-state is the first.  What could go wrong here: pointers into the arena that went when it
+    grew, the node-set epoch, the counters' four words against eight."""
+    from tests import advance_ref as A
+    from tests import test_gpu_prestate_more as M
+    rng = np.random.default_rng(62)
+    doc, root, accounts, writes = small_case(oracle, rng)
+    doc = dict(doc, codes=[R._hex(accounts[0]["code"]), R._hex(accounts[1]["code"])])
+    # (40 accounts with 30 slots each: more than the 1 024 nodes the node-set workspace starts with)
+    many = [_acc(rng, {int(s): 1 + int(s) % 9 for s in rng.integers(1, 1 << 60, 30)}, b"\x03") for _ in range(40)] + [_acc(rng) for _ in range(20)]
+    many_writes = {a["addr"]: ("keep", {s: v + 1 for s, v in a["storage"].items()}) for a in many[:40]}
+    big_doc, big_root = Q.witness_doc(oracle, many, many_writes, rng)
+    assert len(big_doc["state"]) > 1024 > len(doc["state"])
+
+    def pre(d, r, ctx):
+        return M._arrays(P, d, r, ctx)
+
+    infos = {}
+
+    def post(d, r, wr, ctx):
+        got, infos[r] = _run(P, oracle, d, r, wr, ctx)
+        return got
+
+    def advance(ctx):
+        w = P.stateless.StatelessWitness.parse_json(R.dumps(doc))
+        nxt = None
+        try:
+            got, nxt = w.advance_arrays(ctx, root, Q.write_arrays(oracle, w.info(), writes))
+            return got, nxt.to_json()
+        finally:
+            w.close()
+            if nxt is not None:
+                nxt.close()
+
+    calls = {"pre": lambda c: pre(doc, root, c), "post": lambda c: post(doc, root, writes, c), "advance": advance,
+             "big pre": lambda c: pre(big_doc, big_root, c), "big post": lambda c: post(big_doc, big_root, many_writes, c)}
+    fresh = {}
+    for name, call in calls.items():
+        c = M._private_context(P)
+        try:
+            fresh[name] = call(c)
+        finally:
+            c.close()
+    info = infos[root]
+    assert (info["n_accounts"], info["n_slots"], info["n_codes"]) == (3, 4, 2) and infos[big_root]["n_accounts"] == 40
+    M._same(fresh["pre"], R.prestate_ref(oracle, doc, root, strict=True), "fresh context")
+    assert fresh["pre"]["n_failed"] == 0 and fresh["big pre"]["n_failed"] == 0 and len(fresh["big pre"]["account_status"]) == 40
+    want = Q.expected(oracle, info, accounts, writes)
+    for name in ("post", "advance"):
+        got = fresh[name][0] if name == "advance" else fresh[name]
+        assert got["n_failed"] == 0 and got["state_root"] == want["state_root"], name
+        assert np.array_equal(got["storage_roots"], want["storage_roots"]), name
+    assert fresh["big post"]["n_failed"] == 0 and fresh["big post"]["state_root"] == oracle.state_root(Q.apply_writes(many, many_writes))
+
+    ctx = M._private_context(P)
+    try:
+        def same(name):
+            got = calls[name](ctx)
+            if name.endswith("pre"):
+                M._same(got, fresh[name], "shared context, " + name)
+            elif name == "advance":
+                A.arrays_equal(got[0], fresh[name][0])
+                assert got[1] == fresh[name][1]
+            else:
+                A.arrays_equal(got, fresh[name])
+            return got
+
+        first = same("pre")
+        same("post")
+        same("big pre")
+        same("big post")
+        same("advance")
+        M._same(same("pre"), first, "the second pre-state against the first")
+        same("post")
+    finally:
+        ctx.close()
+
+
 # ---------------------------------------------------------------- 3b. chosen trie keys (embedded nodes, 63 shared nibbles)
 def _raw_case(P, oracle, pre_slots, upd, rng, neighbours=True):
     """One contract whose storage trie is keyed by the slots' 32 bytes VERBATIM (PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS), inside a
