@@ -122,9 +122,13 @@ enum {
                                           with chosen keys -- 63 shared nibbles, nodes small enough to embed; the accounts stay hashed).
                                           A TEST HOOK ONLY: it changes what the entry point computes (the root is no state root any
                                           more), so a client never sets it; it holds for the context it was set on until set back to 0 */
-    PHANT_DIAG_ADVANCE_ESTIMATE_BYTES  /* phant_exec_witness_advance: > 0: the room estimated for the emitted nodes is this many bytes (and a
+    PHANT_DIAG_ADVANCE_ESTIMATE_BYTES, /* phant_exec_witness_advance: > 0: the room estimated for the emitted nodes is this many bytes (and a
                                           node descriptor per 64 of them), so that a test reaches the run with the counted sizes; 0: the
                                           call's own estimate.  A TEST HOOK ONLY: the result does not depend on it */
+    PHANT_DIAG_VERIFY_LIST_WGS         /* two-tier verify: > 0: the grid that hashes the listed shallow nodes is at most this many workgroups
+                                          (of four waves), so that a test with a few hundred proofs reaches a queue longer than the grid,
+                                          whose waves then stride over it; 0: sized from the batch.  A TEST HOOK ONLY: the result does not
+                                          depend on it */
 };
 PHANT_API int32_t phant_diag_set(phant_ctx *ctx, uint32_t knob, int64_t value);
 

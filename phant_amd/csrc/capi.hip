@@ -446,6 +446,7 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_CODE_HASH_FORM: c->code_form = value == 1 ? 1u : 0u; return PHANT_OK;
         case PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS: c->post_raw_slot_keys = value != 0; return PHANT_OK;
         case PHANT_DIAG_ADVANCE_ESTIMATE_BYTES: c->advance_estimate = value > 0 ? (uint64_t)value : 0u; return PHANT_OK;
+        case PHANT_DIAG_VERIFY_LIST_WGS: c->tune.list_wgs_cap = (uint32_t)(value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : value); return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }

@@ -86,6 +86,7 @@ struct VerifyTune {
     bool no_coop = false;
     bool no_wave = false;  // (A/B: small S = 0 launches through the half-wave kernel, not the wave-per-node one)
     uint32_t* last_form = nullptr; // diagnostics: 0 = S = 0 (every shipped node hashed in place), 1 = two tiers
+    uint32_t list_wgs_cap = 0;     // tests: != 0: the list role's grid is at most this many workgroups (its waves then stride over the queue)
     // diagnostics (phant_verify_bound_experiment), on a workspace a complete launch over the same witness has just left: 1 = only
     // the hashing of that launch (deep tier + everything listed, next to each other), 2 = only a coalesced read of the witness's
     // bytes (a clean stream with next to no VALU), 3 = both next to each other -- what the chip can overlap at best

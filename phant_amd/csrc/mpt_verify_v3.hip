@@ -8,7 +8,9 @@
 //   deep tier (node index d >= S inside its proof): nothing to deduplicate.  hash_deep_kernel hashes these nodes in
 //        place -- wave = 64 consecutive proofs at one depth, lane = proof; a proof's node at depth d is node
 //        proof_first_node[p] + d, its key nibble comes from the key -- with nothing in front of it: it starts at once, on
-//        the helper stream, and is the VALU-bound bulk of the launch.  It clears nothing and needs nothing cleared.
+//        the helper stream, and is the VALU-bound bulk of the launch.  It clears nothing and needs nothing cleared.  In a
+//        batch of all but uniformly long proofs the last depth has no waves of its own: a proof's last node, one
+//        permutation, rides with the wave that has just hashed its parent (deep_role).
 //   shallow tier (d < S), on the main stream, NEXT TO it: copies are COMPARED with one representative per
 //        (root, d, first d key nibbles) group instead of being hashed.
 //        propose_kernel   one lane per (proof, d < S): every multi-block node writes itself into its group's table slot
@@ -446,8 +448,8 @@ PHANT_DEV void store_node_digest(const Args& a, uint32_t j, const Sponge& s) {
 
 // ---------------------------------------------------------------- hash: the list role
 
-// -> false: no chunk q (the queue is shorter)
-PHANT_DEV bool list_role(const Args& a, uint32_t q, const uint32_t lane) {
+// -> the chunks of the queue (wave-uniform); chunk q is hashed if there is one
+PHANT_DEV uint32_t list_role(const Args& a, uint32_t q, const uint32_t lane) {
     // which list chunk q is in: every lane reads the count of a list (two: there are 72), one prefix sum over the wave
     // (72 dependent scalar loads per wave cost 12 us -- every wave of the grid, the real ones included)
     static_assert(N_QUEUE > 64u && N_QUEUE <= 128u, "two lists per lane");
@@ -455,6 +457,9 @@ PHANT_DEV bool list_role(const Args& a, uint32_t q, const uint32_t lane) {
     const uint32_t cnt_b = lane + 64u < N_QUEUE ? a.hdr[cursor_word(queue_class(lane + 64u), (lane + 64u) % STRIPES)] : 0u;
     const uint32_t ch_a = (cnt_a + 63u) / 64u, ch_b = (cnt_b + 63u) / 64u;
     const uint32_t incl_a = wave_inclusive_scan(ch_a, lane);
+    const uint32_t incl_b = lane_u32(incl_a, 63u) + wave_inclusive_scan(ch_b, lane);
+    const uint32_t chunks = lane_u32(incl_b, 63u);
+    if (q >= chunks) return chunks;
     uint32_t li, before, cnt;
     const unsigned long long m_a = __ballot(q < incl_a);
     if (m_a) {
@@ -463,10 +468,7 @@ PHANT_DEV bool list_role(const Args& a, uint32_t q, const uint32_t lane) {
         before = lane_u32(incl_a, l) - lane_u32(ch_a, l);
         cnt = lane_u32(cnt_a, l);
     } else {
-        const uint32_t incl_b = lane_u32(incl_a, 63u) + wave_inclusive_scan(ch_b, lane);
-        const unsigned long long m_b = __ballot(q < incl_b);
-        if (!m_b) return false;
-        const uint32_t l = (uint32_t)__builtin_ctzll(m_b);
+        const uint32_t l = (uint32_t)__builtin_ctzll(__ballot(q < incl_b));  // (q < chunks: some lane's list holds it)
         li = l + 64u;
         before = lane_u32(incl_b, l) - lane_u32(ch_b, l);
         cnt = lane_u32(cnt_b, l);
@@ -509,18 +511,26 @@ PHANT_DEV bool list_role(const Args& a, uint32_t q, const uint32_t lane) {
     if (refp) ns |= NS_LINK_CHECKED | (digest_equals(s, ref) ? NS_LINK_OK : 0u);
     a.nstat[j] = (uint8_t)ns;
     store_node_digest(a, j, s);
-    return true;
+    return chunks;
 }
 
 // ---------------------------------------------------------------- hash: the deep role, in place
 // Wave = 64 consecutive proofs at one depth, lane = proof.  The deep waves cover `levels` depths per pass (deepest last:
 // the leaves, the short chunks, fill the tail); a wave whose proofs are all shorter leaves at once.
 constexpr uint32_t DEEP_LEVELS = 8;  // at most; the launcher picks fewer when the batch's proofs are short (see there)
+constexpr uint32_t NO_RIDE = 0xffffffffu;
 
+// The last node of a proof RIDES with its parent's wave: where nearly every proof of the batch is as long as the average
+// (the launcher decides), the grid has no row for the last depth.  The waves of the row above it -- depth `ride_d` -- hash that
+// depth as well: in the same trip, right behind the parent, when every lane's next node is its proof's last one and all of
+// them have one length below the rate (BASELINE: the 112-byte leaf behind the depth-6 branch -- a permutation for which a
+// wave of its own would go through the whole prologue: proof range -> two offsets -> key nibble -> parent's offset ->
+// reference); in a trip of its own otherwise.  A pass of the grid then covers `levels` + 1 depths.
+//
 // SOLO: the S = 0 form -- no shallow tier runs, so this role is the one to notice a proof_first_node that is not monotone
 template <bool SOLO>
 PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, const uint32_t waves_per_level, const uint32_t levels,
-                         uint32_t (&s_ref)[8][256]) {
+                         const uint32_t ride_d, uint32_t (&s_ref)[8][256]) {
     const uint32_t level = w / waves_per_level;  // 0 .. levels - 1
     // (the grid is whole workgroups: up to three waves behind the last level would take "level = levels" -- the depths the
     // first level's waves come back for -- and hash those nodes a second time)
@@ -530,9 +540,12 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
     const uint32_t nn = 2u * a.v.key_len;
     uint32_t hashed[N_CLASS] = {0, 0, 0, 0, 0, 0, 0, 0};                    // (wave-uniform)
     const uint32_t stat_buf = a.hdr[HDR_PARITY] & 1u;                      // (requested now, used when the wave is through)
+    const uint32_t span = levels + (ride_d != NO_RIDE ? 1u : 0u);          // depths a pass of the grid covers
+    const bool two_depths = ride_d != NO_RIDE && level + 1u == levels;     // this row's waves own depth ride_d + 1 as well
+    bool second = false;                                                   // ... and are in the trip for it
     // (a wave normally makes one trip: everything about the proof is re-read per trip rather than kept in
     // registers across the sponge)
-    for (uint32_t d = a.shallow + level;; d += levels) {
+    for (uint32_t d = a.shallow + level;;) {
         uint32_t first = 0, count = 0, root = 0;
         if (p < a.v.n) {
             first = a.v.proof_first_node[p];
@@ -548,22 +561,42 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
         if (__ballot(d < count) == 0ull) break;
         const uint32_t j = first + d;
         bool active = d < count;
-        uint64_t b = 0;
+        uint64_t b = 0, e = 0;
         uint32_t len = 0;
         if (active) {
-            const uint64_t e = a.v.node_off[j + 1];
+            e = a.v.node_off[j + 1];
             b = a.v.node_off[j];
             active = e >= b && e <= a.v.nodes_len && e - b <= 0x7fffffffull;
             len = active ? (uint32_t)(e - b) : 0u;
             if (!active) a.nstat[j] = 0u;  // (nobody clears the deep nodes' states: "not hashed" is written like any other)
         }
+        // Does node d + 1 ride?  Wave-uniform: every lane that has a node here hashes it, and its next node is its proof's last,
+        // a well-formed one of the one length `ride_len` below the rate whose rate-block window lies inside the blob.  (A lane
+        // whose own offsets are unusable says no: the next trip treats its node d + 1 as any other.)
+        bool ride = false;
+        uint32_t ride_len = 0;
+        if (two_depths && !second && d == ride_d) {
+            bool ok = d >= count;
+            uint32_t ll = 0;
+            if (active && d + 2u == count) {
+                const uint64_t e2 = a.v.node_off[j + 2];
+                if (e2 >= e && e2 - e < RATE && e + RATE <= a.v.nodes_len) {
+                    ok = true;
+                    ll = (uint32_t)(e2 - e);
+                }
+            }
+            ride_len = lane_u32(ll, (uint32_t)__builtin_ctzll(__ballot(d < count)));
+            ride = __ballot(!ok || (d < count && ll != ride_len)) == 0ull;
+        }
         const bool roomy = a.v.nodes_len >= BRANCH_LEN;
         const uint8_t* const ptr = a.v.nodes + (active ? b : 0ull);
         const uint8_t* refp = nullptr;
+        uint32_t nib = 16u;  // the key's nibble for THIS node: where its child's reference is, if it is a full branch
         if (active) {
             const uint8_t* const key = a.v.keys + (uint64_t)a.v.key_len * p;
             const uint32_t nibp = (d >= 1u && d - 1u < nn) ? key_nibble(key, d - 1u) : 16u;
             refp = ref_location(a, j, d, root, nibp, b);
+            if (ride && d < nn) nib = key_nibble(key, d);
         }
         {
             const RefBytes ref = load_ref(refp);
@@ -577,8 +610,11 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
             for (uint32_t c = 0; c < N_CLASS; ++c) hashed[c] += (uint32_t)__popcll(__ballot(active && cls == c));
         }
         // what must survive the sponge: one word of flags (and the lane's proof index)
-        enum : uint32_t { F_ACTIVE = 1u, F_REF = 2u, F_CANON = 4u };
+        // (and, with a node riding, where it starts: `e`, which the wave holds anyway)
+        enum : uint32_t { F_ACTIVE = 1u, F_REF = 2u, F_CANON = 4u, F_NEXT_REF = 8u, F_NIB_SHIFT = 8u };
         uint32_t flags = (active ? F_ACTIVE : 0u) | (refp != nullptr ? F_REF : 0u);
+        // the riding node's parent is this node: its reference is known iff this is 532 bytes long and the key has a nibble for it
+        if (active && len == BRANCH_LEN && nib < 16u) flags |= F_NEXT_REF | (nib << F_NIB_SHIFT);
         Sponge s;
         const bool is532 = active && len == BRANCH_LEN;
         if (roomy && __ballot(is532) != 0ull) {
@@ -608,6 +644,43 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
             a.nstat[j] = (uint8_t)ns;
             store_node_digest(a, j, s);
         }
+        if (ride) {
+            // node d + 1 = bytes [e, e + ride_len) of every active lane (the others run along on the blob's first bytes: the
+            // blob holds a rate block, or no lane could ride); its reference is 32 bytes of the node this lane has just hashed
+            const bool on = (flags & F_ACTIVE) != 0u, known = (flags & F_NEXT_REF) != 0u;
+            const uint8_t* const np = a.v.nodes + (on ? e : 0ull);
+            {
+                const RefBytes ref = load_ref(known ? np - BRANCH_LEN + (4u + 33u * ((flags >> F_NIB_SHIFT) & 15u)) : nullptr);
+                const uint32_t t = threadIdx.x;
+                s_ref[0][t] = ref.lo.x; s_ref[1][t] = ref.lo.y; s_ref[2][t] = ref.lo.z; s_ref[3][t] = ref.lo.w;
+                s_ref[4][t] = ref.hi.x; s_ref[5][t] = ref.hi.y; s_ref[6][t] = ref.hi.z; s_ref[7][t] = ref.hi.w;
+            }
+            hashed[0] += (uint32_t)__popcll(__ballot(on));
+            hash_short_uniform(s, np, ride_len);
+            if (on) {
+                const uint32_t j1 = a.v.proof_first_node[p] + d + 1u;
+                uint32_t ns = NS_HASHED;
+                if (known) {
+                    const uint32_t t = threadIdx.x;
+                    RefBytes ref;
+                    ref.lo = make_uint4(s_ref[0][t], s_ref[1][t], s_ref[2][t], s_ref[3][t]);
+                    ref.hi = make_uint4(s_ref[4][t], s_ref[5][t], s_ref[6][t], s_ref[7][t]);
+                    ns |= NS_LINK_CHECKED | (digest_equals(s, ref) ? NS_LINK_OK : 0u);
+                }
+                a.nstat[j1] = (uint8_t)ns;
+                store_node_digest(a, j1, s);
+            }
+        }
+        // the wave's next depth: a pass further on -- the row that owns two depths takes the second one first, unless it rode
+        if (!two_depths || ride) {
+            d += span;
+        } else if (second) {
+            d += span - 1u;
+            second = false;
+        } else {
+            d += 1u;
+            second = true;
+        }
     }
     // The statistics, as the wave's last instructions: an atomic issued in front of the rate-block loads is waited for with
     // them (gfx950 counts it in vmcnt), and with thousands of waves on a few counters that wait is microseconds per wave
@@ -624,11 +697,12 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
 // three such waves a SIMD has room for two of dedup_kernel's instead of three).
 // SOLO: the S = 0 form.
 template <bool SOLO>
-__global__ void __launch_bounds__(256, 4) hash_deep_kernel(const Args a, const uint32_t waves_per_level, const uint32_t levels) {
+__global__ void __launch_bounds__(256, 4) hash_deep_kernel(const Args a, const uint32_t waves_per_level, const uint32_t levels,
+                                                            const uint32_t ride_d) {
     // the 32 reference bytes wait in LDS while the sponge has the registers ([dword][lane]: conflict-free)
     __shared__ uint32_t s_ref[8][256];
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    deep_role<SOLO>(a, w, threadIdx.x & 63u, waves_per_level, levels, s_ref);
+    deep_role<SOLO>(a, w, threadIdx.x & 63u, waves_per_level, levels, ride_d, s_ref);
 }
 // ---- the S = 0 form of a SMALL batch: a node per HALF WAVE ----
 // The witness of an ordinary block is a few hundred proofs: far fewer nodes than the chip has lanes, and the launch is as long as
@@ -828,8 +902,21 @@ __global__ void __launch_bounds__(256, 4) hash_list_kernel(const Args a) {
     // On the critical path (propose -> dedup -> this -> walk) with fewer waves than the chip has SIMDs, four permutations in
     // a row each, while the deep tier's waves, which are many and in nobody's way, compete for the same issue slots: go first.
     __builtin_amdgcn_s_setprio(2);
-    const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    (void)list_role(a, q, threadIdx.x & 63u);  // (the grid covers the worst case, the dispatcher keeps every SIMD full)
+    // The grid is sized for the queue a well-formed witness leaves (launch_mpt_verify): a chunk per wave, one trip.  A longer
+    // queue -- copies that differ from their representatives, more nodes without a group than the margin allows for -- is
+    // hashed by the same waves striding over it (as the grid's form for ALL of the work that was measured slower).
+    const uint32_t waves = gridDim.x * 4u;
+    uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    for (;;) {
+        // (the lane's index as a value of THIS trip: what a trip derives from it -- the counts' addresses, the scan's
+        // conditions -- would otherwise be computed in front of the loop and kept in registers across the sponge)
+        uint32_t lane = threadIdx.x & 63u;
+        PHANT_PIN_VGPR(lane);
+        const uint32_t chunks = list_role(a, q, lane);
+        q += waves;
+        if (q >= chunks) break;
+        __builtin_amdgcn_s_setprio(2);
+    }
 }
 
 // ---------------------------------------------------------------- walk
@@ -1281,13 +1368,21 @@ hipError_t launch_mpt_verify(const VerifyArgs& v_in, uint32_t total_nodes, uint8
     hipError_t e = hipSuccess;
     const uint32_t pg = (v.n + 255u) / 256u;
     const uint32_t wpl = (v.n + 63u) / 64u;  // waves per level of the deep role
-    // One pass of the deep waves covers `levels` depths below the shallow tier, a wave whose proofs go deeper loops.  Sized
-    // from the batch's average proof length (+ 1): a wave of a level no proof reaches still has to be dispatched and read
-    // its proofs' lengths before it can leave.
+    // One pass of the deep waves covers `deep_levels` depths below the shallow tier, a wave whose proofs go deeper loops.
+    // Sized from the batch's average proof length: a wave of a depth no proof reaches still has to be dispatched, take a
+    // workgroup slot and read its proofs' lengths under a saturated memory system before it can leave (config 3: a quarter of
+    // the grid).  Where the proofs are all but uniformly long -- the mean within an eighth of a node of its ceiling -- the
+    // depths [0, avg_len) are the ones that exist; a mixed batch has proofs longer than its mean, so a depth more is covered.
     const uint64_t avg_len = total_nodes ? (total_nodes + v.n - 1u) / v.n : 0u;
-    const uint32_t deep_levels = avg_len + 1u <= a.shallow ? 1u
-                                 : (uint32_t)(avg_len + 1u - a.shallow < DEEP_LEVELS ? avg_len + 1u - a.shallow : DEEP_LEVELS);
-    const uint32_t deep_wgs = (wpl * deep_levels + 3u) / 4u;
+    const bool uniform = avg_len != 0u && 8ull * total_nodes + v.n >= 8ull * avg_len * v.n;
+    const uint64_t depths = avg_len + (uniform ? 0u : 1u);
+    const uint32_t deep_levels = depths <= a.shallow ? 1u : (uint32_t)(depths - a.shallow < DEEP_LEVELS ? depths - a.shallow : DEEP_LEVELS);
+    // In such a uniform batch the last depth gets no row of waves: a proof's last node rides with the wave of its parent
+    // (deep_role), if both are the deep tier's and one pass reaches them.
+    const bool ride = uniform && avg_len >= a.shallow + 2ull && avg_len - a.shallow <= DEEP_LEVELS;
+    const uint32_t deep_rows = ride ? deep_levels - 1u : deep_levels;
+    const uint32_t ride_d = ride ? a.shallow + deep_rows - 1u : NO_RIDE;
+    const uint32_t deep_wgs = (wpl * deep_rows + 3u) / 4u;
     if (tune.last_form) *tune.last_form = (a.shallow == 0u || total_nodes == 0u) ? 0u : 1u;
     if (a.shallow == 0u || total_nodes == 0u) {
         // S = 0: clear, hash every node in place, walk on the node states.  No lists, tables or helper stream.
@@ -1310,7 +1405,7 @@ hipError_t launch_mpt_verify(const VerifyArgs& v_in, uint32_t total_nodes, uint8
                 hipLaunchKernelGGL(hash_coop_kernel, dim3((uint32_t)((halves + 7u) / 8u)), dim3(256), 0, st, a, deep_levels);
             }
         else if (total_nodes)
-            hipLaunchKernelGGL(hash_deep_kernel<true>, dim3(deep_wgs), dim3(256), 0, st, a, wpl, deep_levels);
+            hipLaunchKernelGGL(hash_deep_kernel<true>, dim3(deep_wgs), dim3(256), 0, st, a, wpl, deep_rows, ride_d);
         hipLaunchKernelGGL(walk_kernel<true>, dim3(pg), dim3(256), 0, st, a);
         return hipGetLastError();
     }
@@ -1318,9 +1413,22 @@ hipError_t launch_mpt_verify(const VerifyArgs& v_in, uint32_t total_nodes, uint8
     const uint32_t sg = (uint32_t)((lanes + 255u) / 256u);
     const bool two = side && side->stream && side->fork && side->join && !tune.serial;
     hipStream_t hs = two ? side->stream : st;
-    // grid bound of the list role: every shallow node listed (64-node chunks, 4 waves per workgroup) + a short chunk per list
-    const uint64_t listed = lanes < total_nodes ? lanes : total_nodes;
-    const uint32_t list_wgs = (uint32_t)((listed + 255u) / 256u) + (N_QUEUE + 3u) / 4u;
+    // Grid of the list role: a wave per 64-node chunk (4 waves per workgroup) of the queue a well-formed witness leaves, + a
+    // short chunk per list.  Listed are the representatives -- at most one per group, min(16^d n_roots, n) at level d -- and
+    // the nodes without a group, for which an eighth more is allowed; never more than every shallow node.  Whatever else a
+    // witness gets listed (copies that differ) the same waves hash in further trips (hash_list_kernel).  Sized for every
+    // shallow node, as it was, config 3's grid was 1 971 workgroups for a queue of ~220: the surplus ones each took a hash
+    // workgroup's slot at the tail of the launch's critical chain to read the counts and leave.
+    uint64_t listed = 0, groups = (uint64_t)(v.n_roots ? v.n_roots : 1u);
+    for (uint32_t d = 0; d < a.shallow; ++d) {
+        listed += groups < v.n ? groups : v.n;
+        if (groups < v.n) groups *= 16u;
+    }
+    listed += listed / 8u;
+    if (listed > lanes) listed = lanes;
+    if (listed > total_nodes) listed = total_nodes;
+    uint32_t list_wgs = (uint32_t)((listed + 255u) / 256u) + (N_QUEUE + 3u) / 4u;
+    if (tune.list_wgs_cap && list_wgs > tune.list_wgs_cap) list_wgs = tune.list_wgs_cap;
     // An otherwise unused dynamic LDS allocation caps the hash workgroups per CU while the shallow tier's memory-bound
     // kernels run next to them (VerifyTune::hash_lds): a fourth hash wave per SIMD would take the registers they need
     const uint32_t hash_lds = two ? tune.hash_lds : 0u;
@@ -1345,7 +1453,7 @@ hipError_t launch_mpt_verify(const VerifyArgs& v_in, uint32_t total_nodes, uint8
         }
         if (tune.diag & 1u) {
             const uint32_t lds = tune.diag == 3u ? hash_lds : 0u;  // (capped only where something memory-bound runs beside it)
-            hipLaunchKernelGGL(hash_deep_kernel<false>, dim3(deep_wgs), dim3(256), lds, hs, a, wpl, deep_levels);
+            hipLaunchKernelGGL(hash_deep_kernel<false>, dim3(deep_wgs), dim3(256), lds, hs, a, wpl, deep_rows, ride_d);
             hipLaunchKernelGGL(hash_list_kernel, dim3(list_wgs), dim3(256), lds ? lds + 8192u : 0u, st, a);
         }
         if (tune.diag & 2u) {
@@ -1376,7 +1484,7 @@ hipError_t launch_mpt_verify(const VerifyArgs& v_in, uint32_t total_nodes, uint8
     mark(0);
     hipLaunchKernelGGL(propose_kernel, dim3(sg), dim3(256), 0, st, a);
     mark(1);
-    hipLaunchKernelGGL(hash_deep_kernel<false>, dim3(deep_wgs), dim3(256), hash_lds, hs, a, wpl, deep_levels);
+    hipLaunchKernelGGL(hash_deep_kernel<false>, dim3(deep_wgs), dim3(256), hash_lds, hs, a, wpl, deep_rows, ride_d);
     mark(2);
     if (two && (e = hipEventRecord(side->join, side->stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(dedup_kernel, dim3(sg), dim3(256), 0, st, a);

@@ -234,8 +234,10 @@ PHANT_DEV void hash_short_uniform(Sponge& s, const uint8_t* __restrict__ p, uint
 }
 
 // ---------------------------------------------------------------- the queue of list chunks
-// Wave q hashes chunk q (64 nodes of one list) and exits; the grid covers the worst case and the dispatcher keeps every
-// SIMD full.  A short last chunk repeats its last node (same results stored twice) so that no lane is ever idle-masked.
+// Wave q hashes chunk q (64 nodes of one list) and exits; the grid covers the queue and the dispatcher keeps every
+// SIMD full (the per-proof pipeline sizes its grid for the queue a well-formed witness leaves, and a wave comes back for
+// chunk q + the grid's waves where the queue is longer: mpt_verify_v3.hip).  A short last chunk repeats its last node
+// (same results stored twice) so that no lane is ever idle-masked.
 // The chunk queue is the concatenation of the lists in this order: classes by falling rate-block count -- 8+ blocks, 7, 6,
 // 5, [532-byte list], 4 (others), 3, 2, 1 --, inside a class the stripes.
 constexpr uint32_t N_QUEUE = N_LIST * STRIPES;  // 72
