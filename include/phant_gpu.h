@@ -598,7 +598,8 @@ PHANT_API int32_t phant_block_transactions_ex_dev(phant_ctx *ctx, const phant_tx
  * Tuple k belongs to transaction j when auth_first[j] <= k < auth_first[j + 1]; auth_first NULL: the call has no tuples.
  * Per account: sends[j] = the length of row j's sequence; roles[j] = who named the row (PHANT_ROLE_*: the sender or recipient of a
  * participating transaction, the authority of a PHANT_SIG_OK tuple of one, a probe).  Per probe (any further address the caller wants
- * located: coinbase, withdrawal recipients, access-list and delegation targets): probe_row = row_of(probe).
+ * located: coinbase, withdrawal recipients, access-list and delegation targets): probe_row = row_of(probe).  (The targets of the
+ * block's access lists need no probes: phant_block_access_lists, below, decodes the lists and joins them itself.)
  * first_bad (always written): the least i whose state_flags carry an error bit, n if none (0 for n == 0); n_undetermined.
  *
  * Any output pointer may be NULL.  PHANT_E_INVALID_ARG, before anything is indexed with the offending value: a wrong struct_size, an
@@ -676,6 +677,88 @@ typedef struct phant_txstate_out {
 } phant_txstate_out;
 PHANT_API int32_t phant_block_txs_prestate(phant_ctx *ctx, const phant_txstate_in *in, phant_txstate_out *out);
 PHANT_API int32_t phant_block_txs_prestate_dev(phant_ctx *ctx, const phant_txstate_in *in, phant_txstate_out *out);
+
+/* ------------------------------------------------- a block's access lists: entries, warm sets and their witness rows
+ * phant_block_access_lists decodes the access lists (EIP-2930, transaction types 1 - 4) of a block's transactions and joins every
+ * entry with the pre-state rows of the witness: what `processTransaction` turns into state before the EVM runs
+ * (src/blockchain/blockchain.zig:284-295: putAccessedAccount, putAccessedStorageKeys) and what the EVM host's getStorage needs for
+ * every warm slot.  tests/access_ref.py is the same definition in plain Python.
+ *
+ * Transaction i's list is the payload txs[al_off[i], al_off[i] + al_len[i]): al_off / al_len straight from phant_txs_out; al_len == 0
+ * is an empty list (a legacy transaction, an undecodable row, an empty list).  The call does not trust the counts of the transactions
+ * call: it walks every span itself, by the rules phant_block_transactions applies -- [[address20, [key32, ...]], ...], canonical RLP,
+ * nothing else inside a tuple --, and reads nothing outside the span.  A span that is not such a payload gets PHANT_AL_MALFORMED and
+ * contributes NO tuple (tuple_first[i + 1] == tuple_first[i], warm_addresses = warm_keys = 0); it is a flag, never an error.
+ *
+ * A TUPLE is one [address, [keys ...]] item.  Tuples are numbered through the block in order (tuple_first[i] = the first of
+ * transaction i), keys likewise (key_first[e] = the first of tuple e).  With row_of as phant_block_txs_prestate defines it:
+ *   account_row[e] = row_of(address[e]): the LOWEST row with that address over all 20 bytes, else PHANT_ROW_NONE
+ *   tuple_same[e]  = the least tuple e' of the SAME transaction with address[e'] == address[e] (e itself: a first occurrence)
+ *   slot_row[k]    = with r = the account_row of k's tuple: the least s in [slot_first[r], slot_first[r + 1]) with slots[s] == key[k]
+ *                    over all 32 bytes; PHANT_ROW_NONE when r is NONE or there is none (a slot of ANOTHER row with that address or
+ *                    that key does not count)
+ *   key_same[k]    = the least key k' of the same transaction with key[k'] == key[k] under an equal address, across tuples as well
+ *   warm_addresses[i], warm_keys[i] = the first occurrences among i's tuples / keys: the sizes of the sets putAccessed* builds
+ *   PHANT_AL_DUPLICATES (advisory) = some tuple or key of the row is not a first occurrence
+ * n_tuples, n_keys: the totals over well-formed rows; n_missing_accounts, n_missing_slots (advisory: a block need not touch what its
+ * lists name): the FIRST occurrences whose account_row / slot_row is PHANT_ROW_NONE; first_malformed: the least flagged i, n if none.
+ * These five are always written.  n_accounts == 0: nothing is joined, every row is NONE, slot_first / slots / n_slots are not looked at.
+ *
+ * Any output pointer may be NULL.  tuple_cap / key_cap: the rows the per-tuple / per-key buffers hold (key_first: tuple_cap + 1
+ * entries); a buffer nobody wants has no capacity to exceed.  If n_tuples > tuple_cap or n_keys > key_cap the call still returns
+ * PHANT_OK with the totals, the per-transaction outputs written, and touches NONE of the per-tuple and per-key buffers: call again.
+ * PHANT_E_INVALID_ARG, before anything is indexed with the offending value: a wrong struct_size, reserved != 0, a NULL input whose
+ * count is not zero, a span that leaves [0, tx_bytes), slot_first that does not run from 0 to n_slots without going backwards.
+ * PHANT_E_UNSUPPORTED: the spans together hold 2^31 bytes or more (fewer than 2^27 tuples and 2^26 keys fit below that), or
+ * n_accounts or n_slots is above 2^30 -- the tables index with 32 bits and stay at most half full.  n == 0: PHANT_OK, zero totals.
+ * Host form: checked on the host before anything is copied; only the bytes of the spans cross the bus, in one staged upload with the
+ * tables; the launches; one copy back of the span that ends at the last wanted output; one synchronisation.  Device form: every array
+ * is device memory (al_off 8-byte, uint32_t arrays 4-byte aligned), both structs host memory; the spans and slot_first are checked by
+ * a kernel whose verdict the host reads before any other kernel uses them; the call synchronises the ctx stream. */
+#define PHANT_AL_MALFORMED 0x1u  /* the span is no well-formed access-list payload; the row contributes nothing */
+#define PHANT_AL_DUPLICATES 0x2u /* advisory: an address or an (address, key) pair repeats in the row */
+typedef struct phant_access_in {
+    uint32_t struct_size; /* = sizeof(phant_access_in) */
+    uint32_t n;           /* transaction rows */
+    uint32_t n_accounts;  /* pre-state rows */
+    uint32_t n_slots;
+    /* per transaction, straight from phant_txs_in / phant_txs_out */
+    const uint8_t *txs;
+    uint64_t tx_bytes;
+    const uint64_t *al_off; /* n */
+    const uint32_t *al_len; /* n */
+    /* the pre-state tables, straight from phant_exec_witness_info */
+    const uint8_t *addresses;   /* n_accounts x 20 */
+    const uint32_t *slot_first; /* n_accounts + 1 */
+    const uint8_t *slots;       /* n_slots x 32 */
+    uint32_t reserved[2];       /* 0 */
+} phant_access_in;
+typedef struct phant_access_out {
+    uint32_t struct_size;        /* = sizeof(phant_access_out) */
+    uint32_t n_tuples;           /* result */
+    uint32_t n_keys;             /* result */
+    uint32_t n_missing_accounts; /* result */
+    uint32_t n_missing_slots;    /* result */
+    uint32_t first_malformed;    /* result */
+    uint32_t tuple_cap;          /* in: rows of the per-tuple buffers */
+    uint32_t key_cap;            /* in: rows of the per-key buffers */
+    /* per transaction */
+    uint32_t *tuple_first;    /* n + 1 */
+    uint32_t *al_flags;       /* PHANT_AL_* */
+    uint32_t *warm_addresses;
+    uint32_t *warm_keys;
+    /* per tuple */
+    uint8_t *address;         /* 20 */
+    uint32_t *key_first;      /* n_tuples + 1 */
+    uint32_t *account_row;
+    uint32_t *tuple_same;
+    /* per key */
+    uint8_t *key;             /* 32 */
+    uint32_t *slot_row;
+    uint32_t *key_same;
+} phant_access_out;
+PHANT_API int32_t phant_block_access_lists(phant_ctx *ctx, const phant_access_in *in, phant_access_out *out);
+PHANT_API int32_t phant_block_access_lists_dev(phant_ctx *ctx, const phant_access_in *in, phant_access_out *out);
 
 /* ------------------------------------------------------- proof verification
  * ABSENT in the reference: this is the call the TODO at

@@ -76,6 +76,8 @@ SYMBOLS = {
     "phant_block_transactions_ex_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_block_access_lists": (_i32, [_vp, _vp, _vp]),
+    "phant_block_access_lists_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_verify_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_mpt_verify_batch_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
@@ -265,6 +267,26 @@ class PhantTxstateOut(C.Structure):
     """phant_txstate_out (include/phant_gpu.h)"""
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "first_bad", "n_undetermined", "reserved")] + \
                [(name, C.c_void_p) for name, _, _, _ in TXSTATE_OUTPUTS]
+
+
+AL_MALFORMED, AL_DUPLICATES = 1, 2
+# phant_access_out's arrays in the struct's order: (name, numpy dtype, elements per row, the count its rows follow, rows beyond that count)
+ACCESS_OUTPUTS = (("tuple_first", "u4", 1, "n", 1), ("al_flags", "u4", 1, "n", 0), ("warm_addresses", "u4", 1, "n", 0), ("warm_keys", "u4", 1, "n", 0),
+                  ("address", "u1", 20, "n_tuples", 0), ("key_first", "u4", 1, "n_tuples", 1), ("account_row", "u4", 1, "n_tuples", 0),
+                  ("tuple_same", "u4", 1, "n_tuples", 0), ("key", "u1", 32, "n_keys", 0), ("slot_row", "u4", 1, "n_keys", 0), ("key_same", "u4", 1, "n_keys", 0))
+
+
+class PhantAccessIn(C.Structure):
+    """phant_access_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n", "n_accounts", "n_slots")] + \
+               [("txs", C.c_void_p), ("tx_bytes", C.c_uint64), ("al_off", C.c_void_p), ("al_len", C.c_void_p), ("addresses", C.c_void_p),
+                ("slot_first", C.c_void_p), ("slots", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+class PhantAccessOut(C.Structure):
+    """phant_access_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_tuples", "n_keys", "n_missing_accounts", "n_missing_slots", "first_malformed",
+                                                "tuple_cap", "key_cap")] + [(name, C.c_void_p) for name, _, _, _, _ in ACCESS_OUTPUTS]
 
 
 class PhantProveOut(C.Structure):

@@ -24,6 +24,7 @@
 #include "headers.h"
 #include "transactions.h"
 #include "txstate.h"
+#include "access_lists.h"
 #include "trie_build.h"
 #include "witness.h"
 #include "host_rlp.h"
@@ -991,6 +992,54 @@ static int32_t block_txs_prestate_impl(phant_ctx* c, const phant_txstate_in* in,
 int32_t phant_block_txs_prestate(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out) { return block_txs_prestate_impl(c, in, out, false); }
 
 int32_t phant_block_txs_prestate_dev(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out) { return block_txs_prestate_impl(c, in, out, true); }
+
+/* ------------------------------------------------- a block's access lists against the pre-state tables (access_lists.hip.h) */
+
+static int32_t block_access_lists_impl(phant_ctx* c, const phant_access_in* in, phant_access_out* out, bool dev) {
+    const char* const who = dev ? "block_access_lists_dev" : "block_access_lists";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_access_in) || out->struct_size != sizeof(phant_access_out)) return bad("wrong struct_size");
+    if (in->reserved[0] != 0u || in->reserved[1] != 0u) return bad("reserved is not 0");
+    if (in->n && (!in->al_off || !in->al_len)) return bad("null al_off / al_len");
+    if (in->n && in->tx_bytes && !in->txs) return bad("null txs");
+    if (in->n_accounts && (!in->addresses || !in->slot_first)) return bad("null addresses / slot_first");
+    if (in->n_accounts && in->n_slots && !in->slots) return bad("null slots");
+    if (in->n_accounts > (1u << 30) || (in->n_accounts && in->n_slots > (1u << 30)))
+        return fail(c, PHANT_E_UNSUPPORTED, (std::string(who) + ": more than 2^30 pre-state rows or slots").c_str());
+    if (dev) {  // (kernels read these as words; the outputs arrive by device-to-device copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->al_off;
+        const uintptr_t w4 = (uintptr_t)in->al_len | (uintptr_t)in->slot_first | (uintptr_t)out->tuple_first | (uintptr_t)out->al_flags |
+                             (uintptr_t)out->warm_addresses | (uintptr_t)out->warm_keys | (uintptr_t)out->key_first | (uintptr_t)out->account_row |
+                             (uintptr_t)out->tuple_same | (uintptr_t)out->slot_row | (uintptr_t)out->key_same;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    if (in->n == 0) {  // no totals, and the one entry of tuple_first and of key_first
+        out->n_tuples = out->n_keys = out->n_missing_accounts = out->n_missing_slots = out->first_malformed = 0;
+        const uint32_t zero = 0;
+        if (dev && (out->tuple_first || out->key_first)) {
+            DeviceGuard g(c->device);
+            if (out->tuple_first) HIP_TRY(c, hipMemcpyAsync(out->tuple_first, &zero, 4, hipMemcpyHostToDevice, c->stream));
+            if (out->key_first) HIP_TRY(c, hipMemcpyAsync(out->key_first, &zero, 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        } else if (!dev) {
+            if (out->tuple_first) out->tuple_first[0] = zero;
+            if (out->key_first) out->key_first[0] = zero;
+        }
+        return PHANT_OK;
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    const int32_t rc = phant::block_access_lists(c->ws, c->stream, *in, *out, dev, c->ns_salt, err);
+    if (rc) return fail(c, rc, err.c_str());
+    return PHANT_OK;
+}
+
+int32_t phant_block_access_lists(phant_ctx* c, const phant_access_in* in, phant_access_out* out) { return block_access_lists_impl(c, in, out, false); }
+
+int32_t phant_block_access_lists_dev(phant_ctx* c, const phant_access_in* in, phant_access_out* out) { return block_access_lists_impl(c, in, out, true); }
 
 int32_t phant_diag_secp_op(phant_ctx* c, uint32_t op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out) {
     if (!c) return PHANT_E_INVALID_ARG;

@@ -142,6 +142,28 @@ TXST_HD void sender_rule(const RowIn& r, RowOut& o) {
     if (less288(r.balance, r.incl)) o.flags |= PHANT_TXST_NEEDS_INFLOW | (r.i == 0u ? PHANT_TXST_BALANCE_SHORT : 0u);
 }
 
+// ---- an address as five words, where it is looked for first, the compare over all of it (the address table below; access_lists.hip.h)
+TXST_HD void load_addr(const uint8_t* p, uint32_t w[5]) {
+    for (int k = 0; k < 5; ++k) w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+}
+// where an address is looked for first: a keyed mix of all of it (witness keys are attacker-chosen bytes; without the key nobody aims
+// them at one slot)
+TXST_HD uint32_t home_slot(const uint32_t w[5], uint32_t salt0, uint32_t salt1) {
+    uint32_t h = salt0;
+    for (int k = 0; k < 5; ++k) {
+        h = (h ^ w[k]) * 0x9E3779B1u;
+        h ^= h >> 15;
+        h = (h + salt1) * 0x85EBCA77u;
+        h ^= h >> 13;
+    }
+    return h * 0xC2B2AE3Du;
+}
+TXST_HD bool same_addr(const uint8_t* p, const uint32_t w[5]) {
+    uint32_t v[5];
+    load_addr(p, v);
+    return v[0] == w[0] && v[1] == w[1] && v[2] == w[2] && v[3] == w[3] && v[4] == w[4];
+}
+
 #ifndef PHANT_TXST_RULE_ONLY
 
 enum : uint32_t { CTL_WORDS = 4 };  // ctl[0]: what the arguments' check found, [1]: max(n - i) over the flagged rows, [2]: undetermined rows
@@ -164,27 +186,6 @@ struct Args {
     uint32_t* agg;          // tiles x SEG_WORDS: a tile's last
     uint32_t* tp;           // tiles x SEG_WORDS: what runs into a tile
 };
-
-TXST_HD void load_addr(const uint8_t* p, uint32_t w[5]) {
-    for (int k = 0; k < 5; ++k) w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
-}
-// where an address is looked for first: a keyed mix of all of it (witness keys are attacker-chosen bytes; without the key nobody aims
-// them at one slot)
-TXST_HD uint32_t home_slot(const uint32_t w[5], uint32_t salt0, uint32_t salt1) {
-    uint32_t h = salt0;
-    for (int k = 0; k < 5; ++k) {
-        h = (h ^ w[k]) * 0x9E3779B1u;
-        h ^= h >> 15;
-        h = (h + salt1) * 0x85EBCA77u;
-        h ^= h >> 13;
-    }
-    return h * 0xC2B2AE3Du;
-}
-__device__ inline bool same_addr(const uint8_t* p, const uint32_t w[5]) {
-    uint32_t v[5];
-    load_addr(p, v);
-    return v[0] == w[0] && v[1] == w[1] && v[2] == w[2] && v[3] == w[3] && v[4] == w[4];
-}
 
 __global__ void __launch_bounds__(256) txst_check_args_kernel(Args a) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;

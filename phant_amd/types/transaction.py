@@ -1,6 +1,7 @@
 """A block's transactions before execution in one call (`block_transactions` <-> phant_block_transactions: the decoded fields of
 src/types/transaction.zig:152-273, both hashes, the senders, src/blockchain/blockchain.zig:355-381 `calculateIntrinsicCost` and the
-state-free rules of `checkTransaction` / `validateTransaction`), and
+state-free rules of `checkTransaction` / `validateTransaction`), the same rows against the pre-state (`against_prestate`), the access
+lists decoded and joined with the witness's tables (`access_lists` <-> phant_block_access_lists, blockchain.zig:284-295), and
 transaction hashes of a whole block in one launch <-> src/types/transaction.zig:79-85 `Tx.hash`
 (:183-187 legacy = keccak256(rlp(tx)); :223-228 / :256-261 typed = keccak256(type || rlp(tx))): in every case
 the Keccak-256 of the transaction's EIP-2718 encoding, the bytes a block body carries."""
@@ -178,3 +179,59 @@ def against_prestate(bt: BlockTransactions, prestate, witness_info, fork, probe=
     out = L.PhantTxstateOut(C.sizeof(L.PhantTxstateOut), 0, 0, 0, *[ptr(arrays[name]) for name, _, _, _ in L.TXSTATE_OUTPUTS])
     ctx.check(ctx._lib.phant_block_txs_prestate(ctx.handle, C.byref(arg), C.byref(out)))
     return TransactionsAgainstPrestate(arrays, int(out.first_bad), int(out.n_undetermined))
+
+
+class AccessLists:
+    """What phant_block_access_lists answers: one numpy array per output of include/phant_gpu.h's phant_access_out (address as
+    (n_tuples, 20), key as (n_keys, 32) uint8), the five totals, and `lists`: per transaction the list of (address, [keys]) as bytes."""
+    MALFORMED, DUPLICATES, ROW_NONE = L.AL_MALFORMED, L.AL_DUPLICATES, L.ROW_NONE
+
+    def __init__(self, arrays, n_missing_accounts, n_missing_slots, first_malformed):
+        self.n_missing_accounts, self.n_missing_slots, self.first_malformed = n_missing_accounts, n_missing_slots, first_malformed
+        self.__dict__.update(arrays)
+        self.n, self.n_tuples, self.n_keys = len(self.al_flags), len(self.account_row), len(self.slot_row)
+
+    def entries(self, i):
+        """transaction i's access list: [(address, [key, ...]), ...]"""
+        return [(self.address[e].tobytes(), [self.key[k].tobytes() for k in range(int(self.key_first[e]), int(self.key_first[e + 1]))])
+                for e in range(int(self.tuple_first[i]), int(self.tuple_first[i + 1]))]
+
+    @property
+    def lists(self):
+        return [self.entries(i) for i in range(self.n)]
+
+    def malformed(self, i) -> bool:
+        return bool(int(self.al_flags[i]) & L.AL_MALFORMED)
+
+
+def access_lists(bt, prestate=None, ctx: Context | None = None) -> AccessLists:
+    """A block's access lists decoded and joined with the pre-state tables <-> phant_block_access_lists: every [address, [keys]] entry,
+    which witness row every address and every (address, key) pair is, the first occurrences (the warm sets blockchain.zig:284-295
+    builds) and what the witness lacks.  bt: `block_transactions` of the block, or anything with its `blob`, `al_off` and `al_len`
+    (a dict will do); prestate: `StatelessWitness.info()` of phant_amd/stateless.py (anything with n_accounts, addresses, slot_first,
+    n_slots and slots), None: nothing is joined and every row is ROW_NONE."""
+    ctx = ctx or default_context()
+    get = (lambda k: bt[k]) if isinstance(bt, dict) else (lambda k: getattr(bt, k))  # noqa: E731
+    blob = np.ascontiguousarray(get("blob"), np.uint8).reshape(-1)
+    al_off, al_len = np.ascontiguousarray(get("al_off"), np.uint64), np.ascontiguousarray(get("al_len"), np.uint32)
+    n = len(al_len)
+    if len(al_off) != n:
+        raise ValueError("al_off and al_len differ in length")
+    na = int(prestate["n_accounts"]) if prestate is not None else 0
+    ns = int(prestate["n_slots"]) if na else 0
+    addresses = np.ascontiguousarray(np.asarray(prestate["addresses"], np.uint8).reshape(-1, 20)) if na else None
+    slot_first = np.ascontiguousarray(prestate["slot_first"], np.uint32) if na else None
+    slots = np.ascontiguousarray(np.asarray(prestate["slots"], np.uint8).reshape(-1, 32)) if ns else None
+    if na and (len(addresses) < na or len(slot_first) < na + 1 or (ns and len(slots) < ns)):
+        raise ValueError("the pre-state tables are shorter than their counts")
+    total = int(al_len.sum(dtype=np.uint64))
+    rows = {"n": n, "n_tuples": total // 23, "n_keys": total // 33}  # no span has more tuples or keys than its bytes allow
+    arrays = {name: np.zeros((rows[r] + extra, k) if k > 1 else rows[r] + extra, dtype) for name, dtype, k, r, extra in L.ACCESS_OUTPUTS}
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    arg = L.PhantAccessIn(C.sizeof(L.PhantAccessIn), n, na, ns, ptr(blob), blob.size, ptr(al_off), ptr(al_len), ptr(addresses), ptr(slot_first), ptr(slots))
+    out = L.PhantAccessOut(C.sizeof(L.PhantAccessOut), 0, 0, 0, 0, 0, rows["n_tuples"], rows["n_keys"],
+                           *[arrays[name].ctypes.data for name, _, _, _, _ in L.ACCESS_OUTPUTS])
+    ctx.check(ctx._lib.phant_block_access_lists(ctx.handle, C.byref(arg), C.byref(out)))
+    got = {"n": n, "n_tuples": int(out.n_tuples), "n_keys": int(out.n_keys)}
+    arrays = {name: arrays[name][:got[r] + extra] for name, _, _, r, extra in L.ACCESS_OUTPUTS}
+    return AccessLists(arrays, int(out.n_missing_accounts), int(out.n_missing_slots), int(out.first_malformed))
