@@ -2235,10 +2235,8 @@ int32_t phant_mpt_root_nodes(phant_ctx* c, const uint8_t* keys, const uint32_t* 
     if (n && (!key_off || !val_off)) return fail(c, PHANT_E_INVALID_ARG, "mpt_root_nodes: null pointer");
     DeviceGuard g(c->device);
     std::string err;
-    const uint32_t zero32[1] = {0};
-    const uint64_t zero64[1] = {0};
-    int32_t rc = phant::trie_forest_host(c->ws, c->stream, keys, n ? key_off : zero32, vals, n ? val_off : zero64, n,
-                                         seg_first, n_tries, roots, err, node_rlp, node_cap, node_len);
+    int32_t rc = phant::trie_forest_host(c->ws, c->stream, phant::HostPairs{keys, key_off, vals, val_off, n, seg_first, n_tries}, roots, err,
+                                         phant::RootNodes{node_rlp, node_len, node_cap});
     if (rc) return fail(c, rc, err.c_str());
     return PHANT_OK;
 }
@@ -2256,7 +2254,7 @@ int32_t phant_mpt_root(phant_ctx* c, const uint8_t* keys, const uint32_t* key_of
     if (n && (!key_off || !val_off)) return fail(c, PHANT_E_INVALID_ARG, "mpt_root: null pointer");
     DeviceGuard g(c->device);
     std::string err;
-    int32_t rc = phant::trie_root_host(c->ws, c->stream, keys, key_off, vals, val_off, n, out, err);
+    int32_t rc = phant::trie_forest_host(c->ws, c->stream, phant::HostPairs{keys, key_off, vals, val_off, n}, out, err);
     if (rc) return fail(c, rc, err.c_str());
     return PHANT_OK;
 }
@@ -2269,8 +2267,7 @@ int32_t phant_mpt_root_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* 
     DeviceGuard g(c->device);
     std::string err;
     TimedRegion t(c);
-    const int32_t rc = phant::trie_root_dev(c->ws, c->stream, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n,
-                                            d_root, err);
+    const int32_t rc = phant::trie_root_dev(c->ws, c->stream, phant::TriePairs{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, nullptr, 1, d_root}, err);
     if (rc) return fail(c, rc, err.c_str());
     return PHANT_OK;
 }
@@ -2302,17 +2299,10 @@ int32_t phant_mpt_prove_nodeset(phant_ctx* c, const uint8_t* keys, const uint32_
     out->nodes_len = 0;
     DeviceGuard g(c->device);
     std::string err;
-    const uint32_t zero32[1] = {0};
-    const uint64_t zero64[1] = {0};
     phant::ProveArgs a;
     prove_args_of(out, a);
-    a.qkeys = qkeys;
-    a.qkey_off = n_queries ? qkey_off : zero32;
-    a.q_trie = q_trie;
-    a.q_flags = q_flags;
-    a.n_queries = n_queries;
-    const int32_t rc = phant::prove_nodeset_host(c->ws, c->stream, keys, n ? key_off : zero32, vals, n ? val_off : zero64, n, seg_first,
-                                                 n_tries, a, err);
+    a.q = phant::ProveQueries{qkeys, qkey_off, q_trie, q_flags, n_queries};
+    const int32_t rc = phant::prove_nodeset_host(c->ws, c->stream, phant::HostPairs{keys, key_off, vals, val_off, n, seg_first, n_tries}, a, err);
     if (rc) return fail(c, rc, err.c_str());
     out->total_nodes = a.total_nodes;
     out->nodes_len = a.nodes_len;
@@ -2340,13 +2330,9 @@ int32_t phant_mpt_prove_nodeset_dev(phant_ctx* c, const uint8_t* d_keys, const u
     std::string err;
     phant::ProveArgs a;
     prove_args_of(out, a);
-    a.qkeys = d_qkeys;
-    a.qkey_off = d_qkey_off;
-    a.q_trie = d_q_trie;
-    a.q_flags = d_q_flags;
-    a.n_queries = n_queries;
-    const int32_t rc = phant::prove_nodeset_dev(c->ws, c->stream, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first,
-                                                n_tries, a, err);
+    a.q = phant::ProveQueries{d_qkeys, d_qkey_off, d_q_trie, d_q_flags, n_queries};
+    const int32_t rc = phant::prove_nodeset_dev(c->ws, c->stream, phant::TriePairs{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries}, a,
+                                                err);
     if (rc) return fail(c, rc, err.c_str());
     out->total_nodes = a.total_nodes;
     out->nodes_len = a.nodes_len;
@@ -2404,8 +2390,7 @@ int32_t phant_state_root(phant_ctx* c, const uint8_t* addrs, const uint64_t* non
         return fail(c, PHANT_E_INVALID_ARG, "state_root: null pointer");
     DeviceGuard g(c->device);
     std::string err;
-    int32_t rc = phant::state_root_host(c->ws, c->stream, addrs, nonces, balances, code, code_off, slot_keys,
-                                        slot_vals, slot_first, n, out, err);
+    int32_t rc = phant::state_root_host(c->ws, c->stream, phant::StateIn{addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n}, out, err);
     if (rc) return fail(c, rc, err.c_str());
     return PHANT_OK;
 }
@@ -2423,8 +2408,8 @@ int32_t phant_state_witness(phant_ctx* c, const uint8_t* addrs, const uint64_t* 
     if (!w) return fail(c, PHANT_E_OOM, "state_witness: out of host memory");
     DeviceGuard g(c->device);
     std::string err;
-    const int32_t rc = phant::state_witness_host(c->ws, c->stream, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first,
-                                                 n, wkeys, wkey_off, wkey_flags, n_wkeys, w->w, state_root_out, err);
+    const int32_t rc = phant::state_witness_host(c->ws, c->stream, phant::StateIn{addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n},
+                                                 phant::ProveQueries{wkeys, wkey_off, nullptr, wkey_flags, n_wkeys}, w->w, state_root_out, err);
     if (rc) return fail(c, rc, err.c_str());
     *out = w.release();
     return PHANT_OK;
@@ -2442,8 +2427,8 @@ int32_t phant_state_root_dev(phant_ctx* c, const uint8_t* d_addrs, const uint64_
     DeviceGuard g(c->device);
     TimedRegion t(c);
     std::string err;
-    const int32_t rc = phant::state_root_dev(c->ws, c->stream, d_addrs, d_nonces, d_balances, d_code, d_code_off, code_bytes, d_slot_keys,
-                                             d_slot_vals, d_slot_first, n_slots, n, d_root, err);
+    const phant::StateIn in{d_addrs, d_nonces, d_balances, d_code, d_code_off, d_slot_keys, d_slot_vals, d_slot_first, n, n_slots, code_bytes};
+    const int32_t rc = phant::state_root_dev(c->ws, c->stream, in, d_root, err);
     if (rc) return fail(c, rc, err.c_str());
     return PHANT_OK;
 }
@@ -2457,8 +2442,8 @@ int32_t phant_state_subtrie_nodes(phant_ctx* c, const uint8_t* addrs, const uint
         return fail(c, PHANT_E_INVALID_ARG, "state_subtrie_nodes: null pointer");
     DeviceGuard g(c->device);
     std::string err;
-    const int32_t rc = phant::state_subtrie_nodes_host(c->ws, c->stream, addrs, nonces, balances, code, code_off, slot_keys, slot_vals,
-                                                       slot_first, n, roots, root_enc, root_enc_cap, root_enc_len, err);
+    const phant::StateIn in{addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n};
+    const int32_t rc = phant::state_subtrie_nodes_host(c->ws, c->stream, in, roots, phant::RootNodes{root_enc, root_enc_len, root_enc_cap}, err);
     if (rc) return fail(c, rc, err.c_str());
     return PHANT_OK;
 }
@@ -2474,8 +2459,8 @@ int32_t phant_state_trie_leaves(phant_ctx* c, const uint8_t* addrs, const uint64
     std::string err;
     std::vector<uint8_t> k, v;
     std::vector<uint64_t> vo;
-    int32_t rc = phant::state_leaves_host(c->ws, c->stream, addrs, nonces, balances, code, code_off, slot_keys, slot_vals,
-                                          slot_first, n, k, v, vo, err);
+    int32_t rc = phant::state_leaves_host(c->ws, c->stream, phant::StateIn{addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n}, k, v, vo,
+                                          err);
     if (rc) return fail(c, rc, err.c_str());
     if (v.size() > vals_cap) return fail(c, PHANT_E_INVALID_ARG, "state_trie_leaves: vals_cap too small (112 bytes per account suffice)");
     if (n) {

@@ -587,7 +587,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
     // ---- the tries
     const bool want_roots = a.receipts_root || a.roots_out;
     if (want_roots) {
-        const int32_t rc = trie_forest_dev(ws, st, d_keys, d_key_off, key_total, d_vals, d_val_off, rbytes + list_total, total, d_meta, n_tries, d_roots, err);
+        const int32_t rc = trie_forest_dev(ws, st, TriePairs{d_keys, d_key_off, key_total, d_vals, d_val_off, rbytes + list_total, total, d_meta, n_tries, d_roots}, err);
         if (rc) return rc;
     }
 

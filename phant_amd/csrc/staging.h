@@ -1,8 +1,10 @@
-// staging.h -- how a block-level call crosses the bus, once, for the drivers that keep their arrays in the ctx's
-// `io` arena: block_receipts, header_chain, block_transactions, block_txs_prestate.  Plain host C++ on top of arena.h.
+// staging.h -- how a call crosses the bus, once, for the drivers that keep their arrays in the ctx's `io` arena:
+// block_receipts, header_chain, block_transactions, block_txs_prestate, and the host forms of the trie hasher and of its prover.  Plain
+// host C++ on top of arena.h.
 //
 //   lay_out_arena an arena sized by, then carved by, one list of take<T>() calls
 //   StagedInputs  the host form's arrays on their way in: ONE copy through the pinned stage, or a copy each
+//   stage_pairs   a forest's sorted pairs in host memory: validated, laid out, rebased and sent in through StagedInputs
 //   CallOutputs   every output named once; deliver() hands them back as the call's form asks
 //
 // The pinned stage mirrors the first STAGE_BYTES of `io`.  It is used when the bytes in question END within it and the arena does not
@@ -12,9 +14,11 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/phant_gpu.h"
 #include "arena.h"
+#include "trie_build.h"
 
 namespace phant {
 
@@ -67,11 +71,87 @@ struct StagedInputs {
         if (staged) memcpy(ws.staged(d), src, bytes);
         else e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, st);
     }
+    // where to WRITE an array that no host array holds yet (offsets rebased on the way): the pinned twin of dst, or nullptr when the
+    // call is not staged -- the caller then makes the array and put()s it
+    template <class T>
+    T* twin(T* dst) const {
+        return staged && e == hipSuccess ? ws.staged(dst) : nullptr;
+    }
     hipError_t finish() {
         if (e == hipSuccess && staged && end > begin) e = hipMemcpyAsync(begin, ws.staged(begin), (size_t)(end - begin), hipMemcpyHostToDevice, st);
         return e;
     }
 };
+
+// ---- in, host-form pairs: the one way in for trie_forest_host and prove_nodeset_host.  Validates `h` (then `check_more()`: the
+// caller's further inputs; nothing is laid out or copied behind a refusal), lays ws.io out as the five input arrays followed by
+// whatever `carve_more(arena)` takes -- it returns the end of the caller's further INPUTS, which it takes first, or nullptr --, writes
+// the pairs with their offsets rebased to 0 (in place in the pinned mirror when staged: no host allocation), lets `put_more(ins)` add
+// the caller's inputs and sends everything in.  -> the device view to launch on (roots left to the caller) and whether it was staged.
+struct StagedPairs {
+    int32_t rc = PHANT_OK;
+    bool staged = false;
+    TriePairs pairs;
+};
+template <class Check, class Carve, class Put>
+StagedPairs stage_pairs(Workspaces& ws, hipStream_t st, const HostPairs& h, const char* call, std::string& err, Check&& check_more, Carve&& carve_more,
+                        Put&& put_more) {
+    auto refuse = [&](int32_t rc, const char* why) { return err = why, StagedPairs{rc, false, TriePairs{}}; };
+    const uint32_t n = h.n, one[2] = {0, n};
+    const uint32_t* const seg = h.seg_first || h.n_tries != 1 ? h.seg_first : one;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (h.key_off[i + 1] < h.key_off[i] || h.val_off[i + 1] < h.val_off[i]) return refuse(PHANT_E_INVALID_ARG, "offsets not monotone");
+        if (h.key_off[i + 1] - h.key_off[i] > 255) return refuse(PHANT_E_UNSUPPORTED, "key longer than 255 bytes");
+    }
+    for (uint32_t s = 0; s < h.n_tries; ++s)
+        if (seg[s] > seg[s + 1] || seg[s + 1] > n) return refuse(PHANT_E_INVALID_ARG, "seg_first not monotone");
+    if (seg[0] != 0 || seg[h.n_tries] != n) return refuse(PHANT_E_INVALID_ARG, "seg_first must span [0, n]");
+    StagedPairs r;
+    if ((r.rc = check_more()) != PHANT_OK) return r;
+    const uint32_t k0 = n ? h.key_off[0] : 0u;
+    const uint64_t v0 = n ? h.val_off[0] : 0u, kb = n ? h.key_off[n] - k0 : 0u, vb = n ? h.val_off[n] - v0 : 0u;
+    uint8_t *d_keys = nullptr, *d_vals = nullptr;
+    const void* end = nullptr;
+    uint32_t *d_koff = nullptr, *d_seg = nullptr;
+    uint64_t* d_voff = nullptr;
+    r.rc = lay_out_status(lay_out_arena(ws.io, st, [&](auto& io) {
+        d_keys = io.template take<uint8_t>(kb + 16);
+        d_koff = io.template take<uint32_t>((size_t)n + 1);
+        d_vals = io.template take<uint8_t>(vb + 16);
+        d_voff = io.template take<uint64_t>((size_t)n + 1);
+        d_seg = io.template take<uint32_t>((size_t)h.n_tries + 1);
+        end = carve_more(io);
+    }), call, "io", err);
+    if (r.rc != PHANT_OK) return r;
+    StagedInputs ins(ws, st, d_keys, end ? end : d_seg + h.n_tries + 1);
+    ins.put(d_keys, kb ? h.keys + k0 : nullptr, kb);
+    ins.put(d_vals, vb ? h.vals + v0 : nullptr, vb);
+    std::vector<uint32_t> ko;
+    std::vector<uint64_t> vo;
+    uint32_t* rel_k = ins.twin(d_koff);
+    uint64_t* rel_v = ins.twin(d_voff);
+    if (!ins.staged) {  // (pageable sources: hipMemcpyAsync has taken its copy of them when put() returns)
+        ko.resize((size_t)n + 1);
+        vo.resize((size_t)n + 1);
+        rel_k = ko.data(), rel_v = vo.data();
+    }
+    if (rel_k && rel_v) {
+        rel_k[0] = 0, rel_v[0] = 0;
+        for (uint32_t i = 0; i <= n && n; ++i) rel_k[i] = h.key_off[i] - k0, rel_v[i] = h.val_off[i] - v0;
+    }
+    if (!ins.staged) ins.put(d_koff, rel_k, ((size_t)n + 1) * 4), ins.put(d_voff, rel_v, ((size_t)n + 1) * 8);
+    ins.put(d_seg, seg, ((size_t)h.n_tries + 1) * 4);
+    put_more(ins);
+    const hipError_t e = ins.finish();
+    if (e != hipSuccess) {
+        err = std::string(call) + ": staging the pairs: " + hipGetErrorString(e);
+        r.rc = e == hipErrorOutOfMemory ? PHANT_E_OOM : PHANT_E_DEVICE;
+        return r;
+    }
+    r.staged = ins.staged;
+    r.pairs = TriePairs{d_keys, d_koff, kb, d_vals, d_voff, vb, n, d_seg, h.n_tries, nullptr};
+    return r;
+}
 
 // ---- out: add() names an output once (a NULL caller pointer or no bytes: nobody wants it), deliver() hands back what was added since
 // the last deliver():

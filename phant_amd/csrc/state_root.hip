@@ -31,6 +31,7 @@
 #include "../../include/phant_gpu.h"
 #include "launch.h"
 #include "rlp.h"
+#include "staging.h"
 #include "trie_build.h"
 #include "witness.h"
 
@@ -209,16 +210,18 @@ int32_t order_digests_async(const TrieTune& tune, hipStream_t st, const uint8_t*
     return PHANT_OK;
 }
 
-// the state trie's leaves in device memory (inside ws.io: valid until the next call that stages something there)
+// the state trie's leaves in device memory (inside ws.io: valid until the next call that lays something out there)
 struct DevLeaves {
     uint8_t* keys = nullptr;      // n x 32, ascending
     uint32_t* key_off = nullptr;  // n + 1
     uint8_t* vals = nullptr;
     uint64_t* val_off = nullptr;  // n + 1
     uint64_t val_bytes = 0;
-    uint32_t* seg = nullptr;      // {0, n}: the one trie's segment table
+    uint32_t n = 0;
+    uint32_t* seg = nullptr;      // {0, n}: the one trie's segment table (room for 17 entries: the sixteen sub-tries')
     uint8_t* root = nullptr;      // 32 bytes for the caller's forest pass
     uint8_t* code_hash = nullptr; // n x 32, in the caller's account order
+    TriePairs pairs(uint32_t n_tries = 1) const { return {keys, key_off, 32ull * n, vals, val_off, val_bytes, n, seg, n_tries, root}; }
 };
 
 // phant_state_witness: the slot queries the storage forest is proven for while its tables stand (the state trie's pass reuses
@@ -229,11 +232,6 @@ struct StateProve {
     std::vector<uint8_t> slot_flags;  // ns
     std::vector<uint8_t> nodes;
     std::vector<uint64_t> node_off{0};
-    static size_t io_bytes(size_t ns, size_t na) {  // what the queries take of ws.io on top of the state pass
-        auto R = [](size_t b) { return DevArena::round(b); };
-        return 2 * R(32 * ns + 16) + 2 * R(4 * ns + 4) + R(ns + 1) + R(20 * na + 16) + R(32 * na + 16) + R(4 * na + 4) + R(na + 1) +
-               R(4 * na + 4) + R(32 * na + 16) + 4096;
-    }
 };
 
 // the queries' trie keys: 32-byte digests back to back
@@ -250,46 +248,107 @@ __global__ void __launch_bounds__(256) gather32_kernel(const uint8_t* __restrict
     dst[i] = src[32ull * idx[i >> 5] + (i & 31u)];
 }
 
-// the AccountState fields as device-resident struct-of-arrays, offsets relative (code_off[0] == 0, slot_first[0] == 0)
-struct StateIn {
-    const uint8_t* addrs;        // n x 20
-    const uint64_t* nonces;      // n
-    const uint8_t* bal;          // n x 32, big-endian
-    const uint8_t* code;         // code_bytes
-    const uint64_t* code_off;    // n + 1
-    const uint8_t* skeys;        // m x 32
-    const uint8_t* svals;        // m x 32 (4-byte aligned)
-    const uint32_t* slot_first;  // n + 1
-    uint32_t n, m;
-    uint64_t code_bytes;
+constexpr uint32_t SUBTRIE_CAP_MAX = 256;  // state_subtrie_nodes_host: the longest root node it hands back
+
+// Everything a state call keeps in ws.io, sized and carved by this one list: the counts in front decide which parts there are.
+struct StateLayout {
+    uint32_t n = 0, m = 0;    // accounts, slots
+    uint64_t code_bytes = 0;
+    bool host_form = false;   // the caller's arrays are copied in here (else: the device form's flag word)
+    uint32_t ns = 0;          // phant_state_witness: slot queries against the storage forest (StateProve)
+    bool witness = false;     // ... and the touched accounts' arrays
+    uint32_t na = 0;
+    size_t subtrie_out = 0;   // state_subtrie_nodes_host: bytes of its output block
+    // the caller's arrays (host form)
+    uint8_t *addrs = nullptr, *bal = nullptr, *code = nullptr, *skeys_in = nullptr, *svals_in = nullptr;
+    uint64_t *nonces = nullptr, *code_off = nullptr;
+    uint32_t *slot_first = nullptr, *flag = nullptr;
+    // storage: live slots -> hashed keys -> per-account order -> leaves
+    uint32_t *acc_first = nullptr, *pos = nullptr, *live_src = nullptr, *seg_of = nullptr, *len = nullptr, *lkoff = nullptr, *scan = nullptr;
+    uint8_t *live_keys = nullptr, *hk = nullptr, *sort = nullptr, *lkeys = nullptr, *lvals = nullptr, *sroots = nullptr;
+    uint64_t *lvoff = nullptr;
+    // the slot queries
+    uint8_t *qpre = nullptr, *qkeys = nullptr, *qflags = nullptr;
+    uint32_t *qoff = nullptr, *qtrie = nullptr;
+    // accounts: hashed addresses, code hashes, leaves
+    uint8_t *ha = nullptr, *hc = nullptr, *akeys = nullptr, *avals = nullptr, *root = nullptr;
+    uint32_t *alen = nullptr, *akoff = nullptr, *seg = nullptr;
+    uint64_t *avoff = nullptr;
+    uint8_t *sub_out = nullptr;
+    // the touched accounts
+    uint8_t *apre = nullptr, *tkeys = nullptr, *aflags = nullptr, *thc = nullptr;
+    uint32_t *aoff = nullptr, *held = nullptr;
+
+    template <class A>
+    void carve(A& a) {
+        const size_t n1 = (size_t)n + 1, m1 = (size_t)m + 1, big = m > n ? m : n;
+        if (host_form) {
+            addrs = a.template take<uint8_t>(20 * (size_t)n + 16);
+            nonces = a.template take<uint64_t>(n);
+            bal = a.template take<uint8_t>(32 * (size_t)n);
+            code = a.template take<uint8_t>(code_bytes + 16);
+            code_off = a.template take<uint64_t>(n1);
+            skeys_in = a.template take<uint8_t>(32 * (size_t)m + 16);
+            svals_in = a.template take<uint8_t>(32 * (size_t)m + 16);
+            slot_first = a.template take<uint32_t>(n1);
+        } else {
+            flag = a.template take<uint32_t>(1);
+        }
+        acc_first = a.template take<uint32_t>(n1);
+        pos = a.template take<uint32_t>(m1);
+        live_keys = a.template take<uint8_t>(32 * (size_t)m + 16);
+        live_src = a.template take<uint32_t>(m1);
+        seg_of = a.template take<uint32_t>(m1);
+        hk = a.template take<uint8_t>(32 * (size_t)m + 16);
+        sort = a.template take<uint8_t>(order_workspace_bytes((uint32_t)big));
+        len = a.template take<uint32_t>(m1);
+        lkeys = a.template take<uint8_t>(32 * (size_t)m + 16);
+        lkoff = a.template take<uint32_t>(m1);
+        lvals = a.template take<uint8_t>(33 * (size_t)m + 16);
+        lvoff = a.template take<uint64_t>(m1);
+        sroots = a.template take<uint8_t>(32 * (size_t)n);
+        scan = a.template take<uint32_t>(scan_scratch_entries((uint32_t)big + 1u));
+        if (ns) {
+            qpre = a.template take<uint8_t>(32 * (size_t)ns + 16);
+            qkeys = a.template take<uint8_t>(32 * (size_t)ns + 16);
+            qoff = a.template take<uint32_t>((size_t)ns + 1);
+            qtrie = a.template take<uint32_t>((size_t)ns + 1);
+            qflags = a.template take<uint8_t>((size_t)ns + 1);
+        }
+        ha = a.template take<uint8_t>(32 * (size_t)n);
+        hc = a.template take<uint8_t>(32 * (size_t)n);
+        alen = a.template take<uint32_t>(n1);
+        akeys = a.template take<uint8_t>(32 * (size_t)n + 16);
+        akoff = a.template take<uint32_t>(n1);
+        avals = a.template take<uint8_t>(112 * (size_t)n + 16);
+        avoff = a.template take<uint64_t>(n1);
+        seg = a.template take<uint32_t>(17);
+        root = a.template take<uint8_t>(32);
+        if (subtrie_out) sub_out = a.template take<uint8_t>(subtrie_out);
+        if (witness) {
+            apre = a.template take<uint8_t>(20 * (size_t)na + 16);
+            tkeys = a.template take<uint8_t>(32 * (size_t)na + 16);
+            aoff = a.template take<uint32_t>((size_t)na + 1);
+            aflags = a.template take<uint8_t>((size_t)na + 1);
+            held = a.template take<uint32_t>((size_t)na + 1);
+            thc = a.template take<uint8_t>(32 * (size_t)na + 16);
+        }
+    }
 };
-
-// what state_subtrie_nodes_host takes on top: 16 x (root 32 + length 4 + encoding <= SUBTRIE_CAP_MAX) bytes and a flag line
-constexpr uint32_t SUBTRIE_CAP_MAX = 256;
-constexpr size_t SUBTRIE_OUT_BYTES = 16u * (36u + SUBTRIE_CAP_MAX) + 64u;
-
-size_t state_scratch_bytes(uint32_t n, uint32_t m) {
-    const size_t n1 = (size_t)n + 1, m1 = (size_t)m + 1;
-    auto R = [](size_t b) { return DevArena::round(b); };
-    const size_t sort_ws = order_workspace_bytes(m > n ? m : n);
-    const size_t scan_entries = scan_scratch_entries((m > n ? m : n) + 1u);
-    return R(4 * n1) + R(4 * m1) + R(32 * (size_t)m + 16) + 2 * R(4 * (size_t)m + 4) + R(32 * (size_t)m + 16) + R(sort_ws) + R(4 * m1) +
-           R(32 * (size_t)m + 16) + R(4 * m1) + R(33 * (size_t)m + 16) + R(8 * m1) + R(32 * (size_t)n) + 2 * R(32 * (size_t)n) + R(4 * n1) +
-           R(32 * (size_t)n + 16) + R(4 * n1) + R(112 * (size_t)n + 16) + R(8 * n1) + R(4 * scan_entries) + R(17 * 4) +
-           R(SUBTRIE_OUT_BYTES) + 8192;
-}
-
-// device-resident inputs -> the state trie's leaves in device memory (scratch from ws.io, which the caller has reset to
-// hold state_scratch_bytes on top of whatever it staged there)
-int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, DevLeaves& out, std::string& err, StateProve* pv = nullptr) {
-    const uint32_t n = in.n, m = in.m;
-    if ((uint64_t)n * 112u > 0xffffffffull || (uint64_t)m * 33u > 0xffffffffull) {  // (leaf offsets are scanned as 32-bit counters)
+// (the stream is synchronised before the arena grows; a call that fits what is there pays nothing)
+int32_t lay_out_state(Workspaces& ws, hipStream_t st, StateLayout& lay, std::string& err) {
+    if ((uint64_t)lay.n * 112u > 0xffffffffull || (uint64_t)lay.m * 33u > 0xffffffffull) {  // (leaf offsets are scanned as 32-bit counters)
         err = "state root: more than 4 GiB of leaves in one call";
         return PHANT_E_UNSUPPORTED;
     }
+    return lay_out_status(lay_out_arena(ws.io, st, [&](auto& a) { lay.carve(a); }), "state root", "io", err);
+}
+
+// device-resident inputs -> the state trie's leaves in device memory (everything else in ws.io, as `lay` was laid out there)
+int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, const StateLayout& lay, DevLeaves& out, std::string& err,
+                          StateProve* pv = nullptr) {
+    const uint32_t n = in.n, m = in.m;
     const size_t n1 = (size_t)n + 1, m1 = (size_t)m + 1;
-    const size_t sort_ws = order_workspace_bytes(m > n ? m : n);
-    const size_t scan_entries = scan_scratch_entries((m > n ? m : n) + 1u);
     const uint8_t* d_addrs = in.addrs;
     const uint64_t* d_nonces = in.nonces;
     const uint8_t* d_bal = in.bal;
@@ -300,24 +359,11 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, Dev
     const uint32_t* d_slot_first = in.slot_first;
 
     // ---- storage: live slots -> hashed keys -> per-account order -> leaves -> one forest pass ----
-    uint32_t* d_acc_first = ws.io.take<uint32_t>(n1);
-    uint32_t* d_pos = ws.io.take<uint32_t>(m1);
-    uint8_t* d_live_keys = ws.io.take<uint8_t>(32 * (size_t)m + 16);
-    uint32_t* d_live_src = ws.io.take<uint32_t>((size_t)m + 1);
-    uint32_t* d_seg_of = ws.io.take<uint32_t>((size_t)m + 1);
-    uint8_t* d_hk = ws.io.take<uint8_t>(32 * (size_t)m + 16);
-    uint8_t* d_sort = ws.io.take<uint8_t>(sort_ws);
-    uint32_t* d_len = ws.io.take<uint32_t>(m1);
-    uint8_t* d_lkeys = ws.io.take<uint8_t>(32 * (size_t)m + 16);
-    uint32_t* d_lkoff = ws.io.take<uint32_t>(m1);
-    uint8_t* d_lvals = ws.io.take<uint8_t>(33 * (size_t)m + 16);
-    uint64_t* d_lvoff = ws.io.take<uint64_t>(m1);
-    uint8_t* d_sroots = ws.io.take<uint8_t>(32 * (size_t)n);
-    uint32_t* d_scan = ws.io.take<uint32_t>(scan_entries);
-    if (ws.io.overflowed) {  // (a sizing bug upstream: never a kernel or a copy on memory behind the allocation)
-        err = "state-root arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
+    uint32_t *const d_acc_first = lay.acc_first, *const d_pos = lay.pos, *const d_live_src = lay.live_src, *const d_seg_of = lay.seg_of;
+    uint32_t *const d_len = lay.len, *const d_lkoff = lay.lkoff, *const d_scan = lay.scan;
+    uint8_t *const d_live_keys = lay.live_keys, *const d_hk = lay.hk, *const d_sort = lay.sort, *const d_lkeys = lay.lkeys;
+    uint8_t *const d_lvals = lay.lvals, *const d_sroots = lay.sroots;
+    uint64_t* const d_lvoff = lay.lvoff;
     // what the host reads back on the way goes through the ctx's pinned mailbox (a copy into pageable memory is ~25 us a piece);
     // the words behind the trie builder's
     SR_TRY(ws.ensure_mailbox());
@@ -352,42 +398,29 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, Dev
     }
     int32_t rc;
     const uint32_t ns = pv ? (uint32_t)pv->slot_trie.size() : 0u;
+    const TriePairs storage{d_lkeys, d_lkoff, 32ull * L, d_lvals, d_lvoff, leaf_bytes, L, d_acc_first, n, d_sroots};
     if (ns && L) {  // the same pass with its tables kept, and the touched slots' paths cut from it (no live slot: no storage node)
-        uint8_t* d_qpre = ws.io.take<uint8_t>(32 * (size_t)ns + 16);
-        uint8_t* d_qkeys = ws.io.take<uint8_t>(32 * (size_t)ns + 16);
-        uint32_t* d_qoff = ws.io.take<uint32_t>((size_t)ns + 1);
-        uint32_t* d_qtrie = ws.io.take<uint32_t>((size_t)ns + 1);
-        uint8_t* d_qflags = ws.io.take<uint8_t>((size_t)ns + 1);
-        if (ws.io.overflowed) {
-            err = "state-witness arena sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
-        SR_TRY(hipMemcpyAsync(d_qpre, pv->slot_pre.data(), 32 * (size_t)ns, hipMemcpyHostToDevice, st));
-        SR_TRY(hipMemcpyAsync(d_qtrie, pv->slot_trie.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, st));
-        SR_TRY(hipMemcpyAsync(d_qflags, pv->slot_flags.data(), ns, hipMemcpyHostToDevice, st));
-        SR_TRY(launch_keccak256_fixed(d_qpre, 32, 32, ns, d_qkeys, st));
-        hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)ns + 1)), dim3(256), 0, st, ns, d_qoff);
-        rc = prove_forest_collect(ws, st, d_lkeys, d_lkoff, 32ull * L, d_lvals, d_lvoff, leaf_bytes, L, d_acc_first, n, d_sroots, d_qkeys, d_qoff,
-                                  d_qtrie, d_qflags, ns, pv->nodes, pv->node_off, err);
+        SR_TRY(hipMemcpyAsync(lay.qpre, pv->slot_pre.data(), 32 * (size_t)ns, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(lay.qtrie, pv->slot_trie.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(lay.qflags, pv->slot_flags.data(), ns, hipMemcpyHostToDevice, st));
+        SR_TRY(launch_keccak256_fixed(lay.qpre, 32, 32, ns, lay.qkeys, st));
+        hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)ns + 1)), dim3(256), 0, st, ns, lay.qoff);
+        rc = prove_forest_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, lay.qflags, ns}, pv->nodes, pv->node_off, err);
     } else {
-        rc = trie_forest_dev(ws, st, d_lkeys, d_lkoff, 32ull * L, d_lvals, d_lvoff, leaf_bytes, L, d_acc_first, n, d_sroots, err);
+        rc = trie_forest_dev(ws, st, storage, err);
     }
     if (rc) return rc;
 
     // ---- accounts: hashed addresses in order, code hashes, leaves ----
-    uint8_t* d_ha = ws.io.take<uint8_t>(32 * (size_t)n);
-    uint8_t* d_hc = ws.io.take<uint8_t>(32 * (size_t)n);
-    uint32_t* d_alen = ws.io.take<uint32_t>(n1);
-    out.keys = ws.io.take<uint8_t>(32 * (size_t)n + 16);
-    out.key_off = ws.io.take<uint32_t>(n1);
-    out.vals = ws.io.take<uint8_t>(112 * (size_t)n + 16);
-    out.val_off = ws.io.take<uint64_t>(n1);
-    out.seg = ws.io.take<uint32_t>(17);
-    out.root = ws.io.take<uint8_t>(32);
-    if (ws.io.overflowed) {  // (a sizing bug upstream: never a kernel or a copy on memory behind the allocation)
-        err = "state-root arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
+    uint8_t *const d_ha = lay.ha, *const d_hc = lay.hc;
+    uint32_t* const d_alen = lay.alen;
+    out.keys = lay.akeys;
+    out.key_off = lay.akoff;
+    out.vals = lay.avals;
+    out.val_off = lay.avoff;
+    out.n = n;
+    out.seg = lay.seg;
+    out.root = lay.root;
     SR_TRY(launch_keccak256_fixed(d_addrs, 20, 20, n, d_ha, st));
     SR_TRY(launch_keccak256_var(d_code, d_code_off, n, d_hc, st));
     out.code_hash = d_hc;
@@ -414,59 +447,45 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, Dev
     return PHANT_OK;
 }
 
-// the caller's HOST arrays -> staged once -> state_leaves_core
-int32_t state_leaves_dev(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances,
-                         const uint8_t* code, const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals,
-                         const uint32_t* slot_first, uint32_t n, DevLeaves& out, std::string& err, StateProve* pv = nullptr,
-                         size_t extra_io = 0) {
+// the caller's HOST arrays -> copied in once -> state_leaves_core; `lay` comes with the caller's own parts (ns, witness, subtrie_out)
+// set.  A copy per array and a synchronisation: a state is rarely small, and its arrays are followed by scratch.
+int32_t state_leaves_dev(Workspaces& ws, hipStream_t st, const StateIn& h, StateLayout& lay, DevLeaves& out, std::string& err, StateProve* pv = nullptr) {
+    const uint32_t n = h.n;
     for (uint32_t a = 0; a < n; ++a) {
-        if (slot_first[a + 1] < slot_first[a]) {
+        if (h.slot_first[a + 1] < h.slot_first[a]) {
             err = "slot_first not monotone";
             return PHANT_E_INVALID_ARG;
         }
-        if (code_off[a + 1] < code_off[a]) {
+        if (h.code_off[a + 1] < h.code_off[a]) {
             err = "code_off not monotone";
             return PHANT_E_INVALID_ARG;
         }
     }
-    const uint32_t m = slot_first[n] - slot_first[0];
-    const uint64_t code_bytes = code_off[n] - code_off[0];
+    const uint32_t m = h.slot_first[n] - h.slot_first[0];
+    const uint64_t code_bytes = h.code_off[n] - h.code_off[0];
     const size_t n1 = (size_t)n + 1;
-    auto R = [](size_t b) { return DevArena::round(b); };
-    SR_TRY(ws.io.reset(R(20 * (size_t)n + 16) + R(8 * (size_t)n) + R(32 * (size_t)n) + R(code_bytes + 16) + R(8 * n1) + 2 * R(32 * (size_t)m + 16) +
-                       R(4 * n1) + state_scratch_bytes(n, m) + extra_io));
-    // ---- the caller's arrays, once ----
-    uint8_t* d_addrs = ws.io.take<uint8_t>(20 * (size_t)n + 16);
-    uint64_t* d_nonces = ws.io.take<uint64_t>(n);
-    uint8_t* d_bal = ws.io.take<uint8_t>(32 * (size_t)n);
-    uint8_t* d_code = ws.io.take<uint8_t>(code_bytes + 16);
-    uint64_t* d_code_off = ws.io.take<uint64_t>(n1);
-    uint8_t* d_skeys_in = ws.io.take<uint8_t>(32 * (size_t)m + 16);
-    uint8_t* d_svals_in = ws.io.take<uint8_t>(32 * (size_t)m + 16);
-    uint32_t* d_slot_first = ws.io.take<uint32_t>(n1);
-    if (ws.io.overflowed) {  // (a sizing bug upstream: never a kernel or a copy on memory behind the allocation)
-        err = "state-root arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
-    SR_TRY(hipMemcpyAsync(d_addrs, addrs, 20 * (size_t)n, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemcpyAsync(d_nonces, nonces, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemcpyAsync(d_bal, balances, 32 * (size_t)n, hipMemcpyHostToDevice, st));
-    if (code_bytes) SR_TRY(hipMemcpyAsync(d_code, code + code_off[0], code_bytes, hipMemcpyHostToDevice, st));
+    lay.n = n, lay.m = m, lay.code_bytes = code_bytes, lay.host_form = true;
+    const int32_t rc = lay_out_state(ws, st, lay, err);
+    if (rc) return rc;
+    SR_TRY(hipMemcpyAsync(lay.addrs, h.addrs, 20 * (size_t)n, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemcpyAsync(lay.nonces, h.nonces, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemcpyAsync(lay.bal, h.bal, 32 * (size_t)n, hipMemcpyHostToDevice, st));
+    if (code_bytes) SR_TRY(hipMemcpyAsync(lay.code, h.code + h.code_off[0], code_bytes, hipMemcpyHostToDevice, st));
     std::vector<uint64_t> rel_code(n1);
     std::vector<uint32_t> rel_slot(n1);
     for (size_t i = 0; i < n1; ++i) {
-        rel_code[i] = code_off[i] - code_off[0];
-        rel_slot[i] = slot_first[i] - slot_first[0];
+        rel_code[i] = h.code_off[i] - h.code_off[0];
+        rel_slot[i] = h.slot_first[i] - h.slot_first[0];
     }
-    SR_TRY(hipMemcpyAsync(d_code_off, rel_code.data(), 8 * n1, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemcpyAsync(d_slot_first, rel_slot.data(), 4 * n1, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemcpyAsync(lay.code_off, rel_code.data(), 8 * n1, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemcpyAsync(lay.slot_first, rel_slot.data(), 4 * n1, hipMemcpyHostToDevice, st));
     if (m) {
-        SR_TRY(hipMemcpyAsync(d_skeys_in, slot_keys + 32ull * slot_first[0], 32 * (size_t)m, hipMemcpyHostToDevice, st));
-        SR_TRY(hipMemcpyAsync(d_svals_in, slot_vals + 32ull * slot_first[0], 32 * (size_t)m, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(lay.skeys_in, h.skeys + 32ull * h.slot_first[0], 32 * (size_t)m, hipMemcpyHostToDevice, st));
+        SR_TRY(hipMemcpyAsync(lay.svals_in, h.svals + 32ull * h.slot_first[0], 32 * (size_t)m, hipMemcpyHostToDevice, st));
     }
     SR_TRY(hipStreamSynchronize(st));  // (the rel_* vectors may go; the core synchronises within microseconds anyway)
-    const StateIn in{d_addrs, d_nonces, d_bal, d_code, d_code_off, d_skeys_in, d_svals_in, d_slot_first, n, m, code_bytes};
-    return state_leaves_core(ws, st, in, out, err, pv);
+    const StateIn in{lay.addrs, lay.nonces, lay.bal, lay.code, lay.code_off, lay.skeys_in, lay.svals_in, lay.slot_first, n, m, code_bytes};
+    return state_leaves_core(ws, st, in, lay, out, err, pv);
 }
 
 // device form: what only the device can see -- offsets that go backwards or do not span what the caller says
@@ -497,17 +516,16 @@ __global__ void __launch_bounds__(64) nibble_segments_kernel(const uint8_t* __re
 
 // The leaves of the state trie: keys = keccak256(address), ascending; values = rlp([nonce, balance, storageRoot,
 // codeHash]) with the storage roots computed here (one forest pass over all accounts' live slots).
-int32_t state_leaves_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces,
-                          const uint8_t* balances, const uint8_t* code, const uint64_t* code_off,
-                          const uint8_t* slot_keys, const uint8_t* slot_vals, const uint32_t* slot_first, uint32_t n,
-                          std::vector<uint8_t>& akeys, std::vector<uint8_t>& avals, std::vector<uint64_t>& avoff,
-                          std::string& err) {
+int32_t state_leaves_host(Workspaces& ws, hipStream_t st, const StateIn& in, std::vector<uint8_t>& akeys, std::vector<uint8_t>& avals,
+                          std::vector<uint64_t>& avoff, std::string& err) {
+    const uint32_t n = in.n;
     akeys.clear();
     avals.clear();
     avoff.assign((size_t)n + 1, 0);
     if (n == 0) return PHANT_OK;
+    StateLayout lay;
     DevLeaves l;
-    const int32_t rc = state_leaves_dev(ws, st, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n, l, err);
+    const int32_t rc = state_leaves_dev(ws, st, in, lay, l, err);
     if (rc) return rc;
     akeys.resize((size_t)n * 32);
     avals.resize(l.val_bytes);
@@ -519,34 +537,33 @@ int32_t state_leaves_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, 
 }
 
 // StateDB.root() over DEVICE-resident struct-of-arrays: nothing of the state crosses the bus, the root stays on the device.
-int32_t state_root_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_addrs, const uint64_t* d_nonces, const uint8_t* d_balances,
-                       const uint8_t* d_code, const uint64_t* d_code_off, uint64_t code_bytes, const uint8_t* d_slot_keys,
-                       const uint8_t* d_slot_vals, const uint32_t* d_slot_first, uint32_t n_slots, uint32_t n, uint8_t* d_root,
-                       std::string& err) {
+int32_t state_root_dev(Workspaces& ws, hipStream_t st, const StateIn& in, uint8_t* d_root, std::string& err) {
+    const uint32_t n = in.n;
     if (n == 0) {
         uint8_t root[32];
-        const int32_t rc = trie_root_host(ws, st, nullptr, nullptr, nullptr, nullptr, 0, root, err);
+        const int32_t rc = trie_forest_host(ws, st, HostPairs{}, root, err);
         if (rc) return rc;
         SR_TRY(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, st));
         SR_TRY(hipStreamSynchronize(st));
         return PHANT_OK;
     }
-    SR_TRY(ws.io.reset(state_scratch_bytes(n, n_slots) + 256));
-    uint32_t* d_flag = ws.io.take<uint32_t>(1);
-    SR_TRY(hipMemsetAsync(d_flag, 0, 4, st));
-    hipLaunchKernelGGL(state_offsets_check_kernel, dim3(blocks((uint64_t)n + 1)), dim3(256), 0, st, d_code_off, d_slot_first, n, n_slots, code_bytes, d_flag);
+    StateLayout lay;
+    lay.n = n, lay.m = in.m, lay.code_bytes = in.code_bytes;
+    int32_t rc = lay_out_state(ws, st, lay, err);
+    if (rc) return rc;
+    SR_TRY(hipMemsetAsync(lay.flag, 0, 4, st));
+    hipLaunchKernelGGL(state_offsets_check_kernel, dim3(blocks((uint64_t)n + 1)), dim3(256), 0, st, in.code_off, in.slot_first, n, in.m, in.code_bytes, lay.flag);
     uint32_t flag = 0;
-    SR_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    SR_TRY(hipMemcpyAsync(&flag, lay.flag, 4, hipMemcpyDeviceToHost, st));
     SR_TRY(hipStreamSynchronize(st));
     if (flag) {
         err = "state_root_dev: code_off / slot_first not monotone, not starting at 0 or not ending at code_bytes / n_slots";
         return PHANT_E_INVALID_ARG;
     }
-    const StateIn in{d_addrs, d_nonces, d_balances, d_code, d_code_off, d_slot_keys, d_slot_vals, d_slot_first, n, n_slots, code_bytes};
     DevLeaves l;
-    int32_t rc = state_leaves_core(ws, st, in, l, err);
+    rc = state_leaves_core(ws, st, in, lay, l, err);
     if (rc) return rc;
-    rc = trie_forest_dev(ws, st, l.keys, l.key_off, 32ull * n, l.vals, l.val_off, l.val_bytes, n, l.seg, 1, l.root, err);
+    rc = trie_forest_dev(ws, st, l.pairs(), err);
     if (rc) return rc;
     SR_TRY(hipMemcpyAsync(d_root, l.root, 32, hipMemcpyDeviceToDevice, st));
     return PHANT_OK;
@@ -554,39 +571,30 @@ int32_t state_root_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_addrs, c
 
 // One device's share of a SHARDED state root (comm.hip): its accounts -> leaves (device-resident) -> the sixteen sub-tries by
 // top nibble as ONE forest pass -> per nibble the sub-trie's root and the RLP of its root node.  Only those (16 x (32 + cap +
-// 4) bytes) come back; the leaves never leave the device.  enc_len[x] == 0: no account of this share under nibble x.
-int32_t state_subtrie_nodes_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances,
-                                 const uint8_t* code, const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals,
-                                 const uint32_t* slot_first, uint32_t n, uint8_t* roots, uint8_t* enc, uint32_t cap, uint32_t* enc_len,
-                                 std::string& err) {
-    if (cap > SUBTRIE_CAP_MAX) {  // (before anything is done or written)
+// 4) bytes) come back; the leaves never leave the device.  out.len[x] == 0: no account of this share under nibble x.
+int32_t state_subtrie_nodes_host(Workspaces& ws, hipStream_t st, const StateIn& in, uint8_t* roots, const RootNodes& out, std::string& err) {
+    if (out.cap > SUBTRIE_CAP_MAX) {  // (before anything is done or written)
         err = "state_subtrie_nodes: cap > 256";
         return PHANT_E_INVALID_ARG;
     }
-    std::memset(enc_len, 0, 16 * sizeof(uint32_t));
-    if (n == 0) return PHANT_OK;
+    std::memset(out.len, 0, 16 * sizeof(uint32_t));
+    if (in.n == 0) return PHANT_OK;
+    StateLayout lay;
+    lay.subtrie_out = 16u * (36u + (size_t)out.cap) + 64u;  // 16 x (root 32 + length 4 + encoding) bytes and a flag line
     DevLeaves l;
-    int32_t rc = state_leaves_dev(ws, st, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n, l, err);
+    const int32_t rc = state_leaves_dev(ws, st, in, lay, l, err);
     if (rc) return rc;
-    hipLaunchKernelGGL(nibble_segments_kernel, dim3(1), dim3(64), 0, st, l.keys, n, l.seg);
-    uint8_t* d_out = ws.io.take<uint8_t>(16u * (36u + cap) + 64u);  // (SUBTRIE_OUT_BYTES of state_scratch_bytes)
-    if (!d_out) {
-        err = "state_subtrie_nodes: scratch arena too small";
-        return PHANT_E_DEVICE;
-    }
-    return trie_forest_nodes_dev(ws, st, l.keys, l.key_off, 32ull * n, l.vals, l.val_off, l.val_bytes, n, l.seg, 16, d_out, roots, enc, cap,
-                                 enc_len, err);
+    hipLaunchKernelGGL(nibble_segments_kernel, dim3(1), dim3(64), 0, st, l.keys, in.n, l.seg);
+    return trie_forest_nodes_dev(ws, st, l.pairs(16), lay.sub_out, roots, out, err);
 }
 
-int32_t state_root_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces,
-                        const uint8_t* balances, const uint8_t* code, const uint64_t* code_off,
-                        const uint8_t* slot_keys, const uint8_t* slot_vals,
-                        const uint32_t* slot_first, uint32_t n, uint8_t out[32], std::string& err) {
-    if (n == 0) return trie_root_host(ws, st, nullptr, nullptr, nullptr, nullptr, 0, out, err);
+int32_t state_root_host(Workspaces& ws, hipStream_t st, const StateIn& in, uint8_t out[32], std::string& err) {
+    if (in.n == 0) return trie_forest_host(ws, st, HostPairs{}, out, err);
+    StateLayout lay;
     DevLeaves l;
-    int32_t rc = state_leaves_dev(ws, st, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n, l, err);
+    int32_t rc = state_leaves_dev(ws, st, in, lay, l, err);
     if (rc) return rc;
-    rc = trie_forest_dev(ws, st, l.keys, l.key_off, 32ull * n, l.vals, l.val_off, l.val_bytes, n, l.seg, 1, l.root, err);
+    rc = trie_forest_dev(ws, st, l.pairs(), err);
     if (rc) return rc;
     SR_TRY(hipMemcpyAsync(out, l.root, 32, hipMemcpyDeviceToHost, st));
     SR_TRY(hipStreamSynchronize(st));
@@ -596,10 +604,14 @@ int32_t state_root_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, co
 // phant_state_witness: the state pass with both of its forests proven -- the touched slots against the storage forest while its
 // tables stand, the touched addresses against the state trie behind it -- and the result laid out as the parser lays out a
 // document: accounts and slots in order of first appearance, "state" = the state-trie nodes, then the storage nodes.
-int32_t state_witness_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances,
-                           const uint8_t* code, const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals,
-                           const uint32_t* slot_first, uint32_t n, const uint8_t* wkeys, const uint32_t* wkey_off, const uint8_t* wkey_flags,
-                           uint32_t n_wkeys, ExecWitness& w, uint8_t root_out[32], std::string& err) {
+int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, ExecWitness& w, uint8_t root_out[32],
+                           std::string& err) {
+    const uint32_t n = in.n, n_wkeys = touched.n_queries;
+    const uint8_t *const wkeys = touched.qkeys, *const wkey_flags = touched.q_flags;
+    const uint32_t* const wkey_off = touched.qkey_off;
+    const uint8_t* const addrs = in.addrs;
+    const uint8_t* const code = in.code;
+    const uint64_t* const code_off = in.code_off;
     w = ExecWitness();
     w.node_off.push_back(0);
     w.code_off.push_back(0);
@@ -647,7 +659,7 @@ int32_t state_witness_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs,
         t_slot_flags[a][si.first->second] |= fl;
     }
     exec_witness_layout_keys(w, t_addr, t_slots);
-    if (n == 0) return trie_root_host(ws, st, nullptr, nullptr, nullptr, nullptr, 0, root_out, err);  // (every key absent under the empty root)
+    if (n == 0) return trie_forest_host(ws, st, HostPairs{}, root_out, err);  // (every key absent under the empty root)
 
     // ---- which touched addresses the state holds: their slots are queries against that account's storage trie ----
     std::unordered_map<std::string, uint32_t> index_of;
@@ -666,22 +678,15 @@ int32_t state_witness_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs,
             pv.slot_flags.push_back(t_slot_flags[a][j]);
         }
     }
+    StateLayout lay;
+    lay.ns = (uint32_t)pv.slot_trie.size(), lay.witness = true, lay.na = na;
     DevLeaves l;
-    int32_t rc = state_leaves_dev(ws, st, addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n, l, err, &pv,
-                                  StateProve::io_bytes(pv.slot_trie.size(), na));
+    int32_t rc = state_leaves_dev(ws, st, in, lay, l, err, &pv);
     if (rc) return rc;
 
     // ---- the state trie: the touched addresses' paths, exclusion proofs included ----
-    uint8_t* d_apre = ws.io.take<uint8_t>(20 * (size_t)na + 16);
-    uint8_t* d_akeys = ws.io.take<uint8_t>(32 * (size_t)na + 16);
-    uint32_t* d_aoff = ws.io.take<uint32_t>((size_t)na + 1);
-    uint8_t* d_aflags = ws.io.take<uint8_t>((size_t)na + 1);
-    uint32_t* d_held = ws.io.take<uint32_t>((size_t)na + 1);
-    uint8_t* d_hc = ws.io.take<uint8_t>(32 * (size_t)na + 16);
-    if (ws.io.overflowed) {
-        err = "state-witness arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
+    uint8_t *const d_apre = lay.apre, *const d_akeys = lay.tkeys, *const d_aflags = lay.aflags, *const d_hc = lay.thc;
+    uint32_t *const d_aoff = lay.aoff, *const d_held = lay.held;
     if (na) {
         SR_TRY(hipMemcpyAsync(d_apre, w.preimages.data(), 20 * (size_t)na, hipMemcpyHostToDevice, st));
         SR_TRY(hipMemcpyAsync(d_aflags, t_flags.data(), na, hipMemcpyHostToDevice, st));
@@ -696,8 +701,7 @@ int32_t state_witness_host(Workspaces& ws, hipStream_t st, const uint8_t* addrs,
         SR_TRY(hipMemcpyAsync(hc.data(), d_hc, hc.size(), hipMemcpyDeviceToHost, st));
     }
     std::vector<uint8_t> nodes;
-    rc = prove_forest_collect(ws, st, l.keys, l.key_off, 32ull * n, l.vals, l.val_off, l.val_bytes, n, l.seg, 1, l.root, d_akeys, d_aoff, nullptr,
-                              d_aflags, na, nodes, w.node_off, err);
+    rc = prove_forest_collect(ws, st, l.pairs(), ProveQueries{d_akeys, d_aoff, nullptr, d_aflags, na}, nodes, w.node_off, err);
     if (rc) return rc;
     SR_TRY(hipMemcpyAsync(root_out, l.root, 32, hipMemcpyDeviceToHost, st));
     SR_TRY(hipStreamSynchronize(st));

@@ -36,6 +36,7 @@
 #include "coop_sponge.hip.h"
 #include "launch.h"
 #include "rlp.h"
+#include "staging.h"
 
 namespace phant {
 namespace {
@@ -1627,21 +1628,25 @@ constexpr uint32_t SIDE_LEAF_LDS = 20480;     // bytes of unused dynamic LDS per
                                               // 5 or 6 KB, the bins beside them still starved: 146-162 us for a bin of 116 nodes)
 constexpr uint32_t FALLBACK_GRID = 1024;           // workgroups of a bin's fallback pass (its count is on the device)
 
+// The t2 arena: slot tables by dense node id (16 x 32 bytes a node) + the scratch blob of the nodes that take the general way.
+static int32_t lay_out_tables(Workspaces& ws, hipStream_t st, TrieDev& t, uint64_t nodes, uint64_t cap, std::string& err) {
+    const LaidOut r = lay_out_arena(ws.t2, st, [&](auto& a) {
+        t.slot_bytes = a.template take<uint8_t>((size_t)nodes * 16 * 32);
+        t.scratch = a.template take<uint8_t>(cap);
+    });
+    t.scratch_cap = cap;
+    return lay_out_status(r, "trie", "t2", err);
+}
+
 // The small pass (small_head_kernel, small_climb_kernel): t holds the inputs, the outputs and the t1 arena's arrays.
 static int32_t small_forest(Workspaces& ws, hipStream_t st, TrieDev t, uint64_t total_key_bytes, uint64_t total_val_bytes, std::string& err,
                             TrieDev* keep) {
     const uint32_t n = t.n;
     TB_TRY(ws.ensure_small(SS_WORDS * 4u));
-    {   // slot tables by boundary (a node's dense id is its boundary: < n) + the scratch blob of the nodes that take the general way
+    {   // slot tables by boundary (a node's dense id is its boundary: < n)
         const uint64_t cap = total_val_bytes + total_key_bytes + (uint64_t)n * (32 + 3 + 16 * 33 + 16 + 48 + 127 + 16) + 4096;
-        TB_TRY(ws.t2.reset(DevArena::round((size_t)n * 16 * 32) + DevArena::round(cap) + 1024));
-        t.slot_bytes = ws.t2.take<uint8_t>((size_t)n * 16 * 32);
-        t.scratch = ws.t2.take<uint8_t>(cap);
-        t.scratch_cap = cap;
-        if (ws.t2.overflowed || !t.scratch) {
-            err = "trie slot tables sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
+        const int32_t rc = lay_out_tables(ws, st, t, n, cap, err);
+        if (rc) return rc;
     }
     uint32_t* const state = ws.small_state;
     t.counters = state + SS_COUNTERS;
@@ -1700,25 +1705,23 @@ static int32_t small_forest(Workspaces& ws, hipStream_t st, TrieDev t, uint64_t 
 // Device-side forest build; all pointers device memory, except roots_host.
 // keep (optional): the pass's view of its tables as they stand when it returns -- the prover's input (trie_prove.hip.h); they
 // live in the t1 / t2 arenas until the next call resets those.
-static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off,
-                             const uint8_t* d_vals, const uint64_t* d_val_off, uint32_t n,
-                             uint64_t total_key_bytes, uint64_t total_val_bytes,
-                             const uint32_t* d_seg_first, uint32_t n_tries, uint8_t* d_roots,
-                             std::string& err, uint8_t* d_root_enc = nullptr, uint32_t* d_root_enc_len = nullptr,
-                             uint32_t root_enc_cap = 0, TrieDev* keep = nullptr) {
+static int32_t forest_device(Workspaces& ws, hipStream_t st, const TriePairs& p, std::string& err, const RootNodes& nodes = {},
+                             TrieDev* keep = nullptr) {
     TB_TRY(ws.ensure_mailbox());
+    const uint32_t n = p.n, n_tries = p.n_tries;
+    const uint64_t total_key_bytes = p.key_bytes, total_val_bytes = p.val_bytes;
     TrieDev t{};
-    t.root_enc = d_root_enc;
-    t.root_enc_len = d_root_enc_len;
-    t.root_enc_cap = root_enc_cap;
-    t.keys = d_keys;
-    t.key_off = d_key_off;
-    t.vals = d_vals;
-    t.val_off = d_val_off;
+    t.root_enc = nodes.enc;
+    t.root_enc_len = nodes.len;
+    t.root_enc_cap = nodes.cap;
+    t.keys = p.keys;
+    t.key_off = p.key_off;
+    t.vals = p.vals;
+    t.val_off = p.val_off;
     t.n = n;
-    t.seg_first = d_seg_first;
+    t.seg_first = p.seg_first;
     t.n_tries = n_tries;
-    t.roots = d_roots;
+    t.roots = p.roots;
     ws.trie_stats = TrieStats{};  // (phant_trie_stats: what THIS call did)
     TrieStats& stats = ws.trie_stats;
     stats.n = n;
@@ -1727,7 +1730,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
         return PHANT_E_UNSUPPORTED;
     }
     if (n == 0) {
-        hipLaunchKernelGGL(fill_empty_roots_kernel, dim3(blocks(n_tries)), dim3(256), 0, st, d_roots, n_tries);
+        hipLaunchKernelGGL(fill_empty_roots_kernel, dim3(blocks(n_tries)), dim3(256), 0, st, p.roots, n_tries);
         TB_TRY(hipGetLastError());
         if (keep) *keep = t;
         return PHANT_OK;
@@ -1749,34 +1752,29 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     }
     {
         const size_t n1 = (size_t)n + 1;
-        const size_t total = DevArena::round(n1) + DevArena::round(n1 * 4 + 64) * 7 + DevArena::round(tree_ints * 4 + 64) +
-                             DevArena::round((size_t)n * 4) * 5 + DevArena::round((size_t)n * 16) + DevArena::round(N_COUNTERS * 4) + 256 +
-                             DevArena::round(MAX_DEPTH_BINS * 4) * 3 + 256 + 4096;
-        TB_TRY(ws.t1.reset(total));
-        t.first_flag = ws.t1.take<uint8_t>(n1);
-        t.lcp = ws.t1.take<int32_t>(t.lvl_size[0]);
-        t.tree = ws.t1.take<int32_t>(tree_ints + FAN);
-        t.dense = ws.t1.take<uint32_t>(n1);
-        t.nd_l = ws.t1.take<uint32_t>(n1);
-        t.nd_pd = ws.t1.take<int32_t>(n1);
-        t.nd_parent = ws.t1.take<uint32_t>(n1);
-        t.nd_rep = ws.t1.take<uint32_t>(n1);
-        t.value_key = ws.t1.take<uint32_t>(n1);
-        t.leaf_parent = ws.t1.take<uint32_t>(n);
-        t.leaf_ps = ws.t1.take<uint32_t>(n);
-        t.order = ws.t1.take<uint32_t>(n);
-        t.order2 = ws.t1.take<uint32_t>(n);
-        t.misfit = ws.t1.take<uint32_t>(MAX_DEPTH_BINS);
-        t.deep_leaves = ws.t1.take<uint32_t>(n);
-        t.deep_count = ws.t1.take<uint32_t>(1);
-        t.slot_len = ws.t1.take<uint8_t>((size_t)n * 16);  // (n_rep <= n: sized before the host has seen n_rep)
-        t.counters = ws.t1.take<uint32_t>(N_COUNTERS);
-        t.depth_cursor = ws.t1.take<uint32_t>(MAX_DEPTH_BINS);
-        t.cursor = ws.t1.take<unsigned long long>(1);
-        if (ws.t1.overflowed || !t.cursor) {  // (a sizing bug upstream: never a kernel on memory behind the allocation)
-            err = "trie workspace sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
+        const int32_t rc = lay_out_status(lay_out_arena(ws.t1, st, [&](auto& a) {
+            t.first_flag = a.template take<uint8_t>(n1);
+            t.lcp = a.template take<int32_t>(t.lvl_size[0]);
+            t.tree = a.template take<int32_t>(tree_ints + FAN);
+            t.dense = a.template take<uint32_t>(n1);
+            t.nd_l = a.template take<uint32_t>(n1);
+            t.nd_pd = a.template take<int32_t>(n1);
+            t.nd_parent = a.template take<uint32_t>(n1);
+            t.nd_rep = a.template take<uint32_t>(n1);
+            t.value_key = a.template take<uint32_t>(n1);
+            t.leaf_parent = a.template take<uint32_t>(n);
+            t.leaf_ps = a.template take<uint32_t>(n);
+            t.order = a.template take<uint32_t>(n);
+            t.order2 = a.template take<uint32_t>(n);
+            t.misfit = a.template take<uint32_t>(MAX_DEPTH_BINS);
+            t.deep_leaves = a.template take<uint32_t>(n);
+            t.deep_count = a.template take<uint32_t>(1);
+            t.slot_len = a.template take<uint8_t>((size_t)n * 16);  // (n_rep <= n: sized before the host has seen n_rep)
+            t.counters = a.template take<uint32_t>(N_COUNTERS);
+            t.depth_cursor = a.template take<uint32_t>(MAX_DEPTH_BINS);
+            t.cursor = a.template take<unsigned long long>(1);
+        }), "trie", "t1", err);
+        if (rc) return rc;
         stats.cursor_off = (size_t)(reinterpret_cast<const uint8_t*>(t.cursor) - ws.t1.base);
         stats.has_cursor = true;
     }
@@ -1825,15 +1823,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     auto size_tables = [&](uint64_t reps) -> int32_t {
         const uint64_t max_key = 255;
         const uint64_t cap = total_val_bytes + total_key_bytes + (uint64_t)n * 32 + reps * (3 + 16 * 33 + 16 + 48 + max_key / 2 + 16) + 4096;
-        TB_TRY(ws.t2.reset(DevArena::round((size_t)reps * 16 * 32) + DevArena::round(cap) + 1024));
-        t.slot_bytes = ws.t2.take<uint8_t>((size_t)reps * 16 * 32);
-        t.scratch = ws.t2.take<uint8_t>(cap);
-        t.scratch_cap = cap;
-        if (ws.t2.overflowed || !t.scratch) {
-            err = "trie slot tables sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
-        return PHANT_OK;
+        return lay_out_tables(ws, st, t, reps, cap, err);
     };
     const uint64_t ahead_max_keys = ws.tune.ahead_max_keys >= 0 ? (uint64_t)ws.tune.ahead_max_keys : LEAVES_AHEAD_MAX_KEYS;
     bool ahead = n <= ahead_max_keys;
@@ -2045,58 +2035,23 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     return PHANT_OK;
 }
 
-int32_t trie_forest_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, const uint32_t* key_off,
-                         const uint8_t* vals, const uint64_t* val_off, uint32_t n,
-                         const uint32_t* seg_first, uint32_t n_tries, uint8_t* roots_out,
-                         std::string& err, uint8_t* root_enc_out, uint32_t root_enc_cap, uint32_t* root_enc_len_out) {
+int32_t trie_forest_host(Workspaces& ws, hipStream_t st, const HostPairs& h, uint8_t* roots_out, std::string& err, const RootNodes& out) {
+    const uint32_t n_tries = h.n_tries;
     if (n_tries == 0) return PHANT_OK;
-    const uint64_t kb = n ? key_off[n] - key_off[0] : 0;
-    const uint64_t vb = n ? val_off[n] - val_off[0] : 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (key_off[i + 1] < key_off[i] || val_off[i + 1] < val_off[i]) {
-            err = "offsets not monotone";
-            return PHANT_E_INVALID_ARG;
-        }
-        if (key_off[i + 1] - key_off[i] > 255) {
-            err = "key longer than 255 bytes";
-            return PHANT_E_UNSUPPORTED;
-        }
-    }
-    for (uint32_t s = 0; s < n_tries; ++s)
-        if (seg_first[s] > seg_first[s + 1] || seg_first[s + 1] > n) {
-            err = "seg_first not monotone";
-            return PHANT_E_INVALID_ARG;
-        }
-    if (seg_first[0] != 0 || seg_first[n_tries] != n) {
-        err = "seg_first must span [0, n]";
-        return PHANT_E_INVALID_ARG;
-    }
-    TB_TRY(ws.io.reset(DevArena::round(kb + 16) + DevArena::round(((size_t)n + 1) * 4) + DevArena::round(vb + 16) +
-                       DevArena::round(((size_t)n + 1) * 8) + DevArena::round(((size_t)n_tries + 1) * 4) +
-                       DevArena::round((size_t)n_tries * 32) + DevArena::round((size_t)n_tries * root_enc_cap + 4) +
-                       DevArena::round((size_t)n_tries * 4) + 1024));
-    uint8_t* d_keys = ws.io.take<uint8_t>(kb + 16);
-    uint32_t* d_koff = ws.io.take<uint32_t>((size_t)n + 1);
-    uint8_t* d_vals = ws.io.take<uint8_t>(vb + 16);
-    uint64_t* d_voff = ws.io.take<uint64_t>((size_t)n + 1);
-    uint32_t* d_seg = ws.io.take<uint32_t>((size_t)n_tries + 1);
-    uint8_t* d_roots = ws.io.take<uint8_t>((size_t)n_tries * 32);
-    uint8_t* d_enc = ws.io.take<uint8_t>((size_t)n_tries * root_enc_cap + 4);
-    uint32_t* d_enc_len = ws.io.take<uint32_t>(n_tries);
-    if (ws.io.overflowed) {  // (a sizing bug upstream: never a kernel or a copy on memory behind the allocation)
-        err = "trie staging arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
-    const bool want_enc = root_enc_out && root_enc_len_out && root_enc_cap;
-    // Small calls (the tries of an ordinary block): the five input arrays are laid out in the pinned mirror of the arena and cross
-    // the bus in one copy; the offsets are rebased in place there (Workspaces::stage).  The results go the other way without a
-    // copy command at all: the kernels store roots (and root nodes) into the mirror -- it is device-visible --, and they are
-    // there when the pass's own synchronisation returns.
-    const size_t in_span = (size_t)(reinterpret_cast<uint8_t*>(d_seg + n_tries + 1) - ws.io.base);
-    const size_t out_span = (size_t)(reinterpret_cast<uint8_t*>(d_enc_len + n_tries) - ws.io.base);
-    const bool staged = !PHANT_ARENA_POISONS && in_span <= Workspaces::STAGE_BYTES;
-    const bool staged_out = staged && out_span <= Workspaces::STAGE_BYTES;
-    if (staged) TB_TRY(ws.ensure_stage());
+    const bool want_enc = out.enc && out.len && out.cap;
+    uint8_t *d_roots = nullptr, *d_enc = nullptr;
+    uint32_t* d_enc_len = nullptr;
+    const StagedPairs in = stage_pairs(ws, st, h, "trie", err, [] { return PHANT_OK; }, [&](auto& io) -> const void* {
+        d_roots = io.template take<uint8_t>((size_t)n_tries * 32);
+        d_enc = io.template take<uint8_t>((size_t)n_tries * out.cap + 4);
+        d_enc_len = io.template take<uint32_t>(n_tries);
+        return nullptr;
+    }, [](StagedInputs&) {});
+    if (in.rc) return in.rc;
+    // Small calls (the tries of an ordinary block): the five input arrays have crossed the bus in one copy (stage_pairs).  The results
+    // go the other way without a copy command at all: the kernels store roots (and root nodes) into the pinned mirror -- it is
+    // device-visible --, and they are there when the pass's own synchronisation returns.
+    const bool staged_out = in.staged && (size_t)(reinterpret_cast<uint8_t*>(d_enc_len + n_tries) - ws.io.base) <= Workspaces::STAGE_BYTES;
     if (staged_out) {
         d_roots = ws.staged(d_roots);
         d_enc = ws.staged(d_enc);
@@ -2105,84 +2060,55 @@ int32_t trie_forest_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, co
     } else if (want_enc) {
         TB_TRY(hipMemsetAsync(d_enc_len, 0, (size_t)n_tries * 4, st));
     }
-    if (staged) {
-        if (kb) std::memcpy(ws.staged(d_keys), keys + key_off[0], kb);
-        if (vb) std::memcpy(ws.staged(d_vals), vals + val_off[0], vb);
-        uint32_t* const ko = ws.staged(d_koff);
-        uint64_t* const vo = ws.staged(d_voff);
-        ko[0] = 0;
-        vo[0] = 0;
-        for (uint32_t i = 0; i <= n && n; ++i) {
-            ko[i] = key_off[i] - key_off[0];
-            vo[i] = val_off[i] - val_off[0];
-        }
-        std::memcpy(ws.staged(d_seg), seg_first, ((size_t)n_tries + 1) * 4);
-        TB_TRY(hipMemcpyAsync(ws.io.base, ws.stage, in_span, hipMemcpyHostToDevice, st));
-    } else {
-        std::vector<uint32_t> ko((size_t)n + 1, 0);
-        std::vector<uint64_t> vo((size_t)n + 1, 0);
-        for (uint32_t i = 0; i <= n && n; ++i) {
-            ko[i] = key_off[i] - key_off[0];
-            vo[i] = val_off[i] - val_off[0];
-        }
-        if (kb) TB_TRY(hipMemcpyAsync(d_keys, keys + key_off[0], kb, hipMemcpyHostToDevice, st));
-        if (vb) TB_TRY(hipMemcpyAsync(d_vals, vals + val_off[0], vb, hipMemcpyHostToDevice, st));
-        TB_TRY(hipMemcpyAsync(d_koff, ko.data(), ko.size() * 4, hipMemcpyHostToDevice, st));
-        TB_TRY(hipMemcpyAsync(d_voff, vo.data(), vo.size() * 8, hipMemcpyHostToDevice, st));
-        TB_TRY(hipMemcpyAsync(d_seg, seg_first, ((size_t)n_tries + 1) * 4, hipMemcpyHostToDevice, st));
-        // (pageable sources: hipMemcpyAsync has taken its copy of ko / vo when it returns)
-    }
-    int32_t rc = forest_device(ws, st, d_keys, d_koff, d_vals, d_voff, n, kb, vb, d_seg, n_tries, d_roots, err,
-                               want_enc ? d_enc : nullptr, want_enc ? d_enc_len : nullptr, want_enc ? root_enc_cap : 0u);
+    TriePairs p = in.pairs;
+    p.roots = d_roots;
+    const int32_t rc = forest_device(ws, st, p, err, want_enc ? RootNodes{d_enc, d_enc_len, out.cap} : RootNodes{});
     if (rc) {
         (void)hipStreamSynchronize(st);
         return rc;
     }
+    if (!staged_out) {
+        TB_TRY(hipMemcpyAsync(roots_out, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
+        if (want_enc) {
+            TB_TRY(hipMemcpyAsync(out.enc, d_enc, (size_t)n_tries * out.cap, hipMemcpyDeviceToHost, st));
+            TB_TRY(hipMemcpyAsync(out.len, d_enc_len, (size_t)n_tries * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    TB_TRY(hipStreamSynchronize(st));  // (staged: forest_device has synchronised already unless there were no keys)
     if (staged_out) {
-        TB_TRY(hipStreamSynchronize(st));  // (forest_device has synchronised already unless there were no keys)
         std::memcpy(roots_out, d_roots, (size_t)n_tries * 32);
         if (want_enc) {
-            std::memcpy(root_enc_out, d_enc, (size_t)n_tries * root_enc_cap);
-            std::memcpy(root_enc_len_out, d_enc_len, (size_t)n_tries * 4);
+            std::memcpy(out.enc, d_enc, (size_t)n_tries * out.cap);
+            std::memcpy(out.len, d_enc_len, (size_t)n_tries * 4);
         }
-        return PHANT_OK;
     }
-    TB_TRY(hipMemcpyAsync(roots_out, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
-    if (want_enc) {
-        TB_TRY(hipMemcpyAsync(root_enc_out, d_enc, (size_t)n_tries * root_enc_cap, hipMemcpyDeviceToHost, st));
-        TB_TRY(hipMemcpyAsync(root_enc_len_out, d_enc_len, (size_t)n_tries * 4, hipMemcpyDeviceToHost, st));
-    }
-    TB_TRY(hipStreamSynchronize(st));
     return PHANT_OK;
 }
 
-// The forest pass over device-resident arrays for callers that own the io arena themselves (state_root.hip): d_seg_first
-// (n_tries + 1 entries) and d_roots (n_tries x 32) are device memory as well.  Uses the t1 / t2 arenas only.
-int32_t trie_forest_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
-                        const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n,
-                        const uint32_t* d_seg_first, uint32_t n_tries, uint8_t* d_roots, std::string& err) {
-    const int32_t rc = forest_device(ws, st, d_keys, d_key_off, d_vals, d_val_off, n, key_bytes, val_bytes, d_seg_first, n_tries, d_roots, err);
+// The forest pass over device-resident arrays for callers that own the io arena themselves (state_root.hip): p.seg_first
+// (n_tries + 1 entries) and p.roots (n_tries x 32) are device memory as well.  Uses the t1 / t2 arenas only.
+int32_t trie_forest_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, std::string& err) {
+    const int32_t rc = forest_device(ws, st, p, err);
     if (rc) (void)hipStreamSynchronize(st);
     return rc;
 }
 
 // the forest pass over device-resident arrays that also delivers every trie's root NODE; results to HOST buffers (small)
-int32_t trie_forest_nodes_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
-                              const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n,
-                              const uint32_t* d_seg_first, uint32_t n_tries, uint8_t* d_out, uint8_t* roots_out, uint8_t* root_enc_out,
-                              uint32_t root_enc_cap, uint32_t* root_enc_len_out, std::string& err) {
-    // d_out: n_tries x (32 + root_enc_cap + 4) + 64 bytes of device memory from the caller, 4-byte aligned
-    uint8_t* d_roots = d_out;
-    uint8_t* d_enc = d_out + (size_t)n_tries * 32;
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_out + ((size_t)n_tries * 32 + (size_t)n_tries * root_enc_cap + 3) / 4 * 4);
-    TB_TRY(hipMemsetAsync(d_len, 0, (size_t)n_tries * 4, st));  // (an empty trie has no root node: nobody writes its length)
-    int32_t rc = forest_device(ws, st, d_keys, d_key_off, d_vals, d_val_off, n, key_bytes, val_bytes, d_seg_first, n_tries, d_roots, err,
-                               d_enc, d_len, root_enc_cap);
+int32_t trie_forest_nodes_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, uint8_t* d_out, uint8_t* roots_out, const RootNodes& out,
+                              std::string& err) {
+    // d_out: n_tries x (32 + out.cap + 4) + 64 bytes of device memory from the caller, 4-byte aligned
+    const size_t n_tries = pairs.n_tries;
+    TriePairs p = pairs;
+    p.roots = d_out;
+    uint8_t* d_enc = d_out + n_tries * 32;
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_out + (n_tries * 32 + n_tries * out.cap + 3) / 4 * 4);
+    TB_TRY(hipMemsetAsync(d_len, 0, n_tries * 4, st));  // (an empty trie has no root node: nobody writes its length)
+    int32_t rc = forest_device(ws, st, p, err, RootNodes{d_enc, d_len, out.cap});
     hipError_t e = hipSuccess;
     if (rc == PHANT_OK) {
-        e = hipMemcpyAsync(roots_out, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(root_enc_out, d_enc, (size_t)n_tries * root_enc_cap, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(root_enc_len_out, d_len, (size_t)n_tries * 4, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(roots_out, p.roots, n_tries * 32, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out.enc, d_enc, n_tries * out.cap, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out.len, d_len, n_tries * 4, hipMemcpyDeviceToHost, st);
     }
     (void)hipStreamSynchronize(st);
     if (rc == PHANT_OK && e != hipSuccess) {
@@ -2192,27 +2118,34 @@ int32_t trie_forest_nodes_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_k
     return rc;
 }
 
-int32_t trie_root_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
-                      const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, uint8_t* d_root,
-                      std::string& err) {
-    // the one trie's segment table: two words in the io arena (nothing else of a device-form call lives there)
-    TB_TRY(ws.io.reset(1024));
-    uint32_t* d_seg = ws.io.take<uint32_t>(2);
-    const uint32_t seg[2] = {0, n};
-    TB_TRY(hipMemcpyAsync(d_seg, seg, sizeof seg, hipMemcpyHostToDevice, st));
-    const int32_t rc = forest_device(ws, st, d_keys, d_key_off, d_vals, d_val_off, n, key_bytes, val_bytes, d_seg, 1, d_root, err);
-    if (rc) (void)hipStreamSynchronize(st);
-    return rc;
+// A device-form call's own words in the io arena (nothing else of such a call lives there): the one trie's segment table {0, n} when
+// the caller gave none, and n_tries x 32 bytes for roots nobody wants.  -> p with both in place.
+static int32_t fill_in_dev(Workspaces& ws, hipStream_t st, TriePairs& p, const char* call, std::string& err) {
+    uint32_t* d_seg = nullptr;
+    uint8_t* d_roots = nullptr;
+    const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, [&](auto& io) {
+        d_seg = io.template take<uint32_t>(2);
+        if (!p.roots) d_roots = io.template take<uint8_t>((size_t)p.n_tries * 32);
+    }), call, "io", err);
+    if (rc) return rc;
+    if (!p.roots) p.roots = d_roots;
+    if (!p.seg_first) {
+        const uint32_t seg[2] = {0, p.n};  // (a pageable source: hipMemcpyAsync has taken its copy when it returns)
+        TB_TRY(hipMemcpyAsync(d_seg, seg, sizeof seg, hipMemcpyHostToDevice, st));
+        p.seg_first = d_seg;
+    }
+    return PHANT_OK;
 }
 
-int32_t trie_root_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, const uint32_t* key_off,
-                       const uint8_t* vals, const uint64_t* val_off, uint32_t n, uint8_t out[32],
-                       std::string& err) {
-    const uint32_t seg[2] = {0, n};
-    const uint32_t zero32[1] = {0};
-    const uint64_t zero64[1] = {0};
-    return trie_forest_host(ws, st, keys, n ? key_off : zero32, vals, n ? val_off : zero64, n, seg, 1, out, err, nullptr,
-                            0, nullptr);
+int32_t trie_root_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, std::string& err) {
+    TriePairs p = pairs;
+    p.seg_first = nullptr;
+    p.n_tries = 1;
+    int32_t rc = fill_in_dev(ws, st, p, "trie", err);
+    if (rc) return rc;
+    rc = forest_device(ws, st, p, err);
+    if (rc) (void)hipStreamSynchronize(st);
+    return rc;
 }
 
 // ---- witness generation (trie_prove.hip.h): the nodes on the paths of queried keys ----
@@ -2225,20 +2158,18 @@ struct ProveRun {
 };
 }  // namespace
 
-// The build with its tables kept, then locate / mark, sizes and offsets.  Every pointer is device memory; d_seg_first and d_roots
-// are required here.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the emit pass would write.
-static int32_t prove_plan(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
-                          const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first,
-                          uint32_t n_tries, uint8_t* d_roots, const uint8_t* d_qkeys, const uint32_t* d_qkey_off, const uint32_t* d_q_trie,
-                          const uint8_t* d_q_flags, uint32_t n_queries, uint8_t* d_q_status, ProveRun& run, std::string& err) {
-    int32_t rc = forest_device(ws, st, d_keys, d_key_off, d_vals, d_val_off, n, key_bytes, val_bytes, d_seg_first, n_tries, d_roots, err,
-                               nullptr, nullptr, 0, &run.t);
+// The build with its tables kept, then locate / mark, sizes and offsets.  Every pointer is device memory; pairs.seg_first and
+// pairs.roots are required here.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the emit pass would write.
+static int32_t prove_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status, ProveRun& run,
+                          std::string& err) {
+    int32_t rc = forest_device(ws, st, pairs, err, RootNodes{}, &run.t);
     if (rc) return rc;
+    const uint32_t n = pairs.n, n_queries = q.n_queries;
     const size_t n1 = (size_t)n + 1;
     const uint32_t tiles = n ? (uint32_t)((n1 + PV_TILE - 1u) / PV_TILE) : 0u;
     ProveDev& p = run.p;
     p = ProveDev{};
-    auto carve = [&](auto& a) {
+    rc = lay_out_status(lay_out_arena(ws.pv, st, [&](auto& a) {
         p.nmark = a.template take<uint32_t>(n1);
         p.lmark = a.template take<uint8_t>(n1);
         p.members = a.template take<uint8_t>(n1);
@@ -2247,27 +2178,18 @@ static int32_t prove_plan(Workspaces& ws, hipStream_t st, const uint8_t* d_keys,
         p.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
         p.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
         p.flags = a.template take<uint32_t>(4);
-    };
-    {
-        ArenaSizer sz;
-        carve(sz);
-        TB_TRY(ws.pv.reset(sz.bytes + 1024));
-        carve(ws.pv);
-        if (ws.pv.overflowed || !p.flags) {
-            err = "prover workspace sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
-    }
+    }), "prove_nodeset", "pv", err);
+    if (rc) return rc;
     p.tiles = tiles;
-    p.qkeys = d_qkeys;
-    p.qkey_off = d_qkey_off;
-    p.q_trie = d_q_trie;
-    p.q_flags = d_q_flags;
+    p.qkeys = q.qkeys;
+    p.qkey_off = q.qkey_off;
+    p.q_trie = q.q_trie;
+    p.q_flags = q.q_flags;
     p.n_queries = n_queries;
     p.q_status = d_q_status;
     p.mailbox = ws.mailbox;
-    run.t.n_tries = n_tries;
-    run.t.seg_first = d_seg_first;
+    run.t.n_tries = pairs.n_tries;
+    run.t.seg_first = pairs.seg_first;
     if (n) {
         TB_TRY(hipMemsetAsync(p.nmark, 0, n1 * 4, st));
         TB_TRY(hipMemsetAsync(p.lmark, 0, n1, st));
@@ -2275,7 +2197,7 @@ static int32_t prove_plan(Workspaces& ws, hipStream_t st, const uint8_t* d_keys,
     hipLaunchKernelGGL(prove_reset_kernel, dim3(1), dim3(64), 0, st, run.t, p);
     if (n_queries) hipLaunchKernelGGL(prove_locate_kernel, dim3(blocks(n_queries)), dim3(256), 0, st, run.t, p);
     if (n) {
-        if (d_q_flags && n_queries) hipLaunchKernelGGL(prove_sibling_kernel, dim3(blocks(n)), dim3(256), 0, st, run.t, p);
+        if (q.q_flags && n_queries) hipLaunchKernelGGL(prove_sibling_kernel, dim3(blocks(n)), dim3(256), 0, st, run.t, p);
         hipLaunchKernelGGL(prove_size_kernel, dim3(tiles), dim3(PV_TILE), 0, st, run.t, p);
     }
     hipLaunchKernelGGL(prove_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, p);
@@ -2320,25 +2242,22 @@ static int32_t prove_emit(hipStream_t st, ProveRun& run, uint8_t* d_nodes, uint6
     return PHANT_OK;
 }
 
-int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
-                          const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first,
-                          uint32_t n_tries, ProveArgs& a, std::string& err) {
-    // what the caller left out: the one trie's segment table, roots nobody wants
-    TB_TRY(ws.io.reset(DevArena::round((size_t)n_tries * 32) + 1024));
-    uint32_t* d_seg = ws.io.take<uint32_t>(2);
-    uint8_t* d_roots = a.roots ? a.roots : ws.io.take<uint8_t>((size_t)n_tries * 32);
-    if (ws.io.overflowed) {
-        err = "prover staging arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
-    if (!d_seg_first) {
-        const uint32_t seg[2] = {0, n};
-        TB_TRY(hipMemcpyAsync(d_seg, seg, sizeof seg, hipMemcpyHostToDevice, st));
-        d_seg_first = d_seg;
-    }
+// the node blob and its offsets at their exact sizes, in the pvo arena (either may be left out: nobody wants it)
+static int32_t lay_out_nodes(Workspaces& ws, hipStream_t st, const ProveRun& run, bool blob, bool offsets, uint8_t*& d_nodes, uint64_t*& d_noff,
+                             std::string& err) {
+    return lay_out_status(lay_out_arena(ws.pvo, st, [&](auto& a) {
+        if (blob) d_nodes = a.template take<uint8_t>(run.nodes_len + 16);
+        if (offsets) d_noff = a.template take<uint64_t>((size_t)run.total_nodes + 1);
+    }), "prove_nodeset", "pvo", err);
+}
+
+int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, ProveArgs& a, std::string& err) {
+    TriePairs p = pairs;
+    p.roots = a.roots;
+    int32_t rc = fill_in_dev(ws, st, p, "prove_nodeset", err);
+    if (rc) return rc;
     ProveRun run;
-    int32_t rc = prove_plan(ws, st, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries, d_roots, a.qkeys,
-                            a.qkey_off, a.q_trie, a.q_flags, a.n_queries, a.q_status, run, err);
+    rc = prove_plan(ws, st, p, a.q, a.q_status, run, err);
     if (rc) {
         (void)hipStreamSynchronize(st);
         return rc;
@@ -2351,29 +2270,21 @@ int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const uint8_t* d_keys,
     return rc;
 }
 
-// The forest pass of a caller that owns ws.io (phant_state_witness): everything device-resident, d_seg_first and d_roots required.
+// The forest pass of a caller that owns ws.io (phant_state_witness): everything device-resident, p.seg_first and p.roots required.
 // The emitted nodes are APPENDED to the host vectors (node_off holds one entry per node so far + 1), so two forests that reuse
 // t1 / t2 / pv / pvo one after the other end up in one set.
-int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
-                             const uint8_t* d_vals, const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first,
-                             uint32_t n_tries, uint8_t* d_roots, const uint8_t* d_qkeys, const uint32_t* d_qkey_off, const uint32_t* d_q_trie,
-                             const uint8_t* d_q_flags, uint32_t n_queries, std::vector<uint8_t>& nodes, std::vector<uint64_t>& node_off,
-                             std::string& err) {
+int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
+                             std::vector<uint64_t>& node_off, std::string& err) {
     ProveRun run;
-    int32_t rc = prove_plan(ws, st, d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries, d_roots, d_qkeys,
-                            d_qkey_off, d_q_trie, d_q_flags, n_queries, nullptr, run, err);
+    int32_t rc = prove_plan(ws, st, p, q, nullptr, run, err);
     if (rc) {
         (void)hipStreamSynchronize(st);
         return rc;
     }
     if (!run.total_nodes) return PHANT_OK;
-    TB_TRY(ws.pvo.reset(DevArena::round(run.nodes_len + 16) + DevArena::round(((size_t)run.total_nodes + 1) * 8) + 1024));
-    uint8_t* d_nodes = ws.pvo.take<uint8_t>(run.nodes_len + 16);
-    uint64_t* d_noff = ws.pvo.take<uint64_t>((size_t)run.total_nodes + 1);
-    if (ws.pvo.overflowed || !d_noff) {
-        err = "prover output arena sized too small (internal)";
-        return PHANT_E_DEVICE;
-    }
+    uint8_t* d_nodes = nullptr;
+    uint64_t* d_noff = nullptr;
+    if ((rc = lay_out_nodes(ws, st, run, true, true, d_nodes, d_noff, err)) != PHANT_OK) return rc;
     rc = prove_emit(st, run, d_nodes, d_noff, nullptr, err);
     if (rc) {
         (void)hipStreamSynchronize(st);
@@ -2390,90 +2301,48 @@ int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const uint8_t* d_ke
     return PHANT_OK;
 }
 
-int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, const uint32_t* key_off, const uint8_t* vals,
-                           const uint64_t* val_off, uint32_t n, const uint32_t* seg_first, uint32_t n_tries, ProveArgs& a, std::string& err) {
-    const uint32_t one[2] = {0, n};
-    if (!seg_first) seg_first = one;
-    const uint32_t nq = a.n_queries;
-    const uint64_t kb = n ? key_off[n] - key_off[0] : 0;
-    const uint64_t vb = n ? val_off[n] - val_off[0] : 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (key_off[i + 1] < key_off[i] || val_off[i + 1] < val_off[i]) {
-            err = "offsets not monotone";
-            return PHANT_E_INVALID_ARG;
+int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveArgs& a, std::string& err) {
+    const ProveQueries& q = a.q;
+    const uint32_t nq = q.n_queries, n_tries = h.n_tries;
+    const uint64_t qb = nq ? q.qkey_off[nq] - q.qkey_off[0] : 0;
+    uint8_t *d_roots = nullptr, *d_qkeys = nullptr, *d_qflags = nullptr, *d_qstatus = nullptr;
+    uint32_t *d_qoff = nullptr, *d_qtrie = nullptr, *d_first = nullptr;
+    // The queries ride with the pairs: their arrays lie behind the five of the forest and in front of the outputs, so that a small
+    // witness's inputs cross the bus in ONE copy.  The outputs keep a copy each: the prover's kernels do not write into the mirror.
+    const StagedPairs in = stage_pairs(ws, st, h, "prove_nodeset", err, [&]() -> int32_t {
+        for (uint32_t j = 0; j < nq; ++j) {
+            if (q.qkey_off[j + 1] < q.qkey_off[j]) return err = "query key offsets not monotone", PHANT_E_INVALID_ARG;
+            if (q.q_trie && q.q_trie[j] >= n_tries)
+                return err = "prove_nodeset: q_trie[" + std::to_string(j) + "] is not below n_tries", PHANT_E_INVALID_ARG;
         }
-        if (key_off[i + 1] - key_off[i] > 255) {
-            err = "key longer than 255 bytes";
-            return PHANT_E_UNSUPPORTED;
+        return PHANT_OK;
+    }, [&](auto& io) -> const void* {
+        d_qkeys = io.template take<uint8_t>(qb + 16);
+        d_qoff = io.template take<uint32_t>((size_t)nq + 1);
+        d_qtrie = io.template take<uint32_t>((size_t)nq + 1);
+        d_qflags = io.template take<uint8_t>((size_t)nq + 1);
+        d_roots = io.template take<uint8_t>((size_t)n_tries * 32);
+        d_qstatus = io.template take<uint8_t>((size_t)nq + 1);
+        d_first = io.template take<uint32_t>((size_t)n_tries + 1);
+        return d_qflags ? d_qflags + nq + 1 : nullptr;  // (the sizer hands out no addresses)
+    }, [&](StagedInputs& ins) {
+        ins.put(d_qkeys, qb ? q.qkeys + q.qkey_off[0] : nullptr, qb);
+        std::vector<uint32_t> qo;
+        uint32_t* rel = ins.twin(d_qoff);
+        if (!ins.staged) qo.resize((size_t)nq + 1), rel = qo.data();
+        if (rel) {
+            rel[0] = 0;
+            for (uint32_t j = 0; j <= nq && nq; ++j) rel[j] = q.qkey_off[j] - q.qkey_off[0];
         }
-    }
-    for (uint32_t s = 0; s < n_tries; ++s)
-        if (seg_first[s] > seg_first[s + 1] || seg_first[s + 1] > n) {
-            err = "seg_first not monotone";
-            return PHANT_E_INVALID_ARG;
-        }
-    if (seg_first[0] != 0 || seg_first[n_tries] != n) {
-        err = "seg_first must span [0, n]";
-        return PHANT_E_INVALID_ARG;
-    }
-    for (uint32_t j = 0; j < nq; ++j) {
-        if (a.qkey_off[j + 1] < a.qkey_off[j]) {
-            err = "query key offsets not monotone";
-            return PHANT_E_INVALID_ARG;
-        }
-        if (a.q_trie && a.q_trie[j] >= n_tries) {
-            err = "prove_nodeset: q_trie[" + std::to_string(j) + "] is not below n_tries";
-            return PHANT_E_INVALID_ARG;
-        }
-    }
-    const uint64_t qb = nq ? a.qkey_off[nq] - a.qkey_off[0] : 0;
-    uint8_t *d_keys, *d_vals, *d_roots, *d_qkeys, *d_qflags, *d_qstatus;
-    uint32_t *d_koff, *d_seg, *d_qoff, *d_qtrie, *d_first;
-    uint64_t* d_voff;
-    auto carve = [&](auto& ar) {
-        d_keys = ar.template take<uint8_t>(kb + 16);
-        d_koff = ar.template take<uint32_t>((size_t)n + 1);
-        d_vals = ar.template take<uint8_t>(vb + 16);
-        d_voff = ar.template take<uint64_t>((size_t)n + 1);
-        d_seg = ar.template take<uint32_t>((size_t)n_tries + 1);
-        d_roots = ar.template take<uint8_t>((size_t)n_tries * 32);
-        d_qkeys = ar.template take<uint8_t>(qb + 16);
-        d_qoff = ar.template take<uint32_t>((size_t)nq + 1);
-        d_qtrie = ar.template take<uint32_t>((size_t)nq + 1);
-        d_qflags = ar.template take<uint8_t>((size_t)nq + 1);
-        d_qstatus = ar.template take<uint8_t>((size_t)nq + 1);
-        d_first = ar.template take<uint32_t>((size_t)n_tries + 1);
-    };
-    {
-        ArenaSizer sz;
-        carve(sz);
-        TB_TRY(ws.io.reset(sz.bytes + 1024));
-        carve(ws.io);
-        if (ws.io.overflowed || !d_first) {
-            err = "prover staging arena sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
-    }
-    std::vector<uint32_t> ko((size_t)n + 1, 0), qo((size_t)nq + 1, 0);
-    std::vector<uint64_t> vo((size_t)n + 1, 0);
-    for (uint32_t i = 0; i <= n && n; ++i) {
-        ko[i] = key_off[i] - key_off[0];
-        vo[i] = val_off[i] - val_off[0];
-    }
-    for (uint32_t j = 0; j <= nq && nq; ++j) qo[j] = a.qkey_off[j] - a.qkey_off[0];
-    if (kb) TB_TRY(hipMemcpyAsync(d_keys, keys + key_off[0], kb, hipMemcpyHostToDevice, st));
-    if (vb) TB_TRY(hipMemcpyAsync(d_vals, vals + val_off[0], vb, hipMemcpyHostToDevice, st));
-    TB_TRY(hipMemcpyAsync(d_koff, ko.data(), ko.size() * 4, hipMemcpyHostToDevice, st));
-    TB_TRY(hipMemcpyAsync(d_voff, vo.data(), vo.size() * 8, hipMemcpyHostToDevice, st));
-    TB_TRY(hipMemcpyAsync(d_seg, seg_first, ((size_t)n_tries + 1) * 4, hipMemcpyHostToDevice, st));
-    if (qb) TB_TRY(hipMemcpyAsync(d_qkeys, a.qkeys + a.qkey_off[0], qb, hipMemcpyHostToDevice, st));
-    TB_TRY(hipMemcpyAsync(d_qoff, qo.data(), qo.size() * 4, hipMemcpyHostToDevice, st));
-    if (a.q_trie && nq) TB_TRY(hipMemcpyAsync(d_qtrie, a.q_trie, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    if (a.q_flags && nq) TB_TRY(hipMemcpyAsync(d_qflags, a.q_flags, nq, hipMemcpyHostToDevice, st));
-    // (pageable sources: hipMemcpyAsync has taken its copy when it returns)
+        if (!ins.staged) ins.put(d_qoff, rel, ((size_t)nq + 1) * 4);  // (a pageable source: the copy is taken when put() returns)
+        ins.put(d_qtrie, q.q_trie, (size_t)nq * 4);
+        ins.put(d_qflags, q.q_flags, nq);
+    });
+    if (in.rc) return in.rc;
+    TriePairs p = in.pairs;
+    p.roots = d_roots;
     ProveRun run;
-    int32_t rc = prove_plan(ws, st, d_keys, d_koff, kb, d_vals, d_voff, vb, n, d_seg, n_tries, d_roots, d_qkeys, d_qoff,
-                            a.q_trie ? d_qtrie : nullptr, a.q_flags ? d_qflags : nullptr, nq, d_qstatus, run, err);
+    int32_t rc = prove_plan(ws, st, p, ProveQueries{d_qkeys, d_qoff, q.q_trie ? d_qtrie : nullptr, q.q_flags ? d_qflags : nullptr, nq}, d_qstatus, run, err);
     if (rc) {
         (void)hipStreamSynchronize(st);
         return rc;
@@ -2483,15 +2352,7 @@ int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const uint8_t* keys, 
     const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
     uint8_t* d_nodes = nullptr;
     uint64_t* d_noff = nullptr;
-    if (fits && (a.nodes || a.node_off)) {  // the blob and its offsets at their exact sizes, in an arena of their own
-        TB_TRY(ws.pvo.reset(DevArena::round(run.nodes_len + 16) + DevArena::round(((size_t)run.total_nodes + 1) * 8) + 1024));
-        if (a.nodes) d_nodes = ws.pvo.take<uint8_t>(run.nodes_len + 16);
-        if (a.node_off) d_noff = ws.pvo.take<uint64_t>((size_t)run.total_nodes + 1);
-        if (ws.pvo.overflowed) {
-            err = "prover output arena sized too small (internal)";
-            return PHANT_E_DEVICE;
-        }
-    }
+    if (fits && (a.nodes || a.node_off) && (rc = lay_out_nodes(ws, st, run, a.nodes, a.node_off, d_nodes, d_noff, err)) != PHANT_OK) return rc;
     rc = prove_emit(st, run, d_nodes, d_noff, a.trie_first_node ? d_first : nullptr, err);
     if (rc) {
         (void)hipStreamSynchronize(st);
@@ -2577,8 +2438,7 @@ int32_t index_roots_host(Workspaces& ws, hipStream_t st, const uint8_t* const* i
         append_rlp_index_pairs(items[l], item_off[l], n[l], keys, key_off, vals, val_off);
         seg.push_back((uint32_t)(key_off.size() - 1));
     }
-    return trie_forest_host(ws, st, keys.data(), key_off.data(), vals.data(), val_off.data(), seg.back(), seg.data(), n_lists,
-                            roots_out, err);
+    return trie_forest_host(ws, st, HostPairs{keys.data(), key_off.data(), vals.data(), val_off.data(), seg.back(), seg.data(), n_lists}, roots_out, err);
 }
 
 int32_t index_root_host(Workspaces& ws, hipStream_t st, const uint8_t* items, const uint64_t* item_off, uint32_t n,
@@ -2603,15 +2463,14 @@ int32_t index_root_host(Workspaces& ws, hipStream_t st, const uint8_t* items, co
             key_off[i + 1] = 32 * (i + 1);
         }
         for (uint32_t i = 0; i <= n && n; ++i) val_off[i] = item_off[i] - item_off[0];
-        return trie_root_host(ws, st, keys.data(), key_off.data(), n ? items + item_off[0] : nullptr,
-                              val_off.data(), n, out, err);
+        return trie_forest_host(ws, st, HostPairs{keys.data(), key_off.data(), n ? items + item_off[0] : nullptr, val_off.data(), n}, out, err);
     }
     keys.reserve((size_t)n * 4);
     vals.reserve(n ? (size_t)(item_off[n] - item_off[0]) : 0);
     key_off.assign(1, 0);
     val_off.assign(1, 0);
     append_rlp_index_pairs(items, item_off, n, keys, key_off, vals, val_off);
-    return trie_root_host(ws, st, keys.data(), key_off.data(), vals.data(), val_off.data(), n, out, err);
+    return trie_forest_host(ws, st, HostPairs{keys.data(), key_off.data(), vals.data(), val_off.data(), n}, out, err);
 }
 
 }  // namespace phant

@@ -101,6 +101,52 @@ def test_mptize_device_form_matches_host_form_and_oracle(P, oracle):
     assert dev_root([b"\x01", b"\x02"], [b"a", b"b"]) == oracle.mptize([b"\x01", b"\x02"], [b"a", b"b"])  # (the ctx is fine)
 
 
+def test_host_forms_beyond_the_pinned_stage(P, oracle):
+    """Nine pairs with 1 MiB values: the inputs of the host forms exceed the 8 MiB pinned stage and cross the bus array by array
+    (staging.h: stage_pairs, its unstaged path) -- mptize against the oracle and the device form, phant_mpt_root_nodes over the same
+    pairs as three tries against three separate calls, prove_nodeset against its device form; then, on the same context, a 5-key
+    mptize and a 5-key prove_nodeset: the staged path after an arena that grew."""
+    import torch
+    from phant_amd import shard
+    from tests import prove_ref
+    M = P.mpt
+    rng = np.random.default_rng(77)
+    keys, _ = random_kv(rng, 9, 32, 1, 1)
+    vals = [rng.integers(0, 256, 1 << 20, dtype=np.uint8).tobytes() for _ in keys]
+    kv = [M.KeyVal(k, v) for k, v in zip(keys, vals)]
+    kb, ko = M._pack(keys, np.uint32)
+    vb, vo = M._pack(vals, np.uint64)
+    assert kb.nbytes + ko.nbytes + vb.nbytes + vo.nbytes > 8 << 20
+    dev = lambda a, dt: torch.from_numpy(a.astype(dt)).cuda()  # noqa: E731
+    d = [dev(kb, np.uint8), dev(ko, np.int32), dev(vb, np.uint8), dev(vo, np.int64)]
+    root = M.mptize(kv)
+    assert root == oracle.mptize(keys, vals)
+    assert M.mptize_dev(*d).cpu().numpy().tobytes() == root
+    seg = [0, 4, 4, 9]  # (the middle trie is empty)
+    got = shard.gpu_root_nodes(keys, vals, seg)
+    assert [r for r, _ in got] == [M.mptize(kv[a:b]) for a, b in zip(seg, seg[1:])]
+    queries = [keys[0], keys[5], keys[8]]
+    host = M.prove_nodeset(kv, queries)
+    qb, qo = M._pack(queries, np.uint32)
+    tn, nl = host.total_nodes, len(host.nodes)
+    nodes, off = torch.zeros(nl, dtype=torch.uint8).cuda(), torch.zeros(tn + 1, dtype=torch.int64).cuda()
+    roots, st = torch.zeros(32, dtype=torch.uint8).cuda(), torch.zeros(3, dtype=torch.uint8).cuda()
+    assert M.prove_nodeset_dev(*d, None, dev(qb, np.uint8), dev(qo, np.int32), None, None, nodes, off, None, roots, st) == (tn, nl)
+    torch.cuda.synchronize()
+    assert tn > 0 and nodes.cpu().numpy().tobytes() == host.nodes.tobytes()
+    assert off.cpu().numpy().astype(np.uint64).tobytes() == host.node_off.tobytes()
+    assert roots.cpu().numpy().tobytes() == host.roots.tobytes() == root and np.array_equal(st.cpu().numpy(), host.q_status)
+    # the staged path again, on the arena that grew
+    k5, v5 = random_kv(rng, 5, 32, 1, 80)
+    kv5 = [M.KeyVal(k, v) for k, v in zip(k5, v5)]
+    assert M.mptize(kv5) == oracle.mptize(k5, v5)
+    q5 = [k5[1], k5[4], rng.integers(0, 256, 32, dtype=np.uint8).tobytes()]
+    p5 = M.prove_nodeset(kv5, q5)
+    want = prove_ref.oracle_union(oracle.Trie(k5, v5), q5)
+    assert set(p5.trie_nodes(0)) == want and p5.total_nodes == len(want)
+    assert p5.roots[0].tobytes() == oracle.mptize(k5, v5) and np.array_equal(p5.q_status, prove_ref.statuses(k5, q5))
+
+
 @pytest.mark.parametrize("n", [1_000_000, 3_000_000])
 def test_mptize_big_tries_vs_oracle(P, oracle, n):
     """What only a big trie reaches in trie_build.hip: a crowded sparse depth bin in the one-block slot class with its fallback
