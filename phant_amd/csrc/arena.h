@@ -69,7 +69,7 @@ struct ArenaSizer {
 };
 
 // Switches of the trie hasher and of the state root's key sort (per ctx; set through include/phant_gpu_diag.h's phant_diag_set by
-// tests and tools, never read from the environment).  -1 / 0 / false = the library's own choice (the constants in trie_build.hip).
+// tests and tools, never read from the environment).  -1 / 0 / false = the library's own choice (trie_plan.h: the constants, resolve_choices).
 struct TrieTune {
     bool no_side = false;            // never run the deepest bins on the helper stream beside the leaves (A/B)
     int64_t side_min_keys = -1;      // ... from this many keys on (tests)
@@ -168,12 +168,25 @@ struct Workspaces {
         return e;
     }
     // the small pass's persistent words (trie_build.hip: the call's flags, a count of workgroups), zeroed when allocated and by
-    // every call's last workgroup
+    // every call's last workgroup.  small_dirty: a call left its kernels on a way other than that one (a failed launch, a stream in
+    // error) -- the next small call zeroes the words itself before it launches.
     uint32_t* small_state = nullptr;
+    bool small_dirty = false;
     hipError_t ensure_small(size_t bytes) {
         if (small_state) return hipSuccess;
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&small_state), bytes);
+        if (e != hipSuccess) return e;
+        e = hipMemset(small_state, 0, bytes);
+        if (e != hipSuccess) {  // (never words nobody has zeroed)
+            (void)hipFree(small_state);
+            small_state = nullptr;
+        }
+        return e;
+    }
+    hipError_t rezero_small(size_t bytes, hipStream_t st) {
+        hipError_t e = hipStreamSynchronize(st);  // (whatever of the call that went wrong is still running writes them)
         if (e == hipSuccess) e = hipMemset(small_state, 0, bytes);
+        if (e == hipSuccess) small_dirty = false;
         return e;
     }
     // the pinned twin of a device address inside `io`

@@ -37,19 +37,18 @@
 #include "launch.h"
 #include "rlp.h"
 #include "staging.h"
+#include "trie_plan.h"
 
 namespace phant {
 namespace {
 
+static_assert(PLAN_RATE == RATE && PLAN_RATE_DWORDS == RATE_DWORDS, "trie_plan.h plans with the sponge's rate");
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t BRANCH_VALUE = 0xfffffffeu;  // leaf_ps marker: key is a branch's value
 constexpr int MAX_DEPTH_BINS = 512;             // nibble depth <= 2*255
 constexpr int INF_LCP = 0x7fffffff;
-constexpr uint32_t FAN = 16;      // fan-out of the min-tree: a group of children is one 64-byte line
-constexpr int MAX_LEVELS = 8;      // 16^8 boundaries
 constexpr uint32_t N_COUNTERS = 8u + 2u * (uint32_t)MAX_DEPTH_BINS;
 constexpr uint32_t SIDE_MAX_NODES = 65536;         // nodes in the bins that run beside the leaves (one generation of four-block workgroups)
-constexpr uint32_t CROWDED_BIN = 4u * 256u * 64u;  // nodes: above it a bin in four-block slots (one wave per SIMD) no longer fits the chip at once
 // The pinned mailbox (arena.h) as order_kernel's first workgroup fills it: the counters at [0, N_COUNTERS), then the depth from which
 // the bins run beside the leaves (or -1), then the word the host waits for.
 constexpr uint32_t MAILBOX_DEEP_FROM = N_COUNTERS, MAILBOX_READY = N_COUNTERS + 1u, MAILBOX_ORDERED = N_COUNTERS + 2u, MAILBOX_DONE = N_COUNTERS + 3u;
@@ -682,8 +681,9 @@ PHANT_DEV void deliver(const TrieDev& t, uint32_t parent, uint32_t nib, uint32_t
     }
 }
 
-constexpr uint32_t BRANCH_STAGE_BYTES_ = 4u * RATE;        // (= BRANCH_STAGE_BYTES below)
-constexpr uint32_t BRANCH_STAGE_DW_ = 4u * RATE_DWORDS + 1u;  // (= BRANCH_STAGE_DW below)
+// One wave per workgroup: the LDS slot of a lane holds BRANCH_STAGE_BLOCKS = four rate blocks (a full 17-item branch is 532 bytes).
+constexpr uint32_t BRANCH_STAGE_DW = BRANCH_STAGE_BLOCKS * RATE_DWORDS + 1u;  // 137: odd
+constexpr uint32_t BRANCH_STAGE_BYTES = BRANCH_STAGE_BLOCKS * RATE;
 
 // LeafNode, mpt.zig:54-56 / :254-261: what key i's leaf looks like ...
 struct LeafPlan {
@@ -692,7 +692,6 @@ struct LeafPlan {
     uint64_t vlen, payload;
     const uint8_t* v;
 };
-constexpr uint32_t LEAF_STAGE_DW = RATE_DWORDS + 1u;  // 35 (odd): one rate block of LDS per lane (a state-trie leaf is ~112 bytes)
 PHANT_DEV LeafPlan leaf_plan(const TrieDev& t, const uint32_t i) {
     LeafPlan p;
     p.live = i < t.n && t.leaf_ps[i] != BRANCH_VALUE;
@@ -744,7 +743,7 @@ PHANT_DEV void leaf_emit_scratch(const TrieDev& t, const uint32_t i, const LeafP
 // Three size classes: under one rate block (a state-trie leaf: 256 lanes per workgroup, 35 dwords of LDS each), under four
 // (a transaction, a receipt: leaf_big_kernel, 64 lanes per workgroup with the branch kernel's 137-dword slots), the rest
 // through the scratch blob (byte stores to global memory: slow, rare).
-constexpr uint32_t LEAF_BIG_MAX = BRANCH_STAGE_BYTES_;  // 4 x 136: the padding needs a byte
+constexpr uint32_t LEAF_BIG_MAX = BRANCH_STAGE_BYTES;  // 4 x 136: the padding needs a byte
 // `list` (with its count on the device: a grid that strides) = the keys under the deepest nodes, which go first when the deepest
 // bins are hashed next to the other leaves; that pass (no list) then skips them (t.deep_from).
 __global__ void __launch_bounds__(256) leaf_kernel(TrieDev t, const uint32_t* list, const uint32_t* dev_count) {
@@ -844,12 +843,6 @@ PHANT_DEV uint32_t put_extension(uint8_t* xenc, const TrieDev& t, uint32_t l, ui
     }
     return (uint32_t)(x - xenc);
 }
-
-// One wave per workgroup: the LDS slot of a lane holds four rate blocks (a full 17-item branch is 532 bytes).
-constexpr uint32_t BRANCH_LANES = 64;
-constexpr uint32_t BRANCH_STAGE_BLOCKS = 4;
-constexpr uint32_t BRANCH_STAGE_DW = BRANCH_STAGE_BLOCKS * RATE_DWORDS + 1u;  // 137: odd
-constexpr uint32_t BRANCH_STAGE_BYTES = BRANCH_STAGE_BLOCKS * RATE;
 
 // what the branch node with representative boundary order[at] looks like (live: there is one)
 struct BranchPlan {
@@ -1121,7 +1114,6 @@ __global__ void __launch_bounds__(256 / BLOCKS) branch_kernel(TrieDev t, const u
 // sponge each (coop_sponge.hip.h: 5.8 us per permutation).  A twentieth of the states per second of the lane-per-node kernels -- for bins of at most COOP_MAX_NODES nodes
 // (two waves per SIMD): the three or four levels at the top of every trie, the sparse ones at its bottom.  A node with a value, under an extension, or
 // whose bytes the caller wants (a sharded trie's root) takes the general way, on the half wave's first lane.
-constexpr uint32_t COOP_MAX_NODES = 4096;  // (512 / 2 048 / 4 096 / 8 192 measured: 10 000 keys 0.288 / 0.267 / 0.247 / 0.250 ms, a million 0.669 / 0.663 / 0.651 / 0.654)
 // Keccak-256 over the `nb` padded rate blocks at `buf` (digest: the words of lanes 0 .. 3 of the half).  The two halves of a wave
 // go through the loop together, `nb_max` trips (the longer one's): the shorter half keeps its digest from its own last block.
 PHANT_DEV void coop_keccak256(const CoopLane& c, const uint32_t* buf, uint32_t nb, uint32_t nb_max, uint32_t& dlo, uint32_t& dhi) {
@@ -1267,7 +1259,6 @@ __global__ void __launch_bounds__(256) branch_coop_kernel(TrieDev t, uint32_t be
 // The same with a WAVE per node and the sponge of coop_sponge.hip.h's second form (lane = x + 8 y, theta on DPP and row swaps: 3.8-5.2
 // us per permutation up to two waves per SIMD against the half wave's 4.9-8.4 at the same node count): bins of up to WAVE_MAX_NODES
 // nodes.  Everything but the lanes' roles is wave-uniform here.
-constexpr uint32_t WAVE_MAX_NODES = 2048;
 PHANT_DEV void wave_keccak256(const WaveLane& c, const uint32_t* buf, uint32_t nb, uint32_t& lo, uint32_t& hi) {
     lo = hi = 0u;
     for (uint32_t k = 0; k < nb; ++k) {
@@ -1412,14 +1403,11 @@ __global__ void __launch_bounds__(256) branch_wave_kernel(TrieDev t, uint32_t be
 // (Measured on the way, profiles/r6_explore/NOTES.md section 3: the same phases inside ONE kernel with a barrier across the grid
 // between them -- 2 us faster than launches of their own up to ~100 workgroups, 40 us slower at 300, and a kernel that waits for
 // workgroups that may not be resident; and a launch per trie depth, which is what the general pass does.)
-constexpr uint32_t SMALL_MAX_KEYS = 4096;       // (what the first kernel's LDS holds)
-constexpr uint32_t SMALL_SURE_KEYS = 2048;      // up to here whatever the leaves are; beyond, where the mean value is a rate block or more
-constexpr uint32_t SMALL_MAX_WGS = 512;
+// (SMALL_MAX_KEYS, SMALL_SURE_KEYS, SMALL_MAX_WGS, SMALL_LCP_INTS: trie_plan.h)
 constexpr uint32_t SMALL_HEAD_LANES = 1024;
 constexpr uint32_t SMALL_BUF_BLOCKS = 16;
 constexpr uint32_t SMALL_BUF_DW = SMALL_BUF_BLOCKS * RATE_DWORDS + 4u;  // (a multiple of four: a wave's buffer starts on a 16-byte boundary)
 constexpr uint32_t SMALL_PRE_BYTES = 288;  // list header (<= 9) + hex-prefix string (<= 3 + 256) + value header (<= 9), rounded
-constexpr uint32_t SMALL_LCP_INTS = (SMALL_MAX_KEYS + 1u + FAN - 1u) / FAN * FAN + 512u;  // level 0 + the levels above it (272 + 32 + 16 at the most) + slack
 static_assert(SMALL_BUF_DW >= BRANCH_STAGE_DW, "a wave's buffer holds a branch node");
 // Workspaces::small_state, in words: the flags of the call (lcp_element's and the scratch blob's: t.counters points here) and the
 // count of workgroups that have left the second kernel -- zeroed when allocated and by every call's last workgroup
@@ -1549,6 +1537,14 @@ __global__ void __launch_bounds__(256) small_climb_kernel(TrieDev t, uint32_t* s
             if (t.leaf_ps[i] == BRANCH_VALUE) continue;  // (the value of a branch: that node carries it)
             leaf_wave_node(t, i, s_buf[wv], s_pre[wv], l);
             uint32_t node = t.leaf_parent[i];
+            // The hand-off from a child's wave to the wave that goes on with the parent.  The child: PLAIN stores of its reference
+            // (slot_bytes, slot_len), __threadfence, a RELAXED atomicAdd on the parent's count.  The wave whose add makes the count
+            // complete: __threadfence, then PLAIN loads of all the children's references.  No store-release / load-acquire pair
+            // is spelled out: the protocol relies on __threadfence being an agent-scope release fence before the atomic and an
+            // agent-scope acquire fence after it (on gfx950: the wave's stores written back to L2 and waited for in front of the
+            // atomic, which is resolved in L2; its L1 lines dropped behind it, so that the loads go to L2) -- the fences around
+            // a relaxed atomic give every earlier child's stores a happens-before to the last child's loads.  It runs under
+            // tests/test_gpu_trie_choices.py::test_small_pass_hand_off_repeated.
             while (node != NONE) {
                 __threadfence();  // (the reference before the count)
                 uint32_t arrived = 0;
@@ -1585,7 +1581,6 @@ __global__ void __launch_bounds__(256) small_climb_kernel(TrieDev t, uint32_t* s
     if (tid == 0) *reinterpret_cast<volatile uint32_t*>(t.mailbox + MAILBOX_DONE) = t.mailbox_tag;
 }
 
-static_assert(BRANCH_STAGE_BYTES_ == BRANCH_STAGE_BYTES && BRANCH_STAGE_DW_ == BRANCH_STAGE_DW, "one slot size for big leaves and branches");
 __global__ void __launch_bounds__(BRANCH_LANES) leaf_big_kernel(TrieDev t) {
     __shared__ uint32_t s_stage[BRANCH_LANES * BRANCH_STAGE_DW];
     const uint32_t i = blockIdx.x * BRANCH_LANES + threadIdx.x;
@@ -1620,142 +1615,89 @@ inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 
 }  // namespace
 
-// Up to this many keys the slot tables and the scratch blob are sized for the worst case (a branch node per key: 1.3 KB per key against
-// ~0.45 KB for uniformly spread keys -- 10.6 GB at the limit) so that the leaves need not wait for the host to learn the node count.
-constexpr uint64_t LEAVES_AHEAD_MAX_KEYS = 8u << 20;
-constexpr uint32_t SIDE_MIN_KEYS = 400000;    // below it the leaves are too few to hide the deepest bins behind (200 000 keys: 0.497 vs 0.491 ms without)
-constexpr uint32_t SIDE_LEAF_LDS = 20480;     // bytes of unused dynamic LDS per leaf workgroup meanwhile: TWO of them per CU instead of four (with three,
-                                              // 5 or 6 KB, the bins beside them still starved: 146-162 us for a bin of 116 nodes)
-constexpr uint32_t FALLBACK_GRID = 1024;           // workgroups of a bin's fallback pass (its count is on the device)
+// What the driver chooses -- the pass, the leaves ahead or not, the tables' sizes, every bin's kernel and grid, the knobs -- is stated
+// in trie_plan.h; here the runtime is asked, the plan is launched and the mailbox is watched.
 
-// The t2 arena: slot tables by dense node id (16 x 32 bytes a node) + the scratch blob of the nodes that take the general way.
-static int32_t lay_out_tables(Workspaces& ws, hipStream_t st, TrieDev& t, uint64_t nodes, uint64_t cap, std::string& err) {
-    const LaidOut r = lay_out_arena(ws.t2, st, [&](auto& a) {
-        t.slot_bytes = a.template take<uint8_t>((size_t)nodes * 16 * 32);
-        t.scratch = a.template take<uint8_t>(cap);
-    });
-    t.scratch_cap = cap;
-    return lay_out_status(r, "trie", "t2", err);
+// ---- the mailbox, the guard, the flags ----
+// A call's tag: one more than the last call's (which ended with a synchronisation: nothing else writes the word), never 0.
+static uint32_t next_mailbox_tag(const volatile uint32_t* mbox) {
+    const uint32_t tag = mbox[MAILBOX_READY] + 1u;
+    return tag ? tag : 1u;
 }
-
-// The small pass (small_head_kernel, small_climb_kernel): t holds the inputs, the outputs and the t1 arena's arrays.
-static int32_t small_forest(Workspaces& ws, hipStream_t st, TrieDev t, uint64_t total_key_bytes, uint64_t total_val_bytes, std::string& err,
-                            TrieDev* keep) {
-    const uint32_t n = t.n;
-    TB_TRY(ws.ensure_small(SS_WORDS * 4u));
-    {   // slot tables by boundary (a node's dense id is its boundary: < n)
-        const uint64_t cap = total_val_bytes + total_key_bytes + (uint64_t)n * (32 + 3 + 16 * 33 + 16 + 48 + 127 + 16) + 4096;
-        const int32_t rc = lay_out_tables(ws, st, t, n, cap, err);
-        if (rc) return rc;
-    }
-    uint32_t* const state = ws.small_state;
-    t.counters = state + SS_COUNTERS;
-    t.first_flag = nullptr;
-    volatile uint32_t* const mbox = ws.mailbox;
-    t.mailbox = ws.mailbox;
-    t.mailbox_tag = mbox[MAILBOX_READY] + 1u;
-    if (t.mailbox_tag == 0u) t.mailbox_tag = 1u;
-    mbox[MAILBOX_READY] = t.mailbox_tag;  // (the small pass has no use for this word but the next call counts on from it)
-    struct MainGuard {
-        hipStream_t s;
-        bool armed = true;
-        ~MainGuard() {
-            if (armed) (void)hipStreamSynchronize(s);
+// Until a kernel of this call has raised mbox[word] to its tag: the host watches the word -- a look at the stream now and then, so
+// that a launch that failed cannot keep it waiting.  `what`: the call's "counters" (the general pass) or "flags" (the small one).
+static int32_t wait_mailbox(const volatile uint32_t* mbox, uint32_t word, uint32_t tag, hipStream_t st, const char* what, std::string& err) {
+    for (uint32_t spins = 1; mbox[word] != tag; ++spins) {
+        if (spins % 4096u) continue;
+        const hipError_t q = hipStreamQuery(st);
+        if (q == hipErrorNotReady) continue;
+        TB_TRY(q);
+        if (mbox[word] != tag) {  // (the stream is through and the word is not there)
+            err = std::string("the trie builder's ") + what + " did not reach the mailbox (internal)";
+            return PHANT_E_DEVICE;
         }
-    } main_guard{st};
-    auto wait_done = [&]() -> int32_t {
-        for (uint32_t spins = 1; mbox[MAILBOX_DONE] != t.mailbox_tag; ++spins) {
-            if (spins % 4096u) continue;
-            const hipError_t q = hipStreamQuery(st);
-            if (q == hipErrorNotReady) continue;
-            TB_TRY(q);
-            if (mbox[MAILBOX_DONE] != t.mailbox_tag) {
-                err = "the trie builder's flags did not reach the mailbox (internal)";
-                return PHANT_E_DEVICE;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return PHANT_OK;
-    };
-    const uint32_t G = std::max(1u, std::min(SMALL_MAX_WGS, (n + 3u) / 4u));
-    hipLaunchKernelGGL(small_head_kernel, dim3(1), dim3(SMALL_HEAD_LANES), 0, st, t);
-    hipLaunchKernelGGL(small_climb_kernel, dim3(G), dim3(256), 0, st, t, state);
-    TB_TRY(hipGetLastError());
-    {
-        const int32_t rc = wait_done();
-        if (rc) return rc;
     }
-    main_guard.armed = false;
-    if (ws.mailbox[1] & ERR_KEY_RANGE) {
+    std::atomic_thread_fence(std::memory_order_acquire);  // (what lies behind the word is read after it)
+    return PHANT_OK;
+}
+// Kernels of a call may be in a stream when something fails: whatever the way out, an armed guard waits for the stream before the
+// arenas can be handed to another call.
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    bool armed = false;
+    void arm(hipStream_t on) {
+        s = on;
+        armed = true;
+    }
+    ~StreamGuard() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+// counters[1] (lcp_element's refusals) and counters[2] (the scratch blob's overflow) as the mailbox brings them
+static int32_t flags_status(uint32_t flags, uint32_t overflow, std::string& err) {
+    if (flags & ERR_KEY_RANGE) {
         err = "key longer than 255 bytes, or key offsets not monotone";
         return PHANT_E_INVALID_ARG;
     }
-    if (ws.mailbox[1] & ERR_UNSORTED) {
+    if (flags & ERR_UNSORTED) {
         err = "keys are not strictly increasing (mpt.zig:39)";
         return PHANT_E_UNSORTED;
     }
-    if (ws.mailbox[2]) {
+    if (overflow) {
         err = "trie scratch overflow (internal bound too small)";
         return PHANT_E_DEVICE;
     }
-    if (keep) *keep = t;
     return PHANT_OK;
 }
 
-// Device-side forest build; all pointers device memory, except roots_host.
-// keep (optional): the pass's view of its tables as they stand when it returns -- the prover's input (trie_prove.hip.h); they
-// live in the t1 / t2 arenas until the next call resets those.
-static int32_t forest_device(Workspaces& ws, hipStream_t st, const TriePairs& p, std::string& err, const RootNodes& nodes = {},
-                             TrieDev* keep = nullptr) {
-    TB_TRY(ws.ensure_mailbox());
-    const uint32_t n = p.n, n_tries = p.n_tries;
-    const uint64_t total_key_bytes = p.key_bytes, total_val_bytes = p.val_bytes;
+// ---- one call: its stages in the order they run (general_forest and, below, forest_device are the sequence) ----
+namespace {
+struct ForestCall {
+    Workspaces& ws;
+    hipStream_t st;
+    uint64_t key_bytes, val_bytes;
+    TrieChoices ch;
     TrieDev t{};
-    t.root_enc = nodes.enc;
-    t.root_enc_len = nodes.len;
-    t.root_enc_cap = nodes.cap;
-    t.keys = p.keys;
-    t.key_off = p.key_off;
-    t.vals = p.vals;
-    t.val_off = p.val_off;
-    t.n = n;
-    t.seg_first = p.seg_first;
-    t.n_tries = n_tries;
-    t.roots = p.roots;
-    ws.trie_stats = TrieStats{};  // (phant_trie_stats: what THIS call did)
-    TrieStats& stats = ws.trie_stats;
-    stats.n = n;
-    if (n >= 0x7fffffffu) {  // (identify_element keeps a bit of a boundary index for itself)
-        err = "more than 2^31 - 2 keys in one call";
-        return PHANT_E_UNSUPPORTED;
-    }
-    if (n == 0) {
-        hipLaunchKernelGGL(fill_empty_roots_kernel, dim3(blocks(n_tries)), dim3(256), 0, st, p.roots, n_tries);
-        TB_TRY(hipGetLastError());
-        if (keep) *keep = t;
-        return PHANT_OK;
-    }
+    bool ahead = false;
+    // what order_kernel handed over through the mailbox (read_counters), and the plan made from it
+    uint32_t cnt[N_COUNTERS];
+    int deep_from = -1;
+    uint32_t depth_begin[MAX_DEPTH_BINS];
+    BinLaunch bin[MAX_DEPTH_BINS];       // (of the non-empty bins)
+    StreamGuard main_guard, side_guard;  // (the helper stream is waited for first)
+    // (a constructor, so that the 18 KB of arrays are not cleared for a call that may be the small pass's 100 us: read_counters fills them)
+    ForestCall(Workspaces& w, hipStream_t s, const TriePairs& p) : ws(w), st(s), key_bytes(p.key_bytes), val_bytes(p.val_bytes), ch(resolve_choices(w.tune)) {}
 
-    // the min-tree's levels: level 0 = the n + 1 lcp values, every level padded to whole groups, the top level ONE group
-    size_t tree_ints = 0;
-    {
-        auto pad = [](uint64_t v) { return (uint32_t)((v + FAN - 1u) / FAN * FAN); };
-        t.lvl_size[0] = pad((uint64_t)n + 1);
-        t.lvl_off[0] = 0;
-        t.n_lvl = 1;
-        while (t.lvl_size[t.n_lvl - 1u] > FAN) {
-            t.lvl_size[t.n_lvl] = pad(t.lvl_size[t.n_lvl - 1u] / FAN);
-            t.lvl_off[t.n_lvl] = (uint32_t)tree_ints;
-            tree_ints += t.lvl_size[t.n_lvl];
-            ++t.n_lvl;
-        }
-    }
-    {
+    // The t1 arena: the per-key and per-boundary arrays, the min-tree's levels as `lv` sizes them.
+    int32_t lay_out_t1(const TreeLevels& lv, std::string& err) {
+        const uint32_t n = t.n;
+        for (uint32_t k = 0; k < lv.n_lvl; ++k) t.lvl_size[k] = lv.size[k], t.lvl_off[k] = lv.off[k];
+        t.n_lvl = lv.n_lvl;
         const size_t n1 = (size_t)n + 1;
         const int32_t rc = lay_out_status(lay_out_arena(ws.t1, st, [&](auto& a) {
             t.first_flag = a.template take<uint8_t>(n1);
             t.lcp = a.template take<int32_t>(t.lvl_size[0]);
-            t.tree = a.template take<int32_t>(tree_ints + FAN);
+            t.tree = a.template take<int32_t>(lv.tree_ints + FAN);
             t.dense = a.template take<uint32_t>(n1);
             t.nd_l = a.template take<uint32_t>(n1);
             t.nd_pd = a.template take<int32_t>(n1);
@@ -1775,217 +1717,185 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const TriePairs& p,
             t.cursor = a.template take<unsigned long long>(1);
         }), "trie", "t1", err);
         if (rc) return rc;
-        stats.cursor_off = (size_t)(reinterpret_cast<const uint8_t*>(t.cursor) - ws.t1.base);
-        stats.has_cursor = true;
-    }
-
-    // head (roots, counters, a forest's start flags) -> [first_flag] -> lcp (+ markers, + the min-tree's padding): three or two
-    // launches where there were five.  ONE trie has no start but key 0 and goes without the flags.
-    {
-        // Measured (profiles/r6_explore/NOTES.md section 3): one-block leaves (a state trie's) -- the two passes level at 2 048 keys, the
-        // general one ahead beyond (0.19 against 0.30 ms at 4 096); a block's lists (values of 50 .. 700 bytes: several permutations a
-        // leaf, which a wave's sponge runs at twice a lane's pace) -- ahead up to 3 x 1 000 items, level at 3 x 1 400.
-        const bool fits = n <= SMALL_MAX_KEYS && (size_t)t.lvl_size[0] + tree_ints + FAN <= SMALL_LCP_INTS;  // (the first kernel's LDS)
-        const bool by_default = fits && (n <= SMALL_SURE_KEYS || total_val_bytes >= (uint64_t)RATE * n);
-        const bool small = ws.tune.small_max_keys >= 0 ? fits && n <= (uint64_t)ws.tune.small_max_keys : by_default;
-        if (small) {
-            stats.pass = 1u;
-            return small_forest(ws, st, t, total_key_bytes, total_val_bytes, err, keep);
-        }
-        stats.pass = 2u;
-    }
-    if (n_tries == 1) t.first_flag = nullptr;
-    {
-        uint64_t lanes = N_COUNTERS;
-        if (n_tries > lanes) lanes = n_tries;
-        if (t.first_flag && (uint64_t)n + 1 > lanes) lanes = (uint64_t)n + 1;
-        hipLaunchKernelGGL(head_kernel, dim3(blocks(lanes)), dim3(256), 0, st, t);
-    }
-    if (t.first_flag) hipLaunchKernelGGL(first_flag_kernel, dim3(blocks(n_tries)), dim3(256), 0, st, t);
-    hipLaunchKernelGGL(lcp_kernel, dim3(blocks(t.lvl_size[0])), dim3(256), 0, st, t);
-    for (uint32_t base = 0; base + 1u < t.n_lvl; base += 3u) {  // (the grid covers the widest of the three levels it writes)
-        uint32_t g = (t.lvl_size[base + 1u] + 255u) / 256u;
-        if (base + 2u < t.n_lvl && (t.lvl_size[base + 2u] + FAN - 1u) / FAN > g) g = (t.lvl_size[base + 2u] + FAN - 1u) / FAN;
-        if (base + 3u < t.n_lvl && t.lvl_size[base + 3u] > g) g = t.lvl_size[base + 3u];
-        hipLaunchKernelGGL(tree_levels_kernel, dim3(g), dim3(256), 0, st, t, base);
-    }
-    hipLaunchKernelGGL(identify_kernel, dim3((n + COUNT_BLOCK - 1u) / COUNT_BLOCK), dim3(COUNT_BLOCK), 0, st, t);
-    // order_kernel goes straight behind it and hands the counters over through the mailbox while it runs (see there); the host
-    // watches the word it raises -- a look at the stream now and then, so that a launch that failed cannot keep it waiting
-    {
-        const uint32_t side_min = ws.tune.side_min_keys >= 0 ? (uint32_t)std::min<int64_t>(ws.tune.side_min_keys, 0xffffffffll) : SIDE_MIN_KEYS;
-        t.side_ok = (!ws.tune.no_side && n >= side_min) ? 1u : 0u;
-    }
-    // The slot tables and the scratch blob: sized for n_rep = n (a node has two children at least) when that is affordable, so that
-    // the bulk of the leaves can be queued behind order_kernel at once -- else from the n_rep the mailbox brings, the leaves after it.
-    // leaves: list hdr (<=9) + HP (<= 3 + key bytes + 1) + value (<= 9 + len), 4-byte rounded;
-    // branches: <= 3 + 16*33 + value; extensions <= 48 + key bytes / 2
-    auto size_tables = [&](uint64_t reps) -> int32_t {
-        const uint64_t max_key = 255;
-        const uint64_t cap = total_val_bytes + total_key_bytes + (uint64_t)n * 32 + reps * (3 + 16 * 33 + 16 + 48 + max_key / 2 + 16) + 4096;
-        return lay_out_tables(ws, st, t, reps, cap, err);
-    };
-    const uint64_t ahead_max_keys = ws.tune.ahead_max_keys >= 0 ? (uint64_t)ws.tune.ahead_max_keys : LEAVES_AHEAD_MAX_KEYS;
-    bool ahead = n <= ahead_max_keys;
-    // (a leaf workgroup's static LDS + this must stay within the 64 KiB a launch gets without opting in)
-    const uint32_t side_lds_knob = ws.tune.side_lds >= 0 ? (uint32_t)std::min<int64_t>(ws.tune.side_lds, 65536 - 4 * 256 * (int)LEAF_STAGE_DW) : SIDE_LEAF_LDS;
-    if (t.side_ok) TB_TRY(ws.ensure_side());
-    if (ahead) {
-        // The worst-case tables are ~3 x what the trie will need (1.3 KB against ~0.45 KB per key).  Where that much is not to be
-        // had -- torch sharing the device, several ctxs or slots -- the call falls back to what it did before the leaves went
-        // ahead: tables sized from the node count the mailbox brings, the leaves behind it.
-        size_t free_b = 0, total_b = 0;
-        const uint64_t worst = (uint64_t)n * (16 * 32 + 3 + 16 * 33 + 16 + 48 + 127 + 16 + 32) + total_val_bytes + total_key_bytes;
-        if (worst > ws.t2.cap && hipMemGetInfo(&free_b, &total_b) == hipSuccess && worst > (uint64_t)free_b + ws.t2.cap) {
-            ahead = false;
-        } else {
-            const int32_t rc = size_tables(n);
-            if (rc == PHANT_E_OOM) {
-                (void)hipGetLastError();  // (the failed hipMalloc's sticky error)
-                err.clear();
-                ahead = false;
-            } else if (rc) {
-                return rc;
-            }
-        }
-    }
-    volatile uint32_t* const mbox = ws.mailbox;
-    t.mailbox = ws.mailbox;
-    t.mailbox_tag = mbox[MAILBOX_READY] + 1u;  // (the previous call ended with a synchronisation: nothing else writes the word)
-    if (t.mailbox_tag == 0u) t.mailbox_tag = 1u;
-    // (from here on kernels of this call may be in the stream when something fails: whatever the way out, the stream is waited for
-    // before the arenas can be handed to another call -- the good way out ends on MAILBOX_DONE and has nothing left to wait for)
-    struct MainGuard {
-        hipStream_t s;
-        bool armed = true;
-        ~MainGuard() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } main_guard{st};
-    hipLaunchKernelGGL(order_kernel, dim3((n + COUNT_BLOCK - 1u) / COUNT_BLOCK), dim3(COUNT_BLOCK), 0, st, t);
-    // (the bulk of the leaves: with room for the bins beside them wherever order_kernel MAY decide for such bins -- from SIDE_MIN_KEYS
-    // keys on the leaf workgroups carry the idle LDS, two of them a CU instead of four, also in the rare trie whose deepest bins
-    // turn out too crowded to run beside them: the leaf kernel is LDS- and latency-bound at either occupancy, measured +-1 %)
-    if (ahead) hipLaunchKernelGGL(leaf_kernel, dim3(blocks(n)), dim3(256), t.side_ok ? side_lds_knob : 0u, st, t, nullptr, nullptr);
-    TB_TRY(hipGetLastError());
-    auto wait_for = [&](uint32_t word) -> int32_t {
-        for (uint32_t spins = 1; mbox[word] != t.mailbox_tag; ++spins) {
-            if (spins % 4096u) continue;
-            const hipError_t q = hipStreamQuery(st);
-            if (q == hipErrorNotReady) continue;
-            TB_TRY(q);
-            if (mbox[word] != t.mailbox_tag) {  // (the stream is through and the word is not there)
-                err = "the trie builder's counters did not reach the mailbox (internal)";
-                return PHANT_E_DEVICE;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);  // (the counters behind the word are read after it)
+        ws.trie_stats.cursor_off = (size_t)(reinterpret_cast<const uint8_t*>(t.cursor) - ws.t1.base);
+        ws.trie_stats.has_cursor = true;
         return PHANT_OK;
-    };
-    {
-        const int32_t rc = wait_for(MAILBOX_READY);
-        if (rc) return rc;
     }
-    const std::vector<uint32_t> cnt(ws.mailbox, ws.mailbox + N_COUNTERS);
-    const int deep_from = (int32_t)ws.mailbox[MAILBOX_DEEP_FROM];
-    // (keys lcp_kernel refused: order_kernel and the leaves do nothing on them; main_guard waits for both on the way out)
-    if (cnt[1] & ERR_KEY_RANGE) {
-        err = "key longer than 255 bytes, or key offsets not monotone";
-        return PHANT_E_INVALID_ARG;
-    }
-    if (cnt[1] & ERR_UNSORTED) {
-        err = "keys are not strictly increasing (mpt.zig:39)";
-        return PHANT_E_UNSORTED;
-    }
-    const uint32_t n_rep = cnt[0];
-    std::vector<uint32_t> depth_begin(MAX_DEPTH_BINS);
-    uint32_t acc = 0;
-    for (int d = 0; d < MAX_DEPTH_BINS; ++d) {
-        depth_begin[d] = acc;
-        acc += cnt[8 + d];
-        if (cnt[8 + d]) ++stats.bins;
-        stats.max_bin = std::max(stats.max_bin, cnt[8 + d]);
-    }
-    stats.n_rep = n_rep;
-    stats.ahead = ahead ? 1u : 0u;
-    stats.deep_from = deep_from;
-    stats.misfit_off = (size_t)(reinterpret_cast<const uint8_t*>(t.misfit) - ws.t1.base);
-    stats.has_misfit = true;
 
-    if (!ahead) {
-        const int32_t rc = size_tables(n_rep);
-        if (rc) return rc;
+    // The t2 arena: the slot tables and the scratch blob for `nodes` branch nodes (trie_plan.h: slot_table_bytes, scratch_bound).
+    int32_t size_tables(uint64_t nodes, std::string& err) {
+        const uint64_t cap = scratch_bound(nodes, t.n, key_bytes, val_bytes);
+        const LaidOut r = lay_out_arena(ws.t2, st, [&](auto& a) {
+            t.slot_bytes = a.template take<uint8_t>((size_t)slot_table_bytes(nodes));
+            t.scratch = a.template take<uint8_t>(cap);
+        });
+        t.scratch_cap = cap;
+        return lay_out_status(r, "trie", "t2", err);
     }
-    // (order_kernel has cleared the slot lengths and formed the bins' starts from the histogram it found in t.counters)
-    // A bin's slot class (branch_kernel): four blocks unless the bin is crowded (more workgroups than the chip holds at once) and
-    // its mean fan-out says that most of its nodes fit less; what does not fit is run through the four-block class behind it.
-    const uint32_t fallback_grid = ws.tune.fallback_grid >= 1 ? (uint32_t)std::min<int64_t>(ws.tune.fallback_grid, 1 << 20) : FALLBACK_GRID;
-    const int force_blocks = ws.tune.slot_blocks;
-    auto launch_bin = [&](int d, hipStream_t on) {
-        const uint32_t c = cnt[8 + d];
-        if (!c) return;
-        if (on != st) ++stats.side_bins;
-        const bool no_coop = ws.tune.no_coop;
-        const uint32_t coop_max = ws.tune.coop_max >= 0 ? (uint32_t)std::min<int64_t>(ws.tune.coop_max, 1 << 20) : COOP_MAX_NODES;
-        if (c <= coop_max && !no_coop && !force_blocks) {
-            // (the sponge's fetches share the CU's LDS pipeline: with one wave on a CU a permutation takes 4.9 us, with four 5.7 --
-            // up to two waves per CU the workgroups are single waves, which the dispatcher spreads over the CUs)
-            const bool no_wave = ws.tune.no_wave;  // (A/B: the half-wave kernel for every thin bin)
-            const bool wave = c <= WAVE_MAX_NODES && !no_wave;
-            ++stats.by_class[wave ? 0 : 1];
-            if (wave) {  // a wave per node
-                if (c <= 512u) hipLaunchKernelGGL(branch_wave_kernel, dim3(c), dim3(64), 0, on, t, depth_begin[d], c);
-                else hipLaunchKernelGGL(branch_wave_kernel, dim3((c + 3u) / 4u), dim3(256), 0, on, t, depth_begin[d], c);
-            } else if (c <= 1024u) {
-                hipLaunchKernelGGL(branch_coop_kernel, dim3((c + 1u) / 2u), dim3(64), 0, on, t, depth_begin[d], c);
-            } else {
-                hipLaunchKernelGGL(branch_coop_kernel, dim3((c + 7u) / 8u), dim3(256), 0, on, t, depth_begin[d], c);
-            }
-            return;
+
+    // The small pass (small_head_kernel, small_climb_kernel): t holds the inputs, the outputs and the t1 arena's arrays.
+    int32_t small_forest(std::string& err) {
+        TB_TRY(ws.ensure_small(SS_WORDS * 4u));
+        if (ws.small_dirty) TB_TRY(ws.rezero_small(SS_WORDS * 4u, st));
+        {   // slot tables by boundary (a node's dense id is its boundary: < n)
+            const int32_t rc = size_tables(t.n, err);
+            if (rc) return rc;
         }
-        const uint64_t children = cnt[8 + MAX_DEPTH_BINS + d];
-        uint32_t blocks = BRANCH_STAGE_BLOCKS;
-        if (c >= CROWDED_BIN) {
-            if (children <= 3ull * c) blocks = 1;       // (<= 3 children of 33 bytes: one rate block)
-            else if (children <= 6ull * c) blocks = 2;  // (<= 7: two)
+        uint32_t* const state = ws.small_state;
+        t.counters = state + SS_COUNTERS;
+        t.first_flag = nullptr;
+        t.mailbox = ws.mailbox;
+        t.mailbox_tag = next_mailbox_tag(ws.mailbox);
+        ws.mailbox[MAILBOX_READY] = t.mailbox_tag;  // (the small pass has no use for this word but the next call counts on from it)
+        main_guard.arm(st);
+        // (from here on a way out other than through MAILBOX_DONE leaves the words of small_state as the kernels left them: the
+        // next small call zeroes them first)
+        ws.small_dirty = true;
+        hipLaunchKernelGGL(small_head_kernel, dim3(1), dim3(SMALL_HEAD_LANES), 0, st, t);
+        hipLaunchKernelGGL(small_climb_kernel, dim3(small_climb_grid(t.n)), dim3(256), 0, st, t, state);
+        TB_TRY(hipGetLastError());
+        {
+            const int32_t rc = wait_mailbox(ws.mailbox, MAILBOX_DONE, t.mailbox_tag, st, "flags", err);
+            if (rc) return rc;
         }
-        if (force_blocks == 1 || force_blocks == 2 || force_blocks == 4) blocks = (uint32_t)force_blocks;
+        ws.small_dirty = false;  // (the workgroup that raised the word had cleared them)
+        main_guard.armed = false;
+        return flags_status(ws.mailbox[1], ws.mailbox[2], err);
+    }
+
+    // head (roots, counters, a forest's start flags) -> [first_flag] -> lcp (+ markers, + the min-tree's padding) -> the tree's levels
+    // -> identify: three or two launches in front of the tree where there were five.  ONE trie has no start but key 0 and goes
+    // without the flags.
+    void queue_head() {
+        const uint32_t n = t.n, n_tries = t.n_tries;
+        if (n_tries == 1) t.first_flag = nullptr;
+        {
+            uint64_t lanes = N_COUNTERS;
+            if (n_tries > lanes) lanes = n_tries;
+            if (t.first_flag && (uint64_t)n + 1 > lanes) lanes = (uint64_t)n + 1;
+            hipLaunchKernelGGL(head_kernel, dim3(blocks(lanes)), dim3(256), 0, st, t);
+        }
+        if (t.first_flag) hipLaunchKernelGGL(first_flag_kernel, dim3(blocks(n_tries)), dim3(256), 0, st, t);
+        hipLaunchKernelGGL(lcp_kernel, dim3(blocks(t.lvl_size[0])), dim3(256), 0, st, t);
+        for (uint32_t base = 0; base + 1u < t.n_lvl; base += 3u) {  // (the grid covers the widest of the three levels it writes)
+            uint32_t g = (t.lvl_size[base + 1u] + 255u) / 256u;
+            if (base + 2u < t.n_lvl && (t.lvl_size[base + 2u] + FAN - 1u) / FAN > g) g = (t.lvl_size[base + 2u] + FAN - 1u) / FAN;
+            if (base + 3u < t.n_lvl && t.lvl_size[base + 3u] > g) g = t.lvl_size[base + 3u];
+            hipLaunchKernelGGL(tree_levels_kernel, dim3(g), dim3(256), 0, st, t, base);
+        }
+        hipLaunchKernelGGL(identify_kernel, dim3((n + COUNT_BLOCK - 1u) / COUNT_BLOCK), dim3(COUNT_BLOCK), 0, st, t);
+    }
+
+    // Whether the bins may run beside the leaves, and whether the leaves go ahead (trie_plan.h: leaves_ahead) -- then the tables are
+    // laid out here, for a node per key.  Where that much memory is not to be had after all, the call goes on with the leaves behind.
+    int32_t choose_ahead(std::string& err) {
+        const uint32_t n = t.n;
+        t.side_ok = side_ok(n, ch) ? 1u : 0u;
+        if (t.side_ok) TB_TRY(ws.ensure_side());
+        const uint64_t worst = ahead_need(n, key_bytes, val_bytes);
+        size_t free_b = 0, total_b = 0;
+        const bool free_known = ask_free_bytes(n, worst, ws.t2.cap, ch) && hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+        ahead = leaves_ahead(n, worst, ws.t2.cap, free_known, free_b, ch);
+        if (!ahead) return PHANT_OK;
+        const int32_t rc = size_tables(n, err);
+        if (rc != PHANT_E_OOM) return rc;
+        (void)hipGetLastError();  // (the failed hipMalloc's sticky error)
+        err.clear();
+        ahead = false;
+        return PHANT_OK;
+    }
+
+    // order_kernel goes straight behind identify_kernel and hands the counters over through the mailbox while it runs (see there).
+    int32_t queue_order_and_leaves(std::string& err) {
+        const uint32_t n = t.n;
+        t.mailbox = ws.mailbox;
+        t.mailbox_tag = next_mailbox_tag(ws.mailbox);
+        // (from here on kernels of this call may be in the stream when something fails -- the good way out ends on MAILBOX_DONE and
+        // has nothing left to wait for)
+        main_guard.arm(st);
+        hipLaunchKernelGGL(order_kernel, dim3((n + COUNT_BLOCK - 1u) / COUNT_BLOCK), dim3(COUNT_BLOCK), 0, st, t);
+        // (the bulk of the leaves: with room for the bins beside them wherever order_kernel MAY decide for such bins -- from
+        // SIDE_MIN_KEYS keys on the leaf workgroups carry the idle LDS, two of them a CU instead of four, also in the rare trie whose
+        // deepest bins turn out too crowded to run beside them: the leaf kernel is LDS- and latency-bound at either occupancy,
+        // measured +-1 %)
+        if (ahead) hipLaunchKernelGGL(leaf_kernel, dim3(blocks(n)), dim3(256), t.side_ok ? ch.side_lds : 0u, st, t, nullptr, nullptr);
+        TB_TRY(hipGetLastError());
+        return PHANT_OK;
+    }
+
+    // The counters order_kernel put into the mailbox: the refusals, the node count, every depth bin's start and launch (trie_plan.h:
+    // plan_bin) -- and, in this one place, what phant_trie_stats tells of them.
+    int32_t read_counters(std::string& err) {
+        int32_t rc = wait_mailbox(ws.mailbox, MAILBOX_READY, t.mailbox_tag, st, "counters", err);
+        if (rc) return rc;
+        std::copy(ws.mailbox, ws.mailbox + N_COUNTERS, cnt);
+        deep_from = (int32_t)ws.mailbox[MAILBOX_DEEP_FROM];
+        // (keys lcp_kernel refused: order_kernel and the leaves do nothing on them; main_guard waits for both on the way out)
+        rc = flags_status(cnt[1], 0u, err);
+        if (rc) return rc;
+        // (order_kernel has cleared the slot lengths and formed the bins' starts from the histogram it found in t.counters)
+        TrieStats& stats = ws.trie_stats;
+        uint32_t acc = 0;
+        for (int d = 0; d < MAX_DEPTH_BINS; ++d) {
+            const uint32_t count = cnt[8 + d];
+            depth_begin[d] = acc;
+            acc += count;
+            if (!count) continue;
+            bin[d] = plan_bin(count, cnt[8 + MAX_DEPTH_BINS + d], ch);
+            ++stats.bins;
+            stats.max_bin = std::max(stats.max_bin, count);
+            ++stats.by_class[bin[d].cls];
+            if (bin_on_side(d, deep_from)) ++stats.side_bins;
+        }
+        stats.n_rep = cnt[0];
+        stats.ahead = ahead ? 1u : 0u;
+        stats.deep_from = deep_from;
+        stats.leaf_big = deep_from < 0 && cnt[3] ? 1u : 0u;
+        stats.misfit_off = (size_t)(reinterpret_cast<const uint8_t*>(t.misfit) - ws.t1.base);
+        stats.has_misfit = true;
+        return PHANT_OK;
+    }
+
+    // depth bin d as planned, on stream `on`
+    void launch_bin(int d, hipStream_t on) {
+        const uint32_t count = cnt[8 + d], begin = depth_begin[d];
+        if (!count) return;
+        const BinLaunch& b = bin[d];
         uint32_t* const mis = t.misfit + d;
-        ++stats.by_class[blocks == 1 ? 2 : blocks == 2 ? 3 : 4];
-        if (blocks == 1)
-            hipLaunchKernelGGL(branch_kernel<1>, dim3((c + 255u) / 256u), dim3(256), 0, on, t, t.order, depth_begin[d], c, nullptr, mis);
-        else if (blocks == 2)
-            hipLaunchKernelGGL(branch_kernel<2>, dim3((c + 127u) / 128u), dim3(128), 0, on, t, t.order, depth_begin[d], c, nullptr, mis);
-        if (blocks != BRANCH_STAGE_BLOCKS)
-            hipLaunchKernelGGL(branch_kernel<BRANCH_STAGE_BLOCKS>, dim3(std::min((c + BRANCH_LANES - 1u) / BRANCH_LANES, fallback_grid)), dim3(BRANCH_LANES), 0,
-                               on, t, t.order2, depth_begin[d], 0u, mis, nullptr);
-        else
-            hipLaunchKernelGGL(branch_kernel<BRANCH_STAGE_BLOCKS>, dim3((c + BRANCH_LANES - 1u) / BRANCH_LANES), dim3(BRANCH_LANES), 0, on, t, t.order,
-                               depth_begin[d], c, nullptr, nullptr);
-    };
+        if (b.cls == BIN_WAVE) {
+            hipLaunchKernelGGL(branch_wave_kernel, dim3(b.grid), dim3(b.block), 0, on, t, begin, count);
+        } else if (b.cls == BIN_HALF_WAVE) {
+            hipLaunchKernelGGL(branch_coop_kernel, dim3(b.grid), dim3(b.block), 0, on, t, begin, count);
+        } else if (b.cls == BIN_BLOCKS1) {
+            hipLaunchKernelGGL(branch_kernel<1>, dim3(b.grid), dim3(b.block), 0, on, t, t.order, begin, count, nullptr, mis);
+        } else if (b.cls == BIN_BLOCKS2) {
+            hipLaunchKernelGGL(branch_kernel<2>, dim3(b.grid), dim3(b.block), 0, on, t, t.order, begin, count, nullptr, mis);
+        } else {
+            hipLaunchKernelGGL(branch_kernel<BRANCH_STAGE_BLOCKS>, dim3(b.grid), dim3(b.block), 0, on, t, t.order, begin, count, nullptr, nullptr);
+        }
+        if (b.fb_grid) {  // (what did not fit the slots: its count is on the device)
+            hipLaunchKernelGGL(branch_kernel<BRANCH_STAGE_BLOCKS>, dim3(b.fb_grid), dim3(b.fb_block), 0, on, t, t.order2, begin, 0u, mis, nullptr);
+        }
+    }
+
     // The deepest bins of a big trie hold a handful of nodes each and cost a node's latency apiece (~30 us: launch, nine dependent
     // round trips, the Keccak-f) -- time in which the chip does nothing else.  They only need the leaves that hang under THEM: so
     // those leaves go first (order_kernel lists them), and then the deepest bins run on a stream of their own NEXT TO the bulk of
     // the leaves, which keeps a workgroup's worth of LDS per CU free for them.
     // (whatever fails behind the fork: the helper stream is waited for before the arenas can be handed to another call)
-    struct SideGuard {
-        hipStream_t s = nullptr;
-        ~SideGuard() {
-            if (s) (void)hipStreamSynchronize(s);
-        }
-    } side_guard;
-    if (deep_from >= 0) {
-        side_guard.s = ws.side;
+    int32_t queue_bins_beside_leaves(std::string& err) {
+        const uint32_t n = t.n;
+        side_guard.arm(ws.side);
         if (ahead) {
             // the leaves under the deepest bins, then those bins, on the helper stream next to the bulk of the leaves -- started
             // by hand once the kernel behind order_kernel says that it has started (MAILBOX_ORDERED), no event in the main stream
-            const int32_t rc = wait_for(MAILBOX_ORDERED);
+            const int32_t rc = wait_mailbox(ws.mailbox, MAILBOX_ORDERED, t.mailbox_tag, st, "counters", err);
             if (rc) return rc;
             hipLaunchKernelGGL(leaf_kernel, dim3(std::min(blocks(n), 256u)), dim3(256), 0, ws.side, t, t.deep_leaves, t.deep_count);
         } else {
             hipLaunchKernelGGL(leaf_kernel, dim3(std::min(blocks(n), 256u)), dim3(256), 0, st, t, t.deep_leaves, t.deep_count);
             TB_TRY(hipEventRecord(ws.side_fork, st));
-            hipLaunchKernelGGL(leaf_kernel, dim3(blocks(n)), dim3(256), side_lds_knob, st, t, nullptr, nullptr);
+            hipLaunchKernelGGL(leaf_kernel, dim3(blocks(n)), dim3(256), ch.side_lds, st, t, nullptr, nullptr);
             TB_TRY(hipStreamWaitEvent(ws.side, ws.side_fork, 0));
         }
         for (int d = MAX_DEPTH_BINS - 1; d >= deep_from; --d) launch_bin(d, ws.side);
@@ -1993,8 +1903,7 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const TriePairs& p,
         // The bins above them need these bins AND all leaves.  The helper stream is normally through well before the leaves are: the
         // host watches its event and queues the rest behind the leaves by hand -- a wait for the event IN the main stream stood
         // between the leaves and the next bin for 11 us even when the event had long been reached.
-        const bool join_in_stream = ws.tune.join_in_stream;  // (A/B)
-        if (join_in_stream) {
+        if (ch.join_in_stream) {
             TB_TRY(hipStreamWaitEvent(st, ws.side_join, 0));
         } else {
             // (watched, not slept on: the event is normally reached ~30 us before the leaves end.  A bounded watch -- a helper
@@ -2007,33 +1916,88 @@ static int32_t forest_device(Workspaces& ws, hipStream_t st, const TriePairs& p,
             TB_TRY(q);
         }
         for (int d = deep_from - 1; d >= 0; --d) launch_bin(d, st);
-    } else {
+        return PHANT_OK;
+    }
+
+    // ... and without such bins: the leaves, if they did not go ahead, then every bin from the deepest up, all in the main stream
+    void queue_bins_behind_leaves() {
+        const uint32_t n = t.n;
         if (!ahead) hipLaunchKernelGGL(leaf_kernel, dim3(blocks(n)), dim3(256), 0, st, t, nullptr, nullptr);
         // (leaves of 136 .. 543 bytes: identify_kernel said whether there can be any -- a grid of lanes that only find out that
         // their leaf is small was 24 us per million keys)
-        if (cnt[3]) {
-            stats.leaf_big = 1u;
-            hipLaunchKernelGGL(leaf_big_kernel, dim3((n + BRANCH_LANES - 1u) / BRANCH_LANES), dim3(BRANCH_LANES), 0, st, t);
-        }
+        if (cnt[3]) hipLaunchKernelGGL(leaf_big_kernel, dim3((n + BRANCH_LANES - 1u) / BRANCH_LANES), dim3(BRANCH_LANES), 0, st, t);
         for (int d = MAX_DEPTH_BINS - 1; d >= 0; --d) launch_bin(d, st);
     }
+
     // The end of the call the same way: finish_kernel, last in the stream, puts the overflow flag into the mailbox and raises
     // MAILBOX_DONE; the host watches that word instead of sleeping on the stream behind a 12-byte copy (10 000 keys: 0.237 against
     // 0.248 ms per call; a million: the same).  Everything this call queued has run when the word is there.
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, st, t);
-    TB_TRY(hipGetLastError());
-    {
-        const int32_t rc = wait_for(MAILBOX_DONE);
+    int32_t finish(std::string& err) {
+        hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(64), 0, st, t);
+        TB_TRY(hipGetLastError());
+        int32_t rc = wait_mailbox(ws.mailbox, MAILBOX_DONE, t.mailbox_tag, st, "counters", err);
+        if (rc == PHANT_OK) rc = flags_status(0u, ws.mailbox[2], err);
+        if (rc == PHANT_OK) main_guard.armed = false;
+        return rc;
+    }
+
+    // The general pass: a launch per stage of the construction and per depth bin.
+    int32_t general_forest(std::string& err) {
+        queue_head();
+        int32_t rc = choose_ahead(err);
+        if (rc == PHANT_OK) rc = queue_order_and_leaves(err);
+        if (rc == PHANT_OK) rc = read_counters(err);
+        if (rc == PHANT_OK && !ahead) rc = size_tables(cnt[0], err);  // (the leaves wait for the tables the node count asks for)
         if (rc) return rc;
+        if (deep_from < 0) queue_bins_behind_leaves();
+        else if ((rc = queue_bins_beside_leaves(err)) != PHANT_OK) return rc;
+        return finish(err);
     }
-    if (ws.mailbox[2]) {
-        err = "trie scratch overflow (internal bound too small)";
-        return PHANT_E_DEVICE;
+};
+}  // namespace
+
+// Device-side forest build; all pointers device memory, except roots_host.
+// keep (optional): the pass's view of its tables as they stand when it returns -- the prover's input (trie_prove.hip.h); they
+// live in the t1 / t2 arenas until the next call resets those.
+static int32_t forest_device(Workspaces& ws, hipStream_t st, const TriePairs& p, std::string& err, const RootNodes& nodes = {},
+                             TrieDev* keep = nullptr) {
+    TB_TRY(ws.ensure_mailbox());
+    ForestCall c(ws, st, p);
+    TrieDev& t = c.t;
+    const uint32_t n = p.n;
+    t.root_enc = nodes.enc;
+    t.root_enc_len = nodes.len;
+    t.root_enc_cap = nodes.cap;
+    t.keys = p.keys;
+    t.key_off = p.key_off;
+    t.vals = p.vals;
+    t.val_off = p.val_off;
+    t.n = n;
+    t.seg_first = p.seg_first;
+    t.n_tries = p.n_tries;
+    t.roots = p.roots;
+    ws.trie_stats = TrieStats{};  // (phant_trie_stats: what THIS call did)
+    ws.trie_stats.n = n;
+    if (n >= 0x7fffffffu) {  // (identify_element keeps a bit of a boundary index for itself)
+        err = "more than 2^31 - 2 keys in one call";
+        return PHANT_E_UNSUPPORTED;
     }
-    main_guard.armed = false;
-    if (keep) *keep = t;
-    return PHANT_OK;
+    int32_t rc = PHANT_OK;
+    if (n == 0) {
+        hipLaunchKernelGGL(fill_empty_roots_kernel, dim3(blocks(p.n_tries)), dim3(256), 0, st, p.roots, p.n_tries);
+        TB_TRY(hipGetLastError());
+    } else {
+        const TreeLevels lv = tree_levels(n);
+        rc = c.lay_out_t1(lv, err);
+        if (rc) return rc;
+        const bool small = small_pass(n, c.val_bytes, lv, c.ch);
+        ws.trie_stats.pass = small ? 1u : 2u;
+        rc = small ? c.small_forest(err) : c.general_forest(err);
+    }
+    if (rc == PHANT_OK && keep) *keep = t;
+    return rc;
 }
+
 
 int32_t trie_forest_host(Workspaces& ws, hipStream_t st, const HostPairs& h, uint8_t* roots_out, std::string& err, const RootNodes& out) {
     const uint32_t n_tries = h.n_tries;

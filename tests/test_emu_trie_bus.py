@@ -9,7 +9,12 @@ their own validation, staging arrays, rebasing and uploads and every arena was s
 with this file, before that code was rewritten on top of staging.h's stage_pairs and lay_out_arena.  Every tuple is reproduced exactly
 but for one deliberate change: the host form of phant_mpt_prove_nodeset now sends its inputs through the pinned stage, ONE host-to-device
 copy where there were five to nine (PROVE_HOST holds the new tuples beside the parent's).  This module runs against the plain emulated
-library: the sanitized one poisons the arena's padding, so it never stages."""
+library: the sanitized one poisons the arena's padding, so it never stages.
+
+The last section holds the kernel launches of the same kind of calls (the emulated runtime's hipemu::M.launches, through
+tests/native/hipemu_export.cpp: hipemu_counters): LAUNCHES was recorded on commit 343780c, the last one whose forest_device was one
+function with its choices, its mailbox protocol and its bins' launches inline, with this file, before that driver was rewritten on top
+of trie_plan.h's plan."""
 import ctypes as C
 import os
 
@@ -159,6 +164,67 @@ def test_state():
     print(got)
     assert got == {k: PARENT[k] for k in got}, got
 
+
+# ---- kernel launches ----
+LAUNCH_SETTINGS = {"side": {"trie_side_min_keys": 0}, "side_behind": {"trie_side_min_keys": 0, "trie_ahead_max_keys": 0},
+                   "side_join": {"trie_side_min_keys": 0, "trie_join_in_stream": 1}, "blocks1_grid1": {"trie_slot_blocks": 1, "trie_fallback_grid": 1},
+                   "no_wave": {"trie_no_wave": 1}, "no_coop": {"trie_no_coop": 1}}
+LAUNCH_KNOB_DEFAULTS = {"trie_side_min_keys": -1, "trie_ahead_max_keys": -1, "trie_join_in_stream": 0, "trie_slot_blocks": 0, "trie_fallback_grid": -1,
+                        "trie_no_wave": 0, "trie_no_coop": 0}
+
+
+def launches_of_second(call):
+    """kernel launches of the second of two equal calls"""
+    lib = _ctx()._lib
+    out = (C.c_ulonglong * 3)()
+    call()
+    lib.hipemu_counters(out)
+    before = out[0]
+    call()
+    lib.hipemu_counters(out)
+    return out[0] - before
+
+
+def test_launches_held_to_parent():
+    """phant_mpt_root without keys, with one, in the small and in the general pass; the general pass under the knobs that move its
+    launches (the helper stream with the leaves ahead, behind and joined in the stream, one-block slots with a one-workgroup fallback,
+    no wave-per-node and no thin-bin kernels at all); the forest with root nodes; a block's lists; one host call of the prover"""
+    from phant_amd import mpt, shard
+    from tests.witness_util import random_kv
+    ctx = _ctx()
+    got = {}
+    for n in (0, 1, 50, 3000):
+        kv = _kv(10 + n, n)[2]
+        got[("mpt_root", n)] = launches_of_second(lambda: mpt.mptize(kv))
+    # (keys that share their first byte: the root is an extension, no bin at depth 0 -- order_kernel sends bins to the helper stream)
+    kv = [mpt.KeyVal(k, v) for k, v in zip(*random_kv(np.random.default_rng(3010), 3000, 32, 1, 80, shared_prefix_nibbles=2))]
+    for name, knobs in dict({"shared_byte": {}}, **LAUNCH_SETTINGS).items():
+        try:
+            for k, v in knobs.items():
+                ctx.diag_set(k, v)
+            got[(name, 3000)] = launches_of_second(lambda: mpt.mptize(kv))
+        finally:
+            for k, v in LAUNCH_KNOB_DEFAULTS.items():
+                ctx.diag_set(k, v)
+    keys, vals, _ = _kv(4, 200)
+    cuts = sorted(np.random.default_rng(4).integers(0, 201, 13).tolist())
+    seg = [0] + cuts[:6] + [cuts[5]] + cuts[6:] + [cuts[-1], 200]  # 16 tries, (at least) two of them empty
+    got[("mpt_root_nodes", 200)] = launches_of_second(lambda: shard.gpu_root_nodes(keys, vals, seg))
+    rng = np.random.default_rng(5)
+    lists = [[rng.integers(0, 256, int(rng.integers(60, 200)), dtype=np.uint8).tobytes() for _ in range(20)] for _ in range(3)]
+    got[("block_roots", 60)] = launches_of_second(lambda: mpt.block_roots(lists))
+    keys, vals, _ = _kv(6, 50)
+    rng = np.random.default_rng(6)
+    queries = [keys[i] for i in rng.choice(50, 7, replace=False)] + [rng.integers(0, 256, 32, dtype=np.uint8).tobytes() for _ in range(3)]
+    got[("prove_nodeset", 50)] = launches_of_second(_prove_call(keys, vals, queries))
+    print(got)
+    assert got == LAUNCHES, got
+
+
+# ---- recorded at commit 343780c (see the module's docstring): kernel launches
+LAUNCHES = {("mpt_root", 0): 1, ("mpt_root", 1): 2, ("mpt_root", 50): 2, ("mpt_root", 3000): 13, ("shared_byte", 3000): 14, ("side", 3000): 15,
+            ("side_behind", 3000): 15, ("side_join", 3000): 15, ("blocks1_grid1", 3000): 21, ("no_wave", 3000): 14, ("no_coop", 3000): 14,
+            ("mpt_root_nodes", 200): 2, ("block_roots", 60): 2, ("prove_nodeset", 50): 9}
 
 # ---- recorded at commit 8264687 (see the module's docstring): (H2D, D2H, D2D, memsets, stream synchronisations)
 PARENT = {("mpt_root", 0): (1, 0, 0, 0, 1), ("mpt_root", 1): (1, 0, 0, 0, 1), ("mpt_root", 50): (1, 0, 0, 0, 1), ("mpt_root", 3000): (1, 0, 0, 0, 1),

@@ -1,4 +1,5 @@
-"""The trie hasher's launch-time choices (phant_amd/csrc/trie_build.hip: forest_device, launch_bin), each FORCED on the GPU over
+"""The trie hasher's launch-time choices (stated in phant_amd/csrc/trie_plan.h: resolve_choices, small_pass, leaves_ahead, side_ok,
+plan_bin; launched by phant_amd/csrc/trie_build.hip: general_forest's stages, launch_bin), each FORCED on the GPU over
 tries chosen for it, against the oracle -- and, through Context.trie_stats() (phant_trie_stats), the proof that the call took
 the path the case names: the pass, whether the leaves went ahead, the depth from which the bins ran on the helper stream, the
 bins per kernel class, the nodes on the fallback lists, whether the kernel for 136 .. 543-byte leaves ran.
