@@ -91,6 +91,25 @@ PHANT_API int32_t phant_nodeset_tune(phant_ctx *ctx, int32_t form, uint32_t orde
 #define PHANT_DIAG_SECP_OPS 9
 PHANT_API int32_t phant_diag_secp_op(phant_ctx *ctx, uint32_t op, const uint8_t *a, const uint8_t *b, uint32_t n, uint8_t *out);
 
+/* The three primitives of phant_amd/csrc/radix_sort.hip that headers, receipts, transactions, access lists, the post-state, the
+ * transactions' pre-state and the state root share, each alone on inputs of the caller's choice: host arrays in and out, on the ctx
+ * stream, synchronised on return.  Every device buffer is carved at exactly the size phant_amd/csrc/launch.h documents for it, with
+ * 256 bytes of 0xEE behind it that are read back after the run: a touched guard is PHANT_E_DEVICE, and phant_last_error names the
+ * buffer.  A null pointer where n > 0 needs an array and a null ctx are PHANT_E_INVALID_ARG; a refused call writes nothing.
+ *   phant_diag_scan_u32       the exclusive prefix sum of counters[0 .. n), in place, modulo 2^32.
+ *   phant_diag_sort_pairs     the stable sort of n (64-bit key, 32-bit value) pairs by the low `bits` (0 .. 64; more: INVALID_ARG)
+ *                             key bits, rounded up to whole bytes; keys come back whole.  bits == 0 or n == 0: the input unchanged.
+ *   phant_diag_order_digests  order_out[0 .. n): the 32-byte digests in ascending order of (seg_of[i], digest i); seg_of may be null
+ *                             (one segment), a seg_of[i] >= n_seg is INVALID_ARG.  prefix_bits: 0 = the product's choice (32 bits,
+ *                             ties repaired), k = sorted on k key bits (rounded up to bytes) and ties left alone, k | 0x80000000 =
+ *                             ties repaired.  *flag_out != 0: the device did not decide the order (a run of more than 16 equal
+ *                             prefixes, a digest twice in a segment, ties left alone) -- order_out is then what the callers throw away. */
+PHANT_API int32_t phant_diag_scan_u32(phant_ctx *ctx, uint32_t *counters, uint32_t n);
+PHANT_API int32_t phant_diag_sort_pairs(phant_ctx *ctx, const uint64_t *keys, const uint32_t *vals, uint32_t n, uint32_t bits,
+                                        uint64_t *keys_out, uint32_t *vals_out);
+PHANT_API int32_t phant_diag_order_digests(phant_ctx *ctx, const uint8_t *digests, const uint32_t *seg_of, uint32_t n, uint32_t n_seg,
+                                           uint32_t prefix_bits, uint32_t *order_out, uint32_t *flag_out);
+
 /* Per-ctx switches of measured alternatives and test hooks (phant_diag_set(ctx, knob, value)).  The library's defaults are what
  * the measurements in profiles/ chose; nothing here changes a result, only how it is computed. */
 enum {

@@ -79,6 +79,9 @@ SYMBOLS = {
     "phant_block_access_lists": (_i32, [_vp, _vp, _vp]),
     "phant_block_access_lists_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
+    "phant_diag_scan_u32": (_i32, [_vp, _vp, _u32]),
+    "phant_diag_sort_pairs": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "phant_diag_order_digests": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
     "phant_mpt_verify_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_mpt_verify_batch_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
                                           _vp, _vp]),

@@ -1064,6 +1064,100 @@ int32_t phant_diag_secp_op(phant_ctx* c, uint32_t op, const uint8_t* a, const ui
     return PHANT_OK;
 }
 
+// phant_diag_scan_u32 / _sort_pairs / _order_digests: a device buffer of exactly `bytes` bytes (a multiple of 4: what launch.h's size
+// functions give) with GUARD_BYTES of 0xEE directly behind it, so that a kernel that writes past what its launcher asked for is caught.
+namespace {
+constexpr size_t GUARD_BYTES = 256;
+struct Guarded {
+    const char* name;
+    size_t bytes;
+    uint8_t* p = nullptr;
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+template <size_t N>
+int32_t carve_guarded(phant_ctx* c, Guarded (&b)[N]) {
+    const int32_t rc = lay_out(c, c->stream, c->ws.io, [&](auto& io) {
+        for (Guarded& g : b) g.p = io.template take<uint8_t>(g.bytes + GUARD_BYTES);
+    });
+    if (rc) return rc;
+    for (const Guarded& g : b) HIP_TRY(c, hipMemsetAsync(g.p + g.bytes, 0xEE, GUARD_BYTES, c->stream));
+    return PHANT_OK;
+}
+// (synchronises the ctx stream: the call's results are in host memory behind it, too)
+template <size_t N>
+int32_t check_guards(phant_ctx* c, const char* who, const Guarded (&b)[N]) {
+    std::vector<uint8_t> seen(N * GUARD_BYTES);
+    for (size_t i = 0; i < N; ++i)
+        HIP_TRY(c, hipMemcpyAsync(seen.data() + i * GUARD_BYTES, b[i].p + b[i].bytes, GUARD_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < N; ++i)
+        for (size_t k = 0; k < GUARD_BYTES; ++k)
+            if (seen[i * GUARD_BYTES + k] != 0xEE)
+                return fail(c, PHANT_E_DEVICE, (std::string(who) + ": the guard behind " + b[i].name + " (" + std::to_string(b[i].bytes) +
+                                                " bytes) was written at byte " + std::to_string(k)).c_str());
+    return PHANT_OK;
+}
+}  // namespace
+
+int32_t phant_diag_scan_u32(phant_ctx* c, uint32_t* counters, uint32_t n) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (n == 0) return PHANT_OK;
+    if (!counters) return fail(c, PHANT_E_INVALID_ARG, "diag_scan_u32: null pointer");
+    DeviceGuard g(c->device);
+    Guarded b[2] = {{"counters", 4 * (size_t)n}, {"scan scratch", 4 * phant::scan_scratch_entries(n)}};
+    const int32_t rc = carve_guarded(c, b);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(b[0].p, counters, b[0].bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, phant::launch_exclusive_scan_u32(b[0].as<uint32_t>(), n, b[1].as<uint32_t>(), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counters, b[0].p, b[0].bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_guards(c, "diag_scan_u32", b);
+}
+
+int32_t phant_diag_sort_pairs(phant_ctx* c, const uint64_t* keys, const uint32_t* vals, uint32_t n, uint32_t bits, uint64_t* keys_out,
+                              uint32_t* vals_out) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (bits > 64u) return fail(c, PHANT_E_INVALID_ARG, "diag_sort_pairs: more than 64 key bits");
+    if (n == 0) return PHANT_OK;
+    if (!keys || !vals || !keys_out || !vals_out) return fail(c, PHANT_E_INVALID_ARG, "diag_sort_pairs: null pointer");
+    DeviceGuard g(c->device);
+    const size_t kb = 8 * (size_t)n, vb = 4 * (size_t)n;
+    Guarded b[6] = {{"keys", kb},       {"alternate keys", kb}, {"values", vb}, {"alternate values", vb}, {"digit table", 4 * phant::sort_hist_entries(n)},
+                    {"digit totals", 512 * 4}};
+    const int32_t rc = carve_guarded(c, b);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(b[0].p, keys, kb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(b[2].p, vals, vb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(b[5].p, 0, b[5].bytes, c->stream));
+    uint64_t* d_keys = nullptr;
+    uint32_t* d_vals = nullptr;
+    HIP_TRY(c, phant::launch_sort_pairs(b[0].as<uint64_t>(), b[2].as<uint32_t>(), b[1].as<uint64_t>(), b[3].as<uint32_t>(), n, bits, b[4].as<uint32_t>(),
+                                        b[5].as<uint32_t>(), &d_keys, &d_vals, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(keys_out, d_keys, kb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(vals_out, d_vals, vb, hipMemcpyDeviceToHost, c->stream));
+    return check_guards(c, "diag_sort_pairs", b);
+}
+
+int32_t phant_diag_order_digests(phant_ctx* c, const uint8_t* digests, const uint32_t* seg_of, uint32_t n, uint32_t n_seg, uint32_t prefix_bits,
+                                 uint32_t* order_out, uint32_t* flag_out) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!flag_out || (n && (!digests || !order_out))) return fail(c, PHANT_E_INVALID_ARG, "diag_order_digests: null pointer");
+    if (seg_of)
+        for (uint32_t i = 0; i < n; ++i)
+            if (seg_of[i] >= n_seg) return fail(c, PHANT_E_INVALID_ARG, "diag_order_digests: a segment index beyond n_seg");
+    DeviceGuard g(c->device);
+    Guarded b[3] = {{"digests", 32 * (size_t)n}, {"segments", seg_of ? 4 * (size_t)n : 0}, {"order workspace", phant::order_workspace_bytes(n)}};
+    const int32_t rc = carve_guarded(c, b);
+    if (rc) return rc;
+    if (n) HIP_TRY(c, hipMemcpyAsync(b[0].p, digests, b[0].bytes, hipMemcpyHostToDevice, c->stream));
+    if (n && seg_of) HIP_TRY(c, hipMemcpyAsync(b[1].p, seg_of, b[1].bytes, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_order = nullptr, *d_flag = nullptr;
+    HIP_TRY(c, phant::launch_order_digests(b[0].p, seg_of ? b[1].as<uint32_t>() : nullptr, n, n_seg, b[2].p, &d_order, &d_flag, prefix_bits, c->stream));
+    if (n) HIP_TRY(c, hipMemcpyAsync(order_out, d_order, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(flag_out, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    return check_guards(c, "diag_order_digests", b);
+}
+
 /* ------------------------------------------------------- proof verification */
 
 // helper stream + events of the two-tier pipeline (created on first use)

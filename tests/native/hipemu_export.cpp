@@ -20,7 +20,9 @@ extern "C" __attribute__((visibility("default"))) void hipemu_bus_counters(unsig
     out[4] = hipemu::M.stream_syncs;
 }
 
-// radix_sort.hip's prefix sum over caller-supplied counters (test hook: the C-ABI reaches it only through the state root).
+// radix_sort.hip's prefix sum over caller-supplied counters (test hook: the product's C-ABI reaches it only inside its callers -- headers,
+// receipts, transactions, access lists, the post-state and, three times, the state root; phant_diag_scan_u32 is the same offer
+// through the C-ABI, with guards behind the buffers).
 #include "../../phant_amd/csrc/launch.h"
 extern "C" __attribute__((visibility("default"))) int hipemu_test_exclusive_scan(unsigned* counters, unsigned n) {
     unsigned *d = nullptr, *scratch = nullptr;

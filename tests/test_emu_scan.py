@@ -1,6 +1,8 @@
 """radix_sort.hip's tiled exclusive scan (sums / scan of sums / tiles, recursively) on the host emulator, against numpy:
 sizes around the tile (2 048) and level (2 048^2) boundaries, so that the one-, two- and three-level forms all run.
-The C-ABI reaches this scan only through phant_state_root (leaf offsets, the radix sort's digit tables)."""
+The product's C-ABI reaches this scan only inside its callers -- headers, receipts, transactions, access lists, the post-state and,
+three times, the state root --, whose counters are whatever their inputs give; the diagnostics entry
+point phant_diag_scan_u32 offers it chosen counters through the C-ABI (tests/test_gpu_sort.py, tests/test_emu_sort.py)."""
 import ctypes as C
 
 import numpy as np
