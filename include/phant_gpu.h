@@ -678,6 +678,131 @@ typedef struct phant_txstate_out {
 PHANT_API int32_t phant_block_txs_prestate(phant_ctx *ctx, const phant_txstate_in *in, phant_txstate_out *out);
 PHANT_API int32_t phant_block_txs_prestate_dev(phant_ctx *ctx, const phant_txstate_in *in, phant_txstate_out *out);
 
+/* ------------------------------------------------- a block of plain transfers settled: balances, gas, account writes
+ * phant_block_settle takes the rows phant_block_transactions[_ex] and phant_block_txs_prestate answer, the pre-state rows of the
+ * witness and the block's withdrawals, and does what `applyBody` (src/blockchain/blockchain.zig:155-205) and `processTransaction`
+ * (:262-343) do for the transactions that meet no code: the gas each uses, the running gas_available, the sender's exact balance
+ * before each, and per pre-state row exactly the account_op / nonces / balances / code_hashes phant_exec_witness_poststate reads.
+ * tests/settle_ref.py is the same definition in Python integers.
+ *
+ * A row j is PROVEN as above.  coinbase_row and wd_row[j] are probe_row entries of the pre-state call (the coinbase and the
+ * withdrawal addresses passed as probes), or PHANT_ROW_NONE.
+ *
+ * The CLASS of transaction i follows from the row's own inputs alone, never from a running value:
+ *   UPSTREAM (PHANT_SETTLE_UPSTREAM, an error bit): tx_flags[i] has an error bit of the transactions call (every PHANT_TX_* bit but
+ *     PHANT_TX_IS_CREATE), state_flags[i] has PHANT_TXST_SKIPPED or one of PHANT_TXST_ERROR_BITS, or effective_gas_price < base_fee.
+ *     Also -- which cannot happen behind calls that raised none of those bits -- sender_row is NONE, to_row is NONE without
+ *     PHANT_TX_IS_CREATE, or gas_used x effective_gas_price + value exceeds 2^256 - 1 (it is at most upfront_cost).
+ *   NOT_PLAIN (PHANT_SETTLE_NOT_PLAIN, advisory; counted in n_not_plain, the least index in first_not_plain, n if none): otherwise, when
+ *     type is 3 or 4, PHANT_TX_IS_CREATE, PHANT_TXST_UNDETERMINED, code_hashes[to_row] is not the empty code hash, or `to` is a
+ *     precompile of the fork: its first 19 bytes are zero and the last is in 1..0x09 (LONDON), 1..0x0a (CANCUN), 1..0x11 (PRAGUE).
+ *     These rows need the EVM and stay with the CALLER.
+ *   PLAIN otherwise.
+ * UPSTREAM and NOT_PLAIN rows contribute no event and no gas; settle_flags holds the class bit, cumulative_gas_used and
+ * balance_before are 0.
+ *
+ * A plain row i: gas_used_i = max(intrinsic_gas, floor_gas) (floor_gas NULL: 0); cum_before_i = the sum of gas_used over the plain
+ * rows before i.  PHANT_SETTLE_GAS_LIMIT (error) when gas_limit_i + cum_before_i > block_gas_limit, in full width (the reference's
+ * gas_available check).  cumulative_gas_used[i] = cum_before_i + gas_used_i, clamped to 2^64 - 1.  Its EVENTS (row, time, value):
+ *   (sender_row, 2i, -(gas_used_i x effective_gas_price_i + value_i)),  (to_row, 2i + 1, +value_i),
+ *   (coinbase_row, 2i + 1, +gas_used_i x (effective_gas_price_i - base_fee)) when coinbase_row is proven.
+ * Withdrawal j is the event (wd_row[j], 2n + j, +wd_amount_gwei[j] x 10^9) when wd_row[j] is proven; otherwise it is dropped,
+ * wd_flags[j] = PHANT_SETTLE_WD_UNKNOWN and n_wd_unknown counts it.  block_flags has PHANT_SETTLE_COINBASE_UNKNOWN when there is a
+ * plain row and coinbase_row is NONE or not proven.
+ * balance_before[i] = balances[sender_row] plus every event on that row with time < 2i: exact and signed, written clamped to
+ * [0, 2^256 - 1].  PHANT_SETTLE_BALANCE_SHORT (error) when the unclamped value is below upfront_cost_i: the reference's
+ * NotEnoughBalance (blockchain.zig:273) -- the exact check phant_block_txs_prestate leaves open behind PHANT_TXST_NEEDS_INFLOW.
+ * Self-transfers, a sender that is the coinbase and a withdrawal to a sender need no rule of their own: the times order them.
+ * EVERY VERDICT ASSUMES THAT EVERY EARLIER PLAIN ROW WAS APPLIED, flagged or not: only the verdicts up to first_bad carry consensus
+ * meaning (a block with first_bad < n is invalid whatever comes behind), as the nonces of phant_block_txs_prestate do.
+ *
+ * Per pre-state row.  A row is TOUCHED when it is the sender or recipient of a plain row, the proven coinbase while a plain row
+ * exists, or the target of a withdrawal that was not dropped.  Untouched: account_op = PHANT_POST_KEEP, nonces_after, balances_after
+ * the pre-state's.  Touched: nonces_after = nonces + its plain sends, saturating at 2^64 - 1; balances_after = the balance plus all
+ * its events -- above 2^256 - 1: clamped, with PHANT_SETTLE_ACCT_OVERFLOW in account_flags; negative (possible only behind a
+ * BALANCE_SHORT row): 0, with PHANT_SETTLE_ACCT_NEGATIVE.  EIP-161, as processTransaction's last loop and the Shanghai withdrawal
+ * rule apply it: a touched row with nonces_after == 0, balances_after == 0 and the empty code hash is PHANT_POST_DELETE when
+ * account_status is PRESENT and PHANT_POST_KEEP when it is ABSENT; every other touched row is PHANT_POST_SET.  Evaluating this once
+ * at the end of the block equals evaluating it after every transaction: a codeless account that never sends (nonce 0) only ever
+ * GAINS balance here, so if it is empty at the end it was empty at every touch, and if it is not, nothing was deleted in between
+ * that the end would not show.  code_hashes_after is always the pre-state's (no plain row changes code).
+ *
+ * Scalars (always written): first_bad = the least i with an error bit, n if none; n_not_plain; first_not_plain; block_flags;
+ * n_wd_unknown; gas_used = the block's, clamped to 2^64 - 1.  The block is SETTLED when first_bad == n, n_not_plain == 0,
+ * block_flags == 0, n_wd_unknown == 0 and no account_flags bit is set: the outputs then are what the reference's loop leaves.
+ *
+ * Any output pointer may be NULL.  PHANT_E_INVALID_ARG, before anything is indexed with the offending value: a wrong struct_size, an
+ * unknown fork, reserved != 0, a NULL input whose count is not zero (floor_gas may be NULL), a sender_row, to_row, wd_row or
+ * coinbase_row that is neither < n_accounts nor PHANT_ROW_NONE.  PHANT_E_UNSUPPORTED: 3 n + n_wd or n_accounts beyond 2^31 - 1.
+ * Host form: checked on the host before anything is copied; one staged upload, the launches, one copy back of the wanted outputs, one
+ * synchronisation.  Device form: every array is device memory (uint64_t arrays 8-byte, uint32_t arrays 4-byte aligned), both structs
+ * host memory; the row indices are checked by a kernel whose verdict the host reads before any other kernel uses them; the call
+ * synchronises the ctx stream. */
+#define PHANT_SETTLE_UPSTREAM 0x001u      /* an earlier call flagged the row, or its price is below the base fee */
+#define PHANT_SETTLE_GAS_LIMIT 0x002u     /* the block's gas does not cover gas_limit behind the rows before */
+#define PHANT_SETTLE_BALANCE_SHORT 0x004u /* NotEnoughBalance, exact */
+#define PHANT_SETTLE_ERROR_BITS 0x007u    /* first_bad counts these */
+#define PHANT_SETTLE_NOT_PLAIN 0x100u     /* advisory: the row needs the EVM */
+#define PHANT_SETTLE_COINBASE_UNKNOWN 1u  /* block_flags */
+#define PHANT_SETTLE_WD_UNKNOWN 1u        /* wd_flags[j] */
+#define PHANT_SETTLE_ACCT_OVERFLOW 1u     /* account_flags[j] */
+#define PHANT_SETTLE_ACCT_NEGATIVE 2u
+typedef struct phant_settle_in {
+    uint32_t struct_size;  /* = sizeof(phant_settle_in) */
+    uint32_t fork;         /* PHANT_TXS_FORK_* */
+    uint32_t n;            /* transaction rows */
+    uint32_t n_accounts;   /* pre-state rows */
+    uint32_t n_wd;         /* withdrawals */
+    uint32_t coinbase_row; /* or PHANT_ROW_NONE */
+    uint32_t reserved[2];  /* 0 */
+    uint64_t block_gas_limit;
+    const uint8_t *base_fee; /* 32 big-endian */
+    /* per transaction, straight from phant_txs_out / phant_txs_ex_out / phant_txstate_out */
+    const uint8_t *type;                /* n */
+    const uint32_t *tx_flags;           /* n: phant_txs_out.flags */
+    const uint64_t *gas_limit;          /* n */
+    const uint64_t *intrinsic_gas;      /* n */
+    const uint64_t *floor_gas;          /* n, or NULL */
+    const uint8_t *value;               /* n x 32 */
+    const uint8_t *effective_gas_price; /* n x 32 */
+    const uint8_t *upfront_cost;        /* n x 32 */
+    const uint8_t *to;                  /* n x 20 */
+    const uint32_t *sender_row;         /* n */
+    const uint32_t *to_row;             /* n */
+    const uint32_t *state_flags;        /* n */
+    /* per pre-state row, straight from phant_prestate */
+    const uint8_t *account_status; /* n_accounts */
+    const uint64_t *nonces;        /* n_accounts */
+    const uint8_t *balances;       /* n_accounts x 32 */
+    const uint8_t *code_hashes;    /* n_accounts x 32 */
+    /* per withdrawal */
+    const uint32_t *wd_row;         /* n_wd */
+    const uint64_t *wd_amount_gwei; /* n_wd */
+} phant_settle_in;
+typedef struct phant_settle_out {
+    uint32_t struct_size;     /* = sizeof(phant_settle_out) */
+    uint32_t first_bad;       /* results ... */
+    uint32_t n_not_plain;
+    uint32_t first_not_plain;
+    uint32_t block_flags;     /* PHANT_SETTLE_COINBASE_UNKNOWN */
+    uint32_t n_wd_unknown;
+    uint64_t gas_used;
+    /* per transaction */
+    uint32_t *settle_flags;        /* PHANT_SETTLE_* */
+    uint64_t *cumulative_gas_used;
+    uint8_t *balance_before;       /* 32 big-endian */
+    /* per pre-state row: what phant_poststate reads */
+    uint8_t *account_op;           /* PHANT_POST_* */
+    uint64_t *nonces_after;
+    uint8_t *balances_after;       /* 32 big-endian */
+    uint8_t *code_hashes_after;    /* 32 */
+    uint8_t *account_flags;        /* PHANT_SETTLE_ACCT_* */
+    /* per withdrawal */
+    uint8_t *wd_flags;             /* PHANT_SETTLE_WD_UNKNOWN */
+} phant_settle_out;
+PHANT_API int32_t phant_block_settle(phant_ctx *ctx, const phant_settle_in *in, phant_settle_out *out);
+PHANT_API int32_t phant_block_settle_dev(phant_ctx *ctx, const phant_settle_in *in, phant_settle_out *out);
+
 /* ------------------------------------------------- a block's access lists: entries, warm sets and their witness rows
  * phant_block_access_lists decodes the access lists (EIP-2930, transaction types 1 - 4) of a block's transactions and joins every
  * entry with the pre-state rows of the witness: what `processTransaction` turns into state before the EVM runs

@@ -76,6 +76,8 @@ SYMBOLS = {
     "phant_block_transactions_ex_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_block_settle": (_i32, [_vp, _vp, _vp]),
+    "phant_block_settle_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_access_lists": (_i32, [_vp, _vp, _vp]),
     "phant_block_access_lists_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
@@ -270,6 +272,32 @@ class PhantTxstateOut(C.Structure):
     """phant_txstate_out (include/phant_gpu.h)"""
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "first_bad", "n_undetermined", "reserved")] + \
                [(name, C.c_void_p) for name, _, _, _ in TXSTATE_OUTPUTS]
+
+
+# phant_settle_in's arrays in the struct's order
+SETTLE_INPUTS = ("base_fee", "type", "tx_flags", "gas_limit", "intrinsic_gas", "floor_gas", "value", "effective_gas_price", "upfront_cost", "to",
+                 "sender_row", "to_row", "state_flags", "account_status", "nonces", "balances", "code_hashes", "wd_row", "wd_amount_gwei")
+# phant_settle_out's arrays in the struct's order: (name, numpy dtype, elements per row, the count its rows follow)
+SETTLE_OUTPUTS = (("settle_flags", "u4", 1, "n"), ("cumulative_gas_used", "u8", 1, "n"), ("balance_before", "u1", 32, "n"),
+                  ("account_op", "u1", 1, "n_accounts"), ("nonces_after", "u8", 1, "n_accounts"), ("balances_after", "u1", 32, "n_accounts"),
+                  ("code_hashes_after", "u1", 32, "n_accounts"), ("account_flags", "u1", 1, "n_accounts"), ("wd_flags", "u1", 1, "n_wd"))
+# PHANT_SETTLE_*: bit k of settle_flags[i]; the bits below 0x8 are errors
+SETTLE_FLAG_NAMES = ("Upstream", "GasLimit", "BalanceShort", None, None, None, None, None, "NotPlain")
+SETTLE_ERROR_BITS = 0x7
+SETTLE_NOT_PLAIN = 0x100
+SETTLE_COINBASE_UNKNOWN, SETTLE_WD_UNKNOWN, SETTLE_ACCT_OVERFLOW, SETTLE_ACCT_NEGATIVE = 1, 1, 1, 2
+
+
+class PhantSettleIn(C.Structure):
+    """phant_settle_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "fork", "n", "n_accounts", "n_wd", "coinbase_row")] + \
+               [("reserved", C.c_uint32 * 2), ("block_gas_limit", C.c_uint64)] + [(name, C.c_void_p) for name in SETTLE_INPUTS]
+
+
+class PhantSettleOut(C.Structure):
+    """phant_settle_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "first_bad", "n_not_plain", "first_not_plain", "block_flags", "n_wd_unknown")] + \
+               [("gas_used", C.c_uint64)] + [(name, C.c_void_p) for name, _, _, _ in SETTLE_OUTPUTS]
 
 
 AL_MALFORMED, AL_DUPLICATES = 1, 2

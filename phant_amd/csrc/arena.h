@@ -142,7 +142,9 @@ struct Workspaces {
     static constexpr size_t MAILBOX_TXST = MAILBOX_TXS + MAILBOX_TXS_WORDS, MAILBOX_TXST_WORDS = 4;
     // ... and block_access_lists (access_lists.hip.h) the MAILBOX_AL_WORDS behind those
     static constexpr size_t MAILBOX_AL = MAILBOX_TXST + MAILBOX_TXST_WORDS, MAILBOX_AL_WORDS = 8;
-    static_assert(MAILBOX_AL + MAILBOX_AL_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
+    // ... and block_settle (settle.hip.h) the MAILBOX_SETTLE_WORDS behind those
+    static constexpr size_t MAILBOX_SETTLE = MAILBOX_AL + MAILBOX_AL_WORDS, MAILBOX_SETTLE_WORDS = 8;
+    static_assert(MAILBOX_SETTLE + MAILBOX_SETTLE_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
     uint32_t* mailbox = nullptr;
     hipError_t ensure_mailbox() {
         if (mailbox) return hipSuccess;

@@ -261,4 +261,5 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 
 #include "transactions.hip.h"
 #include "txstate.hip.h"
+#include "settle.hip.h"
 #include "access_lists.hip.h"

@@ -23,6 +23,7 @@
 #include "receipts.h"
 #include "headers.h"
 #include "transactions.h"
+#include "settle.h"
 #include "txstate.h"
 #include "access_lists.h"
 #include "trie_build.h"
@@ -992,6 +993,44 @@ static int32_t block_txs_prestate_impl(phant_ctx* c, const phant_txstate_in* in,
 int32_t phant_block_txs_prestate(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out) { return block_txs_prestate_impl(c, in, out, false); }
 
 int32_t phant_block_txs_prestate_dev(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out) { return block_txs_prestate_impl(c, in, out, true); }
+
+/* ------------------------------------------------- a block of plain transfers settled (settle.hip.h) */
+
+static int32_t block_settle_impl(phant_ctx* c, const phant_settle_in* in, phant_settle_out* out, bool dev) {
+    const char* const who = dev ? "block_settle_dev" : "block_settle";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_settle_in) || out->struct_size != sizeof(phant_settle_out)) return bad("wrong struct_size");
+    if (in->fork > PHANT_TXS_FORK_PRAGUE) return bad("unknown fork");
+    if (in->reserved[0] != 0u || in->reserved[1] != 0u) return bad("reserved is not 0");
+    if (!in->base_fee) return bad("null base_fee");
+    if (in->n && (!in->type || !in->tx_flags || !in->gas_limit || !in->intrinsic_gas || !in->value || !in->effective_gas_price || !in->upfront_cost ||
+                  !in->to || !in->sender_row || !in->to_row || !in->state_flags))
+        return bad("null transaction array");
+    if (in->n_accounts && (!in->account_status || !in->nonces || !in->balances || !in->code_hashes)) return bad("null pre-state array");
+    if (in->n_wd && (!in->wd_row || !in->wd_amount_gwei)) return bad("null wd_row / wd_amount_gwei");
+    if (in->coinbase_row != PHANT_ROW_NONE && in->coinbase_row >= in->n_accounts) return bad("coinbase_row is neither a pre-state row nor the NONE value");
+    if (in->n_accounts > 0x7fffffffu || 3ull * in->n + in->n_wd > 0x7fffffffull)
+        return fail(c, PHANT_E_UNSUPPORTED, (std::string(who) + ": 2^31 pre-state rows or balance events or more").c_str());
+    if (dev) {  // (kernels read these as words; the outputs arrive by device-to-device copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->gas_limit | (uintptr_t)in->intrinsic_gas | (uintptr_t)in->floor_gas | (uintptr_t)in->nonces |
+                             (uintptr_t)in->wd_amount_gwei | (uintptr_t)out->cumulative_gas_used | (uintptr_t)out->nonces_after;
+        const uintptr_t w4 = (uintptr_t)in->tx_flags | (uintptr_t)in->sender_row | (uintptr_t)in->to_row | (uintptr_t)in->state_flags |
+                             (uintptr_t)in->wd_row | (uintptr_t)out->settle_flags;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    const int32_t rc = phant::block_settle(c->ws, c->stream, *in, *out, dev, err);
+    if (rc) return fail(c, rc, err.c_str());
+    return PHANT_OK;
+}
+
+int32_t phant_block_settle(phant_ctx* c, const phant_settle_in* in, phant_settle_out* out) { return block_settle_impl(c, in, out, false); }
+
+int32_t phant_block_settle_dev(phant_ctx* c, const phant_settle_in* in, phant_settle_out* out) { return block_settle_impl(c, in, out, true); }
 
 /* ------------------------------------------------- a block's access lists against the pre-state tables (access_lists.hip.h) */
 

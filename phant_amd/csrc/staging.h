@@ -1,5 +1,5 @@
 // staging.h -- how a call crosses the bus, once, for the drivers that keep their arrays in the ctx's `io` arena:
-// block_receipts, header_chain, block_transactions, block_txs_prestate, and the host forms of the trie hasher and of its prover.  Plain
+// block_receipts, header_chain, block_transactions, block_txs_prestate, block_settle, and the host forms of the trie hasher and of its prover.  Plain
 // host C++ on top of arena.h.
 //
 //   lay_out_arena an arena sized by, then carved by, one list of take<T>() calls

@@ -178,7 +178,9 @@ def against_prestate(bt: BlockTransactions, prestate, witness_info, fork, probe=
         arg.auth_first = ins["auth_first"].ctypes.data
     out = L.PhantTxstateOut(C.sizeof(L.PhantTxstateOut), 0, 0, 0, *[ptr(arrays[name]) for name, _, _, _ in L.TXSTATE_OUTPUTS])
     ctx.check(ctx._lib.phant_block_txs_prestate(ctx.handle, C.byref(arg), C.byref(out)))
-    return TransactionsAgainstPrestate(arrays, int(out.first_bad), int(out.n_undetermined))
+    r = TransactionsAgainstPrestate(arrays, int(out.first_bad), int(out.n_undetermined))
+    r.probe = [bytes(p) for p in probe]  # (probe_row's addresses, for the calls that take rows: blockchain.settle)
+    return r
 
 
 class AccessLists:
