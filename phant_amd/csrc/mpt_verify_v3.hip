@@ -27,8 +27,9 @@
 //   nibble sits at byte 4 + 33 nibble (root nodes: the root table).  One status byte per hashed node (nstat[]).
 //        walk_kernel      one lane per proof.  Steps over the run of nodes whose state says "hash matches, canonical full
 //                         branch" -- a copy takes its representative's state when it was the same comparison (below) --
-//                         and decodes the rest (DESIGN.md section 3 order of checks) from an LDS copy: for BASELINE's
-//                         proofs just the leaf.  Counts the per-root verdict.
+//                         and decodes the rest (DESIGN.md section 3 order of checks) from an LDS copy.  A last node that
+//                         is a leaf was decoded by the deep role's lane that hashed it, from the dwords it had loaded
+//                         (last[proof], NS_LAST): for BASELINE's proofs the walk decodes nothing.  Counts the per-root verdict.
 //
 //   S = 0 (small batches: under 72 MB of nodes the chip hashes everything in a few rounds of waves): zero_kernel,
 //   hash_deep_kernel over every depth, walk_kernel reading the node states directly.
@@ -143,6 +144,8 @@ struct Args {
     uint32_t* hdr;           // header: HDR_*; cleared per call (propose_kernel / zero_kernel)
     uint32_t* digest;        // total_nodes x 8
     uint8_t* nstat;          // total_nodes: NS_* of the node, written by the lane that hashed it
+    uint64_t* last;          // total_nodes (proofs of a higher index have no entry): what a proof's last node decodes to
+                             // (verify_hash.hip.h: decode_last_leaf), valid iff that node's state has NS_LAST
 };
 
 // The memory-bound kernels run NEXT TO hash waves that never stop issuing: a few instructions, then a wait for memory -- at
@@ -547,16 +550,20 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
     // registers across the sponge)
     for (uint32_t d = a.shallow + level;;) {
         uint32_t first = 0, count = 0, root = 0;
-        if (p < a.v.n) {
-            first = a.v.proof_first_node[p];
-            const uint32_t last = a.v.proof_first_node[p + 1];
+        // (the proof index as a value of THIS trip: the addresses derived from it are the same in every trip and would otherwise
+        // be computed in front of the loop and kept in registers across every sponge -- the same wherever it is used below)
+        uint32_t pt = p;
+        PHANT_PIN_VGPR(pt);
+        if (pt < a.v.n) {
+            first = a.v.proof_first_node[pt];
+            const uint32_t last = a.v.proof_first_node[pt + 1];
             if (last >= first && last <= a.total_nodes) count = last - first;
             // (node ranges of other proofs may overlap then: what a lane finds out about a node holds for ITS proof's key
             // and parent only -- the walk must not use it.  The shallow tier's kernels say so when they run)
             if constexpr (SOLO) {
                 if (last < first) a.hdr[HDR_PFN_BROKEN] = 1u;
             }
-            if (a.v.root_idx) root = a.v.root_idx[p];
+            if (a.v.root_idx) root = a.v.root_idx[pt];
         }
         if (__ballot(d < count) == 0ull) break;
         const uint32_t j = first + d;
@@ -593,7 +600,7 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
         const uint8_t* refp = nullptr;
         uint32_t nib = 16u;  // the key's nibble for THIS node: where its child's reference is, if it is a full branch
         if (active) {
-            const uint8_t* const key = a.v.keys + (uint64_t)a.v.key_len * p;
+            const uint8_t* const key = a.v.keys + (uint64_t)a.v.key_len * pt;
             const uint32_t nibp = (d >= 1u && d - 1u < nn) ? key_nibble(key, d - 1u) : 16u;
             refp = ref_location(a, j, d, root, nibp, b);
             if (ride && d < nn) nib = key_nibble(key, d);
@@ -611,10 +618,12 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
         }
         // what must survive the sponge: one word of flags (and the lane's proof index)
         // (and, with a node riding, where it starts: `e`, which the wave holds anyway)
-        enum : uint32_t { F_ACTIVE = 1u, F_REF = 2u, F_CANON = 4u, F_NEXT_REF = 8u, F_NIB_SHIFT = 8u };
+        enum : uint32_t { F_ACTIVE = 1u, F_REF = 2u, F_CANON = 4u, F_NEXT_REF = 8u, F_LAST = 16u, F_DECODED = 32u, F_NIB_SHIFT = 8u };
         uint32_t flags = (active ? F_ACTIVE : 0u) | (refp != nullptr ? F_REF : 0u);
         // the riding node's parent is this node: its reference is known iff this is 532 bytes long and the key has a nibble for it
         if (active && len == BRANCH_LEN && nib < 16u) flags |= F_NEXT_REF | (nib << F_NIB_SHIFT);
+        // this node is its proof's last one: if it is hashed as one of a wave of equally long short nodes, it is decoded there
+        if (active && d + 1u == count && pt < a.total_nodes) flags |= F_LAST;
         Sponge s;
         const bool is532 = active && len == BRANCH_LEN;
         if (roomy && __ballot(is532) != 0ull) {
@@ -626,14 +635,21 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
         if (__ballot(rest) != 0ull) {
             const uint32_t len0 = (uint32_t)__builtin_amdgcn_readfirstlane(len);
             if (len0 < RATE && __ballot(!rest || len != len0 || ptr + RATE > safe_end) == 0ull) {
-                hash_short_uniform(s, ptr, len0);  // every lane, one length below the rate: BASELINE's leaves
+                // every lane, one length below the rate: BASELINE's leaves
+                uint32_t pl = p;
+                PHANT_PIN_VGPR(pl);
+                const bool dec = hash_short_uniform_last(s, ptr, len0, (flags & F_LAST) != 0u, a.last + pl,
+                                                         a.v.keys + (uint64_t)a.v.key_len * pl, a.v.key_len, d, b);
+                if (dec) flags |= F_DECODED;
             } else if (rest) {
                 hash_any(s, ptr, len, safe_end);
             }
         }
         if (flags & F_ACTIVE) {
-            const uint32_t j = a.v.proof_first_node[p] + d;  // (re-read: not kept across the sponge)
-            uint32_t ns = NS_HASHED | ((flags & F_CANON) ? NS_CANON : 0u);
+            uint32_t pq = p;
+            PHANT_PIN_VGPR(pq);
+            const uint32_t j = a.v.proof_first_node[pq] + d;  // (re-read: not kept across the sponge)
+            uint32_t ns = NS_HASHED | ((flags & F_CANON) ? NS_CANON : 0u) | ((flags & F_DECODED) ? NS_LAST : 0u);
             if (flags & F_REF) {
                 const uint32_t t = threadIdx.x;
                 RefBytes ref;
@@ -656,10 +672,16 @@ PHANT_DEV void deep_role(const Args& a, const uint32_t w, const uint32_t lane, c
                 s_ref[4][t] = ref.hi.x; s_ref[5][t] = ref.hi.y; s_ref[6][t] = ref.hi.z; s_ref[7][t] = ref.hi.w;
             }
             hashed[0] += (uint32_t)__popcll(__ballot(on));
-            hash_short_uniform(s, np, ride_len);
+            // (every lane that is on ends with this node: `ride`)
+            uint32_t pl = p;
+            PHANT_PIN_VGPR(pl);
+            const bool dec = hash_short_uniform_last(s, np, ride_len, on && pl < a.total_nodes, a.last + pl,
+                                                     a.v.keys + (uint64_t)a.v.key_len * pl, a.v.key_len, d + 1u, e);
             if (on) {
-                const uint32_t j1 = a.v.proof_first_node[p] + d + 1u;
-                uint32_t ns = NS_HASHED;
+                uint32_t pq = p;
+                PHANT_PIN_VGPR(pq);
+                const uint32_t j1 = a.v.proof_first_node[pq] + d + 1u;
+                uint32_t ns = NS_HASHED | (dec ? NS_LAST : 0u);
                 if (known) {
                     const uint32_t t = threadIdx.x;
                     RefBytes ref;
@@ -953,6 +975,9 @@ __global__ void __launch_bounds__(256) walk_kernel(const Args a) {
         uint64_t voff = 0;
         uint32_t vlen = 0;
         const uint32_t first = a.v.proof_first_node[i], last = a.v.proof_first_node[i + 1];
+        // what the lane that hashed the proof's last node made of it (requested with the node range; believed below only if
+        // that node's state, written in this launch, says that the word is there)
+        const uint64_t rec = i < a.total_nodes ? a.last[i] : 0ull;
         r = a.v.root_idx ? a.v.root_idx[i] : 0u;
         if (last < first || last > a.total_nodes || r >= a.v.n_roots) {
             status = PHANT_PROOF_BAD_INPUT;
@@ -978,10 +1003,6 @@ __global__ void __launch_bounds__(256) walk_kernel(const Args a) {
             // byte access into a flat load, which goes through the vector-memory path even when it hits LDS).
             const uint8_t* const slot_key = reinterpret_cast<const uint8_t*>(slot + WALK_STAGE_BYTES / 4);
             const bool key_in_lds = a.v.key_len <= WALK_KEY_BYTES;  // the lane's own slot: no barrier needed
-            if (key_in_lds) {
-                uint8_t* kdst = reinterpret_cast<uint8_t*>(slot + WALK_STAGE_BYTES / 4);
-                for (uint32_t t = 0; t < a.v.key_len; ++t) kdst[t] = key[t];
-            }
             WalkState w;
             w.pos = 0;
             w.status = PHANT_PROOF_BAD_INPUT;
@@ -995,6 +1016,7 @@ __global__ void __launch_bounds__(256) walk_kernel(const Args a) {
             // group = same root), below them when the two parents are the same bytes (same representative one level up; the
             // key nibble is the same because the group is) ----
             bool hash_known = false;  // the node at `used` is already known to hash to its reference
+            bool recorded = false;    // ... by the lane that hashed it in place, which left what it decodes to in last[i]
             uint32_t rprev = 0;       // representative of the node stepped over last
             for (bool run = true; run && used < last;) {
                 const uint32_t base = used, dbase = used - first;
@@ -1061,8 +1083,26 @@ __global__ void __launch_bounds__(256) walk_kernel(const Args a) {
                         run = false;
                         if (c == LINK_BAD_HASH) status = PHANT_PROOF_BAD_HASH;
                         else hash_known = c == LINK_HASH_OK;
+                        recorded = me == used && (own & NS_LAST) != 0u;  // (only the deep role sets the bit, in a state of its own)
                     }
                 }
+            }
+
+            // ---- the proof's last node, settled by the lane that hashed it: nothing to stage, nothing to decode ----
+            if (status == 0xffffffffu && hash_known && recorded && used + 1u == last && last_pos(rec) == w.pos &&
+                last_code(rec) != LAST_NONE) {
+                ++used;
+                if (last_code(rec) == LAST_PRESENT) {
+                    status = PHANT_PROOF_PRESENT;
+                    voff = last_value_off(rec);
+                    vlen = last_value_len(rec);
+                } else {
+                    status = PHANT_PROOF_ABSENT;
+                }
+            }
+            if (status == 0xffffffffu && key_in_lds) {  // the key, for the decoder's single-byte reads
+                uint8_t* kdst = reinterpret_cast<uint8_t*>(slot + WALK_STAGE_BYTES / 4);
+                for (uint32_t t = 0; t < a.v.key_len; ++t) kdst[t] = key[t];
             }
 
             // ---- everything else: the reference the next node must hash to, then node by node ----
@@ -1300,7 +1340,7 @@ static uint32_t table_entries(uint32_t n, uint32_t n_roots, uint32_t direct, uin
 }
 
 struct Layout {
-    size_t nstat, dtab, table, rep, ent, digest, end;
+    size_t nstat, dtab, table, rep, ent, digest, last, end;
     uint32_t stripe_cap;
 };
 // `lanes`: the shallow tier's lanes (proofs x shallow levels; 0 for the S = 0 form)
@@ -1316,6 +1356,9 @@ static Layout layout(uint32_t total_nodes, uint32_t te, uint64_t direct_entries,
     l.rep = p;    p += rnd256(tn * 4 + 64);
     l.ent = p;    p += rnd256((size_t)N_LIST * STRIPES * l.stripe_cap * 8u);
     l.digest = p; p += rnd256(tn * 32);
+    // (a word per proof, but the workspace is sized from the nodes alone: an entry for every proof index below total_nodes --
+    // every proof of a witness without empty proofs; a proof of a higher index is decoded by its walk lane)
+    l.last = p;   p += rnd256(tn * 8);
     l.end = p + 1024;
     return l;
 }
@@ -1339,6 +1382,7 @@ static void bind(Args& a, uint8_t* ws, const Layout& l, uint32_t te) {
     a.ent = reinterpret_cast<uint2*>(ws + l.ent);
     a.stripe_cap = l.stripe_cap;
     a.digest = reinterpret_cast<uint32_t*>(ws + l.digest);
+    a.last = reinterpret_cast<uint64_t*>(ws + l.last);
 }
 
 }  // namespace v3
@@ -1492,8 +1536,9 @@ hipError_t launch_mpt_verify(const VerifyArgs& v_in, uint32_t total_nodes, uint8
     hipLaunchKernelGGL(hash_list_kernel, dim3(list_wgs), dim3(256), hash_lds ? hash_lds + 8192u : 0u, st, a);
     mark(4);
     if (two && (e = hipStreamWaitEvent(st, side->join, 0)) != hipSuccess) return e;
-    // (the walk decodes the leaves itself: decoded ahead by a kernel of their own the walk is 8 us shorter and the launch no
-    // shorter, and the extra kernel costs 2.5 % of the throughput with two launches in flight: profiles/r5_explore/NOTES.md)
+    // (the leaves are decoded by the deep role's lanes that hash them: decoded ahead by a kernel of their own the walk was 8 us
+    // shorter and the launch no shorter, and the extra kernel cost 2.5 % of the throughput with two launches in flight:
+    // profiles/r5_explore/NOTES.md)
     hipLaunchKernelGGL(walk_kernel<false>, dim3(pg), dim3(256), 0, st, a);
     mark(5);
     if (e != hipSuccess) return e;

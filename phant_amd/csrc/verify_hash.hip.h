@@ -26,6 +26,7 @@ constexpr uint32_t BRANCH_LEN = 532u;  // f9 02 11 | 16 x (a0 + 32 bytes) | 80
 
 // nstat[] bits
 constexpr uint32_t NS_HASHED = 1u, NS_CANON = 2u, NS_LINK_CHECKED = 4u, NS_LINK_OK = 8u;
+constexpr uint32_t NS_LAST = 16u;  // the proof's last node, and the lane that hashed it left what it decodes to in last[proof]
 
 PHANT_DEV uint32_t node_list(uint32_t len) {
     if (len == BRANCH_LEN) return LIST_B532;
@@ -215,10 +216,7 @@ PHANT_DEV void hash_any(Sponge& s, const uint8_t* __restrict__ p, uint32_t len, 
 
 // Keccak-256 of one node per lane where every lane's node has the SAME length `len` < 136 (wave-uniform): the
 // padding masks are scalars.
-PHANT_DEV void hash_short_uniform(Sponge& s, const uint8_t* __restrict__ p, uint32_t len /* wave-uniform */) {
-    sponge_zero(s);
-    uint32_t d[RATE_DWORDS];
-    load_block_wide(d, p);
+PHANT_DEV void short_uniform_fill(Sponge& s, const uint32_t (&d)[RATE_DWORDS], uint32_t len /* wave-uniform */) {
 #pragma unroll
     for (int i = 0; i < (int)RATE_DWORDS; ++i) {
         const int m = (int)len - 4 * i;  // message bytes inside this dword (scalar)
@@ -230,7 +228,139 @@ PHANT_DEV void hash_short_uniform(Sponge& s, const uint8_t* __restrict__ p, uint
         if (i & 1) s.hi[i >> 1] = v;
         else s.lo[i >> 1] = v;
     }
+}
+PHANT_DEV void hash_short_uniform(Sponge& s, const uint8_t* __restrict__ p, uint32_t len /* wave-uniform */) {
+    sponge_zero(s);
+    uint32_t d[RATE_DWORDS];
+    load_block_wide(d, p);
+    short_uniform_fill(s, d, len);
     keccak_f1600(s);
+}
+
+// ---------------------------------------------------------------- a proof's last node, decoded where it is hashed
+// What the walk would find out about the last node of a proof -- for BASELINE's proofs the 112-byte account leaf -- by copying
+// it into LDS and running the generic decoder over the copy (mpt_walk.hip.h: walk_node) is settled by the lane that hashes the
+// node, from the dwords it has loaded for the sponge: one 64-bit word per proof, last[proof].
+//   bits [0, 40)  byte offset of the value inside the node blob (PRESENT)
+//   bits [40, 48) its length
+//   bits [48, 62) key nibbles consumed in front of the node: the node's index in its proof
+//   bits [62, 64) LAST_NONE (nothing decoded: the walk decodes the node itself), LAST_PRESENT, LAST_ABSENT
+constexpr uint32_t LAST_NONE = 0u, LAST_PRESENT = 1u, LAST_ABSENT = 2u;
+constexpr uint32_t LAST_POS_MAX = (1u << 14) - 1u;
+PHANT_DEV uint32_t last_code(uint64_t w) { return (uint32_t)(w >> 62); }
+PHANT_DEV uint32_t last_pos(uint64_t w) { return (uint32_t)(w >> 48) & LAST_POS_MAX; }
+PHANT_DEV uint32_t last_value_len(uint64_t w) { return (uint32_t)(w >> 40) & 0xffu; }
+PHANT_DEV uint64_t last_value_off(uint64_t w) { return w & ((1ull << 40) - 1ull); }
+
+// The node of `len` bytes (wave-uniform, below the rate) whose rate-block window is in d, at byte `at` of the blob, for the key
+// `key` of which `pos` nibbles (wave-uniform) are consumed.  Decoded are exactly the nodes walk_node settles as a leaf:
+//   the list header is canonical and spans the node (its form follows from `len`: a scalar comparison);
+//   item 0 is a canonical string of 1..33 bytes (so item 1 starts at byte 36 at the latest: ten dwords to select from);
+//   hex-prefix flag 2 or 3, an even flag with a zero pad nibble;
+//   item 1 is a canonical string -- not a list -- that ends the list;
+//   the path is byte-aligned with the key at `pos`: flag 3 for an odd `pos`, flag 2 for an even one.
+// PRESENT iff the path is the rest of the key (walk_node: plen == nn - pos and the bytes equal -- with the path that long its
+// bytes start at byte 2 + header of the node and there are key_len - ceil(pos / 2) of them: scalars), ABSENT otherwise.
+// Everything else -- extensions, branches, embedded or malformed nodes, a path that is not byte-aligned -- is LAST_NONE.
+// No byte of the node at or behind `len` decides anything.
+PHANT_DEV uint64_t decode_last_leaf(const uint32_t (&d)[RATE_DWORDS], const uint32_t len, const uint8_t* __restrict__ key,
+                                    const uint32_t key_len, const uint32_t pos, const uint64_t at) {
+    const uint32_t nn = 2u * key_len;
+    if (pos > nn || pos > LAST_POS_MAX) return 0ull;
+    uint32_t hp;  // bytes of the list header
+    bool ok;
+    if (len >= 3u && len <= 56u) {
+        hp = 1u;
+        ok = (d[0] & 0xffu) == 0xc0u + (len - 1u);
+    } else if (len >= 58u && len < RATE) {
+        hp = 2u;
+        ok = (d[0] & 0xffffu) == (0xf8u | ((len - 2u) << 8));
+    } else {
+        return 0ull;
+    }
+    ok = ok && (at >> 39) == 0ull;
+    // item 0: the hex-prefix path
+    const uint32_t h0 = (d[0] >> (8u * hp)) & 0xffu, n0 = (d[0] >> (8u * hp + 8u)) & 0xffu;
+    const bool single0 = h0 < 0x80u;
+    const uint32_t l0 = single0 ? 1u : h0 - 0x80u;
+    const uint32_t b0 = single0 ? h0 : n0;
+    const uint32_t o1 = hp + (single0 ? 1u : 1u + l0);  // where item 1 starts
+    ok = ok && l0 >= 1u && l0 <= 33u && (single0 || l0 != 1u || n0 >= 0x80u) && o1 < len;
+    const uint32_t odd = pos & 1u;
+    ok = ok && (b0 >> 4) == 2u + odd && (odd != 0u || (b0 & 0x0fu) == 0u);
+    // item 1: the value.  Its header byte and the byte behind it, out of the dwords that can hold them
+    uint32_t lo = 0u, hi = 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < 10u; ++i) {
+        const bool here = (o1 >> 2) == i;
+        lo = here ? d[i] : lo;
+        hi = here ? d[i + 1u] : hi;
+    }
+    const uint32_t w1 = alignbyte(hi, lo, o1 & 3u);
+    const uint32_t h1 = w1 & 0xffu, n1 = (w1 >> 8) & 0xffu;
+    uint32_t l1, p1;
+    if (h1 < 0x80u) {
+        l1 = 1u;
+        p1 = o1;
+    } else if (h1 <= 0xb7u) {
+        l1 = h1 - 0x80u;
+        p1 = o1 + 1u;
+        ok = ok && (l1 != 1u || n1 >= 0x80u);
+    } else {
+        l1 = n1;
+        p1 = o1 + 2u;
+        ok = ok && h1 == 0xb8u && n1 >= 56u;
+    }
+    ok = ok && p1 + l1 == len;  // (with it the byte behind the header, where it was looked at, is the node's)
+    if (!ok) return 0ull;
+    // the path against the rest of the key
+    const uint32_t plen = 2u * (l0 - 1u) + odd;
+    const uint32_t kb = (pos + odd) >> 1, nk = key_len - kb;  // the key bytes behind the nibble an odd path starts with
+    bool present = plen == nn - pos && nk <= 32u;
+    if (present) {
+        uint32_t diff = odd ? ((b0 ^ key[pos >> 1]) & 0x0fu) : 0u;
+        // (one address in a register pair and constant offsets from it: left to itself the compiler keeps a scalar base per load,
+        // all of them computed in front of the caller's loop and held across its sponges)
+        const uint8_t* kp = key + kb;
+        PHANT_PIN_VGPR(kp);
+#pragma unroll
+        for (uint32_t t = 0; t < 8u; ++t) {
+            if (4u * t < nk) {  // (wave-uniform)
+                const uint32_t m = nk - 4u * t;  // key bytes left
+                const uint32_t nw = hp == 2u ? d[1u + t] : alignbyte(d[t + 1u], d[t], 3u);  // node bytes [hp + 2 + 4 t, + 4)
+                uint32_t kw = 0u;
+                if (m >= 4u) {
+                    kw = load4u(kp + 4u * t);
+                } else {
+                    for (uint32_t q = 0; q < m; ++q) kw |= (uint32_t)kp[4u * t + q] << (8u * q);
+                }
+                diff |= (nw ^ kw) & (m >= 4u ? 0xffffffffu : (1u << (8u * m)) - 1u);
+            }
+        }
+        present = diff == 0u;
+    }
+    const uint64_t code = present ? LAST_PRESENT : LAST_ABSENT;
+    const uint64_t value = present ? (at + p1) | ((uint64_t)l1 << 40) : 0ull;
+    return (code << 62) | ((uint64_t)pos << 48) | value;
+}
+
+// hash_short_uniform for a wave some of whose lanes (`is_last`) hold their proof's last node: those decode it from the loaded
+// dwords and store the word at `rec` before the permutation (nothing of it has to outlive the sponge but "a result is there").
+PHANT_DEV bool hash_short_uniform_last(Sponge& s, const uint8_t* __restrict__ p, uint32_t len /* wave-uniform */, const bool is_last,
+                                       uint64_t* __restrict__ rec, const uint8_t* __restrict__ key, const uint32_t key_len,
+                                       const uint32_t pos /* wave-uniform */, const uint64_t at) {
+    sponge_zero(s);
+    uint32_t d[RATE_DWORDS];
+    load_block_wide(d, p);
+    bool decoded = false;
+    if (is_last) {
+        const uint64_t w = decode_last_leaf(d, len, key, key_len, pos, at);
+        *rec = w;
+        decoded = last_code(w) != LAST_NONE;
+    }
+    short_uniform_fill(s, d, len);
+    keccak_f1600(s);
+    return decoded;
 }
 
 // ---------------------------------------------------------------- the queue of list chunks
