@@ -1123,6 +1123,13 @@ PHANT_API int32_t phant_witness_get(const phant_witness *w, phant_witness_info *
  * (tests, tools), not a validation. */
 PHANT_API int32_t phant_witness_verify(phant_ctx *ctx, const phant_witness *w, const uint8_t *expected_state_root,
                                        uint8_t *status, uint32_t *n_failed);
+/* The way back: w as the document phant_witness_parse_json reads -- the per-proof form, or the node-set form for a witness that
+ * came from one.  Every declaration the witness holds is written and no other, hex at its full width: parsing the text gives the
+ * same phant_witness_get arrays and the same declared fields.  Host only.  *len_out (required) always receives the document's
+ * length in bytes (there is no terminating NUL); the text is written only if cap >= *len_out (buf may be NULL with cap == 0):
+ * call again with a buffer of the reported size.  The index form (phant_witness_index_json) holds no decoded nodes:
+ * PHANT_E_UNSUPPORTED. */
+PHANT_API int32_t phant_witness_to_json(const phant_witness *w, char *buf, uint64_t cap, uint64_t *len_out);
 
 /* ------------------------------------------------------- execution witness -> pre-state
  * The witness stateless clients exchange DECLARES nothing: every trie node once in any order, the bytecodes, and the preimages of
@@ -1343,6 +1350,58 @@ PHANT_API int32_t phant_mpt_prove_nodeset_dev(phant_ctx *ctx, const uint8_t *d_k
                                               const uint32_t *d_q_trie /* or NULL */, const uint8_t *d_q_flags /* or NULL */,
                                               uint32_t n_queries, phant_prove_out *out);
 
+/* The per-proof form: an ordered node list per query, root first -- the EIP-1186 eth_getProof shape, the producing half of
+ * phant_mpt_verify_batch.  (roots, root_idx = q_trie, nodes, node_off, proof_first_node) go into phant_mpt_verify_batch[_dev]
+ * unchanged, and the statuses it finds are the q_status reported here.
+ *
+ * 1. The forest and the queries exactly as phant_mpt_prove_nodeset takes them (rules 1 and 2 above: the same sortedness, key-length
+ *    and q_trie errors; queries of any length, repeated, in any order).  There are no q_flags: PHANT_PROVE_MAY_REMOVE names nodes
+ *    off a key's path, which have no place in an ordered proof.
+ * 2. Proof j = nodes [proof_first_node[j], proof_first_node[j + 1]), root first: the hashed nodes on the verifier's walk (DESIGN.md
+ *    section 3) for query j, down to the key's leaf or branch value, to the leaf or extension whose path diverges from the key (that
+ *    node included), or to the branch whose slot for the key's next nibble is empty.  A node shorter than 32 bytes lives inside its
+ *    parent and is not listed; a trie's root node is always listed; an extension and the branch under it are two nodes.  An empty
+ *    trie gives an empty proof (no nodes) with status PHANT_PROOF_ABSENT.
+ * 3. Proofs lie back to back in query order, node_off[0] == 0, node k = nodes[node_off[k] .. node_off[k + 1]).  Repeated queries
+ *    repeat their bytes.  The same inputs give the same bytes.
+ * 4. roots is written for every trie, queried or not.  n_queries == 0: PHANT_OK, both totals 0, proof_first_node[0] = 0,
+ *    node_off[0] = 0.
+ * 5. Capacity, as rule 6 above: total_nodes and nodes_len are always written.  If total_nodes > max_nodes or nodes_len > nodes_cap
+ *    the call still returns PHANT_OK and leaves nodes, node_off and proof_first_node untouched: call again with the reported sizes.
+ *    Every output pointer may be NULL (not wanted; a buffer nobody wants has no capacity to exceed).  struct_size must be
+ *    sizeof(phant_prove_batch_out), else PHANT_E_INVALID_ARG.
+ * 6. All proofs together hold at most 2^32 - 1 nodes; more is PHANT_E_UNSUPPORTED. */
+typedef struct phant_prove_batch_out {
+    uint32_t struct_size;       /* = sizeof(phant_prove_batch_out) */
+    uint32_t max_nodes;         /* node_off holds max_nodes + 1 entries */
+    uint64_t nodes_cap;         /* bytes of nodes */
+    uint8_t *nodes;             /* node bytes back to back */
+    uint64_t *node_off;         /* total_nodes + 1 */
+    uint32_t *proof_first_node; /* n_queries + 1 */
+    uint8_t *roots;             /* n_tries x 32: the mptize roots */
+    uint8_t *q_status;          /* n_queries: PHANT_PROOF_PRESENT / PHANT_PROOF_ABSENT */
+    /* results */
+    uint64_t nodes_len;
+    uint32_t total_nodes;
+    uint32_t reserved;
+} phant_prove_batch_out;
+PHANT_API int32_t phant_mpt_prove_batch(phant_ctx *ctx, const uint8_t *keys, const uint32_t *key_off,
+                                        const uint8_t *vals, const uint64_t *val_off, uint32_t n,
+                                        const uint32_t *seg_first /* n_tries + 1, or NULL */, uint32_t n_tries,
+                                        const uint8_t *qkeys, const uint32_t *qkey_off /* n_queries + 1 */,
+                                        const uint32_t *q_trie /* or NULL */, uint32_t n_queries, phant_prove_batch_out *out);
+/* The same over DEVICE-resident tries and queries (offsets relative to their blobs, key_bytes / val_bytes / qkey_bytes the blobs'
+ * totals as in phant_mpt_root_dev).  `out` itself is host memory; the buffers it points to are device memory (roots and
+ * proof_first_node 4-byte aligned, node_off 8-byte aligned, nodes at any address); an out-of-range q_trie entry is found on the
+ * device.  d_qkey_off is TRUSTED: the caller who packed the queries guarantees n_queries + 1 ascending entries from 0 to
+ * qkey_bytes; the locate lanes read d_qkeys through it unchecked (the forest's own offsets are checked on the device as in
+ * phant_mpt_root_dev).  The call synchronises the ctx stream. */
+PHANT_API int32_t phant_mpt_prove_batch_dev(phant_ctx *ctx, const uint8_t *d_keys, const uint32_t *d_key_off, uint64_t key_bytes,
+                                            const uint8_t *d_vals, const uint64_t *d_val_off, uint64_t val_bytes, uint32_t n,
+                                            const uint32_t *d_seg_first /* n_tries + 1, or NULL */, uint32_t n_tries,
+                                            const uint8_t *d_qkeys, const uint32_t *d_qkey_off, uint64_t qkey_bytes,
+                                            const uint32_t *d_q_trie /* or NULL */, uint32_t n_queries, phant_prove_batch_out *out);
+
 /* Callers of mptize ("next" rows):
  * src/blockchain/blockchain.zig:209-235 calculateMPTRoot -- key rlp(index) */
 PHANT_API int32_t phant_index_root_rlp(phant_ctx *ctx, const uint8_t *items,
@@ -1430,6 +1489,27 @@ PHANT_API int32_t phant_state_witness(phant_ctx *ctx, const uint8_t *addrs, cons
                                       const uint8_t *slot_vals, const uint32_t *slot_first, uint32_t n, const uint8_t *wkeys,
                                       const uint32_t *wkey_off /* n_wkeys + 1 */, const uint8_t *wkey_flags /* or NULL */,
                                       uint32_t n_wkeys, phant_exec_witness **out, uint8_t state_root_out[32]);
+
+/* phant_state_proofs: eth_getProof for a node that HOLDS the state -- the per-proof twin of phant_state_witness.
+ *  - The state and the keys as phant_state_witness takes them (host memory; 20-byte address or 52-byte address ++ slot, accounts
+ *    in order of first appearance, slots grouped under their account, duplicates collapse; any other length:
+ *    PHANT_E_INVALID_ARG, the key's index in phant_last_error).  There are no flags.
+ *  - The result is a phant_witness in its per-proof form, the object phant_witness_parse_json returns: phant_witness_get /
+ *    _verify / _to_json / _free work on it unchanged.  Proofs come in document order: an account's proof, then its storage
+ *    proofs, each the ordered list phant_mpt_prove_batch cuts.  roots = the state root, then every account's storage root.
+ *    The declared nonce / balance / storageHash / codeHash and the slot values are taken from the state.
+ *  - An address the state does not hold gets its exclusion proof, the declarations of the empty account (nonce 0, balance 0,
+ *    the empty storage root, the hash of the empty code) and, for its slots, zero-node proofs against the empty root with value
+ *    0.  A zero-valued or missing slot of a held account gets its exclusion proof with value 0 (an account without live slots
+ *    has the empty root: a zero-node proof).
+ *  - state_root_out (required): the state root, equal to phant_state_root on the same arrays.
+ *  - The storage forest is proven while its tables stand, the state trie behind it; the keys are hashed on the device.  Host
+ *    form only.  A call without keys returns a witness without proofs. */
+PHANT_API int32_t phant_state_proofs(phant_ctx *ctx, const uint8_t *addrs, const uint64_t *nonces, const uint8_t *balances,
+                                     const uint8_t *code, const uint64_t *code_off, const uint8_t *slot_keys,
+                                     const uint8_t *slot_vals, const uint32_t *slot_first, uint32_t n, const uint8_t *wkeys,
+                                     const uint32_t *wkey_off /* n_wkeys + 1 */, uint32_t n_wkeys, phant_witness **out,
+                                     uint8_t state_root_out[32]);
 
 /* One rank's share of a SHARDED state root (arguments as phant_state_root): the sub-tries of its accounts by the top nibble x
  * of the hashed address, in one pass -- roots[32 x] = that sub-trie's mptize root, root_enc[root_enc_cap x ..] = the RLP of its

@@ -106,6 +106,7 @@ SYMBOLS = {
     "phant_witness_free": (None, [_vp]),
     "phant_witness_get": (_i32, [_vp, _vp]),
     "phant_witness_verify": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "phant_witness_to_json": (_i32, [_vp, _vp, _u64, C.POINTER(_u64)]),
     "phant_exec_witness_parse_json": (_i32, [C.c_char_p, _u64, C.POINTER(_vp), C.c_char_p, _u32]),
     "phant_exec_witness_free": (None, [_vp]),
     "phant_exec_witness_get": (_i32, [_vp, _vp]),
@@ -116,12 +117,15 @@ SYMBOLS = {
     "phant_mpt_root_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp]),
     "phant_mpt_prove_nodeset": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
     "phant_mpt_prove_nodeset_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u32, _vp]),
+    "phant_mpt_prove_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "phant_mpt_prove_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _u32, _vp]),
     "phant_mpt_strip_first_nibble": (_i32, [_vp, _u32, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "phant_index_root_rlp": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "phant_block_roots": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_index_root_be32": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "phant_state_root": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "phant_state_witness": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, C.POINTER(_vp), _vp]),
+    "phant_state_proofs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(_vp), _vp]),
     "phant_state_trie_leaves": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp]),
     "phant_state_root_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_state_subtrie_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
@@ -324,6 +328,13 @@ class PhantProveOut(C.Structure):
     """phant_prove_out (include/phant_gpu.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("max_nodes", C.c_uint32), ("nodes_cap", C.c_uint64), ("nodes", C.c_void_p),
                 ("node_off", C.c_void_p), ("trie_first_node", C.c_void_p), ("roots", C.c_void_p), ("q_status", C.c_void_p),
+                ("nodes_len", C.c_uint64), ("total_nodes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PhantProveBatchOut(C.Structure):
+    """phant_prove_batch_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_nodes", C.c_uint32), ("nodes_cap", C.c_uint64), ("nodes", C.c_void_p),
+                ("node_off", C.c_void_p), ("proof_first_node", C.c_void_p), ("roots", C.c_void_p), ("q_status", C.c_void_p),
                 ("nodes_len", C.c_uint64), ("total_nodes", C.c_uint32), ("reserved", C.c_uint32)]
 
 

@@ -114,7 +114,8 @@ struct Workspaces {
     DevArena t1;  // trie builder: per-key / per-boundary arrays
     DevArena t2;  // trie builder: slot tables + encoding scratch
     DevArena pv;  // prover (trie_prove.hip.h): marks, sizes, offsets -- next to t1 / t2, which hold the build it reads
-    DevArena pvo; // prover, host form: the node blob and its offsets on their way out
+    DevArena pvo; // prover, host form: the node blob and its offsets on their way out (the per-proof form: the set the proofs are cut from)
+    DevArena pvb; // prover, per-proof form: the set index of every output node; host form: the proofs on their way out
     DevArena txa; // block_transactions: the rows of the authorization tuples, sized in the middle of a call (whose other arrays stay in `io`)
     // Pinned mirror of the first STAGE_BYTES of `io` for SMALL host-form calls: the caller's pageable arrays are packed into
     // it at the offsets their device copies have in the arena and cross the bus in ONE copy (a pageable hipMemcpyAsync costs
@@ -202,6 +203,7 @@ struct Workspaces {
         t2.release();
         pv.release();
         pvo.release();
+        pvb.release();
         txa.release();
         if (stage) (void)hipHostFree(stage);
         stage = nullptr;

@@ -1810,6 +1810,11 @@ int32_t phant_witness_get(const phant_witness* pw, phant_witness_info* info) {
     return PHANT_OK;
 }
 
+int32_t phant_witness_to_json(const phant_witness* pw, char* buf, uint64_t cap, uint64_t* len_out) {
+    if (!pw || !len_out || (!buf && cap)) return PHANT_E_INVALID_ARG;
+    return phant::witness_to_json(pw->w, buf, cap, *len_out) ? PHANT_OK : PHANT_E_UNSUPPORTED;  // (the index form: its nodes were never decoded)
+}
+
 int32_t phant_witness_verify(phant_ctx* c, const phant_witness* pw, const uint8_t* expected_state_root, uint8_t* status,
                              uint32_t* n_failed) {
     if (!c || !pw) return PHANT_E_INVALID_ARG;
@@ -2472,6 +2477,68 @@ int32_t phant_mpt_prove_nodeset_dev(phant_ctx* c, const uint8_t* d_keys, const u
     return PHANT_OK;
 }
 
+static void prove_batch_args_of(const phant_prove_batch_out* out, phant::ProveBatchArgs& a) {
+    a.nodes = out->nodes;
+    a.node_off = out->node_off;
+    a.proof_first_node = out->proof_first_node;
+    a.roots = out->roots;
+    a.q_status = out->q_status;
+    a.nodes_cap = out->nodes ? out->nodes_cap : ~0ull;  // (as prove_args_of)
+    a.max_nodes = out->node_off ? out->max_nodes : 0xffffffffu;
+}
+
+int32_t phant_mpt_prove_batch(phant_ctx* c, const uint8_t* keys, const uint32_t* key_off, const uint8_t* vals, const uint64_t* val_off,
+                              uint32_t n, const uint32_t* seg_first, uint32_t n_tries, const uint8_t* qkeys, const uint32_t* qkey_off,
+                              const uint32_t* q_trie, uint32_t n_queries, phant_prove_batch_out* out) {
+    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: out is null") : PHANT_E_INVALID_ARG;
+    if (out->struct_size != sizeof(phant_prove_batch_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: wrong struct_size");
+    if (n_tries == 0 || (!seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: seg_first is null, or no trie");
+    if (n && (!key_off || !val_off)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: null pointer");
+    if (n_queries && !qkey_off) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: qkey_off is null");
+    if (n_queries && !q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: q_trie is null with several tries");
+    out->total_nodes = 0;
+    out->nodes_len = 0;
+    DeviceGuard g(c->device);
+    std::string err;
+    phant::ProveBatchArgs a;
+    prove_batch_args_of(out, a);
+    a.q = phant::ProveQueries{qkeys, qkey_off, q_trie, nullptr, n_queries};
+    const int32_t rc = phant::prove_batch_host(c->ws, c->stream, phant::HostPairs{keys, key_off, vals, val_off, n, seg_first, n_tries}, a, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->total_nodes = a.total_nodes;
+    out->nodes_len = a.nodes_len;
+    return PHANT_OK;
+}
+
+int32_t phant_mpt_prove_batch_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes, const uint8_t* d_vals,
+                                  const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first, uint32_t n_tries,
+                                  const uint8_t* d_qkeys, const uint32_t* d_qkey_off, uint64_t qkey_bytes, const uint32_t* d_q_trie,
+                                  uint32_t n_queries, phant_prove_batch_out* out) {
+    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: out is null") : PHANT_E_INVALID_ARG;
+    if (out->struct_size != sizeof(phant_prove_batch_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: wrong struct_size");
+    if (n_tries == 0 || (!d_seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: d_seg_first is null, or no trie");
+    if (n && (!d_key_off || !d_val_off || (key_bytes && !d_keys) || (val_bytes && !d_vals)))
+        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: null pointer");
+    if (n_queries && (!d_qkey_off || (qkey_bytes && !d_qkeys))) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: null query pointer");
+    if (n_queries && !d_q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: d_q_trie is null with several tries");
+    if (((uintptr_t)out->roots & 3u) || ((uintptr_t)out->node_off & 7u) || ((uintptr_t)out->proof_first_node & 3u))
+        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: roots / proof_first_node 4-byte, node_off 8-byte aligned");
+    out->total_nodes = 0;
+    out->nodes_len = 0;
+    DeviceGuard g(c->device);
+    TimedRegion t(c);
+    std::string err;
+    phant::ProveBatchArgs a;
+    prove_batch_args_of(out, a);
+    a.q = phant::ProveQueries{d_qkeys, d_qkey_off, d_q_trie, nullptr, n_queries};
+    const int32_t rc = phant::prove_batch_dev(c->ws, c->stream, phant::TriePairs{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries}, a,
+                                              err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->total_nodes = a.total_nodes;
+    out->nodes_len = a.nodes_len;
+    return PHANT_OK;
+}
+
 int32_t phant_index_root_rlp(phant_ctx* c, const uint8_t* items, const uint64_t* item_off,
                              uint32_t n, uint8_t out[32]) {
     if (!c || !out) return PHANT_E_INVALID_ARG;
@@ -2543,6 +2610,25 @@ int32_t phant_state_witness(phant_ctx* c, const uint8_t* addrs, const uint64_t* 
     std::string err;
     const int32_t rc = phant::state_witness_host(c->ws, c->stream, phant::StateIn{addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n},
                                                  phant::ProveQueries{wkeys, wkey_off, nullptr, wkey_flags, n_wkeys}, w->w, state_root_out, err);
+    if (rc) return fail(c, rc, err.c_str());
+    *out = w.release();
+    return PHANT_OK;
+}
+
+int32_t phant_state_proofs(phant_ctx* c, const uint8_t* addrs, const uint64_t* nonces, const uint8_t* balances, const uint8_t* code,
+                           const uint64_t* code_off, const uint8_t* slot_keys, const uint8_t* slot_vals, const uint32_t* slot_first, uint32_t n,
+                           const uint8_t* wkeys, const uint32_t* wkey_off, uint32_t n_wkeys, phant_witness** out, uint8_t state_root_out[32]) {
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!out || !state_root_out) return fail(c, PHANT_E_INVALID_ARG, "state_proofs: out / state_root_out is null");
+    if (n && (!addrs || !nonces || !balances || !code_off || !slot_first)) return fail(c, PHANT_E_INVALID_ARG, "state_proofs: null pointer");
+    if (n_wkeys && (!wkeys || !wkey_off)) return fail(c, PHANT_E_INVALID_ARG, "state_proofs: wkeys / wkey_off is null");
+    std::unique_ptr<phant_witness> w(new (std::nothrow) phant_witness());
+    if (!w) return fail(c, PHANT_E_OOM, "state_proofs: out of host memory");
+    DeviceGuard g(c->device);
+    std::string err;
+    const int32_t rc = phant::state_proofs_host(c->ws, c->stream, phant::StateIn{addrs, nonces, balances, code, code_off, slot_keys, slot_vals, slot_first, n},
+                                                phant::ProveQueries{wkeys, wkey_off, nullptr, nullptr, n_wkeys}, w->w, state_root_out, err);
     if (rc) return fail(c, rc, err.c_str());
     *out = w.release();
     return PHANT_OK;

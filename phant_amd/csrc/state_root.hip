@@ -232,6 +232,9 @@ struct StateProve {
     std::vector<uint8_t> slot_flags;  // ns
     std::vector<uint8_t> nodes;
     std::vector<uint64_t> node_off{0};
+    // phant_state_proofs: an ordered list per slot query instead (slot_flags is not read): query j = nodes [first[j], first[j + 1])
+    bool per_proof = false;
+    std::vector<uint32_t> first{0};
 };
 
 // the queries' trie keys: 32-byte digests back to back
@@ -402,10 +405,11 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, con
     if (ns && L) {  // the same pass with its tables kept, and the touched slots' paths cut from it (no live slot: no storage node)
         SR_TRY(hipMemcpyAsync(lay.qpre, pv->slot_pre.data(), 32 * (size_t)ns, hipMemcpyHostToDevice, st));
         SR_TRY(hipMemcpyAsync(lay.qtrie, pv->slot_trie.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, st));
-        SR_TRY(hipMemcpyAsync(lay.qflags, pv->slot_flags.data(), ns, hipMemcpyHostToDevice, st));
+        if (!pv->per_proof) SR_TRY(hipMemcpyAsync(lay.qflags, pv->slot_flags.data(), ns, hipMemcpyHostToDevice, st));
         SR_TRY(launch_keccak256_fixed(lay.qpre, 32, 32, ns, lay.qkeys, st));
         hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)ns + 1)), dim3(256), 0, st, ns, lay.qoff);
-        rc = prove_forest_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, lay.qflags, ns}, pv->nodes, pv->node_off, err);
+        if (pv->per_proof) rc = prove_forest_batch_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, nullptr, ns}, pv->nodes, pv->node_off, pv->first, err);
+        else rc = prove_forest_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, lay.qflags, ns}, pv->nodes, pv->node_off, err);
     } else {
         rc = trie_forest_dev(ws, st, storage, err);
     }
@@ -601,35 +605,33 @@ int32_t state_root_host(Workspaces& ws, hipStream_t st, const StateIn& in, uint8
     return PHANT_OK;
 }
 
-// phant_state_witness: the state pass with both of its forests proven -- the touched slots against the storage forest while its
-// tables stand, the touched addresses against the state trie behind it -- and the result laid out as the parser lays out a
-// document: accounts and slots in order of first appearance, "state" = the state-trie nodes, then the storage nodes.
-int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, ExecWitness& w, uint8_t root_out[32],
-                           std::string& err) {
-    const uint32_t n = in.n, n_wkeys = touched.n_queries;
+// The touched keys of phant_state_witness / phant_state_proofs (host view; 20-byte address | 52-byte address ++ slot), grouped as
+// exec_witness_parse_json groups them: accounts in order of first appearance, slots under their account in order of first
+// appearance, duplicates collapsed with their flags ORed.
+struct TouchedKeys {
+    std::vector<std::array<uint8_t, 20>> addr;
+    std::vector<std::vector<std::array<uint8_t, 32>>> slots;
+    std::vector<std::vector<uint8_t>> slot_flags;
+    std::vector<uint8_t> flags;
+};
+static int32_t group_touched_keys(const ProveQueries& touched, const char* call, TouchedKeys& tk, std::string& err) {
+    const uint32_t n_wkeys = touched.n_queries;
     const uint8_t *const wkeys = touched.qkeys, *const wkey_flags = touched.q_flags;
     const uint32_t* const wkey_off = touched.qkey_off;
-    const uint8_t* const addrs = in.addrs;
-    const uint8_t* const code = in.code;
-    const uint64_t* const code_off = in.code_off;
-    w = ExecWitness();
-    w.node_off.push_back(0);
-    w.code_off.push_back(0);
-    // ---- the keys, grouped as exec_witness_parse_json groups them ----
-    std::vector<std::array<uint8_t, 20>> t_addr;
-    std::vector<std::vector<std::array<uint8_t, 32>>> t_slots;
-    std::vector<std::vector<uint8_t>> t_slot_flags;
-    std::vector<uint8_t> t_flags;
+    std::vector<std::array<uint8_t, 20>>& t_addr = tk.addr;
+    std::vector<std::vector<std::array<uint8_t, 32>>>& t_slots = tk.slots;
+    std::vector<std::vector<uint8_t>>& t_slot_flags = tk.slot_flags;
+    std::vector<uint8_t>& t_flags = tk.flags;
     std::unordered_map<std::string, uint32_t> touched_of;
     std::unordered_map<std::string, uint32_t> slot_of;  // address ++ slot -> its index under the account
     for (uint32_t k = 0; k < n_wkeys; ++k) {
         if (wkey_off[k + 1] < wkey_off[k]) {
-            err = "state_witness: wkey_off not monotone";
+            err = std::string(call) + ": wkey_off not monotone";
             return PHANT_E_INVALID_ARG;
         }
         const uint32_t len = wkey_off[k + 1] - wkey_off[k];
         if (len != 20 && len != 52) {
-            err = "state_witness: key " + std::to_string(k) + " is " + std::to_string(len) +
+            err = std::string(call) + ": key " + std::to_string(k) + " is " + std::to_string(len) +
                   " bytes: a key is a 20-byte address or a 52-byte address ++ slot";
             return PHANT_E_INVALID_ARG;
         }
@@ -658,6 +660,28 @@ int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, co
         }
         t_slot_flags[a][si.first->second] |= fl;
     }
+    return PHANT_OK;
+}
+
+// phant_state_witness: the state pass with both of its forests proven -- the touched slots against the storage forest while its
+// tables stand, the touched addresses against the state trie behind it -- and the result laid out as the parser lays out a
+// document: accounts and slots in order of first appearance, "state" = the state-trie nodes, then the storage nodes.
+int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, ExecWitness& w, uint8_t root_out[32],
+                           std::string& err) {
+    const uint32_t n = in.n;
+    const uint8_t* const addrs = in.addrs;
+    const uint8_t* const code = in.code;
+    const uint64_t* const code_off = in.code_off;
+    w = ExecWitness();
+    w.node_off.push_back(0);
+    w.code_off.push_back(0);
+    // ---- the keys, grouped as exec_witness_parse_json groups them ----
+    TouchedKeys tk;
+    if (const int32_t bad = group_touched_keys(touched, "state_witness", tk, err)) return bad;
+    std::vector<std::array<uint8_t, 20>>& t_addr = tk.addr;
+    std::vector<std::vector<std::array<uint8_t, 32>>>& t_slots = tk.slots;
+    std::vector<std::vector<uint8_t>>& t_slot_flags = tk.slot_flags;
+    std::vector<uint8_t>& t_flags = tk.flags;
     exec_witness_layout_keys(w, t_addr, t_slots);
     if (n == 0) return trie_forest_host(ws, st, HostPairs{}, root_out, err);  // (every key absent under the empty root)
 
@@ -721,6 +745,134 @@ int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, co
         w.codes.resize(c0 + len);
         std::memcpy(w.codes.data() + c0, code + code_off[i], len);
         w.code_off.push_back((uint64_t)w.codes.size());
+    }
+    return PHANT_OK;
+}
+
+// phant_state_proofs: the same pass with both forests proven in the per-proof form (prove_forest_batch_collect) and the result laid
+// out as witness_parse_json lays out an EIP-1186 document: per touched account its account proof, then its storage proofs; the
+// declarations are the state's own.
+int32_t state_proofs_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, Witness& w, uint8_t root_out[32],
+                          std::string& err) {
+    static const uint8_t EMPTY_ROOT[32] = {0x56, 0xe8, 0x1f, 0x17, 0x1b, 0xcc, 0x55, 0xa6, 0xff, 0x83, 0x45, 0xe6, 0x92, 0xc0, 0xf8, 0x6e,
+                                           0x5b, 0x48, 0xe0, 0x1b, 0x99, 0x6c, 0xad, 0xc0, 0x01, 0x62, 0x2f, 0xb5, 0xe3, 0x63, 0xb4, 0x21};
+    static const uint8_t EMPTY_CODE[32] = {0xc5, 0xd2, 0x46, 0x01, 0x86, 0xf7, 0x23, 0x3c, 0x92, 0x7e, 0x7d, 0xb2, 0xdc, 0xc7, 0x03, 0xc0,
+                                           0xe5, 0x00, 0xb6, 0x53, 0xca, 0x82, 0x27, 0x3b, 0x7b, 0xfa, 0xd8, 0x04, 0x5d, 0x85, 0xa4, 0x70};
+    const uint32_t n = in.n;
+    w = Witness();
+    w.node_off.push_back(0);
+    w.proof_first_node.push_back(0);
+    w.preimage_off.push_back(0);
+    TouchedKeys tk;
+    if (const int32_t bad = group_touched_keys(ProveQueries{touched.qkeys, touched.qkey_off, nullptr, nullptr, touched.n_queries}, "state_proofs", tk, err))
+        return bad;
+    const uint32_t na = (uint32_t)tk.addr.size();
+
+    // ---- which touched addresses the state holds; their slots are queries against that account's storage trie ----
+    constexpr uint32_t NOT_HELD = 0xffffffffu;
+    std::vector<uint32_t> index_of_touched(na, NOT_HELD), held_idx;
+    StateProve pv;
+    pv.per_proof = true;
+    if (n) {
+        std::unordered_map<std::string, uint32_t> index_of;
+        index_of.reserve((size_t)n * 2);
+        for (uint32_t i = 0; i < n; ++i) index_of.emplace(std::string(reinterpret_cast<const char*>(in.addrs + 20ull * i), 20), i);
+        for (uint32_t a = 0; a < na; ++a) {
+            const auto it = index_of.find(std::string(reinterpret_cast<const char*>(tk.addr[a].data()), 20));
+            if (it == index_of.end()) continue;
+            index_of_touched[a] = it->second;
+            held_idx.push_back(it->second);
+            for (const std::array<uint8_t, 32>& sl : tk.slots[a]) {
+                pv.slot_pre.insert(pv.slot_pre.end(), sl.begin(), sl.end());
+                pv.slot_trie.push_back(it->second);
+            }
+        }
+    }
+    // ---- the device passes: storage forest, then the state trie ----
+    std::vector<uint8_t> anodes, hc(32 * held_idx.size()), sr(32 * held_idx.size());
+    std::vector<uint64_t> anode_off{0};
+    std::vector<uint32_t> afirst((size_t)na + 1, 0);
+    bool storage_proven = false;
+    if (n == 0) {
+        const int32_t rc = trie_forest_host(ws, st, HostPairs{}, root_out, err);  // (every key absent under the empty root: zero-node proofs)
+        if (rc) return rc;
+    } else {
+        StateLayout lay;
+        lay.ns = (uint32_t)pv.slot_trie.size(), lay.witness = true, lay.na = na;
+        DevLeaves l;
+        int32_t rc = state_leaves_dev(ws, st, in, lay, l, err, &pv);
+        if (rc) return rc;
+        storage_proven = pv.first.size() == pv.slot_trie.size() + 1;  // (no live slot in the whole state: no forest pass, every storage root empty)
+        std::vector<uint8_t> addr_pre(20 * (size_t)na);
+        for (uint32_t a = 0; a < na; ++a) std::memcpy(addr_pre.data() + 20 * (size_t)a, tk.addr[a].data(), 20);
+        if (na) {
+            SR_TRY(hipMemcpyAsync(lay.apre, addr_pre.data(), addr_pre.size(), hipMemcpyHostToDevice, st));
+            SR_TRY(launch_keccak256_fixed(lay.apre, 20, 20, na, lay.tkeys, st));
+        }
+        hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)na + 1)), dim3(256), 0, st, na, lay.aoff);
+        if (!held_idx.empty()) {  // the held accounts' code hashes and storage roots, one after the other through the same 32 x na bytes
+            SR_TRY(hipMemcpyAsync(lay.held, held_idx.data(), 4 * held_idx.size(), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * held_idx.size())), dim3(256), 0, st, l.code_hash, lay.held,
+                               (uint32_t)held_idx.size(), lay.thc);
+            SR_TRY(hipMemcpyAsync(hc.data(), lay.thc, hc.size(), hipMemcpyDeviceToHost, st));
+            hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * held_idx.size())), dim3(256), 0, st, lay.sroots, lay.held,
+                               (uint32_t)held_idx.size(), lay.thc);
+            SR_TRY(hipMemcpyAsync(sr.data(), lay.thc, sr.size(), hipMemcpyDeviceToHost, st));
+        }
+        rc = prove_forest_batch_collect(ws, st, l.pairs(), ProveQueries{lay.tkeys, lay.aoff, nullptr, nullptr, na}, anodes, anode_off, afirst, err);
+        if (rc) return rc;
+        SR_TRY(hipMemcpyAsync(root_out, l.root, 32, hipMemcpyDeviceToHost, st));
+        SR_TRY(hipStreamSynchronize(st));
+    }
+    // ---- the document: account proof, then its storage proofs ----
+    w.roots.assign(root_out, root_out + 32);
+    auto add_proof = [&](uint32_t root, uint32_t account, const uint8_t* pre, size_t pre_len, const std::vector<uint8_t>& nodes,
+                         const std::vector<uint64_t>& off, uint32_t k0, uint32_t k1) {
+        w.root_idx.push_back(root);
+        w.account_of.push_back(account);
+        w.preimages.insert(w.preimages.end(), pre, pre + pre_len);
+        w.preimage_off.push_back((uint32_t)w.preimages.size());
+        for (uint32_t k = k0; k < k1; ++k) {
+            w.nodes.insert(w.nodes.end(), nodes.begin() + (ptrdiff_t)off[k], nodes.begin() + (ptrdiff_t)off[k + 1]);
+            w.node_off.push_back((uint64_t)w.nodes.size());
+        }
+        w.proof_first_node.push_back((uint32_t)(w.node_off.size() - 1));
+    };
+    uint32_t h = 0, sq = 0;  // the next held account, the next storage query
+    for (uint32_t a = 0; a < na; ++a) {
+        const uint32_t i = index_of_touched[a];
+        const bool held = i != NOT_HELD;
+        WitnessAccount acc{};
+        std::memcpy(acc.address, tk.addr[a].data(), 20);
+        std::memcpy(acc.storage_hash, held ? sr.data() + 32 * (size_t)h : EMPTY_ROOT, 32);
+        std::memcpy(acc.code_hash, held ? hc.data() + 32 * (size_t)h : EMPTY_CODE, 32);
+        if (held) {
+            std::memcpy(acc.balance, in.bal + 32ull * i, 32);
+            acc.nonce = in.nonces[i];
+        }
+        acc.has_storage_hash = acc.has_code_hash = acc.has_balance = acc.has_nonce = 1;
+        acc.proof = (uint32_t)w.root_idx.size();
+        add_proof(0u, a, acc.address, 20, anodes, anode_off, afirst[a], afirst[a + 1]);
+        w.accounts.push_back(acc);
+        w.roots.insert(w.roots.end(), acc.storage_hash, acc.storage_hash + 32);
+        // the values of this account's touched slots, from the state's own arrays
+        std::unordered_map<std::string, const uint8_t*> value_of;
+        if (held && !tk.slots[a].empty())
+            for (uint32_t s = in.slot_first[i]; s < in.slot_first[i + 1]; ++s)
+                value_of.emplace(std::string(reinterpret_cast<const char*>(in.skeys + 32ull * s), 32), in.svals + 32ull * s);
+        for (const std::array<uint8_t, 32>& sl : tk.slots[a]) {
+            WitnessSlot slot{};
+            slot.proof = (uint32_t)w.root_idx.size();
+            slot.account = a;
+            slot.has_value = 1;
+            const auto it = value_of.find(std::string(reinterpret_cast<const char*>(sl.data()), 32));
+            if (it != value_of.end()) std::memcpy(slot.value, it->second, 32);
+            const bool proven = held && storage_proven;
+            add_proof(1u + a, a, sl.data(), 32, pv.nodes, pv.node_off, proven ? pv.first[sq] : 0u, proven ? pv.first[sq + 1] : 0u);
+            if (held) ++sq;
+            w.slots.push_back(slot);
+        }
+        if (held) ++h;
     }
     return PHANT_OK;
 }

@@ -88,10 +88,33 @@ int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const HostPairs& h, P
 // every array of `a` and of the forest in device memory (p.seg_first null with n_tries == 1: one trie; p.roots ignored: a.roots)
 int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, ProveArgs& a, std::string& err);
 
+// The per-proof form (phant_mpt_prove_batch): the same forest and queries (q.q_flags is not read), every query's own ordered node list,
+// root first, the lists back to back in query order.  total_nodes / nodes_len are always written; nodes, node_off and
+// proof_first_node only when the totals fit the capacities.
+struct ProveBatchArgs {
+    ProveQueries q;
+    uint8_t* nodes = nullptr;
+    uint64_t nodes_cap = 0;
+    uint64_t* node_off = nullptr;          // max_nodes + 1
+    uint32_t max_nodes = 0;
+    uint32_t* proof_first_node = nullptr;  // n_queries + 1
+    uint8_t* roots = nullptr;              // n_tries x 32
+    uint8_t* q_status = nullptr;           // n_queries
+    uint32_t total_nodes = 0;              // out
+    uint64_t nodes_len = 0;                // out
+};
+int32_t prove_batch_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveBatchArgs& a, std::string& err);
+int32_t prove_batch_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, ProveBatchArgs& a, std::string& err);
+
 // the proving forest pass of a caller that owns ws.io (everything device-resident, p.seg_first / p.roots required): the emitted
 // nodes are appended to the host vectors (node_off: one entry per node so far + 1)
 int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
                              std::vector<uint64_t>& node_off, std::string& err);
+
+// ... and its per-proof twin (phant_state_proofs): the proofs of the queries REPLACE the host vectors' contents (node_off:
+// total_nodes + 1 entries, first: n_queries + 1)
+int32_t prove_forest_batch_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
+                                   std::vector<uint64_t>& node_off, std::vector<uint32_t>& first, std::string& err);
 
 // calculateMPTRoot (src/blockchain/blockchain.zig:209-235) when !be32,
 // ExecutionPayload.toBlock keys (src/engine_api/execution_payload.zig:127-139)
@@ -126,6 +149,11 @@ int32_t state_root_host(Workspaces& ws, hipStream_t st, const StateIn& in, uint8
 // null, q_trie is not read) proven against both forests: `w` as the parser would return it for the document, root_out the state root
 int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, ExecWitness& w, uint8_t root_out[32],
                            std::string& err);
+
+// phant_state_proofs: the same pass with the keys (host view, as above; q_flags / q_trie are not read) proven in the per-proof
+// form: `w` as witness_parse_json would return it for the EIP-1186 document, root_out the state root
+int32_t state_proofs_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& keys, Witness& w, uint8_t root_out[32],
+                          std::string& err);
 
 // the same over a DEVICE-resident state, the root written to device memory
 int32_t state_root_dev(Workspaces& ws, hipStream_t st, const StateIn& in, uint8_t* d_root, std::string& err);

@@ -2119,13 +2119,16 @@ struct ProveRun {
     ProveDev p;
     uint32_t total_nodes = 0;
     uint64_t nodes_len = 0;
+    const char* call = "prove_nodeset";  // the entry point's name in this run's error texts
 };
 }  // namespace
 
 // The build with its tables kept, then locate / mark, sizes and offsets.  Every pointer is device memory; pairs.seg_first and
 // pairs.roots are required here.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the emit pass would write.
+// keep_located: the per-proof form's (key, common prefix) of every query stay in the pv arena (run.p.qk / qc).
 static int32_t prove_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status, ProveRun& run,
-                          std::string& err) {
+                          std::string& err, bool keep_located = false, const char* call = "prove_nodeset") {
+    run.call = call;
     int32_t rc = forest_device(ws, st, pairs, err, RootNodes{}, &run.t);
     if (rc) return rc;
     const uint32_t n = pairs.n, n_queries = q.n_queries;
@@ -2142,7 +2145,11 @@ static int32_t prove_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs
         p.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
         p.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
         p.flags = a.template take<uint32_t>(4);
-    }), "prove_nodeset", "pv", err);
+        if (keep_located) {
+            p.qk = a.template take<uint32_t>((size_t)n_queries + 1);
+            p.qc = a.template take<uint32_t>((size_t)n_queries + 1);
+        }
+    }), call, "pv", err);
     if (rc) return rc;
     p.tiles = tiles;
     p.qkeys = q.qkeys;
@@ -2173,7 +2180,7 @@ static int32_t prove_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs
     run.total_nodes = mb[0];
     run.nodes_len = (uint64_t)mb[1] | ((uint64_t)mb[2] << 32);
     if (mb[3] & PV_ERR_TRIE) {
-        err = "prove_nodeset: a q_trie index is not below n_tries";
+        err = std::string(call) + ": a q_trie index is not below n_tries";
         return PHANT_E_INVALID_ARG;
     }
     return PHANT_OK;
@@ -2200,7 +2207,7 @@ static int32_t prove_emit(hipStream_t st, ProveRun& run, uint8_t* d_nodes, uint6
     TB_TRY(hipMemcpyAsync(&flags, p.flags, 4, hipMemcpyDeviceToHost, st));
     TB_TRY(hipStreamSynchronize(st));
     if (flags & PV_ERR_SCRATCH) {
-        err = "prove_nodeset: scratch overflow (internal bound too small)";
+        err = std::string(run.call) + ": scratch overflow (internal bound too small)";
         return PHANT_E_DEVICE;
     }
     return PHANT_OK;
@@ -2327,6 +2334,233 @@ int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const HostPairs& h, P
     if (a.trie_first_node) TB_TRY(hipMemcpyAsync(a.trie_first_node, d_first, ((size_t)n_tries + 1) * 4, hipMemcpyDeviceToHost, st));
     if (a.roots) TB_TRY(hipMemcpyAsync(a.roots, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
     if (a.q_status && nq) TB_TRY(hipMemcpyAsync(a.q_status, d_qstatus, nq, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipStreamSynchronize(st));
+    return PHANT_OK;
+}
+
+// ---- the per-proof form (phant_mpt_prove_batch): every query's ordered node list, cut from the set ----
+namespace {
+struct ProveBatchRun {
+    ProveRun set;
+    ProveBatchDev b;
+    uint32_t total_nodes = 0;
+    uint64_t nodes_len = 0;
+};
+}  // namespace
+
+// The build and the node set as prove_plan / prove_emit make them -- the set into the pvo arena, not to the caller --, then every
+// query's node count and bytes and their scan.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the writing
+// passes would lay out.  Every pointer is device memory; pairs.seg_first and pairs.roots are required.
+static int32_t prove_batch_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status,
+                                ProveBatchRun& run, std::string& err) {
+    int32_t rc = prove_plan(ws, st, pairs, ProveQueries{q.qkeys, q.qkey_off, q.q_trie, nullptr, q.n_queries}, d_q_status, run.set, err, true, "prove_batch");
+    if (rc) return rc;
+    ProveBatchDev& b = run.b;
+    b = ProveBatchDev{};
+    b.n_queries = q.n_queries;
+    if (!run.set.total_nodes) return PHANT_OK;  // no keys, no queries, or queries of empty tries only: every proof is empty
+    const size_t nq1 = (size_t)q.n_queries + 1;
+    const uint32_t tiles = (uint32_t)((nq1 + PV_TILE - 1u) / PV_TILE);
+    uint8_t* d_set = nullptr;
+    uint64_t* d_set_off = nullptr;
+    rc = lay_out_status(lay_out_arena(ws.pvo, st, [&](auto& a) {
+        d_set = a.template take<uint8_t>(run.set.nodes_len + 16);
+        d_set_off = a.template take<uint64_t>((size_t)run.set.total_nodes + 1);
+        b.q_cnt = a.template take<uint32_t>(nq1);
+        b.q_bytes = a.template take<unsigned long long>(nq1);
+        b.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
+        b.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
+    }), "prove_batch", "pvo", err);
+    if (rc) return rc;
+    if ((rc = prove_emit(st, run.set, d_set, d_set_off, nullptr, err)) != PHANT_OK) return rc;
+    b.set_nodes = d_set;
+    b.set_off = reinterpret_cast<const unsigned long long*>(d_set_off);
+    b.tiles = tiles;
+    b.mailbox = ws.mailbox;
+    hipLaunchKernelGGL(prove_batch_count_kernel, dim3(tiles), dim3(PV_TILE), 0, st, run.set.t, run.set.p, b);
+    hipLaunchKernelGGL(prove_batch_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, b);
+    TB_TRY(hipGetLastError());
+    TB_TRY(hipStreamSynchronize(st));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    const volatile uint32_t* const mb = ws.mailbox + MAILBOX_PROVE_BATCH;
+    const uint64_t total = (uint64_t)mb[0] | ((uint64_t)mb[1] << 32);
+    if (total > 0xffffffffull) {
+        err = "prove_batch: more than 2^32 - 1 nodes in all proofs";
+        return PHANT_E_UNSUPPORTED;
+    }
+    run.total_nodes = (uint32_t)total;
+    run.nodes_len = (uint64_t)mb[2] | ((uint64_t)mb[3] << 32);
+    return PHANT_OK;
+}
+
+// The writing passes into DEVICE buffers: node offsets (total_nodes + 1) and the proofs' first nodes (n_queries + 1), then the bytes.
+// d_nodes / d_first may be null; d_node_off and d_src (total_nodes words of the prover's own) only when there are no nodes at all.
+// The caller has checked the capacities.  Does not synchronise.
+static int32_t prove_batch_write(hipStream_t st, ProveBatchRun& run, uint8_t* d_nodes, uint64_t* d_node_off, uint32_t* d_first, uint32_t* d_src,
+                                 std::string& err) {
+    ProveBatchDev& b = run.b;
+    if (!run.total_nodes) {
+        if (d_first) TB_TRY(hipMemsetAsync(d_first, 0, ((size_t)b.n_queries + 1) * 4, st));
+        if (d_node_off) TB_TRY(hipMemsetAsync(d_node_off, 0, 8, st));
+        return PHANT_OK;
+    }
+    b.total_nodes = run.total_nodes;
+    b.src = d_src;
+    b.node_off = reinterpret_cast<unsigned long long*>(d_node_off);
+    b.proof_first_node = d_first;
+    b.nodes = d_nodes;
+    hipLaunchKernelGGL(prove_batch_place_kernel, dim3(blocks((uint64_t)b.n_queries + 1)), dim3(256), 0, st, run.set.t, run.set.p, b);
+    if (d_nodes) hipLaunchKernelGGL(prove_batch_gather_kernel, dim3((run.total_nodes + 3u) / 4u), dim3(256), 0, st, b);
+    TB_TRY(hipGetLastError());
+    return PHANT_OK;
+}
+
+int32_t prove_batch_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, ProveBatchArgs& a, std::string& err) {
+    TriePairs p = pairs;
+    p.roots = a.roots;
+    int32_t rc = fill_in_dev(ws, st, p, "prove_batch", err);
+    if (rc) return rc;
+    ProveBatchRun run;
+    rc = prove_batch_plan(ws, st, p, a.q, a.q_status, run, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    a.total_nodes = run.total_nodes;
+    a.nodes_len = run.nodes_len;
+    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
+    if (fits && (a.nodes || a.node_off || a.proof_first_node)) {
+        uint32_t* d_src = nullptr;
+        uint64_t* d_off = a.node_off;
+        if (run.total_nodes) {
+            rc = lay_out_status(lay_out_arena(ws.pvb, st, [&](auto& ar) {
+                d_src = ar.template take<uint32_t>(run.total_nodes);
+                if (!a.node_off) d_off = ar.template take<uint64_t>((size_t)run.total_nodes + 1);
+            }), "prove_batch", "pvb", err);
+            if (rc) {
+                (void)hipStreamSynchronize(st);
+                return rc;
+            }
+        }
+        rc = prove_batch_write(st, run, a.nodes, d_off, a.proof_first_node, d_src, err);
+        if (rc) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+    }
+    TB_TRY(hipStreamSynchronize(st));
+    return PHANT_OK;
+}
+
+int32_t prove_batch_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveBatchArgs& a, std::string& err) {
+    const ProveQueries& q = a.q;
+    const uint32_t nq = q.n_queries, n_tries = h.n_tries;
+    const uint64_t qb = nq ? q.qkey_off[nq] - q.qkey_off[0] : 0;
+    uint8_t *d_roots = nullptr, *d_qkeys = nullptr, *d_qstatus = nullptr;
+    uint32_t *d_qoff = nullptr, *d_qtrie = nullptr;
+    // the queries ride with the pairs, as in prove_nodeset_host
+    const StagedPairs in = stage_pairs(ws, st, h, "prove_batch", err, [&]() -> int32_t {
+        for (uint32_t j = 0; j < nq; ++j) {
+            if (q.qkey_off[j + 1] < q.qkey_off[j]) return err = "query key offsets not monotone", PHANT_E_INVALID_ARG;
+            if (q.q_trie && q.q_trie[j] >= n_tries)
+                return err = "prove_batch: q_trie[" + std::to_string(j) + "] is not below n_tries", PHANT_E_INVALID_ARG;
+        }
+        return PHANT_OK;
+    }, [&](auto& io) -> const void* {
+        d_qkeys = io.template take<uint8_t>(qb + 16);
+        d_qoff = io.template take<uint32_t>((size_t)nq + 1);
+        d_qtrie = io.template take<uint32_t>((size_t)nq + 1);
+        d_roots = io.template take<uint8_t>((size_t)n_tries * 32);
+        d_qstatus = io.template take<uint8_t>((size_t)nq + 1);
+        return d_qtrie ? d_qtrie + nq + 1 : nullptr;  // (the sizer hands out no addresses)
+    }, [&](StagedInputs& ins) {
+        ins.put(d_qkeys, qb ? q.qkeys + q.qkey_off[0] : nullptr, qb);
+        std::vector<uint32_t> qo;
+        uint32_t* rel = ins.twin(d_qoff);
+        if (!ins.staged) qo.resize((size_t)nq + 1), rel = qo.data();
+        if (rel) {
+            rel[0] = 0;
+            for (uint32_t j = 0; j <= nq && nq; ++j) rel[j] = q.qkey_off[j] - q.qkey_off[0];
+        }
+        if (!ins.staged) ins.put(d_qoff, rel, ((size_t)nq + 1) * 4);  // (a pageable source: the copy is taken when put() returns)
+        ins.put(d_qtrie, q.q_trie, (size_t)nq * 4);
+    });
+    if (in.rc) return in.rc;
+    TriePairs p = in.pairs;
+    p.roots = d_roots;
+    ProveBatchRun run;
+    int32_t rc = prove_batch_plan(ws, st, p, ProveQueries{d_qkeys, d_qoff, q.q_trie ? d_qtrie : nullptr, nullptr, nq}, d_qstatus, run, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    a.total_nodes = run.total_nodes;
+    a.nodes_len = run.nodes_len;
+    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
+    if (fits && (a.nodes || a.node_off || a.proof_first_node)) {
+        uint8_t* d_nodes = nullptr;
+        uint64_t* d_off = nullptr;
+        uint32_t *d_first = nullptr, *d_src = nullptr;
+        rc = lay_out_status(lay_out_arena(ws.pvb, st, [&](auto& ar) {
+            d_off = ar.template take<uint64_t>((size_t)run.total_nodes + 1);
+            d_src = ar.template take<uint32_t>((size_t)run.total_nodes + 1);
+            if (a.proof_first_node) d_first = ar.template take<uint32_t>((size_t)nq + 1);
+            if (a.nodes) d_nodes = ar.template take<uint8_t>(run.nodes_len + 16);
+        }), "prove_batch", "pvb", err);
+        if (rc) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        rc = prove_batch_write(st, run, d_nodes, d_off, d_first, d_src, err);
+        if (rc) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        if (a.nodes && run.nodes_len) TB_TRY(hipMemcpyAsync(a.nodes, d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
+        if (a.node_off) TB_TRY(hipMemcpyAsync(a.node_off, d_off, ((size_t)run.total_nodes + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (a.proof_first_node) TB_TRY(hipMemcpyAsync(a.proof_first_node, d_first, ((size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (a.roots) TB_TRY(hipMemcpyAsync(a.roots, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
+    if (a.q_status && nq) TB_TRY(hipMemcpyAsync(a.q_status, d_qstatus, nq, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipStreamSynchronize(st));
+    return PHANT_OK;
+}
+
+// The per-proof forest pass of a caller that owns ws.io (phant_state_proofs): everything device-resident, p.seg_first and p.roots
+// required.  The proofs REPLACE the host vectors' contents: node_off holds total_nodes + 1 entries, first n_queries + 1.
+int32_t prove_forest_batch_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
+                                   std::vector<uint64_t>& node_off, std::vector<uint32_t>& first, std::string& err) {
+    ProveBatchRun run;
+    int32_t rc = prove_batch_plan(ws, st, p, q, nullptr, run, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    nodes.assign(run.nodes_len, 0);
+    node_off.assign((size_t)run.total_nodes + 1, 0);
+    first.assign((size_t)q.n_queries + 1, 0);
+    if (!run.total_nodes) return PHANT_OK;
+    uint8_t* d_nodes = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t *d_first = nullptr, *d_src = nullptr;
+    rc = lay_out_status(lay_out_arena(ws.pvb, st, [&](auto& ar) {
+        d_off = ar.template take<uint64_t>((size_t)run.total_nodes + 1);
+        d_src = ar.template take<uint32_t>(run.total_nodes);
+        d_first = ar.template take<uint32_t>((size_t)q.n_queries + 1);
+        d_nodes = ar.template take<uint8_t>(run.nodes_len + 16);
+    }), "prove_batch", "pvb", err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    rc = prove_batch_write(st, run, d_nodes, d_off, d_first, d_src, err);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    TB_TRY(hipMemcpyAsync(nodes.data(), d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipMemcpyAsync(node_off.data(), d_off, node_off.size() * 8, hipMemcpyDeviceToHost, st));
+    TB_TRY(hipMemcpyAsync(first.data(), d_first, first.size() * 4, hipMemcpyDeviceToHost, st));
     TB_TRY(hipStreamSynchronize(st));
     return PHANT_OK;
 }

@@ -23,6 +23,14 @@
 //                         The digest an extension carries is recomputed: its branch is encoded into the build's scratch blob and
 //                         hashed there (the build keeps only the extension's own hash, in the parent's slot).
 //
+// The per-proof form (phant_mpt_prove_batch) runs all of the above with the set emitted into the prover's own arena, then:
+//   prove_batch_count_kernel   a lane per query: the climb of the locate pass once more from the kept (key, common prefix), to the
+//                              root without an early stop; the members on it counted, their bytes summed; scan inside the tile
+//   prove_batch_scan_kernel    one workgroup: the tiles' sums scanned, the totals (64 bits each) to the pinned mailbox
+//   prove_batch_place_kernel   the same climb: member `step` of query j (deepest first) lands at node base(j + 1) - 1 - step -- its
+//                              set index and its byte offset; proof_first_node
+//   prove_batch_gather_kernel  a wave per output node: the node's bytes from the set into the proof blob, 16 bytes a lane
+//
 // Position (index i, kind) in ascending order IS the output order: tries are runs of indices, so nodes come grouped by trie, every
 // position once, and the same inputs give the same bytes.
 
@@ -33,8 +41,10 @@ constexpr uint32_t PV_TILE = 1024;
 constexpr uint32_t PV_ERR_TRIE = 1u, PV_ERR_SCRATCH = 2u;
 // the mailbox words behind the build's own: total nodes, total bytes (two words), error flags
 constexpr uint32_t MAILBOX_PROVE = N_COUNTERS + 8u;
-static_assert(MAILBOX_PROVE + 4u <= Workspaces::MAILBOX_WORDS, "the prover's totals fit the pinned mailbox");
-static_assert(MAILBOX_PROVE + 4u <= Workspaces::MAILBOX_RECEIPTS, "the builder's and the prover's words end in front of the receipts'");
+// ... and behind those the per-proof form's: total nodes (two words), total bytes (two words)
+constexpr uint32_t MAILBOX_PROVE_BATCH = MAILBOX_PROVE + 4u;
+static_assert(MAILBOX_PROVE_BATCH + 4u <= Workspaces::MAILBOX_WORDS, "the prover's totals fit the pinned mailbox");
+static_assert(MAILBOX_PROVE_BATCH + 4u <= Workspaces::MAILBOX_RECEIPTS, "the builder's and the prover's words end in front of the receipts'");
 
 struct ProveDev {
     const uint8_t* qkeys;
@@ -57,6 +67,10 @@ struct ProveDev {
     uint8_t* nodes;
     unsigned long long* node_off;
     uint32_t* trie_first_node;
+    // the per-proof form keeps what the locate pass found (optional): the key whose leaf query j climbs from (NONE: an empty trie)
+    // and the nibbles the two share
+    uint32_t* qk;
+    uint32_t* qc;
 };
 
 // nibble j of query key bytes q
@@ -91,6 +105,7 @@ __global__ void __launch_bounds__(256) prove_locate_kernel(TrieDev t, ProveDev p
         }
     }
     uint8_t status = PHANT_PROOF_ABSENT;
+    uint32_t kept_k = NONE, kept_c = 0;
     const uint32_t lo = t.n ? t.seg_first[tr] : 0u, hi = t.n ? t.seg_first[tr + 1u] : 0u;
     if (lo < hi) {
         const uint8_t* q = p.qkeys + p.qkey_off[j];
@@ -120,6 +135,8 @@ __global__ void __launch_bounds__(256) prove_locate_kernel(TrieDev t, ProveDev p
             }
         }
         if (exact) status = PHANT_PROOF_PRESENT;
+        kept_k = k;
+        kept_c = c;
         const bool flagged = exact && p.q_flags && (p.q_flags[j] & PHANT_PROVE_MAY_REMOVE);
         // the climb from key k
         const uint32_t ps = t.leaf_ps[k];
@@ -141,6 +158,10 @@ __global__ void __launch_bounds__(256) prove_locate_kernel(TrieDev t, ProveDev p
         }
     }
     if (p.q_status) p.q_status[j] = status;
+    if (p.qk) {
+        p.qk[j] = kept_k;
+        p.qc[j] = kept_c;
+    }
 }
 
 // key x against the d nibbles that key l starts with followed by nibble s: is x below that string?
@@ -370,4 +391,167 @@ __global__ void __launch_bounds__(64) prove_reset_kernel(TrieDev t, ProveDev p) 
         if (t.cursor) *t.cursor = 0ull;  // (no keys: no build, no arenas)
         p.flags[0] = 0u;
     }
+}
+
+// ---- the per-proof form: every query's own ordered list, cut from the emitted set ----
+struct ProveBatchDev {
+    uint32_t n_queries;
+    const uint8_t* set_nodes;               // the node set in the prover's arena
+    const unsigned long long* set_off;      // its offsets (set nodes + 1)
+    uint32_t* q_cnt;                        // n_queries + 1: the first node of proof j (inside its tile until the place pass adds the tile's base)
+    unsigned long long* q_bytes;            // n_queries + 1: its byte offset, likewise
+    uint32_t* tile_cnt;                     // tiles + 1
+    unsigned long long* tile_bytes;         // tiles + 1
+    uint32_t tiles;
+    uint32_t* mailbox;
+    // the writing passes
+    uint32_t total_nodes;
+    uint32_t* src;                          // total_nodes: the set index of every output node
+    unsigned long long* node_off;           // total_nodes + 1
+    uint32_t* proof_first_node;             // n_queries + 1 (optional)
+    uint8_t* nodes;
+};
+
+// The members on the walk of a query that shares c nibbles with key k, deepest first: visit(set index).  The conditions are the
+// locate pass's own marks; members[] says which of the marked are hashed nodes, nbase[] where an index's members (extension, branch,
+// leaf, in that order) stand in the set.
+template <class Visit>
+PHANT_DEV void pv_walk_up(const TrieDev& t, const ProveDev& p, uint32_t k, uint32_t c, Visit&& visit) {
+    const uint32_t ps = t.leaf_ps[k];
+    if (ps != BRANCH_VALUE && c >= ps) {
+        const uint32_t mem = p.members[k];
+        if (mem & PV_M_LEAF) visit(p.nbase[k] + (uint32_t)__popc(mem & (PV_M_EXT | PV_M_BRANCH)));
+    }
+    uint32_t node = t.leaf_parent[k];
+    while (node != NONE) {
+        const int32_t d = t.lcp[node], pd = t.nd_pd[node];
+        const uint32_t mem = p.members[node];
+        if ((int32_t)c >= d && (mem & PV_M_BRANCH)) visit(p.nbase[node] + ((mem & PV_M_EXT) ? 1u : 0u));
+        if (d > pd + 1 && (int32_t)c >= pd + 1 && (mem & PV_M_EXT)) visit(p.nbase[node]);
+        node = t.nd_parent[node];
+    }
+}
+
+__global__ void __launch_bounds__(PV_TILE) prove_batch_count_kernel(TrieDev t, ProveDev p, ProveBatchDev b) {
+    __shared__ uint32_t s_c[2][PV_TILE];
+    __shared__ unsigned long long s_b[2][PV_TILE];
+    const uint32_t tid = threadIdx.x;
+    const unsigned long long j = (unsigned long long)blockIdx.x * PV_TILE + tid;
+    uint32_t cnt = 0;
+    unsigned long long bytes = 0;
+    if (j < b.n_queries) {
+        const uint32_t k = p.qk[j];
+        if (k != NONE)
+            pv_walk_up(t, p, k, p.qc[j], [&](uint32_t s) {
+                ++cnt;
+                bytes += b.set_off[s + 1u] - b.set_off[s];
+            });
+    }
+    s_c[0][tid] = cnt;
+    s_b[0][tid] = bytes;
+    __syncthreads();
+    uint32_t cur = 0;
+    for (uint32_t o = 1; o < PV_TILE; o <<= 1) {  // inclusive scan, two buffers
+        s_c[cur ^ 1u][tid] = s_c[cur][tid] + (tid >= o ? s_c[cur][tid - o] : 0u);
+        s_b[cur ^ 1u][tid] = s_b[cur][tid] + (tid >= o ? s_b[cur][tid - o] : 0ull);
+        cur ^= 1u;
+        __syncthreads();
+    }
+    if (j <= b.n_queries) {
+        b.q_cnt[j] = s_c[cur][tid] - cnt;
+        b.q_bytes[j] = s_b[cur][tid] - bytes;
+    }
+    if (tid == PV_TILE - 1u) {
+        b.tile_cnt[blockIdx.x] = s_c[cur][tid];  // (keys of at most 255 bytes: a walk passes fewer than 2^11 nodes, a tile's 1 024 walks fit 32 bits)
+        b.tile_bytes[blockIdx.x] = s_b[cur][tid];
+    }
+}
+
+// the tiles' sums -> their exclusive prefix, in place; the totals to the mailbox.  The node total is kept in 64 bits: the host
+// refuses one beyond 2^32 - 1, and nobody reads the (wrapped) prefixes then.
+__global__ void __launch_bounds__(PV_TILE) prove_batch_scan_kernel(ProveBatchDev b) {
+    __shared__ uint32_t s_c[2][PV_TILE];
+    __shared__ unsigned long long s_b[2][PV_TILE];
+    __shared__ unsigned long long s_run_c, s_run_b;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        s_run_c = 0ull;
+        s_run_b = 0ull;
+    }
+    __syncthreads();
+    for (uint32_t first = 0; first < b.tiles; first += PV_TILE) {
+        const uint32_t q = first + tid;
+        const uint32_t cnt = q < b.tiles ? b.tile_cnt[q] : 0u;
+        const unsigned long long bytes = q < b.tiles ? b.tile_bytes[q] : 0ull;
+        s_c[0][tid] = cnt;
+        s_b[0][tid] = bytes;
+        __syncthreads();
+        uint32_t cur = 0;
+        for (uint32_t o = 1; o < PV_TILE; o <<= 1) {
+            s_c[cur ^ 1u][tid] = s_c[cur][tid] + (tid >= o ? s_c[cur][tid - o] : 0u);
+            s_b[cur ^ 1u][tid] = s_b[cur][tid] + (tid >= o ? s_b[cur][tid - o] : 0ull);
+            cur ^= 1u;
+            __syncthreads();
+        }
+        if (q < b.tiles) {
+            b.tile_cnt[q] = (uint32_t)s_run_c + s_c[cur][tid] - cnt;
+            b.tile_bytes[q] = s_run_b + s_b[cur][tid] - bytes;
+        }
+        __syncthreads();
+        if (tid == PV_TILE - 1u) {
+            s_run_c += s_c[cur][tid];  // (1 024 tiles' sums, each below 2^21, stay below 2^32)
+            s_run_b += s_b[cur][tid];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        b.mailbox[MAILBOX_PROVE_BATCH] = (uint32_t)s_run_c;
+        b.mailbox[MAILBOX_PROVE_BATCH + 1u] = (uint32_t)(s_run_c >> 32);
+        b.mailbox[MAILBOX_PROVE_BATCH + 2u] = (uint32_t)s_run_b;
+        b.mailbox[MAILBOX_PROVE_BATCH + 3u] = (uint32_t)(s_run_b >> 32);
+        __threadfence_system();
+    }
+}
+
+__global__ void __launch_bounds__(256) prove_batch_place_kernel(TrieDev t, ProveDev p, ProveBatchDev b) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (j > b.n_queries) return;
+    const uint32_t first = b.q_cnt[j] + b.tile_cnt[j / PV_TILE];
+    if (b.proof_first_node) b.proof_first_node[j] = first;
+    if (j == b.n_queries) {
+        b.node_off[first] = b.q_bytes[j] + b.tile_bytes[j / PV_TILE];  // the end of the last node
+        return;
+    }
+    const uint32_t k = p.qk[j];
+    if (k == NONE) return;
+    // filled from the proof's end: the climb meets the deepest node first
+    uint32_t at = b.q_cnt[j + 1u] + b.tile_cnt[(j + 1u) / PV_TILE];
+    unsigned long long end = b.q_bytes[j + 1u] + b.tile_bytes[(j + 1u) / PV_TILE];
+    pv_walk_up(t, p, k, p.qc[j], [&](uint32_t s) {
+        end -= b.set_off[s + 1u] - b.set_off[s];
+        --at;
+        b.node_off[at] = end;
+        b.src[at] = s;
+    });
+}
+
+// A wave per output node.  Both ends sit at any byte address: the bytes up to the destination's next 16-byte boundary and the
+// last (length - head) % 16 go a byte a lane, what lies between as unaligned 16-byte loads (absorb.hip.h) and aligned 16-byte stores.
+__global__ void __launch_bounds__(256) prove_batch_gather_kernel(ProveBatchDev b) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long o = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (o >= b.total_nodes) return;
+    const uint32_t s = b.src[o];
+    const unsigned long long from = b.set_off[s], len = b.set_off[s + 1u] - from;
+    const uint8_t* __restrict__ const src = b.set_nodes + from;
+    uint8_t* __restrict__ const dst = b.nodes + b.node_off[o];
+    unsigned long long head = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
+    if (head > len) head = len;
+    if (lane < head) dst[lane] = src[lane];
+    const unsigned long long body_end = head + ((len - head) & ~15ull);
+    for (unsigned long long at = head + 16u * lane; at < body_end; at += 16u * 64u) {
+        const PackedU32x4 v = *reinterpret_cast<const PackedU32x4*>(src + at);
+        *reinterpret_cast<uint4*>(dst + at) = make_uint4(v.x, v.y, v.z, v.w);
+    }
+    if (body_end + lane < len) dst[body_end + lane] = src[body_end + lane];  // (fewer than 16 are left)
 }

@@ -96,6 +96,11 @@ void exec_witness_layout_keys(ExecWitness& w, const std::vector<std::array<uint8
                               const std::vector<std::vector<std::array<uint8_t, 32>>>& slots);
 
 bool witness_parse_json(const char* json, size_t len, Witness& out, std::string& err);
+// the way back (phant_witness_to_json): the per-proof or node-set document that parses to the same Witness; false for the index
+// form, whose nodes were never decoded
+bool witness_to_json(const Witness& w, std::string& out);
+// ... into a caller's buffer: len = the document's length (always), the text written only when cap >= len
+bool witness_to_json(const Witness& w, char* buf, uint64_t cap, uint64_t& len);
 // the same result with the accounts parsed on `threads` host threads (0 = as many as the host has, at most 32)
 bool witness_parse_json_mt(const char* json, size_t len, unsigned threads, Witness& out, std::string& err);
 // index form: everything but the proof nodes' hex is parsed as above (threads as above, 1 = on the caller's thread)

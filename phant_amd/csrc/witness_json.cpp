@@ -1009,4 +1009,87 @@ bool exec_witness_parse_json(const char* json, size_t len, ExecWitness& w, std::
     return true;
 }
 
+// ---- the way back: a Witness as the document witness_parse_json reads (phant_witness_to_json) ----
+namespace {
+void put_hex(std::string& out, const uint8_t* p, size_t n) {
+    static const char digits[] = "0123456789abcdef";
+    out += "\"0x";
+    const size_t at = out.size();
+    out.resize(at + 2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        out[at + 2 * i] = digits[p[i] >> 4];
+        out[at + 2 * i + 1] = digits[p[i] & 15];
+    }
+    out += '"';
+}
+void put_nodes(std::string& out, const Witness& w, size_t first, size_t last) {
+    out += '[';
+    for (size_t k = first; k < last; ++k) {
+        if (k != first) out += ',';
+        put_hex(out, w.nodes.data() + w.node_off[k], (size_t)(w.node_off[k + 1] - w.node_off[k]));
+    }
+    out += ']';
+}
+}  // namespace
+
+// Every member the witness holds is written, and only those (a declaration the document did not carry stays out), fixed-width
+// hex throughout: parsing the text gives the same arrays, the same declared fields and the same has_* flags.  The index form has
+// no decoded nodes to write: false.
+bool witness_to_json(const Witness& w, std::string& out) {
+    out.clear();
+    if (w.deferred) return false;
+    out.reserve(2 * w.nodes.size() + 4 * w.node_off.size() + 512 * w.accounts.size() + 256 * w.slots.size() + 128);
+    out += "{\"stateRoot\":";
+    put_hex(out, w.roots.data(), 32);
+    if (w.node_set) {
+        out += ",\"state\":";
+        put_nodes(out, w, 0, w.node_off.size() - 1);
+    }
+    out += ",\"accounts\":[";
+    size_t s = 0;  // (the slots lie in document order: an account's follow its predecessor's)
+    for (size_t a = 0; a < w.accounts.size(); ++a) {
+        const WitnessAccount& acc = w.accounts[a];
+        out += a ? ",{\"address\":" : "{\"address\":";
+        put_hex(out, acc.address, 20);
+        if (acc.has_nonce) {
+            uint8_t n8[8];
+            for (int i = 0; i < 8; ++i) n8[7 - i] = (uint8_t)(acc.nonce >> (8 * i));
+            out += ",\"nonce\":";
+            put_hex(out, n8, 8);
+        }
+        if (acc.has_balance) out += ",\"balance\":", put_hex(out, acc.balance, 32);
+        if (acc.has_code_hash) out += ",\"codeHash\":", put_hex(out, acc.code_hash, 32);
+        if (acc.has_storage_hash) out += ",\"storageHash\":", put_hex(out, acc.storage_hash, 32);
+        if (!w.node_set) {
+            out += ",\"accountProof\":";
+            put_nodes(out, w, w.proof_first_node[acc.proof], w.proof_first_node[acc.proof + 1]);
+        }
+        out += ",\"storageProof\":[";
+        for (bool first = true; s < w.slots.size() && w.slots[s].account == a; ++s, first = false) {
+            const WitnessSlot& sl = w.slots[s];
+            out += first ? "{\"key\":" : ",{\"key\":";
+            put_hex(out, w.preimages.data() + w.preimage_off[sl.proof], 32);
+            if (sl.has_value) out += ",\"value\":", put_hex(out, sl.value, 32);
+            if (!w.node_set) {
+                out += ",\"proof\":";
+                put_nodes(out, w, w.proof_first_node[sl.proof], w.proof_first_node[sl.proof + 1]);
+            }
+            out += '}';
+        }
+        out += "]}";
+    }
+    out += "]}";
+    return true;
+}
+
+// The buffer-and-capacity form of the C ABI: len = the document's length, always; the text goes into buf only when cap holds it.
+bool witness_to_json(const Witness& w, char* buf, uint64_t cap, uint64_t& len) {
+    std::string text;
+    len = 0;
+    if (!witness_to_json(w, text)) return false;
+    len = (uint64_t)text.size();
+    if (buf && cap >= len && len) std::memcpy(buf, text.data(), text.size());
+    return true;
+}
+
 }  // namespace phant

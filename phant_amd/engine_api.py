@@ -111,6 +111,19 @@ class ExecutionWitness:
         ctx.check(rc)
         return status[:n], int(bad.value)
 
+    def to_json(self) -> str:
+        """phant_witness_to_json: the document parse_json reads back to the same witness (per-proof or node-set form; the index
+        form, whose nodes are still hex in its text, is refused)."""
+        need = C.c_uint64(0)
+        rc = self._lib.phant_witness_to_json(self._h, None, 0, C.byref(need))
+        if rc != L.OK:
+            raise L.PhantError(rc, "phant_witness_to_json: the index form holds no decoded nodes" if rc == L.E_UNSUPPORTED else "phant_witness_to_json")
+        buf = C.create_string_buffer(max(int(need.value), 1))
+        rc = self._lib.phant_witness_to_json(self._h, buf, need.value, C.byref(need))
+        if rc != L.OK:
+            raise L.PhantError(rc, "phant_witness_to_json")
+        return buf.raw[:need.value].decode()
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.phant_witness_free(self._h)

@@ -9,6 +9,7 @@ verifier the reference only has as a TODO
                                        execution_payload.zig:125-158
     verify_batch / verify_batch_dev    DESIGN.md section 3
     prove_nodeset / _packed / _dev     DESIGN.md section 7d (witness generation)
+    prove_batch / _packed / _dev       DESIGN.md section 7d (per-proof form: eth_getProof)
 """
 from __future__ import annotations
 
@@ -534,4 +535,100 @@ def prove_nodeset_dev(keys: torch.Tensor, key_off: torch.Tensor, vals: torch.Ten
     ctx.check(ctx._lib.phant_mpt_prove_nodeset_dev(ctx.handle, keys.data_ptr(), key_off.data_ptr(), keys.numel(), vals.data_ptr(),
                                                    val_off.data_ptr(), vals.numel(), n, ptr(seg_first), n_tries, qkeys.data_ptr(),
                                                    qkey_off.data_ptr(), qkeys.numel(), ptr(q_trie), ptr(q_flags), nq, C.byref(o)))
+    return int(o.total_nodes), int(o.nodes_len)
+
+
+@dataclass
+class ProvenBatch:
+    """What phant_mpt_prove_batch emits (numpy, host): an ordered node list per query, root first, the lists back to back in query
+    order.  (roots, root_idx = q_trie, nodes, node_off, proof_first_node) are what verify_batch takes.
+
+    roots (n_tries, 32) u8 | nodes u8[nodes_len] | node_off u64[total_nodes + 1] | proof_first_node u32[n_queries + 1] |
+    q_status u8[n_queries] (PROOF_PRESENT / PROOF_ABSENT)
+    """
+    roots: np.ndarray
+    nodes: np.ndarray
+    node_off: np.ndarray
+    proof_first_node: np.ndarray
+    q_status: np.ndarray
+
+    @property
+    def total_nodes(self) -> int:
+        return len(self.node_off) - 1
+
+    @property
+    def n_queries(self) -> int:
+        return len(self.proof_first_node) - 1
+
+    def node(self, k: int) -> bytes:
+        return self.nodes[int(self.node_off[k]):int(self.node_off[k + 1])].tobytes()
+
+    def proof(self, j: int) -> list[bytes]:
+        """the proof of query j: its nodes, root first"""
+        return [self.node(k) for k in range(int(self.proof_first_node[j]), int(self.proof_first_node[j + 1]))]
+
+
+def prove_batch_packed(keys, key_off, vals, val_off, seg_first, qkeys, qkey_off, q_trie=None, ctx: Context | None = None) -> ProvenBatch:
+    """phant_mpt_prove_batch over packed arrays: the forest and the queries as prove_nodeset_packed takes them (no q_flags).  The
+    first call guesses the capacities; if the proofs are larger the call is made once more with the sizes the first one reported."""
+    ctx = ctx or default_context()
+    keys = np.ascontiguousarray(keys, np.uint8)
+    key_off = np.ascontiguousarray(key_off, np.uint32)
+    vals = np.ascontiguousarray(vals, np.uint8)
+    val_off = np.ascontiguousarray(val_off, np.uint64)
+    n = len(key_off) - 1
+    seg = None if seg_first is None else np.ascontiguousarray(seg_first, np.uint32)
+    n_tries = 1 if seg is None else len(seg) - 1
+    qkeys = np.ascontiguousarray(qkeys, np.uint8)
+    qkey_off = np.ascontiguousarray(qkey_off, np.uint32)
+    nq = len(qkey_off) - 1
+    qt = None if q_trie is None else np.ascontiguousarray(q_trie, np.uint32)
+    roots = np.zeros((max(n_tries, 1), 32), np.uint8)
+    first = np.zeros(nq + 1, np.uint32)
+    status = np.zeros(max(nq, 1), np.uint8)
+    max_nodes, nodes_cap = 8 * nq + 64, (8 * nq + 64) * 256
+    for attempt in (0, 1):
+        nodes = np.zeros(max(nodes_cap, 1), np.uint8)
+        node_off = np.zeros(max_nodes + 1, np.uint64)
+        o = L.PhantProveBatchOut(C.sizeof(L.PhantProveBatchOut), max_nodes, nodes_cap, _np_ptr(nodes), _np_ptr(node_off), _np_ptr(first),
+                                 _np_ptr(roots), _np_ptr(status), 0, 0, 0)
+        rc = ctx._lib.phant_mpt_prove_batch(ctx.handle, _np_ptr(keys), _np_ptr(key_off), _np_ptr(vals), _np_ptr(val_off), n,
+                                            None if seg is None else _np_ptr(seg), n_tries, _np_ptr(qkeys), _np_ptr(qkey_off),
+                                            None if qt is None else _np_ptr(qt), nq, C.byref(o))
+        if rc == L.E_UNSORTED:
+            raise UnsortedError("prove_batch: keys must be strictly increasing inside every trie")
+        ctx.check(rc)
+        if o.total_nodes <= max_nodes and o.nodes_len <= nodes_cap:
+            return ProvenBatch(roots[:n_tries], nodes[:o.nodes_len], node_off[:o.total_nodes + 1], first, status[:nq])
+        max_nodes, nodes_cap = int(o.total_nodes), int(o.nodes_len)
+    raise RuntimeError("prove_batch: the reported sizes did not hold on the second call")
+
+
+def prove_batch(keyvals, queries, q_trie=None, seg_first=None, ctx: Context | None = None) -> ProvenBatch:
+    """An eth_getProof-shaped proof per query (an iterable of key bytes) against the trie holding `keyvals` (sorted KeyVals) -- or,
+    with seg_first, against a forest of tries laid end to end (q_trie says which).  -> ProvenBatch."""
+    kb, ko = _pack([kv.key for kv in keyvals], np.uint32)
+    vb, vo = _pack([kv.value for kv in keyvals], np.uint64)
+    qb, qo = _pack([bytes(q) for q in queries], np.uint32)
+    return prove_batch_packed(kb, ko, vb, vo, seg_first, qb, qo, q_trie, ctx)
+
+
+def prove_batch_dev(keys: torch.Tensor, key_off: torch.Tensor, vals: torch.Tensor, val_off: torch.Tensor,
+                    seg_first: torch.Tensor | None, qkeys: torch.Tensor, qkey_off: torch.Tensor, q_trie: torch.Tensor | None,
+                    nodes: torch.Tensor | None, node_off: torch.Tensor | None, proof_first_node: torch.Tensor | None = None,
+                    roots: torch.Tensor | None = None, q_status: torch.Tensor | None = None,
+                    ctx: Context | None = None) -> tuple[int, int]:
+    """phant_mpt_prove_batch_dev: every tensor device-resident (the forest and the queries as prove_nodeset_dev takes them; outputs
+    nodes u8[cap], node_off i64[max_nodes + 1], proof_first_node i32[nq + 1], roots u8, q_status u8, each optional).
+    -> (total_nodes, nodes_len); nodes / node_off / proof_first_node are valid only if both fit."""
+    ctx = ctx or default_context(keys.device.index)
+    n, nq = key_off.numel() - 1, qkey_off.numel() - 1
+    n_tries = 1 if seg_first is None else seg_first.numel() - 1
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    o = L.PhantProveBatchOut(C.sizeof(L.PhantProveBatchOut), 0 if node_off is None else node_off.numel() - 1,
+                             0 if nodes is None else nodes.numel(), ptr(nodes), ptr(node_off), ptr(proof_first_node), ptr(roots),
+                             ptr(q_status), 0, 0, 0)
+    ctx.check(ctx._lib.phant_mpt_prove_batch_dev(ctx.handle, keys.data_ptr(), key_off.data_ptr(), keys.numel(), vals.data_ptr(),
+                                                 val_off.data_ptr(), vals.numel(), n, ptr(seg_first), n_tries, qkeys.data_ptr(),
+                                                 qkey_off.data_ptr(), qkeys.numel(), ptr(q_trie), nq, C.byref(o)))
     return int(o.total_nodes), int(o.nodes_len)

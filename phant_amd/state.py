@@ -110,6 +110,29 @@ def state_trie_leaves(accounts, ctx: Context | None = None):
             [vals[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)])
 
 
+def get_proofs(accounts, keys, ctx: Context | None = None):
+    """eth_getProof over a state the caller holds (phant_state_proofs): `keys` are 20-byte addresses and 52-byte address ++ slot
+    strings (accounts in order of first appearance, slots grouped under their account, duplicates collapse).
+    -> engine_api.ExecutionWitness in its per-proof form (.info(), .verify(), .to_json()); the state root is left in `.state_root`."""
+    import ctypes as C
+
+    from .engine_api import ExecutionWitness
+    ctx = ctx or default_context()
+    n, arrays = _soa(accounts)
+    ks = [bytes(k) for k in keys]
+    off = np.zeros(len(ks) + 1, np.uint32)
+    if ks:
+        off[1:] = np.cumsum([len(k) for k in ks])
+    blob = np.frombuffer(b"".join(ks), np.uint8).copy() if off[-1] else np.zeros(1, np.uint8)
+    root = np.zeros(32, np.uint8)
+    h = C.c_void_p()
+    ctx.check(ctx._lib.phant_state_proofs(ctx.handle, *[_np_ptr(a) for a in arrays], n, _np_ptr(blob), _np_ptr(off), len(ks), C.byref(h),
+                                          _np_ptr(root)))
+    w = ExecutionWitness(h)
+    w.state_root = root.tobytes()
+    return w
+
+
 def code_hashes(codes, ctx: Context | None = None) -> np.ndarray:
     """keccak256 of every contract code in one launch <-> src/blockchain/vm.zig:284-298 `get_code_hash`
     (an account without code gets keccak256("") = vm.zig:22 `empty_hash`, which is what hashing the empty string

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""phant_mpt_prove_nodeset_dev on a big trie: one JSON line.
+"""phant_mpt_prove_nodeset_dev and phant_mpt_prove_batch_dev on a big trie: one JSON line.
 
 A trie of --keys random 32-byte keys (values of 70 .. 110 bytes, a state trie's leaves), --queries random queries of which one in
 ten is a key that is not stored.  Reported (medians over --reps calls, device time = phant_timing's region of the call):
@@ -8,7 +8,14 @@ ten is a key that is not stored.  Reported (medians over --reps calls, device ti
   oracle_ms           the oracle's trie_build + one prove per query on one core (one run)
   prove_over_root     prove_device_ms / root_device_ms
 The emitted set is checked against the oracle's union before anything is timed.
-Needs a GPU.  python tools/bench_prove.py [--keys 1000000] [--queries 3000] [--reps 20] [--warmup 3]
+The per-proof leg, on the same trie, for --queries and for --more-queries queries ("batch" / "batch_more" in the line):
+  batch_device_ms     phant_mpt_prove_batch_dev with every output wanted (median; _iqr: the interquartile spread)
+  nodeset_device_ms   phant_mpt_prove_nodeset_dev on the same queries: the yardstick
+  gather_ms           batch_device_ms minus the same call without a node blob (no gather launch): the gather kernel's share
+  gather_GBps         the proof blob's bytes / gather_ms (written; as many are read from the set)
+  oracle_prove_ms     the oracle's proofs of the same queries on one core (its trie built before)
+Every proof list is compared with the oracle's before anything is timed.
+Needs a GPU.  python tools/bench_prove.py [--keys 1000000] [--queries 3000] [--more-queries 100000] [--reps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -65,6 +72,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keys", type=int, default=1000000)
     ap.add_argument("--queries", type=int, default=3000)
+    ap.add_argument("--more-queries", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
@@ -121,7 +129,7 @@ def main():
     assert root.cpu().numpy().tobytes() == trie.root()
     assert int((status.cpu().numpy() == mpt.PROOF_ABSENT).sum()) == int(absent.sum())
 
-    def timed(fn):
+    def timed(fn, spread=False):
         ctx.check(ctx._lib.phant_timing(ctx.handle, 1))
         ms = []
         try:
@@ -131,14 +139,51 @@ def main():
                     ms.append(ctx.last_kernel_ms())
         finally:
             ctx.check(ctx._lib.phant_timing(ctx.handle, 0))
-        return float(np.median(ms))
+        q1, med, q3 = (float(x) for x in np.percentile(ms, [25, 50, 75]))
+        return (med, q3 - q1) if spread else med
 
     prove_ms = timed(prove)
     root_ms = timed(lambda: mpt.mptize_dev(*d, out=root, ctx=ctx))
+
+    def batch_leg(qs, tag):
+        """phant_mpt_prove_batch_dev over the queries `qs` (rows of 32 bytes) of the same trie"""
+        m = qs.shape[0]
+        dqs = [dev(qs.reshape(-1), np.uint8), dev((np.arange(m + 1, dtype=np.uint64) * 32).astype(np.uint32), np.int32)]
+        btn, bnl = mpt.prove_batch_dev(*d, None, *dqs, None, None, None, ctx=ctx)
+        b_nodes = torch.zeros(bnl, dtype=torch.uint8, device="cuda")
+        b_off = torch.zeros(btn + 1, dtype=torch.int64, device="cuda")
+        b_first = torch.zeros(m + 1, dtype=torch.int32, device="cuda")
+        b_status = torch.zeros(m, dtype=torch.uint8, device="cuda")
+        full = lambda: mpt.prove_batch_dev(*d, None, *dqs, None, b_nodes, b_off, b_first, root, b_status, ctx=ctx)  # noqa: E731
+        assert full() == (btn, bnl)
+        torch.cuda.synchronize()
+        hn, ho, hf = b_nodes.cpu().numpy().tobytes(), b_off.cpu().numpy(), b_first.cpu().numpy()
+        t0 = time.perf_counter()
+        lists = [trie.prove(qs[j].tobytes()) for j in range(m)]
+        oracle_prove_ms = (time.perf_counter() - t0) * 1e3
+        for j in range(m):
+            assert [hn[int(ho[k]):int(ho[k + 1])] for k in range(int(hf[j]), int(hf[j + 1]))] == lists[j], f"proof {j} differs from the oracle's"
+        assert root.cpu().numpy().tobytes() == trie.root()
+        sn, sl = mpt.prove_nodeset_dev(*d, None, *dqs, None, None, None, None, ctx=ctx)
+        s_nodes, s_off = torch.zeros(sl, dtype=torch.uint8, device="cuda"), torch.zeros(sn + 1, dtype=torch.int64, device="cuda")
+        b_ms, b_iqr = timed(full, True)
+        nb_ms, _ = timed(lambda: mpt.prove_batch_dev(*d, None, *dqs, None, None, b_off, b_first, root, b_status, ctx=ctx), True)
+        s_ms, s_iqr = timed(lambda: mpt.prove_nodeset_dev(*d, None, *dqs, None, None, s_nodes, s_off, None, root, b_status, ctx=ctx), True)
+        gather_ms = b_ms - nb_ms
+        return {tag: {"queries": m, "nodes": btn, "node_bytes": bnl, "batch_device_ms": round(b_ms, 4), "batch_device_ms_iqr": round(b_iqr, 4),
+                      "nodeset_device_ms": round(s_ms, 4), "nodeset_device_ms_iqr": round(s_iqr, 4), "gather_ms": round(gather_ms, 4),
+                      "gather_GBps": round(bnl / gather_ms / 1e6, 1) if gather_ms > 0 else None, "oracle_prove_ms": round(oracle_prove_ms, 1)}}
+
+    legs = batch_leg(q, "batch")
+    if args.more_queries:
+        q2 = raw[rng.integers(0, n, args.more_queries)].copy()
+        miss = rng.random(args.more_queries) < 0.1
+        q2[miss] = rng.integers(0, 256, (int(miss.sum()), 32), dtype=np.uint8)
+        legs.update(batch_leg(q2, "batch_more"))
     sw = state_witness_leg(O, ctx, args)
     print(json.dumps({"tool": "bench_prove", "keys": n, "queries": nq, "absent_queries": int(absent.sum()), "nodes": tn, "node_bytes": nl,
                       "prove_device_ms": round(prove_ms, 4), "root_device_ms": round(root_ms, 4), "oracle_ms": round(oracle_ms, 1),
-                      "prove_over_root": round(prove_ms / root_ms, 3), "reps": args.reps, **sw}))
+                      "prove_over_root": round(prove_ms / root_ms, 3), "reps": args.reps, **legs, **sw}))
 
 
 if __name__ == "__main__":
