@@ -81,6 +81,20 @@ PHANT_API int32_t phant_trie_stats(phant_ctx *ctx, uint32_t out[PHANT_TRIE_STATS
 PHANT_API int32_t phant_nodeset_tune(phant_ctx *ctx, int32_t form, uint32_t order, uint32_t hash_lds_bytes,
                                      uint32_t resident_wgs);
 
+/* What the last node-set launch on this ctx's own workspace did (phant_mpt_verify_nodeset*, the execution-witness calls; not the
+ * streaming slots): the path its launcher took and what its kernels counted, so that a test that forces a path can tell that the call
+ * took it.  All zeros if there was none.  Host integers the launcher has anyway, and the header words phant_verify_stats reads.
+ * Synchronises the ctx stream.
+ *   out[0]      the path: 0 = none, 1 = a wave per node in single-wave workgroups, 2 = a wave per node in four-wave workgroups,
+ *               3 = class lists
+ *   out[1 .. 9] nodes per list: the lists of 1, 2, ... 7, 8-or-more rate blocks, then the list of the nodes of exactly 532 bytes
+ *               (which phant_verify_stats counts with the four-block class, and this call does not)
+ *   out[10]     nodes that went to the overflow list (the record table did not take them: copies of a node already there)
+ *   out[11]     workgroups of the hash grid             out[12]  nodes offered
+ *   out[13]     the launch's epoch on the workspace */
+#define PHANT_NODESET_STATS 14
+PHANT_API int32_t phant_nodeset_stats(phant_ctx *ctx, uint32_t out[PHANT_NODESET_STATS]);
+
 /* One primitive of the secp256k1 arithmetic (phant_amd/csrc/secp256k1.hip.h) per lane, host arrays in and out, so that a carry
  * bug shows at the primitive and not as a wrong address 3 000 multiplications later.  Numbers are 32 big-endian bytes.
  *   op 0 field mul, 1 field sqr, 2 field inverse (0 -> 0), 4 scalar mul, 5 scalar inverse: rows of 32 bytes in a (and b for
@@ -134,7 +148,7 @@ enum {
     PHANT_DIAG_SORT_NO_FALLBACK,      /* state root: != 0: an undecided device sort is an error, not a host sort (tests) */
     PHANT_DIAG_SORT_PREFIX_BITS,      /* state root: the device sort on this many key bits, ties left undecided (-1: its own choice) */
     PHANT_DIAG_SORT_REPAIR_BITS,      /* ... ties repaired (-1: its own choice) */
-    PHANT_DIAG_NODESET_WAVE_MAX,      /* node-set witnesses of up to this many nodes are hashed a node per wave (default 2 048; 0: never) */
+    PHANT_DIAG_NODESET_WAVE_MAX,      /* node-set witnesses of up to this many nodes are hashed a node per wave (default 3 500; 0: never) */
     PHANT_DIAG_TRIE_SMALL_MAX_KEYS,   /* trie hasher: up to this many keys a call takes the two-launch pass for small tries (-1: the default, 0: never) */
     PHANT_DIAG_CODE_HASH_FORM,        /* phant_exec_witness_prestate: the codes hashed 0 = a half wave per code (the default), 1 = a lane per code */
     PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS,/* phant_exec_witness_poststate: != 0: a slot's 32 bytes ARE its storage-trie key, not hashed (tests: tries

@@ -142,6 +142,7 @@ SYMBOLS = {
     "phant_verify_path_stats": (_i32, [_vp, C.POINTER(C.c_uint32 * 2)]),
     "phant_verify_tier_stats": (_i32, [_vp, C.POINTER(C.c_uint32 * 5)]),
     "phant_trie_stats": (_i32, [_vp, C.POINTER(C.c_uint32 * 16)]),
+    "phant_nodeset_stats": (_i32, [_vp, C.POINTER(C.c_uint32 * 14)]),
     "phant_mpt_root_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp]),
     "phant_comm_create": (_i32, [_vp, _u32, _u32, C.POINTER(_vp)]),
     "phant_comm_destroy": (None, [_vp]),

@@ -149,6 +149,14 @@ class Context:
                 "bins": v[3], "max_bin": v[4], "wave": v[5], "half_wave": v[6], "blocks1": v[7], "blocks2": v[8], "blocks4": v[9],
                 "misfits": v[10], "leaf_big": bool(v[11]), "n_rep": v[12], "n": v[13], "side_bins": v[14], "scratch_bytes": v[15]}
 
+    def nodeset_stats(self) -> list[int]:
+        """What the last node-set launch on this ctx did (phant_nodeset_stats): [0] the path (0 none, 1 / 2 a wave per node in
+        workgroups of one / four waves, 3 class lists), [1..9] nodes per list (1 .. 7, 8 or more rate blocks, then exactly 532 bytes),
+        [10] nodes on the overflow list, [11] workgroups of the hash grid, [12] nodes offered, [13] the epoch."""
+        out = (C.c_uint32 * 14)()
+        self.check(self._lib.phant_nodeset_stats(self._h, C.byref(out)))
+        return [int(x) for x in out]
+
     def verify_path_stats(self) -> tuple[int, int]:
         """(proofs verified from scratch by their walk lane, nodes decoded by walks that decoded more than one)."""
         out = (C.c_uint32 * 2)()

@@ -58,6 +58,7 @@ struct phant_ctx {
     uint32_t ns_salt[2] = {0, 0};  // key of its record table's slot function
     phant::NodesetTune ns_tune;
     bool last_was_nodeset = false;  // which pipeline phant_verify_stats reports on
+    uint32_t ns_last[3] = {0, 0, 0};  // what the last node-set launch on `ns` chose (NodesetTune::last; phant_nodeset_stats)
     phant::VerifyTune tune;
     int32_t dedup_levels = -1;  // trie levels deduplicated by the two-tier pipeline: < 0 = from the batch size, 0 = none
     // helper stream of the two-tier pipeline: its deep tier runs there, next to the shallow tier (created on first use)
@@ -308,6 +309,26 @@ int32_t phant_verify_stats(phant_ctx* c, uint32_t hashed[8]) {
     uint32_t hdr[phant::VERIFY_HEADER_WORDS];
     HIP_TRY(c, hipMemcpy(hdr, c->dv.base, sizeof(hdr), hipMemcpyDeviceToHost));
     phant::verify_stats_from_header(hdr, hashed);
+    return PHANT_OK;
+}
+
+int32_t phant_nodeset_stats(phant_ctx* c, uint32_t out[PHANT_NODESET_STATS]) {
+    if (!c || !out) return PHANT_E_INVALID_ARG;
+    for (int i = 0; i < PHANT_NODESET_STATS; ++i) out[i] = 0;
+    // (a workspace about to be zeroed -- fresh, or a launch on it failed -- holds no launch to describe)
+    if (!c->ns.dv.base || c->ns.dirty || c->ns.epoch == 0u || c->ns_last[0] == 0u) return PHANT_OK;
+    DeviceGuard g(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t hdr[phant::VERIFY_HEADER_WORDS];
+    HIP_TRY(c, hipMemcpy(hdr, c->ns.dv.base, sizeof(hdr), hipMemcpyDeviceToHost));
+    uint32_t hashed[8], overflow = 0;
+    phant::verify_nodeset_stats_from_header(hdr, c->ns.epoch, hashed, &overflow);
+    phant::verify_nodeset_lists_from_header(hdr, c->ns.epoch, out + 1);
+    out[0] = c->ns_last[0];
+    out[10] = overflow;
+    out[11] = c->ns_last[1];
+    out[12] = c->ns_last[2];
+    out[13] = c->ns.epoch;
     return PHANT_OK;
 }
 
@@ -1233,6 +1254,13 @@ static int32_t nodeset_prepare(phant_ctx* c, uint32_t total_nodes, hipStream_t s
     return PHANT_OK;
 }
 
+// The ctx's tune for a launch on `sp`; on the ctx's own workspace the launcher notes what it chose (phant_nodeset_stats).
+static phant::NodesetTune nodeset_tune_on(phant_ctx* c, const NodesetSpace& sp) {
+    phant::NodesetTune t = c->ns_tune;
+    t.last = &sp == &c->ns ? c->ns_last : nullptr;
+    return t;
+}
+
 namespace {
 
 // A copy in of an array that may be empty, and a copy back that the caller may not want (a NULL destination): neither is a copy.
@@ -1305,7 +1333,7 @@ struct PrestateStage {
         const phant::VerifyArgs acc{root, 1, nullptr, keys, 32, nodes, nodes_len, noff, nullptr, na, p.acc_status, avoff, avlen};
         const phant::VerifyArgs sto{p.storage_roots, na, sacc, keys + 32ull * na, 32, nodes, nodes_len, noff, nullptr, ns,
                                     p.slot_status, svoff, svlen};
-        hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s, c->ns_tune);
+        hipError_t e = phant::launch_nodeset_hash(acc, total_nodes, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s, nodeset_tune_on(c, sp));
         if (e == hipSuccess) e = phant::launch_nodeset_walk(acc, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s);
         if (e == hipSuccess) e = phant::launch_prestate_accounts(p, s);
         if (e == hipSuccess) e = phant::launch_nodeset_walk(sto, sp.cap_nodes, sp.dv.base, sp.epoch, c->ns_salt, s);
@@ -1360,7 +1388,7 @@ static int32_t run_verify(phant_ctx* c, const Lane& w, phant::VerifyArgs a, uint
         {
             TimedRegion t(c, w.timed);
             e = phant::launch_mpt_verify_nodeset(a, total_nodes, w.ns.cap_nodes, w.ns.dv.base, w.ns.epoch, c->ns_salt, w.stream,
-                                                 c->ns_tune);
+                                                 nodeset_tune_on(c, w.ns));
         }
         if (e != hipSuccess) {
             w.ns.dirty = true;  // (whatever part of the launch ran: the next one starts from zeroed memory)

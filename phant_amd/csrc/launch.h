@@ -130,6 +130,9 @@ struct NodesetTune {
                                 // over the chunk queue (A/B: one generation of waves, every wave a four-permutation chunk and then
                                 // maybe a one-permutation one -- measured SLOWER, 199 against 190 us: the lockstep it creates costs
                                 // more than the thin second generation it avoids)
+    uint32_t* last = nullptr;   // diagnostics (phant_nodeset_stats): where launch_nodeset_hash notes what it chose -- [0] the path (1 = a wave
+                                // per node in single-wave workgroups, 2 = in four-wave workgroups, 3 = class lists), [1] the workgroups
+                                // of the hash grid, [2] the nodes offered
 };
 uint32_t verify_nodeset_capacity(uint32_t total_nodes);
 size_t verify_nodeset_workspace_bytes(uint32_t cap_nodes);
@@ -138,6 +141,9 @@ hipError_t launch_mpt_verify_nodeset(const VerifyArgs& a, uint32_t total_nodes, 
 // nodes hashed per rate-block class by the launch of `epoch`, from a host copy of the workspace's first VERIFY_HEADER_WORDS
 // words; *overflow (may be null): nodes that went through the second table
 void verify_nodeset_stats_from_header(const uint32_t* hdr, uint32_t epoch, uint32_t hashed[8], uint32_t* overflow);
+// the same counts list by list, not folded into classes: lists[0 .. 7] = the rate-block classes without the 532-byte nodes, lists[8] =
+// the nodes of exactly 532 bytes
+void verify_nodeset_lists_from_header(const uint32_t* hdr, uint32_t epoch, uint32_t lists[9]);
 // prestate.hip.h (included by mpt_verify_nodeset.hip): the pre-state of an execution witness between and behind the two walks of
 // the node-set pipeline (phant_exec_witness_prestate).  Every pointer is device memory of the call.
 struct PrestateArgs {

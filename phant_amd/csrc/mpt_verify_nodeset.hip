@@ -650,13 +650,19 @@ hipError_t launch_nodeset_hash(const VerifyArgs& v, uint32_t total_nodes, uint32
     if (total_nodes > cap_nodes) return hipErrorInvalidValue;
     const Args a = nodeset_args(v, total_nodes, cap_nodes, ws, epoch, salt, tune.order);
     const uint32_t ng = total_nodes ? (total_nodes + 255u) / 256u : 1u;
+    const auto note = [&](uint32_t path, uint32_t hash_wgs) {
+        if (tune.last) tune.last[0] = path, tune.last[1] = hash_wgs, tune.last[2] = total_nodes;
+    };
     if (v.n != 0 && total_nodes != 0 && total_nodes <= tune.wave_max) {
         // a wave per node (up to two waves per CU the workgroups are single waves, which the dispatcher spreads over the CUs:
         // the sponge's fetches share a CU's LDS pipeline); the kernel clears what set_classify_kernel clears
-        if (total_nodes <= 512u) hipLaunchKernelGGL(set_hash_wave_kernel, dim3(total_nodes), dim3(64), 0, st, a);
+        const bool single = total_nodes <= 512u;
+        note(single ? 1u : 2u, single ? total_nodes : (total_nodes + 3u) / 4u);
+        if (single) hipLaunchKernelGGL(set_hash_wave_kernel, dim3(total_nodes), dim3(64), 0, st, a);
         else hipLaunchKernelGGL(set_hash_wave_kernel, dim3((total_nodes + 3u) / 4u), dim3(256), 0, st, a);
     } else {
         // (always: it is what clears the next launch's cursors and this launch's verdict)
+        note(3u, 0u);
         hipLaunchKernelGGL(set_classify_kernel, dim3(ng), dim3(256), 0, st, a);
         if (v.n == 0) return hipGetLastError();
         if (total_nodes) {
@@ -664,6 +670,7 @@ hipError_t launch_nodeset_hash(const VerifyArgs& v, uint32_t total_nodes, uint32
             // workgroups as the chip holds at once (NodesetTune::resident_wgs), whose waves then stride over the queue
             const uint32_t all = ng + (N_QUEUE + 3u) / 4u;
             const uint32_t wgs = tune.resident_wgs && tune.resident_wgs < all ? tune.resident_wgs : all;
+            note(3u, wgs);
             if (tune.form == 2u) hipLaunchKernelGGL(set_hash_kernel<2>, dim3(wgs), dim3(256), tune.hash_lds, st, a);
             else if (tune.form == 1u) hipLaunchKernelGGL(set_hash_kernel<1>, dim3(wgs), dim3(256), tune.hash_lds, st, a);
             else hipLaunchKernelGGL(set_hash_kernel<0>, dim3(wgs), dim3(256), tune.hash_lds, st, a);
@@ -689,17 +696,25 @@ hipError_t launch_mpt_verify_nodeset(const VerifyArgs& v, uint32_t total_nodes, 
     return launch_nodeset_walk(v, cap_nodes, ws, epoch, salt, st);
 }
 
-// nodes hashed per rate-block class by the launch of `epoch` on this workspace (host copy of its header)
+// nodes per list of the launch of `epoch` on this workspace (host copy of its header): the eight rate-block classes, then the 532-byte list
+void verify_nodeset_lists_from_header(const uint32_t* hdr, uint32_t epoch, uint32_t lists[9]) {
+    using namespace ns;
+    static_assert(N_LIST == 9, "lists[9]");
+    const uint32_t parity = epoch & 1u;
+    for (uint32_t c = 0; c < N_LIST; ++c) {
+        lists[c] = 0;
+        for (uint32_t s = 0; s < STRIPES; ++s) lists[c] += hdr[HDR_CUR + 256u * parity + 32u * s + c];
+    }
+}
+
+// nodes hashed per rate-block class by that launch (the 532-byte list counted with the four-block class)
 void verify_nodeset_stats_from_header(const uint32_t* hdr, uint32_t epoch, uint32_t hashed[8], uint32_t* overflow) {
     using namespace ns;
-    const uint32_t parity = epoch & 1u;
-    for (uint32_t c = 0; c < N_CLASS; ++c) hashed[c] = 0;
-    for (uint32_t c = 0; c < N_LIST; ++c) {
-        uint32_t cnt = 0;
-        for (uint32_t s = 0; s < STRIPES; ++s) cnt += hdr[HDR_CUR + 256u * parity + 32u * s + c];
-        hashed[c == LIST_B532 ? BRANCH_LEN / RATE : c] += cnt;
-    }
-    if (overflow) *overflow = hdr[HDR_OVF + 32u * parity];
+    uint32_t lists[N_LIST];
+    verify_nodeset_lists_from_header(hdr, epoch, lists);
+    for (uint32_t c = 0; c < N_CLASS; ++c) hashed[c] = lists[c];
+    hashed[BRANCH_LEN / RATE] += lists[LIST_B532];
+    if (overflow) *overflow = hdr[HDR_OVF + 32u * (epoch & 1u)];
 }
 
 }  // namespace phant

@@ -99,6 +99,7 @@ _PROTOS = {
                                             _vp, _vp, _vp]),
     "phant_mpt_verify_nodeset": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp]),
     "phant_verify_stats": (_i32, [_vp, _vp]),
+    "phant_nodeset_stats": (_i32, [_vp, _vp]),
     "phant_verify_path_stats": (_i32, [_vp, _vp]),
 }
 

@@ -47,7 +47,7 @@ def test_the_boundary_header_holds_no_diagnostics_and_the_library_reads_no_envir
     for name in ("phant_timing", "phant_last_kernel_ms", "phant_verify_stats", "phant_verify_path_stats", "phant_verify_tier_stats",
                  "phant_verify_kernel_ms", "phant_verify_form", "phant_verify_bound_experiment", "phant_keccak_rate",
                  "phant_nodeset_tune", "phant_diag_set", "phant_trie_stats", "phant_diag_scan_u32", "phant_diag_sort_pairs",
-                 "phant_diag_order_digests"):
+                 "phant_diag_order_digests", "phant_nodeset_stats"):
         assert name in diag and name not in boundary, name
     hdr = open(os.path.join(ROOT, "include", "phant_gpu.h")).read()
     for gone in ("VERIFY_FUSED", "VERIFY_NODEDUP", "VERIFY_ORDERED", "KEY_ORDERED"):

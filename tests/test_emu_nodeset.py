@@ -60,7 +60,7 @@ def test_hostile_index_arrays_match_the_checked_oracle(M, oracle):
 
 
 def test_small_sets_through_the_class_lists_as_well():
-    """A set of up to 2 048 nodes takes the wave-per-node kernel (set_hash_wave_kernel), so most of this module's sets do; here
+    """A set of up to 3 500 nodes takes the wave-per-node kernel (set_hash_wave_kernel), so most of this module's sets do; here
     the same tests with it off (nodeset_wave_max = 0: classify + the lane-per-node hash kernel at every size), in a child pytest
     (the switch is per ctx: tests/diag.py)."""
     import os, subprocess, sys
