@@ -50,8 +50,9 @@
 #include "staging.h"
 #define AL_HD __host__ __device__ inline
 #endif
+#include "keyed_table.hip.h"   // the keyed mix; claim and find over the slot, tuple and key tables
 #include "transactions.hip.h"  // tx::rlp_item: rlp.h's decoder over a span
-#include "txstate.hip.h"       // txst::load_addr, home_slot, same_addr: the address table's lane functions
+#include "txstate.hip.h"       // txst::Args, txst_insert_kernel, row_of: the address table over the witness's addresses
 
 namespace phant {
 namespace al {
@@ -102,19 +103,19 @@ AL_HD bool same_key(const uint8_t* p, const uint32_t w[8]) {
     for (int k = 0; k < 8; ++k) same = same && v[k] == w[k];
     return same;
 }
-// The keyed mix of the address table carried on over four more words: txst::home_slot again, keyed with what it made of the words
+// The keyed mix of the address table carried on over four more words: keyed::home_slot again, keyed with what it made of the words
 // before.  Witness keys and access-list keys are attacker-chosen bytes; without the ctx's key nobody aims them at one slot.
 AL_HD uint32_t mix_on(uint32_t h, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t salt1) {
     const uint32_t w[5] = {x0, x1, x2, x3, 0u};
-    return txst::home_slot(w, h, salt1);
+    return keyed::home_slot(w, h, salt1);
 }
 // where (row, key) is looked for first: all 32 key bytes and the row
 AL_HD uint32_t slot_home(uint32_t row, const uint32_t key[8], uint32_t salt0, uint32_t salt1) {
-    return mix_on(txst::home_slot(key, salt0, salt1), key[5], key[6], key[7], row, salt1);
+    return mix_on(keyed::home_slot(key, salt0, salt1), key[5], key[6], key[7], row, salt1);
 }
 // where (transaction, address) is looked for first
 AL_HD uint32_t tuple_home(uint32_t txi, const uint32_t addr[5], uint32_t salt0, uint32_t salt1) {
-    return mix_on(txst::home_slot(addr, salt0, salt1), txi, 0u, 0u, 0u, salt1);
+    return mix_on(keyed::home_slot(addr, salt0, salt1), txi, 0u, 0u, 0u, salt1);
 }
 
 #ifndef PHANT_AL_WALK_ONLY
@@ -165,34 +166,6 @@ __device__ inline uint32_t last_at_or_below(const uint32_t* first, uint32_t cnt,
 __device__ inline const uint8_t* key_bytes(const Args& a, uint32_t k) {
     const uint32_t e = a.k_tuple[k];
     return span_of(a, a.t_tx[e]) + key_at(a.t_keys[e], k - a.t_kfirst[e]);
-}
-
-// `me` into a table: a free slot is claimed by compare-and-swap; a slot whose holder is `same` as me is lowered to the lower index, so
-// equal entries resolve to the lowest whatever the order of arrival.  (A slot only ever holds entries equal to its first; the table is at
-// most half full: the walk ends long before it has gone round.)
-template <class Same>
-__device__ inline void claim(uint32_t* table, uint32_t mask, uint32_t home, uint32_t me, Same same) {
-    uint32_t slot = home & mask;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        const uint32_t old = atomicCAS(table + slot, (uint32_t)NONE, me);
-        if (old == NONE) return;
-        if (same(old)) {
-            atomicMin(table + slot, me);
-            return;
-        }
-        slot = (slot + 1u) & mask;
-    }
-}
-template <class Same>
-__device__ inline uint32_t find(const uint32_t* table, uint32_t mask, uint32_t home, Same same) {
-    uint32_t slot = home & mask;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        const uint32_t j = table[slot];
-        if (j == NONE) return NONE;
-        if (same(j)) return j;
-        slot = (slot + 1u) & mask;
-    }
-    return NONE;
 }
 
 // Of the lanes of a wave that have a record of the same transaction, the lowest adds the group's first occurrences to the row's
@@ -296,8 +269,8 @@ __global__ void __launch_bounds__(256) al_insert_kernel(Args a, uint32_t slot_bl
         const uint32_t lo = in.slot_first[row], hi = in.slot_first[row + 1u];
         uint32_t w[8];
         load_key(in.slots + 32ull * s, w);
-        claim(a.slot_table, a.slot_mask, slot_home(row, w, a.salt0, a.salt1), s,
-              [&](uint32_t old) { return old >= lo && old < hi && same_key(in.slots + 32ull * old, w); });
+        keyed::claim(a.slot_table, a.slot_mask, slot_home(row, w, a.salt0, a.salt1), s,
+                     [&](uint32_t old) { return old >= lo && old < hi && same_key(in.slots + 32ull * old, w); });
     } else {
         const uint32_t e = (blockIdx.x - slot_blocks) * 256u + threadIdx.x;
         if (e >= tuples_claimed(a) || e >= a.tuple_bound) return;
@@ -305,9 +278,9 @@ __global__ void __launch_bounds__(256) al_insert_kernel(Args a, uint32_t slot_bl
         if (flagged(a, txi)) return;
         const uint8_t* const p = span_of(a, txi);
         uint32_t w[5];
-        txst::load_addr(p + a.t_addr[e], w);
-        claim(a.tuple_table, a.tuple_mask, tuple_home(txi, w, a.salt0, a.salt1), e,
-              [&](uint32_t old) { return a.t_tx[old] == txi && txst::same_addr(p + a.t_addr[old], w); });
+        keyed::load_addr(p + a.t_addr[e], w);
+        keyed::claim(a.tuple_table, a.tuple_mask, tuple_home(txi, w, a.salt0, a.salt1), e,
+                     [&](uint32_t old) { return a.t_tx[old] == txi && keyed::same_addr(p + a.t_addr[old], w); });
     }
 }
 
@@ -328,9 +301,9 @@ __global__ void __launch_bounds__(256) al_tuples_kernel(Args a, txst::Args ta) {
     if (has) {
         const uint8_t* const p = span_of(a, txi);
         uint32_t w[5];
-        txst::load_addr(p + a.t_addr[e], w);
-        const uint32_t same = find(a.tuple_table, a.tuple_mask, tuple_home(txi, w, a.salt0, a.salt1),
-                                   [&](uint32_t j) { return a.t_tx[j] == txi && txst::same_addr(p + a.t_addr[j], w); });
+        keyed::load_addr(p + a.t_addr[e], w);
+        const uint32_t same = keyed::find(a.tuple_table, a.tuple_mask, tuple_home(txi, w, a.salt0, a.salt1),
+                                          [&](uint32_t j) { return a.t_tx[j] == txi && keyed::same_addr(p + a.t_addr[j], w); });
         row = ta.in.n_accounts ? txst::row_of(ta, ta.table, ta.mask, p + a.t_addr[e]) : (uint32_t)NONE;
         a.t_same[e] = same, a.t_row[e] = row;
         first = same == e;
@@ -353,8 +326,8 @@ __global__ void __launch_bounds__(256) al_key_insert_kernel(Args a) {
     const uint32_t under = a.t_same[e];
     uint32_t w[8];
     load_key(key_bytes(a, k), w);
-    claim(a.key_table, a.key_mask, slot_home(under, w, a.salt0, a.salt1), k,
-          [&](uint32_t old) { return a.t_same[a.k_tuple[old]] == under && same_key(key_bytes(a, old), w); });
+    keyed::claim(a.key_table, a.key_mask, slot_home(under, w, a.salt0, a.salt1), k,
+                 [&](uint32_t old) { return a.t_same[a.k_tuple[old]] == under && same_key(key_bytes(a, old), w); });
 }
 
 __global__ void __launch_bounds__(256) al_key_finish_kernel(Args a) {
@@ -371,12 +344,12 @@ __global__ void __launch_bounds__(256) al_key_finish_kernel(Args a) {
         const uint32_t under = a.t_same[e], row = a.t_row[e];
         uint32_t w[8];
         load_key(key_bytes(a, k), w);
-        const uint32_t same = find(a.key_table, a.key_mask, slot_home(under, w, a.salt0, a.salt1),
-                                   [&](uint32_t j) { return a.t_same[a.k_tuple[j]] == under && same_key(key_bytes(a, j), w); });
+        const uint32_t same = keyed::find(a.key_table, a.key_mask, slot_home(under, w, a.salt0, a.salt1),
+                                          [&](uint32_t j) { return a.t_same[a.k_tuple[j]] == under && same_key(key_bytes(a, j), w); });
         if (row != NONE) {
             const uint32_t lo = in.slot_first[row], hi = in.slot_first[row + 1u];
-            srow = find(a.slot_table, a.slot_mask, slot_home(row, w, a.salt0, a.salt1),
-                        [&](uint32_t s) { return s >= lo && s < hi && same_key(in.slots + 32ull * s, w); });
+            srow = keyed::find(a.slot_table, a.slot_mask, slot_home(row, w, a.salt0, a.salt1),
+                               [&](uint32_t s) { return s >= lo && s < hi && same_key(in.slots + 32ull * s, w); });
         }
         first = same == k;
         const uint32_t shift = key_shift(a, txi), out = k - shift;
@@ -388,15 +361,6 @@ __global__ void __launch_bounds__(256) al_key_finish_kernel(Args a) {
     tally(a, has, txi, first, a.o.warm_keys);
     tally_missing(a.ctl + C_MISS_SLOTS, has && first && srow == NONE);
 }
-
-#define AL_TRY(call)                                                               \
-    do {                                                                           \
-        const hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) {                                                    \
-            err = std::string("block_access_lists: " #call ": ") + hipGetErrorString(e_); \
-            return PHANT_E_DEVICE;                                                 \
-        }                                                                          \
-    } while (0)
 
 // what the host form refuses before anything is copied -> the bytes of all spans in `total`
 inline const char* check_host(const phant_access_in& in, uint64_t& total) {
@@ -413,12 +377,6 @@ inline const char* check_host(const phant_access_in& in, uint64_t& total) {
     return nullptr;
 }
 
-inline uint32_t table_slots(uint64_t entries) {  // a power of two, at least twice the entries (entries <= 2^30)
-    uint32_t slots = 64;
-    while (slots < 2ull * entries) slots <<= 1;
-    return slots;
-}
-
 }  // namespace al
 
 int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in& in, phant_access_out& out, bool dev, const uint32_t salt[2],
@@ -426,7 +384,7 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
     using namespace al;
     const char* const who = dev ? "block_access_lists_dev: " : "block_access_lists: ";
     const uint32_t n = in.n, na = in.n_accounts, ns = na ? in.n_slots : 0u;
-    AL_TRY(ws.ensure_mailbox());
+    CALL_TRY("block_access_lists", ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_AL_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_AL;
     Args a;
@@ -442,11 +400,11 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
         if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, [&](auto& io) { a.ctl = io.template take<uint32_t>(CTL_WORDS); }),
                                               "block_access_lists_dev", "workspace", err))
             return rc;
-        AL_TRY(hipMemsetAsync(a.ctl, 0, 4 * CTL_WORDS, st));
+        CALL_TRY("block_access_lists", hipMemsetAsync(a.ctl, 0, 4 * CTL_WORDS, st));
         const uint64_t lanes = std::max<uint64_t>(n, na ? (uint64_t)na + 1u : 0u);
         hipLaunchKernelGGL(al_check_args_kernel, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, st, a);
-        AL_TRY(hipGetLastError());
-        AL_TRY(ws.read_words(Workspaces::MAILBOX_AL, a.ctl, CTL_WORDS, st));
+        CALL_TRY("block_access_lists", hipGetLastError());
+        CALL_TRY("block_access_lists", ws.read_words(Workspaces::MAILBOX_AL, a.ctl, CTL_WORDS, st));
         if (mb[C_BAD] & BAD_SPAN) return err = std::string(who) + "a span leaves [0, tx_bytes)", PHANT_E_INVALID_ARG;
         if (mb[C_BAD] & BAD_SLOT_FIRST) return err = std::string(who) + "slot_first does not run from 0 to n_slots without going backwards", PHANT_E_INVALID_ARG;
         total = (uint64_t)mb[C_BYTES_LO] | (uint64_t)mb[C_BYTES_HI] << 32;
@@ -456,7 +414,7 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
     // ---- the arena: the zeroed words (control, flags and warm counts) and the outputs in front (one span goes back), (host form) the
     // inputs, then the records and the tables
     const uint32_t tb = (uint32_t)(total / MIN_TUPLE_BYTES), kb = (uint32_t)(total / KEY_ITEM_BYTES);
-    const uint32_t addr_slots = table_slots(na), slot_slots = table_slots(ns), tuple_slots = table_slots(tb), key_slots = table_slots(kb);
+    const uint32_t addr_slots = keyed::table_slots(na), slot_slots = keyed::table_slots(ns), tuple_slots = keyed::table_slots(tb), key_slots = keyed::table_slots(kb);
     const size_t zero_words = (size_t)CTL_WORDS + 3 * (size_t)n, scan_n = 2 * (size_t)n + 2;
     a.tuple_bound = tb, a.key_bound = kb;
     a.slot_mask = slot_slots - 1u, a.tuple_mask = tuple_slots - 1u, a.key_mask = key_slots - 1u;
@@ -504,15 +462,15 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
     ta.in.n_accounts = na, ta.in.addresses = a.in.addresses;
     ta.table = ones, ta.mask = addr_slots - 1u, ta.salt0 = salt[0], ta.salt1 = salt[1];
     a.slot_table = ones + addr_slots, a.tuple_table = a.slot_table + slot_slots, a.key_table = a.tuple_table + tuple_slots;
-    AL_TRY(hipMemsetAsync(zero, 0, 4 * zero_words, st));
-    AL_TRY(hipMemsetAsync(ones, 0xff, 4 * ((size_t)addr_slots + slot_slots + tuple_slots + key_slots), st));
+    CALL_TRY("block_access_lists", hipMemsetAsync(zero, 0, 4 * zero_words, st));
+    CALL_TRY("block_access_lists", hipMemsetAsync(ones, 0xff, 4 * ((size_t)addr_slots + slot_slots + tuple_slots + key_slots), st));
 
     // ---- in, host form: the spans' bytes back to back (nothing else of the transactions crosses the bus), where they begin, the tables
     std::vector<uint64_t> off;
     std::vector<uint8_t> blob;
     if (!dev) {
         StagedInputs ins(ws, st, in_begin, in_end);
-        AL_TRY(ins.e);
+        CALL_TRY("block_access_lists", ins.e);
         off.resize(n);
         if (!ins.staged) blob.resize(total);
         uint8_t* const pack = ins.staged ? ws.staged(d_blob) : blob.data();
@@ -528,7 +486,7 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
         ins.put(a.in.addresses, in.addresses, 20 * (size_t)na);
         if (na) ins.put(a.in.slot_first, in.slot_first, 4 * ((size_t)na + 1));
         ins.put(a.in.slots, in.slots, 32 * (size_t)ns);
-        AL_TRY(ins.finish());
+        CALL_TRY("block_access_lists", ins.finish());
         a.in.txs = d_blob, a.in.al_off = d_off, a.in.tx_bytes = total;
         ta.in.addresses = a.in.addresses;
     }
@@ -536,37 +494,37 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
     // ---- the walk, the verdicts, the final places
     const auto blocks = [](uint64_t lanes) { return dim3((uint32_t)((lanes + 255u) / 256u)); };
     hipLaunchKernelGGL(al_walk_kernel, blocks(n), dim3(256), 0, st, a);
-    AL_TRY(hipGetLastError());
-    AL_TRY(launch_exclusive_scan_u32(a.s1, (uint32_t)scan_n, scan, st));
+    CALL_TRY("block_access_lists", hipGetLastError());
+    CALL_TRY("block_access_lists", launch_exclusive_scan_u32(a.s1, (uint32_t)scan_n, scan, st));
     if (tb) {
         hipLaunchKernelGGL(al_emit_kernel, blocks(n), dim3(256), 0, st, a);
-        AL_TRY(hipGetLastError());
+        CALL_TRY("block_access_lists", hipGetLastError());
     }
     if (kb) {
         hipLaunchKernelGGL(al_keys_kernel, blocks(kb), dim3(256), 0, st, a);
-        AL_TRY(hipGetLastError());
+        CALL_TRY("block_access_lists", hipGetLastError());
     }
     hipLaunchKernelGGL(al_verdict_kernel, blocks(n), dim3(256), 0, st, a);
-    AL_TRY(hipGetLastError());
-    AL_TRY(launch_exclusive_scan_u32(a.s2, (uint32_t)scan_n, scan, st));
+    CALL_TRY("block_access_lists", hipGetLastError());
+    CALL_TRY("block_access_lists", launch_exclusive_scan_u32(a.s2, (uint32_t)scan_n, scan, st));
 
     // ---- the tables, the joins
     if (na && tb) {
         hipLaunchKernelGGL(txst::txst_insert_kernel, blocks(na), dim3(256), 0, st, ta);
-        AL_TRY(hipGetLastError());
+        CALL_TRY("block_access_lists", hipGetLastError());
     }
     const uint32_t slot_blocks = kb ? blocks(ns).x : 0u;  // (without a key nobody asks the slot table)
     if (slot_blocks + blocks(tb).x) {
         hipLaunchKernelGGL(al_insert_kernel, dim3(slot_blocks + blocks(tb).x), dim3(256), 0, st, a, slot_blocks);
-        AL_TRY(hipGetLastError());
+        CALL_TRY("block_access_lists", hipGetLastError());
     }
     hipLaunchKernelGGL(al_tuples_kernel, blocks(std::max(tb, 1u)), dim3(256), 0, st, a, ta);
-    AL_TRY(hipGetLastError());
+    CALL_TRY("block_access_lists", hipGetLastError());
     if (kb) {
         hipLaunchKernelGGL(al_key_insert_kernel, blocks(kb), dim3(256), 0, st, a);
-        AL_TRY(hipGetLastError());
+        CALL_TRY("block_access_lists", hipGetLastError());
         hipLaunchKernelGGL(al_key_finish_kernel, blocks(kb), dim3(256), 0, st, a);
-        AL_TRY(hipGetLastError());
+        CALL_TRY("block_access_lists", hipGetLastError());
     }
 
     // ---- out: the control words and the per-transaction outputs; the host form's one span also reaches over the per-tuple and per-key
@@ -587,7 +545,7 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
         if (out.slot_row) outs.cover(a.o.slot_row + kcap);
         if (out.key_same) outs.cover(a.o.key_same + kcap);
     }
-    AL_TRY(outs.deliver());
+    CALL_TRY("block_access_lists", outs.deliver());
     const uint32_t tuples = outs.ctl()[C_TUPLES], keys = outs.ctl()[C_KEYS];
     out.n_tuples = tuples, out.n_keys = keys;
     out.n_missing_accounts = outs.ctl()[C_MISS_ACCOUNTS], out.n_missing_slots = outs.ctl()[C_MISS_SLOTS];
@@ -601,12 +559,11 @@ int32_t block_access_lists(Workspaces& ws, hipStream_t st, const phant_access_in
     outs.add(out.key, a.o.key, 32 * (size_t)keys);
     outs.add(out.slot_row, a.o.slot_row, 4 * (size_t)keys);
     outs.add(out.key_same, a.o.key_same, 4 * (size_t)keys);
-    AL_TRY(outs.deliver());
-    if (dev) AL_TRY(hipStreamSynchronize(st));
+    CALL_TRY("block_access_lists", outs.deliver());
+    if (dev) CALL_TRY("block_access_lists", hipStreamSynchronize(st));
     return PHANT_OK;
 }
 
-#undef AL_TRY
 
 }  // namespace phant
 #else

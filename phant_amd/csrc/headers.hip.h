@@ -349,15 +349,6 @@ __global__ void __launch_bounds__(256) hdr_check_kernel(In in, const uint8_t* __
     if (f) atomicMax(ctl + 1, in.n - i);
 }
 
-#define HD_TRY(call)                                                       \
-    do {                                                                   \
-        const hipError_t e_ = (call);                                      \
-        if (e_ != hipSuccess) {                                            \
-            err = std::string("header_chain: " #call ": ") + hipGetErrorString(e_); \
-            return PHANT_E_DEVICE;                                         \
-        }                                                                  \
-    } while (0)
-
 // what the host form refuses before anything is copied
 inline int32_t check_host(const In& in, std::string& err) {
     const uint32_t nulls = null_mask(in);
@@ -386,7 +377,7 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
     const uint32_t n = hin.n, nulls = null_mask(hin);
     const bool small = n < SMALL_MAX;  // (n + 1 offsets, eight a lane)
     const uint32_t grid = blocks_of((uint64_t)n, 256);
-    HD_TRY(ws.ensure_mailbox());
+    CALL_TRY("header_chain", ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_HEADERS_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_HEADERS;
 
@@ -403,10 +394,10 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
         // arena is sized from what this launch reports)
         auto carve_ctl = [&](auto& t1) { d_ctl = t1.template take<uint32_t>(CTL_WORDS); };
         if (const int32_t rc = lay_out_status(lay_out_arena(ws.t1, st, carve_ctl), "header_chain_dev", "workspace", err)) return rc;
-        HD_TRY(hipMemsetAsync(d_ctl, 0, 4 * CTL_WORDS, st));
+        CALL_TRY("header_chain", hipMemsetAsync(d_ctl, 0, 4 * CTL_WORDS, st));
         hipLaunchKernelGGL(hdr_check_args_kernel, dim3(grid), dim3(256), 0, st, hin, nulls, d_ctl);
-        HD_TRY(hipGetLastError());
-        HD_TRY(ws.read_words(Workspaces::MAILBOX_HEADERS, d_ctl, CTL_WORDS, st));
+        CALL_TRY("header_chain", hipGetLastError());
+        CALL_TRY("header_chain", ws.read_words(Workspaces::MAILBOX_HEADERS, d_ctl, CTL_WORDS, st));
         if (mb[0] & F_INVALID)
             return err = "header_chain_dev: an n_fields outside 15, 16, 17, 19, 20, 21, a NULL array that a header needs, extra_off not running up from 0, "
                          "or seg_first not increasing from 0 to n",
@@ -452,29 +443,29 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
         ins.put(d.extra_data, hin.extra_data, (size_t)extra_bytes);
         ins.put(d.extra_off, hin.extra_off, 4 * ((size_t)n + 1));
         ins.put(d.seg_first, hin.seg_first, 4 * ((size_t)hin.n_segs + 1));
-        HD_TRY(ins.finish());
-        HD_TRY(hipMemsetAsync(d_ctl, 0, 4 * CTL_WORDS, st));
+        CALL_TRY("header_chain", ins.finish());
+        CALL_TRY("header_chain", hipMemsetAsync(d_ctl, 0, 4 * CTL_WORDS, st));
     }
 
     // ---- lengths and offsets, encodings, digests, checks
     if (small) hipLaunchKernelGGL(hdr_plan_small_kernel, dim3(1), dim3(256), 0, st, d, d_enc_off);
     else {
         hipLaunchKernelGGL(hdr_size_kernel, dim3(grid), dim3(256), 0, st, d, d_len);
-        HD_TRY(hipMemsetAsync(d_len + n, 0, 4, st));
-        HD_TRY(launch_exclusive_scan_u32(d_len, n + 1u, d_scan, st));
+        CALL_TRY("header_chain", hipMemsetAsync(d_len + n, 0, 4, st));
+        CALL_TRY("header_chain", launch_exclusive_scan_u32(d_len, n + 1u, d_scan, st));
     }
     const uint32_t waves = 4u * std::min(blocks_of(n, 4), 4096u);
     hipLaunchKernelGGL(hdr_encode_kernel, dim3(waves / 4u), dim3(256), 0, st, d, small ? nullptr : d_len, d_enc_off, d_enc, enc_bound, waves);
-    HD_TRY(hipGetLastError());
-    HD_TRY(launch_keccak256_var(d_enc, d_enc_off, n, d_hashes, st));
+    CALL_TRY("header_chain", hipGetLastError());
+    CALL_TRY("header_chain", launch_keccak256_var(d_enc, d_enc_off, n, d_hashes, st));
     hipLaunchKernelGGL(hdr_check_kernel, dim3(grid), dim3(256), 0, st, d, d_hashes, d_enc_off, d_flags, d_ctl);
-    HD_TRY(hipGetLastError());
+    CALL_TRY("header_chain", hipGetLastError());
 
     // ---- out: the control words, digests, flags and offsets lie next to each other (one span in the host form while it fits the pinned
     // stage); the control words first, since only they tell the encodings' size, which follow by a copy of their own when wanted
     CallOutputs outs(ws, st, dev, d_ctl, d_ctl, Workspaces::MAILBOX_HEADERS, CTL_WORDS);
     outs.cover(d_enc_off + n + 1);
-    HD_TRY(outs.deliver());
+    CALL_TRY("header_chain", outs.deliver());
     const uint32_t bad_from_end = outs.ctl()[1];
     const uint64_t total = (uint64_t)outs.ctl()[2] | ((uint64_t)outs.ctl()[3] << 32);
     const bool fits = !out.enc || total <= out.enc_cap;  // (a buffer nobody wants has no capacity to exceed)
@@ -484,13 +475,12 @@ int32_t header_chain(Workspaces& ws, hipStream_t st, const phant_headers_in& hin
         outs.add(out.enc_off, d_enc_off, 8 * ((size_t)n + 1));
         outs.add(out.enc, d_enc, (size_t)total);
     }
-    HD_TRY(outs.deliver());
+    CALL_TRY("header_chain", outs.deliver());
     out.first_bad = n - bad_from_end;
     out.enc_len = total;
     return PHANT_OK;
 }
 
-#undef HD_TRY
 #undef HD_HD
 #undef HD_ARRAYS
 

@@ -263,6 +263,12 @@ hipError_t launch_order_digests(const uint8_t* d_digests, const uint32_t* d_seg_
 size_t sort_hist_entries(uint32_t n);
 hipError_t launch_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt, uint32_t n, uint32_t bits, uint32_t* hist,
                              uint32_t* digit_totals, uint64_t** keys_out, uint32_t** vals_out, hipStream_t st);
+// `bits` for keys that are pre-state rows: they run from 0 to n_accounts (n_accounts: no row)
+inline uint32_t sort_key_bits(uint32_t n_accounts) {
+    uint32_t bits = 1;
+    while (bits < 32u && (n_accounts >> bits)) ++bits;
+    return bits;
+}
 
 // exclusive prefix sum of d[0 .. n) in place; d 16-byte aligned, scratch = scan_scratch_entries(n) counters of device memory
 size_t scan_scratch_entries(uint32_t n);

@@ -375,15 +375,6 @@ __global__ void __launch_bounds__(256) rc_gather_kernel(const uint8_t* __restric
 }
 
 
-#define RC_TRY(call)                                                        \
-    do {                                                                    \
-        const hipError_t e_ = (call);                                       \
-        if (e_ != hipSuccess) {                                             \
-            err = std::string("block_receipts: " #call ": ") + hipGetErrorString(e_); \
-            return PHANT_E_DEVICE;                                          \
-        }                                                                   \
-    } while (0)
-
 // what the host form refuses before anything is copied; *total = the bytes of all receipts
 inline int32_t check_host(const In& in, uint64_t* total, std::string& err) {
     const uint32_t n = in.n, nl = in.n_logs;
@@ -499,7 +490,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
     d_block = d_rows + 64 * (size_t)n;
     d_ctl = d_block + 64;
     d_len = d_ctl + 2 * CTL_WORDS;
-    RC_TRY(ws.ensure_mailbox());
+    CALL_TRY("block_receipts", ws.ensure_mailbox());
     static_assert(2 * CTL_WORDS <= Workspaces::MAILBOX_RECEIPTS_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_RECEIPTS;  // (behind everything the trie builder writes)
 
@@ -524,12 +515,12 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
             ins.put(d_loff[l], rel[l].data(), 8 * rel[l].size());
         }
         ins.put(d_meta, meta.data(), 4 * meta.size());
-        RC_TRY(ins.finish());
-        if (!ins.staged) RC_TRY(hipStreamSynchronize(st));  // (the copies read `rel`, which goes at the end of this block)
+        CALL_TRY("block_receipts", ins.finish());
+        if (!ins.staged) CALL_TRY("block_receipts", hipStreamSynchronize(st));  // (the copies read `rel`, which goes at the end of this block)
     } else {
-        RC_TRY(hipMemcpyAsync(d_meta, meta.data(), 4 * meta.size(), hipMemcpyHostToDevice, st));
+        CALL_TRY("block_receipts", hipMemcpyAsync(d_meta, meta.data(), 4 * meta.size(), hipMemcpyHostToDevice, st));
     }
-    RC_TRY(hipMemsetAsync(d_zero, 0, zero_bytes, st));
+    CALL_TRY("block_receipts", hipMemsetAsync(d_zero, 0, zero_bytes, st));
 
     // a small block: one workgroup sizes, scans and keys (the device form still checks its lists first, a launch each)
     const bool small = total < SMALL_PLAN_MAX && a.n_lists <= SMALL_PLAN_LISTS;
@@ -543,7 +534,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
                                d_len + meta[t], d_ctl);
     }
     if (dev) {
-        RC_TRY(read_ctl());
+        CALL_TRY("block_receipts", read_ctl());
         if (mb[0] & F_INVALID)
             return err = "block_receipts_dev: status > 1, tx_type > 0x7f, or offsets that are not monotone or do not span the stated totals", PHANT_E_INVALID_ARG;
     }
@@ -557,7 +548,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
         hipLaunchKernelGGL(rc_size_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, d, d_len + base_r, d_log_rel, d_logs_payload, d_ctl);
     }
     if (dev) {
-        RC_TRY(read_ctl());
+        CALL_TRY("block_receipts", read_ctl());
         if (mb[0] & F_INVALID) return err = "block_receipts_dev: a list's item offsets are not monotone", PHANT_E_INVALID_ARG;
         if (mb[0] & F_UNSUPPORTED) return err = "block_receipts_dev: a receipt or an item exceeds 2^32 - 1 bytes", PHANT_E_UNSUPPORTED;
         rbytes = (uint64_t)mb[2] | ((uint64_t)mb[3] << 32);
@@ -567,7 +558,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
 
     // ---- offsets, keys, values
     if (total && !small) {
-        RC_TRY(launch_exclusive_scan_u32(d_len, total + 1u, d_scan, st));
+        CALL_TRY("block_receipts", launch_exclusive_scan_u32(d_len, total + 1u, d_scan, st));
         hipLaunchKernelGGL(rc_keys_kernel, dim3(blocks_of((uint64_t)total + 1, 256)), dim3(256), 0, st, d_len, d_meta, n_tries, total, (uint32_t)key_total,
                            d_val_off, d_key_off, d_keys);
     }
@@ -582,7 +573,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
             hipLaunchKernelGGL(rc_scatter_kernel, dim3(blocks_of(a.list_n[l], 4)), dim3(256), 0, st, d_list[l], d_loff[l], a.list_n[l], d_val_off + meta[t],
                                d_vals, val_cap);
     }
-    RC_TRY(hipGetLastError());
+    CALL_TRY("block_receipts", hipGetLastError());
 
     // ---- the tries
     const bool want_roots = a.receipts_root || a.roots_out;
@@ -598,8 +589,8 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
         uint8_t* const o = dev ? a.encoded : (a.encoded ? d_enc : nullptr);
         uint64_t* const oo = dev ? a.encoded_off : (a.encoded_off ? d_enc_off : nullptr);
         if (n) hipLaunchKernelGGL(rc_gather_kernel, dim3(blocks_of(n, 4)), dim3(256), 0, st, d_vals, d_val_off + base_r, n, o, oo);
-        else if (oo) RC_TRY(hipMemsetAsync(oo, 0, 8, st));
-        RC_TRY(hipGetLastError());
+        else if (oo) CALL_TRY("block_receipts", hipMemsetAsync(oo, 0, 8, st));
+        CALL_TRY("block_receipts", hipGetLastError());
     }
     // roots, rows and the block's bloom (inside d_zero) and the host form's encodings lie next to each other: one span in the host form
     // while it fits the pinned stage.  No control words go back: the device form has read them above, the host form needs none.
@@ -613,11 +604,10 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
         outs.add(a.encoded, d_enc, (size_t)rbytes);
         outs.add(a.encoded_off, d_enc_off, 8 * ((size_t)n + 1));
     }
-    RC_TRY(outs.deliver());
+    CALL_TRY("block_receipts", outs.deliver());
     return PHANT_OK;
 }
 
-#undef RC_TRY
 #undef RC_HD
 
 }  // namespace phant

@@ -20,13 +20,17 @@
 //                          last event writes that row's account outputs; the lanes beyond the events write the untouched rows
 // No lane runs a loop over the events of an account: ten thousand credits to one coinbase cost what ten thousand to distinct rows cost.
 //
-// With PHANT_SETTLE_RULE_ONLY (and PHANT_TXST_RULE_ONLY) defined only the per-row functions and the 320-bit arithmetic are declared,
-// without any HIP header: tests/native/settle_main.cpp builds them as a program of its own.
+// The 320-bit arithmetic is wide_uint.h's, the scan seg_scan.hip.h's (L = 10), the wave's vote on a row keyed_table.hip.h's.
+//
+// With PHANT_SETTLE_RULE_ONLY (and PHANT_TXST_RULE_ONLY) defined only the per-row functions are declared, without any HIP header:
+// tests/native/settle_main.cpp builds them and wide_uint.h as a program of its own.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/phant_gpu.h"
-#include "txstate.hip.h"  // txst::load_be256, store_be256, is_empty_code_hash, proven; wave_first_of
+#include "keyed_table.hip.h"
+#include "txstate.hip.h"  // txst::is_empty_code_hash, proven; the PHANT_TXST_* flag rules
+#include "wide_uint.h"
 
 #ifdef PHANT_SETTLE_RULE_ONLY
 #define SETTLE_HD inline
@@ -36,6 +40,7 @@
 #include <string>
 
 #include "launch.h"
+#include "seg_scan.hip.h"
 #include "settle.h"
 #include "staging.h"
 #define SETTLE_HD __host__ __device__ inline
@@ -44,35 +49,15 @@
 namespace phant {
 namespace settle {
 
-// ---- 320-bit two's-complement integers, ten little-endian limbs: 2^32 events of magnitude below 2^256 and a balance sum exactly
+// ---- 320-bit two's-complement integers, ten little-endian limbs (wide_uint.h): 2^32 events of magnitude below 2^256 and a balance sum
+// exactly
 enum : uint32_t { LIMBS = 10 };
-SETTLE_HD void add320(uint32_t a[LIMBS], const uint32_t b[LIMBS]) {
-    uint64_t c = 0;
-    for (int k = 0; k < (int)LIMBS; ++k) {
-        c += (uint64_t)a[k] + b[k];
-        a[k] = (uint32_t)c, c >>= 32;
-    }
-}
-SETTLE_HD void sub320(uint32_t a[LIMBS], const uint32_t b[LIMBS]) {
-    uint64_t borrow = 0;
-    for (int k = 0; k < (int)LIMBS; ++k) {
-        const uint64_t t = (uint64_t)a[k] - b[k] - borrow;
-        a[k] = (uint32_t)t, borrow = (t >> 32) & 1u;
-    }
-}
-SETTLE_HD void neg320(uint32_t a[LIMBS]) {
-    uint64_t c = 1;
-    for (int k = 0; k < (int)LIMBS; ++k) {
-        c += (uint64_t)(~a[k]);
-        a[k] = (uint32_t)c, c >>= 32;
-    }
-}
+SETTLE_HD void add320(uint32_t a[LIMBS], const uint32_t b[LIMBS]) { wide::add<LIMBS>(a, b); }
+SETTLE_HD void sub320(uint32_t a[LIMBS], const uint32_t b[LIMBS]) { wide::sub<LIMBS>(a, b); }
+SETTLE_HD void neg320(uint32_t a[LIMBS]) { wide::neg<LIMBS>(a); }
 SETTLE_HD bool negative(const uint32_t a[LIMBS]) { return (a[LIMBS - 1] >> 31) != 0u; }
 // 32 bytes big-endian -> ten limbs
-SETTLE_HD void load256(const uint8_t* row, uint32_t w[LIMBS]) {
-    txst::load_be256(row, w);  // (w[8] = 0)
-    w[9] = 0u;
-}
+SETTLE_HD void load256(const uint8_t* row, uint32_t w[LIMBS]) { wide::load_be256<LIMBS>(row, w); }
 // g x p, p < 2^256
 SETTLE_HD void mul_u64_u256(uint64_t g, const uint32_t p[8], uint32_t out[LIMBS]) {
     const uint32_t g0 = (uint32_t)g, g1 = (uint32_t)(g >> 32);
@@ -96,12 +81,7 @@ SETTLE_HD uint32_t clamp256(const uint32_t a[LIMBS], uint32_t out[8]) {
     return neg ? PHANT_SETTLE_ACCT_NEGATIVE : over ? PHANT_SETTLE_ACCT_OVERFLOW : 0u;
 }
 // a < c, for 0 <= c < 2^256 (its limbs 8 and 9 are zero)
-SETTLE_HD bool below(const uint32_t a[LIMBS], const uint32_t c[LIMBS]) {
-    if (negative(a)) return true;
-    for (int k = (int)LIMBS - 1; k >= 0; --k)
-        if (a[k] != c[k]) return a[k] < c[k];
-    return false;
-}
+SETTLE_HD bool below(const uint32_t a[LIMBS], const uint32_t c[LIMBS]) { return negative(a) || wide::less<LIMBS>(a, c); }
 SETTLE_HD bool less_be256(const uint8_t* a, const uint8_t* b) {
     uint32_t x[LIMBS], y[LIMBS];
     load256(a, x);
@@ -173,15 +153,8 @@ SETTLE_HD uint32_t row_rule(uint64_t gas, uint64_t gas_limit, uint64_t block_gas
     // cum_before + gas_limit against block_gas_limit, in 128 bits
     uint32_t s[4] = {cum[0], cum[1], cum[2], 0u};
     const uint32_t sub[4] = {(uint32_t)gas, (uint32_t)(gas >> 32), 0u, 0u}, add[4] = {(uint32_t)gas_limit, (uint32_t)(gas_limit >> 32), 0u, 0u};
-    uint64_t borrow = 0, c = 0;
-    for (int k = 0; k < 4; ++k) {
-        const uint64_t t = (uint64_t)s[k] - sub[k] - borrow;
-        s[k] = (uint32_t)t, borrow = (t >> 32) & 1u;
-    }
-    for (int k = 0; k < 4; ++k) {
-        c += (uint64_t)s[k] + add[k];
-        s[k] = (uint32_t)c, c >>= 32;
-    }
+    wide::sub<4>(s, sub);
+    wide::add<4>(s, add);
     if ((s[2] | s[3]) != 0u || ((uint64_t)s[1] << 32 | s[0]) > block_gas_limit) f |= PHANT_SETTLE_GAS_LIMIT;
     cum_out = cum[2] ? ~0ull : (uint64_t)cum[1] << 32 | cum[0];
     uint32_t cost[LIMBS];
@@ -207,7 +180,8 @@ SETTLE_HD uint32_t account_rule(uint8_t status, uint64_t nonce, uint32_t sends, 
 // ctl[0]: what the rows' check found, [1]: max(n - i) over the rows with an error bit, [2]: rows that are not plain, [3]: max(n - i)
 // over those, [4]: block_flags, [5]: withdrawals dropped, [6 .. 7]: the block's gas_used
 enum : uint32_t { CTL_WORDS = 8 };
-enum : uint32_t { NONE = PHANT_ROW_NONE, SEG_WORDS = 12, TILE = 256 };
+enum : uint32_t { NONE = PHANT_ROW_NONE, SEG_WORDS = seg::SEG_WORDS, TILE = seg::TILE };
+using Seg = seg::Seg<LIMBS>;  // {signed sum, sender events, "a segment starts at or before me in what was combined"}
 
 // the call's device arrays
 struct Args {
@@ -241,7 +215,7 @@ __global__ void __launch_bounds__(256) settle_check_kernel(Args a) {
 }
 
 __device__ inline void touch(const Args& a, uint32_t row) {
-    if (txst::wave_first_of(row != NONE, row)) atomicOr(a.touched + (row >> 5), 1u << (row & 31u));
+    if (keyed::wave_first_of(row != NONE, row)) atomicOr(a.touched + (row >> 5), 1u << (row & 31u));
 }
 
 __global__ void __launch_bounds__(256) settle_classify_kernel(Args a) {
@@ -299,70 +273,12 @@ __device__ inline void event_of(const Args& a, uint32_t e, uint32_t w[LIMBS]) {
 }
 __device__ inline bool is_sender_event(const Args& a, uint32_t e) { return e < 3u * a.in.n && e % 3u == 0u; }
 
-// ---- the segmented scan.  An element: {signed sum, sender events, "a segment starts at or before me in what was combined"}
-struct Seg {
-    uint32_t w[LIMBS], cnt, f;
-};
-__device__ __forceinline__ void seg_zero(Seg& s) {
-#pragma unroll
-    for (int k = 0; k < (int)LIMBS; ++k) s.w[k] = 0u;
-    s.cnt = 0u, s.f = 0u;
-}
-// s = before (+) s
-__device__ __forceinline__ void seg_combine(Seg& s, const Seg& before) {
-    if (!s.f) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int k = 0; k < (int)LIMBS; ++k) {
-            c += (uint64_t)s.w[k] + before.w[k];
-            s.w[k] = (uint32_t)c, c >>= 32;
-        }
-        s.cnt += before.cnt;
-    }
-    s.f |= before.f;
-}
-__device__ __forceinline__ void seg_load(const uint32_t* p, Seg& s) {
-    const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1], c = reinterpret_cast<const uint4*>(p)[2];
-    s.w[0] = a.x, s.w[1] = a.y, s.w[2] = a.z, s.w[3] = a.w, s.w[4] = b.x, s.w[5] = b.y, s.w[6] = b.z, s.w[7] = b.w, s.w[8] = c.x, s.w[9] = c.y;
-    s.cnt = c.z, s.f = c.w;
-}
-__device__ __forceinline__ void seg_store(uint32_t* p, const Seg& s) {
-    reinterpret_cast<uint4*>(p)[0] = make_uint4(s.w[0], s.w[1], s.w[2], s.w[3]);
-    reinterpret_cast<uint4*>(p)[1] = make_uint4(s.w[4], s.w[5], s.w[6], s.w[7]);
-    reinterpret_cast<uint4*>(p)[2] = make_uint4(s.w[8], s.w[9], s.cnt, s.f);
-}
-// inclusive over the 256 lanes of a workgroup: the wave by shuffles (six steps), the waves in front through LDS.  Every lane calls it.
-__device__ __forceinline__ void seg_scan_block(Seg& s, uint32_t tid, Seg* s_wave /* [4] */) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        Seg o;
-#pragma unroll
-        for (int k = 0; k < (int)LIMBS; ++k) o.w[k] = (uint32_t)__shfl_up((int)s.w[k], d);
-        o.cnt = (uint32_t)__shfl_up((int)s.cnt, d);
-        o.f = (uint32_t)__shfl_up((int)s.f, d);
-        if (lane >= d) seg_combine(s, o);
-    }
-    if (lane == 63u) s_wave[wave] = s;
-    __syncthreads();
-    Seg run;
-    seg_zero(run);
-#pragma unroll
-    for (uint32_t w = 0; w < 3u; ++w)
-        if (w < wave) {
-            Seg t = s_wave[w];
-            seg_combine(t, run);
-            run = t;
-        }
-    seg_combine(s, run);
-}
-
 // workgroups [0, ev_tiles): the sorted events; [ev_tiles, ev_tiles + gas_tiles): gas_used in block order (f stays 0: one plain sum)
 __global__ void __launch_bounds__(256) settle_scan_tiles_kernel(Args a, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals) {
     __shared__ Seg s_wave[4];
     const uint32_t tid = threadIdx.x;
     Seg s;
-    seg_zero(s);
+    seg::zero(s);
     if (blockIdx.x < a.ev_tiles) {
         const uint32_t p = blockIdx.x * TILE + tid;
         if (p < a.events) {
@@ -381,41 +297,16 @@ __global__ void __launch_bounds__(256) settle_scan_tiles_kernel(Args a, const ui
             s.w[0] = (uint32_t)g, s.w[1] = (uint32_t)(g >> 32);
         }
     }
-    seg_scan_block(s, tid, s_wave);
-    seg_store(a.loc + (size_t)SEG_WORDS * ((size_t)blockIdx.x * TILE + tid), s);
-    if (tid == TILE - 1u) seg_store(a.agg + (size_t)SEG_WORDS * blockIdx.x, s);
+    seg::scan_block(s, tid, s_wave);
+    seg::store(a.loc + (size_t)SEG_WORDS * ((size_t)blockIdx.x * TILE + tid), s);
+    if (tid == TILE - 1u) seg::store(a.agg + (size_t)SEG_WORDS * blockIdx.x, s);
 }
 
-// tp[t] = what runs into tile t: the tiles of its kind before it combined, 256 of them at a time.  Workgroup 0: the events' tiles, 1: the gas's
+// tp[t] = what runs into tile t: the tiles of its kind before it combined.  Workgroup 0: the events' tiles, 1: the gas's
 __global__ void __launch_bounds__(256) settle_scan_aggr_kernel(Args a) {
     __shared__ Seg s_wave[4];
     __shared__ Seg s_carry;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t first = blockIdx.x ? a.ev_tiles : 0u, tiles = blockIdx.x ? a.gas_tiles : a.ev_tiles;
-    Seg carry;
-    seg_zero(carry);
-    if (tid == 0u && tiles) seg_store(a.tp + (size_t)SEG_WORDS * first, carry);
-    for (uint32_t c0 = 0; c0 < tiles; c0 += 256u) {
-        const uint32_t t = c0 + tid;
-        Seg s;
-        seg_zero(s);
-        if (t < tiles) seg_load(a.agg + (size_t)SEG_WORDS * (first + t), s);
-        seg_scan_block(s, tid, s_wave);
-        seg_combine(s, carry);
-        if (t + 1u < tiles) seg_store(a.tp + (size_t)SEG_WORDS * (first + t + 1u), s);
-        if (tid == 255u) s_carry = s;
-        __syncthreads();
-        carry = s_carry;
-        __syncthreads();  // (s_wave and s_carry are written again by the next chunk)
-    }
-}
-
-// the scan up to and including slot q (an event's place in the sorted order, or ev_tiles x TILE + i for the gas of row i)
-__device__ inline void scan_at(const Args& a, size_t q, Seg& here) {
-    Seg into;
-    seg_load(a.loc + (size_t)SEG_WORDS * q, here);
-    seg_load(a.tp + (size_t)SEG_WORDS * (q / TILE), into);
-    seg_combine(here, into);
+    seg::aggregate(a.agg, a.tp, blockIdx.x ? a.ev_tiles : 0u, blockIdx.x ? a.gas_tiles : a.ev_tiles, threadIdx.x, s_wave, &s_carry);
 }
 
 // transaction i, whose sender event stands at sorted slot p with the scan `here` (exists: the row is plain)
@@ -424,8 +315,8 @@ __device__ inline void finish_row(const Args& a, uint32_t i, bool exists, const 
     uint32_t f = a.o.settle_flags[i];  // (the class, from the classify kernel)
     uint64_t cum_out = 0;
     uint32_t bal[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    Seg gas;
-    scan_at(a, (size_t)a.ev_tiles * TILE + i, gas);
+    Seg gas;  // (the gas of row i stands at slot ev_tiles x TILE + i)
+    seg::scan_at(a.loc, a.tp, (size_t)a.ev_tiles * TILE + i, gas);
     if (exists) {
         const uint32_t s = in.sender_row[i];
         uint32_t before[LIMBS], own[LIMBS];
@@ -438,7 +329,7 @@ __device__ inline void finish_row(const Args& a, uint32_t i, bool exists, const 
     }
     a.o.settle_flags[i] = f;
     a.o.cumulative_gas_used[i] = cum_out;
-    txst::store_be256(a.o.balance_before + 32ull * i, bal);
+    wide::store_be256(a.o.balance_before + 32ull * i, bal);
     if (f & PHANT_SETTLE_ERROR_BITS) atomicMax(a.ctl + 1, in.n - i);
     if (i + 1u == in.n) a.ctl[6] = gas.w[2] ? 0xffffffffu : gas.w[0], a.ctl[7] = gas.w[2] ? 0xffffffffu : gas.w[1];
 }
@@ -456,8 +347,8 @@ __global__ void __launch_bounds__(256) settle_finish_kernel(Args a, const uint64
         const uint64_t key = keys[p];
         const bool exists = key != in.n_accounts;
         Seg here;
-        seg_zero(here);
-        if (exists) scan_at(a, p, here);
+        seg::zero(here);
+        if (exists) seg::scan_at(a.loc, a.tp, p, here);
         if (is_sender_event(a, e)) finish_row(a, e / 3u, exists, here);
         if (exists && (p + 1u == a.events || keys[p + 1u] != key)) {  // the last event of row j's segment
             const uint32_t j = (uint32_t)key;
@@ -469,7 +360,7 @@ __global__ void __launch_bounds__(256) settle_finish_kernel(Args a, const uint64
                                              nonce_after, bal, flags);
             a.o.account_op[j] = (uint8_t)op;
             a.o.nonces_after[j] = nonce_after;
-            txst::store_be256(a.o.balances_after + 32ull * j, bal);
+            wide::store_be256(a.o.balances_after + 32ull * j, bal);
             a.o.account_flags[j] = (uint8_t)flags;
         }
     } else if (g - a.events < in.n_accounts) {
@@ -483,15 +374,6 @@ __global__ void __launch_bounds__(256) settle_finish_kernel(Args a, const uint64
         }
     }
 }
-
-#define SETTLE_TRY(call)                                                      \
-    do {                                                                      \
-        const hipError_t e_ = (call);                                         \
-        if (e_ != hipSuccess) {                                               \
-            err = std::string("block_settle: " #call ": ") + hipGetErrorString(e_); \
-            return PHANT_E_DEVICE;                                            \
-        }                                                                     \
-    } while (0)
 
 // the arrays that cross the bus in the host form: (member, type, elements)
 #define SETTLE_INPUTS(X)                                                                                                                        \
@@ -521,7 +403,7 @@ int32_t block_settle(Workspaces& ws, hipStream_t st, const phant_settle_in& in, 
     using namespace settle;
     const uint32_t n = in.n, na = in.n_accounts, nw = in.n_wd;
     const uint32_t events = 3u * n + nw;  // (below 2^31: checked by the caller)
-    SETTLE_TRY(ws.ensure_mailbox());
+    CALL_TRY("block_settle", ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_SETTLE_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_SETTLE;
     if (!dev)
@@ -563,7 +445,7 @@ int32_t block_settle(Workspaces& ws, hipStream_t st, const phant_settle_in& in, 
     if (!in.floor_gas) a.in.floor_gas = nullptr;
     a.ctl = zero, digit_totals = zero + CTL_WORDS;
     a.touched = digit_totals + 512;
-    SETTLE_TRY(hipMemsetAsync(zero, 0, 4 * zero_words, st));
+    CALL_TRY("block_settle", hipMemsetAsync(zero, 0, 4 * zero_words, st));
 
     // ---- in: (host form) every array in ONE copy through the pinned stage where they fit it; (device form) the check
     if (!dev) {
@@ -571,11 +453,11 @@ int32_t block_settle(Workspaces& ws, hipStream_t st, const phant_settle_in& in, 
 #define X(m, T, e) ins.put(a.in.m, in.m, (size_t)(e) * sizeof(T));
         SETTLE_INPUTS(X)
 #undef X
-        SETTLE_TRY(ins.finish());
+        CALL_TRY("block_settle", ins.finish());
     } else if (std::max(n, nw)) {
         hipLaunchKernelGGL(settle_check_kernel, dim3((std::max(n, nw) + 255u) / 256u), dim3(256), 0, st, a);
-        SETTLE_TRY(hipGetLastError());
-        SETTLE_TRY(ws.read_words(Workspaces::MAILBOX_SETTLE, a.ctl, CTL_WORDS, st));
+        CALL_TRY("block_settle", hipGetLastError());
+        CALL_TRY("block_settle", ws.read_words(Workspaces::MAILBOX_SETTLE, a.ctl, CTL_WORDS, st));
         if (mb[0]) return err = "block_settle_dev: a sender_row / to_row / wd_row is neither a pre-state row nor the NONE value", PHANT_E_INVALID_ARG;
     }
 
@@ -584,21 +466,19 @@ int32_t block_settle(Workspaces& ws, hipStream_t st, const phant_settle_in& in, 
     const uint32_t* vals = a.vals;
     if (events) {
         hipLaunchKernelGGL(settle_classify_kernel, dim3((n + nw + 255u) / 256u), dim3(256), 0, st, a);
-        SETTLE_TRY(hipGetLastError());
-        uint32_t bits = 1;  // (the keys run from 0 to n_accounts)
-        while (bits < 32u && (na >> bits)) ++bits;
+        CALL_TRY("block_settle", hipGetLastError());
         uint64_t* k_out = nullptr;
         uint32_t* v_out = nullptr;
-        SETTLE_TRY(launch_sort_pairs(a.keys, a.vals, keys_alt, vals_alt, events, bits, hist, digit_totals, &k_out, &v_out, st));
+        CALL_TRY("block_settle", launch_sort_pairs(a.keys, a.vals, keys_alt, vals_alt, events, sort_key_bits(na), hist, digit_totals, &k_out, &v_out, st));
         keys = k_out, vals = v_out;
         hipLaunchKernelGGL(settle_scan_tiles_kernel, dim3(tiles), dim3(256), 0, st, a, keys, vals);
-        SETTLE_TRY(hipGetLastError());
+        CALL_TRY("block_settle", hipGetLastError());
         hipLaunchKernelGGL(settle_scan_aggr_kernel, dim3(2), dim3(256), 0, st, a);
-        SETTLE_TRY(hipGetLastError());
+        CALL_TRY("block_settle", hipGetLastError());
     }
     if ((uint64_t)events + na) {
         hipLaunchKernelGGL(settle_finish_kernel, dim3((uint32_t)(((uint64_t)events + na + 255u) / 256u)), dim3(256), 0, st, a, keys, vals);
-        SETTLE_TRY(hipGetLastError());
+        CALL_TRY("block_settle", hipGetLastError());
     }
 
     // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage)
@@ -606,14 +486,13 @@ int32_t block_settle(Workspaces& ws, hipStream_t st, const phant_settle_in& in, 
 #define X(m, T, e) outs.add(out.m, a.o.m, (size_t)(e) * sizeof(T));
     SETTLE_OUTPUTS(X)
 #undef X
-    SETTLE_TRY(outs.deliver());
+    CALL_TRY("block_settle", outs.deliver());
     const volatile uint32_t* const c = outs.ctl();
     out.first_bad = n - c[1], out.n_not_plain = c[2], out.first_not_plain = n - c[3], out.block_flags = c[4], out.n_wd_unknown = c[5];
     out.gas_used = (uint64_t)c[7] << 32 | c[6];
     return PHANT_OK;
 }
 
-#undef SETTLE_TRY
 #undef SETTLE_INPUTS
 #undef SETTLE_OUTPUTS
 

@@ -6,6 +6,7 @@
 //   StagedInputs  the host form's arrays on their way in: ONE copy through the pinned stage, or a copy each
 //   stage_pairs   a forest's sorted pairs in host memory: validated, laid out, rebased and sent in through StagedInputs
 //   CallOutputs   every output named once; deliver() hands them back as the call's form asks
+//   CALL_TRY      a HIP call of a block-level driver: its failure is the driver's PHANT_E_DEVICE with the call's text in err
 //
 // The pinned stage mirrors the first STAGE_BYTES of `io`.  It is used when the bytes in question END within it and the arena does not
 // poison its padding (a copy of a span crosses the padding between sub-allocations; a sanitizer build therefore copies array by array,
@@ -19,6 +20,16 @@
 #include "../../include/phant_gpu.h"
 #include "arena.h"
 #include "trie_build.h"
+
+// a HIP call inside the driver `name`, which has `std::string& err` and returns a PHANT_E_* code: "<name>: <call text>: <hip error string>"
+#define CALL_TRY(name, call)                                                    \
+    do {                                                                        \
+        const hipError_t e_ = (call);                                           \
+        if (e_ != hipSuccess) {                                                 \
+            err = std::string(name ": " #call ": ") + hipGetErrorString(e_);    \
+            return PHANT_E_DEVICE;                                              \
+        }                                                                       \
+    } while (0)
 
 namespace phant {
 

@@ -742,15 +742,6 @@ __global__ void __launch_bounds__(64) tx_rules_kernel(uint32_t n, Rules ru, Dev 
     if (f & ERROR_BITS) atomicMax(dv.ctl + 1, n - i);
 }
 
-#define TX_TRY(call)                                                              \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) {                                                   \
-            err = std::string("block_transactions: " #call ": ") + hipGetErrorString(e_); \
-            return PHANT_E_DEVICE;                                                \
-        }                                                                         \
-    } while (0)
-
 // what the host form refuses before anything is copied
 inline int32_t check_host(const In& in, std::string& err) {
     if (in.tx_off[0] != 0u) return err = "block_transactions: tx_off does not run from 0", PHANT_E_INVALID_ARG;
@@ -770,7 +761,7 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
     phant_txs_out& out = xout.base;
     const uint32_t n = in.n, fork = xin.fork;
     const bool recover = !(in.flags & PHANT_TXS_NO_RECOVERY);
-    TX_TRY(ws.ensure_mailbox());
+    CALL_TRY("block_transactions", ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXS_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXS;
     uint64_t bytes = in.tx_bytes;
@@ -814,7 +805,7 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
         }
     };
     if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_transactions", "workspace", err)) return rc;
-    TX_TRY(hipMemsetAsync(d.ctl, 0, 4 * CTL_WORDS, st));
+    CALL_TRY("block_transactions", hipMemsetAsync(d.ctl, 0, 4 * CTL_WORDS, st));
 
     // ---- in: (host form) offsets and bytes in ONE copy through the pinned stage where they fit it; (device form) the offsets' check
     const uint32_t grid256 = (n + 255u) / 256u, grid64 = (n + 63u) / 64u;
@@ -822,11 +813,11 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
         StagedInputs ins(ws, st, d_off, d_txs + bytes);
         ins.put(d_off, in.tx_off, 8 * ((size_t)n + 1));
         ins.put(d_txs, in.txs, (size_t)bytes);
-        TX_TRY(ins.finish());
+        CALL_TRY("block_transactions", ins.finish());
     } else {
         hipLaunchKernelGGL(tx_check_args_kernel, dim3(grid256), dim3(256), 0, st, d_off, n, bytes, d.ctl);
-        TX_TRY(hipGetLastError());
-        TX_TRY(ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
+        CALL_TRY("block_transactions", hipGetLastError());
+        CALL_TRY("block_transactions", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
         if (mb[0] & F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
         if (mb[0] & F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
     }
@@ -840,15 +831,15 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
     ru.block_gas_limit = in.block_gas_limit;
     ru.fork = fork;
     hipLaunchKernelGGL(tx_decode_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, in.chain_id, fork, d);
-    TX_TRY(hipGetLastError());
+    CALL_TRY("block_transactions", hipGetLastError());
     hipLaunchKernelGGL(tx_hash_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, d.plan, d.o.tx_hash, d.o.sig_hash, d.o.intrinsic_gas);
-    TX_TRY(hipGetLastError());
+    CALL_TRY("block_transactions", hipGetLastError());
     const uint32_t low_s = PHANT_RECOVER_LOW_S;  // validateSignatureFields
     uint32_t n_auth = 0;
     AuthDev ad;
     std::memset(&ad, 0, sizeof ad);
     if (maybe_tuples) {
-        TX_TRY(ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
+        CALL_TRY("block_transactions", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
         n_auth = mb[2];
     }
     if (n_auth) {
@@ -864,17 +855,17 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
         };
         // (no synchronisation before the arena grows -- the stream is idle: the control words were just read)
         if (const int32_t rc = lay_out_status(lay_out_arena(ws.txa, st, carve_auth, true), "block_transactions", "authorizations", err)) return rc;
-        TX_TRY(launch_exclusive_scan_u32(d.x.auth_first, n + 1u, d_scan, st));
+        CALL_TRY("block_transactions", launch_exclusive_scan_u32(d.x.auth_first, n + 1u, d_scan, st));
         hipLaunchKernelGGL(tx_auth_rows_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, in.chain_id, d, ad, n_auth);
-        TX_TRY(hipGetLastError());
+        CALL_TRY("block_transactions", hipGetLastError());
         hipLaunchKernelGGL(tx_auth_hash_kernel, dim3((n_auth + 63u) / 64u), dim3(64), 0, st, ad, n_auth);
-        TX_TRY(hipGetLastError());
+        CALL_TRY("block_transactions", hipGetLastError());
         if (recover)
-            TX_TRY(launch_ecrecover(ad.x.auth_hash, ad.r, ad.s, ad.recid, ad.pre_status, n_auth, low_s, gtable, nullptr, ad.x.authority, ad.x.auth_status, st));
+            CALL_TRY("block_transactions", launch_ecrecover(ad.x.auth_hash, ad.r, ad.s, ad.recid, ad.pre_status, n_auth, low_s, gtable, nullptr, ad.x.authority, ad.x.auth_status, st));
     }
-    if (recover) TX_TRY(launch_ecrecover(d.o.sig_hash, d.r, d.s, d.recid, d.pre_status, n, low_s, gtable, nullptr, d.o.sender, d.o.sig_status, st));
+    if (recover) CALL_TRY("block_transactions", launch_ecrecover(d.o.sig_hash, d.r, d.s, d.recid, d.pre_status, n, low_s, gtable, nullptr, d.o.sender, d.o.sig_status, st));
     hipLaunchKernelGGL(tx_rules_kernel, dim3(grid64), dim3(64), 0, st, n, ru, d, recover ? d.o.sig_status : nullptr);
-    TX_TRY(hipGetLastError());
+    CALL_TRY("block_transactions", hipGetLastError());
 
     // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage);
     // the rows of the tuples (at most auth_cap of them), which lie in their own arena, by copies of their own in both forms
@@ -893,7 +884,7 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
 #define X(m, T, e) outs.add(xout.m, d.x.m, (size_t)n * e * sizeof(T));
     TX_EX_OUTPUTS(X)
 #undef X
-    TX_TRY(outs.deliver());
+    CALL_TRY("block_transactions", outs.deliver());
     const volatile uint32_t* const ctl = outs.ctl();
     out.first_bad = n - ctl[1];
     xout.n_auth = ctl[2];
@@ -901,7 +892,6 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
     return PHANT_OK;
 }
 
-#undef TX_TRY
 #undef TX_OUTPUTS
 #undef TX_EX_OUTPUTS
 #undef TX_AUTH_OUTPUTS

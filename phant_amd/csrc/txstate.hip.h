@@ -24,12 +24,16 @@
 // No lane runs a loop over the transactions of a sender: ten thousand transactions of one address cost what ten thousand of distinct
 // addresses cost.
 //
-// With PHANT_TXST_RULE_ONLY defined only the per-row rule and the 288-bit arithmetic are declared, without any HIP header:
-// tests/native/txstate_main.cpp builds them as a program of its own.
+// The 288-bit arithmetic is wide_uint.h's, the address table keyed_table.hip.h's, the scan seg_scan.hip.h's (L = 9).
+//
+// With PHANT_TXST_RULE_ONLY defined only the per-row rule is declared, without any HIP header: tests/native/txstate_main.cpp builds it
+// and wide_uint.h as a program of its own.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/phant_gpu.h"
+#include "keyed_table.hip.h"
+#include "wide_uint.h"
 
 #ifdef PHANT_TXST_RULE_ONLY
 #define TXST_HD inline
@@ -40,6 +44,7 @@
 #include <vector>
 
 #include "launch.h"
+#include "seg_scan.hip.h"
 #include "staging.h"
 #include "txstate.h"
 #define TXST_HD __host__ __device__ inline
@@ -48,41 +53,16 @@
 namespace phant {
 namespace txst {
 
-// ---- 288-bit unsigned integers, nine little-endian limbs: the sum of 2^32 costs of at most 2^256 each fits
-TXST_HD void add288(uint32_t a[9], const uint32_t b[9]) {
-    uint64_t c = 0;
-    for (int k = 0; k < 9; ++k) {
-        c += (uint64_t)a[k] + b[k];
-        a[k] = (uint32_t)c, c >>= 32;
-    }
-}
-// a -= b, for a >= b
-TXST_HD void sub288(uint32_t a[9], const uint32_t b[9]) {
-    uint64_t borrow = 0;
-    for (int k = 0; k < 9; ++k) {
-        const uint64_t t = (uint64_t)a[k] - b[k] - borrow;
-        a[k] = (uint32_t)t, borrow = (t >> 32) & 1u;
-    }
-}
-TXST_HD bool less288(const uint32_t a[9], const uint32_t b[9]) {
-    for (int k = 8; k >= 0; --k)
-        if (a[k] != b[k]) return a[k] < b[k];
-    return false;
-}
-// 32 bytes big-endian <-> limbs (w[8] = 0)
-TXST_HD void load_be256(const uint8_t* row, uint32_t w[9]) {
-    for (int k = 0; k < 8; ++k) {
-        const uint8_t* p = row + 28 - 4 * k;
-        w[k] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3];
-    }
-    w[8] = 0u;
-}
-TXST_HD void store_be256(uint8_t* row, const uint32_t w[8]) {
-    for (int k = 0; k < 8; ++k) {
-        uint8_t* p = row + 28 - 4 * k;
-        p[0] = (uint8_t)(w[k] >> 24), p[1] = (uint8_t)(w[k] >> 16), p[2] = (uint8_t)(w[k] >> 8), p[3] = (uint8_t)w[k];
-    }
-}
+// ---- sums are 288-bit unsigned integers, nine little-endian limbs: the sum of 2^32 costs of at most 2^256 each fits.  The rule code's
+// names for wide_uint.h at nine limbs, and for keyed_table.hip.h's address functions (tests/native/ calls them by these names)
+TXST_HD void add288(uint32_t a[9], const uint32_t b[9]) { wide::add<9>(a, b); }
+TXST_HD void sub288(uint32_t a[9], const uint32_t b[9]) { wide::sub<9>(a, b); }  // for a >= b
+TXST_HD bool less288(const uint32_t a[9], const uint32_t b[9]) { return wide::less<9>(a, b); }
+TXST_HD void load_be256(const uint8_t* row, uint32_t w[9]) { wide::load_be256<9>(row, w); }  // (w[8] = 0)
+using wide::store_be256;
+using keyed::home_slot;
+using keyed::load_addr;
+using keyed::same_addr;
 // what a row adds to its sender's sequence: upfront_cost, or 2^256 for a row the transactions call marked PHANT_TX_COST_OVERFLOW
 TXST_HD void cost_of(const uint8_t* row, uint32_t tx_flags, uint32_t w[9]) {
     if (tx_flags & PHANT_TX_COST_OVERFLOW) {
@@ -142,33 +122,12 @@ TXST_HD void sender_rule(const RowIn& r, RowOut& o) {
     if (less288(r.balance, r.incl)) o.flags |= PHANT_TXST_NEEDS_INFLOW | (r.i == 0u ? PHANT_TXST_BALANCE_SHORT : 0u);
 }
 
-// ---- an address as five words, where it is looked for first, the compare over all of it (the address table below; access_lists.hip.h)
-TXST_HD void load_addr(const uint8_t* p, uint32_t w[5]) {
-    for (int k = 0; k < 5; ++k) w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
-}
-// where an address is looked for first: a keyed mix of all of it (witness keys are attacker-chosen bytes; without the key nobody aims
-// them at one slot)
-TXST_HD uint32_t home_slot(const uint32_t w[5], uint32_t salt0, uint32_t salt1) {
-    uint32_t h = salt0;
-    for (int k = 0; k < 5; ++k) {
-        h = (h ^ w[k]) * 0x9E3779B1u;
-        h ^= h >> 15;
-        h = (h + salt1) * 0x85EBCA77u;
-        h ^= h >> 13;
-    }
-    return h * 0xC2B2AE3Du;
-}
-TXST_HD bool same_addr(const uint8_t* p, const uint32_t w[5]) {
-    uint32_t v[5];
-    load_addr(p, v);
-    return v[0] == w[0] && v[1] == w[1] && v[2] == w[2] && v[3] == w[3] && v[4] == w[4];
-}
-
 #ifndef PHANT_TXST_RULE_ONLY
 
 enum : uint32_t { CTL_WORDS = 4 };  // ctl[0]: what the arguments' check found, [1]: max(n - i) over the flagged rows, [2]: undetermined rows
 enum : uint32_t { BAD_AUTH_FIRST = 1, BAD_CODE_OFF = 2, BAD_CODE_INDEX = 4 };
-enum : uint32_t { NONE = PHANT_ROW_NONE, SEG_WORDS = 12, TILE = 256 };
+enum : uint32_t { NONE = PHANT_ROW_NONE, SEG_WORDS = seg::SEG_WORDS, TILE = seg::TILE };
+using Seg = seg::Seg<9>;  // {sum of costs, rows, "a sequence starts at or before me in what was combined"}
 
 // the call's device arrays
 struct Args {
@@ -207,20 +166,11 @@ __global__ void __launch_bounds__(256) txst_check_args_kernel(Args a) {
     if (f) atomicOr(a.ctl, f);
 }
 
-// row j into the address table (global memory, or the small path's in LDS)
+// row j into the address table (global memory, or the small path's in LDS): duplicates resolve to the lowest row
 __device__ inline void insert_row(const Args& a, uint32_t* table, uint32_t mask, uint32_t j) {
     uint32_t w[5];
     load_addr(a.in.addresses + 20ull * j, w);
-    uint32_t slot = home_slot(w, a.salt0, a.salt1) & mask;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {  // (the table is at most half full: the walk ends long before)
-        const uint32_t old = atomicCAS(table + slot, (uint32_t)NONE, j);
-        if (old == NONE) return;
-        if (same_addr(a.in.addresses + 20ull * old, w)) {  // (whichever row the slot holds by now has this address)
-            atomicMin(table + slot, j);
-            return;
-        }
-        slot = (slot + 1u) & mask;
-    }
+    keyed::claim(table, mask, home_slot(w, a.salt0, a.salt1), j, [&](uint32_t old) { return same_addr(a.in.addresses + 20ull * old, w); });
 }
 __global__ void __launch_bounds__(256) txst_insert_kernel(Args a) {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
@@ -230,30 +180,7 @@ __global__ void __launch_bounds__(256) txst_insert_kernel(Args a) {
 __device__ inline uint32_t row_of(const Args& a, const uint32_t* table, uint32_t mask, const uint8_t* addr) {
     uint32_t w[5];
     load_addr(addr, w);
-    uint32_t slot = home_slot(w, a.salt0, a.salt1) & mask;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        const uint32_t j = table[slot];
-        if (j == NONE) return NONE;
-        if (same_addr(a.in.addresses + 20ull * j, w)) return j;
-        slot = (slot + 1u) & mask;
-    }
-    return NONE;
-}
-
-// Of the lanes of a wave that have something to say about the same row, the lowest: many transactions name one recipient, and atomics
-// on one address are served one at a time.  Every lane of the wave calls this; the loop runs once per distinct row in the wave.
-__device__ inline bool wave_first_of(bool has, uint32_t row) {
-    const uint32_t lane = threadIdx.x & 63u;
-    unsigned long long todo = __ballot(has);
-    bool first = false;
-    while (todo) {
-        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
-        const uint32_t theirs = (uint32_t)__shfl((int)row, (int)leader);
-        const unsigned long long same = __ballot(has && row == theirs);
-        if (lane == leader) first = true;
-        todo &= ~same;
-    }
-    return first;
+    return keyed::find(table, mask, home_slot(w, a.salt0, a.salt1), [&](uint32_t j) { return same_addr(a.in.addresses + 20ull * j, w); });
 }
 __device__ inline void add_role(const Args& a, uint32_t row, uint32_t role) {
     atomicOr(reinterpret_cast<uint32_t*>(a.o.roles) + (row >> 2), role << (8u * (row & 3u)));
@@ -293,7 +220,7 @@ __device__ inline uint32_t locate_auth(const Args& a, const uint32_t* table, uin
 // a role for `row` (NONE: nothing to say), ONE atomic per distinct row and wave; every lane of the wave calls this.  (The lanes of a
 // call hold one kind: the role is the group's; the lowest tuple of a group is the earliest.)
 __device__ inline void publish(const Args& a, uint32_t* first_auth, uint32_t row, uint32_t role, uint32_t first_tx) {
-    if (wave_first_of(row != NONE, row)) {
+    if (keyed::wave_first_of(row != NONE, row)) {
         add_role(a, row, role);
         if (first_tx != NONE) atomicMin(first_auth + row, first_tx);
     }
@@ -324,70 +251,12 @@ __global__ void __launch_bounds__(256) txst_locate_kernel(Args a, uint32_t tx_bl
     publish(a, a.first_auth, row, role, first_tx);
 }
 
-// ---- the segmented scan.  An element: {sum of costs, rows, "a sequence starts at or before me in what was combined"}
-struct Seg {
-    uint32_t w[9], cnt, f;
-};
-__device__ __forceinline__ void seg_zero(Seg& s) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s.w[k] = 0u;
-    s.cnt = 0u, s.f = 0u;
-}
-// s = before (+) s
-__device__ __forceinline__ void seg_combine(Seg& s, const Seg& before) {
-    if (!s.f) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            c += (uint64_t)s.w[k] + before.w[k];
-            s.w[k] = (uint32_t)c, c >>= 32;
-        }
-        s.cnt += before.cnt;
-    }
-    s.f |= before.f;
-}
-__device__ __forceinline__ void seg_load(const uint32_t* p, Seg& s) {
-    const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1], c = reinterpret_cast<const uint4*>(p)[2];
-    s.w[0] = a.x, s.w[1] = a.y, s.w[2] = a.z, s.w[3] = a.w, s.w[4] = b.x, s.w[5] = b.y, s.w[6] = b.z, s.w[7] = b.w, s.w[8] = c.x;
-    s.cnt = c.y, s.f = c.z;
-}
-__device__ __forceinline__ void seg_store(uint32_t* p, const Seg& s) {
-    reinterpret_cast<uint4*>(p)[0] = make_uint4(s.w[0], s.w[1], s.w[2], s.w[3]);
-    reinterpret_cast<uint4*>(p)[1] = make_uint4(s.w[4], s.w[5], s.w[6], s.w[7]);
-    reinterpret_cast<uint4*>(p)[2] = make_uint4(s.w[8], s.cnt, s.f, 0u);
-}
-// inclusive over the 256 lanes of a workgroup: the wave by shuffles (six steps), the waves in front through LDS.  Every lane calls it.
-__device__ __forceinline__ void seg_scan_block(Seg& s, uint32_t tid, Seg* s_wave /* [4] */) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        Seg o;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) o.w[k] = (uint32_t)__shfl_up((int)s.w[k], d);
-        o.cnt = (uint32_t)__shfl_up((int)s.cnt, d);
-        o.f = (uint32_t)__shfl_up((int)s.f, d);
-        if (lane >= d) seg_combine(s, o);
-    }
-    if (lane == 63u) s_wave[wave] = s;
-    __syncthreads();
-    Seg run;
-    seg_zero(run);
-#pragma unroll
-    for (uint32_t w = 0; w < 3u; ++w)
-        if (w < wave) {
-            Seg t = s_wave[w];
-            seg_combine(t, run);
-            run = t;
-        }
-    seg_combine(s, run);
-}
-
 __global__ void __launch_bounds__(256) txst_scan_tiles_kernel(Args a, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals) {
     __shared__ Seg s_wave[4];
     const uint32_t tid = threadIdx.x, p = blockIdx.x * TILE + tid;
     const bool valid = p < a.in.n;
     Seg s;
-    seg_zero(s);
+    seg::zero(s);
     uint32_t i = 0;
     if (valid) {
         i = vals[p];
@@ -395,35 +264,19 @@ __global__ void __launch_bounds__(256) txst_scan_tiles_kernel(Args a, const uint
         s.cnt = 1u;
         s.f = (p == 0u || keys[p - 1u] != keys[p]) ? 1u : 0u;
     }
-    seg_scan_block(s, tid, s_wave);
+    seg::scan_block(s, tid, s_wave);
     if (valid) {
-        seg_store(a.loc + (size_t)SEG_WORDS * p, s);
+        seg::store(a.loc + (size_t)SEG_WORDS * p, s);
         a.inv[i] = p;
     }
-    if (tid == TILE - 1u) seg_store(a.agg + (size_t)SEG_WORDS * blockIdx.x, s);  // (the last tile's is never read)
+    if (tid == TILE - 1u) seg::store(a.agg + (size_t)SEG_WORDS * blockIdx.x, s);  // (the last tile's is never read)
 }
 
-// tp[t] = what runs into tile t: the tiles before it combined, 256 of them at a time
+// tp[t] = what runs into tile t: the tiles before it combined (one workgroup)
 __global__ void __launch_bounds__(256) txst_scan_aggr_kernel(Args a, uint32_t tiles) {
     __shared__ Seg s_wave[4];
     __shared__ Seg s_carry;
-    const uint32_t tid = threadIdx.x;
-    Seg carry;
-    seg_zero(carry);
-    if (tid == 0u) seg_store(a.tp, carry);
-    for (uint32_t c0 = 0; c0 < tiles; c0 += 256u) {
-        const uint32_t t = c0 + tid;
-        Seg s;
-        seg_zero(s);
-        if (t < tiles) seg_load(a.agg + (size_t)SEG_WORDS * t, s);
-        seg_scan_block(s, tid, s_wave);
-        seg_combine(s, carry);
-        if (t + 1u < tiles) seg_store(a.tp + (size_t)SEG_WORDS * (t + 1u), s);
-        if (tid == 255u) s_carry = s;
-        __syncthreads();
-        carry = s_carry;
-        __syncthreads();  // (s_wave and s_carry are written again by the next chunk)
-    }
+    seg::aggregate(a.agg, a.tp, 0u, tiles, threadIdx.x, s_wave, &s_carry);
 }
 
 // Row i, whose sender's row is s (NONE: the witness lacks it, or the row was skipped) and whose flags so far are f: `here` = the scan up to and
@@ -467,14 +320,11 @@ __global__ void __launch_bounds__(64) txst_rules_kernel(Args a, const uint64_t* 
     if (i >= a.in.n) return;
     const uint32_t s = a.o.sender_row[i];
     Seg here;
-    seg_zero(here);
+    seg::zero(here);
     bool last = false;
     if (s != NONE) {
         const uint32_t p = a.inv[i];
-        Seg into;
-        seg_load(a.loc + (size_t)SEG_WORDS * p, here);
-        seg_load(a.tp + (size_t)SEG_WORDS * (p / TILE), into);
-        seg_combine(here, into);
+        seg::scan_at(a.loc, a.tp, p, here);
         last = p + 1u == a.in.n || keys[p + 1u] != s;
     }
     finish_row(a, i, s, a.o.state_flags[i], here, last, a.first_auth);  // (the locate kernel's flags: SKIPPED, SENDER_UNKNOWN, TO_UNKNOWN)
@@ -532,28 +382,19 @@ __global__ void __launch_bounds__(256) txst_small_kernel(Args a, uint32_t n_auth
     const bool valid = tid < in.n;  // (the sorted order holds the n rows in front)
     const uint32_t i = (uint32_t)key, srow = (uint32_t)(key >> 32);
     Seg s;
-    seg_zero(s);
+    seg::zero(s);
     s.f = 1u;
     if (valid) {
         cost_of(in.upfront_cost + 32ull * i, in.tx_flags[i], s.w);
         s.cnt = 1u;
         s.f = (tid == 0u || (uint32_t)(s_key[tid - 1u] >> 32) != srow) ? 1u : 0u;
     }
-    seg_scan_block(s, tid, s_wave);
+    seg::scan_block(s, tid, s_wave);
     if (valid) {
         const bool last = tid + 1u == in.n || (uint32_t)(s_key[tid + 1u] >> 32) != srow;
         finish_row(a, i, srow == in.n_accounts ? (uint32_t)NONE : srow, s_flags[i], s, last, s_first_auth);
     }
 }
-
-#define TXST_TRY(call)                                                             \
-    do {                                                                           \
-        const hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) {                                                    \
-            err = std::string("block_txs_prestate: " #call ": ") + hipGetErrorString(e_); \
-            return PHANT_E_DEVICE;                                                 \
-        }                                                                          \
-    } while (0)
 
 // the arrays that cross the bus in the host form: (member, type, elements)
 #define TXST_INPUTS(X)                                                                                                                     \
@@ -590,7 +431,7 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
     using namespace txst;
     const uint32_t n = in.n, na = in.n_accounts, nc = in.n_codes, np = in.n_probe;
     const uint32_t n_auth = in.auth_first && n ? in.n_auth : 0u;  // (without auth_first, or without a transaction, a tuple belongs to none)
-    TXST_TRY(ws.ensure_mailbox());
+    CALL_TRY("block_txs_prestate", ws.ensure_mailbox());
     static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXST_WORDS, "the control words fit their part of the mailbox");
     volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXST;
     std::vector<uint8_t> kind;
@@ -599,8 +440,7 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
 
     // ---- the arena: the zeroed words (control, the sort's digit totals, sends, roles) and the outputs in front (one span goes back), (host
     // form) the inputs, then the table and what the sort and the scan need
-    uint32_t slots = 64;
-    while (slots < 2ull * na) slots <<= 1;  // (n_accounts < 2^31 is checked by the caller)
+    const uint32_t slots = keyed::table_slots(na);  // (n_accounts < 2^31 is checked by the caller)
     const uint32_t tiles = (uint32_t)(((uint64_t)n + TILE - 1u) / TILE);
     const size_t zero_words = (size_t)CTL_WORDS + 512 + na + ((size_t)na + 3) / 4;
     Args a;
@@ -639,9 +479,9 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
     a.o.sends = digit_totals + 512;
     a.o.roles = reinterpret_cast<uint8_t*>(a.o.sends + na);
     a.table = ones, a.first_auth = ones + slots;
-    TXST_TRY(hipMemsetAsync(zero, 0, 4 * zero_words, st));
+    CALL_TRY("block_txs_prestate", hipMemsetAsync(zero, 0, 4 * zero_words, st));
     const bool small = n != 0u && n <= SMALL_ROWS && na <= SMALL_ACCOUNTS;  // (its table and first-tuple words are in LDS)
-    if (!small) TXST_TRY(hipMemsetAsync(ones, 0xff, 4 * ((size_t)slots + na), st));
+    if (!small) CALL_TRY("block_txs_prestate", hipMemsetAsync(ones, 0xff, 4 * ((size_t)slots + na), st));
 
     // ---- in: (host form) every array and the codes' kinds in ONE copy through the pinned stage where they fit it; (device form) the check
     if (!dev) {
@@ -650,13 +490,13 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
         TXST_INPUTS(X)
 #undef X
         ins.put(a.code_kind, kind.data(), nc);  // (`kind` outlives the call's last synchronisation)
-        TXST_TRY(ins.finish());
+        CALL_TRY("block_txs_prestate", ins.finish());
         a.in.code_off = nullptr, a.in.codes = nullptr;  // (no kernel of the host form reads them: the kinds are there)
     } else {
         const uint64_t lanes = std::max<uint64_t>(std::max<uint64_t>((uint64_t)n + 1u, nc), na);
         hipLaunchKernelGGL(txst_check_args_kernel, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, st, a);
-        TXST_TRY(hipGetLastError());
-        TXST_TRY(ws.read_words(Workspaces::MAILBOX_TXST, a.ctl, CTL_WORDS, st));
+        CALL_TRY("block_txs_prestate", hipGetLastError());
+        CALL_TRY("block_txs_prestate", ws.read_words(Workspaces::MAILBOX_TXST, a.ctl, CTL_WORDS, st));
         if (mb[0] & BAD_AUTH_FIRST) return err = "block_txs_prestate_dev: auth_first does not run within [0, n_auth] without going backwards", PHANT_E_INVALID_ARG;
         if (mb[0] & BAD_CODE_OFF) return err = "block_txs_prestate_dev: code_off does not run within [0, code_bytes] without going backwards", PHANT_E_INVALID_ARG;
         if (mb[0] & BAD_CODE_INDEX) return err = "block_txs_prestate_dev: a code_index names no code", PHANT_E_INVALID_ARG;
@@ -666,27 +506,25 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
     const uint32_t tx_blocks = tiles, auth_blocks = (n_auth + 255u) / 256u, probe_blocks = (np + 255u) / 256u;
     if (small) {
         hipLaunchKernelGGL(txst_small_kernel, dim3(1), dim3(256), 0, st, a, n_auth);
-        TXST_TRY(hipGetLastError());
+        CALL_TRY("block_txs_prestate", hipGetLastError());
     } else if (na) {
         hipLaunchKernelGGL(txst_insert_kernel, dim3((na + 255u) / 256u), dim3(256), 0, st, a);
-        TXST_TRY(hipGetLastError());
+        CALL_TRY("block_txs_prestate", hipGetLastError());
     }
     if (!small && tx_blocks + auth_blocks + probe_blocks) {
         hipLaunchKernelGGL(txst_locate_kernel, dim3(tx_blocks + auth_blocks + probe_blocks), dim3(256), 0, st, a, tx_blocks, auth_blocks);
-        TXST_TRY(hipGetLastError());
+        CALL_TRY("block_txs_prestate", hipGetLastError());
     }
     if (n && !small) {
-        uint32_t bits = 1;  // (the keys run from 0 to n_accounts)
-        while (bits < 32u && (na >> bits)) ++bits;
         uint64_t* keys = nullptr;
         uint32_t* vals = nullptr;
-        TXST_TRY(launch_sort_pairs(a.keys, a.vals, keys_alt, vals_alt, n, bits, hist, digit_totals, &keys, &vals, st));
+        CALL_TRY("block_txs_prestate", launch_sort_pairs(a.keys, a.vals, keys_alt, vals_alt, n, sort_key_bits(na), hist, digit_totals, &keys, &vals, st));
         hipLaunchKernelGGL(txst_scan_tiles_kernel, dim3(tiles), dim3(256), 0, st, a, (const uint64_t*)keys, (const uint32_t*)vals);
-        TXST_TRY(hipGetLastError());
+        CALL_TRY("block_txs_prestate", hipGetLastError());
         hipLaunchKernelGGL(txst_scan_aggr_kernel, dim3(1), dim3(256), 0, st, a, tiles);
-        TXST_TRY(hipGetLastError());
+        CALL_TRY("block_txs_prestate", hipGetLastError());
         hipLaunchKernelGGL(txst_rules_kernel, dim3((n + 63u) / 64u), dim3(64), 0, st, a, (const uint64_t*)keys);
-        TXST_TRY(hipGetLastError());
+        CALL_TRY("block_txs_prestate", hipGetLastError());
     }
 
     // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage)
@@ -696,12 +534,11 @@ int32_t block_txs_prestate(Workspaces& ws, hipStream_t st, const phant_txstate_i
 #define X(m, T, e) outs.add(out.m, a.o.m, (size_t)(e) * sizeof(T));
     TXST_OUTPUTS(X)
 #undef X
-    TXST_TRY(outs.deliver());
+    CALL_TRY("block_txs_prestate", outs.deliver());
     out.first_bad = n - outs.ctl()[1], out.n_undetermined = outs.ctl()[2];
     return PHANT_OK;
 }
 
-#undef TXST_TRY
 #undef TXST_INPUTS
 #undef TXST_OUTPUTS
 

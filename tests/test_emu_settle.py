@@ -15,7 +15,7 @@ from tests.test_gpu_settle import (  # noqa: E402,F401
     P, test_event_counts_around_a_tile, test_a_segment_across_three_tiles, test_no_transactions_and_no_withdrawals,
     test_table_sizes_around_a_key_byte, test_coincidences, test_a_balance_that_an_earlier_credit_covers, test_values_near_the_ends,
     test_gas_limit_at_the_boundary, test_classes, test_random_blocks_at_each_fork, test_subsets_of_the_outputs,
-    test_a_call_beyond_the_pinned_stage, test_refused_arguments, test_the_fixtures_through_run_transfer_block, test_a_synthetic_block_end_to_end)
+    test_a_call_beyond_the_pinned_stage, test_both_scans_beyond_one_chunk_of_aggregates, test_refused_arguments, test_the_fixtures_through_run_transfer_block, test_a_synthetic_block_end_to_end)
 
 
 def test_launch_counts(P):

@@ -13,7 +13,7 @@ def _emulated_backend():
 
 from tests.test_gpu_txstate import (  # noqa: E402,F401
     P, test_sizes_and_sender_arrangements, test_join, test_sums, test_rules, test_random_blocks_at_each_fork, test_subsets_of_the_outputs,
-    test_a_call_beyond_the_pinned_stage, test_refused_arguments, test_end_to_end_over_the_fixtures)
+    test_a_call_beyond_the_pinned_stage, test_one_sequence_across_a_chunk_of_aggregates, test_refused_arguments, test_end_to_end_over_the_fixtures)
 
 
 def test_launch_counts(P):

@@ -367,6 +367,33 @@ def test_a_call_beyond_the_pinned_stage(P):
     assert sc["gas_used"] > 0
 
 
+def test_both_scans_beyond_one_chunk_of_aggregates(P):
+    """65 600 plain transfers of distinct senders that all pay ONE coinbase, which also sends, and 10 withdrawals against 2 048 rows:
+    196 810 events in 769 tiles, so the aggregate pass over the events runs four chunks of 256 tiles, and 257 gas tiles, so the second
+    workgroup's range starts behind the events' and carries into a second chunk.  The coinbase's segment begins inside the first chunk and
+    ends inside the last: its running balance crosses every chunk boundary.  Row for row against the definition, in both forms."""
+    rng = np.random.default_rng(65600)
+    n, na = 65600, 2048
+    accounts = make_accounts(na, rng)
+    ok = senders_of(accounts)
+    c = ok[-2]
+    txs = [dict(t, to_row=c) for t in make_block(n, accounts, "distinct", rng)]
+    for i, t in enumerate(txs):
+        if i % 23 == 17:
+            t["cost"] = accounts[t["sender_row"]]["balance"] * 3  # short of balance
+        elif i % 23 == 19:
+            t["gas_limit"] = BGL
+    wd = [(ok[k], int(rng.integers(0, 1 << 40))) for k in range(10)]
+    events, chunk = 3 * n + len(wd), 256 * 256
+    assert (events + 255) // 256 == 769 and (n + 255) // 256 == 257
+    before = sum(t["sender_row"] < c for t in txs) + sum(r < c for r, _ in wd)  # the sorted slots in front of the coinbase's segment
+    segment = 2 * n + sum(t["sender_row"] == c for t in txs) + sum(r == c for r, _ in wd)
+    assert before < chunk and before + segment > 3 * chunk
+    out, sc = check(P, R.PRAGUE, txs, accounts, wd, coinbase_row=c)
+    assert sc["n_not_plain"] == 0 and sc["gas_used"] > 21000 * n
+    assert {0, R.GAS_LIMIT, R.BALANCE_SHORT} <= set(out["settle_flags"]) and out["nonces_after"][c] > accounts[c]["nonce"]
+
+
 def test_refused_arguments(P):
     """one refusal per rule of the header, in both forms; nothing is written"""
     rng = np.random.default_rng(6)

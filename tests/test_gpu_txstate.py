@@ -118,12 +118,12 @@ def make_accounts(na, rng):
 
 def make_block(n, accounts, arrangement, rng):
     """n transactions whose senders are arranged as asked; nonces right except every seventh, costs of up to 250 bits, a row in 29
-    skipped (none in the "straddle" arrangement, which counts positions)"""
+    skipped (none in the "straddle" and "unbroken" arrangements, which count positions)"""
     na = len(accounts)
-    skipped = [i % 29 == 17 and arrangement != "straddle" for i in range(n)]
+    skipped = [i % 29 == 17 and arrangement not in ("straddle", "unbroken") for i in range(n)]
     if arrangement == "distinct":
         who = [i % na for i in range(n)]
-    elif arrangement == "one":
+    elif arrangement in ("one", "unbroken"):  # "unbroken": the one sender's sequence is all n rows, the first n places of the sorted order
         who = [na // 2] * n
     elif arrangement == "interleaved":  # one sender with 257 rows, one with 65, the others between them: only a stable order ranks them
         quota = {0: 257, na - 1: 65}
@@ -330,6 +330,23 @@ def test_a_call_beyond_the_pinned_stage(P, n, na):
         assert out_bytes > 8 << 20
     flags = check(P, R.LONDON, txs, accounts, probes=probes)
     assert len(set(flags.tolist())) >= 3
+
+
+@pytest.mark.parametrize("n, tiles", [(65600, 257), (65800, 258)])
+def test_one_sequence_across_a_chunk_of_aggregates(P, n, tiles):
+    """n rows of ONE sender against 2 048 pre-state rows, its sequence unbroken over every tile.  65 600 rows are 257 tiles: the aggregate
+    pass runs a second chunk of 256 tiles, and the rank and the 288-bit sum of the rows in tile 256 are what the first chunk's last lane
+    hands on.  65 800 rows are 258: what runs into tile 257 is tile 256's aggregate combined with the CARRY of the first chunk (a pass that
+    dropped the carry passes at 257 tiles: its second chunk has nothing to store).  Row for row against the definition, in both forms."""
+    rng = np.random.default_rng(n)
+    na = 2048
+    accounts = make_accounts(na, rng)
+    txs = make_block(n, accounts, "unbroken", rng)
+    assert (n + 255) // 256 == tiles and accounts[na // 2]["status"] == R.PRESENT
+    flags = check(P, R.LONDON, txs, accounts)
+    out, _, _ = R.define(R.LONDON, txs, accounts)
+    assert out["sends"][na // 2] == n and out["expected_nonce"][n - 1] == accounts[na // 2]["nonce"] + n - 1
+    assert len(set(flags.tolist())) >= 3 and int(flags[n - 1]) & R.SPENT_SATURATED
 
 
 def test_refused_arguments(P):
