@@ -2440,39 +2440,72 @@ int32_t phant_mpt_root_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* 
 
 /* ---------------------------------------------------------------- witness generation */
 
-static void prove_args_of(const phant_prove_out* out, phant::ProveArgs& a) {
+// The four entry points of the prover: two forms (the node set, a list per query), each over host and over device arrays.  Their out
+// structs differ in the name of the first-node table alone (Out: either; first_node: that table), their refusals in the entry
+// point's `name`.
+static int32_t prove_refuse(phant_ctx* c, const char* name, const std::string& what) {
+    return fail(c, PHANT_E_INVALID_ARG, (std::string(name) + ": " + what).c_str());
+}
+
+template <class Out>
+static int32_t prove_check_host(phant_ctx* c, const char* name, const Out* out, const phant::HostPairs& h, const phant::ProveQueries& q) {
+    if (!c || !out) return c ? prove_refuse(c, name, "out is null") : PHANT_E_INVALID_ARG;
+    if (out->struct_size != sizeof(Out)) return prove_refuse(c, name, "wrong struct_size");
+    if (h.n_tries == 0 || (!h.seg_first && h.n_tries != 1)) return prove_refuse(c, name, "seg_first is null, or no trie");
+    if (h.n && (!h.key_off || !h.val_off)) return prove_refuse(c, name, "null pointer");
+    if (q.n_queries && !q.qkey_off) return prove_refuse(c, name, "qkey_off is null");
+    if (q.n_queries && !q.q_trie && h.n_tries != 1) return prove_refuse(c, name, "q_trie is null with several tries");
+    return PHANT_OK;
+}
+
+template <class Out>
+static int32_t prove_check_dev(phant_ctx* c, const char* name, const Out* out, uint32_t* Out::*first_node, const char* first_name,
+                               const phant::TriePairs& p, const phant::ProveQueries& q, uint64_t qkey_bytes) {
+    if (!c || !out) return c ? prove_refuse(c, name, "out is null") : PHANT_E_INVALID_ARG;
+    if (out->struct_size != sizeof(Out)) return prove_refuse(c, name, "wrong struct_size");
+    if (p.n_tries == 0 || (!p.seg_first && p.n_tries != 1)) return prove_refuse(c, name, "d_seg_first is null, or no trie");
+    if (p.n && (!p.key_off || !p.val_off || (p.key_bytes && !p.keys) || (p.val_bytes && !p.vals))) return prove_refuse(c, name, "null pointer");
+    if (q.n_queries && (!q.qkey_off || (qkey_bytes && !q.qkeys))) return prove_refuse(c, name, "null query pointer");
+    if (q.n_queries && !q.q_trie && p.n_tries != 1) return prove_refuse(c, name, "d_q_trie is null with several tries");
+    if (((uintptr_t)out->roots & 3u) || ((uintptr_t)out->node_off & 7u) || ((uintptr_t)(out->*first_node) & 3u))
+        return prove_refuse(c, name, std::string("roots / ") + first_name + " 4-byte, node_off 8-byte aligned");
+    return PHANT_OK;
+}
+
+// The call behind the checks: the out struct's buffers and capacities as the driver's arguments, `run(args, err)`, the totals back.
+template <class Out, class Run>
+static int32_t prove_run(phant_ctx* c, Out* out, uint32_t* Out::*first_node, bool per_proof, const phant::ProveQueries& q, Run&& run) {
+    out->total_nodes = 0;
+    out->nodes_len = 0;
+    DeviceGuard g(c->device);
+    std::string err;
+    phant::ProveArgs a;
+    a.q = q;
+    a.per_proof = per_proof;
     a.nodes = out->nodes;
     a.node_off = out->node_off;
-    a.trie_first_node = out->trie_first_node;
+    a.first_node = out->*first_node;
     a.roots = out->roots;
     a.q_status = out->q_status;
     // (a buffer nobody wants has no capacity to exceed: the other one is then written under its own bound alone)
     a.nodes_cap = out->nodes ? out->nodes_cap : ~0ull;
     a.max_nodes = out->node_off ? out->max_nodes : 0xffffffffu;
+    const int32_t rc = run(a, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->total_nodes = a.total_nodes;
+    out->nodes_len = a.nodes_len;
+    return PHANT_OK;
 }
 
 int32_t phant_mpt_prove_nodeset(phant_ctx* c, const uint8_t* keys, const uint32_t* key_off, const uint8_t* vals,
                                 const uint64_t* val_off, uint32_t n, const uint32_t* seg_first, uint32_t n_tries,
                                 const uint8_t* qkeys, const uint32_t* qkey_off, const uint32_t* q_trie, const uint8_t* q_flags,
                                 uint32_t n_queries, phant_prove_out* out) {
-    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: out is null") : PHANT_E_INVALID_ARG;
-    if (out->struct_size != sizeof(phant_prove_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: wrong struct_size");
-    if (n_tries == 0 || (!seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: seg_first is null, or no trie");
-    if (n && (!key_off || !val_off)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: null pointer");
-    if (n_queries && !qkey_off) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: qkey_off is null");
-    if (n_queries && !q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset: q_trie is null with several tries");
-    out->total_nodes = 0;
-    out->nodes_len = 0;
-    DeviceGuard g(c->device);
-    std::string err;
-    phant::ProveArgs a;
-    prove_args_of(out, a);
-    a.q = phant::ProveQueries{qkeys, qkey_off, q_trie, q_flags, n_queries};
-    const int32_t rc = phant::prove_nodeset_host(c->ws, c->stream, phant::HostPairs{keys, key_off, vals, val_off, n, seg_first, n_tries}, a, err);
-    if (rc) return fail(c, rc, err.c_str());
-    out->total_nodes = a.total_nodes;
-    out->nodes_len = a.nodes_len;
-    return PHANT_OK;
+    const phant::HostPairs h{keys, key_off, vals, val_off, n, seg_first, n_tries};
+    const phant::ProveQueries q{qkeys, qkey_off, q_trie, q_flags, n_queries};
+    if (const int32_t bad = prove_check_host(c, "mpt_prove_nodeset", out, h, q)) return bad;
+    return prove_run(c, out, &phant_prove_out::trie_first_node, false, q,
+                     [&](phant::ProveArgs& a, std::string& err) { return phant::prove_host(c->ws, c->stream, h, a, err); });
 }
 
 int32_t phant_mpt_prove_nodeset_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes,
@@ -2480,91 +2513,38 @@ int32_t phant_mpt_prove_nodeset_dev(phant_ctx* c, const uint8_t* d_keys, const u
                                     const uint32_t* d_seg_first, uint32_t n_tries, const uint8_t* d_qkeys, const uint32_t* d_qkey_off,
                                     uint64_t qkey_bytes, const uint32_t* d_q_trie, const uint8_t* d_q_flags, uint32_t n_queries,
                                     phant_prove_out* out) {
-    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: out is null") : PHANT_E_INVALID_ARG;
-    if (out->struct_size != sizeof(phant_prove_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: wrong struct_size");
-    if (n_tries == 0 || (!d_seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: d_seg_first is null, or no trie");
-    if (n && (!d_key_off || !d_val_off || (key_bytes && !d_keys) || (val_bytes && !d_vals)))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: null pointer");
-    if (n_queries && (!d_qkey_off || (qkey_bytes && !d_qkeys))) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: null query pointer");
-    if (n_queries && !d_q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: d_q_trie is null with several tries");
-    if (((uintptr_t)out->roots & 3u) || ((uintptr_t)out->node_off & 7u) || ((uintptr_t)out->trie_first_node & 3u))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_nodeset_dev: roots / trie_first_node 4-byte, node_off 8-byte aligned");
-    out->total_nodes = 0;
-    out->nodes_len = 0;
-    DeviceGuard g(c->device);
-    TimedRegion t(c);
-    std::string err;
-    phant::ProveArgs a;
-    prove_args_of(out, a);
-    a.q = phant::ProveQueries{d_qkeys, d_qkey_off, d_q_trie, d_q_flags, n_queries};
-    const int32_t rc = phant::prove_nodeset_dev(c->ws, c->stream, phant::TriePairs{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries}, a,
-                                                err);
-    if (rc) return fail(c, rc, err.c_str());
-    out->total_nodes = a.total_nodes;
-    out->nodes_len = a.nodes_len;
-    return PHANT_OK;
-}
-
-static void prove_batch_args_of(const phant_prove_batch_out* out, phant::ProveBatchArgs& a) {
-    a.nodes = out->nodes;
-    a.node_off = out->node_off;
-    a.proof_first_node = out->proof_first_node;
-    a.roots = out->roots;
-    a.q_status = out->q_status;
-    a.nodes_cap = out->nodes ? out->nodes_cap : ~0ull;  // (as prove_args_of)
-    a.max_nodes = out->node_off ? out->max_nodes : 0xffffffffu;
+    const phant::TriePairs p{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries};
+    const phant::ProveQueries q{d_qkeys, d_qkey_off, d_q_trie, d_q_flags, n_queries};
+    if (const int32_t bad = prove_check_dev(c, "mpt_prove_nodeset_dev", out, &phant_prove_out::trie_first_node, "trie_first_node", p, q, qkey_bytes))
+        return bad;
+    return prove_run(c, out, &phant_prove_out::trie_first_node, false, q, [&](phant::ProveArgs& a, std::string& err) {
+        TimedRegion t(c);
+        return phant::prove_dev(c->ws, c->stream, p, a, err);
+    });
 }
 
 int32_t phant_mpt_prove_batch(phant_ctx* c, const uint8_t* keys, const uint32_t* key_off, const uint8_t* vals, const uint64_t* val_off,
                               uint32_t n, const uint32_t* seg_first, uint32_t n_tries, const uint8_t* qkeys, const uint32_t* qkey_off,
                               const uint32_t* q_trie, uint32_t n_queries, phant_prove_batch_out* out) {
-    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: out is null") : PHANT_E_INVALID_ARG;
-    if (out->struct_size != sizeof(phant_prove_batch_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: wrong struct_size");
-    if (n_tries == 0 || (!seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: seg_first is null, or no trie");
-    if (n && (!key_off || !val_off)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: null pointer");
-    if (n_queries && !qkey_off) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: qkey_off is null");
-    if (n_queries && !q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch: q_trie is null with several tries");
-    out->total_nodes = 0;
-    out->nodes_len = 0;
-    DeviceGuard g(c->device);
-    std::string err;
-    phant::ProveBatchArgs a;
-    prove_batch_args_of(out, a);
-    a.q = phant::ProveQueries{qkeys, qkey_off, q_trie, nullptr, n_queries};
-    const int32_t rc = phant::prove_batch_host(c->ws, c->stream, phant::HostPairs{keys, key_off, vals, val_off, n, seg_first, n_tries}, a, err);
-    if (rc) return fail(c, rc, err.c_str());
-    out->total_nodes = a.total_nodes;
-    out->nodes_len = a.nodes_len;
-    return PHANT_OK;
+    const phant::HostPairs h{keys, key_off, vals, val_off, n, seg_first, n_tries};
+    const phant::ProveQueries q{qkeys, qkey_off, q_trie, nullptr, n_queries};
+    if (const int32_t bad = prove_check_host(c, "mpt_prove_batch", out, h, q)) return bad;
+    return prove_run(c, out, &phant_prove_batch_out::proof_first_node, true, q,
+                     [&](phant::ProveArgs& a, std::string& err) { return phant::prove_host(c->ws, c->stream, h, a, err); });
 }
 
 int32_t phant_mpt_prove_batch_dev(phant_ctx* c, const uint8_t* d_keys, const uint32_t* d_key_off, uint64_t key_bytes, const uint8_t* d_vals,
                                   const uint64_t* d_val_off, uint64_t val_bytes, uint32_t n, const uint32_t* d_seg_first, uint32_t n_tries,
                                   const uint8_t* d_qkeys, const uint32_t* d_qkey_off, uint64_t qkey_bytes, const uint32_t* d_q_trie,
                                   uint32_t n_queries, phant_prove_batch_out* out) {
-    if (!c || !out) return c ? fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: out is null") : PHANT_E_INVALID_ARG;
-    if (out->struct_size != sizeof(phant_prove_batch_out)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: wrong struct_size");
-    if (n_tries == 0 || (!d_seg_first && n_tries != 1)) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: d_seg_first is null, or no trie");
-    if (n && (!d_key_off || !d_val_off || (key_bytes && !d_keys) || (val_bytes && !d_vals)))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: null pointer");
-    if (n_queries && (!d_qkey_off || (qkey_bytes && !d_qkeys))) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: null query pointer");
-    if (n_queries && !d_q_trie && n_tries != 1) return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: d_q_trie is null with several tries");
-    if (((uintptr_t)out->roots & 3u) || ((uintptr_t)out->node_off & 7u) || ((uintptr_t)out->proof_first_node & 3u))
-        return fail(c, PHANT_E_INVALID_ARG, "mpt_prove_batch_dev: roots / proof_first_node 4-byte, node_off 8-byte aligned");
-    out->total_nodes = 0;
-    out->nodes_len = 0;
-    DeviceGuard g(c->device);
-    TimedRegion t(c);
-    std::string err;
-    phant::ProveBatchArgs a;
-    prove_batch_args_of(out, a);
-    a.q = phant::ProveQueries{d_qkeys, d_qkey_off, d_q_trie, nullptr, n_queries};
-    const int32_t rc = phant::prove_batch_dev(c->ws, c->stream, phant::TriePairs{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries}, a,
-                                              err);
-    if (rc) return fail(c, rc, err.c_str());
-    out->total_nodes = a.total_nodes;
-    out->nodes_len = a.nodes_len;
-    return PHANT_OK;
+    const phant::TriePairs p{d_keys, d_key_off, key_bytes, d_vals, d_val_off, val_bytes, n, d_seg_first, n_tries};
+    const phant::ProveQueries q{d_qkeys, d_qkey_off, d_q_trie, nullptr, n_queries};
+    if (const int32_t bad = prove_check_dev(c, "mpt_prove_batch_dev", out, &phant_prove_batch_out::proof_first_node, "proof_first_node", p, q, qkey_bytes))
+        return bad;
+    return prove_run(c, out, &phant_prove_batch_out::proof_first_node, true, q, [&](phant::ProveArgs& a, std::string& err) {
+        TimedRegion t(c);
+        return phant::prove_dev(c->ws, c->stream, p, a, err);
+    });
 }
 
 int32_t phant_index_root_rlp(phant_ctx* c, const uint8_t* items, const uint64_t* item_off,

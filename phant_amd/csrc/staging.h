@@ -94,7 +94,7 @@ struct StagedInputs {
     }
 };
 
-// ---- in, host-form pairs: the one way in for trie_forest_host and prove_nodeset_host.  Validates `h` (then `check_more()`: the
+// ---- in, host-form pairs: the one way in for trie_forest_host and the prover's prove_host.  Validates `h` (then `check_more()`: the
 // caller's further inputs; nothing is laid out or copied behind a refusal), lays ws.io out as the five input arrays followed by
 // whatever `carve_more(arena)` takes -- it returns the end of the caller's further INPUTS, which it takes first, or nullptr --, writes
 // the pairs with their offsets rebased to 0 (in place in the pinned mirror when staged: no host allocation), lets `put_more(ins)` add

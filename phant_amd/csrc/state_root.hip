@@ -408,8 +408,8 @@ int32_t state_leaves_core(Workspaces& ws, hipStream_t st, const StateIn& in, con
         if (!pv->per_proof) SR_TRY(hipMemcpyAsync(lay.qflags, pv->slot_flags.data(), ns, hipMemcpyHostToDevice, st));
         SR_TRY(launch_keccak256_fixed(lay.qpre, 32, 32, ns, lay.qkeys, st));
         hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)ns + 1)), dim3(256), 0, st, ns, lay.qoff);
-        if (pv->per_proof) rc = prove_forest_batch_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, nullptr, ns}, pv->nodes, pv->node_off, pv->first, err);
-        else rc = prove_forest_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, lay.qflags, ns}, pv->nodes, pv->node_off, err);
+        rc = prove_collect(ws, st, storage, ProveQueries{lay.qkeys, lay.qoff, lay.qtrie, pv->per_proof ? nullptr : lay.qflags, ns}, pv->nodes, pv->node_off,
+                           pv->per_proof ? &pv->first : nullptr, err);
     } else {
         rc = trie_forest_dev(ws, st, storage, err);
     }
@@ -663,69 +663,84 @@ static int32_t group_touched_keys(const ProveQueries& touched, const char* call,
     return PHANT_OK;
 }
 
+// Which touched accounts the state holds: index_of_touched[a] = the state's row of touched account a, or NOT_HELD; held_idx = the rows
+// of those it holds, in touched order.  Their touched slots become pv's queries against that account's storage trie.
+constexpr uint32_t NOT_HELD = 0xffffffffu;
+struct HeldAccounts {
+    std::vector<uint32_t> index_of_touched, held_idx;
+};
+static HeldAccounts held_accounts(const StateIn& in, const TouchedKeys& tk, StateProve& pv) {
+    std::unordered_map<std::string, uint32_t> index_of;
+    index_of.reserve((size_t)in.n * 2);
+    for (uint32_t i = 0; i < in.n; ++i) index_of.emplace(std::string(reinterpret_cast<const char*>(in.addrs + 20ull * i), 20), i);
+    HeldAccounts h;
+    h.index_of_touched.assign(tk.addr.size(), NOT_HELD);
+    for (size_t a = 0; a < tk.addr.size(); ++a) {
+        const auto it = index_of.find(std::string(reinterpret_cast<const char*>(tk.addr[a].data()), 20));
+        if (it == index_of.end()) continue;
+        h.index_of_touched[a] = it->second;
+        h.held_idx.push_back(it->second);
+        for (size_t j = 0; j < tk.slots[a].size(); ++j) {
+            pv.slot_pre.insert(pv.slot_pre.end(), tk.slots[a][j].begin(), tk.slots[a][j].end());
+            pv.slot_trie.push_back(it->second);
+            pv.slot_flags.push_back(tk.slot_flags[a][j]);
+        }
+    }
+    return h;
+}
+
+// The device steps in front of the state trie's proving pass: the touched addresses in (with their flags when the form reads any),
+// hashed to the queries' keys (lay.tkeys, offsets lay.aoff), and the held accounts' code hashes -- with `sr` their storage roots as
+// well, through the same 32 x na bytes -- on their way back: those copies ride on the pass's synchronisations.
+static int32_t stage_touched_addresses(hipStream_t st, const StateLayout& lay, const DevLeaves& l, const TouchedKeys& tk, bool with_flags,
+                                       const std::vector<uint32_t>& held_idx, std::vector<uint8_t>& hc, std::vector<uint8_t>* sr, std::string& err) {
+    static_assert(sizeof(std::array<uint8_t, 20>) == 20, "tk.addr is the addresses back to back");
+    const uint32_t na = (uint32_t)tk.addr.size(), nh = (uint32_t)held_idx.size();
+    if (na) {
+        SR_TRY(hipMemcpyAsync(lay.apre, tk.addr.data(), 20 * (size_t)na, hipMemcpyHostToDevice, st));
+        if (with_flags) SR_TRY(hipMemcpyAsync(lay.aflags, tk.flags.data(), na, hipMemcpyHostToDevice, st));
+        SR_TRY(launch_keccak256_fixed(lay.apre, 20, 20, na, lay.tkeys, st));
+    }
+    hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)na + 1)), dim3(256), 0, st, na, lay.aoff);
+    hc.resize(32 * (size_t)nh);
+    if (sr) sr->resize(32 * (size_t)nh);
+    if (!nh) return PHANT_OK;
+    SR_TRY(hipMemcpyAsync(lay.held, held_idx.data(), 4 * (size_t)nh, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * nh)), dim3(256), 0, st, l.code_hash, lay.held, nh, lay.thc);
+    SR_TRY(hipMemcpyAsync(hc.data(), lay.thc, hc.size(), hipMemcpyDeviceToHost, st));
+    if (sr) {
+        hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * nh)), dim3(256), 0, st, lay.sroots, lay.held, nh, lay.thc);
+        SR_TRY(hipMemcpyAsync(sr->data(), lay.thc, sr->size(), hipMemcpyDeviceToHost, st));
+    }
+    return PHANT_OK;
+}
+
 // phant_state_witness: the state pass with both of its forests proven -- the touched slots against the storage forest while its
 // tables stand, the touched addresses against the state trie behind it -- and the result laid out as the parser lays out a
 // document: accounts and slots in order of first appearance, "state" = the state-trie nodes, then the storage nodes.
 int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, ExecWitness& w, uint8_t root_out[32],
                            std::string& err) {
-    const uint32_t n = in.n;
-    const uint8_t* const addrs = in.addrs;
-    const uint8_t* const code = in.code;
-    const uint64_t* const code_off = in.code_off;
     w = ExecWitness();
     w.node_off.push_back(0);
     w.code_off.push_back(0);
     // ---- the keys, grouped as exec_witness_parse_json groups them ----
     TouchedKeys tk;
     if (const int32_t bad = group_touched_keys(touched, "state_witness", tk, err)) return bad;
-    std::vector<std::array<uint8_t, 20>>& t_addr = tk.addr;
-    std::vector<std::vector<std::array<uint8_t, 32>>>& t_slots = tk.slots;
-    std::vector<std::vector<uint8_t>>& t_slot_flags = tk.slot_flags;
-    std::vector<uint8_t>& t_flags = tk.flags;
-    exec_witness_layout_keys(w, t_addr, t_slots);
-    if (n == 0) return trie_forest_host(ws, st, HostPairs{}, root_out, err);  // (every key absent under the empty root)
-
-    // ---- which touched addresses the state holds: their slots are queries against that account's storage trie ----
-    std::unordered_map<std::string, uint32_t> index_of;
-    index_of.reserve((size_t)n * 2);
-    for (uint32_t i = 0; i < n; ++i) index_of.emplace(std::string(reinterpret_cast<const char*>(addrs + 20ull * i), 20), i);
-    const uint32_t na = (uint32_t)t_addr.size();
-    std::vector<uint32_t> held_idx;  // the state's index of every touched account it holds, in touched order
+    exec_witness_layout_keys(w, tk.addr, tk.slots);
+    if (in.n == 0) return trie_forest_host(ws, st, HostPairs{}, root_out, err);  // (every key absent under the empty root)
+    // ---- the device passes: the storage forest with the held accounts' touched slots, then the state trie with the touched
+    // addresses' paths, exclusion proofs included ----
     StateProve pv;
-    for (uint32_t a = 0; a < na; ++a) {
-        const auto it = index_of.find(std::string(reinterpret_cast<const char*>(t_addr[a].data()), 20));
-        if (it == index_of.end()) continue;
-        held_idx.push_back(it->second);
-        for (size_t j = 0; j < t_slots[a].size(); ++j) {
-            pv.slot_pre.insert(pv.slot_pre.end(), t_slots[a][j].begin(), t_slots[a][j].end());
-            pv.slot_trie.push_back(it->second);
-            pv.slot_flags.push_back(t_slot_flags[a][j]);
-        }
-    }
+    const HeldAccounts held = held_accounts(in, tk, pv);
+    const uint32_t na = (uint32_t)tk.addr.size();
     StateLayout lay;
     lay.ns = (uint32_t)pv.slot_trie.size(), lay.witness = true, lay.na = na;
     DevLeaves l;
     int32_t rc = state_leaves_dev(ws, st, in, lay, l, err, &pv);
     if (rc) return rc;
-
-    // ---- the state trie: the touched addresses' paths, exclusion proofs included ----
-    uint8_t *const d_apre = lay.apre, *const d_akeys = lay.tkeys, *const d_aflags = lay.aflags, *const d_hc = lay.thc;
-    uint32_t *const d_aoff = lay.aoff, *const d_held = lay.held;
-    if (na) {
-        SR_TRY(hipMemcpyAsync(d_apre, w.preimages.data(), 20 * (size_t)na, hipMemcpyHostToDevice, st));
-        SR_TRY(hipMemcpyAsync(d_aflags, t_flags.data(), na, hipMemcpyHostToDevice, st));
-        SR_TRY(launch_keccak256_fixed(d_apre, 20, 20, na, d_akeys, st));
-    }
-    hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)na + 1)), dim3(256), 0, st, na, d_aoff);
-    std::vector<uint8_t> hc(32 * held_idx.size());
-    if (!held_idx.empty()) {  // (before the forest pass: the copy rides on its synchronisations)
-        SR_TRY(hipMemcpyAsync(d_held, held_idx.data(), 4 * held_idx.size(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * held_idx.size())), dim3(256), 0, st, l.code_hash, d_held,
-                           (uint32_t)held_idx.size(), d_hc);
-        SR_TRY(hipMemcpyAsync(hc.data(), d_hc, hc.size(), hipMemcpyDeviceToHost, st));
-    }
-    std::vector<uint8_t> nodes;
-    rc = prove_forest_collect(ws, st, l.pairs(), ProveQueries{d_akeys, d_aoff, nullptr, d_aflags, na}, nodes, w.node_off, err);
+    std::vector<uint8_t> nodes, hc;
+    if ((rc = stage_touched_addresses(st, lay, l, tk, true, held.held_idx, hc, nullptr, err)) != PHANT_OK) return rc;
+    rc = prove_collect(ws, st, l.pairs(), ProveQueries{lay.tkeys, lay.aoff, nullptr, lay.aflags, na}, nodes, w.node_off, nullptr, err);
     if (rc) return rc;
     SR_TRY(hipMemcpyAsync(root_out, l.root, 32, hipMemcpyDeviceToHost, st));
     SR_TRY(hipStreamSynchronize(st));
@@ -737,28 +752,27 @@ int32_t state_witness_host(Workspaces& ws, hipStream_t st, const StateIn& in, co
     for (size_t i = 1; i < pv.node_off.size(); ++i) w.node_off.push_back(b0 + pv.node_off[i]);
     // "codes": every distinct non-empty code of a touched account the state holds, once, by the hash the pass computed
     std::unordered_set<std::string> seen_code;
-    for (size_t h = 0; h < held_idx.size(); ++h) {
-        const uint32_t i = held_idx[h];
-        const uint64_t len = code_off[i + 1] - code_off[i];
+    for (size_t h = 0; h < held.held_idx.size(); ++h) {
+        const uint32_t i = held.held_idx[h];
+        const uint64_t len = in.code_off[i + 1] - in.code_off[i];
         if (!len || !seen_code.emplace(reinterpret_cast<const char*>(hc.data() + 32 * h), 32).second) continue;
         const size_t c0 = w.codes.size();
         w.codes.resize(c0 + len);
-        std::memcpy(w.codes.data() + c0, code + code_off[i], len);
+        std::memcpy(w.codes.data() + c0, in.code + in.code_off[i], len);
         w.code_off.push_back((uint64_t)w.codes.size());
     }
     return PHANT_OK;
 }
 
-// phant_state_proofs: the same pass with both forests proven in the per-proof form (prove_forest_batch_collect) and the result laid
-// out as witness_parse_json lays out an EIP-1186 document: per touched account its account proof, then its storage proofs; the
-// declarations are the state's own.
+// phant_state_proofs: the same pass with both forests proven in the per-proof form and the result laid out as witness_parse_json
+// lays out an EIP-1186 document: per touched account its account proof, then its storage proofs; the declarations are the state's
+// own.
 int32_t state_proofs_host(Workspaces& ws, hipStream_t st, const StateIn& in, const ProveQueries& touched, Witness& w, uint8_t root_out[32],
                           std::string& err) {
     static const uint8_t EMPTY_ROOT[32] = {0x56, 0xe8, 0x1f, 0x17, 0x1b, 0xcc, 0x55, 0xa6, 0xff, 0x83, 0x45, 0xe6, 0x92, 0xc0, 0xf8, 0x6e,
                                            0x5b, 0x48, 0xe0, 0x1b, 0x99, 0x6c, 0xad, 0xc0, 0x01, 0x62, 0x2f, 0xb5, 0xe3, 0x63, 0xb4, 0x21};
     static const uint8_t EMPTY_CODE[32] = {0xc5, 0xd2, 0x46, 0x01, 0x86, 0xf7, 0x23, 0x3c, 0x92, 0x7e, 0x7d, 0xb2, 0xdc, 0xc7, 0x03, 0xc0,
                                            0xe5, 0x00, 0xb6, 0x53, 0xca, 0x82, 0x27, 0x3b, 0x7b, 0xfa, 0xd8, 0x04, 0x5d, 0x85, 0xa4, 0x70};
-    const uint32_t n = in.n;
     w = Witness();
     w.node_off.push_back(0);
     w.proof_first_node.push_back(0);
@@ -767,33 +781,16 @@ int32_t state_proofs_host(Workspaces& ws, hipStream_t st, const StateIn& in, con
     if (const int32_t bad = group_touched_keys(ProveQueries{touched.qkeys, touched.qkey_off, nullptr, nullptr, touched.n_queries}, "state_proofs", tk, err))
         return bad;
     const uint32_t na = (uint32_t)tk.addr.size();
-
-    // ---- which touched addresses the state holds; their slots are queries against that account's storage trie ----
-    constexpr uint32_t NOT_HELD = 0xffffffffu;
-    std::vector<uint32_t> index_of_touched(na, NOT_HELD), held_idx;
     StateProve pv;
     pv.per_proof = true;
-    if (n) {
-        std::unordered_map<std::string, uint32_t> index_of;
-        index_of.reserve((size_t)n * 2);
-        for (uint32_t i = 0; i < n; ++i) index_of.emplace(std::string(reinterpret_cast<const char*>(in.addrs + 20ull * i), 20), i);
-        for (uint32_t a = 0; a < na; ++a) {
-            const auto it = index_of.find(std::string(reinterpret_cast<const char*>(tk.addr[a].data()), 20));
-            if (it == index_of.end()) continue;
-            index_of_touched[a] = it->second;
-            held_idx.push_back(it->second);
-            for (const std::array<uint8_t, 32>& sl : tk.slots[a]) {
-                pv.slot_pre.insert(pv.slot_pre.end(), sl.begin(), sl.end());
-                pv.slot_trie.push_back(it->second);
-            }
-        }
-    }
+    const HeldAccounts held = held_accounts(in, tk, pv);
+    const std::vector<uint32_t>& index_of_touched = held.index_of_touched;
     // ---- the device passes: storage forest, then the state trie ----
-    std::vector<uint8_t> anodes, hc(32 * held_idx.size()), sr(32 * held_idx.size());
+    std::vector<uint8_t> anodes, hc, sr;
     std::vector<uint64_t> anode_off{0};
     std::vector<uint32_t> afirst((size_t)na + 1, 0);
     bool storage_proven = false;
-    if (n == 0) {
+    if (in.n == 0) {
         const int32_t rc = trie_forest_host(ws, st, HostPairs{}, root_out, err);  // (every key absent under the empty root: zero-node proofs)
         if (rc) return rc;
     } else {
@@ -803,23 +800,8 @@ int32_t state_proofs_host(Workspaces& ws, hipStream_t st, const StateIn& in, con
         int32_t rc = state_leaves_dev(ws, st, in, lay, l, err, &pv);
         if (rc) return rc;
         storage_proven = pv.first.size() == pv.slot_trie.size() + 1;  // (no live slot in the whole state: no forest pass, every storage root empty)
-        std::vector<uint8_t> addr_pre(20 * (size_t)na);
-        for (uint32_t a = 0; a < na; ++a) std::memcpy(addr_pre.data() + 20 * (size_t)a, tk.addr[a].data(), 20);
-        if (na) {
-            SR_TRY(hipMemcpyAsync(lay.apre, addr_pre.data(), addr_pre.size(), hipMemcpyHostToDevice, st));
-            SR_TRY(launch_keccak256_fixed(lay.apre, 20, 20, na, lay.tkeys, st));
-        }
-        hipLaunchKernelGGL(query_offsets_kernel, dim3(blocks((uint64_t)na + 1)), dim3(256), 0, st, na, lay.aoff);
-        if (!held_idx.empty()) {  // the held accounts' code hashes and storage roots, one after the other through the same 32 x na bytes
-            SR_TRY(hipMemcpyAsync(lay.held, held_idx.data(), 4 * held_idx.size(), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * held_idx.size())), dim3(256), 0, st, l.code_hash, lay.held,
-                               (uint32_t)held_idx.size(), lay.thc);
-            SR_TRY(hipMemcpyAsync(hc.data(), lay.thc, hc.size(), hipMemcpyDeviceToHost, st));
-            hipLaunchKernelGGL(gather32_kernel, dim3(blocks(32ull * held_idx.size())), dim3(256), 0, st, lay.sroots, lay.held,
-                               (uint32_t)held_idx.size(), lay.thc);
-            SR_TRY(hipMemcpyAsync(sr.data(), lay.thc, sr.size(), hipMemcpyDeviceToHost, st));
-        }
-        rc = prove_forest_batch_collect(ws, st, l.pairs(), ProveQueries{lay.tkeys, lay.aoff, nullptr, nullptr, na}, anodes, anode_off, afirst, err);
+        if ((rc = stage_touched_addresses(st, lay, l, tk, false, held.held_idx, hc, &sr, err)) != PHANT_OK) return rc;
+        rc = prove_collect(ws, st, l.pairs(), ProveQueries{lay.tkeys, lay.aoff, nullptr, nullptr, na}, anodes, anode_off, &afirst, err);
         if (rc) return rc;
         SR_TRY(hipMemcpyAsync(root_out, l.root, 32, hipMemcpyDeviceToHost, st));
         SR_TRY(hipStreamSynchronize(st));

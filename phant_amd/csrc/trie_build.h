@@ -68,53 +68,35 @@ int32_t trie_forest_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, std:
 int32_t trie_forest_nodes_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, uint8_t* d_out, uint8_t* roots_out, const RootNodes& out,
                               std::string& err);
 
-// Witness generation (phant_mpt_prove_nodeset; kernels in trie_prove.hip.h): the forest pass with its tables kept, then the hashed
-// nodes on the paths of the queried keys as a node set.  The queries and the caller's output buffers (any may be null: not wanted);
-// total_nodes / nodes_len are always written, node bytes and offsets only when both fit their capacities.
+// Witness generation (kernels in trie_prove.hip.h; the host driver's stages: DESIGN.md section 7d): the forest pass with its tables
+// kept, then the hashed nodes on the paths of the queried keys -- as one node set, every node once (phant_mpt_prove_nodeset), or
+// with per_proof as every query's own ordered node list, root first, the lists back to back in query order (phant_mpt_prove_batch;
+// q.q_flags is not read).  The queries and the caller's output buffers (any may be null: not wanted); total_nodes / nodes_len are
+// always written, node bytes and offsets only when both fit their capacities.  first_node is the set's trie_first_node (n_tries + 1,
+// written whether or not the rest fits) or the proofs' proof_first_node (n_queries + 1, written with the rest).
 struct ProveArgs {
     ProveQueries q;
+    bool per_proof = false;
     uint8_t* nodes = nullptr;
     uint64_t nodes_cap = 0;
-    uint64_t* node_off = nullptr;        // max_nodes + 1
+    uint64_t* node_off = nullptr;    // max_nodes + 1
     uint32_t max_nodes = 0;
-    uint32_t* trie_first_node = nullptr; // n_tries + 1
-    uint8_t* roots = nullptr;            // n_tries x 32
-    uint8_t* q_status = nullptr;         // n_queries
-    uint32_t total_nodes = 0;            // out
-    uint64_t nodes_len = 0;              // out
+    uint32_t* first_node = nullptr;  // n_tries + 1 | n_queries + 1
+    uint8_t* roots = nullptr;        // n_tries x 32
+    uint8_t* q_status = nullptr;     // n_queries
+    uint32_t total_nodes = 0;        // out
+    uint64_t nodes_len = 0;          // out
 };
 // every array in host memory
-int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveArgs& a, std::string& err);
+int32_t prove_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveArgs& a, std::string& err);
 // every array of `a` and of the forest in device memory (p.seg_first null with n_tries == 1: one trie; p.roots ignored: a.roots)
-int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, ProveArgs& a, std::string& err);
+int32_t prove_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, ProveArgs& a, std::string& err);
 
-// The per-proof form (phant_mpt_prove_batch): the same forest and queries (q.q_flags is not read), every query's own ordered node list,
-// root first, the lists back to back in query order.  total_nodes / nodes_len are always written; nodes, node_off and
-// proof_first_node only when the totals fit the capacities.
-struct ProveBatchArgs {
-    ProveQueries q;
-    uint8_t* nodes = nullptr;
-    uint64_t nodes_cap = 0;
-    uint64_t* node_off = nullptr;          // max_nodes + 1
-    uint32_t max_nodes = 0;
-    uint32_t* proof_first_node = nullptr;  // n_queries + 1
-    uint8_t* roots = nullptr;              // n_tries x 32
-    uint8_t* q_status = nullptr;           // n_queries
-    uint32_t total_nodes = 0;              // out
-    uint64_t nodes_len = 0;                // out
-};
-int32_t prove_batch_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveBatchArgs& a, std::string& err);
-int32_t prove_batch_dev(Workspaces& ws, hipStream_t st, const TriePairs& p, ProveBatchArgs& a, std::string& err);
-
-// the proving forest pass of a caller that owns ws.io (everything device-resident, p.seg_first / p.roots required): the emitted
-// nodes are appended to the host vectors (node_off: one entry per node so far + 1)
-int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
-                             std::vector<uint64_t>& node_off, std::string& err);
-
-// ... and its per-proof twin (phant_state_proofs): the proofs of the queries REPLACE the host vectors' contents (node_off:
-// total_nodes + 1 entries, first: n_queries + 1)
-int32_t prove_forest_batch_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
-                                   std::vector<uint64_t>& node_off, std::vector<uint32_t>& first, std::string& err);
+// the proving forest pass of a caller that owns ws.io (everything device-resident, p.seg_first / p.roots required): the set's nodes
+// are appended to the host vectors (node_off: one entry per node so far + 1); with `first` the per-proof form, whose proofs REPLACE
+// the vectors' contents (node_off: total_nodes + 1 entries, first: n_queries + 1)
+int32_t prove_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
+                      std::vector<uint64_t>& node_off, std::vector<uint32_t>* first, std::string& err);
 
 // calculateMPTRoot (src/blockchain/blockchain.zig:209-235) when !be32,
 // ExecutionPayload.toBlock keys (src/engine_api/execution_payload.zig:127-139)

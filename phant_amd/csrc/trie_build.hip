@@ -2112,456 +2112,335 @@ int32_t trie_root_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, st
     return rc;
 }
 
-// ---- witness generation (trie_prove.hip.h): the nodes on the paths of queried keys ----
+// ---- witness generation (trie_prove.hip.h): the nodes on the paths of queried keys, as one set or as a list per query ----
 namespace {
-struct ProveRun {
+// One prover call of either form, its stages in the order they run:
+//   plan_set      the build with its tables kept, locate / mark, sizes and offsets          -> the set's totals
+//   emit_set      the set's node bytes, offsets and the tries' first nodes
+//   plan_proofs   the set into the pvo arena, every query's node count and bytes, scanned   -> the proofs' totals
+//   write_proofs  every proof's place, then its bytes gathered from the set
+// A node-set call is plan_set -> emit_set; a per-proof call runs all four (plan_proofs does the second for itself).  plan() is the
+// first half of either, deliver() the second, with the caller's buffers in device or in host memory.  Every stage arms the guard
+// before it queues anything and the synchronisation that ends a stage lets it go: whatever the way out, no arena is handed to the
+// next call under a running kernel.
+struct ProveCall {
+    Workspaces& ws;
+    const hipStream_t st;
+    const bool per_proof;
+    const char* const call;  // the call's name in every error text
+    std::string& err;
+    StreamGuard guard;
     TrieDev t;
-    ProveDev p;
-    uint32_t total_nodes = 0;
+    ProveDev p{};
+    ProveBatchDev b{};
+    uint32_t set_nodes = 0;  // the node set: what emit_set writes
+    uint64_t set_len = 0;
+    uint32_t total_nodes = 0;  // what the caller is told: the set's, or those of all proofs together
     uint64_t nodes_len = 0;
-    const char* call = "prove_nodeset";  // the entry point's name in this run's error texts
-};
-}  // namespace
+    ProveCall(Workspaces& w, hipStream_t s, bool proofs, std::string& e)
+        : ws(w), st(s), per_proof(proofs), call(proofs ? "prove_batch" : "prove_nodeset"), err(e) {}
 
-// The build with its tables kept, then locate / mark, sizes and offsets.  Every pointer is device memory; pairs.seg_first and
-// pairs.roots are required here.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the emit pass would write.
-// keep_located: the per-proof form's (key, common prefix) of every query stay in the pv arena (run.p.qk / qc).
-static int32_t prove_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status, ProveRun& run,
-                          std::string& err, bool keep_located = false, const char* call = "prove_nodeset") {
-    run.call = call;
-    int32_t rc = forest_device(ws, st, pairs, err, RootNodes{}, &run.t);
-    if (rc) return rc;
-    const uint32_t n = pairs.n, n_queries = q.n_queries;
-    const size_t n1 = (size_t)n + 1;
-    const uint32_t tiles = n ? (uint32_t)((n1 + PV_TILE - 1u) / PV_TILE) : 0u;
-    ProveDev& p = run.p;
-    p = ProveDev{};
-    rc = lay_out_status(lay_out_arena(ws.pv, st, [&](auto& a) {
-        p.nmark = a.template take<uint32_t>(n1);
-        p.lmark = a.template take<uint8_t>(n1);
-        p.members = a.template take<uint8_t>(n1);
-        p.nbase = a.template take<uint32_t>(n1);
-        p.bbase = a.template take<unsigned long long>(n1);
-        p.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
-        p.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
-        p.flags = a.template take<uint32_t>(4);
-        if (keep_located) {
-            p.qk = a.template take<uint32_t>((size_t)n_queries + 1);
-            p.qc = a.template take<uint32_t>((size_t)n_queries + 1);
-        }
-    }), call, "pv", err);
-    if (rc) return rc;
-    p.tiles = tiles;
-    p.qkeys = q.qkeys;
-    p.qkey_off = q.qkey_off;
-    p.q_trie = q.q_trie;
-    p.q_flags = q.q_flags;
-    p.n_queries = n_queries;
-    p.q_status = d_q_status;
-    p.mailbox = ws.mailbox;
-    run.t.n_tries = pairs.n_tries;
-    run.t.seg_first = pairs.seg_first;
-    if (n) {
-        TB_TRY(hipMemsetAsync(p.nmark, 0, n1 * 4, st));
-        TB_TRY(hipMemsetAsync(p.lmark, 0, n1, st));
-    }
-    hipLaunchKernelGGL(prove_reset_kernel, dim3(1), dim3(64), 0, st, run.t, p);
-    if (n_queries) hipLaunchKernelGGL(prove_locate_kernel, dim3(blocks(n_queries)), dim3(256), 0, st, run.t, p);
-    if (n) {
-        if (q.q_flags && n_queries) hipLaunchKernelGGL(prove_sibling_kernel, dim3(blocks(n)), dim3(256), 0, st, run.t, p);
-        hipLaunchKernelGGL(prove_size_kernel, dim3(tiles), dim3(PV_TILE), 0, st, run.t, p);
-    }
-    hipLaunchKernelGGL(prove_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, p);
-    if (n) hipLaunchKernelGGL(prove_base_kernel, dim3(blocks(n1)), dim3(256), 0, st, run.t, p);
-    TB_TRY(hipGetLastError());
-    TB_TRY(hipStreamSynchronize(st));
-    std::atomic_thread_fence(std::memory_order_acquire);
-    const volatile uint32_t* const mb = ws.mailbox + MAILBOX_PROVE;
-    run.total_nodes = mb[0];
-    run.nodes_len = (uint64_t)mb[1] | ((uint64_t)mb[2] << 32);
-    if (mb[3] & PV_ERR_TRIE) {
-        err = std::string(call) + ": a q_trie index is not below n_tries";
-        return PHANT_E_INVALID_ARG;
-    }
-    return PHANT_OK;
-}
-
-// The writing pass: node bytes, node offsets (total_nodes + 1) and the tries' first nodes (n_tries + 1) into DEVICE buffers; any
-// may be null.  The caller has checked that the blob and the offsets hold run.nodes_len / run.total_nodes.  Synchronises.
-static int32_t prove_emit(hipStream_t st, ProveRun& run, uint8_t* d_nodes, uint64_t* d_node_off, uint32_t* d_first, std::string& err) {
-    const uint32_t n = run.t.n;
-    ProveDev& p = run.p;
-    p.nodes = d_nodes;
-    p.node_off = reinterpret_cast<unsigned long long*>(d_node_off);
-    p.trie_first_node = d_first;
-    if (d_first) {
-        if (n) hipLaunchKernelGGL(prove_first_kernel, dim3(blocks((uint64_t)run.t.n_tries + 1)), dim3(256), 0, st, run.t, p);
-        else TB_TRY(hipMemsetAsync(d_first, 0, ((size_t)run.t.n_tries + 1) * 4, st));
-    }
-    if (d_nodes || d_node_off) {
-        if (n) hipLaunchKernelGGL(prove_emit_kernel, dim3((uint32_t)(((uint64_t)n + 1 + 63u) / 64u)), dim3(64), 0, st, run.t, p);
-        else if (d_node_off) TB_TRY(hipMemsetAsync(d_node_off, 0, 8, st));
-    }
-    TB_TRY(hipGetLastError());
-    uint32_t flags = 0;
-    TB_TRY(hipMemcpyAsync(&flags, p.flags, 4, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipStreamSynchronize(st));
-    if (flags & PV_ERR_SCRATCH) {
-        err = std::string(run.call) + ": scratch overflow (internal bound too small)";
-        return PHANT_E_DEVICE;
-    }
-    return PHANT_OK;
-}
-
-// the node blob and its offsets at their exact sizes, in the pvo arena (either may be left out: nobody wants it)
-static int32_t lay_out_nodes(Workspaces& ws, hipStream_t st, const ProveRun& run, bool blob, bool offsets, uint8_t*& d_nodes, uint64_t*& d_noff,
-                             std::string& err) {
-    return lay_out_status(lay_out_arena(ws.pvo, st, [&](auto& a) {
-        if (blob) d_nodes = a.template take<uint8_t>(run.nodes_len + 16);
-        if (offsets) d_noff = a.template take<uint64_t>((size_t)run.total_nodes + 1);
-    }), "prove_nodeset", "pvo", err);
-}
-
-int32_t prove_nodeset_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, ProveArgs& a, std::string& err) {
-    TriePairs p = pairs;
-    p.roots = a.roots;
-    int32_t rc = fill_in_dev(ws, st, p, "prove_nodeset", err);
-    if (rc) return rc;
-    ProveRun run;
-    rc = prove_plan(ws, st, p, a.q, a.q_status, run, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    a.total_nodes = run.total_nodes;
-    a.nodes_len = run.nodes_len;
-    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
-    rc = prove_emit(st, run, fits ? a.nodes : nullptr, fits ? a.node_off : nullptr, a.trie_first_node, err);
-    if (rc) (void)hipStreamSynchronize(st);
-    return rc;
-}
-
-// The forest pass of a caller that owns ws.io (phant_state_witness): everything device-resident, p.seg_first and p.roots required.
-// The emitted nodes are APPENDED to the host vectors (node_off holds one entry per node so far + 1), so two forests that reuse
-// t1 / t2 / pv / pvo one after the other end up in one set.
-int32_t prove_forest_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
-                             std::vector<uint64_t>& node_off, std::string& err) {
-    ProveRun run;
-    int32_t rc = prove_plan(ws, st, p, q, nullptr, run, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (!run.total_nodes) return PHANT_OK;
-    uint8_t* d_nodes = nullptr;
-    uint64_t* d_noff = nullptr;
-    if ((rc = lay_out_nodes(ws, st, run, true, true, d_nodes, d_noff, err)) != PHANT_OK) return rc;
-    rc = prove_emit(st, run, d_nodes, d_noff, nullptr, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    const size_t b0 = nodes.size(), k0 = node_off.size();  // (node_off[k0 - 1] == b0)
-    nodes.resize(b0 + run.nodes_len);
-    node_off.resize(k0 + run.total_nodes);
-    std::vector<uint64_t> rel((size_t)run.total_nodes + 1);
-    TB_TRY(hipMemcpyAsync(nodes.data() + b0, d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipMemcpyAsync(rel.data(), d_noff, rel.size() * 8, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipStreamSynchronize(st));
-    for (uint32_t i = 0; i < run.total_nodes; ++i) node_off[k0 + i] = b0 + rel[i + 1];
-    return PHANT_OK;
-}
-
-int32_t prove_nodeset_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveArgs& a, std::string& err) {
-    const ProveQueries& q = a.q;
-    const uint32_t nq = q.n_queries, n_tries = h.n_tries;
-    const uint64_t qb = nq ? q.qkey_off[nq] - q.qkey_off[0] : 0;
-    uint8_t *d_roots = nullptr, *d_qkeys = nullptr, *d_qflags = nullptr, *d_qstatus = nullptr;
-    uint32_t *d_qoff = nullptr, *d_qtrie = nullptr, *d_first = nullptr;
-    // The queries ride with the pairs: their arrays lie behind the five of the forest and in front of the outputs, so that a small
-    // witness's inputs cross the bus in ONE copy.  The outputs keep a copy each: the prover's kernels do not write into the mirror.
-    const StagedPairs in = stage_pairs(ws, st, h, "prove_nodeset", err, [&]() -> int32_t {
-        for (uint32_t j = 0; j < nq; ++j) {
-            if (q.qkey_off[j + 1] < q.qkey_off[j]) return err = "query key offsets not monotone", PHANT_E_INVALID_ARG;
-            if (q.q_trie && q.q_trie[j] >= n_tries)
-                return err = "prove_nodeset: q_trie[" + std::to_string(j) + "] is not below n_tries", PHANT_E_INVALID_ARG;
-        }
-        return PHANT_OK;
-    }, [&](auto& io) -> const void* {
-        d_qkeys = io.template take<uint8_t>(qb + 16);
-        d_qoff = io.template take<uint32_t>((size_t)nq + 1);
-        d_qtrie = io.template take<uint32_t>((size_t)nq + 1);
-        d_qflags = io.template take<uint8_t>((size_t)nq + 1);
-        d_roots = io.template take<uint8_t>((size_t)n_tries * 32);
-        d_qstatus = io.template take<uint8_t>((size_t)nq + 1);
-        d_first = io.template take<uint32_t>((size_t)n_tries + 1);
-        return d_qflags ? d_qflags + nq + 1 : nullptr;  // (the sizer hands out no addresses)
-    }, [&](StagedInputs& ins) {
-        ins.put(d_qkeys, qb ? q.qkeys + q.qkey_off[0] : nullptr, qb);
-        std::vector<uint32_t> qo;
-        uint32_t* rel = ins.twin(d_qoff);
-        if (!ins.staged) qo.resize((size_t)nq + 1), rel = qo.data();
-        if (rel) {
-            rel[0] = 0;
-            for (uint32_t j = 0; j <= nq && nq; ++j) rel[j] = q.qkey_off[j] - q.qkey_off[0];
-        }
-        if (!ins.staged) ins.put(d_qoff, rel, ((size_t)nq + 1) * 4);  // (a pageable source: the copy is taken when put() returns)
-        ins.put(d_qtrie, q.q_trie, (size_t)nq * 4);
-        ins.put(d_qflags, q.q_flags, nq);
-    });
-    if (in.rc) return in.rc;
-    TriePairs p = in.pairs;
-    p.roots = d_roots;
-    ProveRun run;
-    int32_t rc = prove_plan(ws, st, p, ProveQueries{d_qkeys, d_qoff, q.q_trie ? d_qtrie : nullptr, q.q_flags ? d_qflags : nullptr, nq}, d_qstatus, run, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    a.total_nodes = run.total_nodes;
-    a.nodes_len = run.nodes_len;
-    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
-    uint8_t* d_nodes = nullptr;
-    uint64_t* d_noff = nullptr;
-    if (fits && (a.nodes || a.node_off) && (rc = lay_out_nodes(ws, st, run, a.nodes, a.node_off, d_nodes, d_noff, err)) != PHANT_OK) return rc;
-    rc = prove_emit(st, run, d_nodes, d_noff, a.trie_first_node ? d_first : nullptr, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (d_nodes && run.nodes_len) TB_TRY(hipMemcpyAsync(a.nodes, d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
-    if (d_noff) TB_TRY(hipMemcpyAsync(a.node_off, d_noff, ((size_t)run.total_nodes + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (a.trie_first_node) TB_TRY(hipMemcpyAsync(a.trie_first_node, d_first, ((size_t)n_tries + 1) * 4, hipMemcpyDeviceToHost, st));
-    if (a.roots) TB_TRY(hipMemcpyAsync(a.roots, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
-    if (a.q_status && nq) TB_TRY(hipMemcpyAsync(a.q_status, d_qstatus, nq, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipStreamSynchronize(st));
-    return PHANT_OK;
-}
-
-// ---- the per-proof form (phant_mpt_prove_batch): every query's ordered node list, cut from the set ----
-namespace {
-struct ProveBatchRun {
-    ProveRun set;
-    ProveBatchDev b;
-    uint32_t total_nodes = 0;
-    uint64_t nodes_len = 0;
-};
-}  // namespace
-
-// The build and the node set as prove_plan / prove_emit make them -- the set into the pvo arena, not to the caller --, then every
-// query's node count and bytes and their scan.  Ends with a synchronisation: run.total_nodes / run.nodes_len are what the writing
-// passes would lay out.  Every pointer is device memory; pairs.seg_first and pairs.roots are required.
-static int32_t prove_batch_plan(Workspaces& ws, hipStream_t st, const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status,
-                                ProveBatchRun& run, std::string& err) {
-    int32_t rc = prove_plan(ws, st, pairs, ProveQueries{q.qkeys, q.qkey_off, q.q_trie, nullptr, q.n_queries}, d_q_status, run.set, err, true, "prove_batch");
-    if (rc) return rc;
-    ProveBatchDev& b = run.b;
-    b = ProveBatchDev{};
-    b.n_queries = q.n_queries;
-    if (!run.set.total_nodes) return PHANT_OK;  // no keys, no queries, or queries of empty tries only: every proof is empty
-    const size_t nq1 = (size_t)q.n_queries + 1;
-    const uint32_t tiles = (uint32_t)((nq1 + PV_TILE - 1u) / PV_TILE);
-    uint8_t* d_set = nullptr;
-    uint64_t* d_set_off = nullptr;
-    rc = lay_out_status(lay_out_arena(ws.pvo, st, [&](auto& a) {
-        d_set = a.template take<uint8_t>(run.set.nodes_len + 16);
-        d_set_off = a.template take<uint64_t>((size_t)run.set.total_nodes + 1);
-        b.q_cnt = a.template take<uint32_t>(nq1);
-        b.q_bytes = a.template take<unsigned long long>(nq1);
-        b.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
-        b.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
-    }), "prove_batch", "pvo", err);
-    if (rc) return rc;
-    if ((rc = prove_emit(st, run.set, d_set, d_set_off, nullptr, err)) != PHANT_OK) return rc;
-    b.set_nodes = d_set;
-    b.set_off = reinterpret_cast<const unsigned long long*>(d_set_off);
-    b.tiles = tiles;
-    b.mailbox = ws.mailbox;
-    hipLaunchKernelGGL(prove_batch_count_kernel, dim3(tiles), dim3(PV_TILE), 0, st, run.set.t, run.set.p, b);
-    hipLaunchKernelGGL(prove_batch_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, b);
-    TB_TRY(hipGetLastError());
-    TB_TRY(hipStreamSynchronize(st));
-    std::atomic_thread_fence(std::memory_order_acquire);
-    const volatile uint32_t* const mb = ws.mailbox + MAILBOX_PROVE_BATCH;
-    const uint64_t total = (uint64_t)mb[0] | ((uint64_t)mb[1] << 32);
-    if (total > 0xffffffffull) {
-        err = "prove_batch: more than 2^32 - 1 nodes in all proofs";
-        return PHANT_E_UNSUPPORTED;
-    }
-    run.total_nodes = (uint32_t)total;
-    run.nodes_len = (uint64_t)mb[2] | ((uint64_t)mb[3] << 32);
-    return PHANT_OK;
-}
-
-// The writing passes into DEVICE buffers: node offsets (total_nodes + 1) and the proofs' first nodes (n_queries + 1), then the bytes.
-// d_nodes / d_first may be null; d_node_off and d_src (total_nodes words of the prover's own) only when there are no nodes at all.
-// The caller has checked the capacities.  Does not synchronise.
-static int32_t prove_batch_write(hipStream_t st, ProveBatchRun& run, uint8_t* d_nodes, uint64_t* d_node_off, uint32_t* d_first, uint32_t* d_src,
-                                 std::string& err) {
-    ProveBatchDev& b = run.b;
-    if (!run.total_nodes) {
-        if (d_first) TB_TRY(hipMemsetAsync(d_first, 0, ((size_t)b.n_queries + 1) * 4, st));
-        if (d_node_off) TB_TRY(hipMemsetAsync(d_node_off, 0, 8, st));
+    int32_t synchronise() {
+        TB_TRY(hipStreamSynchronize(st));
+        guard.armed = false;
         return PHANT_OK;
     }
-    b.total_nodes = run.total_nodes;
-    b.src = d_src;
-    b.node_off = reinterpret_cast<unsigned long long*>(d_node_off);
-    b.proof_first_node = d_first;
-    b.nodes = d_nodes;
-    hipLaunchKernelGGL(prove_batch_place_kernel, dim3(blocks((uint64_t)b.n_queries + 1)), dim3(256), 0, st, run.set.t, run.set.p, b);
-    if (d_nodes) hipLaunchKernelGGL(prove_batch_gather_kernel, dim3((run.total_nodes + 3u) / 4u), dim3(256), 0, st, b);
-    TB_TRY(hipGetLastError());
-    return PHANT_OK;
-}
 
-int32_t prove_batch_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, ProveBatchArgs& a, std::string& err) {
-    TriePairs p = pairs;
-    p.roots = a.roots;
-    int32_t rc = fill_in_dev(ws, st, p, "prove_batch", err);
-    if (rc) return rc;
-    ProveBatchRun run;
-    rc = prove_batch_plan(ws, st, p, a.q, a.q_status, run, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    a.total_nodes = run.total_nodes;
-    a.nodes_len = run.nodes_len;
-    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
-    if (fits && (a.nodes || a.node_off || a.proof_first_node)) {
-        uint32_t* d_src = nullptr;
-        uint64_t* d_off = a.node_off;
-        if (run.total_nodes) {
-            rc = lay_out_status(lay_out_arena(ws.pvb, st, [&](auto& ar) {
-                d_src = ar.template take<uint32_t>(run.total_nodes);
-                if (!a.node_off) d_off = ar.template take<uint64_t>((size_t)run.total_nodes + 1);
-            }), "prove_batch", "pvb", err);
-            if (rc) {
-                (void)hipStreamSynchronize(st);
-                return rc;
+    // Every pointer is device memory; pairs.seg_first and pairs.roots are required.  A per-proof call reads no q_flags and keeps the
+    // (key, common prefix) of every query in the pv arena (p.qk / qc).  Ends with a synchronisation.
+    int32_t plan_set(const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status) {
+        guard.arm(st);
+        int32_t rc = forest_device(ws, st, pairs, err, RootNodes{}, &t);
+        if (rc) return rc;
+        const uint32_t n = pairs.n, n_queries = q.n_queries;
+        const size_t n1 = (size_t)n + 1;
+        const uint32_t tiles = n ? (uint32_t)((n1 + PV_TILE - 1u) / PV_TILE) : 0u;
+        rc = lay_out_status(lay_out_arena(ws.pv, st, [&](auto& a) {
+            p.nmark = a.template take<uint32_t>(n1);
+            p.lmark = a.template take<uint8_t>(n1);
+            p.members = a.template take<uint8_t>(n1);
+            p.nbase = a.template take<uint32_t>(n1);
+            p.bbase = a.template take<unsigned long long>(n1);
+            p.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
+            p.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
+            p.flags = a.template take<uint32_t>(4);
+            if (per_proof) {
+                p.qk = a.template take<uint32_t>((size_t)n_queries + 1);
+                p.qc = a.template take<uint32_t>((size_t)n_queries + 1);
             }
+        }), call, "pv", err);
+        if (rc) return rc;
+        p.tiles = tiles;
+        p.qkeys = q.qkeys;
+        p.qkey_off = q.qkey_off;
+        p.q_trie = q.q_trie;
+        p.q_flags = per_proof ? nullptr : q.q_flags;
+        p.n_queries = n_queries;
+        p.q_status = d_q_status;
+        p.mailbox = ws.mailbox;
+        t.n_tries = pairs.n_tries;
+        t.seg_first = pairs.seg_first;
+        if (n) {
+            TB_TRY(hipMemsetAsync(p.nmark, 0, n1 * 4, st));
+            TB_TRY(hipMemsetAsync(p.lmark, 0, n1, st));
         }
-        rc = prove_batch_write(st, run, a.nodes, d_off, a.proof_first_node, d_src, err);
-        if (rc) {
-            (void)hipStreamSynchronize(st);
-            return rc;
+        hipLaunchKernelGGL(prove_reset_kernel, dim3(1), dim3(64), 0, st, t, p);
+        if (n_queries) hipLaunchKernelGGL(prove_locate_kernel, dim3(blocks(n_queries)), dim3(256), 0, st, t, p);
+        if (n) {
+            if (p.q_flags && n_queries) hipLaunchKernelGGL(prove_sibling_kernel, dim3(blocks(n)), dim3(256), 0, st, t, p);
+            hipLaunchKernelGGL(prove_size_kernel, dim3(tiles), dim3(PV_TILE), 0, st, t, p);
         }
+        hipLaunchKernelGGL(prove_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, p);
+        if (n) hipLaunchKernelGGL(prove_base_kernel, dim3(blocks(n1)), dim3(256), 0, st, t, p);
+        TB_TRY(hipGetLastError());
+        if ((rc = synchronise()) != PHANT_OK) return rc;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const volatile uint32_t* const mb = ws.mailbox + MAILBOX_PROVE;
+        total_nodes = set_nodes = mb[0];
+        nodes_len = set_len = (uint64_t)mb[1] | ((uint64_t)mb[2] << 32);
+        if (mb[3] & PV_ERR_TRIE) {
+            err = std::string(call) + ": a q_trie index is not below n_tries";
+            return PHANT_E_INVALID_ARG;
+        }
+        return PHANT_OK;
     }
-    TB_TRY(hipStreamSynchronize(st));
-    return PHANT_OK;
-}
 
-int32_t prove_batch_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveBatchArgs& a, std::string& err) {
-    const ProveQueries& q = a.q;
+    // Node bytes, node offsets (set_nodes + 1) and the tries' first nodes (n_tries + 1) into DEVICE buffers; any may be null.  The
+    // caller has checked that the blob and the offsets hold set_len / set_nodes.  Synchronises.
+    int32_t emit_set(uint8_t* d_nodes, uint64_t* d_node_off, uint32_t* d_first) {
+        guard.arm(st);
+        const uint32_t n = t.n;
+        p.nodes = d_nodes;
+        p.node_off = reinterpret_cast<unsigned long long*>(d_node_off);
+        p.trie_first_node = d_first;
+        if (d_first) {
+            if (n) hipLaunchKernelGGL(prove_first_kernel, dim3(blocks((uint64_t)t.n_tries + 1)), dim3(256), 0, st, t, p);
+            else TB_TRY(hipMemsetAsync(d_first, 0, ((size_t)t.n_tries + 1) * 4, st));
+        }
+        if (d_nodes || d_node_off) {
+            if (n) hipLaunchKernelGGL(prove_emit_kernel, dim3((uint32_t)(((uint64_t)n + 1 + 63u) / 64u)), dim3(64), 0, st, t, p);
+            else if (d_node_off) TB_TRY(hipMemsetAsync(d_node_off, 0, 8, st));
+        }
+        TB_TRY(hipGetLastError());
+        uint32_t flags = 0;
+        TB_TRY(hipMemcpyAsync(&flags, p.flags, 4, hipMemcpyDeviceToHost, st));
+        const int32_t rc = synchronise();
+        if (rc) return rc;
+        if (flags & PV_ERR_SCRATCH) {
+            err = std::string(call) + ": scratch overflow (internal bound too small)";
+            return PHANT_E_DEVICE;
+        }
+        return PHANT_OK;
+    }
+
+    // The set as emit_set makes it -- into the pvo arena, not to the caller --, then every query's node count and bytes and their
+    // scan.  Ends with a synchronisation: total_nodes / nodes_len are what write_proofs would lay out.
+    int32_t plan_proofs() {
+        b.n_queries = p.n_queries;
+        total_nodes = 0, nodes_len = 0;
+        if (!set_nodes) return PHANT_OK;  // no keys, no queries, or queries of empty tries only: every proof is empty
+        const size_t nq1 = (size_t)p.n_queries + 1;
+        const uint32_t tiles = (uint32_t)((nq1 + PV_TILE - 1u) / PV_TILE);
+        uint8_t* d_set = nullptr;
+        uint64_t* d_set_off = nullptr;
+        int32_t rc = lay_out_status(lay_out_arena(ws.pvo, st, [&](auto& a) {
+            d_set = a.template take<uint8_t>(set_len + 16);
+            d_set_off = a.template take<uint64_t>((size_t)set_nodes + 1);
+            b.q_cnt = a.template take<uint32_t>(nq1);
+            b.q_bytes = a.template take<unsigned long long>(nq1);
+            b.tile_cnt = a.template take<uint32_t>((size_t)tiles + 1);
+            b.tile_bytes = a.template take<unsigned long long>((size_t)tiles + 1);
+        }), call, "pvo", err);
+        if (rc) return rc;
+        if ((rc = emit_set(d_set, d_set_off, nullptr)) != PHANT_OK) return rc;
+        guard.arm(st);
+        b.set_nodes = d_set;
+        b.set_off = reinterpret_cast<const unsigned long long*>(d_set_off);
+        b.tiles = tiles;
+        b.mailbox = ws.mailbox;
+        hipLaunchKernelGGL(prove_batch_count_kernel, dim3(tiles), dim3(PV_TILE), 0, st, t, p, b);
+        hipLaunchKernelGGL(prove_batch_scan_kernel, dim3(1), dim3(PV_TILE), 0, st, b);
+        TB_TRY(hipGetLastError());
+        if ((rc = synchronise()) != PHANT_OK) return rc;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const volatile uint32_t* const mb = ws.mailbox + MAILBOX_PROVE_BATCH;
+        const uint64_t total = (uint64_t)mb[0] | ((uint64_t)mb[1] << 32);
+        if (total > 0xffffffffull) {
+            err = "prove_batch: more than 2^32 - 1 nodes in all proofs";
+            return PHANT_E_UNSUPPORTED;
+        }
+        total_nodes = (uint32_t)total;
+        nodes_len = (uint64_t)mb[2] | ((uint64_t)mb[3] << 32);
+        return PHANT_OK;
+    }
+
+    // Into DEVICE buffers: node offsets (total_nodes + 1) and the proofs' first nodes (n_queries + 1), then the bytes.  d_nodes /
+    // d_first may be null; d_node_off and d_src (total_nodes words of the prover's own) only when there are no nodes at all.  The
+    // caller has checked the capacities.  Does not synchronise.
+    int32_t write_proofs(uint8_t* d_nodes, uint64_t* d_node_off, uint32_t* d_first, uint32_t* d_src) {
+        guard.arm(st);
+        if (!total_nodes) {
+            if (d_first) TB_TRY(hipMemsetAsync(d_first, 0, ((size_t)b.n_queries + 1) * 4, st));
+            if (d_node_off) TB_TRY(hipMemsetAsync(d_node_off, 0, 8, st));
+            return PHANT_OK;
+        }
+        b.total_nodes = total_nodes;
+        b.src = d_src;
+        b.node_off = reinterpret_cast<unsigned long long*>(d_node_off);
+        b.proof_first_node = d_first;
+        b.nodes = d_nodes;
+        hipLaunchKernelGGL(prove_batch_place_kernel, dim3(blocks((uint64_t)b.n_queries + 1)), dim3(256), 0, st, t, p, b);
+        if (d_nodes) hipLaunchKernelGGL(prove_batch_gather_kernel, dim3((total_nodes + 3u) / 4u), dim3(256), 0, st, b);
+        TB_TRY(hipGetLastError());
+        return PHANT_OK;
+    }
+
+    int32_t plan(const TriePairs& pairs, const ProveQueries& q, uint8_t* d_q_status) {
+        const int32_t rc = plan_set(pairs, q, d_q_status);
+        return rc == PHANT_OK && per_proof ? plan_proofs() : rc;
+    }
+
+    // The second half: node bytes, node offsets and the first-node table to the caller's buffers, each only if wanted.  Bytes and
+    // offsets are written when the totals fit a.nodes_cap / a.max_nodes; the set's table is written in any case, the proofs' only
+    // with them.  host: the caller's buffers are host memory and the results pass through buffers of the prover's own; else they are
+    // written where they are wanted.  The prover's own are carved in one place for every form, from the pvo arena for the set and
+    // from pvb for the proofs: the blob and the proofs' table of a host caller; the offsets when they are wanted or the gather needs
+    // them and the caller has no device buffer for them; the gather's source table, total_nodes words.  (A device call without
+    // nodes therefore carves nothing, a host call without nodes its offsets' one entry and its table: the memsets' targets.)
+    // d_first: the set's table of a host caller that has room for it already (its io arena), else null.  A device call ends
+    // synchronised; a host call leaves its copies in the stream for the caller to add to and to synchronise.
+    int32_t deliver(const ProveArgs& a, bool host, uint32_t* d_first) {
+        const bool write = total_nodes <= a.max_nodes && nodes_len <= a.nodes_cap && (a.nodes || a.node_off || (per_proof && a.first_node));
+        uint8_t* d_nodes = host || !write ? nullptr : a.nodes;
+        uint64_t* d_off = host || !write ? nullptr : a.node_off;
+        uint32_t* d_src = nullptr;
+        if (!host) d_first = a.first_node;
+        int32_t rc = PHANT_OK;
+        if (write && (host || per_proof)) {
+            const bool own_off = host ? a.node_off || (per_proof && total_nodes) : total_nodes && !a.node_off;
+            rc = lay_out_status(lay_out_arena(per_proof ? ws.pvb : ws.pvo, st, [&](auto& ar) {
+                if (host && a.nodes) d_nodes = ar.template take<uint8_t>(nodes_len + 16);
+                if (own_off) d_off = ar.template take<uint64_t>((size_t)total_nodes + 1);
+                if (host && per_proof && a.first_node) d_first = ar.template take<uint32_t>((size_t)p.n_queries + 1);
+                if (per_proof && total_nodes) d_src = ar.template take<uint32_t>(total_nodes);
+            }), call, per_proof ? "pvb" : "pvo", err);
+            if (rc) return rc;
+        }
+        if (!per_proof) rc = emit_set(d_nodes, d_off, a.first_node ? d_first : nullptr);
+        else if (write) rc = write_proofs(d_nodes, d_off, d_first, d_src);
+        if (rc) return rc;
+        if (!host) return per_proof ? synchronise() : PHANT_OK;
+        guard.arm(st);
+        if (write && a.nodes && nodes_len) TB_TRY(hipMemcpyAsync(a.nodes, d_nodes, nodes_len, hipMemcpyDeviceToHost, st));
+        if (write && a.node_off) TB_TRY(hipMemcpyAsync(a.node_off, d_off, ((size_t)total_nodes + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (a.first_node && (write || !per_proof))
+            TB_TRY(hipMemcpyAsync(a.first_node, d_first, ((size_t)(per_proof ? p.n_queries : t.n_tries) + 1) * 4, hipMemcpyDeviceToHost, st));
+        return PHANT_OK;
+    }
+};
+
+// A host call's queries and small outputs in the io arena.  They ride with the pairs: the queries' arrays lie behind the five of the
+// forest and in front of the outputs, so that a small call's inputs cross the bus in ONE copy.  The outputs keep a copy each: the
+// prover's kernels do not write into the mirror.
+struct StagedQueries {
+    uint8_t *qkeys = nullptr, *qflags = nullptr, *roots = nullptr, *qstatus = nullptr;
+    uint32_t *qoff = nullptr, *qtrie = nullptr, *first = nullptr;  // (qflags, first = the tries' first nodes: the set form's)
+};
+// stage_pairs with the validation, the carve and the rebase-and-put of the queries q (host view)
+StagedPairs stage_queries(Workspaces& ws, hipStream_t st, const HostPairs& h, const ProveQueries& q, const ProveCall& c, StagedQueries& d) {
     const uint32_t nq = q.n_queries, n_tries = h.n_tries;
     const uint64_t qb = nq ? q.qkey_off[nq] - q.qkey_off[0] : 0;
-    uint8_t *d_roots = nullptr, *d_qkeys = nullptr, *d_qstatus = nullptr;
-    uint32_t *d_qoff = nullptr, *d_qtrie = nullptr;
-    // the queries ride with the pairs, as in prove_nodeset_host
-    const StagedPairs in = stage_pairs(ws, st, h, "prove_batch", err, [&]() -> int32_t {
+    std::string& err = c.err;
+    return stage_pairs(ws, st, h, c.call, err, [&]() -> int32_t {
         for (uint32_t j = 0; j < nq; ++j) {
             if (q.qkey_off[j + 1] < q.qkey_off[j]) return err = "query key offsets not monotone", PHANT_E_INVALID_ARG;
             if (q.q_trie && q.q_trie[j] >= n_tries)
-                return err = "prove_batch: q_trie[" + std::to_string(j) + "] is not below n_tries", PHANT_E_INVALID_ARG;
+                return err = std::string(c.call) + ": q_trie[" + std::to_string(j) + "] is not below n_tries", PHANT_E_INVALID_ARG;
         }
         return PHANT_OK;
     }, [&](auto& io) -> const void* {
-        d_qkeys = io.template take<uint8_t>(qb + 16);
-        d_qoff = io.template take<uint32_t>((size_t)nq + 1);
-        d_qtrie = io.template take<uint32_t>((size_t)nq + 1);
-        d_roots = io.template take<uint8_t>((size_t)n_tries * 32);
-        d_qstatus = io.template take<uint8_t>((size_t)nq + 1);
-        return d_qtrie ? d_qtrie + nq + 1 : nullptr;  // (the sizer hands out no addresses)
+        d.qkeys = io.template take<uint8_t>(qb + 16);
+        d.qoff = io.template take<uint32_t>((size_t)nq + 1);
+        d.qtrie = io.template take<uint32_t>((size_t)nq + 1);
+        const void* end = d.qtrie ? d.qtrie + nq + 1 : nullptr;  // (the end of the inputs; the sizer hands out no addresses)
+        if (!c.per_proof) {
+            d.qflags = io.template take<uint8_t>((size_t)nq + 1);
+            end = d.qflags ? d.qflags + nq + 1 : nullptr;
+        }
+        d.roots = io.template take<uint8_t>((size_t)n_tries * 32);
+        d.qstatus = io.template take<uint8_t>((size_t)nq + 1);
+        if (!c.per_proof) d.first = io.template take<uint32_t>((size_t)n_tries + 1);
+        return end;
     }, [&](StagedInputs& ins) {
-        ins.put(d_qkeys, qb ? q.qkeys + q.qkey_off[0] : nullptr, qb);
+        ins.put(d.qkeys, qb ? q.qkeys + q.qkey_off[0] : nullptr, qb);
         std::vector<uint32_t> qo;
-        uint32_t* rel = ins.twin(d_qoff);
+        uint32_t* rel = ins.twin(d.qoff);
         if (!ins.staged) qo.resize((size_t)nq + 1), rel = qo.data();
         if (rel) {
             rel[0] = 0;
             for (uint32_t j = 0; j <= nq && nq; ++j) rel[j] = q.qkey_off[j] - q.qkey_off[0];
         }
-        if (!ins.staged) ins.put(d_qoff, rel, ((size_t)nq + 1) * 4);  // (a pageable source: the copy is taken when put() returns)
-        ins.put(d_qtrie, q.q_trie, (size_t)nq * 4);
+        if (!ins.staged) ins.put(d.qoff, rel, ((size_t)nq + 1) * 4);  // (a pageable source: the copy is taken when put() returns)
+        ins.put(d.qtrie, q.q_trie, (size_t)nq * 4);
+        if (!c.per_proof) ins.put(d.qflags, q.q_flags, nq);
     });
+}
+}  // namespace
+
+int32_t prove_host(Workspaces& ws, hipStream_t st, const HostPairs& h, ProveArgs& a, std::string& err) {
+    const ProveQueries& q = a.q;
+    ProveCall c(ws, st, a.per_proof, err);
+    StagedQueries d;
+    const StagedPairs in = stage_queries(ws, st, h, q, c, d);
     if (in.rc) return in.rc;
     TriePairs p = in.pairs;
-    p.roots = d_roots;
-    ProveBatchRun run;
-    int32_t rc = prove_batch_plan(ws, st, p, ProveQueries{d_qkeys, d_qoff, q.q_trie ? d_qtrie : nullptr, nullptr, nq}, d_qstatus, run, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    a.total_nodes = run.total_nodes;
-    a.nodes_len = run.nodes_len;
-    const bool fits = run.total_nodes <= a.max_nodes && run.nodes_len <= a.nodes_cap;
-    if (fits && (a.nodes || a.node_off || a.proof_first_node)) {
-        uint8_t* d_nodes = nullptr;
-        uint64_t* d_off = nullptr;
-        uint32_t *d_first = nullptr, *d_src = nullptr;
-        rc = lay_out_status(lay_out_arena(ws.pvb, st, [&](auto& ar) {
-            d_off = ar.template take<uint64_t>((size_t)run.total_nodes + 1);
-            d_src = ar.template take<uint32_t>((size_t)run.total_nodes + 1);
-            if (a.proof_first_node) d_first = ar.template take<uint32_t>((size_t)nq + 1);
-            if (a.nodes) d_nodes = ar.template take<uint8_t>(run.nodes_len + 16);
-        }), "prove_batch", "pvb", err);
-        if (rc) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
-        rc = prove_batch_write(st, run, d_nodes, d_off, d_first, d_src, err);
-        if (rc) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
-        if (a.nodes && run.nodes_len) TB_TRY(hipMemcpyAsync(a.nodes, d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
-        if (a.node_off) TB_TRY(hipMemcpyAsync(a.node_off, d_off, ((size_t)run.total_nodes + 1) * 8, hipMemcpyDeviceToHost, st));
-        if (a.proof_first_node) TB_TRY(hipMemcpyAsync(a.proof_first_node, d_first, ((size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (a.roots) TB_TRY(hipMemcpyAsync(a.roots, d_roots, (size_t)n_tries * 32, hipMemcpyDeviceToHost, st));
-    if (a.q_status && nq) TB_TRY(hipMemcpyAsync(a.q_status, d_qstatus, nq, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipStreamSynchronize(st));
-    return PHANT_OK;
+    p.roots = d.roots;
+    int32_t rc = c.plan(p, ProveQueries{d.qkeys, d.qoff, q.q_trie ? d.qtrie : nullptr, q.q_flags ? d.qflags : nullptr, q.n_queries}, d.qstatus);
+    if (rc) return rc;
+    a.total_nodes = c.total_nodes;
+    a.nodes_len = c.nodes_len;
+    if ((rc = c.deliver(a, true, d.first)) != PHANT_OK) return rc;
+    if (a.roots) TB_TRY(hipMemcpyAsync(a.roots, d.roots, (size_t)h.n_tries * 32, hipMemcpyDeviceToHost, st));
+    if (a.q_status && q.n_queries) TB_TRY(hipMemcpyAsync(a.q_status, d.qstatus, q.n_queries, hipMemcpyDeviceToHost, st));
+    return c.synchronise();
 }
 
-// The per-proof forest pass of a caller that owns ws.io (phant_state_proofs): everything device-resident, p.seg_first and p.roots
-// required.  The proofs REPLACE the host vectors' contents: node_off holds total_nodes + 1 entries, first n_queries + 1.
-int32_t prove_forest_batch_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
-                                   std::vector<uint64_t>& node_off, std::vector<uint32_t>& first, std::string& err) {
-    ProveBatchRun run;
-    int32_t rc = prove_batch_plan(ws, st, p, q, nullptr, run, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
+int32_t prove_dev(Workspaces& ws, hipStream_t st, const TriePairs& pairs, ProveArgs& a, std::string& err) {
+    ProveCall c(ws, st, a.per_proof, err);
+    TriePairs p = pairs;
+    p.roots = a.roots;
+    int32_t rc = fill_in_dev(ws, st, p, c.call, err);
+    if (rc == PHANT_OK) rc = c.plan(p, a.q, a.q_status);
+    if (rc) return rc;
+    a.total_nodes = c.total_nodes;
+    a.nodes_len = c.nodes_len;
+    return c.deliver(a, false, nullptr);
+}
+
+// The proving pass of a caller that owns ws.io (phant_state_witness, phant_state_proofs): everything device-resident, p.seg_first and
+// p.roots required.  The nodes are APPENDED to the host vectors (node_off holds one entry per node so far + 1), so two forests that
+// reuse t1 / t2 / pv / pvo one after the other end up in one set.  With `first` (the per-proof form: n_queries + 1 entries) the
+// vectors are emptied before that, so the proofs replace what they held.
+int32_t prove_collect(Workspaces& ws, hipStream_t st, const TriePairs& p, const ProveQueries& q, std::vector<uint8_t>& nodes,
+                      std::vector<uint64_t>& node_off, std::vector<uint32_t>* first, std::string& err) {
+    ProveCall c(ws, st, first != nullptr, err);
+    int32_t rc = c.plan(p, q, nullptr);
+    if (rc) return rc;
+    if (first) {
+        nodes.clear();
+        node_off.assign(1, 0);
+        first->assign((size_t)q.n_queries + 1, 0);
     }
-    nodes.assign(run.nodes_len, 0);
-    node_off.assign((size_t)run.total_nodes + 1, 0);
-    first.assign((size_t)q.n_queries + 1, 0);
-    if (!run.total_nodes) return PHANT_OK;
-    uint8_t* d_nodes = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t *d_first = nullptr, *d_src = nullptr;
-    rc = lay_out_status(lay_out_arena(ws.pvb, st, [&](auto& ar) {
-        d_off = ar.template take<uint64_t>((size_t)run.total_nodes + 1);
-        d_src = ar.template take<uint32_t>(run.total_nodes);
-        d_first = ar.template take<uint32_t>((size_t)q.n_queries + 1);
-        d_nodes = ar.template take<uint8_t>(run.nodes_len + 16);
-    }), "prove_batch", "pvb", err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    rc = prove_batch_write(st, run, d_nodes, d_off, d_first, d_src, err);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    TB_TRY(hipMemcpyAsync(nodes.data(), d_nodes, run.nodes_len, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipMemcpyAsync(node_off.data(), d_off, node_off.size() * 8, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipMemcpyAsync(first.data(), d_first, first.size() * 4, hipMemcpyDeviceToHost, st));
-    TB_TRY(hipStreamSynchronize(st));
+    if (!c.total_nodes) return PHANT_OK;
+    const size_t b0 = nodes.size(), k0 = node_off.size() - 1;  // (node_off[k0] == b0)
+    nodes.resize(b0 + c.nodes_len);
+    node_off.resize(k0 + c.total_nodes + 1);
+    ProveArgs a;
+    a.nodes = nodes.data() + b0, a.nodes_cap = c.nodes_len;
+    a.node_off = node_off.data() + k0, a.max_nodes = c.total_nodes;
+    a.first_node = first ? first->data() : nullptr;
+    if ((rc = c.deliver(a, true, nullptr)) != PHANT_OK || (rc = c.synchronise()) != PHANT_OK) return rc;
+    for (size_t i = k0; i < node_off.size(); ++i) node_off[i] += b0;  // (they came relative to this forest's first byte)
     return PHANT_OK;
 }
 

@@ -14,7 +14,7 @@ def _emulated_backend():
 
 
 from tests.test_gpu_prove import (  # noqa: E402,F401
-    M, build_pass, test_oracle_parity, test_forests, test_round_trip_through_the_verifier, test_capacity_and_arguments,
+    M, build_pass, test_oracle_parity, test_forests, test_round_trip_through_the_verifier, test_capacity_and_arguments, test_device_capacity_and_arguments,
     test_one_context_small_large_small, test_may_remove_adds_the_siblings, test_device_form, P,
     test_state_witness_of_every_fixture_alloc, test_state_witness_of_a_block_shaped_state, test_state_witness_arguments,
     test_removals_need_the_flag_and_the_flag_suffices)

@@ -16,7 +16,7 @@ def _emulated_backend():
 
 from tests.test_gpu_prove_batch import (  # noqa: E402,F401
     M, build_pass, test_oracle_parity, test_forests, test_cross_form, test_through_the_verifier, test_device_form_feeds_the_verifier,
-    test_capacity_and_arguments, test_one_context_small_large_small, P, test_state_proofs_of_fixture_allocs,
+    test_capacity_and_arguments, test_device_capacity_and_arguments, test_one_context_small_large_small, P, test_state_proofs_of_fixture_allocs,
     test_state_proofs_of_a_block_shaped_state, test_state_proofs_arguments)
 
 # reset, locate, size, scan, base, the set's emit; count, scan, place, gather

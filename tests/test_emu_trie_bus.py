@@ -9,7 +9,8 @@ their own validation, staging arrays, rebasing and uploads and every arena was s
 with this file, before that code was rewritten on top of staging.h's stage_pairs and lay_out_arena.  Every tuple is reproduced exactly
 but for one deliberate change: the host form of phant_mpt_prove_nodeset now sends its inputs through the pinned stage, ONE host-to-device
 copy where there were five to nine (PROVE_HOST holds the new tuples beside the parent's).  This module runs against the plain emulated
-library: the sanitized one poisons the arena's padding, so it never stages.
+library: the sanitized one poisons the arena's padding, so it never stages.  PROVE_BATCH, ("state_proofs", 40) and ("prove_batch", 50)
+were recorded the same way at commit d344bc8, before the prover's two forms were given one host driver.
 
 The last section holds the kernel launches of the same kind of calls (the emulated runtime's hipemu::M.launches, through
 tests/native/hipemu_export.cpp: hipemu_counters): LAUNCHES was recorded on commit 343780c, the last one whose forest_device was one
@@ -75,8 +76,8 @@ def test_trie_roots():
     assert got == {k: PARENT[k] for k in got}, got
 
 
-def _prove_call(keys, vals, queries, seg=None, q_trie=None, q_flags=None, want=True, dev=False):
-    """-> a closure that makes one phant_mpt_prove_nodeset[_dev] call with every output wanted, or none"""
+def _prove_call(keys, vals, queries, seg=None, q_trie=None, q_flags=None, want=True, dev=False, batch=False):
+    """-> a closure that makes one phant_mpt_prove_nodeset[_dev] (batch: phant_mpt_prove_batch[_dev]) call with every output wanted, or none"""
     import torch
     from phant_amd import _lib as L, mpt
     ctx = _ctx()
@@ -88,17 +89,24 @@ def _prove_call(keys, vals, queries, seg=None, q_trie=None, q_flags=None, want=T
     ins = [kb, ko, vb, vo, None if seg is None else np.asarray(seg, np.uint32), qb, qo,
            None if q_trie is None else np.asarray(q_trie, np.uint32), None if q_flags is None else np.asarray(q_flags, np.uint8)]
     max_nodes, cap = 8 * nq + 64, (8 * nq + 64) * 256
-    outs = [np.zeros(cap, np.uint8), np.zeros(max_nodes + 1, np.uint64), np.zeros(n_tries + 1, np.uint32), np.zeros(n_tries * 32, np.uint8),
-            np.zeros(max(nq, 1), np.uint8)]
+    outs = [np.zeros(cap, np.uint8), np.zeros(max_nodes + 1, np.uint64), np.zeros((nq if batch else n_tries) + 1, np.uint32),
+            np.zeros(n_tries * 32, np.uint8), np.zeros(max(nq, 1), np.uint8)]
     if dev:
         ins = [None if a is None else _dev(a) for a in ins]
         outs = [torch.from_numpy(a.view(np.uint8)).cuda() for a in outs]
     p = lambda a: None if a is None else C.c_void_p(a.data_ptr()) if dev else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     po = [p(a) if want else None for a in outs]
-    o = L.PhantProveOut(C.sizeof(L.PhantProveOut), max_nodes, cap, *po, 0, 0, 0)
+    Out = L.PhantProveBatchOut if batch else L.PhantProveOut
+    o = Out(C.sizeof(Out), max_nodes, cap, *po, 0, 0, 0)
 
     def call():
-        if dev:
+        if batch and dev:
+            rc = ctx._lib.phant_mpt_prove_batch_dev(ctx.handle, p(ins[0]), p(ins[1]), len(kb) if n else 0, p(ins[2]), p(ins[3]), int(vo[-1]), n,
+                                                    p(ins[4]), n_tries, p(ins[5]), p(ins[6]), int(qo[-1]), p(ins[7]), nq, C.byref(o))
+        elif batch:
+            rc = ctx._lib.phant_mpt_prove_batch(ctx.handle, p(ins[0]), p(ins[1]), p(ins[2]), p(ins[3]), n, p(ins[4]), n_tries, p(ins[5]), p(ins[6]),
+                                                p(ins[7]), nq, C.byref(o))
+        elif dev:
             rc = ctx._lib.phant_mpt_prove_nodeset_dev(ctx.handle, p(ins[0]), p(ins[1]), len(kb) if n else 0, p(ins[2]), p(ins[3]),
                                                       int(vo[-1]), n, p(ins[4]), n_tries, p(ins[5]), p(ins[6]), int(qo[-1]), p(ins[7]), p(ins[8]),
                                                       nq, C.byref(o))
@@ -131,6 +139,21 @@ def test_prove_nodeset():
     assert dev == {k: PARENT[k] for k in dev}, dev
 
 
+def test_prove_batch():
+    """phant_mpt_prove_batch on the shapes of test_prove_nodeset (it has no q_flags), and its device form"""
+    keys, vals, _ = _kv(6, 200)
+    rng = np.random.default_rng(6)
+    queries = [keys[i] for i in rng.choice(200, 7, replace=False)] + [rng.integers(0, 256, 32, dtype=np.uint8).tobytes() for _ in range(3)]
+    got = {("all outputs", 200): bus_of_second(_prove_call(keys, vals, queries, batch=True)),
+           ("no output", 200): bus_of_second(_prove_call(keys, vals, queries, want=False, batch=True)),
+           ("three tries", 200): bus_of_second(_prove_call(keys, vals, queries, seg=[0, 70, 70, 200], q_trie=[0, 2, 2, 0, 1, 2, 0, 2, 1, 0],
+                                                             batch=True)),
+           ("no keys", 0): bus_of_second(_prove_call([], [], queries[:3], batch=True)),
+           ("prove_batch_dev", 200): bus_of_second(_prove_call(keys, vals, queries, dev=True, batch=True))}
+    print(got)
+    assert got == PROVE_BATCH, got
+
+
 def _state(seed=7, n=40, m=200):
     from phant_amd.state import AccountState
     rng = np.random.default_rng(seed)
@@ -161,6 +184,7 @@ def test_state():
     touched += [held[0].addr + rng.bytes(32), held[1].addr + rng.bytes(32), rng.bytes(52)]  # two absent, one of an absent account
     assert len(touched) == 10
     got[("state_witness", 40)] = bus_of_second(lambda: stateless.build_witness(acc, touched, may_remove=touched[4:6]))
+    got[("state_proofs", 40)] = bus_of_second(lambda: state.get_proofs(acc, touched))
     print(got)
     assert got == {k: PARENT[k] for k in got}, got
 
@@ -217,6 +241,7 @@ def test_launches_held_to_parent():
     rng = np.random.default_rng(6)
     queries = [keys[i] for i in rng.choice(50, 7, replace=False)] + [rng.integers(0, 256, 32, dtype=np.uint8).tobytes() for _ in range(3)]
     got[("prove_nodeset", 50)] = launches_of_second(_prove_call(keys, vals, queries))
+    got[("prove_batch", 50)] = launches_of_second(_prove_call(keys, vals, queries, batch=True))
     print(got)
     assert got == LAUNCHES, got
 
@@ -224,14 +249,19 @@ def test_launches_held_to_parent():
 # ---- recorded at commit 343780c (see the module's docstring): kernel launches
 LAUNCHES = {("mpt_root", 0): 1, ("mpt_root", 1): 2, ("mpt_root", 50): 2, ("mpt_root", 3000): 13, ("shared_byte", 3000): 14, ("side", 3000): 15,
             ("side_behind", 3000): 15, ("side_join", 3000): 15, ("blocks1_grid1", 3000): 21, ("no_wave", 3000): 14, ("no_coop", 3000): 14,
-            ("mpt_root_nodes", 200): 2, ("block_roots", 60): 2, ("prove_nodeset", 50): 9}
+            ("mpt_root_nodes", 200): 2, ("block_roots", 60): 2, ("prove_nodeset", 50): 9, ("prove_batch", 50): 12}
 
 # ---- recorded at commit 8264687 (see the module's docstring): (H2D, D2H, D2D, memsets, stream synchronisations)
 PARENT = {("mpt_root", 0): (1, 0, 0, 0, 1), ("mpt_root", 1): (1, 0, 0, 0, 1), ("mpt_root", 50): (1, 0, 0, 0, 1), ("mpt_root", 3000): (1, 0, 0, 0, 1),
           ("mpt_root_dev", 50): (1, 0, 0, 0, 0), ("mpt_root_nodes", 200): (1, 0, 0, 0, 1), ("block_roots", 60): (1, 0, 0, 0, 1),
           ("index_root_be32", 20): (1, 0, 0, 0, 1), ("prove_nodeset_dev", 200): (1, 1, 0, 2, 2),
           ("state_root", 0): (1, 0, 0, 0, 1), ("state_root", 40): (9, 6, 0, 2, 5), ("state_root_dev", 40): (1, 6, 1, 3, 4),
-          ("state_subtrie_nodes", 40): (9, 8, 0, 3, 5), ("state_witness", 40): (15, 13, 0, 6, 11)}
+          ("state_subtrie_nodes", 40): (9, 8, 0, 3, 5), ("state_witness", 40): (15, 13, 0, 6, 11),
+          ("state_proofs", 40): (13, 16, 0, 6, 13)}
+# ---- recorded at commit d344bc8, the last one in which the two forms of the prover each had their own host driver: phant_mpt_prove_batch
+# on the shapes of PROVE_HOST and its device form; ("state_proofs", 40) in PARENT and ("prove_batch", 50) in LAUNCHES are of that commit too
+PROVE_BATCH = {("all outputs", 200): (1, 6, 0, 2, 4), ("no output", 200): (1, 1, 0, 2, 4), ("three tries", 200): (1, 6, 0, 2, 4),
+               ("no keys", 0): (1, 4, 0, 2, 2), ("prove_batch_dev", 200): (1, 1, 0, 2, 4)}
 # phant_mpt_prove_nodeset, host form: (the parent's tuple, the tuple since its inputs cross through the pinned stage)
 PROVE_HOST = {("all outputs", 200): ((7, 6, 0, 2, 3), (1, 6, 0, 2, 3)), ("no output", 200): ((7, 1, 0, 2, 3), (1, 1, 0, 2, 3)),
               ("three tries", 200): ((9, 6, 0, 2, 3), (1, 6, 0, 2, 3)), ("no keys", 0): ((5, 5, 0, 2, 3), (1, 5, 0, 2, 3))}

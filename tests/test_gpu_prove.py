@@ -252,6 +252,104 @@ def test_capacity_and_arguments(M, oracle):
     assert rc == L.E_INVALID_ARG
 
 
+def _raw_dev(M, L, ctx, keys, vals, queries, seg=None, q_trie=None, max_nodes=4096, nodes_cap=1 << 18, null=(), batch=False):
+    """the device form's C call itself (batch: phant_mpt_prove_batch_dev), every array in device memory, 0xEE in the outputs
+    -> (rc, out struct, the buffers as they are afterwards, in host memory and under the names _raw gives them)"""
+    import torch
+    kb, ko = M._pack(list(keys), np.uint32)
+    vb, vo = M._pack(list(vals), np.uint64)
+    qb, qo = M._pack(list(queries), np.uint32)
+    n, nq, nt = len(keys), len(queries), 1 if seg is None else len(seg) - 1
+    first = "proof_first_node" if batch else "trie_first_node"
+    buf = {"nodes": np.full(max(nodes_cap, 1), 0xEE, np.uint8), "node_off": np.full(max_nodes + 1, 0xEEEEEEEE, np.uint64),
+           first: np.full((nq if batch else nt) + 1, 0xEEEEEEEE, np.uint32), "roots": np.full(32 * nt, 0xEE, np.uint8),
+           "q_status": np.full(max(nq, 1), 0xEE, np.uint8)}
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    ins = [dev(a) for a in (kb, ko, vb, vo, None if seg is None else np.asarray(seg, np.uint32), qb, qo,
+                            None if q_trie is None else np.asarray(q_trie, np.uint32))]
+    d = {k: dev(v) for k, v in buf.items()}
+    p = {k: (None if k in null else ptr(t)) for k, t in d.items()}
+    Out = L.PhantProveBatchOut if batch else L.PhantProveOut
+    o = Out(C.sizeof(Out), max_nodes, nodes_cap, p["nodes"], p["node_off"], p[first], p["roots"], p["q_status"], 0, 0, 0)
+    head = [ctx.handle, ptr(ins[0]), ptr(ins[1]), int(ko[-1]), ptr(ins[2]), ptr(ins[3]), int(vo[-1]), n, ptr(ins[4]), nt, ptr(ins[5]), ptr(ins[6]),
+            int(qo[-1]), ptr(ins[7])]
+    if batch:
+        rc = ctx._lib.phant_mpt_prove_batch_dev(*head, nq, C.byref(o))
+    else:
+        rc = ctx._lib.phant_mpt_prove_nodeset_dev(*head, None, nq, C.byref(o))
+    torch.cuda.synchronize()
+    return rc, o, {k: t.cpu().numpy().view(buf[k].dtype).copy() for k, t in d.items()}
+
+
+def device_form_edge_cases(M, oracle, L, ctx, host, dev, first):
+    """The device form of either prover against its host form, call by call on the same arguments: the same code, the same totals and
+    the same five buffers to the last 0xEE (`host` / `dev`: the two _raw functions, `first`: the first-node table's name); what the
+    host form returns is held to the oracle here or in the host form's own test_capacity_and_arguments.  -> the full call's buffers"""
+    rng = np.random.default_rng(12)
+    keys, vals = random_kv(rng, 60, 32, 1, 80)
+    queries = list(keys[::2]) + [bytes(rng.integers(0, 256, 32, dtype=np.uint8)) for _ in range(9)] + [b""]
+    names = ("nodes", "node_off", first, "roots", "q_status")
+
+    def both(k, v, q, **kw):
+        kw.setdefault("nodes_cap", 1 << 18)
+        rh, oh, bh = host(M, L, ctx, k, v, q, **kw)
+        rd, od, bd = dev(M, L, ctx, k, v, q, **kw)
+        assert rd == rh == 0 and (od.total_nodes, od.nodes_len) == (oh.total_nodes, oh.nodes_len), kw
+        for name in names:
+            assert np.array_equal(bd[name], bh[name]), (name, kw)
+        return od, bd
+
+    o, full = both(keys, vals, queries, nodes_cap=1 << 18)
+    tn, nl = int(o.total_nodes), int(o.nodes_len)
+    assert tn > 0 and int(full["node_off"][tn]) == nl and full["roots"].tobytes() == oracle.mptize(keys, vals)
+    assert np.array_equal(full["q_status"], prove_ref.statuses(keys, queries))
+    # exact capacity
+    o, b = both(keys, vals, queries, max_nodes=tn, nodes_cap=nl)
+    assert np.array_equal(b["nodes"], full["nodes"][:nl]) and np.array_equal(b["node_off"], full["node_off"][:tn + 1])
+    # one node too few, one byte too few: the totals, the laid-out buffers untouched, roots and q_status still written
+    for mn, nc in ((tn - 1, nl), (tn, nl - 1)):
+        o, b = both(keys, vals, queries, max_nodes=mn, nodes_cap=nc)
+        assert (o.total_nodes, o.nodes_len) == (tn, nl)
+        assert (b["nodes"] == 0xEE).all() and (b["node_off"] == 0xEEEEEEEE).all()
+        assert first == "trie_first_node" or (b[first] == 0xEEEEEEEE).all()
+        assert np.array_equal(b["q_status"], full["q_status"]) and np.array_equal(b["roots"], full["roots"])
+    # each output NULL in turn, then all of them
+    for null in [(name,) for name in names] + [names]:
+        o, b = both(keys, vals, queries, nodes_cap=1 << 18, null=null)
+        assert (o.total_nodes, o.nodes_len) == (tn, nl), null
+        for name in names:
+            if name in null:
+                assert (b[name] == (0xEE if b[name].dtype == np.uint8 else 0xEEEEEEEE)).all(), null
+            elif first == "proof_first_node" or name in (first, "roots", "q_status"):
+                assert np.array_equal(b[name], full[name]), (null, name)
+    # no queries; no keys with two queries
+    o, b = both(keys, vals, [])
+    assert (o.total_nodes, o.nodes_len) == (0, 0) and not b[first].any() and int(b["node_off"][0]) == 0
+    assert b["roots"].tobytes() == oracle.mptize(keys, vals) and (b["node_off"][1:] == 0xEEEEEEEE).all()
+    o, b = both([], [], [b"\x01" * 32, b""])
+    assert (o.total_nodes, o.nodes_len) == (0, 0) and b["roots"].tobytes() == EMPTY_ROOT and not b[first].any()
+    assert list(b["q_status"]) == [M.PROOF_ABSENT, M.PROOF_ABSENT] and int(b["node_off"][0]) == 0
+    # three tries, the queries all of the empty one
+    seg = [0, 30, 30, 60]
+    o, b = both(keys, vals, queries, seg=seg, q_trie=[1] * len(queries))
+    assert (o.total_nodes, o.nodes_len) == (0, 0) and not b[first].any() and int(b["node_off"][0]) == 0
+    assert (b["q_status"] == M.PROOF_ABSENT).all() and (b["nodes"] == 0xEE).all()
+    assert b["roots"].tobytes() == oracle.mptize(keys[:30], vals[:30]) + EMPTY_ROOT + oracle.mptize(keys[30:], vals[30:])
+    # a q_trie entry that names no trie
+    bad = [0] * (len(queries) - 1) + [3]
+    assert host(M, L, ctx, keys, vals, queries, seg=seg, q_trie=bad)[0] == L.E_INVALID_ARG
+    assert dev(M, L, ctx, keys, vals, queries, seg=seg, q_trie=bad)[0] == L.E_INVALID_ARG
+    return tn, full
+
+
+def test_device_capacity_and_arguments(M, oracle):
+    """test_capacity_and_arguments for phant_mpt_prove_nodeset_dev"""
+    from phant_amd import _lib as L
+    tn, full = device_form_edge_cases(M, oracle, L, _ctx(), _raw, _raw_dev, "trie_first_node")
+    assert list(full["trie_first_node"]) == [0, tn]
+
+
 def test_one_context_small_large_small(M, oracle):
     import phant_amd
     from phant_amd.context import Context, default_context

@@ -260,6 +260,22 @@ def test_capacity_and_arguments(M, oracle):
     assert rc == L.E_UNSUPPORTED
 
 
+def test_device_capacity_and_arguments(M, oracle):
+    """test_capacity_and_arguments for phant_mpt_prove_batch_dev"""
+    from functools import partial
+    from phant_amd import _lib as L
+    from tests.test_gpu_prove import _raw_dev, device_form_edge_cases
+    rng = np.random.default_rng(12)  # (the keys and queries of device_form_edge_cases)
+    keys, vals = random_kv(rng, 60, 32, 1, 80)
+    queries = list(keys[::2]) + [bytes(rng.integers(0, 256, 32, dtype=np.uint8)) for _ in range(9)] + [b""]
+    tn, full = device_form_edge_cases(M, oracle, L, _ctx(), _raw, partial(_raw_dev, batch=True), "proof_first_node")
+    trie = oracle.Trie(keys, vals)
+    want = [trie.prove(q) for q in queries]
+    got = [[full["nodes"][int(full["node_off"][k]):int(full["node_off"][k + 1])].tobytes()
+            for k in range(int(full["proof_first_node"][j]), int(full["proof_first_node"][j + 1]))] for j in range(len(queries))]
+    assert got == want and tn == sum(map(len, want))
+
+
 def test_one_context_small_large_small(M, oracle):
     from phant_amd.context import Context, default_context
     rng = np.random.default_rng(21)
