@@ -561,6 +561,131 @@ typedef struct phant_txs_ex_out {
 PHANT_API int32_t phant_block_transactions_ex(phant_ctx *ctx, const phant_txs_ex_in *in, phant_txs_ex_out *out);
 PHANT_API int32_t phant_block_transactions_ex_dev(phant_ctx *ctx, const phant_txs_ex_in *in, phant_txs_ex_out *out);
 
+/* ------------------------------------------------- chain segments of block bodies: many blocks' transactions in one call
+ * What phant_block_transactions_ex and phant_block_roots answer block by block, for the bodies of n_blocks blocks in ONE call:
+ * the headers of a segment go through phant_header_chain, the bodies they commit to through this.  A recovery launch lasts as
+ * long as one lane's chain of multiplications whatever the number of signatures (up to about 65 000), so a segment's
+ * signatures cost what one block's cost.
+ *
+ * Input.  fork (one PHANT_TXS_FORK_* per call: a caller splits a range at a fork boundary), chain_id, flags
+ * (PHANT_TXS_HAVE_GAS_LIMIT, PHANT_TXS_NO_RECOVERY, as above).  n, txs, tx_off (n + 1), tx_bytes: as in phant_txs_in, all
+ * blocks' transactions back to back.  block_first (n_blocks + 1): never backwards, from 0 to n; block b owns the transactions
+ * [block_first[b], block_first[b + 1]); an empty block is ordinary.  n_wd, withdrawals, wd_off (n_wd + 1), wd_bytes, wd_first
+ * (n_blocks + 1): each withdrawal is its RLP list exactly as it stands in the block, which is its trie value; wd_first ==
+ * NULL: the segment has no withdrawal lists (before Shanghai) -- n_wd must then be 0 and withdrawals, wd_off and both
+ * withdrawals_root pointers NULL.  Per block, laid out like the arrays of phant_headers_in, so that a caller can point at the
+ * same memory: base_fee (n_blocks x 32 big-endian; NULL skips the two fee rules), gas_limit (n_blocks, read with
+ * PHANT_TXS_HAVE_GAS_LIMIT), blob_base_fee (n_blocks x 32; NULL skips its rule; the caller derives block b's from its
+ * parent's excess_blob_gas).  Expected values, each may be NULL: transactions_root, withdrawals_root (n_blocks x 32),
+ * blob_gas_used (n_blocks).  UNLIKE phant_block_transactions_ex, whose base_fee and blob_base_fee are host memory in both
+ * forms, every array here is host memory in the host form and DEVICE memory in the device form.  The host form does not read
+ * tx_bytes and wd_bytes (the totals are tx_off[n] and wd_off[n_wd]).
+ *
+ * Output, any pointer may be NULL.  txs: every per-transaction and per-authorization row of phant_txs_ex_out over the n
+ * transactions, auth_first (n + 1) global over the segment; its scalars keep their meaning over the whole segment
+ * (base.first_bad: the least flagged i; n_auth; blob_gas_used: the total).  DEFINITION: the row of transaction i in block b
+ * is exactly row i of phant_block_transactions_ex called over all n transactions with block b's base_fee, gas_limit and
+ * blob_base_fee -- so data_off, al_off and blob_off are offsets into the segment's txs, and a zero row stays zero.
+ *   tx_block (n)                 the block of transaction i
+ *   block_first_bad (n_blocks)   the least i - block_first[b] whose flags carry an error bit, the block's count if none
+ *   block_blob_gas_used (n_blocks, uint64_t)  131072 x the versioned hashes of the block's decodable type-3 transactions
+ *   transactions_root, withdrawals_root (n_blocks x 32)  calculateMPTRoot (blockchain.zig:209-235: the key of item i is
+ *                                rlp(i)) over the block's raw transactions / withdrawals; an empty list: empty_mpt_root
+ *   block_flags (n_blocks)       below
+ *   first_bad_block (always written)  the least b with block_flags[b] != 0, n_blocks if none
+ * When neither root is asked for nor expected, no trie is built. */
+#define PHANT_BODY_TX 1u       /* some transaction of the block carries a bit of PHANT_TX_ERROR_BITS_EX */
+#define PHANT_BODY_TXS_ROOT 2u /* in->transactions_root given and != the computed root */
+#define PHANT_BODY_WD_ROOT 4u  /* in->withdrawals_root given and != the computed root */
+#define PHANT_BODY_BLOB_GAS 8u /* in->blob_gas_used given and != block_blob_gas_used */
+/* A bad transaction or block is a flag, never an error.  PHANT_E_INVALID_ARG, before anything is indexed with the offending
+ * value and with nothing written: a wrong struct_size (of either struct, of out->txs or of out->txs.base), fork >
+ * PHANT_TXS_FORK_PRAGUE, an unknown flag bit, reserved != 0; a NULL input with a non-zero count (txs / tx_off with n,
+ * block_first with n_blocks, withdrawals / wd_off with n_wd, gas_limit with PHANT_TXS_HAVE_GAS_LIMIT); tx_off, wd_off,
+ * block_first or wd_first that do not run from 0 to their totals (device form: tx_bytes, wd_bytes; n; n_wd) or go backwards;
+ * n_wd, withdrawals, wd_off or a withdrawals_root without wd_first; sender, sig_status, authority or auth_status together with
+ * PHANT_TXS_NO_RECOVERY.  PHANT_E_UNSUPPORTED: a transaction or a withdrawal of 2^32 bytes or more, 2^32 bytes of trie
+ * values or 2^31 - 1 items in one call.  n_blocks == 0 is PHANT_OK with first_bad_block = 0 and the scalars of txs zero; so
+ * is n == 0 (the roots are then those of empty lists).  The host form checks on the host before any copy: one staged
+ * upload, the launches, one copy back of the span up to the last wanted output.
+ *
+ * Device form: every array is device memory, the uint64_t arrays 8-byte and the uint32_t arrays 4-byte aligned, byte arrays
+ * not at all; the structs are host memory.  The four offset arrays are checked by a kernel whose verdict the host reads
+ * before any other kernel indexes with them.  The call synchronises the ctx stream (the scalars are valid when it returns). */
+typedef struct phant_bodies_in {
+    uint32_t struct_size; /* = sizeof(phant_bodies_in) */
+    uint32_t fork;        /* PHANT_TXS_FORK_* */
+    uint32_t flags;       /* PHANT_TXS_* */
+    uint32_t n_blocks;
+    uint32_t n;           /* transactions of all blocks */
+    uint32_t n_wd;        /* withdrawals of all blocks */
+    uint32_t auth_cap;    /* rows the per-authorization outputs hold */
+    uint32_t reserved;    /* 0 */
+    uint64_t chain_id;
+    const uint8_t *txs;
+    const uint64_t *tx_off;       /* n + 1 */
+    uint64_t tx_bytes;            /* device form: tx_off[n] as the caller states it */
+    const uint32_t *block_first;  /* n_blocks + 1 */
+    const uint8_t *withdrawals;
+    const uint64_t *wd_off;       /* n_wd + 1 */
+    uint64_t wd_bytes;            /* device form: wd_off[n_wd] as the caller states it */
+    const uint32_t *wd_first;     /* n_blocks + 1, or NULL */
+    const uint8_t *base_fee;      /* n_blocks x 32, or NULL */
+    const uint64_t *gas_limit;    /* n_blocks */
+    const uint8_t *blob_base_fee; /* n_blocks x 32, or NULL */
+    const uint8_t *transactions_root; /* expected, n_blocks x 32, or NULL */
+    const uint8_t *withdrawals_root;  /* expected, n_blocks x 32, or NULL */
+    const uint64_t *blob_gas_used;    /* expected, n_blocks, or NULL */
+} phant_bodies_in;
+typedef struct phant_bodies_out {
+    uint32_t struct_size;     /* = sizeof(phant_bodies_out) */
+    uint32_t first_bad_block; /* result */
+    phant_txs_ex_out txs;     /* txs.struct_size = sizeof(phant_txs_ex_out), txs.base.struct_size = sizeof(phant_txs_out) */
+    uint32_t *tx_block;
+    uint32_t *block_first_bad;
+    uint64_t *block_blob_gas_used;
+    uint8_t *transactions_root;
+    uint8_t *withdrawals_root;
+    uint32_t *block_flags;
+} phant_bodies_out;
+PHANT_API int32_t phant_block_bodies(phant_ctx *ctx, const phant_bodies_in *in, phant_bodies_out *out);
+PHANT_API int32_t phant_block_bodies_dev(phant_ctx *ctx, const phant_bodies_in *in, phant_bodies_out *out);
+/* Host only, strict: the packed arrays phant_block_bodies takes from n raw blocks.  Block b = blob[off[b] .. off[b+1]) =
+ * [header, transactions, uncles, withdrawals?], or with PHANT_BODIES_NO_HEADER an eth-style body [transactions, uncles,
+ * withdrawals?].  Canonical RLP throughout and nothing behind the item; the header, when there, is a list and is not looked
+ * into (phant_headers_decode_rlp does that).  A transaction item is a list (a legacy transaction: its whole encoding is the
+ * value) or a non-empty string whose first byte is at most 0x7f (a typed one: its payload is the value); a withdrawal is a
+ * list, its whole encoding the value; uncles must be the empty list (`runBlock`: NotEmptyUncles).  status[b] (n bytes) says
+ * which rule block b broke first, and such a block contributes no rows: block_first[b + 1] == block_first[b], likewise
+ * wd_first.  A block without a withdrawals list has none; whether it should have one is its header's business.
+ * Sizing in two steps: n, n_wd, tx_bytes and wd_bytes are always written; when one of them exceeds its capacity (tx_cap,
+ * wd_cap: items; tx_bytes_cap, wd_bytes_cap: bytes; a NULL array has capacity 0) NOTHING else is written, status included, and
+ * the call still returns PHANT_OK: call again with arrays of the reported sizes (tx_off tx_cap + 1, block_first and wd_first
+ * n + 1, wd_off wd_cap + 1 entries).  PHANT_E_INVALID_ARG: NULL blob / off / split / status with n > 0, a wrong struct_size,
+ * unknown flags, offsets that go backwards. */
+#define PHANT_BODIES_NO_HEADER 1u
+#define PHANT_SPLIT_OK 0
+#define PHANT_SPLIT_BAD_RLP 1        /* not a canonical list of 3 or 4 (2 or 3) lists with nothing behind it */
+#define PHANT_SPLIT_BAD_TX 2         /* a transaction item that is neither a list nor a string beginning with a type byte */
+#define PHANT_SPLIT_UNCLES 3         /* the uncles are not the empty list */
+#define PHANT_SPLIT_BAD_WITHDRAWAL 4 /* a withdrawal that is not a list */
+typedef struct phant_bodies_split {
+    uint32_t struct_size; /* = sizeof(phant_bodies_split) */
+    uint32_t reserved;    /* 0 */
+    uint32_t tx_cap, wd_cap;
+    uint64_t tx_bytes_cap, wd_bytes_cap;
+    uint8_t *txs;
+    uint64_t *tx_off;
+    uint32_t *block_first;
+    uint8_t *withdrawals;
+    uint64_t *wd_off;
+    uint32_t *wd_first;
+    uint32_t n, n_wd;           /* results */
+    uint64_t tx_bytes, wd_bytes; /* results */
+} phant_bodies_split;
+PHANT_API int32_t phant_bodies_decode_rlp(const uint8_t *blob, const uint64_t *off, uint32_t n, uint32_t flags,
+                                          phant_bodies_split *split, uint8_t *status);
+
 /* ------------------------------------------------- a block's transactions against the pre-state: nonces, EOA and witness rows
  * phant_block_txs_prestate joins the rows phant_block_transactions[_ex] answers (keyed by transaction) with the rows
  * phant_exec_witness_prestate answers (keyed by witness row), and decides what `processTransaction` checks first

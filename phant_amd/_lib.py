@@ -74,6 +74,9 @@ SYMBOLS = {
     "phant_block_transactions_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_transactions_ex": (_i32, [_vp, _vp, _vp]),
     "phant_block_transactions_ex_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_block_bodies": (_i32, [_vp, _vp, _vp]),
+    "phant_block_bodies_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_bodies_decode_rlp": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle": (_i32, [_vp, _vp, _vp]),
@@ -250,6 +253,41 @@ class PhantTxsExOut(C.Structure):
     """phant_txs_ex_out (include/phant_gpu.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("n_auth", C.c_uint32), ("blob_gas_used", C.c_uint64), ("base", PhantTxsOut)] + \
                [(name, C.c_void_p) for name, _, _ in TX_EX_OUTPUTS + TX_AUTH_OUTPUTS]
+
+
+BODY_TX, BODY_TXS_ROOT, BODY_WD_ROOT, BODY_BLOB_GAS = 1, 2, 4, 8
+BODY_FLAG_NAMES = ("Transaction", "TransactionsRoot", "WithdrawalsRoot", "BlobGasUsed")
+# phant_bodies_in's arrays in the struct's order (tx_bytes sits behind tx_off, wd_bytes behind wd_off)
+BODIES_INPUTS = ("txs", "tx_off", "block_first", "withdrawals", "wd_off", "wd_first", "base_fee", "gas_limit", "blob_base_fee", "transactions_root",
+                 "withdrawals_root", "blob_gas_used")
+# phant_bodies_out's own arrays in the struct's order: (name, numpy dtype, elements per row, the count its rows follow)
+BODIES_OUTPUTS = (("tx_block", "u4", 1, "n"), ("block_first_bad", "u4", 1, "n_blocks"), ("block_blob_gas_used", "u8", 1, "n_blocks"),
+                  ("transactions_root", "u1", 32, "n_blocks"), ("withdrawals_root", "u1", 32, "n_blocks"), ("block_flags", "u4", 1, "n_blocks"))
+
+
+BODIES_NO_HEADER = 1
+# phant_bodies_split's arrays in the struct's order
+BODIES_SPLIT_ARRAYS = ("txs", "tx_off", "block_first", "withdrawals", "wd_off", "wd_first")
+
+
+class PhantBodiesSplit(C.Structure):
+    """phant_bodies_split (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "reserved", "tx_cap", "wd_cap")] + [("tx_bytes_cap", C.c_uint64), ("wd_bytes_cap", C.c_uint64)] + \
+               [(name, C.c_void_p) for name in BODIES_SPLIT_ARRAYS] + [("n", C.c_uint32), ("n_wd", C.c_uint32), ("tx_bytes", C.c_uint64), ("wd_bytes", C.c_uint64)]
+
+
+class PhantBodiesIn(C.Structure):
+    """phant_bodies_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "fork", "flags", "n_blocks", "n", "n_wd", "auth_cap", "reserved")] + \
+               [("chain_id", C.c_uint64), ("txs", C.c_void_p), ("tx_off", C.c_void_p), ("tx_bytes", C.c_uint64), ("block_first", C.c_void_p),
+                ("withdrawals", C.c_void_p), ("wd_off", C.c_void_p), ("wd_bytes", C.c_uint64)] + \
+               [(name, C.c_void_p) for name in BODIES_INPUTS[5:]]
+
+
+class PhantBodiesOut(C.Structure):
+    """phant_bodies_out (include/phant_gpu.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("first_bad_block", C.c_uint32), ("txs", PhantTxsExOut)] + \
+               [(name, C.c_void_p) for name, _, _, _ in BODIES_OUTPUTS]
 
 
 ROW_NONE = 0xFFFFFFFF

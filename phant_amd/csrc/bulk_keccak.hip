@@ -16,6 +16,8 @@
 //   transactions    src/types/transaction.zig:152-273 + src/blockchain/blockchain.zig:237-260,345-381  decode, both hashes, senders,
 //                   intrinsic gas and the state-free rules of a block's transactions in one call (transactions.hip.h, behind
 //                   ecrecover_kernel below, which it launches)
+//   block bodies    the transactions of a whole chain segment through those steps in one call, the rules under each block's own
+//                   parameters, and the blocks' transactions and withdrawals tries as one forest (bodies.hip.h)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
@@ -260,6 +262,7 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 }  // namespace phant
 
 #include "transactions.hip.h"
+#include "bodies.hip.h"
 #include "txstate.hip.h"
 #include "settle.hip.h"
 #include "access_lists.hip.h"

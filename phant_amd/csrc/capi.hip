@@ -979,6 +979,90 @@ int32_t phant_block_transactions_ex_dev(phant_ctx* c, const phant_txs_ex_in* in,
     return block_transactions_impl(c, &in->base, &out->base, in, out, true);
 }
 
+/* ------------------------------------------------- chain segments of block bodies (bodies.hip.h) */
+
+int32_t phant_bodies_decode_rlp(const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t flags, phant_bodies_split* sp, uint8_t* status) {
+    if (flags & ~PHANT_BODIES_NO_HEADER) return PHANT_E_INVALID_ARG;
+    if (!sp || sp->struct_size != sizeof(phant_bodies_split) || sp->reserved != 0u) return PHANT_E_INVALID_ARG;
+    if (n && (!off || !status)) return PHANT_E_INVALID_ARG;
+    for (uint32_t b = 0; b < n; ++b)
+        if (off[b + 1] < off[b]) return PHANT_E_INVALID_ARG;
+    if (n && off[n] != off[0] && !blob) return PHANT_E_INVALID_ARG;
+    const bool has_header = !(flags & PHANT_BODIES_NO_HEADER);
+    auto block = [&](uint32_t b, phant::BodyTotals& t, const phant::BodySink* sink) {
+        return phant::body_split(blob ? blob + off[b] : nullptr, (size_t)(off[b + 1] - off[b]), has_header, t, sink);
+    };
+    phant::BodyTotals t{0, 0, 0, 0};
+    for (uint32_t b = 0; b < n; ++b) (void)block(b, t, nullptr);
+    if (t.n > 0xffffffffull || t.n_wd > 0xffffffffull) return PHANT_E_UNSUPPORTED;
+    sp->n = (uint32_t)t.n, sp->n_wd = (uint32_t)t.n_wd, sp->tx_bytes = t.tx_bytes, sp->wd_bytes = t.wd_bytes;
+    const bool room = sp->tx_off && sp->block_first && sp->wd_off && sp->wd_first && t.n <= sp->tx_cap && t.n_wd <= sp->wd_cap &&
+                      (sp->txs ? t.tx_bytes <= sp->tx_bytes_cap : t.tx_bytes == 0) && (sp->withdrawals ? t.wd_bytes <= sp->wd_bytes_cap : t.wd_bytes == 0);
+    if (!room) return PHANT_OK;
+    const phant::BodySink sink{sp->txs, sp->tx_off, sp->withdrawals, sp->wd_off};
+    t = phant::BodyTotals{0, 0, 0, 0};
+    sp->tx_off[0] = 0, sp->wd_off[0] = 0, sp->block_first[0] = 0, sp->wd_first[0] = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        status[b] = block(b, t, &sink);
+        sp->block_first[b + 1] = (uint32_t)t.n, sp->wd_first[b + 1] = (uint32_t)t.n_wd;
+    }
+    return PHANT_OK;
+}
+
+static int32_t block_bodies_impl(phant_ctx* c, const phant_bodies_in* in, phant_bodies_out* out, bool dev) {
+    const char* const who = dev ? "block_bodies_dev" : "block_bodies";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_bodies_in) || out->struct_size != sizeof(phant_bodies_out) || out->txs.struct_size != sizeof(phant_txs_ex_out) ||
+        out->txs.base.struct_size != sizeof(phant_txs_out))
+        return bad("wrong struct_size");
+    if (in->fork > PHANT_TXS_FORK_PRAGUE) return bad("unknown fork");
+    if (in->reserved != 0u) return bad("reserved is not 0");
+    if (in->flags & ~(PHANT_TXS_HAVE_GAS_LIMIT | PHANT_TXS_NO_RECOVERY)) return bad("unknown flag");
+    const phant_txs_ex_out& x = out->txs;
+    const phant_txs_out& o = x.base;
+    if ((in->flags & PHANT_TXS_NO_RECOVERY) && (o.sender || o.sig_status || x.authority || x.auth_status))
+        return bad("sender / sig_status / authority / auth_status asked for together with the no-recovery flag");
+    if (!in->wd_first && (in->n_wd || in->withdrawals || in->wd_off || in->withdrawals_root || out->withdrawals_root))
+        return bad("withdrawals, their count, offsets or roots without wd_first");
+    const uint32_t n = in->n, nb = in->n_blocks;
+    if (nb == 0) {  // (no block: nothing to index, nothing to write but the scalars)
+        if (n || in->n_wd) return bad("transactions or withdrawals without a block");
+        out->first_bad_block = 0;
+        out->txs.base.first_bad = 0, out->txs.n_auth = 0, out->txs.blob_gas_used = 0;
+        return PHANT_OK;
+    }
+    if (!in->block_first) return bad("null block_first");
+    if (n && (!in->txs || !in->tx_off)) return bad("null txs / tx_off");
+    if (in->n_wd && (!in->withdrawals || !in->wd_off)) return bad("null withdrawals / wd_off");
+    if ((in->flags & PHANT_TXS_HAVE_GAS_LIMIT) && !in->gas_limit) return bad("null gas_limit with the gas-limit flag");
+    if (dev) {  // (the offsets and the 64- and 32-bit per-block arrays are read by kernels as words; the outputs arrive by copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->tx_off | (uintptr_t)in->wd_off | (uintptr_t)in->gas_limit | (uintptr_t)in->blob_gas_used | (uintptr_t)o.chain_id |
+                             (uintptr_t)o.nonce | (uintptr_t)o.gas_limit | (uintptr_t)o.data_off | (uintptr_t)o.al_off | (uintptr_t)o.intrinsic_gas |
+                             (uintptr_t)x.blob_off | (uintptr_t)x.floor_gas | (uintptr_t)x.auth_nonce | (uintptr_t)out->block_blob_gas_used;
+        const uintptr_t w4 = (uintptr_t)in->block_first | (uintptr_t)in->wd_first | (uintptr_t)o.data_len | (uintptr_t)o.al_len | (uintptr_t)o.al_addresses |
+                             (uintptr_t)o.al_keys | (uintptr_t)o.flags | (uintptr_t)x.blobs | (uintptr_t)x.auth_first | (uintptr_t)out->tx_block |
+                             (uintptr_t)out->block_first_bad | (uintptr_t)out->block_flags;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    DeviceGuard g(c->device);
+    if (n && !(in->flags & PHANT_TXS_NO_RECOVERY))
+        if (const int32_t rc = ensure_gtable(c)) return rc;
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_bodies_out res = *out;
+    const int32_t rc = phant::block_bodies(c->ws, c->stream, *in, res, dev, c->secp_gtable, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->first_bad_block = res.first_bad_block;
+    out->txs.base.first_bad = res.txs.base.first_bad, out->txs.n_auth = res.txs.n_auth, out->txs.blob_gas_used = res.txs.blob_gas_used;
+    return PHANT_OK;
+}
+
+int32_t phant_block_bodies(phant_ctx* c, const phant_bodies_in* in, phant_bodies_out* out) { return block_bodies_impl(c, in, out, false); }
+
+int32_t phant_block_bodies_dev(phant_ctx* c, const phant_bodies_in* in, phant_bodies_out* out) { return block_bodies_impl(c, in, out, true); }
+
 /* ------------------------------------------------- a block's transactions against the pre-state (txstate.hip.h) */
 
 static int32_t block_txs_prestate_impl(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out, bool dev) {

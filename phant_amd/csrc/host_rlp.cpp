@@ -334,4 +334,79 @@ bool header_decode(const uint8_t* p, size_t len, bool from_block, const HeaderAr
     return true;
 }
 
+// ---- block bodies: [header,] transactions, uncles, (withdrawals) ----
+// The items of the list payload p[0, len): `each(value, bytes)` for every one, given what `value_of` makes of it; false: an item that is
+// not canonical RLP or that value_of refuses.
+template <class ValueOf, class Each>
+static bool walk_list(const uint8_t* p, size_t len, ValueOf&& value_of, Each&& each) {
+    while (len) {
+        size_t ip, il, it;
+        bool ilist;
+        if (!host_rlp_item(p, len, ip, il, it, ilist)) return false;
+        const uint8_t* v;
+        size_t vl;
+        if (!value_of(p, ip, il, it, ilist, v, vl)) return false;
+        each(v, vl);
+        p += it, len -= it;
+    }
+    return true;
+}
+
+uint8_t body_split(const uint8_t* p, size_t len, bool has_header, BodyTotals& t, const BodySink* sink) {
+    if (!p) return PHANT_SPLIT_BAD_RLP;
+    size_t pay, plen, total;
+    bool is_list;
+    if (!host_rlp_item(p, len, pay, plen, total, is_list) || !is_list || total != len) return PHANT_SPLIT_BAD_RLP;
+    // the outer items: every one a list
+    const uint8_t* part[4];
+    size_t part_len[4], count = 0;
+    const uint8_t* q = p + pay;
+    size_t left = plen;
+    const size_t first = has_header ? 1 : 0;
+    while (left) {
+        size_t ip, il, it;
+        bool ilist;
+        if (count == first + 3 || !host_rlp_item(q, left, ip, il, it, ilist) || !ilist) return PHANT_SPLIT_BAD_RLP;
+        part[count] = q + ip, part_len[count] = il;
+        ++count, q += it, left -= it;
+    }
+    if (count != first + 2 && count != first + 3) return PHANT_SPLIT_BAD_RLP;
+    const uint8_t* const txs = part[first];
+    const size_t txs_len = part_len[first];
+    const bool has_wd = count == first + 3;
+    // a transaction: a list as it stands, or the payload of a string that begins with a type byte
+    auto tx_value = [](const uint8_t* item, size_t ip, size_t il, size_t it, bool ilist, const uint8_t*& v, size_t& vl) {
+        if (ilist) return v = item, vl = it, true;
+        if (il == 0 || item[ip] > 0x7fu) return false;
+        return v = item + ip, vl = il, true;
+    };
+    auto wd_value = [](const uint8_t* item, size_t, size_t, size_t it, bool ilist, const uint8_t*& v, size_t& vl) { return v = item, vl = it, ilist; };
+    BodyTotals mine{0, 0, 0, 0};
+    // (which of the two a false means: walk once more for the RLP alone)
+    auto any_value = [](const uint8_t* item, size_t, size_t, size_t it, bool, const uint8_t*& v, size_t& vl) { return v = item, vl = it, true; };
+    auto nothing = [](const uint8_t*, size_t) {};
+    if (!walk_list(txs, txs_len, tx_value, [&](const uint8_t*, size_t vl) { ++mine.n, mine.tx_bytes += vl; }))
+        return walk_list(txs, txs_len, any_value, nothing) ? PHANT_SPLIT_BAD_TX : PHANT_SPLIT_BAD_RLP;
+    if (part_len[first + 1] != 0) return PHANT_SPLIT_UNCLES;
+    if (has_wd && !walk_list(part[first + 2], part_len[first + 2], wd_value, [&](const uint8_t*, size_t vl) { ++mine.n_wd, mine.wd_bytes += vl; }))
+        return walk_list(part[first + 2], part_len[first + 2], any_value, nothing) ? PHANT_SPLIT_BAD_WITHDRAWAL : PHANT_SPLIT_BAD_RLP;
+    if (sink) {
+        uint64_t i = t.n, at = t.tx_bytes;
+        (void)walk_list(txs, txs_len, tx_value, [&](const uint8_t* v, size_t vl) {
+            std::memcpy(sink->txs + at, v, vl);
+            at += vl;
+            sink->tx_off[++i] = at;
+        });
+        i = t.n_wd, at = t.wd_bytes;
+        if (has_wd)
+            (void)walk_list(part[first + 2], part_len[first + 2], wd_value, [&](const uint8_t* v, size_t vl) {
+                std::memcpy(sink->wd + at, v, vl);
+                at += vl;
+                sink->wd_off[++i] = at;
+            });
+    }
+    t.n += mine.n, t.n_wd += mine.n_wd, t.tx_bytes += mine.tx_bytes, t.wd_bytes += mine.wd_bytes;
+    return PHANT_SPLIT_OK;
+}
+
 }  // namespace phant

@@ -42,4 +42,19 @@ struct HeaderArrays {
 };
 bool header_decode(const uint8_t* p, size_t len, bool from_block, const HeaderArrays& f, uint32_t i, uint32_t* extra_at);
 
+// phant_bodies_decode_rlp (include/phant_gpu.h): one raw block (has_header) or body of `len` bytes at `p` -> PHANT_SPLIT_*.  On
+// PHANT_SPLIT_OK its transactions and withdrawals are counted into `t`, and with a sink their values are first appended at t's
+// positions (tx_off[t.n + 1 ..], wd_off[t.n_wd + 1 ..]: the caller has made room and set entry 0); a refused block changes nothing.
+// Untrusted bytes in.
+struct BodyTotals {
+    uint64_t n, n_wd, tx_bytes, wd_bytes;
+};
+struct BodySink {
+    uint8_t* txs;
+    uint64_t* tx_off;
+    uint8_t* wd;
+    uint64_t* wd_off;
+};
+uint8_t body_split(const uint8_t* p, size_t len, bool has_header, BodyTotals& t, const BodySink* sink);
+
 }  // namespace phant

@@ -173,7 +173,7 @@ StagedPairs stage_pairs(Workspaces& ws, hipStream_t st, const HostPairs& h, cons
 // size only the control words tell -- gets a copy of its own in every form; a later deliver() synchronises the host form when it made one.
 // A call without control words leaves mailbox_words at 0; ctl() is valid after the first deliver().
 struct CallOutputs {
-    static constexpr int CAP = 40;  // block_transactions names 35
+    static constexpr int CAP = 48;  // block_transactions names 35, block_bodies 41
     struct Item {
         void* dst;
         const uint8_t* src;

@@ -19,4 +19,10 @@ namespace phant {
 int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in& in, phant_txs_ex_out& out, bool device_form,
                            const uint32_t* gtable, std::string& err);
 
+// The bodies of a chain segment (bodies.hip.h; phant_block_bodies[_dev]): in / out as they came, every array host memory in the host form
+// and device memory in the device form.  The caller has checked struct sizes, flag bits, the fork, NULL arguments and alignment, and
+// n_blocks != 0.  On PHANT_OK out.first_bad_block and the scalars of out.txs are written.
+int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, phant_bodies_out& out, bool device_form, const uint32_t* gtable,
+                     std::string& err);
+
 }  // namespace phant

@@ -23,6 +23,8 @@
 //   tx_auth_rows_kernel   a lane per transaction: its tuples' fields into the rows from auth_first[i] on
 //   tx_auth_hash_kernel   a lane per tuple: keccak256(0x05 || rlp([chain_id, address, nonce])), one block built in registers
 //   (ecrecover_kernel)    over the tuples' rows: the authorities
+// phant_block_bodies (bodies.hip.h) runs the same kernels over the transactions of a whole chain segment: the rules
+// are tx::rules_row for both rules kernels, and the host driver's steps are tx::call_begin / call_carve / call_kernels / call_outputs.
 //
 // Plain C++ plus the builtins the sponge uses: tests/emu.py compiles this file for the host.  With PHANT_TX_DECODE_ONLY defined only
 // tx::decode and what it needs are declared, without any HIP header: tests/native/tx_decode_main.cpp builds it as a program of its own.
@@ -659,10 +661,10 @@ TX_HD bool less_u256(const uint32_t a[8], const uint32_t b[8]) {
     return false;
 }
 
+// The rules of transaction i under the block parameters ru, stated ONCE: tx_rules_kernel has ru from its arguments, bodies.hip.h's
+// body_rules_kernel builds it from the per-block arrays of a chain segment.  Writes the row's rule outputs -> its flags.
 // sig_status: the recovery's verdicts, or null (PHANT_TXS_NO_RECOVERY)
-__global__ void __launch_bounds__(64) tx_rules_kernel(uint32_t n, Rules ru, Dev dv, const uint8_t* __restrict__ sig_status) {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n) return;
+PHANT_DEV uint32_t rules_row(uint32_t i, const Rules& ru, const Dev& dv, const uint8_t* __restrict__ sig_status) {
     const Out& o = dv.o;
     uint32_t f = o.flags[i];
     uint32_t eff[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cost[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -739,6 +741,13 @@ __global__ void __launch_bounds__(64) tx_rules_kernel(uint32_t n, Rules ru, Dev 
     dv.x.floor_gas[i] = floor_gas;
     store_u256(o.effective_gas_price + 32ull * i, eff);
     store_u256(o.upfront_cost + 32ull * i, cost);
+    return f;
+}
+
+__global__ void __launch_bounds__(64) tx_rules_kernel(uint32_t n, Rules ru, Dev dv, const uint8_t* __restrict__ sig_status) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = rules_row(i, ru, dv, sig_status);
     if (f & ERROR_BITS) atomicMax(dv.ctl + 1, n - i);
 }
 
@@ -752,96 +761,85 @@ inline int32_t check_host(const In& in, std::string& err) {
     return PHANT_OK;
 }
 
-}  // namespace tx
+// A call between its steps, which phant_block_transactions[_ex] (below) and phant_block_bodies (bodies.hip.h) both go through:
+//   call_begin    what the host form refuses, the bytes, whether a tuple can occur
+//   call_carve    the call's part of the `io` arena: control words and outputs in front (one span goes back), the internal arrays,
+//                 (host form) offsets and bytes last
+//   call_kernels  decode, hash, (the authorization tuples,) recover: every launch in front of the rules
+//   call_outputs  every output named for CallOutputs
+struct Call {
+    Dev d;
+    AuthDev ad;
+    uint32_t* d_scan;
+    const uint8_t* d_txs;
+    const uint64_t* d_off;
+    uint64_t bytes;
+    uint32_t n, n_auth;
+    bool maybe_tuples;
+};
 
-int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in& xin, phant_txs_ex_out& xout, bool dev, const uint32_t* gtable,
-                           std::string& err) {
-    using namespace tx;
-    const phant_txs_in& in = xin.base;
-    phant_txs_out& out = xout.base;
-    const uint32_t n = in.n, fork = xin.fork;
-    const bool recover = !(in.flags & PHANT_TXS_NO_RECOVERY);
-    CALL_TRY("block_transactions", ws.ensure_mailbox());
-    static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXS_WORDS, "the control words fit their part of the mailbox");
-    volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXS;
-    uint64_t bytes = in.tx_bytes;
+inline int32_t call_begin(Call& c, const In& in, uint32_t fork, bool dev, std::string& err) {
+    std::memset(&c, 0, sizeof c);
+    c.n = in.n, c.d_txs = in.txs, c.d_off = in.tx_off, c.bytes = in.tx_bytes;
     // can the call hold an authorization tuple?  The host form sees every transaction's first byte; the device form cannot know
-    bool maybe_tuples = fork >= FORK_PRAGUE && dev;
+    c.maybe_tuples = fork >= FORK_PRAGUE && dev;
     if (!dev) {
         const int32_t rc = check_host(in, err);
         if (rc) return rc;
-        bytes = in.tx_off[n];
+        c.bytes = in.tx_off[in.n];
         if (fork >= FORK_PRAGUE)
-            for (uint32_t i = 0; i < n && !maybe_tuples; ++i) maybe_tuples = in.tx_off[i + 1u] > in.tx_off[i] && in.txs[in.tx_off[i]] == 4u;
+            for (uint32_t i = 0; i < in.n && !c.maybe_tuples; ++i) c.maybe_tuples = in.tx_off[i + 1u] > in.tx_off[i] && in.txs[in.tx_off[i]] == 4u;
     }
-    if (maybe_tuples && bytes / 27u > 0xffffffffull) return err = "block_transactions: more bytes than 2^32 authorization tuples take", PHANT_E_UNSUPPORTED;
+    if (c.maybe_tuples && c.bytes / 27u > 0xffffffffull) return err = "block_transactions: more bytes than 2^32 authorization tuples take", PHANT_E_UNSUPPORTED;
+    return PHANT_OK;
+}
 
-    // ---- the arena: control words and outputs in front (one span goes back), the internal arrays, (host form) offsets and bytes last
-    Dev d;
-    std::memset(&d, 0, sizeof d);
-    uint32_t* d_scan = nullptr;
-    const uint8_t* d_txs = in.txs;
-    const uint64_t* d_off = in.tx_off;
-    auto carve = [&](auto& io) {
-        d.ctl = io.template take<uint32_t>(CTL_WORDS);
+template <class IO>
+void call_carve(IO& io, Call& c, bool dev) {
+    Dev& d = c.d;
+    const uint32_t n = c.n;
+    d.ctl = io.template take<uint32_t>(CTL_WORDS);
 #define X(m, T, e) d.o.m = io.template take<T>((size_t)n * e);
-        TX_OUTPUTS(X)
+    TX_OUTPUTS(X)
 #undef X
-        d.x.auth_first = io.template take<uint32_t>((size_t)n + 1);
+    d.x.auth_first = io.template take<uint32_t>((size_t)n + 1);
 #define X(m, T, e) d.x.m = io.template take<T>((size_t)n * e);
-        TX_EX_OUTPUTS(X)
+    TX_EX_OUTPUTS(X)
 #undef X
-        d.plan = io.template take<Plan>((size_t)n);
-        d.r = io.template take<uint8_t>(32 * (size_t)n);
-        d.s = io.template take<uint8_t>(32 * (size_t)n);
-        d.recid = io.template take<uint8_t>((size_t)n);
-        d.pre_status = io.template take<uint8_t>((size_t)n);
-        d.auth_at = io.template take<uint32_t>((size_t)n);
-        d.auth_len = io.template take<uint32_t>((size_t)n);
-        if (maybe_tuples) d_scan = io.template take<uint32_t>(scan_scratch_entries(n + 1u));
-        if (!dev) {
-            d_off = io.template take<uint64_t>((size_t)n + 1);
-            d_txs = io.template take<uint8_t>((size_t)bytes + 16);
-        }
-    };
-    if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_transactions", "workspace", err)) return rc;
-    CALL_TRY("block_transactions", hipMemsetAsync(d.ctl, 0, 4 * CTL_WORDS, st));
-
-    // ---- in: (host form) offsets and bytes in ONE copy through the pinned stage where they fit it; (device form) the offsets' check
-    const uint32_t grid256 = (n + 255u) / 256u, grid64 = (n + 63u) / 64u;
+    d.plan = io.template take<Plan>((size_t)n);
+    d.r = io.template take<uint8_t>(32 * (size_t)n);
+    d.s = io.template take<uint8_t>(32 * (size_t)n);
+    d.recid = io.template take<uint8_t>((size_t)n);
+    d.pre_status = io.template take<uint8_t>((size_t)n);
+    d.auth_at = io.template take<uint32_t>((size_t)n);
+    d.auth_len = io.template take<uint32_t>((size_t)n);
+    if (c.maybe_tuples) c.d_scan = io.template take<uint32_t>(scan_scratch_entries(n + 1u));
     if (!dev) {
-        StagedInputs ins(ws, st, d_off, d_txs + bytes);
-        ins.put(d_off, in.tx_off, 8 * ((size_t)n + 1));
-        ins.put(d_txs, in.txs, (size_t)bytes);
-        CALL_TRY("block_transactions", ins.finish());
-    } else {
-        hipLaunchKernelGGL(tx_check_args_kernel, dim3(grid256), dim3(256), 0, st, d_off, n, bytes, d.ctl);
-        CALL_TRY("block_transactions", hipGetLastError());
-        CALL_TRY("block_transactions", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
-        if (mb[0] & F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
-        if (mb[0] & F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
+        c.d_off = io.template take<uint64_t>((size_t)n + 1);
+        c.d_txs = io.template take<uint8_t>((size_t)c.bytes + 16);
     }
+}
 
-    // ---- decode, hash, (the authorization tuples,) recover, rules
-    Rules ru;
-    std::memset(&ru, 0, sizeof ru);
-    if (in.base_fee) load_u256(in.base_fee, ru.base_fee), ru.have_base_fee = 1u;
-    if (xin.blob_base_fee) load_u256(xin.blob_base_fee, ru.blob_base_fee), ru.have_blob_base_fee = 1u;
-    ru.have_gas_limit = (in.flags & PHANT_TXS_HAVE_GAS_LIMIT) ? 1u : 0u;
-    ru.block_gas_limit = in.block_gas_limit;
-    ru.fork = fork;
-    hipLaunchKernelGGL(tx_decode_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, in.chain_id, fork, d);
+inline int32_t call_kernels(Workspaces& ws, hipStream_t st, Call& c, uint64_t chain_id, uint32_t fork, bool recover, const uint32_t* gtable,
+                            std::string& err) {
+    Dev& d = c.d;
+    AuthDev& ad = c.ad;
+    const uint32_t n = c.n, grid64 = (n + 63u) / 64u;
+    const uint8_t* const d_txs = c.d_txs;
+    const uint64_t* const d_off = c.d_off;
+    uint32_t* const d_scan = c.d_scan;
+    volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXS;
+    hipLaunchKernelGGL(tx_decode_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, chain_id, fork, d);
     CALL_TRY("block_transactions", hipGetLastError());
     hipLaunchKernelGGL(tx_hash_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, d.plan, d.o.tx_hash, d.o.sig_hash, d.o.intrinsic_gas);
     CALL_TRY("block_transactions", hipGetLastError());
     const uint32_t low_s = PHANT_RECOVER_LOW_S;  // validateSignatureFields
     uint32_t n_auth = 0;
-    AuthDev ad;
-    std::memset(&ad, 0, sizeof ad);
-    if (maybe_tuples) {
+    if (c.maybe_tuples) {
         CALL_TRY("block_transactions", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
         n_auth = mb[2];
     }
+    c.n_auth = n_auth;
     if (n_auth) {
         // the rows of the tuples, now that they are counted, in an arena of their own (the call's other arrays stay where they are)
         auto carve_auth = [&](auto& io) {
@@ -856,7 +854,7 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
         // (no synchronisation before the arena grows -- the stream is idle: the control words were just read)
         if (const int32_t rc = lay_out_status(lay_out_arena(ws.txa, st, carve_auth, true), "block_transactions", "authorizations", err)) return rc;
         CALL_TRY("block_transactions", launch_exclusive_scan_u32(d.x.auth_first, n + 1u, d_scan, st));
-        hipLaunchKernelGGL(tx_auth_rows_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, in.chain_id, d, ad, n_auth);
+        hipLaunchKernelGGL(tx_auth_rows_kernel, dim3(grid64), dim3(64), 0, st, d_txs, d_off, n, chain_id, d, ad, n_auth);
         CALL_TRY("block_transactions", hipGetLastError());
         hipLaunchKernelGGL(tx_auth_hash_kernel, dim3((n_auth + 63u) / 64u), dim3(64), 0, st, ad, n_auth);
         CALL_TRY("block_transactions", hipGetLastError());
@@ -864,16 +862,22 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
             CALL_TRY("block_transactions", launch_ecrecover(ad.x.auth_hash, ad.r, ad.s, ad.recid, ad.pre_status, n_auth, low_s, gtable, nullptr, ad.x.authority, ad.x.auth_status, st));
     }
     if (recover) CALL_TRY("block_transactions", launch_ecrecover(d.o.sig_hash, d.r, d.s, d.recid, d.pre_status, n, low_s, gtable, nullptr, d.o.sender, d.o.sig_status, st));
-    hipLaunchKernelGGL(tx_rules_kernel, dim3(grid64), dim3(64), 0, st, n, ru, d, recover ? d.o.sig_status : nullptr);
-    CALL_TRY("block_transactions", hipGetLastError());
+    return PHANT_OK;
+}
 
-    // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage);
-    // the rows of the tuples (at most auth_cap of them), which lie in their own arena, by copies of their own in both forms
-    CallOutputs outs(ws, st, dev, d.ctl, d.ctl, Workspaces::MAILBOX_TXS, CTL_WORDS);
-    const size_t auth_rows = std::min(n_auth, xin.auth_cap);
+// how many outputs a call names at most (bodies.hip.h adds its own to them)
 #define X(m, T, e) +1
-    static_assert(0 TX_AUTH_OUTPUTS(X) TX_OUTPUTS(X) TX_EX_OUTPUTS(X) + 1 <= CallOutputs::CAP, "the longest list of outputs fits");
+constexpr int CALL_OUTPUTS = 0 TX_AUTH_OUTPUTS(X) TX_OUTPUTS(X) TX_EX_OUTPUTS(X) + 1;
 #undef X
+static_assert(CALL_OUTPUTS <= CallOutputs::CAP, "the longest list of outputs fits");
+
+// the rows of the tuples (at most auth_cap of them) lie in their own arena: copies of their own in both forms
+inline void call_outputs(CallOutputs& outs, const Call& c, const phant_txs_ex_out& xout, uint32_t auth_cap) {
+    const Dev& d = c.d;
+    const AuthDev& ad = c.ad;
+    const phant_txs_out& out = xout.base;
+    const uint32_t n = c.n;
+    const size_t auth_rows = std::min(c.n_auth, auth_cap);
 #define X(m, T, e) outs.add(xout.m, ad.x.m, auth_rows * e * sizeof(T));
     TX_AUTH_OUTPUTS(X)
 #undef X
@@ -884,6 +888,56 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
 #define X(m, T, e) outs.add(xout.m, d.x.m, (size_t)n * e * sizeof(T));
     TX_EX_OUTPUTS(X)
 #undef X
+}
+
+}  // namespace tx
+
+int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in& xin, phant_txs_ex_out& xout, bool dev, const uint32_t* gtable,
+                           std::string& err) {
+    using namespace tx;
+    const phant_txs_in& in = xin.base;
+    phant_txs_out& out = xout.base;
+    const uint32_t n = in.n, fork = xin.fork;
+    const bool recover = !(in.flags & PHANT_TXS_NO_RECOVERY);
+    CALL_TRY("block_transactions", ws.ensure_mailbox());
+    static_assert(CTL_WORDS <= Workspaces::MAILBOX_TXS_WORDS, "the control words fit their part of the mailbox");
+    volatile uint32_t* const mb = ws.mailbox + Workspaces::MAILBOX_TXS;
+    Call c;
+    if (const int32_t rc = call_begin(c, in, fork, dev, err)) return rc;
+    if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, [&](auto& io) { call_carve(io, c, dev); }), "block_transactions", "workspace", err)) return rc;
+    Dev& d = c.d;
+    CALL_TRY("block_transactions", hipMemsetAsync(d.ctl, 0, 4 * CTL_WORDS, st));
+
+    // ---- in: (host form) offsets and bytes in ONE copy through the pinned stage where they fit it; (device form) the offsets' check
+    const uint32_t grid256 = (n + 255u) / 256u, grid64 = (n + 63u) / 64u;
+    if (!dev) {
+        StagedInputs ins(ws, st, c.d_off, c.d_txs + c.bytes);
+        ins.put(c.d_off, in.tx_off, 8 * ((size_t)n + 1));
+        ins.put(c.d_txs, in.txs, (size_t)c.bytes);
+        CALL_TRY("block_transactions", ins.finish());
+    } else {
+        hipLaunchKernelGGL(tx_check_args_kernel, dim3(grid256), dim3(256), 0, st, c.d_off, n, c.bytes, d.ctl);
+        CALL_TRY("block_transactions", hipGetLastError());
+        CALL_TRY("block_transactions", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
+        if (mb[0] & F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
+        if (mb[0] & F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
+    }
+
+    // ---- decode, hash, (the authorization tuples,) recover, rules
+    Rules ru;
+    std::memset(&ru, 0, sizeof ru);
+    if (in.base_fee) load_u256(in.base_fee, ru.base_fee), ru.have_base_fee = 1u;
+    if (xin.blob_base_fee) load_u256(xin.blob_base_fee, ru.blob_base_fee), ru.have_blob_base_fee = 1u;
+    ru.have_gas_limit = (in.flags & PHANT_TXS_HAVE_GAS_LIMIT) ? 1u : 0u;
+    ru.block_gas_limit = in.block_gas_limit;
+    ru.fork = fork;
+    if (const int32_t rc = call_kernels(ws, st, c, in.chain_id, fork, recover, gtable, err)) return rc;
+    hipLaunchKernelGGL(tx_rules_kernel, dim3(grid64), dim3(64), 0, st, n, ru, d, recover ? d.o.sig_status : nullptr);
+    CALL_TRY("block_transactions", hipGetLastError());
+
+    // ---- out: the control words and everything up to the last wanted output (one span in the host form while it fits the pinned stage)
+    CallOutputs outs(ws, st, dev, d.ctl, d.ctl, Workspaces::MAILBOX_TXS, CTL_WORDS);
+    call_outputs(outs, c, xout, xin.auth_cap);
     CALL_TRY("block_transactions", outs.deliver());
     const volatile uint32_t* const ctl = outs.ctl();
     out.first_bad = n - ctl[1];

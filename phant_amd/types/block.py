@@ -1,6 +1,8 @@
 """Block headers <-> src/types/block.zig:15-69 (`BlockHeader`, `encodeToRLP`) and src/blockchain/blockchain.zig:100-145
 (`validateBlockHeader`): encodings, hashes and the header rules of whole chain segments in ONE call (phant_header_chain), strict
-decoding of raw headers on the host (phant_headers_decode_rlp).  Through the C-ABI; no CPU fallback.
+decoding of raw headers on the host (phant_headers_decode_rlp).  And the bodies those headers commit to, for whole segments in ONE call
+as well (phant_block_bodies; raw blocks split on the host by phant_bodies_decode_rlp): `split_blocks`, `block_bodies`,
+`validate_segment`.  Through the C-ABI; no CPU fallback.
 
 Two deviations from the reference, both where it would panic: a header pair of which exactly one has a base fee, and a parent
 whose gas target is zero while it used gas, set the InvalidBaseFee flag instead."""
@@ -258,3 +260,195 @@ def payload_block_hash(payload_fields: dict, raw_txs, withdrawals, ctx: Context 
                     None if blob is None else int(blob), None if blob is None else int(p["excessBlobGas"]))
     r = header_chain([h], expected_hashes=[bytes(p["blockHash"])], ctx=ctx)
     return r.first_bad == 1, r.hashes[0], h
+
+
+# ---------------------------------------------------------------------------------------------------- bodies of chain segments
+class BodyFlags:
+    """block_flags[b] of block_bodies"""
+    Transaction = L.BODY_TX
+    TransactionsRoot = L.BODY_TXS_ROOT
+    WithdrawalsRoot = L.BODY_WD_ROOT
+    BlobGasUsed = L.BODY_BLOB_GAS
+    NAMES = L.BODY_FLAG_NAMES
+
+
+def _pack_lists(lists):
+    """lists of byte strings -> (bytes back to back, n + 1 offsets, n_lists + 1 firsts); never empty arrays"""
+    items = [bytes(x) for l in lists for x in l]
+    blob = np.frombuffer(b"".join(items) or b"\x00", np.uint8).copy()
+    off = np.cumsum([0] + [len(x) for x in items]).astype(np.uint64)
+    first = np.cumsum([0] + [len(l) for l in lists]).astype(np.uint32)
+    return blob, off, first
+
+
+def pack_bodies(block_txs, block_withdrawals=None):
+    """per block its raw transactions (and, from Shanghai on, its withdrawals, each its RLP list as it stands in the block) -> the packed
+    arrays phant_block_bodies takes: txs, tx_off, block_first, withdrawals, wd_off, wd_first (the last three None without withdrawals)"""
+    block_txs = [list(b) for b in block_txs]
+    txs, tx_off, block_first = _pack_lists(block_txs)
+    a = {"txs": txs, "tx_off": tx_off, "block_first": block_first, "withdrawals": None, "wd_off": None, "wd_first": None}
+    if block_withdrawals is not None:
+        block_withdrawals = [list(b) for b in block_withdrawals]
+        if len(block_withdrawals) != len(block_txs):
+            raise ValueError("one list of withdrawals per block")
+        a["withdrawals"], a["wd_off"], a["wd_first"] = _pack_lists(block_withdrawals)
+    return a
+
+
+SPLIT_OK, SPLIT_BAD_RLP, SPLIT_BAD_TX, SPLIT_UNCLES, SPLIT_BAD_WITHDRAWAL = range(5)
+
+
+def split_blocks(raws, bodies_only=False):
+    """phant_bodies_decode_rlp: raw blocks [header, txs, uncles, withdrawals?] (bodies_only: [txs, uncles, withdrawals?]) -> (the packed
+    arrays of pack_bodies, always with the withdrawals' three, status uint8[n]); a refused block (status != 0: SPLIT_*) has no rows.
+    Host only."""
+    raws = [bytes(r) for r in raws]
+    n = len(raws)
+    blob = np.frombuffer(b"".join(raws) or b"\x00", np.uint8).copy()
+    off = np.cumsum([0] + [len(r) for r in raws]).astype(np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    flags = L.BODIES_NO_HEADER if bodies_only else 0
+    arg = L.PhantBodiesSplit(C.sizeof(L.PhantBodiesSplit))
+    fn = L.lib().phant_bodies_decode_rlp
+    rc = fn(blob.ctypes.data, off.ctypes.data, n, flags, C.byref(arg), status.ctypes.data)  # the totals
+    if rc != L.OK:
+        raise L.PhantError(rc, "phant_bodies_decode_rlp")
+    a = {"txs": np.zeros(max(int(arg.tx_bytes), 1), np.uint8), "tx_off": np.zeros(int(arg.n) + 1, np.uint64), "block_first": np.zeros(n + 1, np.uint32),
+         "withdrawals": np.zeros(max(int(arg.wd_bytes), 1), np.uint8), "wd_off": np.zeros(int(arg.n_wd) + 1, np.uint64), "wd_first": np.zeros(n + 1, np.uint32)}
+    arg.tx_cap, arg.wd_cap, arg.tx_bytes_cap, arg.wd_bytes_cap = int(arg.n), int(arg.n_wd), int(arg.tx_bytes), int(arg.wd_bytes)
+    for k in L.BODIES_SPLIT_ARRAYS:
+        setattr(arg, k, a[k].ctypes.data)
+    rc = fn(blob.ctypes.data, off.ctypes.data, n, flags, C.byref(arg), status.ctypes.data)
+    if rc != L.OK:
+        raise L.PhantError(rc, "phant_bodies_decode_rlp")
+    return a, status[:n]
+
+
+class BlockBodies:
+    """What phant_block_bodies answers: the per-transaction and per-authorization arrays of block_transactions(fork=) over the whole
+    segment (auth_first global), `tx_block`, and per block `block_first_bad`, `block_blob_gas_used`, `transactions_root`,
+    `withdrawals_root` (where computed), `block_flags`; the scalars `first_bad_block`, `first_bad`, `n_auth`, `blob_gas_used`."""
+    FLAG_NAMES = L.BODY_FLAG_NAMES
+
+    def __init__(self, arrays, first_bad_block, first_bad, n_auth, blob_gas_used):
+        self.first_bad_block, self.first_bad, self.n_auth, self.blob_gas_used = first_bad_block, first_bad, n_auth, blob_gas_used
+        self.__dict__.update(arrays)
+        self.n, self.n_blocks = len(self.flags), len(self.block_flags)
+
+    def errors(self, b):
+        """the names of block b's flags"""
+        return [name for k, name in enumerate(self.FLAG_NAMES) if int(self.block_flags[b]) >> k & 1]
+
+
+def _rows32(v, n, what):
+    """None, n integers or n x 32 bytes -> (n, 32) uint8 big-endian, or None"""
+    if v is None:
+        return None
+    if isinstance(v, np.ndarray) and v.dtype == np.uint8:
+        a = np.ascontiguousarray(v).reshape(-1, 32)
+    else:
+        v = list(v)
+        a = np.frombuffer(b"".join(x if isinstance(x, (bytes, bytearray)) else int(x).to_bytes(32, "big") for x in v) or bytes(32), np.uint8).reshape(-1, 32).copy()
+    if len(a) < max(n, 1) and n:
+        raise ValueError(f"{what}: one row per block")
+    return a
+
+
+def block_bodies(bodies, chain_id, fork, base_fee=None, gas_limit=None, blob_base_fee=None, transactions_root=None, withdrawals_root=None,
+                 blob_gas_used=None, recover=True, roots=True, ctx: Context | None = None) -> BlockBodies:
+    """phant_block_bodies over the packed arrays of pack_bodies / split_blocks.  Per block (None: the rule or comparison is skipped):
+    base_fee, blob_base_fee (integers, or (n_blocks, 32) uint8 rows such as a header segment's own array), gas_limit (integers); the
+    expected transactions_root / withdrawals_root (32-byte strings or rows) and blob_gas_used.  roots=False: no root is computed unless
+    one is expected."""
+    ctx = ctx or default_context()
+    a = bodies
+    nb, n = len(a["block_first"]) - 1, len(a["tx_off"]) - 1
+    has_wd = a.get("wd_first") is not None
+    n_wd = len(a["wd_off"]) - 1 if has_wd else 0
+    ins = {k: (None if a.get(k) is None else np.ascontiguousarray(a[k])) for k in ("txs", "tx_off", "block_first", "withdrawals", "wd_off", "wd_first")}
+    ins["base_fee"], ins["blob_base_fee"] = _rows32(base_fee, nb, "base_fee"), _rows32(blob_base_fee, nb, "blob_base_fee")
+    ins["gas_limit"] = None if gas_limit is None else np.ascontiguousarray(gas_limit, np.uint64)
+    ins["transactions_root"] = _rows32(transactions_root, nb, "transactions_root")
+    ins["withdrawals_root"] = _rows32(withdrawals_root, nb, "withdrawals_root") if has_wd else None
+    ins["blob_gas_used"] = None if blob_gas_used is None else np.ascontiguousarray(blob_gas_used, np.uint64)
+    for k in ("gas_limit", "blob_gas_used"):
+        if ins[k] is not None and len(ins[k]) < nb:
+            raise ValueError(f"{k}: one value per block")
+    blob = ins["txs"]
+    flags = (L.TXS_HAVE_GAS_LIMIT if gas_limit is not None else 0) | (0 if recover else L.TXS_NO_RECOVERY)
+    tx_off = ins["tx_off"]
+    cap = sum(int(tx_off[i + 1] - tx_off[i]) for i in range(n) if tx_off[i + 1] > tx_off[i] and blob[int(tx_off[i])] == 4) // 27 if fork >= L.TXS_FORK_PRAGUE else 0
+    arrays = {name: np.zeros((n, k) if k > 1 else n, dtype) for name, dtype, k in L.TX_OUTPUTS if recover or name not in ("sender", "sig_status")}
+    for name, dtype, k in L.TX_EX_OUTPUTS:
+        arrays[name] = np.zeros((n, k) if k > 1 else n + (name == "auth_first"), dtype)
+    auth = {name: np.zeros((cap, k) if k > 1 else cap, dtype) for name, dtype, k in L.TX_AUTH_OUTPUTS if recover or name not in ("authority", "auth_status")}
+    rows = {"n": n, "n_blocks": nb}
+    own = {name: np.zeros((rows[r], k) if k > 1 else rows[r], dtype) for name, dtype, k, r in L.BODIES_OUTPUTS}
+    if not roots:
+        own.pop("transactions_root"), own.pop("withdrawals_root")
+    elif not has_wd:
+        own.pop("withdrawals_root")
+    ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
+    arg = L.PhantBodiesIn(C.sizeof(L.PhantBodiesIn), int(fork), flags, nb, n, n_wd, cap, 0, int(chain_id), ptr(blob) if n else None, ptr(tx_off) if n else None,
+                          int(tx_off[-1]), ins["block_first"].ctypes.data, ptr(ins["withdrawals"]) if n_wd else None, ptr(ins["wd_off"]) if n_wd else None,
+                          int(ins["wd_off"][-1]) if has_wd else 0, *[ptr(ins[k]) for k in L.BODIES_INPUTS[5:]])
+    out_base = L.PhantTxsOut(C.sizeof(L.PhantTxsOut), 0, *[ptr(arrays.get(name)) for name, _, _ in L.TX_OUTPUTS])
+    xout = L.PhantTxsExOut(C.sizeof(L.PhantTxsExOut), 0, 0, out_base, *[arrays[name].ctypes.data for name, _, _ in L.TX_EX_OUTPUTS],
+                           *[ptr(auth.get(name)) for name, _, _ in L.TX_AUTH_OUTPUTS])
+    out = L.PhantBodiesOut(C.sizeof(L.PhantBodiesOut), 0, xout, *[ptr(own.get(name)) for name, _, _, _ in L.BODIES_OUTPUTS])
+    ctx.check(ctx._lib.phant_block_bodies(ctx.handle, C.byref(arg), C.byref(out)))
+    arrays.update({name: x[:int(out.txs.n_auth)] for name, x in auth.items()})
+    arrays.update(own)
+    arrays["blob"] = blob
+    return BlockBodies(arrays, int(out.first_bad_block), int(out.txs.base.first_bad), int(out.txs.n_auth), int(out.txs.blob_gas_used))
+
+
+class SegmentVerdict:
+    """validate_segment's answer: per block `header_flags` (Flags) and `body_flags` (BodyFlags; 0 for a segment's anchor, whose body is
+    not checked, and PHANT_BODY_* otherwise), `split_status` (SPLIT_*), `hashes`, `first_bad` (the least block with any of the three, n
+    if none), and the two calls' results `headers` and `bodies`."""
+
+    def __init__(self, header_flags, body_flags, split_status, hashes, headers, bodies):
+        self.header_flags, self.body_flags, self.split_status, self.hashes, self.headers, self.bodies = header_flags, body_flags, split_status, hashes, headers, bodies
+        bad = np.flatnonzero((header_flags != 0) | (body_flags != 0) | (split_status != 0))
+        self.first_bad = int(bad[0]) if len(bad) else len(header_flags)
+
+
+def validate_segment(raw_blocks, seg_first=None, chain_id=1, fork=L.TXS_FORK_PRAGUE, recover=True, ctx: Context | None = None) -> SegmentVerdict:
+    """Headers and bodies of raw blocks [header, txs, uncles, withdrawals?] in two calls: phant_header_chain over the decoded headers
+    (seg_first as there; a segment's first block is its anchor), phant_block_bodies over the split bodies with the headers' own arrays
+    as parameters and expectations: base fee, gas limit, transactions root, withdrawals root (where the headers have one), blob gas used
+    (where they have it), and each block's blob base fee from its parent's excess blob gas.  An anchor's body is not checked (its
+    parent's excess blob gas is unknown): its transactions do not enter the call."""
+    from .transaction import blob_base_fee as _blob_base_fee
+    ctx = ctx or default_context()
+    raws = [bytes(r) for r in raw_blocks]
+    n = len(raws)
+    ha, hstatus = decode_arrays(raws, from_blocks=True)
+    if hstatus.any():
+        raise ValueError(f"block {int(np.flatnonzero(hstatus)[0])} does not begin with a canonical header")
+    chain = header_chain(None, seg_first, ctx=ctx, arrays=ha)
+    seg = np.asarray([0, n] if seg_first is None else seg_first, np.int64)
+    anchor = np.zeros(n, bool)
+    anchor[seg[:-1][seg[:-1] < n]] = True
+    body = np.flatnonzero(~anchor)
+    a, status = split_blocks([raws[i] for i in body])
+    split_status = np.zeros(n, np.uint8)
+    split_status[body] = status
+    nf = ha["n_fields"][:n]
+    with_wd, with_blob = bool(len(body)) and bool((nf[body] >= 17).all()), bool(len(body)) and bool((nf[body] >= 19).all())
+    if not with_wd:
+        if int(a["wd_first"][-1]):
+            raise ValueError("a block carries withdrawals although a header of the segment has no withdrawals root")
+        a = dict(a, withdrawals=None, wd_off=None, wd_first=None)
+    blob_fee = None
+    if with_blob and fork >= L.TXS_FORK_CANCUN:
+        blob_fee = [_blob_base_fee(int(ha["excess_blob_gas"][i - 1]), fork) for i in body]
+    pick = lambda name: np.ascontiguousarray(ha[name][body])  # noqa: E731
+    bodies = block_bodies(a, chain_id, fork, base_fee=pick("base_fee") if bool(len(body)) and bool((nf[body] >= 16).all()) else None, gas_limit=pick("gas_limit"),
+                          blob_base_fee=blob_fee, transactions_root=pick("transactions_root"), withdrawals_root=pick("withdrawals_root") if with_wd else None,
+                          blob_gas_used=pick("blob_gas_used") if with_blob else None, recover=recover, ctx=ctx) if len(body) else None
+    body_flags = np.zeros(n, np.uint32)
+    if bodies is not None:
+        body_flags[body] = bodies.block_flags
+    return SegmentVerdict(np.asarray(chain.flags, np.uint32).copy(), body_flags, split_status, chain.hashes, chain, bodies)
