@@ -1549,6 +1549,93 @@ PHANT_API int32_t phant_block_roots(phant_ctx *ctx, const uint8_t *const *items,
                                     const uint32_t *bloom_item_receipt, uint32_t n_bloom_items, uint32_t n_receipts,
                                     uint8_t *blooms);
 
+/* ------------------------------------------------------- range proofs
+ * phant_mpt_verify_ranges decides, for n_ranges ranges at once, whether a sorted run of consecutive leaves is EXACTLY what the trie
+ * under a trusted root holds between an origin and the run's last key, and whether anything lies to the right of the run (snap
+ * sync's AccountRange / StorageRanges; any state filled chunk by chunk from untrusted peers).  tests/range_ref.py is the same
+ * definition in plain Python.
+ *
+ * Keys are 32 bytes (64 nibbles).  The call holds ONE node set for all its ranges: nodes[node_off[i] .. node_off[i+1]), any order,
+ * every node hashed once; a node that nothing reachable refers to is never decoded.  Range r: roots[r], origins[r], has_proof[r]
+ * and the leaves leaf_first[r] .. leaf_first[r+1]: keys (32 bytes each) and vals[val_off[j] .. val_off[j+1]), the full leaf values.
+ *
+ * For one range with leaves k_0 < ... < k_(m-1) the ITEM LIST is the concatenation of
+ *  1. (has_proof) what lies to the LEFT of origin.  Walk origin's path from the root through the set.  At a branch at depth d every
+ *     non-empty slot s < origin[d] is an opaque reference with path origin[0..d) + s.  Where the walk leaves the path at a leaf or an
+ *     extension whose path is SMALLER than origin's nibbles there, that leaf (with its value from the node) or that extension's child
+ *     (a known branch, with the extension's path) is an item; a GREATER one is none: it lies in the range and the leaves must supply
+ *     it.  The walk ends at an empty slot, at origin's own leaf (no item: it is k_0, or the root will not match) or at a divergence.
+ *  2. the m leaves with the caller's values.
+ *  3. (has_proof and m > 0) what lies to the RIGHT of k_(m-1): the mirror walk -- slots s > k_(m-1)[d], a diverging leaf / extension
+ *     only when it is GREATER.  has_more = this walk found an item.
+ * The range is VALID iff the list is strictly ordered and prefix-free and the root of the trie over it (the empty list: the empty
+ * root; a root node is always hashed) equals roots[r].  Without a proof origin is ignored and the leaves are the whole trie; with a
+ * proof and no leaves the claim is "nothing at or above origin".  has_more is 0 without a proof, without leaves and on failure.
+ *
+ * status[r] is PHANT_RANGE_VALID or the first failure in this order:
+ *  1. the leaf rules, at the least leaf that breaks one, there in this order: PHANT_RANGE_EMPTY_VALUE (length 0),
+ *     PHANT_RANGE_VALUE_TOO_LONG (more than 560 bytes), PHANT_RANGE_BAD_ORDER (the key is not greater than the one before it),
+ *     PHANT_RANGE_BELOW_ORIGIN (the first leaf of a range with a proof is below origin).  bad_leaf[r] = that leaf's index in the
+ *     call, else 0xFFFFFFFF.
+ *  2. the walks, origin's first: PHANT_PROOF_MISSING_NODE (a reference nothing in the set hashes to), PHANT_PROOF_BAD_NODE (not
+ *     canonical RLP of a trie node, a branch with a value, a path beyond 64 nibbles).
+ *  3. PHANT_RANGE_ROOT_MISMATCH: everything else -- an item of the proof that overlaps or precedes a leaf, a branch left with one
+ *     child whose type the set does not say (such a reference is never looked up and merged), a leaf of the proof itself longer
+ *     than 560 bytes, another root.
+ * computed_root[r] = the root built (32 zero bytes on failure).  A failing range changes nothing about any other range of the call.
+ * n_failed = ranges that are not VALID, first_failed = the least of them (n_ranges: none).
+ *
+ * Any output pointer may be NULL.  PHANT_E_INVALID_ARG, with nothing written: a wrong struct_size, reserved != 0, a NULL input
+ * whose count is not zero (origins is needed when some has_proof is set -- the device form asks for it whenever n_ranges > 0;
+ * nodes / node_off with n_nodes == 0 and keys / vals / val_off with n_leaves == 0 may be NULL), leaf_first / val_off / node_off
+ * that do not start at 0, go backwards or do not end at n_leaves / vals_len / nodes_len, leaves or nodes (n_leaves, n_nodes != 0)
+ * in a call without a range.  PHANT_E_UNSUPPORTED: 2^31 leaves + ranges or more.  PHANT_E_OOM: an item list (the leaves and what the
+ * walks leave beside their paths) of 2^30 items or more, like memory that cannot be had.  n_ranges == 0 without leaves and nodes is
+ * PHANT_OK.  Host form: checked on the host, one staged upload, the launches, one copy back that
+ * ends at the last wanted output, one synchronisation.  Device form: every array is device memory (uint64_t arrays 8-byte, uint32_t
+ * arrays 4-byte aligned; misaligned: PHANT_E_INVALID_ARG), both structs host memory; the offsets are checked by a kernel whose verdict
+ * the host reads before any other kernel indexes with them; the call synchronises the ctx stream. */
+#define PHANT_RANGE_VALID 1
+#define PHANT_RANGE_EMPTY_VALUE 32    /* a leaf without a value */
+#define PHANT_RANGE_VALUE_TOO_LONG 33 /* a leaf value of more than 560 bytes */
+#define PHANT_RANGE_BAD_ORDER 34      /* a key not greater than the one before it */
+#define PHANT_RANGE_BELOW_ORIGIN 35   /* the first leaf lies in front of the origin */
+#define PHANT_RANGE_ROOT_MISMATCH 36  /* the leaves and the proof do not make the trusted root */
+typedef struct phant_ranges_in {
+    uint32_t struct_size; /* = sizeof(phant_ranges_in) */
+    uint32_t n_ranges;
+    uint32_t n_leaves;
+    uint32_t n_nodes;
+    uint32_t reserved[2]; /* 0 */
+    uint64_t vals_len;
+    uint64_t nodes_len;
+    /* per range */
+    const uint8_t *roots;       /* n_ranges x 32 */
+    const uint8_t *origins;     /* n_ranges x 32 */
+    const uint32_t *leaf_first; /* n_ranges + 1 */
+    const uint8_t *has_proof;   /* n_ranges */
+    /* per leaf */
+    const uint8_t *keys;     /* n_leaves x 32 */
+    const uint8_t *vals;     /* vals_len */
+    const uint64_t *val_off; /* n_leaves + 1 */
+    /* the node set */
+    const uint8_t *nodes;     /* nodes_len */
+    const uint64_t *node_off; /* n_nodes + 1 */
+} phant_ranges_in;
+typedef struct phant_ranges_out {
+    uint32_t struct_size; /* = sizeof(phant_ranges_out) */
+    uint32_t n_failed;    /* results ... */
+    uint32_t first_failed;
+    uint32_t reserved[2]; /* 0 */
+    /* per range */
+    uint8_t *status;        /* PHANT_RANGE_* / PHANT_PROOF_MISSING_NODE / PHANT_PROOF_BAD_NODE */
+    uint8_t *has_more;      /* 0 / 1 */
+    uint8_t *computed_root; /* 32 */
+    uint32_t *bad_leaf;
+} phant_ranges_out;
+PHANT_API int32_t phant_mpt_verify_ranges(phant_ctx *ctx, const phant_ranges_in *in, phant_ranges_out *out);
+PHANT_API int32_t phant_mpt_verify_ranges_dev(phant_ctx *ctx, const phant_ranges_in *in, phant_ranges_out *out);
+
 /* ------------------------------------------- sharded trie roots (multi-GPU mptize)
  * a trie shards by the top key nibble -- 16 sub-tries, one exchange of <= 33-byte
  * child references, then the root branch.  A rank calls phant_mpt_root_nodes over its sub-tries (one

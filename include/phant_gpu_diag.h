@@ -158,10 +158,16 @@ enum {
     PHANT_DIAG_ADVANCE_ESTIMATE_BYTES, /* phant_exec_witness_advance: > 0: the room estimated for the emitted nodes is this many bytes (and a
                                           node descriptor per 64 of them), so that a test reaches the run with the counted sizes; 0: the
                                           call's own estimate.  A TEST HOOK ONLY: the result does not depend on it */
-    PHANT_DIAG_VERIFY_LIST_WGS         /* two-tier verify: > 0: the grid that hashes the listed shallow nodes is at most this many workgroups
+    PHANT_DIAG_VERIFY_LIST_WGS,        /* two-tier verify: > 0: the grid that hashes the listed shallow nodes is at most this many workgroups
                                           (of four waves), so that a test with a few hundred proofs reaches a queue longer than the grid,
                                           whose waves then stride over it; 0: sized from the batch.  A TEST HOOK ONLY: the result does not
                                           depend on it */
+    PHANT_DIAG_RANGES_NO_LEAF_PASS,    /* phant_mpt_verify_ranges: != 0: no leaf pass -- every leaf is encoded and hashed by the lane that builds
+                                          its parent branch, as in the post-state build (the A/B of DESIGN.md section 7p) */
+    PHANT_DIAG_RANGES_ITEMS_PER_RANGE  /* phant_mpt_verify_ranges: >= 0: the room estimated for the items outside the leaves, per range, so
+                                          that a test whose ranges' walks leave more than that reaches the run with the counted size
+                                          (0: room for the leaves and 64 items); -1: the call's own estimate.  A TEST HOOK
+                                          ONLY: the result does not depend on it */
 };
 PHANT_API int32_t phant_diag_set(phant_ctx *ctx, uint32_t knob, int64_t value);
 

@@ -36,6 +36,14 @@ PROOF_BAD_INPUT = 21
 PROOF_MISMATCH = 22
 PROOF_BAD_VALUE = 23
 PROOF_MISSING_SIBLING = 24
+# PHANT_RANGE_*: phant_mpt_verify_ranges (beside PROOF_MISSING_NODE and PROOF_BAD_NODE)
+RANGE_VALID = 1
+RANGE_EMPTY_VALUE = 32
+RANGE_VALUE_TOO_LONG = 33
+RANGE_BAD_ORDER = 34
+RANGE_BELOW_ORIGIN = 35
+RANGE_ROOT_MISMATCH = 36
+RANGE_NO_LEAF = 0xFFFFFFFF
 POST_KEEP, POST_SET, POST_DELETE = 0, 1, 2
 PROVE_MAY_REMOVE = 1
 ADVANCE_KEEP_OLD = 1
@@ -81,6 +89,8 @@ SYMBOLS = {
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_mpt_verify_ranges": (_i32, [_vp, _vp, _vp]),
+    "phant_mpt_verify_ranges_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_access_lists": (_i32, [_vp, _vp, _vp]),
     "phant_block_access_lists_dev": (_i32, [_vp, _vp, _vp]),
     "phant_diag_secp_op": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
@@ -361,6 +371,24 @@ class PhantAccessOut(C.Structure):
     """phant_access_out (include/phant_gpu.h)"""
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_tuples", "n_keys", "n_missing_accounts", "n_missing_slots", "first_malformed",
                                                 "tuple_cap", "key_cap")] + [(name, C.c_void_p) for name, _, _, _, _ in ACCESS_OUTPUTS]
+
+
+# phant_ranges_in's arrays in the struct's order
+RANGES_INPUTS = ("roots", "origins", "leaf_first", "has_proof", "keys", "vals", "val_off", "nodes", "node_off")
+# phant_ranges_out's arrays in the struct's order: (name, numpy dtype, elements per range)
+RANGES_OUTPUTS = (("status", "u1", 1), ("has_more", "u1", 1), ("computed_root", "u1", 32), ("bad_leaf", "u4", 1))
+
+
+class PhantRangesIn(C.Structure):
+    """phant_ranges_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_ranges", "n_leaves", "n_nodes")] + \
+               [("reserved", C.c_uint32 * 2), ("vals_len", C.c_uint64), ("nodes_len", C.c_uint64)] + [(name, C.c_void_p) for name in RANGES_INPUTS]
+
+
+class PhantRangesOut(C.Structure):
+    """phant_ranges_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_failed", "first_failed")] + [("reserved", C.c_uint32 * 2)] + \
+               [(name, C.c_void_p) for name, _, _ in RANGES_OUTPUTS]
 
 
 class PhantProveOut(C.Structure):

@@ -166,6 +166,25 @@ PHANT_DEV void keccak256_global(Sponge& s, const uint8_t* __restrict__ p, uint64
     keccak_f1600(s);
 }
 
+// Keccak-256 of the `total` bytes at the start of a ZERO-FILLED slot of a lane's own (LDS: trie_build.hip's and range_verify.hip.h's
+// staged nodes; capacity >= (total / 136 + 1) * 136 bytes): the padding goes into the slot, the sponge absorbs whole dwords.
+PHANT_DEV void keccak256_staged(Sponge& s, uint32_t* slot, uint32_t total) {
+    uint8_t* b = reinterpret_cast<uint8_t*>(slot);
+    const uint32_t nb = total / RATE + 1u;   // rate blocks (pad10*1 always adds at least one byte)
+    b[total] = 0x01;                         // domain byte of Keccak-256 (hasher.zig -> Zig std Keccak256)
+    b[nb * RATE - 1u] |= 0x80;               // (the same byte when total = 136 nb - 1: 0x81)
+    sponge_zero(s);
+    for (uint32_t k = 0; k < nb; ++k) {      // exec-masked: lanes run as many blocks as their node has
+        const uint32_t* w = slot + k * RATE_DWORDS;
+#pragma unroll
+        for (int i = 0; i < 17; ++i) {
+            s.lo[i] ^= w[2 * i];
+            s.hi[i] ^= w[2 * i + 1];
+        }
+        keccak_f1600(s);
+    }
+}
+
 PHANT_DEV void store_digest(const Sponge& s, uint8_t* __restrict__ out) {
     // out is 32-byte aligned in every batch API (row i at out + 32 i)
     uint4* o = reinterpret_cast<uint4*>(out);

@@ -84,6 +84,8 @@ struct phant_ctx {
     uint32_t code_form = 0;
     bool post_raw_slot_keys = false;  // PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS
     uint64_t advance_estimate = 0;    // PHANT_DIAG_ADVANCE_ESTIMATE_BYTES (0: the call's own estimate)
+    bool ranges_no_leaf_pass = false;     // PHANT_DIAG_RANGES_NO_LEAF_PASS
+    int64_t ranges_items_per_range = -1;  // PHANT_DIAG_RANGES_ITEMS_PER_RANGE (-1: the call's own estimate)
     uint32_t* secp_gtable = nullptr;  // phant_ecrecover_batch: 1 G .. 255 G, computed on the device by the first call that needs it
 };
 
@@ -470,6 +472,8 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_POSTSTATE_RAW_SLOT_KEYS: c->post_raw_slot_keys = value != 0; return PHANT_OK;
         case PHANT_DIAG_ADVANCE_ESTIMATE_BYTES: c->advance_estimate = value > 0 ? (uint64_t)value : 0u; return PHANT_OK;
         case PHANT_DIAG_VERIFY_LIST_WGS: c->tune.list_wgs_cap = (uint32_t)(value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : value); return PHANT_OK;
+        case PHANT_DIAG_RANGES_NO_LEAF_PASS: c->ranges_no_leaf_pass = value != 0; return PHANT_OK;
+        case PHANT_DIAG_RANGES_ITEMS_PER_RANGE: c->ranges_items_per_range = value < 0 ? -1 : value > 1922 ? 1922 : value; return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }
@@ -1773,6 +1777,168 @@ int32_t phant_mpt_verify_nodeset(phant_ctx* c, const uint8_t* roots, uint32_t n_
     h.total_nodes = total_nodes;
     return verify_host(c, h, NODESET, "mpt_verify_nodeset");
 }
+
+/* ------------------------------------------------------------------ range proofs (range_verify.hip.h) */
+
+// One run with room for cap_items items: carve -> (host form) one staged upload / (device form) the offsets' check -> node-set hash ->
+// the range kernels -> one copy back.  *need_items: the list's length (beyond cap_items nothing was built).
+static int32_t verify_ranges_run(phant_ctx* c, const phant_ranges_in& in, phant_ranges_out& out, bool dev, uint32_t cap_items, uint32_t* need_items) {
+    const char* const who = dev ? "mpt_verify_ranges_dev" : "mpt_verify_ranges";
+    const uint32_t R = in.n_ranges, L = in.n_leaves, N = in.n_nodes, lanes = L + 2u * R;
+    hipStream_t s = c->stream;
+    phant::Workspaces& ws = c->ws;
+    HIP_TRY(c, ws.ensure_mailbox());
+    phant::RangeArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_ranges = R, a.n_leaves = L, a.n_nodes = N, a.vals_len = in.vals_len, a.nodes_len = in.nodes_len;
+    a.roots = in.roots, a.origins = in.origins, a.leaf_first = in.leaf_first, a.has_proof = in.has_proof, a.keys = in.keys, a.vals = in.vals,
+    a.val_off = in.val_off, a.nodes = in.nodes, a.node_off = in.node_off;
+    a.cap_items = cap_items;
+    a.leaf_pass = c->ranges_no_leaf_pass ? 0u : 1u;
+    // the arena: the zeroed words and the outputs in front (one span goes back), (host form) the inputs, then the workspace
+    const size_t zero_words = (size_t)phant::RANGE_CTL_WORDS + 8 + 4 * (size_t)R;  // ctl, counters, walk_err x 2, more, trie_bad
+    uint32_t* zero = nullptr;
+    uint8_t *in_begin = nullptr, *in_end = nullptr;
+    uint8_t *d_roots = nullptr, *d_origins = nullptr, *d_hp = nullptr, *d_keys = nullptr, *d_vals = nullptr, *d_nodes = nullptr;
+    uint32_t* d_lf = nullptr;
+    uint64_t *d_voff = nullptr, *d_noff = nullptr;
+    const auto carve = [&](auto& io) {
+        zero = io.template take<uint32_t>(zero_words);
+        a.status = io.template take<uint8_t>(R);
+        a.has_more = io.template take<uint8_t>(R);
+        a.computed_root = io.template take<uint8_t>((size_t)R * 32);
+        a.out_bad_leaf = io.template take<uint32_t>(R);
+        if (!dev) {
+            in_begin = d_roots = io.template take<uint8_t>((size_t)R * 32);
+            d_origins = io.template take<uint8_t>((size_t)R * 32);
+            d_lf = io.template take<uint32_t>((size_t)R + 1);
+            d_hp = io.template take<uint8_t>(R);
+            d_keys = io.template take<uint8_t>((size_t)L * 32 + 4);
+            d_vals = io.template take<uint8_t>((size_t)in.vals_len + 16);
+            d_voff = io.template take<uint64_t>((size_t)L + 1);
+            d_nodes = io.template take<uint8_t>((size_t)in.nodes_len + 16);
+            d_noff = io.template take<uint64_t>((size_t)N + 1);
+            in_end = io.template take<uint8_t>(0);
+        }
+        a.bad_leaf = io.template take<uint32_t>(R);
+        a.built_root = io.template take<uint8_t>((size_t)R * 32);
+        a.cnt = io.template take<uint32_t>((size_t)lanes + 4);
+        a.scan_scratch = io.template take<uint32_t>(phant::scan_scratch_entries(lanes + 1u) + 4);
+        a.items_raw = io.template take<uint8_t>((size_t)cap_items * phant::POSTSTATE_ITEM_BYTES);
+    };
+    if (const int32_t rc = lay_out(c, s, ws.io, carve)) return rc;
+    a.ctl = zero, a.counters = zero + phant::RANGE_CTL_WORDS, a.walk_err = a.counters + 8, a.more = a.walk_err + 2 * (size_t)R, a.trie_bad = a.more + R;
+    if (const int32_t rc = nodeset_prepare(c, N, s, c->ns)) return rc;
+    HIP_TRY(c, hipMemsetAsync(zero, 0, 4 * zero_words, s));
+    HIP_TRY(c, hipMemsetAsync(a.bad_leaf, 0xff, 4 * (size_t)R, s));
+    if (!dev) {
+        phant::StagedInputs ins(ws, s, in_begin, in_end);
+        ins.put(d_roots, in.roots, (size_t)R * 32);
+        ins.put(d_origins, in.origins, (size_t)R * 32);
+        ins.put(d_lf, in.leaf_first, ((size_t)R + 1) * 4);
+        ins.put(d_hp, in.has_proof, R);
+        ins.put(d_keys, in.keys, (size_t)L * 32);
+        ins.put(d_vals, in.vals, (size_t)in.vals_len);
+        if (L) ins.put(d_voff, in.val_off, ((size_t)L + 1) * 8);
+        ins.put(d_nodes, in.nodes, (size_t)in.nodes_len);
+        if (N) ins.put(d_noff, in.node_off, ((size_t)N + 1) * 8);
+        HIP_TRY(c, ins.finish());
+        a.roots = d_roots, a.origins = d_origins, a.leaf_first = d_lf, a.has_proof = d_hp, a.keys = d_keys, a.vals = d_vals,
+        a.val_off = L ? d_voff : nullptr, a.nodes = d_nodes, a.node_off = N ? d_noff : nullptr;
+    } else {
+        HIP_TRY(c, phant::launch_range_check(a, s));
+        HIP_TRY(c, ws.read_words(phant::Workspaces::MAILBOX_RANGES, a.ctl, phant::RANGE_CTL_WORDS, s));
+        if (ws.mailbox[phant::Workspaces::MAILBOX_RANGES + phant::RANGE_CTL_CHECK])
+            return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": leaf_first / val_off / node_off do not run from 0 to their totals without going backwards").c_str());
+    }
+    {
+        TimedRegion t(c);
+        phant::VerifyArgs v{};
+        v.nodes = a.nodes, v.nodes_len = a.nodes_len, v.node_off = a.node_off, v.n = R, v.total_nodes = N;
+        hipError_t e = phant::launch_nodeset_hash(v, N, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s, nodeset_tune_on(c, c->ns));
+        if (e == hipSuccess) e = phant::launch_range_verify(a, c->ns.cap_nodes, c->ns.dv.base, c->ns.epoch, c->ns_salt, s);
+        if (e != hipSuccess) {
+            c->ns.dirty = true;
+            (void)hipStreamSynchronize(s);
+            return fail(c, PHANT_E_DEVICE, (std::string(who) + ": launch").c_str(), e);
+        }
+    }
+    // out: the control words and everything up to the last wanted output (a run whose list outgrew its room has built nothing and
+    // left the outputs alone: what goes back then is overwritten by the run with the counted room)
+    phant::CallOutputs outs(ws, s, dev, a.ctl, a.ctl, phant::Workspaces::MAILBOX_RANGES, phant::RANGE_CTL_WORDS);
+    outs.add(out.status, a.status, R);
+    outs.add(out.has_more, a.has_more, R);
+    outs.add(out.computed_root, a.computed_root, (size_t)R * 32);
+    outs.add(out.bad_leaf, a.out_bad_leaf, (size_t)R * 4);
+    HIP_TRY(c, outs.deliver());
+    const volatile uint32_t* const w = outs.ctl();
+    *need_items = w[phant::RANGE_CTL_ITEMS];
+    out.n_failed = w[phant::RANGE_CTL_FAILED], out.first_failed = R - w[phant::RANGE_CTL_FIRST];
+    return PHANT_OK;
+}
+
+static int32_t verify_ranges_impl(phant_ctx* c, const phant_ranges_in* in, phant_ranges_out* out, bool dev) {
+    const char* const who = dev ? "mpt_verify_ranges_dev" : "mpt_verify_ranges";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_ranges_in) || out->struct_size != sizeof(phant_ranges_out)) return bad("wrong struct_size");
+    if (in->reserved[0] != 0u || in->reserved[1] != 0u || out->reserved[0] != 0u || out->reserved[1] != 0u) return bad("reserved is not 0");
+    const uint32_t R = in->n_ranges, L = in->n_leaves, N = in->n_nodes;
+    if (R && (!in->roots || !in->leaf_first || !in->has_proof)) return bad("null roots / leaf_first / has_proof");
+    if (L && (!in->keys || !in->val_off)) return bad("null keys / val_off");
+    if (in->vals_len && !in->vals) return bad("null vals");
+    if (N && !in->node_off) return bad("null node_off");
+    if (in->nodes_len && !in->nodes) return bad("null nodes");
+    if (R == 0 && (L || N)) return bad("leaves or nodes without a range");
+    if (dev && R && !in->origins) return bad("null origins");
+    if ((uint64_t)L + 2ull * R >= 0x7fffffffull) return fail(c, PHANT_E_UNSUPPORTED, (std::string(who) + ": 2^31 leaves + ranges or more").c_str());
+    if (dev) {  // (kernels read these as words; the outputs arrive by device-to-device copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->val_off | (uintptr_t)in->node_off;
+        const uintptr_t w4 = (uintptr_t)in->leaf_first | (uintptr_t)out->bad_leaf;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    } else if (R) {
+        const char* const offsets = "leaf_first / val_off / node_off do not run from 0 to their totals without going backwards";
+        if (in->leaf_first[0] != 0u || in->leaf_first[R] != L) return bad(offsets);
+        for (uint32_t r = 0; r < R; ++r)
+            if (in->leaf_first[r + 1] < in->leaf_first[r]) return bad(offsets);
+        if (L && (in->val_off[0] != 0u || in->val_off[L] != in->vals_len)) return bad(offsets);
+        if (!L && in->vals_len) return bad(offsets);
+        for (uint32_t j = 0; j < L; ++j)
+            if (in->val_off[j + 1] < in->val_off[j]) return bad(offsets);
+        if (N && (in->node_off[0] != 0u || in->node_off[N] != in->nodes_len)) return bad(offsets);
+        if (!N && in->nodes_len) return bad(offsets);
+        for (uint32_t i = 0; i < N; ++i)
+            if (in->node_off[i + 1] < in->node_off[i]) return bad(offsets);
+        bool any_proof = false;
+        for (uint32_t r = 0; r < R; ++r) any_proof = any_proof || in->has_proof[r] != 0u;
+        if (any_proof && !in->origins) return bad("null origins");
+    }
+    if (R == 0) {
+        out->n_failed = 0, out->first_failed = 0;
+        return PHANT_OK;
+    }
+    if (dev && ((!L && in->vals_len) || (!N && in->nodes_len))) return bad("bytes without leaves / nodes");
+    DeviceGuard g(c->device);
+    // The item list: the leaves and what the two walks of a range leave beside their paths -- at most 2 x (64 x 15 + 1) = 1 922 per
+    // range, and in a trie of 16^k keys about 15 k.  Room for sixteen full levels a walk (2 x 241 a range: a balanced trie of 2^64 keys)
+    // is what an ordinary call gets; a list that outgrows it is counted exactly and the call's kernels run once more with that room.
+    const uint64_t per_range = c->ranges_items_per_range >= 0 ? (uint64_t)c->ranges_items_per_range : 482u;
+    uint64_t cap = (uint64_t)L + per_range * R + 64u;
+    for (int attempt = 0;; ++attempt) {
+        if (cap >= 0x40000000ull) return fail(c, PHANT_E_OOM, (std::string(who) + ": item list too long").c_str());
+        uint32_t need = 0;
+        const int32_t rc = verify_ranges_run(c, *in, *out, dev, (uint32_t)cap, &need);
+        if (rc) return rc;
+        if (need <= cap) return PHANT_OK;
+        if (attempt == 1) return fail(c, PHANT_E_DEVICE, (std::string(who) + ": the item list did not settle").c_str());
+        cap = need;
+    }
+}
+
+int32_t phant_mpt_verify_ranges(phant_ctx* c, const phant_ranges_in* in, phant_ranges_out* out) { return verify_ranges_impl(c, in, out, false); }
+
+int32_t phant_mpt_verify_ranges_dev(phant_ctx* c, const phant_ranges_in* in, phant_ranges_out* out) { return verify_ranges_impl(c, in, out, true); }
 
 /* ------------------------------------------------------------------ streaming */
 

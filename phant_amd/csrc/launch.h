@@ -239,6 +239,9 @@ struct PoststateArgs {
     const uint32_t* sink_undecided; // may be null: the device sort's flag -- != 0: this run's key order is not one, it will be discarded
     uint64_t sink_cap_bytes;
     uint32_t sink_cap_desc;
+    // phant_mpt_verify_ranges (range_verify.hip.h; both null: the post-state calls): every trie of the call stands for itself
+    uint32_t* trie_bad;             // per trie, zeroed by the caller: != 0: this trie cannot be built (nothing else of the call is affected)
+    const uint8_t* leaf_vals;       // where the value of an IK_LEAF_OLD item with key != 0 lies (src is an offset in here, not in nodes)
 };
 constexpr size_t POSTSTATE_ITEM_BYTES = 96;
 enum : uint32_t { POST_SINK_NODES = 0, POST_SINK_OVERFLOW = 1 };  // PoststateArgs::sink_cnt
@@ -248,6 +251,45 @@ enum : uint32_t { POST_CNT_ITEMS = 3, POST_CNT_INTERNAL = 4, POST_CNT_EMIT_FAILE
 hipError_t launch_poststate_actions(const PoststateArgs& p, hipStream_t st);
 hipError_t launch_poststate_build(const PoststateArgs& p, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2],
                                   hipStream_t st);
+// range_verify.hip.h (included by mpt_verify_nodeset.hip): range proofs (phant_mpt_verify_ranges) on the record table of the call's
+// epoch.  Every pointer is device memory of the call; the inputs as include/phant_gpu.h describes them.
+struct RangeArgs {
+    uint32_t n_ranges, n_leaves, n_nodes;
+    const uint8_t* roots;         // n_ranges x 32
+    const uint8_t* origins;       // n_ranges x 32
+    const uint32_t* leaf_first;   // n_ranges + 1
+    const uint8_t* has_proof;     // n_ranges
+    const uint8_t* keys;          // n_leaves x 32
+    const uint8_t* vals;
+    const uint64_t* val_off;      // n_leaves + 1
+    uint64_t vals_len;
+    const uint8_t* nodes;
+    const uint64_t* node_off;     // n_nodes + 1
+    uint64_t nodes_len;
+    // the call's workspace
+    uint32_t* ctl;                // RANGE_CTL_*: zeroed by the caller
+    uint32_t* counters;           // 8: the build's PRE_CNT_* / POST_CNT_*, zeroed by the caller
+    uint32_t* bad_leaf;           // n_ranges: the least leaf that breaks a rule (the caller fills it with ff..ff)
+    uint32_t* walk_err;           // 2 x n_ranges: what the origin's / the last key's walk failed with, zeroed by the caller
+    uint32_t* more;               // n_ranges: the right walker emitted something, zeroed by the caller
+    uint32_t* trie_bad;           // n_ranges, zeroed by the caller
+    uint8_t* built_root;          // n_ranges x 32
+    uint32_t* cnt;                // n_leaves + 2 n_ranges + 1 (16-byte aligned): items per lane, then their offsets
+    uint32_t* scan_scratch;       // scan_scratch_entries(n_leaves + 2 n_ranges + 1)
+    void* items_raw;              // cap_items x POSTSTATE_ITEM_BYTES
+    uint32_t cap_items;
+    uint32_t leaf_pass;           // 0: the leaves go through the branch lanes' attach (PHANT_DIAG_RANGES_NO_LEAF_PASS)
+    // out
+    uint8_t* status;              // n_ranges
+    uint8_t* has_more;            // n_ranges
+    uint8_t* computed_root;       // n_ranges x 32
+    uint32_t* out_bad_leaf;       // n_ranges
+};
+// [CHECK] != 0: the device form's offsets are refused; [FAILED] ranges that are not VALID, [FIRST] n_ranges - the least of them (0: none),
+// [ITEMS] the item list's length (beyond cap_items nothing was built: run again with that room)
+enum : uint32_t { RANGE_CTL_CHECK = 0, RANGE_CTL_FAILED = 1, RANGE_CTL_FIRST = 2, RANGE_CTL_ITEMS = 3, RANGE_CTL_WORDS = 4 };
+hipError_t launch_range_check(const RangeArgs& a, hipStream_t st);  // range_check_kernel
+hipError_t launch_range_verify(const RangeArgs& a, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2], hipStream_t st);
 hipError_t launch_mpt_verdict(const uint8_t* d_status, const uint32_t* d_root_idx, uint32_t n,
                               uint32_t n_roots, uint32_t* d_fail_count, hipStream_t st);
 

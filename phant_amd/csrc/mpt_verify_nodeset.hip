@@ -721,3 +721,4 @@ void verify_nodeset_stats_from_header(const uint32_t* hdr, uint32_t epoch, uint3
 
 #include "prestate.hip.h"
 #include "poststate.hip.h"
+#include "range_verify.hip.h"

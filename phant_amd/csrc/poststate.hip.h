@@ -219,66 +219,49 @@ PHANT_DEV void set_ref(Item* it, const uint8_t* nd, const RlpItem& r) {
     }
 }
 
-// One key of the ordered list (rank r).  WRITE = false: only counts.  Returns the number of items, or sets `err`.
-PHANT_DEV uint32_t emit_key(const Args& a, const uint32_t r, const bool write, const uint32_t base, const uint32_t count, uint32_t& err) {
-    const PoststateArgs& p = a.p;
-    const uint32_t nk = p.na + p.ns;
-    const uint32_t k = p.order[r];
-    const uint32_t trie = p.seg_of[k];
-    const uint8_t* const key = p.keys + 32ull * k;
-    int32_t lp = -1, ln = -1;
-    const uint8_t *kp = key, *kn = key;
-    if (r > 0 && p.seg_of[p.order[r - 1]] == trie) {
-        kp = p.keys + 32ull * p.order[r - 1];
-        lp = (int32_t)common_nibbles(kp, key, 64);
-    }
-    if (r + 1 < nk && p.seg_of[p.order[r + 1]] == trie) {
-        kn = p.keys + 32ull * p.order[r + 1];
-        ln = (int32_t)common_nibbles(kn, key, 64);
-    }
-    if (lp == 64 || ln == 64) {  // the same key twice: no trie has it twice
-        err = PHANT_PROOF_BAD_INPUT;
-        return 0;
-    }
-    Emitter e{post_items(p), base, base + count, trie, key, write};
-    if (!write) e.tail = 0x40000000u;
-    const uint32_t tail0 = e.tail;
-    const uint32_t ovf = a.t.hdr[ns::HDR_OVF + 32u * (a.t.epoch & 1u)];
-    const uint8_t* root = trie == p.na ? p.parent_root : p.pre_sroots + 32ull * trie;
+// The walk of one key's path from `root` through the record table, shared by the post-state emit (emit_key) and the range walkers
+// (range_verify.hip.h).  What is emitted next to the path is the caller's RULE:
+//   rule.slots(pos, nib, front_end, back_begin, back_end)   at a branch at depth pos where the key has nibble nib: the slots [0, front_end)
+//                          go in front of the key (in path order), the slots [back_begin, back_end) behind it (written from the back)
+//   rule.diverging(before, pos, cmp)   the walk leaves the path at a leaf / an extension that sorts in front of (before) or behind the key:
+//                          is it this walker's to emit?  cmp(other) compares the node's path with `other`'s nibbles behind pos
+// The key's own leaf is never emitted here.  Sets `err` (PHANT_PROOF_MISSING_NODE / PHANT_PROOF_BAD_NODE) and returns false on failure.
+template <class Rule>
+PHANT_DEV bool walk_emit(const ns::Args& t, const uint8_t* const nodes, const uint8_t* const root, const uint8_t* const key, Emitter& e,
+                         const Rule& rule, uint32_t& err) {
+    const uint32_t ovf = t.hdr[ns::HDR_OVF + 32u * (t.epoch & 1u)];
     uint32_t want[8];
     words_of(root, want);
     const uint8_t* cur = nullptr;
     uint32_t cur_len = 0, pos = 0;
-    bool by_hash = true, at_root = true, done = false;
+    bool by_hash = true, at_root = true;
     Node n;
-    while (!done) {
+    for (;;) {
         if (by_hash) {
             if (at_root && is_empty_root(want)) break;  // an empty trie: nothing but the key's own leaf
-            const ns::Found f = ns::set_find(a.t, want, ovf);
+            const ns::Found f = ns::set_find(t, want, ovf);
             if (!f.ok) {
                 err = PHANT_PROOF_MISSING_NODE;
-                return 0;
+                return false;
             }
-            cur = p.nodes + f.off;
+            cur = nodes + f.off;
             cur_len = f.len_canon & ~ns::CANON_BIT;
         }
         at_root = false;
         decode_node(cur, cur_len, n);
         if (n.cnt == 0u) {
             err = PHANT_PROOF_BAD_NODE;
-            return 0;
+            return false;
         }
         if (n.cnt == 17u) {
             if (pos >= 64u || n.it[16].len != 0u) {  // (keys are 32 bytes: no branch carries a value)
                 err = PHANT_PROOF_BAD_NODE;
-                return 0;
+                return false;
             }
             const uint32_t nib = nib_of(key, pos);
-            // the slots below the key's: this key's unless its predecessor passes through the same branch (which then has emitted
-            // the slots between the two as the ones above its own)
-            uint32_t lo = 0, hi = nib;
-            if (lp >= (int32_t)pos) hi = 0;
-            for (uint32_t s = lo; s < hi; ++s) {
+            uint32_t front_end = 0, back_begin = 16, back_end = 16;
+            rule.slots(pos, nib, front_end, back_begin, back_end);
+            for (uint32_t s = 0; s < front_end; ++s) {
                 if (ref_kind(n.it[s]) == REF_EMPTY) continue;
                 Item* it = e.place(true);
                 if (it) {
@@ -287,12 +270,8 @@ PHANT_DEV uint32_t emit_key(const Args& a, const uint32_t r, const bool write, c
                     set_ref(it, cur, n.it[s]);
                 }
             }
-            // the slots above it, up to its successor's: written from the back, the shallowest branch last
-            lo = nib + 1u;
-            hi = 16u;
-            if (ln > (int32_t)pos) lo = 16u;
-            else if (ln == (int32_t)pos) hi = nib_of(kn, pos);
-            for (uint32_t s = hi; s-- > lo;) {
+            // the slots above it: written from the back, the shallowest branch last
+            for (uint32_t s = back_end; s-- > back_begin;) {
                 if (ref_kind(n.it[s]) == REF_EMPTY) continue;
                 Item* it = e.place(false);
                 if (it) {
@@ -318,7 +297,7 @@ PHANT_DEV uint32_t emit_key(const Args& a, const uint32_t r, const bool write, c
         // a leaf or an extension at depth pos: every key of the list with these pos nibbles arrives here
         if (pos + n.plen > 64u || (n.leaf && pos + n.plen != 64u)) {
             err = PHANT_PROOF_BAD_NODE;
-            return 0;
+            return false;
         }
         auto cmp = [&](const uint8_t* other) -> int {  // the node's path against `other`'s nibbles behind pos
             for (uint32_t j = 0; j < n.plen; ++j) {
@@ -342,24 +321,18 @@ PHANT_DEV uint32_t emit_key(const Args& a, const uint32_t r, const bool write, c
             }
             continue;
         }
-        // the key leaves the path here: the old leaf / the extension's child stays, emitted by exactly one key of the range
-        bool mine, before = c < 0;
-        if (before) mine = lp < (int32_t)pos || cmp(kp) > 0;
-        else mine = ln < (int32_t)pos;
-        if (mine) {
-            // (in front of the key's own leaf it is the last item there; behind it, the first: the deeper slots come later / earlier)
-            Item* it = before ? e.place(true) : nullptr;
-            if (!before) {
-                // behind the key: it must precede everything written from the back so far -- nothing of THIS depth or deeper has
-                // been, and shallower slots sort behind it, so the next place from the back is right
-                it = e.place(false);
-            }
+        // the key leaves the path here: the old leaf / the extension's child stays, emitted by exactly one walker
+        const bool before = c < 0;
+        if (rule.diverging(before, pos, cmp)) {
+            // (in front of the key it is the last item there; behind it, the first: it must precede everything written from the back so
+            // far -- nothing of THIS depth or deeper has been, and shallower slots sort behind it, so the next place from the back is right)
+            Item* it = e.place(before);
             if (it) {
                 e.fill(it, pos, n.leaf ? IK_LEAF_OLD : IK_REF_BRANCH);
                 for (uint32_t j = 0; j < n.plen; ++j) nib_put(it->path, pos + j, hp_nibble(cur, n, j));
                 it->plen = (uint8_t)(pos + n.plen);
                 if (n.leaf) {
-                    it->src = (uint64_t)(cur - p.nodes) + n.it[1].pay;
+                    it->src = (uint64_t)(cur - nodes) + n.it[1].pay;
                     it->vlen = n.it[1].len;
                 } else {
                     set_ref(it, cur, n.it[1]);  // (an extension's child is a branch: IK_REF_BRANCH needs no lookup; embedded: decoded)
@@ -368,6 +341,55 @@ PHANT_DEV uint32_t emit_key(const Args& a, const uint32_t r, const bool write, c
         }
         break;
     }
+    return true;
+}
+
+// the post-state's rule: two neighbours of the ordered list and the common prefixes with them decide who emits what
+struct NeighbourRule {
+    int32_t lp, ln;  // nibbles shared with the predecessor / the successor in the same trie (-1: there is none)
+    const uint8_t *kp, *kn;
+    PHANT_DEV void slots(uint32_t pos, uint32_t nib, uint32_t& front_end, uint32_t& back_begin, uint32_t& back_end) const {
+        // the slots below the key's: this key's unless its predecessor passes through the same branch (which then has emitted
+        // the slots between the two as the ones above its own)
+        front_end = lp >= (int32_t)pos ? 0u : nib;
+        // the slots above it, up to its successor's
+        back_begin = nib + 1u;
+        back_end = 16u;
+        if (ln > (int32_t)pos) back_begin = 16u;
+        else if (ln == (int32_t)pos) back_end = nib_of(kn, pos);
+    }
+    template <class Cmp>
+    PHANT_DEV bool diverging(bool before, uint32_t pos, const Cmp& cmp) const {
+        if (before) return lp < (int32_t)pos || cmp(kp) > 0;
+        return ln < (int32_t)pos;
+    }
+};
+
+// One key of the ordered list (rank r).  WRITE = false: only counts.  Returns the number of items, or sets `err`.
+PHANT_DEV uint32_t emit_key(const Args& a, const uint32_t r, const bool write, const uint32_t base, const uint32_t count, uint32_t& err) {
+    const PoststateArgs& p = a.p;
+    const uint32_t nk = p.na + p.ns;
+    const uint32_t k = p.order[r];
+    const uint32_t trie = p.seg_of[k];
+    const uint8_t* const key = p.keys + 32ull * k;
+    NeighbourRule rule{-1, -1, key, key};
+    if (r > 0 && p.seg_of[p.order[r - 1]] == trie) {
+        rule.kp = p.keys + 32ull * p.order[r - 1];
+        rule.lp = (int32_t)common_nibbles(rule.kp, key, 64);
+    }
+    if (r + 1 < nk && p.seg_of[p.order[r + 1]] == trie) {
+        rule.kn = p.keys + 32ull * p.order[r + 1];
+        rule.ln = (int32_t)common_nibbles(rule.kn, key, 64);
+    }
+    if (rule.lp == 64 || rule.ln == 64) {  // the same key twice: no trie has it twice
+        err = PHANT_PROOF_BAD_INPUT;
+        return 0;
+    }
+    Emitter e{post_items(p), base, base + count, trie, key, write};
+    if (!write) e.tail = 0x40000000u;
+    const uint32_t tail0 = e.tail;
+    const uint8_t* root = trie == p.na ? p.parent_root : p.pre_sroots + 32ull * trie;
+    if (!walk_emit(a.t, p.nodes, root, key, e, rule, err)) return 0;
     // the key's own leaf
     const uint32_t act = p.act[k];
     if (act == ACT_OLD || act == ACT_NEW) {
@@ -399,6 +421,14 @@ PHANT_DEV void key_failed(const PoststateArgs& p, uint32_t k, uint32_t status, u
     else p.slot_status[k - p.na] = (uint8_t)status;
     atomicAdd(&p.counters[counter], 1u);
 }
+
+// what cannot be built: the whole call's (POST_CNT_INTERNAL) -- or, where the tries of a call stand each for itself (trie_bad: the ranges
+// of phant_mpt_verify_ranges), that trie's alone; the kernels behind skip such a trie
+PHANT_DEV void cannot_build(const PoststateArgs& p, uint32_t trie) {
+    if (p.trie_bad) p.trie_bad[trie] = 1u;
+    else atomicAdd(&p.counters[POST_CNT_INTERNAL], 1u);
+}
+PHANT_DEV bool trie_skipped(const PoststateArgs& p, uint32_t trie) { return p.trie_bad && p.trie_bad[trie] != 0u; }
 
 __global__ void __launch_bounds__(64) post_count_kernel(const Args a) {
     const uint32_t r = blockIdx.x * 64u + threadIdx.x, nk = a.p.na + a.p.ns;
@@ -432,7 +462,8 @@ __global__ void __launch_bounds__(256) post_link_kernel(const PoststateArgs p) {
     if (i > 0 && it[-1].trie == it->trie) {
         const uint32_t m = it->plen < it[-1].plen ? it->plen : it[-1].plen;
         l = (int32_t)common_nibbles(it->path, it[-1].path, m);
-        if ((uint32_t)l == m) atomicAdd(&p.counters[POST_CNT_INTERNAL], 1u);  // (one path inside another: the list is not prefix-free)
+        // one path inside another: the list is not prefix-free; (per-trie form) or not in path order
+        if ((uint32_t)l == m || (p.trie_bad && nib_of(it[-1].path, (uint32_t)l) > nib_of(it->path, (uint32_t)l))) cannot_build(p, it->trie);
     }
     it->lcp = l;
     it->nxt = i + 1u;
@@ -547,10 +578,10 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
         uint32_t vl = 0;
         if (kind == IK_LEAF_OLD) {
             if (c->vlen > MAX_VALUE) {
-                atomicAdd(&p.counters[POST_CNT_INTERNAL], 1u);
+                cannot_build(p, c->trie);
                 return 0;
             }
-            vl = put_str(vb, p.nodes + c->src, c->vlen);
+            vl = put_str(vb, (c->key ? p.leaf_vals : p.nodes) + c->src, c->vlen);  // (key != 0: a caller's leaf of a range)
         } else if (kind == IK_LEAF_SLOT) {
             uint8_t v[36];
             const uint32_t l = put_minimal(v, p.post_slot_vals + 32ull * c->key, 32);
@@ -572,7 +603,7 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
     }
     if (n == 0u) {  // the reference fills the slot as it is (the root: the hash of a branch built here)
         if (force && c->reflen != 32u) {  // (over 32-byte keys a root branch is never small enough to embed)
-            atomicAdd(&p.counters[POST_CNT_INTERNAL], 1u);
+            cannot_build(p, c->trie);
             return 0;
         }
         for (uint32_t t = 0; t < c->reflen; ++t) ref[t] = c->ref[t];
@@ -581,6 +612,10 @@ PHANT_DEV uint32_t attach(const Args& a, const Item* c, const int32_t d, const b
     if (kind == IK_BUILT || kind == IK_REF_BRANCH) {  // known to be a branch: it hangs under an extension
         const uint32_t il = put_ref_item(vb, c->ref, c->reflen);
         return node_ref(node, put_short_node(node, nibs, n, false, vb, il), force, ref, here);
+    }
+    if (p.trie_bad) {  // a range: a reference of unknown type that would have to be merged is no proof of anything
+        cannot_build(p, c->trie);
+        return 0;
     }
     // what the reference points to decides: never guessed
     const uint8_t* nd = c->ref;
@@ -621,7 +656,7 @@ __global__ void __launch_bounds__(64) post_level_kernel(const Args a, const int3
     const uint32_t total = n_items_of(p);
     if (i >= total) return;
     Item* const me = post_items(p) + i;
-    if ((me->trie == p.na) != (state_pass != 0u) || me->lcp >= d) return;
+    if ((me->trie == p.na) != (state_pass != 0u) || me->lcp >= d || trie_skipped(p, me->trie)) return;
     const uint32_t first = me->nxt;
     if (first >= total || post_items(p)[first].lcp != d) return;
     // the first child of a branch at depth d: the others are the items behind it that share exactly d nibbles with their predecessor
@@ -661,8 +696,8 @@ __global__ void __launch_bounds__(64) post_root_kernel(const Args a, const uint3
     const uint32_t total = n_items_of(p);
     if (i >= total) return;
     const Item* const me = post_items(p) + i;
-    if ((me->trie == p.na) != (state_pass != 0u) || me->lcp != -1) return;
-    if (me->nxt < total && post_items(p)[me->nxt].lcp != -1) atomicAdd(&p.counters[POST_CNT_INTERNAL], 1u);  // (more than one item left)
+    if ((me->trie == p.na) != (state_pass != 0u) || me->lcp != -1 || trie_skipped(p, me->trie)) return;
+    if (me->nxt < total && post_items(p)[me->nxt].lcp != -1) cannot_build(p, me->trie);  // (more than one item left)
     uint8_t ref[32];
     for (uint32_t t = 0; t < 32u; ++t) ref[t] = 0;
     attach(a, me, -1, true, ref);
@@ -686,6 +721,13 @@ hipError_t launch_poststate_actions(const PoststateArgs& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+// every trie of one pass (0: the tries with an index below p.na, 1: the trie p.na), level by level, then the roots: the one build
+// behind the post-state calls and phant_mpt_verify_ranges
+static void launch_post_levels(const post::Args& a, uint32_t item_groups, uint32_t pass, hipStream_t st) {
+    for (int32_t d = 63; d >= 0; --d) hipLaunchKernelGGL(post::post_level_kernel, dim3(item_groups), dim3(64), 0, st, a, d, pass);
+    hipLaunchKernelGGL(post::post_root_kernel, dim3(item_groups), dim3(64), 0, st, a, pass);
+}
+
 // count -> scan -> emit -> link -> the storage tries level by level -> their roots -> the state trie the same way -> finish
 hipError_t launch_poststate_build(const PoststateArgs& p, uint32_t cap_nodes, uint8_t* ws, uint32_t epoch, const uint32_t salt[2],
                                   hipStream_t st) {
@@ -705,8 +747,7 @@ hipError_t launch_poststate_build(const PoststateArgs& p, uint32_t cap_nodes, ui
     hipLaunchKernelGGL(post::post_link_kernel, dim3(grid256(p.cap_items)), dim3(256), 0, st, p);
     for (uint32_t pass = 0; pass < 2u; ++pass) {
         if (pass == 0u && p.ns == 0u) continue;
-        for (int32_t d = 63; d >= 0; --d) hipLaunchKernelGGL(post::post_level_kernel, dim3(ig), dim3(64), 0, st, a, d, pass);
-        hipLaunchKernelGGL(post::post_root_kernel, dim3(ig), dim3(64), 0, st, a, pass);
+        launch_post_levels(a, ig, pass, st);
     }
     hipLaunchKernelGGL(post::post_finish_kernel, dim3(grid256(nk)), dim3(256), 0, st, p);
     return hipGetLastError();

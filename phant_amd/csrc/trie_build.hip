@@ -638,23 +638,7 @@ PHANT_DEV void stage_clear(uint32_t* slot) {
 }
 // rate blocks needed by `total` message bytes (pad10*1 always adds at least one byte)
 PHANT_DEV uint32_t blocks_of(uint32_t total) { return total / RATE + 1u; }
-// Keccak-256 of the `total` bytes at the start of a ZERO-FILLED slot (capacity >= blocks_of(total) * 136 bytes)
-PHANT_DEV void keccak256_staged(Sponge& s, uint32_t* slot, uint32_t total) {
-    uint8_t* b = reinterpret_cast<uint8_t*>(slot);
-    const uint32_t nb = blocks_of(total);
-    b[total] = 0x01;                         // domain byte of Keccak-256 (hasher.zig -> Zig std Keccak256)
-    b[nb * RATE - 1u] |= 0x80;               // (the same byte when total = 136 nb - 1: 0x81)
-    sponge_zero(s);
-    for (uint32_t k = 0; k < nb; ++k) {      // exec-masked: lanes run as many blocks as their node has
-        const uint32_t* w = slot + k * RATE_DWORDS;
-#pragma unroll
-        for (int i = 0; i < 17; ++i) {
-            s.lo[i] ^= w[2 * i];
-            s.hi[i] ^= w[2 * i + 1];
-        }
-        keccak_f1600(s);
-    }
-}
+// (keccak256_staged, the sponge over such a slot: absorb.hip.h -- the range proofs' leaf pass stages its nodes the same way)
 
 // Deliver a finished node's reference (<= 32 bytes) to its parent slot, or to
 // the trie's root output.

@@ -10,6 +10,7 @@ verifier the reference only has as a TODO
     verify_batch / verify_batch_dev    DESIGN.md section 3
     prove_nodeset / _packed / _dev     DESIGN.md section 7d (witness generation)
     prove_batch / _packed / _dev       DESIGN.md section 7d (per-proof form: eth_getProof)
+    verify_ranges / prove_range        DESIGN.md section 7p (range proofs: snap sync's AccountRange / StorageRanges)
 """
 from __future__ import annotations
 
@@ -632,3 +633,126 @@ def prove_batch_dev(keys: torch.Tensor, key_off: torch.Tensor, vals: torch.Tenso
                                                  val_off.data_ptr(), vals.numel(), n, ptr(seg_first), n_tries, qkeys.data_ptr(),
                                                  qkey_off.data_ptr(), qkeys.numel(), ptr(q_trie), nq, C.byref(o)))
     return int(o.total_nodes), int(o.nodes_len)
+
+
+# ---------------------------------------------------------------------------- range proofs
+@dataclass
+class Range:
+    """One range of a verify_ranges call: the trusted root, the origin (32 bytes; ignored without a proof), the sorted run of
+    (key, value) leaves, and whether the call's node set holds the proofs of its two edges."""
+    root: bytes
+    origin: bytes
+    leaves: list
+    has_proof: bool = True
+
+
+@dataclass
+class RangesResult:
+    """What phant_mpt_verify_ranges answers (numpy, host), one row per range: status u8 (RANGE_* / PROOF_MISSING_NODE /
+    PROOF_BAD_NODE), has_more u8, computed_root (n, 32) u8 (zeros on failure), bad_leaf u32 (the call-wide index of the least leaf
+    that breaks a rule, else RANGE_NO_LEAF); n_failed, first_failed (n: none)."""
+    status: np.ndarray
+    has_more: np.ndarray
+    computed_root: np.ndarray
+    bad_leaf: np.ndarray
+    n_failed: int
+    first_failed: int
+
+    def valid(self, r: int) -> bool:
+        return int(self.status[r]) == L.RANGE_VALID
+
+
+def pack_ranges(ranges, nodes):
+    """ranges: Range objects (or (root, origin, leaves, has_proof) tuples); nodes: the node set, a list of encodings -> the arrays of
+    phant_ranges_in as numpy, in the order of L.RANGES_INPUTS"""
+    rs = [r if isinstance(r, Range) else Range(*r) for r in ranges]
+    n = len(rs)
+    roots = np.frombuffer(b"".join(bytes(r.root) for r in rs), np.uint8).copy().reshape(n, 32) if n else np.zeros((0, 32), np.uint8)
+    origins = np.frombuffer(b"".join(bytes(r.origin or bytes(32)) for r in rs), np.uint8).copy().reshape(n, 32) if n else np.zeros((0, 32), np.uint8)
+    leaf_first = np.zeros(n + 1, np.uint32)
+    leaf_first[1:] = np.cumsum([len(r.leaves) for r in rs]) if n else []
+    has_proof = np.array([1 if r.has_proof else 0 for r in rs], np.uint8)
+    leaves = [kv for r in rs for kv in r.leaves]
+    for k, _ in leaves:
+        if len(k) != 32:
+            raise ValueError("verify_ranges: keys are 32 bytes")
+    keys = np.frombuffer(b"".join(bytes(k) for k, _ in leaves), np.uint8).copy()
+    vals, val_off = _pack([bytes(v) for _, v in leaves], np.uint64)
+    nb, node_off = _pack([bytes(x) for x in nodes], np.uint64)
+    return roots, origins, leaf_first, has_proof, keys, vals[:int(val_off[-1])], val_off, nb[:int(node_off[-1])], node_off
+
+
+def verify_ranges_packed(roots, origins, leaf_first, has_proof, keys, vals, val_off, nodes, node_off, ctx: Context | None = None) -> RangesResult:
+    """Host form of phant_mpt_verify_ranges over packed numpy arrays (include/phant_gpu.h has the contract)."""
+    ctx = ctx or default_context()
+    arrays = [np.ascontiguousarray(a, dt).reshape(-1) for a, dt in zip(
+        (roots, origins, leaf_first, has_proof, keys, vals, val_off, nodes, node_off),
+        (np.uint8, np.uint8, np.uint32, np.uint8, np.uint8, np.uint8, np.uint64, np.uint8, np.uint64))]
+    n, n_leaves, n_nodes = len(arrays[2]) - 1, len(arrays[6]) - 1, len(arrays[8]) - 1
+    i = L.PhantRangesIn(C.sizeof(L.PhantRangesIn), n, n_leaves, n_nodes, (C.c_uint32 * 2)(0, 0), arrays[5].size, arrays[7].size,
+                        *[_np_ptr(a) if a.size else None for a in arrays])
+    outs = {name: np.zeros((max(n, 1), w) if w > 1 else max(n, 1), dt) for name, dt, w in L.RANGES_OUTPUTS}
+    o = L.PhantRangesOut(C.sizeof(L.PhantRangesOut), 0, 0, (C.c_uint32 * 2)(0, 0), *[_np_ptr(outs[name]) for name, _, _ in L.RANGES_OUTPUTS])
+    ctx.check(ctx._lib.phant_mpt_verify_ranges(ctx.handle, C.byref(i), C.byref(o)))
+    return RangesResult(outs["status"][:n], outs["has_more"][:n], outs["computed_root"][:n], outs["bad_leaf"][:n], int(o.n_failed), int(o.first_failed))
+
+
+def verify_ranges(ranges, nodes, ctx: Context | None = None) -> RangesResult:
+    """Are the leaves of every range exactly what the trie under its root holds between its origin and its last key -- and does
+    anything lie to the right (has_more)?  ranges: Range objects; nodes: ONE node set for all of them (a list of node encodings, any
+    order, unrelated nodes allowed).  -> RangesResult."""
+    return verify_ranges_packed(*pack_ranges(ranges, nodes), ctx=ctx)
+
+
+def verify_ranges_dev(roots: torch.Tensor, origins: torch.Tensor, leaf_first: torch.Tensor, has_proof: torch.Tensor, keys: torch.Tensor,
+                      vals: torch.Tensor, val_off: torch.Tensor, nodes: torch.Tensor, node_off: torch.Tensor, status: torch.Tensor | None = None,
+                      has_more: torch.Tensor | None = None, computed_root: torch.Tensor | None = None, bad_leaf: torch.Tensor | None = None,
+                      ctx: Context | None = None):
+    """Device form: every array a device tensor (u8 but leaf_first / bad_leaf: int32 storage of uint32, val_off / node_off: int64
+    storage of uint64).  Outputs that are None are not asked for.  -> (n_failed, first_failed)."""
+    ctx = ctx or default_context()
+    n, n_leaves, n_nodes = leaf_first.numel() - 1, val_off.numel() - 1, node_off.numel() - 1
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    i = L.PhantRangesIn(C.sizeof(L.PhantRangesIn), n, n_leaves, n_nodes, (C.c_uint32 * 2)(0, 0), vals.numel(), nodes.numel(),
+                        ptr(roots), ptr(origins), ptr(leaf_first), ptr(has_proof), ptr(keys), ptr(vals), ptr(val_off), ptr(nodes), ptr(node_off))
+    o = L.PhantRangesOut(C.sizeof(L.PhantRangesOut), 0, 0, (C.c_uint32 * 2)(0, 0), ptr(status), ptr(has_more), ptr(computed_root), ptr(bad_leaf))
+    ctx.check(ctx._lib.phant_mpt_verify_ranges_dev(ctx.handle, C.byref(i), C.byref(o)))
+    return int(o.n_failed), int(o.first_failed)
+
+
+@dataclass
+class ProvenRange:
+    """What prove_range serves: the leaves from the first key >= origin on, the node set that proves the two edges (empty without a
+    proof) and the trie's root.  Range(root, origin, leaves, has_proof) + nodes is what verify_ranges takes."""
+    root: bytes
+    origin: bytes
+    leaves: list
+    nodes: list
+    has_proof: bool
+
+    def range(self) -> Range:
+        return Range(self.root, self.origin, self.leaves, self.has_proof)
+
+
+def prove_range(keyvals, origin: bytes, limit: bytes | None = None, max_leaves: int | None = None, ctx: Context | None = None) -> ProvenRange:
+    """The serving side of a range proof over the trie holding `keyvals` (sorted KeyVals with 32-byte keys): the leaves from the first
+    key >= origin on, none beyond `limit` and at most max_leaves of them; with them the node set of
+    prove_nodeset over {origin, the last key served} -- over {origin} alone when nothing is served -- or no proof at all when the
+    slice is the whole trie and origin is zero."""
+    import bisect
+    origin = bytes(origin)
+    keys = [kv.key for kv in keyvals]
+    lo = bisect.bisect_left(keys, origin)
+    hi = len(keys)
+    if limit is not None:
+        hi = max(lo, bisect.bisect_right(keys, bytes(limit)))
+    if max_leaves is not None:
+        hi = min(hi, lo + max_leaves)
+    leaves = [(kv.key, kv.value) for kv in keyvals[lo:hi]]
+    if lo == 0 and hi == len(keys) and origin == bytes(32):
+        return ProvenRange(mptize(keyvals, ctx) if keyvals else empty_mpt_root, origin, leaves, [], False)
+    if not keyvals:
+        return ProvenRange(empty_mpt_root, origin, [], [], True)
+    queries = [origin] + ([leaves[-1][0]] if leaves and leaves[-1][0] != origin else [])
+    s = prove_nodeset(keyvals, queries, ctx=ctx)
+    return ProvenRange(s.roots[0].tobytes(), origin, leaves, [s.node(j) for j in range(s.total_nodes)], True)
