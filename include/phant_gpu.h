@@ -686,6 +686,139 @@ typedef struct phant_bodies_split {
 PHANT_API int32_t phant_bodies_decode_rlp(const uint8_t *blob, const uint64_t *off, uint32_t n, uint32_t flags,
                                           phant_bodies_split *split, uint8_t *status);
 
+/* ------------------------------------------------- receipts of a chain segment from raw messages: decode, blooms, roots
+ * What phant_block_receipts answers for one block from the FIELDS an EVM has just produced, for the receipts of n_blocks blocks as a
+ * peer sends them -- raw RLP -- in ONE call: the headers of a segment go through phant_header_chain, its bodies through
+ * phant_block_bodies, the receipts they commit to through this.  The reference never compares receipts with a header
+ * (src/blockchain/blockchain.zig:184-191 builds receipts without logs, :86-88 leaves the bloom as a TODO); this is a part the drop-in adds.
+ *
+ * Input.  n, receipts, rc_off (n + 1), rc_bytes: the receipt values of all blocks back to back; block_first (n_blocks + 1): never
+ * backwards, from 0 to n; an empty block is ordinary.  form says what one value is:
+ *   PHANT_RCPTS_CONSENSUS  [type byte 0x01 .. 0x7f, when typed] ++ rlp([status_or_root, cum_gas, bloom(256), logs]) -- what eth/68 and
+ *                          earlier carry and what the receipts trie holds; the trie value is the bytes as given
+ *   PHANT_RCPTS_ETH69      rlp([tx_type, status_or_root, cum_gas, logs]) (EIP-7642), tx_type a canonical integer 0 .. 0x7f; the trie
+ *                          value is BUILT: [tx_type, when != 0] ++ rlp_list(status item ++ gas item ++ 0xb9 0x01 0x00 ++ computed
+ *                          bloom ++ logs item), the three items copied as they stand
+ * A row is decodable when it is canonical RLP throughout with nothing behind the item, has exactly the form's items, status_or_root is
+ * the empty string, 0x01 or a 32-byte string (a pre-Byzantium post-state root), cum_gas a canonical integer of at most 8 bytes, the
+ * bloom a string of exactly 256 bytes, and logs a list of [address(20), [topic(32) ...], data] of exactly three items each.  In the
+ * consensus form a leading 0x00 is undecodable.  A length field may state up to 2^64 - 1 anywhere: nothing outside
+ * [rc_off[i], rc_off[i + 1]) is ever read.  Expected values, one row per block, each may be NULL: receipts_root (32 bytes),
+ * logs_bloom (256), gas_used (uint64_t), tx_count (uint32_t).  The host form does not read rc_bytes (the total is rc_off[n]).
+ *
+ * Output, any pointer may be NULL.  Per receipt (n rows): tx_type; status (0, 1, or 2 for a post-state root); cum_gas; gas_used =
+ * cum_gas minus the predecessor's in the same block modulo 2^64, the block's first against 0; log_first (n + 1); bloom (n x 256,
+ * computed from the logs); flags (below).  An undecodable row has zero fields, no logs and a zero bloom, and its trie value is its raw
+ * bytes in BOTH forms: the root of its block is then defined and wrong, and the block is flagged anyway.
+ * Per log (n_logs rows, from all decodable receipts in order): log_receipt; address (20 bytes); topic_first (n_logs + 1); topics
+ * (n_topics x 32); data_at (an offset into `receipts`), data_len.  n_logs and n_topics are always written; when one exceeds its cap
+ * (log_cap, topic_cap: the rows the per-log outputs hold) no per-log array is touched and the call still returns PHANT_OK.
+ * encoded, encoded_off (n + 1): the consensus encodings in index order -- what an ETH69 caller stores; a copy of the input in the
+ * consensus form.  encoded_len is always written; when it exceeds encoded_cap neither buffer is touched and the call still returns
+ * PHANT_OK (a NULL `encoded` has no capacity to exceed).
+ * Per block: receipts_root (calculateMPTRoot over the values, key rlp(index); an empty block: empty_mpt_root); logs_bloom (the OR of the
+ * block's computed blooms); block_gas_used (the last decodable row's cum_gas, 0 without one); block_first_bad (the least i -
+ * block_first[b] whose flags carry an error bit, the block's count if none); block_flags (below); first_bad_block (always written: the
+ * least b with block_flags[b] != 0, n_blocks if none).  No trie is built when no root is wanted or expected.  No Keccak runs over the
+ * logs when nothing needs a bloom: the consensus form needs one for PHANT_RCPT_BLOOM, the ETH69 form for a root, the encodings, the
+ * bloom outputs and an expected logs_bloom. */
+#define PHANT_RCPTS_CONSENSUS 0u
+#define PHANT_RCPTS_ETH69 1u
+#define PHANT_RCPT_UNDECODABLE 1u     /* the row is not a receipt of the call's form */
+#define PHANT_RCPT_BLOOM 2u           /* consensus form: the embedded bloom is not the logs' bloom */
+#define PHANT_RCPT_GAS_ORDER 4u       /* this row and its predecessor in the block are decodable and cum_gas is not greater than the
+                                         predecessor's; the block's first row: its cum_gas is 0 */
+#define PHANT_RCPT_POST_STATE 0x100u  /* informative: status_or_root is a 32-byte post-state root */
+#define PHANT_RCPT_ERROR_BITS 7u
+#define PHANT_RBLOCK_RECEIPT 1u   /* some row of the block carries a bit of PHANT_RCPT_ERROR_BITS */
+#define PHANT_RBLOCK_ROOT 2u      /* in->receipts_root given and != the computed root */
+#define PHANT_RBLOCK_BLOOM 4u     /* in->logs_bloom given and != the block's computed bloom */
+#define PHANT_RBLOCK_GAS_USED 8u  /* in->gas_used given and != block_gas_used */
+#define PHANT_RBLOCK_COUNT 16u    /* in->tx_count given and != the block's receipts */
+/* A bad receipt or block is a flag, never an error.  PHANT_E_INVALID_ARG, before anything is indexed with the offending value and with
+ * nothing written: a wrong struct_size, an unknown form, reserved != 0, a NULL input with a non-zero count (receipts / rc_off with n,
+ * block_first with n_blocks), receipts without a block, rc_off or block_first that do not run from 0 to their totals (device form:
+ * rc_bytes; n) or go backwards.  PHANT_E_UNSUPPORTED: a receipt of 2^32 bytes or more, 2^32 bytes of receipts or of trie values (an
+ * ETH69 receipt counted with the 268 bytes it can grow by) or 2^31 - 1 items in one call.  n_blocks == 0 is PHANT_OK with
+ * first_bad_block, n_logs, n_topics and encoded_len 0; so is n == 0.  The host form checks on the host before any copy: one staged
+ * upload, the launches, one copy back of the span up to the last wanted output (plain copies beyond the pinned stage).
+ *
+ * Device form: every array is device memory, the uint64_t arrays 8-byte and the uint32_t arrays 4-byte aligned, byte arrays not at all;
+ * the structs are host memory.  rc_off and block_first are checked by a kernel whose verdict the host reads before any other kernel
+ * indexes with them.  The call synchronises the ctx stream (the scalars are valid when it returns); the copies of the per-log rows and
+ * of the encodings are in stream order behind it. */
+typedef struct phant_rcpt_segs_in {
+    uint32_t struct_size; /* = sizeof(phant_rcpt_segs_in) */
+    uint32_t form;        /* PHANT_RCPTS_* */
+    uint32_t n_blocks;
+    uint32_t n;           /* receipts of all blocks */
+    uint32_t log_cap;     /* rows the per-log outputs hold */
+    uint32_t topic_cap;   /* rows `topics` holds */
+    uint32_t reserved[2]; /* 0 */
+    const uint8_t *receipts;
+    const uint64_t *rc_off;      /* n + 1 */
+    uint64_t rc_bytes;           /* device form: rc_off[n] as the caller states it */
+    const uint32_t *block_first; /* n_blocks + 1 */
+    const uint8_t *receipts_root; /* expected, n_blocks x 32, or NULL */
+    const uint8_t *logs_bloom;    /* expected, n_blocks x 256, or NULL */
+    const uint64_t *gas_used;     /* expected, n_blocks, or NULL */
+    const uint32_t *tx_count;     /* expected, n_blocks, or NULL */
+} phant_rcpt_segs_in;
+typedef struct phant_rcpt_segs_out {
+    uint32_t struct_size;     /* = sizeof(phant_rcpt_segs_out) */
+    uint32_t first_bad_block; /* result */
+    uint32_t n_logs;          /* result */
+    uint32_t n_topics;        /* result */
+    uint64_t encoded_cap;     /* bytes of encoded */
+    uint64_t encoded_len;     /* result */
+    uint8_t *tx_type;
+    uint8_t *status;
+    uint64_t *cum_gas;
+    uint64_t *gas_used;
+    uint32_t *log_first;
+    uint8_t *bloom;
+    uint32_t *flags;
+    uint32_t *log_receipt;
+    uint8_t *address;
+    uint32_t *topic_first;
+    uint8_t *topics;
+    uint64_t *data_at;
+    uint32_t *data_len;
+    uint8_t *encoded;
+    uint64_t *encoded_off;
+    uint8_t *receipts_root;
+    uint8_t *logs_bloom;
+    uint64_t *block_gas_used;
+    uint32_t *block_first_bad;
+    uint32_t *block_flags;
+} phant_rcpt_segs_out;
+PHANT_API int32_t phant_block_receipt_segments(phant_ctx *ctx, const phant_rcpt_segs_in *in, phant_rcpt_segs_out *out);
+PHANT_API int32_t phant_block_receipt_segments_dev(phant_ctx *ctx, const phant_rcpt_segs_in *in, phant_rcpt_segs_out *out);
+/* Host only, strict: the packed arrays phant_block_receipt_segments takes from the n per-block elements of a `Receipts` message.
+ * Block b = blob[off[b] .. off[b+1]) = the list of its receipts, canonical RLP with nothing behind it.  Without
+ * PHANT_RCPTS_SPLIT_ETH69 an item is a list (a legacy receipt: its whole encoding is the value) or a non-empty string whose first byte
+ * is at most 0x7f (a typed one: its payload is the value); with it every item is a list, its whole encoding the value.  The splitter
+ * does not look into receipts.  status[b] (n bytes) says which rule block b broke first, and such a block contributes no rows:
+ * block_first[b + 1] == block_first[b].  Sizing in two steps: n and rc_bytes are always written; when one exceeds its capacity (rc_cap:
+ * items; rc_bytes_cap: bytes; a NULL array has capacity 0) NOTHING else is written, status included, and the call still returns
+ * PHANT_OK: call again with arrays of the reported sizes (rc_off rc_cap + 1, block_first n + 1 entries).  PHANT_E_INVALID_ARG: NULL
+ * blob / off / split / status with n > 0, a wrong struct_size, unknown flags, offsets that go backwards. */
+#define PHANT_RCPTS_SPLIT_ETH69 1u
+#define PHANT_SPLIT_BAD_RECEIPT 5 /* an item that is neither a list nor a string beginning with a type byte (ETH69: not a list) */
+typedef struct phant_receipts_split {
+    uint32_t struct_size; /* = sizeof(phant_receipts_split) */
+    uint32_t reserved;    /* 0 */
+    uint32_t rc_cap;
+    uint32_t n;           /* result */
+    uint64_t rc_bytes_cap;
+    uint8_t *receipts;
+    uint64_t *rc_off;
+    uint32_t *block_first;
+    uint64_t rc_bytes;    /* result */
+} phant_receipts_split;
+PHANT_API int32_t phant_receipts_decode_rlp(const uint8_t *blob, const uint64_t *off, uint32_t n, uint32_t flags,
+                                            phant_receipts_split *split, uint8_t *status);
+
 /* ------------------------------------------------- a block's transactions against the pre-state: nonces, EOA and witness rows
  * phant_block_txs_prestate joins the rows phant_block_transactions[_ex] answers (keyed by transaction) with the rows
  * phant_exec_witness_prestate answers (keyed by witness row), and decides what `processTransaction` checks first

@@ -85,6 +85,9 @@ SYMBOLS = {
     "phant_block_bodies": (_i32, [_vp, _vp, _vp]),
     "phant_block_bodies_dev": (_i32, [_vp, _vp, _vp]),
     "phant_bodies_decode_rlp": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "phant_block_receipt_segments": (_i32, [_vp, _vp, _vp]),
+    "phant_block_receipt_segments_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_receipts_decode_rlp": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle": (_i32, [_vp, _vp, _vp]),
@@ -298,6 +301,43 @@ class PhantBodiesOut(C.Structure):
     """phant_bodies_out (include/phant_gpu.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("first_bad_block", C.c_uint32), ("txs", PhantTxsExOut)] + \
                [(name, C.c_void_p) for name, _, _, _ in BODIES_OUTPUTS]
+
+
+RCPTS_CONSENSUS, RCPTS_ETH69 = 0, 1
+RCPT_UNDECODABLE, RCPT_BLOOM, RCPT_GAS_ORDER, RCPT_POST_STATE, RCPT_ERROR_BITS = 1, 2, 4, 0x100, 7
+RCPT_FLAG_NAMES = ("Undecodable", "Bloom", "GasOrder", None, None, None, None, None, "PostState")
+RBLOCK_RECEIPT, RBLOCK_ROOT, RBLOCK_BLOOM, RBLOCK_GAS_USED, RBLOCK_COUNT = 1, 2, 4, 8, 16
+RBLOCK_FLAG_NAMES = ("Receipt", "ReceiptsRoot", "LogsBloom", "GasUsed", "Count")
+# phant_rcpt_segs_in's arrays in the struct's order (rc_bytes sits behind rc_off)
+RSEG_INPUTS = ("receipts", "rc_off", "block_first", "receipts_root", "logs_bloom", "gas_used", "tx_count")
+# phant_rcpt_segs_out's arrays in the struct's order: (name, numpy dtype, elements per row, the count its rows follow, rows beyond that count)
+RSEG_OUTPUTS = (("tx_type", "u1", 1, "n", 0), ("status", "u1", 1, "n", 0), ("cum_gas", "u8", 1, "n", 0), ("gas_used", "u8", 1, "n", 0),
+                ("log_first", "u4", 1, "n", 1), ("bloom", "u1", 256, "n", 0), ("flags", "u4", 1, "n", 0),
+                ("log_receipt", "u4", 1, "n_logs", 0), ("address", "u1", 20, "n_logs", 0), ("topic_first", "u4", 1, "n_logs", 1),
+                ("topics", "u1", 32, "n_topics", 0), ("data_at", "u8", 1, "n_logs", 0), ("data_len", "u4", 1, "n_logs", 0),
+                ("encoded", "u1", 1, "encoded_len", 0), ("encoded_off", "u8", 1, "n", 1),
+                ("receipts_root", "u1", 32, "n_blocks", 0), ("logs_bloom", "u1", 256, "n_blocks", 0), ("block_gas_used", "u8", 1, "n_blocks", 0),
+                ("block_first_bad", "u4", 1, "n_blocks", 0), ("block_flags", "u4", 1, "n_blocks", 0))
+RCPTS_SPLIT_ETH69 = 1
+SPLIT_BAD_RECEIPT = 5
+
+
+class PhantRcptSegsIn(C.Structure):
+    """phant_rcpt_segs_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "form", "n_blocks", "n", "log_cap", "topic_cap")] + [("reserved", C.c_uint32 * 2)] + \
+               [("receipts", C.c_void_p), ("rc_off", C.c_void_p), ("rc_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in RSEG_INPUTS[2:]]
+
+
+class PhantRcptSegsOut(C.Structure):
+    """phant_rcpt_segs_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "first_bad_block", "n_logs", "n_topics")] + \
+               [("encoded_cap", C.c_uint64), ("encoded_len", C.c_uint64)] + [(name, C.c_void_p) for name, _, _, _, _ in RSEG_OUTPUTS]
+
+
+class PhantReceiptsSplit(C.Structure):
+    """phant_receipts_split (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "reserved", "rc_cap", "n")] + [("rc_bytes_cap", C.c_uint64)] + \
+               [(name, C.c_void_p) for name in ("receipts", "rc_off", "block_first")] + [("rc_bytes", C.c_uint64)]
 
 
 ROW_NONE = 0xFFFFFFFF

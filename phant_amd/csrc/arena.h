@@ -147,7 +147,9 @@ struct Workspaces {
     static constexpr size_t MAILBOX_SETTLE = MAILBOX_AL + MAILBOX_AL_WORDS, MAILBOX_SETTLE_WORDS = 8;
     // ... and phant_mpt_verify_ranges (capi.hip) the MAILBOX_RANGES_WORDS behind those
     static constexpr size_t MAILBOX_RANGES = MAILBOX_SETTLE + MAILBOX_SETTLE_WORDS, MAILBOX_RANGES_WORDS = 4;
-    static_assert(MAILBOX_RANGES + MAILBOX_RANGES_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
+    // ... and block_receipt_segments (receipt_segments.hip.h) the MAILBOX_RSEG_WORDS behind those
+    static constexpr size_t MAILBOX_RSEG = MAILBOX_RANGES + MAILBOX_RANGES_WORDS, MAILBOX_RSEG_WORDS = 8;
+    static_assert(MAILBOX_RSEG + MAILBOX_RSEG_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
     uint32_t* mailbox = nullptr;
     hipError_t ensure_mailbox() {
         if (mailbox) return hipSuccess;

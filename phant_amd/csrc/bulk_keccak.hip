@@ -18,6 +18,8 @@
 //                   ecrecover_kernel below, which it launches)
 //   block bodies    the transactions of a whole chain segment through those steps in one call, the rules under each block's own
 //                   parameters, and the blocks' transactions and withdrawals tries as one forest (bodies.hip.h)
+//   receipt segments  the receipts of a whole chain segment from raw consensus or eth/69 messages: strict decode, blooms, the consensus
+//                   encodings, per-block verdicts and the blocks' receipts tries as one forest (receipt_segments.hip.h)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
@@ -263,6 +265,7 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 
 #include "transactions.hip.h"
 #include "bodies.hip.h"
+#include "receipt_segments.hip.h"
 #include "txstate.hip.h"
 #include "settle.hip.h"
 #include "access_lists.hip.h"

@@ -1067,6 +1067,76 @@ int32_t phant_block_bodies(phant_ctx* c, const phant_bodies_in* in, phant_bodies
 
 int32_t phant_block_bodies_dev(phant_ctx* c, const phant_bodies_in* in, phant_bodies_out* out) { return block_bodies_impl(c, in, out, true); }
 
+/* ------------------------------------------------- receipts of a chain segment from raw messages (receipt_segments.hip.h) */
+
+int32_t phant_receipts_decode_rlp(const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t flags, phant_receipts_split* sp, uint8_t* status) {
+    if (flags & ~PHANT_RCPTS_SPLIT_ETH69) return PHANT_E_INVALID_ARG;
+    if (!sp || sp->struct_size != sizeof(phant_receipts_split) || sp->reserved != 0u) return PHANT_E_INVALID_ARG;
+    if (n && (!off || !status)) return PHANT_E_INVALID_ARG;
+    for (uint32_t b = 0; b < n; ++b)
+        if (off[b + 1] < off[b]) return PHANT_E_INVALID_ARG;
+    if (n && off[n] != off[0] && !blob) return PHANT_E_INVALID_ARG;
+    const bool eth69 = (flags & PHANT_RCPTS_SPLIT_ETH69) != 0u;
+    auto block = [&](uint32_t b, phant::ReceiptTotals& t, const phant::ReceiptSink* sink) {
+        return phant::receipts_split(blob ? blob + off[b] : nullptr, (size_t)(off[b + 1] - off[b]), eth69, t, sink);
+    };
+    phant::ReceiptTotals t{0, 0};
+    for (uint32_t b = 0; b < n; ++b) (void)block(b, t, nullptr);
+    if (t.n > 0xffffffffull) return PHANT_E_UNSUPPORTED;
+    sp->n = (uint32_t)t.n, sp->rc_bytes = t.bytes;
+    const bool room = sp->rc_off && sp->block_first && t.n <= sp->rc_cap && (sp->receipts ? t.bytes <= sp->rc_bytes_cap : t.bytes == 0);
+    if (!room) return PHANT_OK;
+    const phant::ReceiptSink sink{sp->receipts, sp->rc_off};
+    t = phant::ReceiptTotals{0, 0};
+    sp->rc_off[0] = 0, sp->block_first[0] = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        status[b] = block(b, t, &sink);
+        sp->block_first[b + 1] = (uint32_t)t.n;
+    }
+    return PHANT_OK;
+}
+
+static int32_t block_receipt_segments_impl(phant_ctx* c, const phant_rcpt_segs_in* in, phant_rcpt_segs_out* out, bool dev) {
+    const char* const who = dev ? "block_receipt_segments_dev" : "block_receipt_segments";
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (!in || !out) return bad("in / out is null");
+    if (in->struct_size != sizeof(phant_rcpt_segs_in) || out->struct_size != sizeof(phant_rcpt_segs_out)) return bad("wrong struct_size");
+    if (in->form > PHANT_RCPTS_ETH69) return bad("unknown form");
+    if (in->reserved[0] != 0u || in->reserved[1] != 0u) return bad("reserved is not 0");
+    const uint32_t n = in->n, nb = in->n_blocks;
+    if (nb == 0) {  // (no block: nothing to index, nothing to write but the scalars)
+        if (n) return bad("receipts without a block");
+        out->first_bad_block = 0, out->n_logs = 0, out->n_topics = 0, out->encoded_len = 0;
+        return PHANT_OK;
+    }
+    if (!in->block_first) return bad("null block_first");
+    if (n && (!in->receipts || !in->rc_off)) return bad("null receipts / rc_off");
+    if (dev) {  // (kernels read the offsets and the per-block integers as words; the outputs arrive by copies of bytes)
+        const uintptr_t w8 = (uintptr_t)in->rc_off | (uintptr_t)in->gas_used | (uintptr_t)out->cum_gas | (uintptr_t)out->gas_used | (uintptr_t)out->data_at |
+                             (uintptr_t)out->encoded_off | (uintptr_t)out->block_gas_used;
+        const uintptr_t w4 = (uintptr_t)in->block_first | (uintptr_t)in->tx_count | (uintptr_t)out->log_first | (uintptr_t)out->flags | (uintptr_t)out->log_receipt |
+                             (uintptr_t)out->topic_first | (uintptr_t)out->data_len | (uintptr_t)out->block_first_bad | (uintptr_t)out->block_flags;
+        if ((w8 & 7u) || (w4 & 3u)) return bad("misaligned array");
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_rcpt_segs_out res = *out;
+    const int32_t rc = phant::block_receipt_segments(c->ws, c->stream, *in, res, dev, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->first_bad_block = res.first_bad_block, out->n_logs = res.n_logs, out->n_topics = res.n_topics, out->encoded_len = res.encoded_len;
+    return PHANT_OK;
+}
+
+int32_t phant_block_receipt_segments(phant_ctx* c, const phant_rcpt_segs_in* in, phant_rcpt_segs_out* out) {
+    return block_receipt_segments_impl(c, in, out, false);
+}
+
+int32_t phant_block_receipt_segments_dev(phant_ctx* c, const phant_rcpt_segs_in* in, phant_rcpt_segs_out* out) {
+    return block_receipt_segments_impl(c, in, out, true);
+}
+
 /* ------------------------------------------------- a block's transactions against the pre-state (txstate.hip.h) */
 
 static int32_t block_txs_prestate_impl(phant_ctx* c, const phant_txstate_in* in, phant_txstate_out* out, bool dev) {

@@ -409,4 +409,32 @@ uint8_t body_split(const uint8_t* p, size_t len, bool has_header, BodyTotals& t,
     return PHANT_SPLIT_OK;
 }
 
+// ---- the per-block element of a `Receipts` message: the list of the block's receipts ----
+uint8_t receipts_split(const uint8_t* p, size_t len, bool eth69, ReceiptTotals& t, const ReceiptSink* sink) {
+    if (!p) return PHANT_SPLIT_BAD_RLP;
+    size_t pay, plen, total;
+    bool is_list;
+    if (!host_rlp_item(p, len, pay, plen, total, is_list) || !is_list || total != len) return PHANT_SPLIT_BAD_RLP;
+    // a receipt: a list as it stands, or (before eth/69) the payload of a string that begins with a type byte
+    auto value = [eth69](const uint8_t* item, size_t ip, size_t il, size_t it, bool ilist, const uint8_t*& v, size_t& vl) {
+        if (ilist) return v = item, vl = it, true;
+        if (eth69 || il == 0 || item[ip] > 0x7fu) return false;
+        return v = item + ip, vl = il, true;
+    };
+    auto any_value = [](const uint8_t* item, size_t, size_t, size_t it, bool, const uint8_t*& v, size_t& vl) { return v = item, vl = it, true; };
+    ReceiptTotals mine{0, 0};
+    if (!walk_list(p + pay, plen, value, [&](const uint8_t*, size_t vl) { ++mine.n, mine.bytes += vl; }))
+        return walk_list(p + pay, plen, any_value, [](const uint8_t*, size_t) {}) ? PHANT_SPLIT_BAD_RECEIPT : PHANT_SPLIT_BAD_RLP;
+    if (sink) {
+        uint64_t i = t.n, at = t.bytes;
+        (void)walk_list(p + pay, plen, value, [&](const uint8_t* v, size_t vl) {
+            std::memcpy(sink->receipts + at, v, vl);
+            at += vl;
+            sink->rc_off[++i] = at;
+        });
+    }
+    t.n += mine.n, t.bytes += mine.bytes;
+    return PHANT_SPLIT_OK;
+}
+
 }  // namespace phant

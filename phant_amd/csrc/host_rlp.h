@@ -57,4 +57,16 @@ struct BodySink {
 };
 uint8_t body_split(const uint8_t* p, size_t len, bool has_header, BodyTotals& t, const BodySink* sink);
 
+// phant_receipts_decode_rlp (include/phant_gpu.h): the receipts list of one block, `len` bytes at `p` -> PHANT_SPLIT_OK,
+// PHANT_SPLIT_BAD_RLP or PHANT_SPLIT_BAD_RECEIPT.  On PHANT_SPLIT_OK its values are counted into `t`, and with a sink first appended
+// at t's positions (rc_off[t.n + 1 ..]); a refused block changes nothing.  The receipts are not looked into.  Untrusted bytes in.
+struct ReceiptTotals {
+    uint64_t n, bytes;
+};
+struct ReceiptSink {
+    uint8_t* receipts;
+    uint64_t* rc_off;
+};
+uint8_t receipts_split(const uint8_t* p, size_t len, bool eth69, ReceiptTotals& t, const ReceiptSink* sink);
+
 }  // namespace phant

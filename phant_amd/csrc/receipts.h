@@ -6,6 +6,7 @@
 
 #include <string>
 
+#include "../../include/phant_gpu.h"
 #include "arena.h"
 
 namespace phant {
@@ -42,5 +43,9 @@ struct ReceiptsArgs {
 };
 
 int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool device_form, std::string& err);
+
+// The receipts of a chain segment from raw messages (receipt_segments.hip.h; phant_block_receipt_segments[_dev]): in / out as they came,
+// every array host memory in the host form and device memory in the device form; the scalars of `out` are written on PHANT_OK.
+int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_segs_in& in, phant_rcpt_segs_out& out, bool device_form, std::string& err);
 
 }  // namespace phant

@@ -1,5 +1,5 @@
 // staging.h -- how a call crosses the bus, once, for the drivers that keep their arrays in the ctx's `io` arena:
-// block_receipts, header_chain, block_transactions, block_txs_prestate, block_settle, and the host forms of the trie hasher and of its prover.  Plain
+// block_receipts, block_receipt_segments, header_chain, block_transactions, block_txs_prestate, block_settle, and the host forms of the trie hasher and of its prover.  Plain
 // host C++ on top of arena.h.
 //
 //   lay_out_arena an arena sized by, then carved by, one list of take<T>() calls
@@ -173,7 +173,7 @@ StagedPairs stage_pairs(Workspaces& ws, hipStream_t st, const HostPairs& h, cons
 // size only the control words tell -- gets a copy of its own in every form; a later deliver() synchronises the host form when it made one.
 // A call without control words leaves mailbox_words at 0; ctl() is valid after the first deliver().
 struct CallOutputs {
-    static constexpr int CAP = 48;  // block_transactions names 35, block_bodies 41
+    static constexpr int CAP = 48;  // block_transactions names 35, block_bodies 41, block_receipt_segments 20
     struct Item {
         void* dst;
         const uint8_t* src;

@@ -452,3 +452,42 @@ def validate_segment(raw_blocks, seg_first=None, chain_id=1, fork=L.TXS_FORK_PRA
     if bodies is not None:
         body_flags[body] = bodies.block_flags
     return SegmentVerdict(np.asarray(chain.flags, np.uint32).copy(), body_flags, split_status, chain.hashes, chain, bodies)
+
+
+# -------------------------------------------------------------------------------------------- receipts of chain segments
+class ReceiptsVerdict:
+    """validate_receipts' answer: per block `block_flags` (receipt.ReceiptBlockFlags) and `split_status` (SPLIT_OK, SPLIT_BAD_RLP,
+    SPLIT_BAD_RECEIPT), `first_bad` (the least block with either, n if none), `reason` (the names of that block's flags, or its split
+    status; [] when every block is good), and the call's result `receipts`."""
+
+    def __init__(self, block_flags, split_status, receipts):
+        self.block_flags, self.split_status, self.receipts = block_flags, split_status, receipts
+        bad = np.flatnonzero((block_flags != 0) | (split_status != 0))
+        self.first_bad = int(bad[0]) if len(bad) else len(block_flags)
+        self.reason = []
+        if len(bad):
+            b = self.first_bad
+            self.reason = ["BadRlp" if split_status[b] == SPLIT_BAD_RLP else "BadReceipt"] if split_status[b] else receipts.errors(b)
+
+
+def validate_receipts(headers, raw_receipts, eth69=False, tx_counts=None, ctx: Context | None = None) -> ReceiptsVerdict:
+    """The receipts of a chain segment against its headers in one call: `headers` are decoded headers (BlockHeader objects, or the arrays
+    of decode_arrays), `raw_receipts` the per-block elements of a peer's Receipts answer, one per header, in the eth/69 form (no blooms
+    on the wire) or the earlier one.  phant_receipts_decode_rlp splits them; phant_block_receipt_segments decodes every receipt,
+    computes the blooms, (eth/69) rebuilds the consensus encodings and compares each block's receipts root, logs bloom and gas used
+    with its header, and its receipt count with tx_counts[b] where the caller has the transaction counts."""
+    from .receipt import receipt_segments, split_receipts
+    n = len(raw_receipts)
+    if isinstance(headers, dict):
+        expect = {"receipts_root": np.ascontiguousarray(headers["receipts_root"]).reshape(-1, 32)[:n], "logs_bloom": np.ascontiguousarray(headers["logs_bloom"]).reshape(-1, 256)[:n],
+                  "gas_used": np.ascontiguousarray(headers["gas_used"][:n], np.uint64)}
+    else:
+        headers = list(headers)
+        expect = {"receipts_root": [h.receipts_root for h in headers], "logs_bloom": [h.logs_bloom for h in headers], "gas_used": [h.gas_used for h in headers]}
+    if len(expect["gas_used"]) != n:
+        raise ValueError("one header per block of receipts")
+    if tx_counts is not None:
+        expect["tx_count"] = tx_counts
+    a, status = split_receipts(raw_receipts, eth69)
+    res = receipt_segments(a, form=L.RCPTS_ETH69 if eth69 else L.RCPTS_CONSENSUS, expect=expect, logs=False, ctx=ctx)
+    return ReceiptsVerdict(np.asarray(res.block_flags, np.uint32).copy(), status.copy(), res)

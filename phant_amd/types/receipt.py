@@ -147,3 +147,121 @@ def block_receipts(receipts, ctx: Context | None = None, other_lists=(), receipt
         cap = int(out.encoded_len)
     encoded = [enc[int(enc_off[i]):int(enc_off[i + 1])].tobytes() for i in range(n)]
     return BlockReceipts([r.tobytes() for r in roots], roots[receipts_at].tobytes(), bloom.tobytes(), rows[:n], encoded)
+
+
+# ------------------------------------------------------------------------------------ receipts of chain segments from raw messages
+class ReceiptFlags:
+    """flags[i] of receipt_segments"""
+    Undecodable = L.RCPT_UNDECODABLE
+    Bloom = L.RCPT_BLOOM
+    GasOrder = L.RCPT_GAS_ORDER
+    PostState = L.RCPT_POST_STATE
+    ERROR_BITS = L.RCPT_ERROR_BITS
+
+
+class ReceiptBlockFlags:
+    """block_flags[b] of receipt_segments"""
+    Receipt = L.RBLOCK_RECEIPT
+    ReceiptsRoot = L.RBLOCK_ROOT
+    LogsBloom = L.RBLOCK_BLOOM
+    GasUsed = L.RBLOCK_GAS_USED
+    Count = L.RBLOCK_COUNT
+    NAMES = L.RBLOCK_FLAG_NAMES
+
+
+def pack_receipt_segments(blocks):
+    """per block its raw receipt values (one wire form for all) -> the packed arrays phant_block_receipt_segments takes: receipts, rc_off,
+    block_first; never empty arrays.  (pack_receipts above packs the FIELDS of one block for phant_block_receipts.)"""
+    blocks = [[bytes(x) for x in b] for b in blocks]
+    items = [x for b in blocks for x in b]
+    return {"receipts": np.frombuffer(b"".join(items) or b"\x00", np.uint8).copy(), "rc_off": np.cumsum([0] + [len(x) for x in items]).astype(np.uint64),
+            "block_first": np.cumsum([0] + [len(b) for b in blocks]).astype(np.uint32)}
+
+
+def split_receipts(raw_blocks, eth69=False):
+    """phant_receipts_decode_rlp: the per-block elements of a Receipts message (each the RLP list of a block's receipts) -> (the packed
+    arrays of pack_receipt_segments, status uint8[n]); a refused block (status != 0: SPLIT_BAD_RLP, SPLIT_BAD_RECEIPT) has no rows.  Host only."""
+    raws = [bytes(r) for r in raw_blocks]
+    n = len(raws)
+    blob = np.frombuffer(b"".join(raws) or b"\x00", np.uint8).copy()
+    off = np.cumsum([0] + [len(r) for r in raws]).astype(np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    flags = L.RCPTS_SPLIT_ETH69 if eth69 else 0
+    arg = L.PhantReceiptsSplit(C.sizeof(L.PhantReceiptsSplit))
+    fn = L.lib().phant_receipts_decode_rlp
+    a = None
+    for _ in range(2):  # the totals, then the arrays
+        rc = fn(blob.ctypes.data, off.ctypes.data, n, flags, C.byref(arg), status.ctypes.data)
+        if rc != L.OK:
+            raise L.PhantError(rc, "phant_receipts_decode_rlp")
+        if a is None:
+            a = {"receipts": np.zeros(max(int(arg.rc_bytes), 1), np.uint8), "rc_off": np.zeros(int(arg.n) + 1, np.uint64), "block_first": np.zeros(n + 1, np.uint32)}
+            arg.rc_cap, arg.rc_bytes_cap = int(arg.n), int(arg.rc_bytes)
+            arg.receipts, arg.rc_off, arg.block_first = (a[k].ctypes.data for k in ("receipts", "rc_off", "block_first"))
+    return a, status[:n]
+
+
+class ReceiptSegments:
+    """What phant_block_receipt_segments answers: per receipt `tx_type`, `status`, `cum_gas`, `gas_used`, `log_first`, `bloom`, `flags`; per
+    log `log_receipt`, `address`, `topic_first`, `topics`, `data_at`, `data_len`; `encoded` (n byte strings: the consensus encodings) where
+    asked for; per block `receipts_root` (where computed), `logs_bloom`, `block_gas_used`, `block_first_bad`, `block_flags`; the scalars
+    `first_bad_block`, `n_logs`, `n_topics`."""
+    FLAG_NAMES = L.RBLOCK_FLAG_NAMES
+
+    def __init__(self, arrays, first_bad_block, n_logs, n_topics):
+        self.first_bad_block, self.n_logs, self.n_topics = first_bad_block, n_logs, n_topics
+        self.__dict__.update(arrays)
+        self.n, self.n_blocks = len(self.flags), len(self.block_flags)
+
+    def errors(self, b):
+        """the names of block b's flags"""
+        return [name for k, name in enumerate(self.FLAG_NAMES) if int(self.block_flags[b]) >> k & 1]
+
+
+def receipt_segments(packed, form=L.RCPTS_CONSENSUS, expect=None, roots=True, logs=True, encoded=False, ctx: Context | None = None) -> ReceiptSegments:
+    """phant_block_receipt_segments over the packed arrays of pack_receipt_segments / split_receipts.  expect: a dict with any of
+    receipts_root ((n_blocks, 32) uint8 or 32-byte strings), logs_bloom ((n_blocks, 256) or 256-byte strings), gas_used, tx_count (integers);
+    a missing key skips its comparison.  roots=False: no root is computed unless one is expected; logs=False: no per-log array;
+    encoded=True: the consensus encodings, which an ETH69 caller stores."""
+    ctx = ctx or default_context()
+    expect = expect or {}
+    a = {k: np.ascontiguousarray(packed[k]) for k in ("receipts", "rc_off", "block_first")}
+    nb, n = len(a["block_first"]) - 1, len(a["rc_off"]) - 1
+    nbytes = int(a["rc_off"][-1])
+
+    def rows(v, width):
+        if v is None:
+            return None
+        if isinstance(v, np.ndarray) and v.dtype == np.uint8:
+            r = np.ascontiguousarray(v).reshape(-1, width)
+        else:
+            r = np.frombuffer(b"".join(bytes(x) for x in v) or bytes(width), np.uint8).reshape(-1, width).copy()
+        if len(r) < nb:
+            raise ValueError("an expected value per block")
+        return r
+
+    ins = dict(a, receipts_root=rows(expect.get("receipts_root"), 32), logs_bloom=rows(expect.get("logs_bloom"), 256),
+               gas_used=None if expect.get("gas_used") is None else np.ascontiguousarray(expect["gas_used"], np.uint64),
+               tx_count=None if expect.get("tx_count") is None else np.ascontiguousarray(expect["tx_count"], np.uint32))
+    for k in ("gas_used", "tx_count"):
+        if ins[k] is not None and len(ins[k]) < nb:
+            raise ValueError(f"{k}: one value per block")
+    ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
+    # the rows of the logs and the bytes of the encodings are the call's to say: room for what the bytes can hold at most first
+    count = {"n": n, "n_blocks": nb, "n_logs": nbytes // 24 if logs else 0, "n_topics": nbytes // 33 if logs else 0, "encoded_len": nbytes + 268 * n if encoded else 0}
+    skip = set() if roots else {"receipts_root"}
+    skip |= set() if logs else {"log_receipt", "address", "topic_first", "topics", "data_at", "data_len"}
+    skip |= set() if encoded else {"encoded", "encoded_off"}
+    out_arrays = {name: np.zeros((count[r] + extra, k) if k > 1 else count[r] + extra, dtype) for name, dtype, k, r, extra in L.RSEG_OUTPUTS if name not in skip}
+    arg = L.PhantRcptSegsIn(C.sizeof(L.PhantRcptSegsIn), int(form), nb, n, count["n_logs"], count["n_topics"], (C.c_uint32 * 2)(0, 0), ptr(a["receipts"]) if n else None,
+                            ptr(a["rc_off"]) if n else None, nbytes, a["block_first"].ctypes.data, *[ptr(ins[k]) for k in L.RSEG_INPUTS[3:]])
+    out = L.PhantRcptSegsOut(C.sizeof(L.PhantRcptSegsOut), 0, 0, 0, count["encoded_len"], 0, *[ptr(out_arrays.get(name)) for name, _, _, _, _ in L.RSEG_OUTPUTS])
+    ctx.check(ctx._lib.phant_block_receipt_segments(ctx.handle, C.byref(arg), C.byref(out)))
+    nl, nt = int(out.n_logs), int(out.n_topics)
+    for name, _, _, r, extra in L.RSEG_OUTPUTS:
+        if name in out_arrays and r in ("n_logs", "n_topics"):
+            out_arrays[name] = out_arrays[name][:(nl if r == "n_logs" else nt) + extra]
+    if encoded:
+        off, blob = out_arrays.pop("encoded_off"), out_arrays["encoded"]
+        out_arrays["encoded"] = [blob[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+    return ReceiptSegments(out_arrays, int(out.first_bad_block), nl, nt)
