@@ -9,21 +9,15 @@
 //   (tx_decode_kernel, tx_hash_kernel, the tuples' kernels, ecrecover_kernel: transactions.hip.h's, over the whole segment)
 //   body_rules_kernel     a lane per transaction: tx::rules_row under the parameters of its block; then per distinct block of the wave ONE
 //                         lane lowers the block's first bad transaction and adds the block's versioned hashes
-//   body_len_kernel       a lane per trie value (its length, in trie order) and per trie (its keys' bytes, its first value)
-//   (exclusive scan)      radix_sort.hip's, over both at once
-//   body_pairs_kernel     a WAVE per value: its offset, its key rlp(index) and that key's offset, its bytes from index order into
-//                         trie order (receipts.hip.h's position functions)
+//   (seg::launch_forest)  segment_lists.hip.h's lengths, scan and pairs over body::Src: a WAVE per value copies its bytes from index
+//                         order into trie order
 //   (trie_forest_dev)     all lists of the segment, tries 0 .. n_blocks - 1 the transactions, the withdrawals behind them
 //   body_verdict_kernel   a lane per block: roots and blob gas against what the header says, block_flags, the least bad block
 //
 // Plain C++ plus the cross-lane builtins keyed_table.hip.h uses: tests/emu.py compiles this file for the host.
 #pragma once
-#include <type_traits>
-
-#include "receipts.hip.h"
+#include "segment_lists.hip.h"
 #include "transactions.hip.h"
-#include "trie_build.h"
-#include "wave_util.hip.h"
 
 namespace phant {
 namespace body {
@@ -49,34 +43,23 @@ struct Seg {
     unsigned long long* blob_gas;        // zeroed: the block's versioned hashes; the verdict multiplies
 };
 
-// 64-bit offsets from 0 to `bytes`, never backwards, no item of 4 GiB; 32-bit firsts from 0 to `total`, never backwards
-PHANT_DEV uint32_t off_flags(const uint64_t* __restrict__ off, uint32_t i, uint32_t n, uint64_t bytes) {
-    const uint64_t b = off[i], e = off[i + 1u];
-    if (e < b || (i == 0u && b != 0u) || (i + 1u == n && e != bytes)) return tx::F_INVALID;
-    return e - b > 0xffffffffull ? (uint32_t)tx::F_TOO_LONG : 0u;
-}
-PHANT_DEV uint32_t first_flags(const uint32_t* __restrict__ first, uint32_t i, uint32_t n, uint32_t total) {
-    const uint32_t b = first[i], e = first[i + 1u];
-    return e < b || (i == 0u && b != 0u) || (i + 1u == n && e != total) ? (uint32_t)tx::F_INVALID : 0u;
-}
-
 __global__ void __launch_bounds__(256) body_check_kernel(const uint64_t* __restrict__ tx_off, uint64_t tx_bytes, const uint64_t* __restrict__ wd_off,
                                                          uint64_t wd_bytes, const uint32_t* __restrict__ block_first,
                                                          const uint32_t* __restrict__ wd_first, uint32_t n, uint32_t n_wd, uint32_t n_blocks,
                                                          uint32_t* __restrict__ ctl) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     uint32_t f = 0;
-    if (i < n) f |= off_flags(tx_off, i, n, tx_bytes);
-    if (i < n_wd) f |= off_flags(wd_off, i, n_wd, wd_bytes);
-    if (i < n_blocks) f |= first_flags(block_first, i, n_blocks, n);
-    if (i < n_blocks && wd_first) f |= first_flags(wd_first, i, n_blocks, n_wd);
+    if (i < n) f |= seg::off_flags(tx_off, i, n, tx_bytes);
+    if (i < n_wd) f |= seg::off_flags(wd_off, i, n_wd, wd_bytes);
+    if (i < n_blocks) f |= seg::first_flags(block_first, i, n_blocks, n);
+    if (i < n_blocks && wd_first) f |= seg::first_flags(wd_first, i, n_blocks, n_wd);
     if (f) atomicOr(ctl, f);
 }
 
 __global__ void __launch_bounds__(256) body_tx_block_kernel(const uint32_t* __restrict__ block_first, uint32_t n_blocks, uint32_t n,
                                                             uint32_t* __restrict__ tx_block) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) tx_block[i] = upper_bound(block_first, n_blocks + 1u, i) - 1u;  // (block_first[n_blocks] = n > i)
+    if (i < n) tx_block[i] = seg::block_of(block_first, n_blocks, i);
 }
 
 // The rules with the parameters read through tx_block.  The lanes of a wave hold consecutive transactions, so the lanes of one block
@@ -126,84 +109,43 @@ __global__ void __launch_bounds__(64) body_rules_kernel(uint32_t n, Seg sg, tx::
     if (all_bad && lane == (uint32_t)__builtin_ctzll(all_bad)) atomicMax(dv.ctl + 1, n - i);  // the segment's least flagged index
 }
 
-// ---- the index-keyed pairs of the forest: values 0 .. n_tx - 1 are the transactions (tries 0 .. tx_tries - 1), the withdrawals
-// follow; each list in trie order.  n_tx / tx_tries (n_wd / wd_tries) are 0 when nobody asks for that root.
-struct Pairs {
+// ---- the lists of the forest (segment_lists.hip.h): values 0 .. n_tx - 1 are the transactions (tries 0 .. tx_tries - 1), the
+// withdrawals follow.  n_tx / tx_tries (n_wd / wd_tries) are 0 when nobody asks for that root.
+struct Src {
     const uint8_t *txs, *wd;
     const uint64_t *tx_off, *wd_off;
     const uint32_t *block_first, *wd_first, *tx_block;
     uint32_t n_blocks, n_tx, n_wd, tx_tries, wd_tries;
-    uint32_t total, tries;  // n_tx + n_wd, tx_tries + wd_tries
-    uint32_t* len;          // total + 1 lengths of values, then tries + 1 of the tries' keys; scanned in place
-    uint32_t* seg_first;    // tries + 1
-    uint32_t* key_off;
-    uint64_t* val_off;
-    uint8_t *keys, *vals;
-    uint64_t key_cap, val_cap;
+    struct Item {
+        uint32_t trie, pos, index;
+        const uint8_t* src;
+        uint64_t len;
+    };
+    // value g: its trie by bisection (a transaction's is its block, which body_tx_block_kernel has found), its position and index there
+    PHANT_DEV Item item(uint32_t g) const {
+        Item it;
+        const bool is_tx = g < n_tx;
+        const uint32_t w = is_tx ? g : g - n_tx;
+        const uint32_t* const first = is_tx ? block_first : wd_first;
+        const uint32_t b = is_tx ? tx_block[g] : seg::block_of(first, n_blocks, w);
+        const uint32_t begin = first[b], count = first[b + 1u] - begin;
+        it.trie = is_tx ? b : tx_tries + b;
+        it.pos = w - begin;
+        it.index = seg::index_of_pos(it.pos, count);
+        const uint64_t* const off = is_tx ? tx_off : wd_off;
+        const uint64_t at = off[begin + it.index];
+        it.src = (is_tx ? txs : wd) + at;
+        it.len = off[begin + it.index + 1u] - at;
+        return it;
+    }
+    PHANT_DEV uint32_t trie(uint32_t t, uint32_t& count) const {
+        const bool is_tx = t < tx_tries;
+        const uint32_t* const first = is_tx ? block_first + t : wd_first + (t - tx_tries);
+        count = first[1] - first[0];
+        return (is_tx ? 0u : n_tx) + first[0];
+    }
+    PHANT_DEV void write(uint8_t* out, const Item& it, uint32_t lane) const { wave_copy(out, it.src, it.len, lane); }
 };
-struct Item {
-    uint32_t trie, pos, index;
-    const uint8_t* src;
-    uint64_t len;
-};
-// value g: its trie by bisection (a transaction's is its block, which body_tx_block_kernel has found), its position and index there
-PHANT_DEV Item item_of(const Pairs& a, uint32_t g) {
-    Item it;
-    const bool is_tx = g < a.n_tx;
-    const uint32_t w = is_tx ? g : g - a.n_tx;
-    const uint32_t* const first = is_tx ? a.block_first : a.wd_first;
-    const uint32_t b = is_tx ? a.tx_block[g] : upper_bound(first, a.n_blocks + 1u, w) - 1u;
-    const uint32_t begin = first[b], count = first[b + 1u] - begin;
-    it.trie = is_tx ? b : a.tx_tries + b;
-    it.pos = w - begin;
-    it.index = rc::index_of_pos(it.pos, count);
-    const uint64_t* const off = is_tx ? a.tx_off : a.wd_off;
-    const uint64_t at = off[begin + it.index];
-    it.src = (is_tx ? a.txs : a.wd) + at;
-    it.len = off[begin + it.index + 1u] - at;
-    return it;
-}
-
-__global__ void __launch_bounds__(256) body_len_kernel(Pairs a) {
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g > a.total + 1u + a.tries) return;
-    uint32_t v = 0;
-    if (g < a.total) {
-        v = (uint32_t)item_of(a, g).len;  // (checked: below 4 GiB)
-    } else if (g > a.total) {
-        const uint32_t t = g - a.total - 1u;
-        if (t == a.tries) {
-            a.seg_first[t] = a.total;
-        } else {
-            const bool is_tx = t < a.tx_tries;
-            const uint32_t* const first = is_tx ? a.block_first : a.wd_first;
-            const uint32_t b = is_tx ? t : t - a.tx_tries;
-            a.seg_first[t] = (is_tx ? 0u : a.n_tx) + first[b];
-            v = rc::key_bytes_before(first[b + 1u] - first[b]);
-        }
-    }
-    a.len[g] = v;
-}
-
-// len scanned: S[g] = the bytes of the values in front of g; S[total] = S[total + 1] = all of them; S[total + 1 + t] - S[total] = the bytes
-// of the keys of the tries in front of t (modulo 2^32, which the difference undoes)
-__global__ void __launch_bounds__(256) body_pairs_kernel(Pairs a) {
-    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (g > a.total) return;
-    const uint32_t all = a.len[a.total];
-    if (g == a.total) {
-        if (lane == 0u) a.val_off[g] = all, a.key_off[g] = a.len[a.total + 1u + a.tries] - all;
-        return;
-    }
-    const Item it = item_of(a, g);
-    const uint32_t at = a.len[g], ko = a.len[a.total + 1u + it.trie] - all + rc::key_bytes_before(it.pos);
-    if ((uint64_t)ko + 5u > a.key_cap || (uint64_t)at + it.len > a.val_cap) return;  // (cannot happen: both arrays are sized from the same rules)
-    if (lane == 0u) {
-        a.val_off[g] = at, a.key_off[g] = ko;
-        (void)put_uint(a.keys + ko, it.index);
-    }
-    wave_copy(a.vals + at, it.src, it.len, lane);
-}
 
 __global__ void __launch_bounds__(256) body_verdict_kernel(Seg sg, uint32_t tx_tries, uint32_t wd_tries, uint32_t* __restrict__ ctl) {
     const uint32_t b = blockIdx.x * 256u + threadIdx.x;
@@ -211,13 +153,8 @@ __global__ void __launch_bounds__(256) body_verdict_kernel(Seg sg, uint32_t tx_t
     const uint32_t count = sg.block_first[b + 1u] - sg.block_first[b], rel = sg.first_bad[b];
     const unsigned long long gas = tx::GAS_PER_BLOB * sg.blob_gas[b];
     uint32_t f = rel ? (uint32_t)PHANT_BODY_TX : 0u;
-    auto differs = [](const uint8_t* x, const uint8_t* y) {
-        uint32_t d = 0;
-        for (uint32_t k = 0; k < 32u; ++k) d |= (uint32_t)(x[k] ^ y[k]);
-        return d != 0u;
-    };
-    if (sg.exp_txs_root && tx_tries && differs(sg.exp_txs_root + 32ull * b, sg.roots + 32ull * b)) f |= PHANT_BODY_TXS_ROOT;
-    if (sg.exp_wd_root && wd_tries && differs(sg.exp_wd_root + 32ull * b, sg.roots + 32ull * (tx_tries + b))) f |= PHANT_BODY_WD_ROOT;
+    if (sg.exp_txs_root && tx_tries && seg::bytes_differ(sg.exp_txs_root + 32ull * b, sg.roots + 32ull * b, 32u)) f |= PHANT_BODY_TXS_ROOT;
+    if (sg.exp_wd_root && wd_tries && seg::bytes_differ(sg.exp_wd_root + 32ull * b, sg.roots + 32ull * (tx_tries + b), 32u)) f |= PHANT_BODY_WD_ROOT;
     if (sg.exp_blob_gas && sg.exp_blob_gas[b] != gas) f |= PHANT_BODY_BLOB_GAS;
     sg.first_bad[b] = count - rel;
     sg.blob_gas[b] = gas;
@@ -227,21 +164,10 @@ __global__ void __launch_bounds__(256) body_verdict_kernel(Seg sg, uint32_t tx_t
 
 // what the host form refuses before anything is copied (tx_off: tx::check_host)
 inline int32_t check_host(const phant_bodies_in& in, std::string& err) {
-    const uint32_t nb = in.n_blocks;
-    if (in.block_first[0] != 0u || in.block_first[nb] != in.n) return err = "block_bodies: block_first does not run from 0 to n", PHANT_E_INVALID_ARG;
-    for (uint32_t b = 0; b < nb; ++b)
-        if (in.block_first[b + 1u] < in.block_first[b]) return err = "block_bodies: block_first goes backwards", PHANT_E_INVALID_ARG;
+    if (const int32_t rc = seg::check_firsts_host("block_bodies", "block_first", "n", in.block_first, in.n_blocks, in.n, err)) return rc;
     if (!in.wd_first) return PHANT_OK;
-    if (in.wd_first[0] != 0u || in.wd_first[nb] != in.n_wd) return err = "block_bodies: wd_first does not run from 0 to n_wd", PHANT_E_INVALID_ARG;
-    for (uint32_t b = 0; b < nb; ++b)
-        if (in.wd_first[b + 1u] < in.wd_first[b]) return err = "block_bodies: wd_first goes backwards", PHANT_E_INVALID_ARG;
-    if (!in.n_wd) return PHANT_OK;
-    if (in.wd_off[0] != 0u) return err = "block_bodies: wd_off does not run from 0", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < in.n_wd; ++i)
-        if (in.wd_off[i + 1u] < in.wd_off[i]) return err = "block_bodies: wd_off goes backwards", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < in.n_wd; ++i)
-        if (in.wd_off[i + 1u] - in.wd_off[i] > 0xffffffffull) return err = "block_bodies: a withdrawal of 4 GiB or more", PHANT_E_UNSUPPORTED;
-    return PHANT_OK;
+    if (const int32_t rc = seg::check_firsts_host("block_bodies", "wd_first", "n_wd", in.wd_first, in.n_blocks, in.n_wd, err)) return rc;
+    return in.n_wd ? seg::check_offsets_host("block_bodies", "wd_off", "withdrawal", in.wd_off, in.n_wd, err) : PHANT_OK;
 }
 
 }  // namespace body
@@ -268,15 +194,14 @@ int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, 
     }
     // which tries: a root somebody asks for or expects
     const bool want_txr = out.transactions_root || in.transactions_root, want_wdr = in.wd_first && (out.withdrawals_root || in.withdrawals_root);
-    Pairs p;
-    std::memset(&p, 0, sizeof p);
-    p.n_blocks = nb, p.n_tx = want_txr ? n : 0u, p.n_wd = want_wdr ? n_wd : 0u, p.tx_tries = want_txr ? nb : 0u, p.wd_tries = want_wdr ? nb : 0u;
-    const uint64_t total64 = (uint64_t)p.n_tx + p.n_wd, val_bytes = (want_txr ? c.bytes : 0u) + (want_wdr ? wd_bytes : 0u);
+    Src src;
+    std::memset(&src, 0, sizeof src);
+    src.n_blocks = nb, src.n_tx = want_txr ? n : 0u, src.n_wd = want_wdr ? n_wd : 0u, src.tx_tries = want_txr ? nb : 0u, src.wd_tries = want_wdr ? nb : 0u;
+    const uint64_t total64 = (uint64_t)src.n_tx + src.n_wd, val_bytes = (want_txr ? c.bytes : 0u) + (want_wdr ? wd_bytes : 0u);
     if (total64 + 2ull * nb + 2u >= 0x7fffffffull) return err = "block_bodies: more than 2^31 - 2 items in one call", PHANT_E_UNSUPPORTED;
     if (val_bytes > 0xffffffffull) return err = "block_bodies: more than 4 GiB of trie values in one call", PHANT_E_UNSUPPORTED;
-    p.total = (uint32_t)total64, p.tries = p.tx_tries + p.wd_tries;
-    p.key_cap = (uint64_t)rc::key_bytes_before(p.total) + 16u, p.val_cap = val_bytes;
-    const uint32_t scan_n = p.total + 1u + p.tries + 1u;
+    seg::IndexForest p{};
+    p.size((uint32_t)total64, src.tx_tries + src.wd_tries, val_bytes);
 
     // ---- the arena: the per-block outputs, the words to zero and the transactions' control words and outputs in front (one span goes
     // back), the internal arrays, (host form) every input in one piece, the forest's pairs last
@@ -288,12 +213,7 @@ int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, 
     sg.exp_txs_root = in.transactions_root, sg.exp_wd_root = in.wd_first ? in.withdrawals_root : nullptr, sg.exp_blob_gas = in.blob_gas_used;
     // (the carve runs twice, and its first run leaves null pointers behind: what is wanted is decided from `in` alone)
     const bool have_gas_limit = (in.flags & PHANT_TXS_HAVE_GAS_LIMIT) != 0u, have_exp_wd = in.wd_first && in.withdrawals_root;
-    uint32_t* d_scan = nullptr;
     const void* inputs_end = nullptr;
-    auto input = [&](auto& io, auto*& member, size_t count, bool wanted) {
-        using T = std::remove_cv_t<std::remove_pointer_t<std::remove_reference_t<decltype(member)>>>;
-        if (wanted) member = io.template take<T>(count + (sizeof(T) == 1 ? 16 : 0));
-    };
     auto carve = [&](auto& io) {
         sg.tx_block = io.template take<uint32_t>((size_t)n);
         sg.roots = io.template take<uint8_t>(32 * (size_t)p.tries);
@@ -302,27 +222,19 @@ int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, 
         sg.blob_gas = io.template take<unsigned long long>((size_t)nb);
         tx::call_carve(io, c, dev || !n);
         if (!dev) {
-            input(io, sg.block_first, (size_t)nb + 1, true);
-            input(io, sg.wd_first, (size_t)nb + 1, in.wd_first != nullptr);
-            input(io, sg.wd_off, (size_t)n_wd + 1, n_wd != 0u);
-            input(io, sg.wd, (size_t)wd_bytes, n_wd != 0u);
-            input(io, sg.base_fee, 32 * (size_t)nb, in.base_fee != nullptr);
-            input(io, sg.blob_base_fee, 32 * (size_t)nb, in.blob_base_fee != nullptr);
-            input(io, sg.gas_limit, (size_t)nb, have_gas_limit);
-            input(io, sg.exp_txs_root, 32 * (size_t)nb, in.transactions_root != nullptr);
-            input(io, sg.exp_wd_root, 32 * (size_t)nb, have_exp_wd);
-            input(io, sg.exp_blob_gas, (size_t)nb, in.blob_gas_used != nullptr);
+            take_input(io, sg.block_first, (size_t)nb + 1, true);
+            take_input(io, sg.wd_first, (size_t)nb + 1, in.wd_first != nullptr);
+            take_input(io, sg.wd_off, (size_t)n_wd + 1, n_wd != 0u);
+            take_input(io, sg.wd, (size_t)wd_bytes, n_wd != 0u);
+            take_input(io, sg.base_fee, 32 * (size_t)nb, in.base_fee != nullptr);
+            take_input(io, sg.blob_base_fee, 32 * (size_t)nb, in.blob_base_fee != nullptr);
+            take_input(io, sg.gas_limit, (size_t)nb, have_gas_limit);
+            take_input(io, sg.exp_txs_root, 32 * (size_t)nb, in.transactions_root != nullptr);
+            take_input(io, sg.exp_wd_root, 32 * (size_t)nb, have_exp_wd);
+            take_input(io, sg.exp_blob_gas, (size_t)nb, in.blob_gas_used != nullptr);
             inputs_end = io.template take<uint8_t>(0);
         }
-        if (p.tries) {
-            p.len = io.template take<uint32_t>((size_t)scan_n + 4);
-            d_scan = io.template take<uint32_t>(scan_scratch_entries(scan_n));
-            p.seg_first = io.template take<uint32_t>((size_t)p.tries + 1);
-            p.key_off = io.template take<uint32_t>((size_t)p.total + 1);
-            p.val_off = io.template take<uint64_t>((size_t)p.total + 1);
-            p.keys = io.template take<uint8_t>((size_t)p.key_cap);
-            p.vals = io.template take<uint8_t>((size_t)p.val_cap + 16);
-        }
+        if (p.tries) p.carve(io);
     };
     if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_bodies", "workspace", err)) return rc;
     tx::Dev& d = c.d;
@@ -351,9 +263,9 @@ int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, 
                            n_wd, nb, d.ctl);
         CALL_TRY("block_bodies", hipGetLastError());
         CALL_TRY("block_bodies", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, tx::CTL_WORDS, st));
-        if (mb[0] & tx::F_INVALID)
+        if (mb[0] & seg::F_INVALID)
             return err = "block_bodies_dev: tx_off, wd_off, block_first or wd_first does not run from 0 to its total, or goes backwards", PHANT_E_INVALID_ARG;
-        if (mb[0] & tx::F_TOO_LONG) return err = "block_bodies_dev: a transaction or a withdrawal of 4 GiB or more", PHANT_E_UNSUPPORTED;
+        if (mb[0] & seg::F_TOO_LONG) return err = "block_bodies_dev: a transaction or a withdrawal of 4 GiB or more", PHANT_E_UNSUPPORTED;
     }
 
     // ---- the transactions: their blocks, decode, hash, (the tuples,) ONE recovery over the segment, the rules per block
@@ -367,17 +279,12 @@ int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, 
 
     // ---- the tries of all blocks: lengths, one scan, pairs, one forest pass
     if (p.tries) {
-        p.txs = c.d_txs, p.tx_off = c.d_off, p.wd = sg.wd, p.wd_off = sg.wd_off;
-        p.block_first = sg.block_first, p.wd_first = sg.wd_first, p.tx_block = sg.tx_block;
-        hipLaunchKernelGGL(body_len_kernel, dim3(blocks_of(scan_n, 256)), dim3(256), 0, st, p);
-        CALL_TRY("block_bodies", hipGetLastError());
-        CALL_TRY("block_bodies", launch_exclusive_scan_u32(p.len, scan_n, d_scan, st));
-        hipLaunchKernelGGL(body_pairs_kernel, dim3(blocks_of((uint64_t)p.total + 1, 4)), dim3(256), 0, st, p);
-        CALL_TRY("block_bodies", hipGetLastError());
-        const int32_t rc = trie_forest_dev(ws, st, TriePairs{p.keys, p.key_off, p.key_cap, p.vals, p.val_off, p.val_cap, p.total, p.seg_first, p.tries, sg.roots}, err);
-        if (rc) return rc;
+        src.txs = c.d_txs, src.tx_off = c.d_off, src.wd = sg.wd, src.wd_off = sg.wd_off;
+        src.block_first = sg.block_first, src.wd_first = sg.wd_first, src.tx_block = sg.tx_block;
+        CALL_TRY("block_bodies", seg::launch_forest(src, p, st));
+        if (const int32_t rc = trie_forest_dev(ws, st, p.trie_pairs(sg.roots), err)) return rc;
     }
-    hipLaunchKernelGGL(body_verdict_kernel, dim3(blocks_of(nb, 256)), dim3(256), 0, st, sg, p.tx_tries, p.wd_tries, d.ctl);
+    hipLaunchKernelGGL(body_verdict_kernel, dim3(blocks_of(nb, 256)), dim3(256), 0, st, sg, src.tx_tries, src.wd_tries, d.ctl);
     CALL_TRY("block_bodies", hipGetLastError());
 
     // ---- out: one span from the per-block outputs through the control words up to the last wanted output
@@ -385,7 +292,7 @@ int32_t block_bodies(Workspaces& ws, hipStream_t st, const phant_bodies_in& in, 
     static_assert(tx::CALL_OUTPUTS + 6 <= CallOutputs::CAP, "the outputs of a segment fit");
     outs.add(out.tx_block, sg.tx_block, 4 * (size_t)n);
     if (want_txr) outs.add(out.transactions_root, sg.roots, 32 * (size_t)nb);
-    if (want_wdr) outs.add(out.withdrawals_root, sg.roots + 32 * (size_t)p.tx_tries, 32 * (size_t)nb);
+    if (want_wdr) outs.add(out.withdrawals_root, sg.roots + 32 * (size_t)src.tx_tries, 32 * (size_t)nb);
     outs.add(out.block_flags, sg.block_flags, 4 * (size_t)nb);
     outs.add(out.block_first_bad, sg.first_bad, 4 * (size_t)nb);
     outs.add(out.block_blob_gas_used, sg.blob_gas, 8 * (size_t)nb);

@@ -1,8 +1,8 @@
-// receipt_segments.hip.h -- the receipts of a chain segment from raw messages in one call (included by bulk_keccak.hip behind receipts.hip.h
-// and bodies.hip.h): a strict RLP decode of every receipt and of its logs, the logs' blooms, the consensus encodings
+// receipt_segments.hip.h -- the receipts of a chain segment from raw messages in one call (included by bulk_keccak.hip behind
+// receipts.hip.h): a strict RLP decode of every receipt and of its logs, the logs' blooms, the consensus encodings
 // an eth/69 peer no longer sends, the per-block verdicts, and the receipts tries of all blocks as ONE forest pass.
 //
-//   rseg_check_kernel    device form only: rc_off and block_first as the caller states them, a lane per entry (bodies.hip.h's rules); the
+//   rseg_check_kernel    device form only: rc_off and block_first as the caller states them, a lane per entry (segment_lists.hip.h's rules); the
 //                        host reads the verdict before any other kernel indexes with them
 //   rseg_decode_kernel   a lane per receipt: the head's items and the headers of its logs, never a payload; shapes validated, logs and
 //                        topics counted
@@ -11,26 +11,23 @@
 //   rseg_items_kernel    a lane per bloom item (an address or a topic): its bytes out, hashed, bloom_add_digest into its receipt's row
 //   rseg_rows_kernel     a WAVE per receipt: the embedded bloom against the computed one (64 dwords), the gas rule, the block's bloom and
 //                        its first bad row
-//   rseg_len_kernel      a lane per trie value (its length, in trie order) and per trie (its keys' bytes, its first value)
-//   (exclusive scan)     over both at once
-//   rseg_pairs_kernel    a WAVE per value: copied (consensus form, or a row nobody could decode) or built (ETH69) in trie order, its
-//                        key rlp(index)
+//   (seg::launch_forest) segment_lists.hip.h's lengths, scan and pairs over rseg::Seg: a WAVE per value, copied (consensus form, or a
+//                        row nobody could decode) or built (ETH69) in trie order
 //   rseg_gather_kernel   ETH69, a wave per receipt: the built encoding back in index order for the caller who stores it
 //   (trie_forest_dev)    one trie per block
 //   rseg_verdict_kernel  a lane per block: the last gas, root, bloom, gas and count against what the header says
 //
 // Every offset inside a receipt is 32 bits and relative to the receipt's first byte; rlp.h's reader compares each declared length with
 // what is left of the ROW before anything is added to it, so no lane reads outside [rc_off[i], rc_off[i + 1]).
-// Plain C++ plus the cross-lane builtins bodies.hip.h uses: tests/emu.py compiles this file for the host.
+// Plain C++ plus the cross-lane builtins segment_lists.hip.h uses: tests/emu.py compiles this file for the host.
 #pragma once
-#include "bodies.hip.h"
 #include "receipts.hip.h"
-#include "wave_util.hip.h"
+#include "segment_lists.hip.h"
 
 namespace phant {
 namespace rseg {
 
-// the call's control words (device memory, zeroed): [0] = tx::F_INVALID / F_TOO_LONG of the check, [1] = n_blocks - (the least flagged
+// the call's control words (device memory, zeroed): [0] = seg::F_INVALID / F_TOO_LONG of the check, [1] = n_blocks - (the least flagged
 // block) or 0, [2] = n_logs, [3] = n_topics, [4] = the bytes of the consensus encodings (ETH69; below 2^32 like the call's values)
 constexpr uint32_t CTL_WORDS = 8, CTL_BAD_BLOCK = 1, CTL_LOGS = 2, CTL_TOPICS = 3, CTL_ENC = 4;
 // what an ETH69 receipt grows by at most when its consensus encoding is built: a type byte, 0xb9 0x01 0x00 and the bloom, a longer list header
@@ -64,6 +61,21 @@ struct Seg {
     uint32_t* first_bad;    // zeroed: count - (the least flagged row of the block); the verdict turns it round
     uint32_t* block_flags;
     uint32_t* ctl;
+    uint8_t* enc;  // ETH69: the built encodings in index order, or null
+    uint64_t* enc_off;
+    uint64_t enc_cap;
+
+    // the lists of the forest (segment_lists.hip.h; defined below): one trie per block
+    struct Item {
+        uint32_t trie, pos, index, row, len;
+        bool built;
+    };
+    PHANT_DEV Item item(uint32_t g) const;
+    PHANT_DEV uint32_t trie(uint32_t t, uint32_t& count) const {
+        count = block_first[t + 1u] - block_first[t];
+        return block_first[t];
+    }
+    PHANT_DEV void write(uint8_t* out, const Item& it, uint32_t lane) const;
 };
 
 // ---- the strict decode of one receipt: m = its bytes, len of them
@@ -144,8 +156,8 @@ __global__ void __launch_bounds__(256) rseg_check_kernel(const uint64_t* __restr
                                                          uint32_t n, uint32_t n_blocks, uint32_t* __restrict__ ctl) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     uint32_t f = 0;
-    if (i < n) f |= body::off_flags(rc_off, i, n, rc_bytes);
-    if (i < n_blocks) f |= body::first_flags(block_first, i, n_blocks, n);
+    if (i < n) f |= seg::off_flags(rc_off, i, n, rc_bytes);
+    if (i < n_blocks) f |= seg::first_flags(block_first, i, n_blocks, n);
     if (f) atomicOr(ctl, f);
 }
 
@@ -223,7 +235,7 @@ __global__ void __launch_bounds__(256) rseg_items_kernel(Seg sg) {
 __global__ void __launch_bounds__(256) rseg_rows_kernel(Seg sg) {
     const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (i >= sg.n) return;
-    const uint32_t b = upper_bound(sg.block_first, sg.n_blocks + 1u, i) - 1u, first = sg.block_first[b];
+    const uint32_t b = seg::block_of(sg.block_first, sg.n_blocks, i), first = sg.block_first[b];
     const uint32_t df = sg.dflags[i];
     const bool ok = !(df & PHANT_RCPT_UNDECODABLE);
     uint32_t f = df;
@@ -250,110 +262,56 @@ __global__ void __launch_bounds__(256) rseg_rows_kernel(Seg sg) {
     if (f & PHANT_RCPT_ERROR_BITS) atomicMax(sg.first_bad + b, sg.block_first[b + 1u] - i);  // = count - (i - first)
 }
 
-// ---- the index-keyed pairs of the forest, one trie per block, each list in trie order
-struct Pairs {
-    uint32_t total, tries;  // n (0: no value is wanted), n_blocks
-    uint32_t* len;          // total + 1 lengths of values, then tries + 1 of the tries' keys; scanned in place
-    uint32_t* seg_first;    // tries + 1
-    uint32_t* key_off;
-    uint64_t* val_off;
-    uint8_t *keys, *vals;
-    uint64_t key_cap, val_cap;
-    uint8_t* enc;           // ETH69: the built encodings in index order, or null
-    uint64_t* enc_off;
-    uint64_t enc_cap;
-};
-struct Item {
-    uint32_t trie, pos, index, row, len;
-    bool built;
-};
-PHANT_DEV Item item_of(const Seg& sg, uint32_t g) {
+// ---- value g of the forest: its block, its position and index there, copied or built
+PHANT_DEV Seg::Item Seg::item(uint32_t g) const {
     Item it;
-    it.trie = upper_bound(sg.block_first, sg.n_blocks + 1u, g) - 1u;
-    const uint32_t begin = sg.block_first[it.trie], count = sg.block_first[it.trie + 1u] - begin;
+    it.trie = seg::block_of(block_first, n_blocks, g);
+    const uint32_t begin = block_first[it.trie], count = block_first[it.trie + 1u] - begin;
     it.pos = g - begin;
-    it.index = rc::index_of_pos(it.pos, count);
+    it.index = seg::index_of_pos(it.pos, count);
     it.row = begin + it.index;
-    const uint32_t raw = (uint32_t)(sg.rc_off[it.row + 1u] - sg.rc_off[it.row]);
-    it.built = sg.eth69 && !(sg.dflags[it.row] & PHANT_RCPT_UNDECODABLE);
-    it.len = it.built ? (uint32_t)built_len(sg.tx_type[it.row], sg.head_at[it.row], raw) : raw;  // (the call's values were bounded below 2^32)
+    const uint32_t raw = (uint32_t)(rc_off[it.row + 1u] - rc_off[it.row]);
+    it.built = eth69 && !(dflags[it.row] & PHANT_RCPT_UNDECODABLE);
+    it.len = it.built ? (uint32_t)built_len(tx_type[it.row], head_at[it.row], raw) : raw;  // (the call's values were bounded below 2^32)
     return it;
 }
 
-__global__ void __launch_bounds__(256) rseg_len_kernel(Seg sg, Pairs a) {
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g > a.total + 1u + a.tries) return;
-    uint32_t v = 0;
-    if (g < a.total) {
-        v = item_of(sg, g).len;
-    } else if (g > a.total) {
-        const uint32_t t = g - a.total - 1u;
-        if (t == a.tries) {
-            a.seg_first[t] = a.total;
-        } else {
-            a.seg_first[t] = sg.block_first[t];
-            v = rc::key_bytes_before(sg.block_first[t + 1u] - sg.block_first[t]);
-        }
-    }
-    a.len[g] = v;
-}
-
-// len scanned as in bodies.hip.h: S[g] = the bytes of the values in front of g, S[total + 1 + t] - S[total] = the bytes of the keys of the
-// tries in front of t
-__global__ void __launch_bounds__(256) rseg_pairs_kernel(Seg sg, Pairs a) {
-    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (g > a.total) return;
-    const uint32_t all = a.len[a.total];
-    if (g == a.total) {
-        if (lane == 0u) a.val_off[g] = all, a.key_off[g] = a.len[a.total + 1u + a.tries] - all;
-        return;
-    }
-    const Item it = item_of(sg, g);
-    const uint32_t at = a.len[g], ko = a.len[a.total + 1u + it.trie] - all + rc::key_bytes_before(it.pos);
-    if ((uint64_t)ko + 5u > a.key_cap || (uint64_t)at + it.len > a.val_cap) return;  // (cannot happen: both arrays are sized from the same rules)
-    if (lane == 0u) {
-        a.val_off[g] = at, a.key_off[g] = ko;
-        (void)put_uint(a.keys + ko, it.index);
-    }
-    const uint8_t* const src = sg.receipts + sg.rc_off[it.row];
-    const uint32_t raw = (uint32_t)(sg.rc_off[it.row + 1u] - sg.rc_off[it.row]);
-    uint8_t* const out = a.vals + at;
-    if (!it.built) {
-        wave_copy(out, src, raw, lane);
-        return;
-    }
+PHANT_DEV void Seg::write(uint8_t* out, const Item& it, uint32_t lane) const {
+    const uint8_t* const src = receipts + rc_off[it.row];
+    const uint32_t raw = (uint32_t)(rc_off[it.row + 1u] - rc_off[it.row]);
+    if (!it.built) return wave_copy(out, src, raw, lane);
     // [tx_type, when != 0] ++ list header ++ status and gas as they stand ++ 0xb9 0x01 0x00 ++ bloom ++ the logs as they stand
-    const uint32_t type = sg.tx_type[it.row], head_at = sg.head_at[it.row], logs_at = sg.logs_at[it.row];
-    const uint64_t payload = (uint64_t)(raw - head_at) + rc::BLOOM_FIELD;
-    const uint32_t at_head = (type ? 1u : 0u) + hdr_len(payload), at_bloom = at_head + (logs_at - head_at) + 3u;
+    const uint32_t type = tx_type[it.row], head = head_at[it.row], logs = logs_at[it.row];
+    const uint64_t payload = (uint64_t)(raw - head) + rc::BLOOM_FIELD;
+    const uint32_t at_head = (type ? 1u : 0u) + hdr_len(payload), at_bloom = at_head + (logs - head) + 3u;
     if (lane == 0u) {
         if (type) out[0] = (uint8_t)type;
         (void)put_hdr(out + (type ? 1u : 0u), 0xc0u, payload);
         out[at_bloom - 3u] = 0xb9u, out[at_bloom - 2u] = 0x01u, out[at_bloom - 1u] = 0x00u;
     }
-    wave_copy(out + at_head, src + head_at, logs_at - head_at, lane);
-    const uint32_t w = sg.rows[64ull * it.row + lane];
+    wave_copy(out + at_head, src + head, logs - head, lane);
+    const uint32_t w = rows[64ull * it.row + lane];
     uint8_t* const bl = out + at_bloom + 4u * lane;
     bl[0] = (uint8_t)w, bl[1] = (uint8_t)(w >> 8), bl[2] = (uint8_t)(w >> 16), bl[3] = (uint8_t)(w >> 24);
-    wave_copy(out + at_bloom + 256u, src + logs_at, raw - logs_at, lane);
+    wave_copy(out + at_bloom + 256u, src + logs, raw - logs, lane);
 }
 
 // the values back in index order (receipts.hip.h's rc_gather_kernel per block): nothing is written when they exceed enc_cap
-__global__ void __launch_bounds__(256) rseg_gather_kernel(Seg sg, Pairs a) {
+__global__ void __launch_bounds__(256) rseg_gather_kernel(Seg sg, seg::IndexForest a) {
     const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (i > sg.n || a.val_off[sg.n] > a.enc_cap) return;
+    if (i > sg.n || a.val_off[sg.n] > sg.enc_cap) return;
     if (i == sg.n) {
-        if (lane == 0u && a.enc_off) a.enc_off[i] = a.val_off[i];
+        if (lane == 0u && sg.enc_off) sg.enc_off[i] = a.val_off[i];
         return;
     }
-    const uint32_t b = upper_bound(sg.block_first, sg.n_blocks + 1u, i) - 1u, first = sg.block_first[b], count = sg.block_first[b + 1u] - first;
+    const uint32_t b = seg::block_of(sg.block_first, sg.n_blocks, i), first = sg.block_first[b], count = sg.block_first[b + 1u] - first;
     const uint32_t k = count < 128u ? count : 128u, j = i - first;
     const uint64_t* const vo = a.val_off + first;
     const uint64_t base = vo[0], len0 = vo[k] - vo[k - 1u];  // index 0 sits at position k - 1
     const uint64_t at = j == 0u ? base : j < k ? vo[j - 1u] + len0 : vo[j];
-    const uint32_t p = rc::pos_of_index(j, count);
-    if (a.enc_off && lane == 0u) a.enc_off[i] = at;
-    if (a.enc) wave_copy(a.enc + at, a.vals + vo[p], vo[p + 1u] - vo[p], lane);
+    const uint32_t p = seg::pos_of_index(j, count);
+    if (sg.enc_off && lane == 0u) sg.enc_off[i] = at;
+    if (sg.enc) wave_copy(sg.enc + at, a.vals + vo[p], vo[p + 1u] - vo[p], lane);
 }
 
 __global__ void __launch_bounds__(256) rseg_verdict_kernel(Seg sg, uint32_t have_roots) {
@@ -367,13 +325,8 @@ __global__ void __launch_bounds__(256) rseg_verdict_kernel(Seg sg, uint32_t have
             break;
         }
     uint32_t f = rel ? (uint32_t)PHANT_RBLOCK_RECEIPT : 0u;
-    auto differs = [](const uint8_t* x, const uint8_t* y, uint32_t bytes) {
-        uint32_t d = 0;
-        for (uint32_t k = 0; k < bytes; ++k) d |= (uint32_t)(x[k] ^ y[k]);
-        return d != 0u;
-    };
-    if (sg.exp_root && have_roots && differs(sg.exp_root + 32ull * b, sg.roots + 32ull * b, 32u)) f |= PHANT_RBLOCK_ROOT;
-    if (sg.exp_bloom && differs(sg.exp_bloom + 256ull * b, reinterpret_cast<const uint8_t*>(sg.block_bloom + 64ull * b), 256u)) f |= PHANT_RBLOCK_BLOOM;
+    if (sg.exp_root && have_roots && seg::bytes_differ(sg.exp_root + 32ull * b, sg.roots + 32ull * b, 32u)) f |= PHANT_RBLOCK_ROOT;
+    if (sg.exp_bloom && seg::bytes_differ(sg.exp_bloom + 256ull * b, reinterpret_cast<const uint8_t*>(sg.block_bloom + 64ull * b), 256u)) f |= PHANT_RBLOCK_BLOOM;
     if (sg.exp_gas && sg.exp_gas[b] != gas) f |= PHANT_RBLOCK_GAS_USED;
     if (sg.exp_count && sg.exp_count[b] != count) f |= PHANT_RBLOCK_COUNT;
     sg.first_bad[b] = count - rel;
@@ -384,17 +337,8 @@ __global__ void __launch_bounds__(256) rseg_verdict_kernel(Seg sg, uint32_t have
 
 // what the host form refuses before anything is copied
 inline int32_t check_host(const phant_rcpt_segs_in& in, std::string& err) {
-    const uint32_t nb = in.n_blocks, n = in.n;
-    if (in.block_first[0] != 0u || in.block_first[nb] != n) return err = "block_receipt_segments: block_first does not run from 0 to n", PHANT_E_INVALID_ARG;
-    for (uint32_t b = 0; b < nb; ++b)
-        if (in.block_first[b + 1u] < in.block_first[b]) return err = "block_receipt_segments: block_first goes backwards", PHANT_E_INVALID_ARG;
-    if (!n) return PHANT_OK;
-    if (in.rc_off[0] != 0u) return err = "block_receipt_segments: rc_off does not run from 0", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < n; ++i)
-        if (in.rc_off[i + 1u] < in.rc_off[i]) return err = "block_receipt_segments: rc_off goes backwards", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < n; ++i)
-        if (in.rc_off[i + 1u] - in.rc_off[i] > 0xffffffffull) return err = "block_receipt_segments: a receipt of 4 GiB or more", PHANT_E_UNSUPPORTED;
-    return PHANT_OK;
+    if (const int32_t rc = seg::check_firsts_host("block_receipt_segments", "block_first", "n", in.block_first, in.n_blocks, in.n, err)) return rc;
+    return in.n ? seg::check_offsets_host("block_receipt_segments", "rc_off", "receipt", in.rc_off, in.n, err) : PHANT_OK;
 }
 
 }  // namespace rseg
@@ -423,11 +367,9 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
     if (val_bytes > 0xffffffffull) return err = "block_receipt_segments: more than 4 GiB of receipts or trie values in one call", PHANT_E_UNSUPPORTED;
     const size_t log_bound = want_logs ? (size_t)(bytes / MIN_LOG_BYTES) : 0u, topic_bound = want_logs ? (size_t)(bytes / TOPIC_BYTES) : 0u;
     const size_t log_rows = std::min<size_t>(log_bound, in.log_cap), topic_rows = std::min<size_t>(topic_bound, in.topic_cap);
-    Pairs p;
-    std::memset(&p, 0, sizeof p);
-    p.total = want_vals ? n : 0u, p.tries = want_vals ? nb : 0u;
-    p.key_cap = (uint64_t)rc::key_bytes_before(p.total) + 16u, p.val_cap = val_bytes, p.enc_cap = out.encoded ? out.encoded_cap : ~0ull;
-    const uint32_t scan_n = p.total + 1u + p.tries + 1u, count_n = 2u * n + 2u;
+    seg::IndexForest p{};
+    p.size(want_vals ? n : 0u, want_vals ? nb : 0u, val_bytes);
+    const uint32_t count_n = 2u * n + 2u;
     const bool gather = eth69 && want_enc;
 
     // ---- the arena: the control words and everything to zero in front, the outputs behind them (one span goes back), the internal
@@ -437,12 +379,9 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
     sg.n_blocks = nb, sg.n = n, sg.eth69 = eth69 ? 1u : 0u, sg.log_cap = in.log_cap, sg.topic_cap = in.topic_cap;
     sg.receipts = in.receipts, sg.rc_off = in.rc_off, sg.block_first = in.block_first;
     sg.exp_root = in.receipts_root, sg.exp_bloom = in.logs_bloom, sg.exp_gas = in.gas_used, sg.exp_count = in.tx_count;
-    uint32_t *d_scan = nullptr, *d_scan2 = nullptr;
+    sg.enc_cap = out.encoded ? out.encoded_cap : ~0ull;
+    uint32_t* d_scan = nullptr;
     const void *zero_end = nullptr, *outputs_end = nullptr, *inputs_begin = nullptr, *inputs_end = nullptr;
-    auto input = [&](auto& io, auto*& member, size_t count, bool wanted) {
-        using T = std::remove_cv_t<std::remove_pointer_t<std::remove_reference_t<decltype(member)>>>;
-        if (wanted) member = io.template take<T>(count + (sizeof(T) == 1 ? 16 : 0));
-    };
     auto carve = [&](auto& io) {
         sg.ctl = io.template take<uint32_t>(CTL_WORDS);
         sg.first_bad = io.template take<uint32_t>((size_t)nb);
@@ -467,8 +406,8 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
             if (out.data_len) sg.data_len = io.template take<uint32_t>(log_rows);
         }
         if (gather) {
-            p.enc_off = io.template take<uint64_t>((size_t)n + 1);
-            if (out.encoded) p.enc = io.template take<uint8_t>((size_t)std::min<uint64_t>(val_bytes, out.encoded_cap) + 16);
+            sg.enc_off = io.template take<uint64_t>((size_t)n + 1);
+            if (out.encoded) sg.enc = io.template take<uint8_t>((size_t)std::min<uint64_t>(val_bytes, out.encoded_cap) + 16);
         }
         outputs_end = io.template take<uint8_t>(0);
         sg.dflags = io.template take<uint32_t>((size_t)n);
@@ -478,24 +417,16 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
         if (want_logs) sg.addr_at = io.template take<uint32_t>(log_bound + 1);
         if (!dev) {
             inputs_begin = io.template take<uint8_t>(0);
-            input(io, sg.rc_off, (size_t)n + 1, n != 0u);
-            input(io, sg.receipts, (size_t)bytes, n != 0u);
-            input(io, sg.block_first, (size_t)nb + 1, true);
-            input(io, sg.exp_root, 32 * (size_t)nb, in.receipts_root != nullptr);
-            input(io, sg.exp_bloom, 256 * (size_t)nb, in.logs_bloom != nullptr);
-            input(io, sg.exp_gas, (size_t)nb, in.gas_used != nullptr);
-            input(io, sg.exp_count, (size_t)nb, in.tx_count != nullptr);
+            take_input(io, sg.rc_off, (size_t)n + 1, n != 0u);
+            take_input(io, sg.receipts, (size_t)bytes, n != 0u);
+            take_input(io, sg.block_first, (size_t)nb + 1, true);
+            take_input(io, sg.exp_root, 32 * (size_t)nb, in.receipts_root != nullptr);
+            take_input(io, sg.exp_bloom, 256 * (size_t)nb, in.logs_bloom != nullptr);
+            take_input(io, sg.exp_gas, (size_t)nb, in.gas_used != nullptr);
+            take_input(io, sg.exp_count, (size_t)nb, in.tx_count != nullptr);
             inputs_end = io.template take<uint8_t>(0);
         }
-        if (want_vals) {
-            p.len = io.template take<uint32_t>((size_t)scan_n + 4);
-            d_scan2 = io.template take<uint32_t>(scan_scratch_entries(scan_n));
-            p.seg_first = io.template take<uint32_t>((size_t)p.tries + 1);
-            p.key_off = io.template take<uint32_t>((size_t)p.total + 1);
-            p.val_off = io.template take<uint64_t>((size_t)p.total + 1);
-            p.keys = io.template take<uint8_t>((size_t)p.key_cap);
-            p.vals = io.template take<uint8_t>((size_t)p.val_cap + 16);
-        }
+        if (want_vals) p.carve(io);
     };
     if (const int32_t rc = lay_out_status(lay_out_arena(ws.io, st, carve), "block_receipt_segments", "workspace", err)) return rc;
     CALL_TRY("block_receipt_segments", hipMemsetAsync(sg.ctl, 0, (size_t)(static_cast<const uint8_t*>(zero_end) - reinterpret_cast<uint8_t*>(sg.ctl)), st));
@@ -515,9 +446,9 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
         hipLaunchKernelGGL(rseg_check_kernel, dim3(blocks_of(std::max(n, nb), 256)), dim3(256), 0, st, sg.rc_off, bytes, sg.block_first, n, nb, sg.ctl);
         CALL_TRY("block_receipt_segments", hipGetLastError());
         CALL_TRY("block_receipt_segments", ws.read_words(Workspaces::MAILBOX_RSEG, sg.ctl, CTL_WORDS, st));
-        if (mb[0] & tx::F_INVALID)
+        if (mb[0] & seg::F_INVALID)
             return err = "block_receipt_segments_dev: rc_off or block_first does not run from 0 to its total, or goes backwards", PHANT_E_INVALID_ARG;
-        if (mb[0] & tx::F_TOO_LONG) return err = "block_receipt_segments_dev: a receipt of 4 GiB or more", PHANT_E_UNSUPPORTED;
+        if (mb[0] & seg::F_TOO_LONG) return err = "block_receipt_segments_dev: a receipt of 4 GiB or more", PHANT_E_UNSUPPORTED;
     }
 
     // ---- the receipts: decode, one scan over both counts, the logs' rows, the bloom items, the rows
@@ -535,16 +466,11 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
 
     // ---- the tries of all blocks: lengths, one scan, pairs, one forest pass; the built encodings back in index order
     if (want_vals) {
-        hipLaunchKernelGGL(rseg_len_kernel, dim3(blocks_of(scan_n, 256)), dim3(256), 0, st, sg, p);
-        CALL_TRY("block_receipt_segments", hipGetLastError());
-        CALL_TRY("block_receipt_segments", launch_exclusive_scan_u32(p.len, scan_n, d_scan2, st));
-        hipLaunchKernelGGL(rseg_pairs_kernel, dim3(blocks_of((uint64_t)p.total + 1, 4)), dim3(256), 0, st, sg, p);
+        CALL_TRY("block_receipt_segments", seg::launch_forest(sg, p, st));
         if (gather) hipLaunchKernelGGL(rseg_gather_kernel, dim3(blocks_of((uint64_t)n + 1, 4)), dim3(256), 0, st, sg, p);
         CALL_TRY("block_receipt_segments", hipGetLastError());
-        if (want_root) {
-            const int32_t rc = trie_forest_dev(ws, st, TriePairs{p.keys, p.key_off, p.key_cap, p.vals, p.val_off, p.val_cap, p.total, p.seg_first, p.tries, sg.roots}, err);
-            if (rc) return rc;
-        }
+        if (want_root)
+            if (const int32_t rc = trie_forest_dev(ws, st, p.trie_pairs(sg.roots), err)) return rc;
     }
     hipLaunchKernelGGL(rseg_verdict_kernel, dim3(blocks_of(nb, 256)), dim3(256), 0, st, sg, want_root ? 1u : 0u);
     CALL_TRY("block_receipt_segments", hipGetLastError());
@@ -578,10 +504,10 @@ int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_
         outs.add(out.data_at, sg.data_at, 8 * (size_t)nl);
         outs.add(out.data_len, sg.data_len, 4 * (size_t)nl);
     }
-    if (want_enc && out.encoded_len <= p.enc_cap) {
+    if (want_enc && out.encoded_len <= sg.enc_cap) {
         if (gather) {
-            outs.add(out.encoded, p.enc, (size_t)out.encoded_len);
-            outs.add(out.encoded_off, p.enc_off, 8 * ((size_t)n + 1));
+            outs.add(out.encoded, sg.enc, (size_t)out.encoded_len);
+            outs.add(out.encoded_off, sg.enc_off, 8 * ((size_t)n + 1));
         } else if (dev) {  // the consensus form's encodings are the input
             outs.add(out.encoded, const_cast<uint8_t*>(in.receipts), (size_t)bytes);
             outs.add(out.encoded_off, const_cast<uint64_t*>(in.rc_off), 8 * ((size_t)n + 1));

@@ -17,7 +17,7 @@
 //   rc_gather_kernel     a wave per receipt: its encoding back in index order for the caller who wants the bytes
 //
 // Trie order of n items keyed by rlp(index) (trie_build.hip: append_rlp_index_pairs): indices 1 .. 0x7f, then 0 (key 0x80), then
-// 0x80 onward.  Plain C++ only: tests/emu.py compiles this file for the host.
+// 0x80 onward: seg::pos_of_index / index_of_pos / key_bytes_before of segment_lists.hip.h.  Plain C++ only: tests/emu.py compiles this file for the host.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -29,6 +29,7 @@
 #include "launch.h"
 #include "receipts.h"
 #include "rlp.h"
+#include "segment_lists.hip.h"
 #include "staging.h"
 #include "trie_build.h"
 #include "wave_util.hip.h"
@@ -73,27 +74,6 @@ struct In {  // device pointers in a kernel, host pointers in the host form's ch
     uint32_t n, n_logs, n_topics;
     uint64_t data_bytes;
 };
-
-// ---- trie order <-> index order
-RC_HD uint32_t pos_of_index(uint32_t i, uint32_t n) {
-    const uint32_t k = n < 128u ? n : 128u;
-    if (i == 0u) return k - 1u;
-    return i < k ? i - 1u : i;
-}
-RC_HD uint32_t index_of_pos(uint32_t p, uint32_t n) {
-    const uint32_t k = n < 128u ? n : 128u;
-    if (p == k - 1u) return 0u;
-    return p < k - 1u ? p + 1u : p;
-}
-// bytes of the keys in front of position p of one list (positions below 128 hold the one-byte keys of indices 0 .. 0x7f)
-RC_HD uint32_t key_bytes_before(uint32_t p) {
-    uint64_t b = p;
-    if (p > 0x80u) b += p - 0x80u;
-    if (p > 0x100u) b += p - 0x100u;
-    if (p > 0x10000u) b += p - 0x10000u;
-    if (p > 0x1000000u) b += p - 0x1000000u;
-    return (uint32_t)b;
-}
 
 // ---- lengths, from rlp.h's rules
 constexpr uint32_t BLOOM_FIELD = 3u + 256u;  // 0xb9 0x01 0x00 ++ bloom
@@ -144,7 +124,7 @@ __global__ void __launch_bounds__(256) rc_list_len_kernel(const uint64_t* __rest
                                                           uint32_t* __restrict__ len, uint32_t* __restrict__ ctl) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= n) return;
-    const uint32_t idx = index_of_pos(p, n);
+    const uint32_t idx = seg::index_of_pos(p, n);
     const uint64_t b = off[idx], e = off[idx + 1u];
     uint32_t flags = 0;
     if (p == 0u && ends && (off[0] != 0ull || off[n] != bytes)) flags |= F_INVALID;
@@ -192,7 +172,7 @@ __global__ void __launch_bounds__(256) rc_size_kernel(In in, uint32_t* __restric
                                                       uint32_t* __restrict__ ctl) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= in.n) return;
-    len[pos_of_index(i, in.n)] = size_receipt(in, i, log_rel, logs_payload, ctl);
+    len[seg::pos_of_index(i, in.n)] = size_receipt(in, i, log_rel, logs_payload, ctl);
 }
 
 // meta = seg_first[n_tries + 1] ++ key_base[n_tries] (the keys of list t start at key_base[t]): the trie of value g
@@ -210,8 +190,8 @@ PHANT_DEV void write_key(const uint32_t* __restrict__ meta, uint32_t n_tries, ui
         return;
     }
     const uint32_t t = trie_of(meta, n_tries, g);
-    const uint32_t p = g - meta[t], n = meta[t + 1u] - meta[t], idx = index_of_pos(p, n);
-    const uint32_t ko = meta[n_tries + 1u + t] + key_bytes_before(p);
+    const uint32_t p = g - meta[t], n = meta[t + 1u] - meta[t], idx = seg::index_of_pos(p, n);
+    const uint32_t ko = meta[n_tries + 1u + t] + seg::key_bytes_before(p);
     key_off[g] = ko;
     (void)put_uint(keys + ko, idx);
 }
@@ -247,7 +227,7 @@ __global__ void __launch_bounds__(256) rc_plan_small_kernel(In in, SmallLists li
         uint32_t v = 0;
         if (g < total) {
             const uint32_t t = trie_of(meta, n_tries, g);
-            const uint32_t p = g - meta[t], n = meta[t + 1u] - meta[t], idx = index_of_pos(p, n);
+            const uint32_t p = g - meta[t], n = meta[t + 1u] - meta[t], idx = seg::index_of_pos(p, n);
             if (t == receipts_at) v = size_receipt(in, idx, log_rel, logs_payload, ctl);
             else {
                 const uint64_t* const off = lists.off[t < receipts_at ? t : t - 1u];
@@ -293,7 +273,7 @@ __global__ void __launch_bounds__(256) rc_encode_kernel(In in, const uint32_t* _
         const bool head = u < in.n;
         const uint32_t l = head ? 0u : u - in.n;
         const uint32_t i = head ? u : upper_bound(in.log_first, in.n + 1u, l) - 1u;
-        const uint32_t pos = pos_of_index(i, in.n);
+        const uint32_t pos = seg::pos_of_index(i, in.n);
         if (val_off[pos + 1u] > val_cap) continue;  // (cannot happen: the array is sized from the same rules)
         uint8_t* const out = vals + val_off[pos];
         const uint64_t lp = logs_payload[i];
@@ -352,7 +332,7 @@ __global__ void __launch_bounds__(256) rc_scatter_kernel(const uint8_t* __restri
                                                          const uint64_t* __restrict__ val_off, uint8_t* __restrict__ vals, uint64_t val_cap) {
     const uint32_t idx = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (idx >= n) return;
-    const uint32_t p = pos_of_index(idx, n);
+    const uint32_t p = seg::pos_of_index(idx, n);
     if (val_off[p + 1u] > val_cap || val_off[p + 1u] - val_off[p] != src_off[idx + 1u] - src_off[idx]) return;  // (cannot happen)
     wave_copy(vals + val_off[p], src + src_off[idx], src_off[idx + 1u] - src_off[idx], lane);
 }
@@ -366,7 +346,7 @@ __global__ void __launch_bounds__(256) rc_gather_kernel(const uint8_t* __restric
     const uint64_t base = val_off[0], len0 = val_off[k] - val_off[k - 1u];  // index 0 sits at position k - 1
     // in front of index i in trie order: indices 1 .. i - 1 (i < k), or every index below i (i >= k)
     const uint64_t at = i == 0u ? 0ull : i < k ? val_off[i - 1u] - base + len0 : val_off[i] - base;
-    const uint32_t p = pos_of_index(i, n);
+    const uint32_t p = seg::pos_of_index(i, n);
     if (out_off && lane == 0u) {
         out_off[i] = at;
         if (i == 0u) out_off[n] = val_off[n] - base;
@@ -426,7 +406,7 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
         meta[t] = (uint32_t)count;
         meta[n_tries + 1u + t] = (uint32_t)key_total;
         count += cnt;
-        key_total += key_bytes_before(cnt);
+        key_total += seg::key_bytes_before(cnt);
     }
     if (count >= 0x7fffffffull || key_total > 0xffffffffull) return err = "block_receipts: more than 2^31 - 2 items in one call", PHANT_E_UNSUPPORTED;
     const uint32_t total = (uint32_t)count, base_r = meta[a.receipts_at];

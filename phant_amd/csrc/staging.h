@@ -3,6 +3,7 @@
 // host C++ on top of arena.h.
 //
 //   lay_out_arena an arena sized by, then carved by, one list of take<T>() calls
+//   take_input    one of those takes: a host-form input array, where it is wanted
 //   StagedInputs  the host form's arrays on their way in: ONE copy through the pinned stage, or a copy each
 //   stage_pairs   a forest's sorted pairs in host memory: validated, laid out, rebased and sent in through StagedInputs
 //   CallOutputs   every output named once; deliver() hands them back as the call's form asks
@@ -61,6 +62,12 @@ inline int32_t lay_out_status(const LaidOut& r, const char* call, const char* wh
     if (r.what == LaidOut::UNDERSIZED) return err = std::string(call) + ": arena sized too small (internal)", PHANT_E_DEVICE;
     err = std::string(call) + (r.what == LaidOut::OOM ? ": hipMalloc(" + std::string(what) + "): " : ": hipStreamSynchronize(st): ") + hipGetErrorString(r.e);
     return r.what == LaidOut::OOM ? PHANT_E_OOM : PHANT_E_DEVICE;
+}
+
+// a host-form input's place in the arena, when `wanted`: count elements, and behind bytes the 16 spare ones their readers may touch
+template <class IO, class T>
+void take_input(IO& io, const T*& member, size_t count, bool wanted) {
+    if (wanted) member = io.template take<T>(count + (sizeof(T) == 1 ? 16 : 0));
 }
 
 // ---- in, host form: the inputs lie in [begin, end) of ws.io.  Whether the caller must synchronise after finish() is the caller's

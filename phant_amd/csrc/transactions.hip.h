@@ -44,6 +44,7 @@
 #include "absorb.hip.h"
 #include "launch.h"
 #include "secp256k1.hip.h"
+#include "segment_lists.hip.h"
 #include "staging.h"
 #include "transactions.h"
 #define TX_HD __host__ __device__ inline
@@ -328,8 +329,7 @@ namespace tx {
 using In = phant_txs_in;
 using Out = phant_txs_out;
 
-enum : uint32_t { F_INVALID = 1u, F_TOO_LONG = 2u };
-// the call's control words (32-bit, device memory, zeroed): [0] = F_*, [1] = n - (the least flagged index) or 0, [2] = the authorization
+// the call's control words (32-bit, device memory, zeroed): [0] = seg::F_*, [1] = n - (the least flagged index) or 0, [2] = the authorization
 // tuples of the call, [4 .. 5] = its versioned hashes as one 64-bit counter
 constexpr size_t CTL_WORDS = 8;
 constexpr uint32_t ERROR_BITS = PHANT_TX_ERROR_BITS_EX;  // (a call without types 3 and 4 never sets a bit above PHANT_TX_IS_CREATE)
@@ -383,10 +383,7 @@ struct Rules {
 __global__ void __launch_bounds__(256) tx_check_args_kernel(const uint64_t* __restrict__ tx_off, uint32_t n, uint64_t tx_bytes, uint32_t* __restrict__ ctl) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const uint64_t b = tx_off[i], e = tx_off[i + 1u];
-    uint32_t f = 0;
-    if (e < b || (i == 0u && b != 0u) || (i + 1u == n && e != tx_bytes)) f |= F_INVALID;
-    else if (e - b > 0xffffffffull) f |= F_TOO_LONG;
+    const uint32_t f = seg::off_flags(tx_off, i, n, tx_bytes);
     if (f) atomicOr(ctl, f);
 }
 
@@ -753,12 +750,7 @@ __global__ void __launch_bounds__(64) tx_rules_kernel(uint32_t n, Rules ru, Dev 
 
 // what the host form refuses before anything is copied
 inline int32_t check_host(const In& in, std::string& err) {
-    if (in.tx_off[0] != 0u) return err = "block_transactions: tx_off does not run from 0", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < in.n; ++i)
-        if (in.tx_off[i + 1u] < in.tx_off[i]) return err = "block_transactions: tx_off goes backwards", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < in.n; ++i)
-        if (in.tx_off[i + 1u] - in.tx_off[i] > 0xffffffffull) return err = "block_transactions: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
-    return PHANT_OK;
+    return seg::check_offsets_host("block_transactions", "tx_off", "transaction", in.tx_off, in.n, err);
 }
 
 // A call between its steps, which phant_block_transactions[_ex] (below) and phant_block_bodies (bodies.hip.h) both go through:
@@ -919,8 +911,8 @@ int32_t block_transactions(Workspaces& ws, hipStream_t st, const phant_txs_ex_in
         hipLaunchKernelGGL(tx_check_args_kernel, dim3(grid256), dim3(256), 0, st, c.d_off, n, c.bytes, d.ctl);
         CALL_TRY("block_transactions", hipGetLastError());
         CALL_TRY("block_transactions", ws.read_words(Workspaces::MAILBOX_TXS, d.ctl, CTL_WORDS, st));
-        if (mb[0] & F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
-        if (mb[0] & F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
+        if (mb[0] & seg::F_INVALID) return err = "block_transactions_dev: tx_off does not run from 0 to tx_bytes, or goes backwards", PHANT_E_INVALID_ARG;
+        if (mb[0] & seg::F_TOO_LONG) return err = "block_transactions_dev: a transaction of 4 GiB or more", PHANT_E_UNSUPPORTED;
     }
 
     // ---- decode, hash, (the authorization tuples,) recover, rules
