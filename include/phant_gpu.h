@@ -124,6 +124,13 @@ PHANT_API int32_t phant_keccak256_batch(phant_ctx *ctx, const uint8_t *blob, con
                                         uint32_t n, uint8_t *out);
 PHANT_API int32_t phant_keccak256_batch_dev(phant_ctx *ctx, const uint8_t *d_blob,
                                             const uint64_t *d_off, uint32_t n, uint8_t *d_out);
+/* SHA-256 (FIPS 180-4) under the same contract: n messages, message i = blob[off[i] .. off[i+1]), out = n x 32 bytes; n == 0 is
+ * PHANT_OK; the host form refuses offsets that go backwards (PHANT_E_INVALID_ARG), the device form wants d_out 16-byte aligned.  The
+ * execution layer's second hash function: EIP-7685 commits a block's requests with it (phant_block_requests below computes
+ * requests_hash for a chain segment), and a client that receives `executionRequests` with engine_newPayloadV4 hashes them with this
+ * before it can check blockHash.  A lane per message. */
+PHANT_API int32_t phant_sha256_batch(phant_ctx *ctx, const uint8_t *blob, const uint64_t *off, uint32_t n, uint8_t *out);
+PHANT_API int32_t phant_sha256_batch_dev(phant_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_off, uint32_t n, uint8_t *d_out);
 /* n messages of msg_len bytes each at d_blob + i*stride (BASELINE config 2:
  * msg_len = stride = 136). */
 PHANT_API int32_t phant_keccak256_fixed_dev(phant_ctx *ctx, const uint8_t *d_blob,
@@ -818,6 +825,95 @@ typedef struct phant_receipts_split {
 } phant_receipts_split;
 PHANT_API int32_t phant_receipts_decode_rlp(const uint8_t *blob, const uint64_t *off, uint32_t n, uint32_t flags,
                                             phant_receipts_split *split, uint8_t *status);
+
+/* ------------------------------------------------- execution requests of a chain segment: deposits, requests hash (EIP-7685, EIP-6110)
+ * Since Prague a header's 21st field, requests_hash, commits to the block's execution requests.  phant_header_chain hashes it into the
+ * block hash; this call computes it for every block of a segment and holds it against the header's.  The deposit requests (type 0) are
+ * not in a block body: they are rebuilt from the logs phant_block_receipt_segments leaves decoded.  The requests the EVM's system calls
+ * produce (types 1 and 2 today) come from the caller.  tests/requests_ref.py is the same definition in Python with hashlib.sha256.
+ *
+ * Input.  The log rows exactly as phant_block_receipt_segments answers them: receipts with rc_bytes, block_first (n_blocks + 1, in
+ * receipts), log_first (n + 1), address (n_logs x 20), topic_first (n_logs + 1), topics (n_topics x 32), data_at and data_len (n_logs;
+ * data_at an offset into `receipts`, of any alignment) -- in the device form the device arrays of that call, handed on without a copy.
+ * deposit_contract: the 20 bytes the caller's chain configuration names (the library has no chain table).  The caller's requests, n_req
+ * rows: req_block_first (n_blocks + 1, in rows), req_type (n_req bytes), req_bytes with req_off (n_req + 1); n_req == 0 with NULL arrays
+ * is legal.  active (n_blocks bytes, or NULL for all): a zero byte marks a block before the fork -- it has no deposit rows, a zero
+ * requests_hash and no flags, and neither its logs nor its rows are looked at.  requests_hash: the expected values, n_blocks x 32, or NULL.
+ *
+ * A log is a deposit CANDIDATE when its block is active, its address equals deposit_contract over all 20 bytes, it has at least one
+ * topic and its first topic is 649bbc62d0e31342afea4e5cd82d4049e7e1ee912fc0889aa790803be39038c5 =
+ * keccak256("DepositEvent(bytes,bytes,bytes,bytes,bytes)"); other logs of the contract are ignored (EIP-6110).  A candidate is
+ * WELL-FORMED when data_len == 576, [data_at, data_at + 576) lies inside [0, rc_bytes) -- nothing outside is ever read --, the five
+ * 32-byte big-endian words at 0, 32, 64, 96, 128 of its data are exactly 160, 256, 320, 384, 512 and the words at 160, 256, 320, 384, 512
+ * are exactly 48, 32, 8, 96, 8 (all 32 bytes of each word are compared).  A well-formed candidate's request row is the 192 bytes
+ * data[192:240] ++ data[288:320] ++ data[352:360] ++ data[416:512] ++ data[544:552]: pubkey, withdrawal credentials, amount, signature
+ * and index as they stand.  A candidate that is not well-formed yields no row and sets PHANT_QBLOCK_DEPOSIT_LAYOUT on its block (EIP-6110
+ * makes such a block invalid).
+ * A block's requests: type 0 = the block's rows in log order, present when there is at least one; then the caller's rows of the block
+ * in the order given, a row without data left out.  h_t = sha256(type ++ data) for each present request; requests_hash = sha256(h_0 ++
+ * h_1 ++ ...); a block with nothing: sha256("") = e3b0c442 98fc1c14 9afbf4c8 996fb924 27ae41e4 649b934c a495991b 7852b855.
+ * Within a block the caller's types must be 1 .. 255 and strictly ascending, rows without data included: otherwise PHANT_QBLOCK_ORDER,
+ * and the hash is still the one of the rows as given.
+ *
+ * Output, any pointer may be NULL.  n_deposits and first_bad_block (the least b with block_flags[b] != 0, n_blocks if none) are always
+ * written.  Per deposit, at most deposit_cap rows: deposit_log (the log's index), deposit (192 bytes).  Per block: deposit_first
+ * (n_blocks + 1), requests_hash, block_flags.  When n_deposits > deposit_cap no per-deposit array is touched and the call still
+ * returns PHANT_OK with hashes and flags complete (the rows the hashes read live in the call's arena).
+ *
+ * A bad block is a flag, never an error.  PHANT_E_INVALID_ARG, with nothing written: a wrong struct_size, reserved != 0, a NULL input
+ * with a non-zero count (block_first with n_blocks; log_first with n; address, topic_first, data_at, data_len with n_logs; topics with
+ * n_topics; receipts with rc_bytes; req_block_first, req_type, req_off with n_req; req_bytes with bytes), rows without a block, logs
+ * without a receipt, topics without a log, or block_first, log_first, topic_first, req_block_first or req_off that do not run from 0 to
+ * their totals (n, n_logs, n_topics, n_req; device form: req_total) or go backwards.  n_blocks == 0 is PHANT_OK with both scalars 0.
+ * The host form checks on the host before any copy and does not read req_total (the total is req_off[n_req]).  Device form: every array
+ * is device memory, the uint64_t arrays 8-byte and the uint32_t arrays 4-byte aligned, byte arrays not at all; the structs are host
+ * memory; the firsts and offsets are checked by a kernel whose verdict the host reads before any other kernel indexes with them.  The
+ * call synchronises the ctx stream (the scalars are valid when it returns); the copies of the per-deposit rows are in stream order behind
+ * it.  The launches depend on neither n_blocks nor n_logs; a call takes as long as its longest message: three compressions per deposit,
+ * serial in the one lane that hashes a block's type-0 request. */
+#define PHANT_QBLOCK_DEPOSIT_LAYOUT 1u /* a deposit candidate of the block is not well-formed */
+#define PHANT_QBLOCK_ORDER 2u          /* a caller's row of type 0, or types not strictly ascending */
+#define PHANT_QBLOCK_HASH 4u           /* in->requests_hash given and != the computed hash */
+typedef struct phant_requests_in {
+    uint32_t struct_size; /* = sizeof(phant_requests_in) */
+    uint32_t n_blocks;
+    uint32_t n;           /* receipts of all blocks */
+    uint32_t n_logs;
+    uint32_t n_topics;
+    uint32_t n_req;       /* the caller's rows of all blocks */
+    uint32_t deposit_cap; /* rows the per-deposit outputs hold */
+    uint32_t reserved;    /* 0 */
+    const uint8_t *receipts;
+    uint64_t rc_bytes;
+    const uint32_t *block_first;     /* n_blocks + 1 */
+    const uint32_t *log_first;       /* n + 1 */
+    const uint8_t *address;          /* n_logs x 20 */
+    const uint32_t *topic_first;     /* n_logs + 1 */
+    const uint8_t *topics;           /* n_topics x 32 */
+    const uint64_t *data_at;         /* n_logs */
+    const uint32_t *data_len;        /* n_logs */
+    const uint32_t *req_block_first; /* n_blocks + 1 */
+    const uint8_t *req_type;         /* n_req */
+    const uint8_t *req_bytes;
+    const uint64_t *req_off;         /* n_req + 1 */
+    uint64_t req_total;              /* device form: req_off[n_req] as the caller states it */
+    const uint8_t *active;           /* n_blocks, or NULL: every block */
+    const uint8_t *requests_hash;    /* expected, n_blocks x 32, or NULL */
+    uint8_t deposit_contract[20];
+} phant_requests_in;
+typedef struct phant_requests_out {
+    uint32_t struct_size;     /* = sizeof(phant_requests_out) */
+    uint32_t n_deposits;      /* result */
+    uint32_t first_bad_block; /* result */
+    uint32_t reserved;        /* 0 */
+    uint32_t *deposit_log;
+    uint8_t *deposit;
+    uint32_t *deposit_first;
+    uint8_t *requests_hash;
+    uint32_t *block_flags;
+} phant_requests_out;
+PHANT_API int32_t phant_block_requests(phant_ctx *ctx, const phant_requests_in *in, phant_requests_out *out);
+PHANT_API int32_t phant_block_requests_dev(phant_ctx *ctx, const phant_requests_in *in, phant_requests_out *out);
 
 /* ------------------------------------------------- a block's transactions against the pre-state: nonces, EOA and witness rows
  * phant_block_txs_prestate joins the rows phant_block_transactions[_ex] answers (keyed by transaction) with the rows

@@ -65,6 +65,8 @@ SYMBOLS = {
     "phant_keccak256_with_prefix": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp]),
     "phant_keccak256_batch": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "phant_keccak256_batch_dev": (_i32, [_vp, _vp, _vp, _u32, _vp]),
+    "phant_sha256_batch": (_i32, [_vp, _vp, _vp, _u32, _vp]),
+    "phant_sha256_batch_dev": (_i32, [_vp, _vp, _vp, _u32, _vp]),
     "phant_keccak256_fixed_dev": (_i32, [_vp, _vp, _u32, _u64, _u32, _vp]),
     "phant_logs_bloom": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "phant_logs_bloom_dev": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
@@ -88,6 +90,8 @@ SYMBOLS = {
     "phant_block_receipt_segments": (_i32, [_vp, _vp, _vp]),
     "phant_block_receipt_segments_dev": (_i32, [_vp, _vp, _vp]),
     "phant_receipts_decode_rlp": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "phant_block_requests": (_i32, [_vp, _vp, _vp]),
+    "phant_block_requests_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle": (_i32, [_vp, _vp, _vp]),
@@ -338,6 +342,31 @@ class PhantReceiptsSplit(C.Structure):
     """phant_receipts_split (include/phant_gpu.h)"""
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "reserved", "rc_cap", "n")] + [("rc_bytes_cap", C.c_uint64)] + \
                [(name, C.c_void_p) for name in ("receipts", "rc_off", "block_first")] + [("rc_bytes", C.c_uint64)]
+
+
+QBLOCK_DEPOSIT_LAYOUT, QBLOCK_ORDER, QBLOCK_HASH = 1, 2, 4
+QBLOCK_FLAG_NAMES = ("DepositLayout", "RequestsOrder", "RequestsHash")
+DEPOSIT_EVENT_TOPIC = bytes.fromhex("649bbc62d0e31342afea4e5cd82d4049e7e1ee912fc0889aa790803be39038c5")
+EMPTY_REQUESTS_HASH = bytes.fromhex("e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855")
+# phant_requests_in's arrays in the struct's order (rc_bytes sits behind receipts, req_total behind req_off): (name, numpy dtype)
+REQUESTS_INPUTS = (("receipts", "u1"), ("block_first", "u4"), ("log_first", "u4"), ("address", "u1"), ("topic_first", "u4"), ("topics", "u1"), ("data_at", "u8"),
+                   ("data_len", "u4"), ("req_block_first", "u4"), ("req_type", "u1"), ("req_bytes", "u1"), ("req_off", "u8"), ("active", "u1"), ("requests_hash", "u1"))
+# phant_requests_out's arrays in the struct's order: (name, numpy dtype, elements per row, the count its rows follow, rows beyond that count)
+REQUESTS_OUTPUTS = (("deposit_log", "u4", 1, "n_deposits", 0), ("deposit", "u1", 192, "n_deposits", 0), ("deposit_first", "u4", 1, "n_blocks", 1),
+                    ("requests_hash", "u1", 32, "n_blocks", 0), ("block_flags", "u4", 1, "n_blocks", 0))
+
+
+class PhantRequestsIn(C.Structure):
+    """phant_requests_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_blocks", "n", "n_logs", "n_topics", "n_req", "deposit_cap", "reserved")] + \
+               [("receipts", C.c_void_p), ("rc_bytes", C.c_uint64)] + [(name, C.c_void_p) for name, _ in REQUESTS_INPUTS[1:12]] + \
+               [("req_total", C.c_uint64), ("active", C.c_void_p), ("requests_hash", C.c_void_p), ("deposit_contract", C.c_uint8 * 20)]
+
+
+class PhantRequestsOut(C.Structure):
+    """phant_requests_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_deposits", "first_bad_block", "reserved")] + \
+               [(name, C.c_void_p) for name, _, _, _, _ in REQUESTS_OUTPUTS]
 
 
 ROW_NONE = 0xFFFFFFFF

@@ -149,7 +149,9 @@ struct Workspaces {
     static constexpr size_t MAILBOX_RANGES = MAILBOX_SETTLE + MAILBOX_SETTLE_WORDS, MAILBOX_RANGES_WORDS = 4;
     // ... and block_receipt_segments (receipt_segments.hip.h) the MAILBOX_RSEG_WORDS behind those
     static constexpr size_t MAILBOX_RSEG = MAILBOX_RANGES + MAILBOX_RANGES_WORDS, MAILBOX_RSEG_WORDS = 8;
-    static_assert(MAILBOX_RSEG + MAILBOX_RSEG_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
+    // ... and block_requests (requests.hip.h) the MAILBOX_QREQ_WORDS behind those
+    static constexpr size_t MAILBOX_QREQ = MAILBOX_RSEG + MAILBOX_RSEG_WORDS, MAILBOX_QREQ_WORDS = 4;
+    static_assert(MAILBOX_QREQ + MAILBOX_QREQ_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
     uint32_t* mailbox = nullptr;
     hipError_t ensure_mailbox() {
         if (mailbox) return hipSuccess;

@@ -21,6 +21,7 @@
 #include "staging.h"
 #include "launch.h"
 #include "receipts.h"
+#include "requests_check.h"
 #include "headers.h"
 #include "transactions.h"
 #include "settle.h"
@@ -515,15 +516,26 @@ int32_t phant_keccak_rate(phant_ctx* c, uint32_t waves_per_simd, uint32_t perms,
 
 /* ------------------------------------------------------------------ Keccak */
 
-int32_t phant_keccak256_batch_dev(phant_ctx* c, const uint8_t* d_blob, const uint64_t* d_off,
-                                  uint32_t n, uint8_t* d_out) {
+// the batch forms of both hash functions: message i = blob[off[i] .. off[i+1]), a launcher of keccak_batch.hip
+using BatchLauncher = hipError_t (*)(const uint8_t*, const uint64_t*, uint32_t, uint8_t*, hipStream_t);
+
+static int32_t hash_batch_dev(phant_ctx* c, const char* who, BatchLauncher launch, const uint8_t* d_blob, const uint64_t* d_off, uint32_t n, uint8_t* d_out) {
     if (!c) return PHANT_E_INVALID_ARG;
     if (n == 0) return PHANT_OK;
-    if (!d_off || !d_out || !aligned16(d_out)) return fail(c, PHANT_E_INVALID_ARG, "keccak256_batch_dev: null or unaligned pointer");
+    if (!d_off || !d_out || !aligned16(d_out)) return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + "_dev: null or unaligned pointer").c_str());
     DeviceGuard g(c->device);
     TimedRegion t(c);
-    HIP_TRY(c, phant::launch_keccak256_var(d_blob, d_off, n, d_out, c->stream));
+    HIP_TRY(c, launch(d_blob, d_off, n, d_out, c->stream));
     return PHANT_OK;
+}
+
+int32_t phant_keccak256_batch_dev(phant_ctx* c, const uint8_t* d_blob, const uint64_t* d_off,
+                                  uint32_t n, uint8_t* d_out) {
+    return hash_batch_dev(c, "keccak256_batch", phant::launch_keccak256_var, d_blob, d_off, n, d_out);
+}
+
+int32_t phant_sha256_batch_dev(phant_ctx* c, const uint8_t* d_blob, const uint64_t* d_off, uint32_t n, uint8_t* d_out) {
+    return hash_batch_dev(c, "sha256_batch", phant::launch_sha256_var, d_blob, d_off, n, d_out);
 }
 
 int32_t phant_keccak256_fixed_dev(phant_ctx* c, const uint8_t* d_blob, uint32_t msg_len,
@@ -538,16 +550,16 @@ int32_t phant_keccak256_fixed_dev(phant_ctx* c, const uint8_t* d_blob, uint32_t 
     return PHANT_OK;
 }
 
-int32_t phant_keccak256_batch(phant_ctx* c, const uint8_t* blob, const uint64_t* off, uint32_t n,
-                              uint8_t* out) {
+static int32_t hash_batch(phant_ctx* c, const char* who, BatchLauncher launch, const uint8_t* blob, const uint64_t* off, uint32_t n, uint8_t* out) {
+    auto bad = [&](const char* what) { return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str()); };
     if (!c) return PHANT_E_INVALID_ARG;
     if (n == 0) return PHANT_OK;
-    if (!off || !out) return fail(c, PHANT_E_INVALID_ARG, "keccak256_batch: null pointer");
+    if (!off || !out) return bad("null pointer");
     for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return fail(c, PHANT_E_INVALID_ARG, "keccak256_batch: offsets not monotone");
+        if (off[i + 1] < off[i]) return bad("offsets not monotone");
     const uint64_t lo = off[0], hi = off[n];
     const size_t blob_len = (size_t)(hi - lo);
-    if (blob_len && !blob) return fail(c, PHANT_E_INVALID_ARG, "keccak256_batch: null blob");
+    if (blob_len && !blob) return bad("null blob");
     DeviceGuard g(c->device);
     uint8_t *d_blob = nullptr, *d_out = nullptr;
     uint64_t* d_off = nullptr;
@@ -561,10 +573,19 @@ int32_t phant_keccak256_batch(phant_ctx* c, const uint8_t* blob, const uint64_t*
     for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
     if (blob_len) HIP_TRY(c, hipMemcpyAsync(d_blob, blob + lo, blob_len, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, phant::launch_keccak256_var(d_blob, d_off, n, d_out, c->stream));
+    HIP_TRY(c, launch(d_blob, d_off, n, d_out, c->stream));
     HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PHANT_OK;
+}
+
+int32_t phant_keccak256_batch(phant_ctx* c, const uint8_t* blob, const uint64_t* off, uint32_t n,
+                              uint8_t* out) {
+    return hash_batch(c, "keccak256_batch", phant::launch_keccak256_var, blob, off, n, out);
+}
+
+int32_t phant_sha256_batch(phant_ctx* c, const uint8_t* blob, const uint64_t* off, uint32_t n, uint8_t* out) {
+    return hash_batch(c, "sha256_batch", phant::launch_sha256_var, blob, off, n, out);
 }
 
 int32_t phant_keccak256(phant_ctx* c, const uint8_t* data, uint64_t len, uint8_t out[32]) {
@@ -1136,6 +1157,30 @@ int32_t phant_block_receipt_segments(phant_ctx* c, const phant_rcpt_segs_in* in,
 int32_t phant_block_receipt_segments_dev(phant_ctx* c, const phant_rcpt_segs_in* in, phant_rcpt_segs_out* out) {
     return block_receipt_segments_impl(c, in, out, true);
 }
+
+/* ------------------------------------------------- execution requests of a chain segment (requests.hip.h) */
+
+static int32_t block_requests_impl(phant_ctx* c, const phant_requests_in* in, phant_requests_out* out, bool dev) {
+    const char* const who = dev ? "block_requests_dev" : "block_requests";
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (const char* const what = phant::qreq::check_args(in, out, dev); *what) return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str());
+    if (in->n_blocks == 0) {  // (no block: nothing to index, nothing to write but the scalars)
+        out->n_deposits = 0, out->first_bad_block = 0;
+        return PHANT_OK;
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_requests_out res = *out;
+    const int32_t rc = phant::block_requests(c->ws, c->stream, *in, res, dev, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->n_deposits = res.n_deposits, out->first_bad_block = res.first_bad_block;
+    return PHANT_OK;
+}
+
+int32_t phant_block_requests(phant_ctx* c, const phant_requests_in* in, phant_requests_out* out) { return block_requests_impl(c, in, out, false); }
+
+int32_t phant_block_requests_dev(phant_ctx* c, const phant_requests_in* in, phant_requests_out* out) { return block_requests_impl(c, in, out, true); }
 
 /* ------------------------------------------------- a block's transactions against the pre-state (txstate.hip.h) */
 

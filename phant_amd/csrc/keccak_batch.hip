@@ -9,6 +9,7 @@
 // 1 M-message batch is 4096 workgroups = 16 per CU.
 #include "absorb.hip.h"
 #include "launch.h"
+#include "sha256.hip.h"
 
 namespace phant {
 
@@ -22,6 +23,22 @@ keccak256_var_kernel(const uint8_t* __restrict__ blob, const uint64_t* __restric
     Sponge s;
     keccak256_global(s, blob + b, e >= b ? e - b : 0, blob + off[n]);
     store_digest(s, out + 32ull * i);
+}
+
+// ---- SHA-256 (sha256.hip.h), the same contract: message i = blob[off[i] .. off[i+1]), a lane per message, the eight state words and the
+// 16-word schedule window in VGPRs ----
+__global__ void __launch_bounds__(256)
+sha256_var_kernel(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ off, uint32_t n,
+                  uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = off[i], e = off[i + 1];
+    uint32_t h[8];
+    sha::sha256_stream(false, 0u, blob + b, e >= b ? e - b : 0, blob + off[n], h);
+    // out is 32-byte aligned in every batch API (row i at out + 32 i)
+    uint4* o = reinterpret_cast<uint4*>(out + 32ull * i);
+    o[0] = make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]), __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+    o[1] = make_uint4(__builtin_bswap32(h[4]), __builtin_bswap32(h[5]), __builtin_bswap32(h[6]), __builtin_bswap32(h[7]));
 }
 
 // ---- fixed length: message i = blob[i*stride .. i*stride + msg_len) ----
@@ -79,6 +96,14 @@ hipError_t launch_keccak256_var(const uint8_t* d_blob, const uint64_t* d_off, ui
     if (n == 0) return hipSuccess;
     const uint32_t grid = (n + 255u) / 256u;
     hipLaunchKernelGGL(keccak256_var_kernel, dim3(grid), dim3(256), 0, st, d_blob, d_off, n, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sha256_var(const uint8_t* d_blob, const uint64_t* d_off, uint32_t n,
+                             uint8_t* d_out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = (n + 255u) / 256u;
+    hipLaunchKernelGGL(sha256_var_kernel, dim3(grid), dim3(256), 0, st, d_blob, d_off, n, d_out);
     return hipGetLastError();
 }
 

@@ -10,6 +10,9 @@ hipError_t launch_keccak256_var(const uint8_t* d_blob, const uint64_t* d_off, ui
                                 uint8_t* d_out, hipStream_t st);
 hipError_t launch_keccak256_fixed(const uint8_t* d_blob, uint32_t msg_len, uint64_t stride,
                                   uint32_t n, uint8_t* d_out, hipStream_t st);
+// SHA-256 of the same messages (sha256.hip.h): d_out n x 32 bytes, 16-byte aligned
+hipError_t launch_sha256_var(const uint8_t* d_blob, const uint64_t* d_off, uint32_t n,
+                             uint8_t* d_out, hipStream_t st);
 
 // diagnostics: blocks x 256 lanes run `perms` Keccak-f each on a register-resident state; d_out: blocks x 256 words
 hipError_t launch_keccak_rate(uint32_t* d_out, uint32_t blocks, uint32_t perms, hipStream_t st);

@@ -48,4 +48,8 @@ int32_t block_receipts(Workspaces& ws, hipStream_t st, ReceiptsArgs& a, bool dev
 // every array host memory in the host form and device memory in the device form; the scalars of `out` are written on PHANT_OK.
 int32_t block_receipt_segments(Workspaces& ws, hipStream_t st, const phant_rcpt_segs_in& in, phant_rcpt_segs_out& out, bool device_form, std::string& err);
 
+// The execution requests of a chain segment (requests.hip.h; phant_block_requests[_dev]): the deposits rebuilt from the log rows of
+// block_receipt_segments, every block's requests_hash; in / out as they came, checked by requests_check.h's check_args.
+int32_t block_requests(Workspaces& ws, hipStream_t st, const phant_requests_in& in, phant_requests_out& out, bool device_form, std::string& err);
+
 }  // namespace phant

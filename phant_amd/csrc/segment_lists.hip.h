@@ -16,6 +16,7 @@
 #include "../../include/phant_gpu.h"
 #include "launch.h"
 #include "rlp.h"
+#include "segment_checks.h"
 #include "trie_build.h"
 #include "wave_util.hip.h"
 
@@ -57,21 +58,7 @@ PHANT_DEV uint32_t first_flags(const uint32_t* __restrict__ first, uint32_t i, u
     const uint32_t b = first[i], e = first[i + 1u];
     return e < b || (i == 0u && b != 0u) || (i + 1u == n && e != total) ? (uint32_t)F_INVALID : 0u;
 }
-// Host form: "<call>: <array> ..." in err; the offsets end where their last entry says (`item`: what one of them holds)
-inline int32_t check_offsets_host(const char* call, const char* array, const char* item, const uint64_t* off, uint32_t n, std::string& err) {
-    if (off[0] != 0u) return err = std::string(call) + ": " + array + " does not run from 0", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1u] < off[i]) return err = std::string(call) + ": " + array + " goes backwards", PHANT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1u] - off[i] > 0xffffffffull) return err = std::string(call) + ": a " + item + " of 4 GiB or more", PHANT_E_UNSUPPORTED;
-    return PHANT_OK;
-}
-inline int32_t check_firsts_host(const char* call, const char* array, const char* to, const uint32_t* first, uint32_t n, uint32_t total, std::string& err) {
-    if (first[0] != 0u || first[n] != total) return err = std::string(call) + ": " + array + " does not run from 0 to " + to, PHANT_E_INVALID_ARG;
-    for (uint32_t b = 0; b < n; ++b)
-        if (first[b + 1u] < first[b]) return err = std::string(call) + ": " + array + " goes backwards", PHANT_E_INVALID_ARG;
-    return PHANT_OK;
-}
+// Host form: check_offsets_host and check_firsts_host of segment_checks.h, plain C++ a host-only program can include
 
 // the block of row i < block_first[n_blocks] (an upper bound: empty blocks are skipped)
 PHANT_DEV uint32_t block_of(const uint32_t* __restrict__ block_first, uint32_t n_blocks, uint32_t i) {

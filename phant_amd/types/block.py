@@ -470,12 +470,13 @@ class ReceiptsVerdict:
             self.reason = ["BadRlp" if split_status[b] == SPLIT_BAD_RLP else "BadReceipt"] if split_status[b] else receipts.errors(b)
 
 
-def validate_receipts(headers, raw_receipts, eth69=False, tx_counts=None, ctx: Context | None = None) -> ReceiptsVerdict:
+def validate_receipts(headers, raw_receipts, eth69=False, tx_counts=None, ctx: Context | None = None, logs=False) -> ReceiptsVerdict:
     """The receipts of a chain segment against its headers in one call: `headers` are decoded headers (BlockHeader objects, or the arrays
     of decode_arrays), `raw_receipts` the per-block elements of a peer's Receipts answer, one per header, in the eth/69 form (no blooms
     on the wire) or the earlier one.  phant_receipts_decode_rlp splits them; phant_block_receipt_segments decodes every receipt,
     computes the blooms, (eth/69) rebuilds the consensus encodings and compares each block's receipts root, logs bloom and gas used
-    with its header, and its receipt count with tx_counts[b] where the caller has the transaction counts."""
+    with its header, and its receipt count with tx_counts[b] where the caller has the transaction counts.  logs=True: the result keeps
+    the per-log arrays, which validate_requests reads."""
     from .receipt import receipt_segments, split_receipts
     n = len(raw_receipts)
     if isinstance(headers, dict):
@@ -489,5 +490,39 @@ def validate_receipts(headers, raw_receipts, eth69=False, tx_counts=None, ctx: C
     if tx_counts is not None:
         expect["tx_count"] = tx_counts
     a, status = split_receipts(raw_receipts, eth69)
-    res = receipt_segments(a, form=L.RCPTS_ETH69 if eth69 else L.RCPTS_CONSENSUS, expect=expect, logs=False, ctx=ctx)
+    res = receipt_segments(a, form=L.RCPTS_ETH69 if eth69 else L.RCPTS_CONSENSUS, expect=expect, logs=logs, ctx=ctx)
     return ReceiptsVerdict(np.asarray(res.block_flags, np.uint32).copy(), status.copy(), res)
+
+
+# ---------------------------------------------------------------------------------- execution requests of chain segments
+class RequestsVerdict:
+    """validate_requests' answer: per block `block_flags` (receipt.RequestsFlags), `first_bad` (the least flagged block, n if none),
+    `reason` (the names of that block's flags; [] when every block is good), and the call's result `requests`."""
+
+    def __init__(self, block_flags, requests):
+        self.block_flags, self.requests = block_flags, requests
+        bad = np.flatnonzero(block_flags != 0)
+        self.first_bad = int(bad[0]) if len(bad) else len(block_flags)
+        self.reason = requests.errors(self.first_bad) if len(bad) else []
+
+
+def validate_requests(headers, segs, deposit_contract, other_requests=None, ctx: Context | None = None) -> RequestsVerdict:
+    """The execution requests of a chain segment against its headers in one call (EIP-7685): `headers` are decoded headers (BlockHeader
+    objects, or the arrays of decode_arrays), `segs` the result of receipt_segments over the same blocks with its per-log arrays (what
+    validate_receipts returns as `.receipts` when it is asked for the logs), `other_requests` per block the (type, data) rows the EVM's
+    system calls produced.  A block is active when its header has the 21st field; its requests_hash is the expected value.  The flags
+    stand beside those of validate_receipts: phant_block_requests rebuilds the deposit requests from the logs of `deposit_contract`
+    (EIP-6110), hashes each block's requests with SHA-256 and compares."""
+    from .receipt import block_requests
+    nb = segs.n_blocks
+    if isinstance(headers, dict):
+        nf = np.asarray(headers["n_fields"][:nb])
+        want = np.ascontiguousarray(headers["requests_hash"]).reshape(-1, 32)[:nb]
+    else:
+        headers = list(headers)
+        nf = np.asarray([h.n_fields for h in headers])
+        want = np.frombuffer(b"".join(h.request_hash or bytes(32) for h in headers) or bytes(32), np.uint8).reshape(-1, 32)
+    if len(nf) != nb:
+        raise ValueError("one header per block of receipts")
+    res = block_requests(segs, deposit_contract, other_requests, active=(nf >= 21).tolist(), expect=np.ascontiguousarray(want), ctx=ctx)
+    return RequestsVerdict(np.asarray(res.block_flags, np.uint32).copy(), res)

@@ -264,4 +264,76 @@ def receipt_segments(packed, form=L.RCPTS_CONSENSUS, expect=None, roots=True, lo
     if encoded:
         off, blob = out_arrays.pop("encoded_off"), out_arrays["encoded"]
         out_arrays["encoded"] = [blob[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+    out_arrays["receipts"], out_arrays["block_first"] = a["receipts"][:nbytes], a["block_first"]  # (what block_requests reads the logs' data from)
     return ReceiptSegments(out_arrays, int(out.first_bad_block), nl, nt)
+
+
+# --------------------------------------------------------------------------------- execution requests of chain segments
+class RequestsFlags:
+    """block_flags[b] of block_requests"""
+    DepositLayout = L.QBLOCK_DEPOSIT_LAYOUT
+    RequestsOrder = L.QBLOCK_ORDER
+    RequestsHash = L.QBLOCK_HASH
+    NAMES = L.QBLOCK_FLAG_NAMES
+
+
+class BlockRequests:
+    """What phant_block_requests answers: per deposit `deposit_log` (its log's index) and `deposit` ((n_deposits, 192) uint8: pubkey,
+    credentials, amount, signature, index); per block `deposit_first`, `requests_hash`, `block_flags`; the scalars `n_deposits` and
+    `first_bad_block`."""
+    FLAG_NAMES = L.QBLOCK_FLAG_NAMES
+
+    def __init__(self, arrays, n_deposits, first_bad_block):
+        self.n_deposits, self.first_bad_block = n_deposits, first_bad_block
+        self.__dict__.update(arrays)
+        self.n_blocks = len(self.block_flags)
+
+    def errors(self, b):
+        """the names of block b's flags"""
+        return [name for k, name in enumerate(self.FLAG_NAMES) if int(self.block_flags[b]) >> k & 1]
+
+    def requests(self, b):
+        """block b's deposit request data: its rows back to back (b"" without one)"""
+        return self.deposit[int(self.deposit_first[b]):int(self.deposit_first[b + 1])].tobytes()
+
+
+def block_requests(segs, deposit_contract, other_requests=None, active=None, expect=None, ctx: Context | None = None) -> BlockRequests:
+    """phant_block_requests over the result of receipt_segments (with its per-log arrays): the deposit requests (EIP-6110) rebuilt from
+    the logs of `deposit_contract` (20 bytes) and every block's requests_hash (EIP-7685).  other_requests: per block a list of
+    (type, data) -- the requests the EVM's system calls produced (types 1 and 2 today), ascending by type; active: per block, False before
+    the fork (None: every block); expect: the headers' requests_hash per block ((n_blocks, 32) uint8 or 32-byte strings), or None."""
+    ctx = ctx or default_context()
+    if not hasattr(segs, "data_at"):
+        raise ValueError("block_requests reads the per-log arrays: receipt_segments(..., logs=True)")
+    nb, n, nl, nt = segs.n_blocks, segs.n, segs.n_logs, segs.n_topics
+    if len(bytes(deposit_contract)) != 20:
+        raise ValueError("deposit_contract: 20 bytes")
+    other = [list(b) for b in other_requests] if other_requests is not None else [[] for _ in range(nb)]
+    if len(other) != nb:
+        raise ValueError("other_requests: one list per block")
+    rows = [(int(t), bytes(d)) for b in other for t, d in b]
+    ins = {"receipts": np.ascontiguousarray(segs.receipts, np.uint8), "block_first": np.ascontiguousarray(segs.block_first, np.uint32),
+           "log_first": np.ascontiguousarray(segs.log_first, np.uint32), "address": np.ascontiguousarray(segs.address, np.uint8),
+           "topic_first": np.ascontiguousarray(segs.topic_first, np.uint32), "topics": np.ascontiguousarray(segs.topics, np.uint8),
+           "data_at": np.ascontiguousarray(segs.data_at, np.uint64), "data_len": np.ascontiguousarray(segs.data_len, np.uint32),
+           "req_block_first": np.cumsum([0] + [len(b) for b in other]).astype(np.uint32), "req_type": np.asarray([t for t, _ in rows], np.uint8),
+           "req_bytes": np.frombuffer(b"".join(d for _, d in rows), np.uint8), "req_off": np.cumsum([0] + [len(d) for _, d in rows]).astype(np.uint64),
+           "active": None if active is None else np.asarray([1 if x else 0 for x in active], np.uint8), "requests_hash": None}
+    if ins["active"] is not None and len(ins["active"]) != nb:
+        raise ValueError("active: one value per block")
+    if expect is not None:
+        e = expect if isinstance(expect, np.ndarray) else np.frombuffer(b"".join(bytes(x) for x in expect), np.uint8)
+        ins["requests_hash"] = np.ascontiguousarray(e, np.uint8).reshape(-1, 32)
+        if len(ins["requests_hash"]) < nb:
+            raise ValueError("expect: one hash per block")
+    ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
+    count = {"n_blocks": nb, "n_deposits": nl}
+    outs = {name: np.zeros((count[r] + extra, k) if k > 1 else count[r] + extra, dtype) for name, dtype, k, r, extra in L.REQUESTS_OUTPUTS}
+    arg = L.PhantRequestsIn(C.sizeof(L.PhantRequestsIn), nb, n, nl, nt, len(rows) if nb else 0, nl, 0, ptr(ins["receipts"]), ins["receipts"].size,
+                            *[ins[name].ctypes.data if name in ("block_first", "log_first", "topic_first") else ptr(ins[name]) for name, _ in L.REQUESTS_INPUTS[1:12]],
+                            int(ins["req_off"][-1]), ptr(ins["active"]), ptr(ins["requests_hash"]), (C.c_uint8 * 20)(*bytes(deposit_contract)))
+    out = L.PhantRequestsOut(C.sizeof(L.PhantRequestsOut), 0, 0, 0, *[ptr(outs[name]) for name, _, _, _, _ in L.REQUESTS_OUTPUTS])
+    ctx.check(ctx._lib.phant_block_requests(ctx.handle, C.byref(arg), C.byref(out)))
+    nd = int(out.n_deposits)
+    outs["deposit_log"], outs["deposit"] = outs["deposit_log"][:nd], outs["deposit"][:nd]
+    return BlockRequests(outs, nd, int(out.first_bad_block))
