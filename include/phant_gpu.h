@@ -915,6 +915,89 @@ typedef struct phant_requests_out {
 PHANT_API int32_t phant_block_requests(phant_ctx *ctx, const phant_requests_in *in, phant_requests_out *out);
 PHANT_API int32_t phant_block_requests_dev(phant_ctx *ctx, const phant_requests_in *in, phant_requests_out *out);
 
+/* ------------------------------------------------- log filters over a chain segment: exact matches and bloom screening
+ * Which logs does a filter select -- the question of eth_getLogs and eth_subscribe("logs").  phant_block_log_filters answers it exactly
+ * over the log rows phant_block_receipt_segments leaves decoded, for many filters in one call; phant_log_filters_bloom answers "which
+ * blocks can hold a match" from nothing but 2048-bit blooms (headers' logs_bloom, or receipts'), so that a node that holds only headers
+ * knows which receipts to fetch.  tests/filters_ref.py is the same definition in Python.
+ *
+ * The filters, n_filters of them (phant_log_filters): addr_first (n_filters + 1) indexes addr (n_addr x 20 bytes): filter f's address
+ * set is addr[addr_first[f] .. addr_first[f + 1]).  topic_first (4 n_filters + 1) indexes topic (n_topic x 32 bytes): set (f, p), the
+ * values topic position p may take, is entry 4 f + p, p = 0 .. 3.  block_lo, block_hi (n_filters each): the blocks [lo, hi) of the
+ * segment the filter looks at; either may be NULL: 0 and n_blocks (n_blooms for the bloom call).  An empty set is a wildcard;
+ * duplicates inside a set are legal and mean nothing.
+ * Log l of block b MATCHES filter f when block_lo[f] <= b < block_hi[f], the address set is empty or address[l] equals one of its
+ * entries over all 20 bytes, and for every p with a non-empty set the log has more than p topics and its topic p equals an entry of
+ * set (f, p) over all 32 bytes.  An address never matches a topic entry, a topic at one position never the set of another.
+ *
+ * phant_block_log_filters.  Input: the log rows as phant_block_receipt_segments answers them -- block_first (n_blocks + 1, in
+ * receipts), log_first (n + 1), address (n_logs x 20), topic_first (n_logs + 1), topics (n_topics x 32); in the device form its device
+ * arrays, handed on without a copy; the logs' data is no input.  Output, any pointer may be NULL: n_matches is always written;
+ * filter_first (n_filters + 1) and filter_count (n_filters); match_log, at most match_cap rows: the logs' indices, ordered by filter
+ * and then by log -- each filter's logs in chain order.  When n_matches > match_cap match_log is not touched and the call still returns
+ * PHANT_OK with the counts complete.  A set of at most PHANT_LOGFILTER_LINEAR_MAX (include/phant_gpu_diag.h) entries is compared entry
+ * by entry, a larger one looked up in one keyed open-addressing table built over all such sets of the call; the launches depend on
+ * neither n_filters nor n_logs (but on whether there is such a set).  n_filters x ceil(n_logs / 64) >= 2^31: PHANT_E_UNSUPPORTED.
+ *
+ * phant_log_filters_bloom.  Input: blooms, n_blooms x 256 bytes; block_lo and block_hi index blooms.  Output, either may be NULL: may,
+ * n_filters x ceil(n_blooms / 64) words: bit b % 64 of word f * ceil(n_blooms / 64) + b / 64 is set when bloom b can hold a match of
+ * f; the padding bits are zero; may_count (n_filters): the set bits of each filter.  Bloom b CAN HOLD a match of f when b is in range,
+ * the address set is empty or all three bits of one of its entries are set in the bloom, and the same for every non-empty topic set.
+ * An entry's bits are Ethereum's: the low 11 bits of each of the big-endian 16-bit words at bytes 0, 2 and 4 of its Keccak-256; value v
+ * is bit 7 - (2047 - v) % 8 of byte (2047 - v) / 8.  No false negatives: a block that holds an exact match is set.  The blooms cross
+ * the device's memory once whatever n_filters is.  n_filters x ceil(n_blooms / 64) >= 2^31: PHANT_E_UNSUPPORTED.
+ *
+ * PHANT_E_INVALID_ARG, with nothing written: a wrong struct_size, reserved != 0, a NULL input with a non-zero count, rows without a
+ * block, logs without a receipt, topics without a log, entries without a filter, 2^30 or more filters, firsts (the rows' and the filters') that do not run from 0 to their totals or
+ * go backwards, block_lo[f] > block_hi[f], block_hi[f] > n_blocks (n_blooms).  n_filters == 0 is PHANT_OK: n_matches = 0 and no array
+ * is written; n_logs == 0 and n_blooms == 0 are PHANT_OK with zero counts.  Device form: every array is device memory, the uint64_t
+ * arrays 8-byte and the uint32_t arrays 4-byte aligned, byte arrays not at all; the structs are host memory; firsts and ranges are
+ * checked by a kernel whose verdict the host reads before any other kernel indexes with them.  The calls synchronise the ctx stream;
+ * the copy of match_log is in stream order behind it. */
+typedef struct phant_log_filters {
+    uint32_t struct_size; /* = sizeof(phant_log_filters) */
+    uint32_t n_filters;
+    uint32_t n_addr;
+    uint32_t n_topic;
+    const uint32_t *addr_first;  /* n_filters + 1 */
+    const uint8_t *addr;         /* n_addr x 20 */
+    const uint32_t *topic_first; /* 4 n_filters + 1 */
+    const uint8_t *topic;        /* n_topic x 32 */
+    const uint32_t *block_lo;    /* n_filters, or NULL: 0 */
+    const uint32_t *block_hi;    /* n_filters, or NULL: n_blocks / n_blooms */
+    uint64_t reserved;           /* 0 */
+} phant_log_filters;
+typedef struct phant_logmatch_in {
+    uint32_t struct_size; /* = sizeof(phant_logmatch_in) */
+    uint32_t n_blocks;
+    uint32_t n; /* receipts of all blocks */
+    uint32_t n_logs;
+    uint32_t n_topics;
+    uint32_t match_cap; /* rows match_log holds */
+    uint32_t reserved;  /* 0 */
+    uint32_t reserved2; /* 0 */
+    const uint32_t *block_first; /* n_blocks + 1 */
+    const uint32_t *log_first;   /* n + 1 */
+    const uint8_t *address;      /* n_logs x 20 */
+    const uint32_t *topic_first; /* n_logs + 1 */
+    const uint8_t *topics;       /* n_topics x 32 */
+} phant_logmatch_in;
+typedef struct phant_logmatch_out {
+    uint32_t struct_size; /* = sizeof(phant_logmatch_out) */
+    uint32_t n_matches;   /* result */
+    uint32_t reserved;    /* 0 */
+    uint32_t reserved2;   /* 0 */
+    uint32_t *filter_first; /* n_filters + 1 */
+    uint32_t *match_log;    /* match_cap */
+    uint32_t *filter_count; /* n_filters */
+} phant_logmatch_out;
+PHANT_API int32_t phant_block_log_filters(phant_ctx *ctx, const phant_logmatch_in *in, const phant_log_filters *filters, phant_logmatch_out *out);
+PHANT_API int32_t phant_block_log_filters_dev(phant_ctx *ctx, const phant_logmatch_in *in, const phant_log_filters *filters, phant_logmatch_out *out);
+PHANT_API int32_t phant_log_filters_bloom(phant_ctx *ctx, const uint8_t *blooms, uint32_t n_blooms, const phant_log_filters *filters,
+                                          uint64_t *may, uint32_t *may_count);
+PHANT_API int32_t phant_log_filters_bloom_dev(phant_ctx *ctx, const uint8_t *d_blooms, uint32_t n_blooms, const phant_log_filters *filters,
+                                              uint64_t *d_may, uint32_t *d_may_count);
+
 /* ------------------------------------------------- a block's transactions against the pre-state: nonces, EOA and witness rows
  * phant_block_txs_prestate joins the rows phant_block_transactions[_ex] answers (keyed by transaction) with the rows
  * phant_exec_witness_prestate answers (keyed by witness row), and decides what `processTransaction` checks first

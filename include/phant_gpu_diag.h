@@ -164,11 +164,17 @@ enum {
                                           depend on it */
     PHANT_DIAG_RANGES_NO_LEAF_PASS,    /* phant_mpt_verify_ranges: != 0: no leaf pass -- every leaf is encoded and hashed by the lane that builds
                                           its parent branch, as in the post-state build (the A/B of DESIGN.md section 7p) */
-    PHANT_DIAG_RANGES_ITEMS_PER_RANGE  /* phant_mpt_verify_ranges: >= 0: the room estimated for the items outside the leaves, per range, so
+    PHANT_DIAG_RANGES_ITEMS_PER_RANGE, /* phant_mpt_verify_ranges: >= 0: the room estimated for the items outside the leaves, per range, so
                                           that a test whose ranges' walks leave more than that reaches the run with the counted size
                                           (0: room for the leaves and 64 items); -1: the call's own estimate.  A TEST HOOK
                                           ONLY: the result does not depend on it */
+    PHANT_DIAG_LOGFILTER_SETS          /* phant_block_log_filters: how a filter's set is compared: 0 = sets of up to
+                                          PHANT_LOGFILTER_LINEAR_MAX entries entry by entry, larger ones through the keyed table (the
+                                          default); 1 = every non-empty set through the table; 2 = every set entry by entry.  The
+                                          result does not depend on it */
 };
+/* phant_block_log_filters: the largest set that is compared entry by entry (tools/bench_log_filters.py measures both forms) */
+#define PHANT_LOGFILTER_LINEAR_MAX 16u
 PHANT_API int32_t phant_diag_set(phant_ctx *ctx, uint32_t knob, int64_t value);
 
 #ifdef __cplusplus

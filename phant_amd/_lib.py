@@ -92,6 +92,10 @@ SYMBOLS = {
     "phant_receipts_decode_rlp": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "phant_block_requests": (_i32, [_vp, _vp, _vp]),
     "phant_block_requests_dev": (_i32, [_vp, _vp, _vp]),
+    "phant_block_log_filters": (_i32, [_vp, _vp, _vp, _vp]),
+    "phant_block_log_filters_dev": (_i32, [_vp, _vp, _vp, _vp]),
+    "phant_log_filters_bloom": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "phant_log_filters_bloom_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle": (_i32, [_vp, _vp, _vp]),
@@ -367,6 +371,31 @@ class PhantRequestsOut(C.Structure):
     """phant_requests_out (include/phant_gpu.h)"""
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_deposits", "first_bad_block", "reserved")] + \
                [(name, C.c_void_p) for name, _, _, _, _ in REQUESTS_OUTPUTS]
+
+
+LOGFILTER_LINEAR_MAX = 16  # PHANT_LOGFILTER_LINEAR_MAX (include/phant_gpu_diag.h)
+# phant_log_filters' arrays in the struct's order: (name, numpy dtype)
+LOG_FILTER_ARRAYS = (("addr_first", "u4"), ("addr", "u1"), ("topic_first", "u4"), ("topic", "u1"), ("block_lo", "u4"), ("block_hi", "u4"))
+# phant_logmatch_in's arrays and phant_logmatch_out's in their structs' order
+LOGMATCH_INPUTS = (("block_first", "u4"), ("log_first", "u4"), ("address", "u1"), ("topic_first", "u4"), ("topics", "u1"))
+LOGMATCH_OUTPUTS = ("filter_first", "match_log", "filter_count")
+
+
+class PhantLogFilters(C.Structure):
+    """phant_log_filters (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_filters", "n_addr", "n_topic")] + \
+               [(name, C.c_void_p) for name, _ in LOG_FILTER_ARRAYS] + [("reserved", C.c_uint64)]
+
+
+class PhantLogMatchIn(C.Structure):
+    """phant_logmatch_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_blocks", "n", "n_logs", "n_topics", "match_cap", "reserved", "reserved2")] + \
+               [(name, C.c_void_p) for name, _ in LOGMATCH_INPUTS]
+
+
+class PhantLogMatchOut(C.Structure):
+    """phant_logmatch_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_matches", "reserved", "reserved2")] + [(name, C.c_void_p) for name in LOGMATCH_OUTPUTS]
 
 
 ROW_NONE = 0xFFFFFFFF

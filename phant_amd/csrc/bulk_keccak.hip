@@ -22,6 +22,8 @@
 //                   encodings, per-block verdicts and the blocks' receipts tries as one forest (receipt_segments.hip.h)
 //   requests        the deposit requests of a chain segment rebuilt from its receipts' logs (EIP-6110) and every block's requests_hash
 //                   (EIP-7685), the one user of SHA-256 (requests.hip.h, sha256.hip.h)
+//   log filters     which logs of a chain segment each of many filters selects, exactly over the decoded rows and as a screen over
+//                   2048-bit blooms (filters.hip.h)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
@@ -269,6 +271,7 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 #include "bodies.hip.h"
 #include "receipt_segments.hip.h"
 #include "requests.hip.h"
+#include "filters.hip.h"
 #include "txstate.hip.h"
 #include "settle.hip.h"
 #include "access_lists.hip.h"

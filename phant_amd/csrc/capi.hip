@@ -22,6 +22,7 @@
 #include "launch.h"
 #include "receipts.h"
 #include "requests_check.h"
+#include "filters_check.h"
 #include "headers.h"
 #include "transactions.h"
 #include "settle.h"
@@ -87,6 +88,7 @@ struct phant_ctx {
     uint64_t advance_estimate = 0;    // PHANT_DIAG_ADVANCE_ESTIMATE_BYTES (0: the call's own estimate)
     bool ranges_no_leaf_pass = false;     // PHANT_DIAG_RANGES_NO_LEAF_PASS
     int64_t ranges_items_per_range = -1;  // PHANT_DIAG_RANGES_ITEMS_PER_RANGE (-1: the call's own estimate)
+    uint32_t logfilter_sets = 0;          // PHANT_DIAG_LOGFILTER_SETS
     uint32_t* secp_gtable = nullptr;  // phant_ecrecover_batch: 1 G .. 255 G, computed on the device by the first call that needs it
 };
 
@@ -475,6 +477,7 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_VERIFY_LIST_WGS: c->tune.list_wgs_cap = (uint32_t)(value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : value); return PHANT_OK;
         case PHANT_DIAG_RANGES_NO_LEAF_PASS: c->ranges_no_leaf_pass = value != 0; return PHANT_OK;
         case PHANT_DIAG_RANGES_ITEMS_PER_RANGE: c->ranges_items_per_range = value < 0 ? -1 : value > 1922 ? 1922 : value; return PHANT_OK;
+        case PHANT_DIAG_LOGFILTER_SETS: c->logfilter_sets = value == 1 ? 1u : value == 2 ? 2u : 0u; return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }
@@ -1181,6 +1184,58 @@ static int32_t block_requests_impl(phant_ctx* c, const phant_requests_in* in, ph
 int32_t phant_block_requests(phant_ctx* c, const phant_requests_in* in, phant_requests_out* out) { return block_requests_impl(c, in, out, false); }
 
 int32_t phant_block_requests_dev(phant_ctx* c, const phant_requests_in* in, phant_requests_out* out) { return block_requests_impl(c, in, out, true); }
+
+/* ------------------------------------------------- log filters over a chain segment (filters.hip.h) */
+
+static int32_t block_log_filters_impl(phant_ctx* c, const phant_logmatch_in* in, const phant_log_filters* filters, phant_logmatch_out* out, bool dev) {
+    const char* const who = dev ? "block_log_filters_dev" : "block_log_filters";
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (const char* const what = phant::lf::check_match_args(in, filters, out, dev); *what) return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str());
+    if (filters->n_filters == 0) {  // (no filter: nothing to index, nothing to write but the scalar)
+        out->n_matches = 0;
+        return PHANT_OK;
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_logmatch_out res = *out;
+    // every non-empty set through the table: none is small; every set entry by entry: none is large
+    const uint32_t linear_max = c->logfilter_sets == 1u ? 0u : c->logfilter_sets == 2u ? 0xffffffffu : PHANT_LOGFILTER_LINEAR_MAX;
+    const int32_t rc = phant::block_log_filters(c->ws, c->stream, *in, *filters, res, dev, c->ns_salt, linear_max, err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->n_matches = res.n_matches;
+    return PHANT_OK;
+}
+
+int32_t phant_block_log_filters(phant_ctx* c, const phant_logmatch_in* in, const phant_log_filters* filters, phant_logmatch_out* out) {
+    return block_log_filters_impl(c, in, filters, out, false);
+}
+
+int32_t phant_block_log_filters_dev(phant_ctx* c, const phant_logmatch_in* in, const phant_log_filters* filters, phant_logmatch_out* out) {
+    return block_log_filters_impl(c, in, filters, out, true);
+}
+
+static int32_t log_filters_bloom_impl(phant_ctx* c, const uint8_t* blooms, uint32_t n_blooms, const phant_log_filters* filters, uint64_t* may, uint32_t* may_count, bool dev) {
+    const char* const who = dev ? "log_filters_bloom_dev" : "log_filters_bloom";
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (const char* const what = phant::lf::check_bloom_args(blooms, n_blooms, filters, may, may_count, dev); *what)
+        return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str());
+    if (filters->n_filters == 0) return PHANT_OK;  // (no filter: no word, no count)
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    const int32_t rc = phant::log_filters_bloom(c->ws, c->stream, blooms, n_blooms, *filters, may, may_count, dev, err);
+    if (rc) return fail(c, rc, err.c_str());
+    return PHANT_OK;
+}
+
+int32_t phant_log_filters_bloom(phant_ctx* c, const uint8_t* blooms, uint32_t n_blooms, const phant_log_filters* filters, uint64_t* may, uint32_t* may_count) {
+    return log_filters_bloom_impl(c, blooms, n_blooms, filters, may, may_count, false);
+}
+
+int32_t phant_log_filters_bloom_dev(phant_ctx* c, const uint8_t* d_blooms, uint32_t n_blooms, const phant_log_filters* filters, uint64_t* d_may, uint32_t* d_may_count) {
+    return log_filters_bloom_impl(c, d_blooms, n_blooms, filters, d_may, d_may_count, true);
+}
 
 /* ------------------------------------------------- a block's transactions against the pre-state (txstate.hip.h) */
 

@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
+#include "../../include/phant_gpu.h"
+
 namespace phant {
 
 hipError_t launch_keccak256_var(const uint8_t* d_blob, const uint64_t* d_off, uint32_t n,
@@ -13,6 +17,15 @@ hipError_t launch_keccak256_fixed(const uint8_t* d_blob, uint32_t msg_len, uint6
 // SHA-256 of the same messages (sha256.hip.h): d_out n x 32 bytes, 16-byte aligned
 hipError_t launch_sha256_var(const uint8_t* d_blob, const uint64_t* d_off, uint32_t n,
                              uint8_t* d_out, hipStream_t st);
+
+// log filters over a chain segment (filters.hip.h; phant_block_log_filters[_dev], phant_log_filters_bloom[_dev]): the structs as they came,
+// checked by filters_check.h's check_match_args / check_bloom_args, n_filters != 0; salt: the ctx's key of the keyed table; linear_max: the
+// largest set compared entry by entry.  PHANT_OK, or the code with the reason in err
+struct Workspaces;
+int32_t block_log_filters(Workspaces& ws, hipStream_t st, const phant_logmatch_in& in, const phant_log_filters& filters, phant_logmatch_out& out, bool device_form,
+                          const uint32_t salt[2], uint32_t linear_max, std::string& err);
+int32_t log_filters_bloom(Workspaces& ws, hipStream_t st, const uint8_t* blooms, uint32_t n_blooms, const phant_log_filters& filters, uint64_t* may,
+                          uint32_t* may_count, bool device_form, std::string& err);
 
 // diagnostics: blocks x 256 lanes run `perms` Keccak-f each on a register-resident state; d_out: blocks x 256 words
 hipError_t launch_keccak_rate(uint32_t* d_out, uint32_t blocks, uint32_t perms, hipStream_t st);

@@ -526,3 +526,18 @@ def validate_requests(headers, segs, deposit_contract, other_requests=None, ctx:
         raise ValueError("one header per block of receipts")
     res = block_requests(segs, deposit_contract, other_requests, active=(nf >= 21).tolist(), expect=np.ascontiguousarray(want), ctx=ctx)
     return RequestsVerdict(np.asarray(res.block_flags, np.uint32).copy(), res)
+
+
+# ---------------------------------------------------------------------------------- log filters over the headers of a segment
+def candidate_blocks(headers, filters, ctx: Context | None = None):
+    """Which blocks of a chain segment can hold a log that a filter selects, from the headers alone (phant_log_filters_bloom over their
+    logs_bloom): `headers` are decoded headers (BlockHeader objects, or the arrays of decode_arrays), `filters` receipt.LogFilter objects
+    whose from_block / to_block index the headers.  -> per filter the ascending indices of its candidate blocks -- the blocks whose
+    receipts are worth fetching; a block that holds a match is always among them."""
+    from .receipt import bloom_candidates
+    if isinstance(headers, dict):
+        blooms = np.ascontiguousarray(headers["logs_bloom"], np.uint8).reshape(-1, 256)
+    else:
+        blooms = np.frombuffer(b"".join(bytes(h.logs_bloom) for h in headers), np.uint8).reshape(-1, 256)
+    may, _ = bloom_candidates(blooms, filters, ctx=ctx)
+    return [np.flatnonzero(row) for row in may]

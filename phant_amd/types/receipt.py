@@ -337,3 +337,130 @@ def block_requests(segs, deposit_contract, other_requests=None, active=None, exp
     nd = int(out.n_deposits)
     outs["deposit_log"], outs["deposit"] = outs["deposit_log"][:nd], outs["deposit"][:nd]
     return BlockRequests(outs, nd, int(out.first_bad_block))
+
+
+# ------------------------------------------------------------------------------------------ log filters over chain segments
+@dataclass
+class LogFilter:
+    """One eth_getLogs filter: `addresses` (20-byte strings; none: any address), `topics` (up to four lists of 32-byte strings, list p
+    the values topic p may take; an empty list or None: anything, or no topic at all), the blocks [from_block, to_block) of the segment
+    (None: from its first / to its last)."""
+    addresses: list = field(default_factory=list)
+    topics: list = field(default_factory=list)
+    from_block: int | None = None
+    to_block: int | None = None
+
+
+class _PackedFilters:
+    """phant_log_filters over numpy arrays (or their copies on the device)"""
+
+    def __init__(self, filters, n_range, device=None):
+        filters = list(filters)
+        sets = [[bytes(a) for a in f.addresses] for f in filters]
+        tsets = [([[bytes(t) for t in (ts or ())] for ts in f.topics] + [[], [], [], []])[:4] for f in filters]
+        if any(len(a) != 20 for s in sets for a in s) or any(len(t) != 32 for f in tsets for s in f for t in s) or any(len(list(f.topics)) > 4 for f in filters):
+            raise ValueError("a filter's addresses are 20 bytes, its topics 32 bytes in at most four positions")
+        addr, topic = [a for s in sets for a in s], [t for f in tsets for s in f for t in s]
+        a = {"addr_first": np.cumsum([0] + [len(s) for s in sets]).astype(np.uint32), "addr": np.frombuffer(b"".join(addr), np.uint8),
+             "topic_first": np.cumsum([0] + [len(s) for f in tsets for s in f]).astype(np.uint32), "topic": np.frombuffer(b"".join(topic), np.uint8),
+             "block_lo": np.asarray([f.from_block or 0 for f in filters], np.uint32),
+             "block_hi": np.asarray([n_range if f.to_block is None else f.to_block for f in filters], np.uint32)}
+        if device is not None:
+            import torch
+            a = {k: torch.from_numpy(np.ascontiguousarray(v).copy()).to(device) for k, v in a.items()}
+            ptr = lambda x: x.data_ptr() if x.numel() else None  # noqa: E731
+        else:
+            ptr = lambda x: x.ctypes.data if x.size else None  # noqa: E731
+        self.keep, self.n = a, len(filters)
+        self.struct = L.PhantLogFilters(C.sizeof(L.PhantLogFilters), len(filters), len(addr), len(topic), *[ptr(a[name]) for name, _ in L.LOG_FILTER_ARRAYS], 0)
+
+
+class LogMatches:
+    """filter_logs' answer: `match_log` (the indices of the selected logs, ordered by filter and then by log), `filter_first`
+    (n_filters + 1) and `filter_count`; logs(f) = the logs filter f selects, in chain order."""
+
+    def __init__(self, filter_first, match_log, filter_count):
+        self.filter_first, self.match_log, self.filter_count = filter_first, match_log, filter_count
+        self.n_matches = len(match_log)
+
+    def logs(self, f):
+        return self.match_log[int(self.filter_first[f]):int(self.filter_first[f + 1])]
+
+
+def filter_logs(segment_rows, filters, ctx: Context | None = None) -> LogMatches:
+    """phant_block_log_filters: which logs of a chain segment each filter selects.  segment_rows: what receipt_segments(..., logs=True)
+    returns (or a dict of its block_first, log_first, address, topic_first, topics), as host arrays or as torch tensors on the device --
+    then the device form runs on them without a copy, and the answer's arrays are device tensors."""
+    ctx = ctx or default_context()
+    get = (lambda k: segment_rows[k]) if isinstance(segment_rows, dict) else (lambda k: getattr(segment_rows, k))
+    try:
+        rows = {name: get(name) for name, _ in L.LOGMATCH_INPUTS}
+    except (KeyError, AttributeError):
+        raise ValueError("filter_logs reads the per-log arrays: receipt_segments(..., logs=True)") from None
+    dev = hasattr(rows["address"], "data_ptr")
+    filters = list(filters)
+    if dev:
+        import torch
+        device = rows["address"].device
+        rows = {name: rows[name].contiguous().view(torch.uint8).view({"u4": torch.int32, "u1": torch.uint8}[dt]) for name, dt in L.LOGMATCH_INPUTS}
+        count = lambda x: x.numel()  # noqa: E731
+        ptr = lambda x: x.data_ptr() if x.numel() else None  # noqa: E731
+        fn = ctx._lib.phant_block_log_filters_dev
+    else:
+        device = None
+        rows = {name: np.ascontiguousarray(rows[name], dt) for name, dt in L.LOGMATCH_INPUTS}
+        count = lambda x: x.size  # noqa: E731
+        ptr = lambda x: x.ctypes.data if x.size else None  # noqa: E731
+        fn = ctx._lib.phant_block_log_filters
+    nb, n, nl, nt = count(rows["block_first"]) - 1, count(rows["log_first"]) - 1, count(rows["address"]) // 20, count(rows["topics"]) // 32
+    nf = len(filters)
+    packed = _PackedFilters(filters, nb, device)
+    cap = min(nf * nl, max(1024, 4 * nl))
+    while True:
+        if dev:
+            outs = {"filter_first": torch.zeros(nf + 1, dtype=torch.int32, device=device), "match_log": torch.zeros(cap, dtype=torch.int32, device=device),
+                    "filter_count": torch.zeros(nf, dtype=torch.int32, device=device)}
+        else:
+            outs = {"filter_first": np.zeros(nf + 1, np.uint32), "match_log": np.zeros(cap, np.uint32), "filter_count": np.zeros(nf, np.uint32)}
+        arg = L.PhantLogMatchIn(C.sizeof(L.PhantLogMatchIn), nb, n, nl, nt, cap, 0, 0,
+                                *[rows[name].data_ptr() if dev else rows[name].ctypes.data for name in ("block_first", "log_first")], ptr(rows["address"]),
+                                rows["topic_first"].data_ptr() if dev else rows["topic_first"].ctypes.data, ptr(rows["topics"]))
+        if nb == 0:
+            arg.block_first = arg.log_first = arg.topic_first = None
+        out = L.PhantLogMatchOut(C.sizeof(L.PhantLogMatchOut), 0, 0, 0, *[ptr(outs[name]) for name in L.LOGMATCH_OUTPUTS])
+        ctx.check(fn(ctx.handle, C.byref(arg), C.byref(packed.struct), C.byref(out)))
+        nm = int(out.n_matches)
+        if nm <= cap:
+            break
+        cap = nm  # (the counts were complete: once more with room for every row)
+    if dev:
+        torch.cuda.synchronize(device)
+    return LogMatches(outs["filter_first"], outs["match_log"][:nm], outs["filter_count"])
+
+
+def bloom_candidates(blooms, filters, ctx: Context | None = None):
+    """phant_log_filters_bloom: which of the 2048-bit blooms (an (n, 256) uint8 array, 256-byte strings, or a uint8 tensor on the device)
+    can hold a match of each filter; a filter's from_block / to_block index the blooms.  -> (may, may_count): may[f, b] a boolean
+    (host form) or the packed words (n_filters, ceil(n / 64)) as an int64 tensor (device form); no false negatives."""
+    ctx = ctx or default_context()
+    filters = list(filters)
+    nf = len(filters)
+    if hasattr(blooms, "data_ptr"):
+        import torch
+        blooms = blooms.contiguous().view(torch.uint8).reshape(-1, 256)
+        n, words = blooms.shape[0], (blooms.shape[0] + 63) // 64
+        packed = _PackedFilters(filters, n, blooms.device)
+        may = torch.zeros((nf, words), dtype=torch.int64, device=blooms.device)
+        may_count = torch.zeros(nf, dtype=torch.int32, device=blooms.device)
+        ctx.check(ctx._lib.phant_log_filters_bloom_dev(ctx.handle, blooms.data_ptr() if n else None, n, C.byref(packed.struct), may.data_ptr() if may.numel() else None,
+                                                       may_count.data_ptr() if nf else None))
+        return may, may_count
+    b = blooms if isinstance(blooms, np.ndarray) else np.frombuffer(b"".join(bytes(x) for x in blooms), np.uint8)
+    b = np.ascontiguousarray(b, np.uint8).reshape(-1, 256)
+    n, words = len(b), (len(b) + 63) // 64
+    packed = _PackedFilters(filters, n)
+    may, may_count = np.zeros((nf, words), np.uint64), np.zeros(nf, np.uint32)
+    ctx.check(ctx._lib.phant_log_filters_bloom(ctx.handle, b.ctypes.data if n else None, n, C.byref(packed.struct), may.ctypes.data if may.size else None,
+                                               may_count.ctypes.data if nf else None))
+    bits = np.unpackbits(may.view(np.uint8).reshape(nf, -1), axis=1, bitorder="little")[:, :n].astype(bool) if may.size else np.zeros((nf, n), bool)
+    return bits, may_count
