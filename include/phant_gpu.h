@@ -998,6 +998,72 @@ PHANT_API int32_t phant_log_filters_bloom(phant_ctx *ctx, const uint8_t *blooms,
 PHANT_API int32_t phant_log_filters_bloom_dev(phant_ctx *ctx, const uint8_t *d_blooms, uint32_t n_blooms, const phant_log_filters *filters,
                                               uint64_t *d_may, uint32_t *d_may_count);
 
+/* ------------------------------------------------- fee history over a chain segment: reward percentiles
+ * The priority fee at chosen percentiles of each block's gas used -- the `reward` of eth_feeHistory.  phant_block_fee_history joins
+ * the rows two segment calls leave behind: every transaction's effective_gas_price (phant_block_bodies) and every receipt's gas_used
+ * (phant_block_receipt_segments).  tests/feehist_ref.py is the same definition in Python integers.
+ *
+ * A segment has n_blocks blocks; block_first (n_blocks + 1) gives block b the rows [block_first[b], block_first[b + 1]) of all n row
+ * arrays.  Transaction i of a block is also receipt i of that block: the caller asserts this (phant_amd/types/block.py's
+ * validate_receipts checks the counts).  Input: price (n x 32, big-endian: effective_gas_price as phant_block_bodies answers it;
+ * before London, the gas price), base_fee (n_blocks x 32, big-endian, laid out like phant_bodies_in.base_fee; NULL means zero),
+ * gas_used (n, as phant_block_receipt_segments answers it), percentile (n_percentiles, HOST memory in both forms): basis points, each
+ * at most 10000, in any order, repeats allowed.
+ *
+ *   tip[i] = price[i] - base_fee[block of i]; where price[i] < base_fee: tip[i] = 0 and the block gets PHANT_FEE_BELOW_BASE -- a flag,
+ *     never an error.
+ *   Within a block the rows are ordered by (tip, row index) ascending -- a stable sort; order[block_first[b] + r] is the GLOBAL row
+ *     with rank r in block b.
+ *   S_r = the sum of gas_used over the ranks 0 .. r of the block, exact (96 bits, as phant_block_settle's cum); G = S_last is the
+ *     block's gas.
+ *   reward[b][k] = the tip of the row at the least rank r with S_r >= threshold, threshold = floor(G x percentile[k] / 10000).  Such
+ *     an r always exists.  This is geth's loop: start at rank 0 and advance while the sum is below the threshold and a row is left.
+ *     THE THRESHOLD IS TAKEN IN INTEGERS, not in float64 as geth takes it (uint64(float64(gasUsed) * p / 100)): no answer depends on
+ *     how a product rounds.  No division is made: S_r >= floor(G p / 10000) holds exactly when 10000 (S_r + 1) > G p, in 128 bits.
+ *     An empty block has all rewards zero and flags 0.
+ *
+ * Output, every pointer may be NULL: reward (n_blocks x n_percentiles x 32, big-endian), tip (n x 32, big-endian), order (n),
+ * block_gas_used (n_blocks: G clamped to 2^64 - 1), block_flags (n_blocks); first_bad_block is always written: the least flagged block,
+ * or n_blocks if none.
+ *
+ * PHANT_E_INVALID_ARG, with nothing written and before anything is indexed with the offending value: a wrong struct_size, reserved != 0,
+ * a NULL input with a non-zero count, rows without a block, a percentile above 10000, block_first that does not run from 0 to n or goes
+ * backwards.  PHANT_E_UNSUPPORTED: a block of more than PHANT_FEEHIST_BLOCK_MAX rows (the ranking is quadratic in a block's rows; the cap
+ * keeps a hostile block_first from buying seconds of device time -- at 21000 gas a row it is 1.4 G gas, beyond any chain);
+ * n_blocks x n_percentiles >= 2^31.  PHANT_OK: n_blocks == 0 (first_bad_block = 0); n_percentiles == 0 (tip, order and the per-block
+ * outputs are still written); n == 0.
+ *
+ * Device form: every array but percentile is device memory, handed on without a copy; the uint64_t arrays are 8-byte, the uint32_t
+ * arrays 4-byte aligned, byte arrays not at all; both structs are host memory.  block_first and the cap are checked by a kernel whose
+ * verdict the host reads before any other kernel indexes with them.  The call synchronises the ctx stream.  The launches depend on
+ * neither n_blocks, n nor n_percentiles. */
+#define PHANT_FEE_BELOW_BASE 0x1u      /* block_flags: a row's price is below the block's base fee (its tip counts as 0) */
+#define PHANT_FEEHIST_BLOCK_MAX 65536u /* the most rows a block may have */
+typedef struct phant_fee_history_in {
+    uint32_t struct_size; /* = sizeof(phant_fee_history_in) */
+    uint32_t n_blocks;
+    uint32_t n; /* rows (transactions = receipts) of all blocks */
+    uint32_t n_percentiles;
+    const uint32_t *block_first; /* n_blocks + 1 */
+    const uint8_t *price;        /* n x 32, big-endian */
+    const uint8_t *base_fee;     /* n_blocks x 32, big-endian, or NULL: zero */
+    const uint64_t *gas_used;    /* n */
+    const uint32_t *percentile;  /* n_percentiles basis points, HOST memory in both forms */
+    uint64_t reserved;           /* 0 */
+} phant_fee_history_in;
+typedef struct phant_fee_history_out {
+    uint32_t struct_size;     /* = sizeof(phant_fee_history_out) */
+    uint32_t first_bad_block; /* result */
+    uint8_t *reward;          /* n_blocks x n_percentiles x 32, big-endian */
+    uint8_t *tip;             /* n x 32, big-endian */
+    uint32_t *order;          /* n */
+    uint64_t *block_gas_used; /* n_blocks */
+    uint32_t *block_flags;    /* n_blocks */
+    uint64_t reserved;        /* 0 */
+} phant_fee_history_out;
+PHANT_API int32_t phant_block_fee_history(phant_ctx *ctx, const phant_fee_history_in *in, phant_fee_history_out *out);
+PHANT_API int32_t phant_block_fee_history_dev(phant_ctx *ctx, const phant_fee_history_in *in, phant_fee_history_out *out);
+
 /* ------------------------------------------------- a block's transactions against the pre-state: nonces, EOA and witness rows
  * phant_block_txs_prestate joins the rows phant_block_transactions[_ex] answers (keyed by transaction) with the rows
  * phant_exec_witness_prestate answers (keyed by witness row), and decides what `processTransaction` checks first

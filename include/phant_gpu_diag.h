@@ -168,10 +168,13 @@ enum {
                                           that a test whose ranges' walks leave more than that reaches the run with the counted size
                                           (0: room for the leaves and 64 items); -1: the call's own estimate.  A TEST HOOK
                                           ONLY: the result does not depend on it */
-    PHANT_DIAG_LOGFILTER_SETS          /* phant_block_log_filters: how a filter's set is compared: 0 = sets of up to
+    PHANT_DIAG_LOGFILTER_SETS,         /* phant_block_log_filters: how a filter's set is compared: 0 = sets of up to
                                           PHANT_LOGFILTER_LINEAR_MAX entries entry by entry, larger ones through the keyed table (the
                                           default); 1 = every non-empty set through the table; 2 = every set entry by entry.  The
                                           result does not depend on it */
+    PHANT_DIAG_FEEHIST_BLOCK_MAX       /* phant_block_fee_history: the most rows a block may have: 0 = PHANT_FEEHIST_BLOCK_MAX (the
+                                          product's value); 1 .. PHANT_FEEHIST_BLOCK_MAX - 1 = that many, so that a test reaches the
+                                          boundary with a few hundred rows.  A TEST HOOK ONLY: the cap is never raised */
 };
 /* phant_block_log_filters: the largest set that is compared entry by entry (tools/bench_log_filters.py measures both forms) */
 #define PHANT_LOGFILTER_LINEAR_MAX 16u

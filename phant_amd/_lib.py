@@ -96,6 +96,8 @@ SYMBOLS = {
     "phant_block_log_filters_dev": (_i32, [_vp, _vp, _vp, _vp]),
     "phant_log_filters_bloom": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "phant_log_filters_bloom_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "phant_block_fee_history": (_i32, [_vp, _vp, _vp]),
+    "phant_block_fee_history_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate": (_i32, [_vp, _vp, _vp]),
     "phant_block_txs_prestate_dev": (_i32, [_vp, _vp, _vp]),
     "phant_block_settle": (_i32, [_vp, _vp, _vp]),
@@ -396,6 +398,25 @@ class PhantLogMatchIn(C.Structure):
 class PhantLogMatchOut(C.Structure):
     """phant_logmatch_out (include/phant_gpu.h)"""
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_matches", "reserved", "reserved2")] + [(name, C.c_void_p) for name in LOGMATCH_OUTPUTS]
+
+
+FEE_BELOW_BASE = 1            # PHANT_FEE_BELOW_BASE (block_flags of phant_block_fee_history)
+FEEHIST_BLOCK_MAX = 65536     # PHANT_FEEHIST_BLOCK_MAX
+# phant_fee_history_in's arrays and phant_fee_history_out's in their structs' order: (name, numpy dtype, elements per row)
+FEEHIST_INPUTS = (("block_first", "u4", 1), ("price", "u1", 32), ("base_fee", "u1", 32), ("gas_used", "u8", 1), ("percentile", "u4", 1))
+FEEHIST_OUTPUTS = (("reward", "u1", 32), ("tip", "u1", 32), ("order", "u4", 1), ("block_gas_used", "u8", 1), ("block_flags", "u4", 1))
+
+
+class PhantFeeHistoryIn(C.Structure):
+    """phant_fee_history_in (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "n_blocks", "n", "n_percentiles")] + \
+               [(name, C.c_void_p) for name, _, _ in FEEHIST_INPUTS] + [("reserved", C.c_uint64)]
+
+
+class PhantFeeHistoryOut(C.Structure):
+    """phant_fee_history_out (include/phant_gpu.h)"""
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "first_bad_block")] + [(name, C.c_void_p) for name, _, _ in FEEHIST_OUTPUTS] + \
+               [("reserved", C.c_uint64)]
 
 
 ROW_NONE = 0xFFFFFFFF

@@ -89,7 +89,8 @@ class Context:
         "trie_no_side", "trie_side_min_keys", "trie_ahead_max_keys", "trie_side_lds", "trie_fallback_grid", "trie_slot_blocks",
         "trie_no_coop", "trie_coop_max", "trie_no_wave", "trie_join_in_stream", "sort_no_fallback", "sort_prefix_bits",
         "sort_repair_bits", "nodeset_wave_max", "trie_small_max_keys", "code_hash_form", "poststate_raw_slot_keys",
-        "advance_estimate_bytes", "verify_list_wgs", "ranges_no_leaf_pass", "ranges_items_per_range", "logfilter_sets"))}
+        "advance_estimate_bytes", "verify_list_wgs", "ranges_no_leaf_pass", "ranges_items_per_range", "logfilter_sets",
+        "feehist_block_max"))}
 
     def diag_set(self, knob: str, value: int):
         """phant_diag_set: a per-ctx switch of a measured alternative or a test hook (the library reads no environment)."""

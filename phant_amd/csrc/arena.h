@@ -153,7 +153,9 @@ struct Workspaces {
     static constexpr size_t MAILBOX_QREQ = MAILBOX_RSEG + MAILBOX_RSEG_WORDS, MAILBOX_QREQ_WORDS = 4;
     // ... and block_log_filters / log_filters_bloom (filters.hip.h) the MAILBOX_LF_WORDS behind those
     static constexpr size_t MAILBOX_LF = MAILBOX_QREQ + MAILBOX_QREQ_WORDS, MAILBOX_LF_WORDS = 4;
-    static_assert(MAILBOX_LF + MAILBOX_LF_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
+    // ... and block_fee_history (fee_history.hip.h) the MAILBOX_FH_WORDS behind those
+    static constexpr size_t MAILBOX_FH = MAILBOX_LF + MAILBOX_LF_WORDS, MAILBOX_FH_WORDS = 4;
+    static_assert(MAILBOX_FH + MAILBOX_FH_WORDS <= MAILBOX_WORDS, "the receipts', the headers' and the transactions' control words fit the pinned mailbox");
     uint32_t* mailbox = nullptr;
     hipError_t ensure_mailbox() {
         if (mailbox) return hipSuccess;

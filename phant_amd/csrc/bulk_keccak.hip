@@ -24,6 +24,8 @@
 //                   (EIP-7685), the one user of SHA-256 (requests.hip.h, sha256.hip.h)
 //   log filters     which logs of a chain segment each of many filters selects, exactly over the decoded rows and as a screen over
 //                   2048-bit blooms (filters.hip.h)
+//   fee history     per block of a chain segment the priority fee at chosen percentiles of its gas used, from the bodies' price rows
+//                   and the receipts' gas rows (fee_history.hip.h)
 // code hashes (src/blockchain/vm.zig:284-298; keccak256("") for an account without code is exactly its
 // `empty_hash`) need no kernel of their own: they are phant_keccak256_batch over the respective byte strings.
 #include "absorb.hip.h"
@@ -272,6 +274,7 @@ hipError_t launch_secp_op(uint32_t op, const uint8_t* d_a, const uint8_t* d_b, u
 #include "receipt_segments.hip.h"
 #include "requests.hip.h"
 #include "filters.hip.h"
+#include "fee_history.hip.h"
 #include "txstate.hip.h"
 #include "settle.hip.h"
 #include "access_lists.hip.h"

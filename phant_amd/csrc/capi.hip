@@ -23,6 +23,7 @@
 #include "receipts.h"
 #include "requests_check.h"
 #include "filters_check.h"
+#include "feehist_check.h"
 #include "headers.h"
 #include "transactions.h"
 #include "settle.h"
@@ -89,6 +90,7 @@ struct phant_ctx {
     bool ranges_no_leaf_pass = false;     // PHANT_DIAG_RANGES_NO_LEAF_PASS
     int64_t ranges_items_per_range = -1;  // PHANT_DIAG_RANGES_ITEMS_PER_RANGE (-1: the call's own estimate)
     uint32_t logfilter_sets = 0;          // PHANT_DIAG_LOGFILTER_SETS
+    int64_t feehist_block_max = 0;        // PHANT_DIAG_FEEHIST_BLOCK_MAX (0: PHANT_FEEHIST_BLOCK_MAX)
     uint32_t* secp_gtable = nullptr;  // phant_ecrecover_batch: 1 G .. 255 G, computed on the device by the first call that needs it
 };
 
@@ -478,6 +480,7 @@ int32_t phant_diag_set(phant_ctx* c, uint32_t knob, int64_t value) {
         case PHANT_DIAG_RANGES_NO_LEAF_PASS: c->ranges_no_leaf_pass = value != 0; return PHANT_OK;
         case PHANT_DIAG_RANGES_ITEMS_PER_RANGE: c->ranges_items_per_range = value < 0 ? -1 : value > 1922 ? 1922 : value; return PHANT_OK;
         case PHANT_DIAG_LOGFILTER_SETS: c->logfilter_sets = value == 1 ? 1u : value == 2 ? 2u : 0u; return PHANT_OK;
+        case PHANT_DIAG_FEEHIST_BLOCK_MAX: c->feehist_block_max = value; return PHANT_OK;
         default: return fail(c, PHANT_E_INVALID_ARG, "diag_set: no such knob");
     }
 }
@@ -1236,6 +1239,31 @@ int32_t phant_log_filters_bloom(phant_ctx* c, const uint8_t* blooms, uint32_t n_
 int32_t phant_log_filters_bloom_dev(phant_ctx* c, const uint8_t* d_blooms, uint32_t n_blooms, const phant_log_filters* filters, uint64_t* d_may, uint32_t* d_may_count) {
     return log_filters_bloom_impl(c, d_blooms, n_blooms, filters, d_may, d_may_count, true);
 }
+
+/* ------------------------------------------------- fee history over a chain segment (fee_history.hip.h) */
+
+static int32_t block_fee_history_impl(phant_ctx* c, const phant_fee_history_in* in, phant_fee_history_out* out, bool dev) {
+    const char* const who = dev ? "block_fee_history_dev" : "block_fee_history";
+    if (!c) return PHANT_E_INVALID_ARG;
+    if (const char* const what = phant::fh::check_args(in, out, dev); *what) return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str());
+    if (const char* const what = phant::fh::check_percentiles(*in); *what) return fail(c, PHANT_E_INVALID_ARG, (std::string(who) + ": " + what).c_str());
+    if (in->n_blocks == 0) {  // (no block: nothing to index, nothing to write but the scalar)
+        out->first_bad_block = 0;
+        return PHANT_OK;
+    }
+    DeviceGuard g(c->device);
+    TimedRegion t(c, dev);
+    std::string err;
+    phant_fee_history_out res = *out;
+    const int32_t rc = phant::block_fee_history(c->ws, c->stream, *in, res, dev, phant::fh::block_max_of(c->feehist_block_max), err);
+    if (rc) return fail(c, rc, err.c_str());
+    out->first_bad_block = res.first_bad_block;
+    return PHANT_OK;
+}
+
+int32_t phant_block_fee_history(phant_ctx* c, const phant_fee_history_in* in, phant_fee_history_out* out) { return block_fee_history_impl(c, in, out, false); }
+
+int32_t phant_block_fee_history_dev(phant_ctx* c, const phant_fee_history_in* in, phant_fee_history_out* out) { return block_fee_history_impl(c, in, out, true); }
 
 /* ------------------------------------------------- a block's transactions against the pre-state (txstate.hip.h) */
 

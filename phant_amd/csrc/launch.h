@@ -27,6 +27,12 @@ int32_t block_log_filters(Workspaces& ws, hipStream_t st, const phant_logmatch_i
 int32_t log_filters_bloom(Workspaces& ws, hipStream_t st, const uint8_t* blooms, uint32_t n_blooms, const phant_log_filters& filters, uint64_t* may,
                           uint32_t* may_count, bool device_form, std::string& err);
 
+// fee history over a chain segment (fee_history.hip.h; phant_block_fee_history[_dev]): the structs as they came, checked by
+// feehist_check.h's check_args and check_percentiles, n_blocks != 0; block_max: the cap on a block's rows.  PHANT_OK, or the code with
+// the reason in err
+int32_t block_fee_history(Workspaces& ws, hipStream_t st, const phant_fee_history_in& in, phant_fee_history_out& out, bool device_form, uint32_t block_max,
+                          std::string& err);
+
 // diagnostics: blocks x 256 lanes run `perms` Keccak-f each on a register-resident state; d_out: blocks x 256 words
 hipError_t launch_keccak_rate(uint32_t* d_out, uint32_t blocks, uint32_t perms, hipStream_t st);
 

@@ -1,5 +1,6 @@
 // wide_uint.h -- unsigned integers of L little-endian 32-bit limbs, stated ONCE for the block calls: txstate.hip.h's 288-bit sums
-// (L = 9), settle.hip.h's 320-bit two's-complement balances (L = 10) and its 128-bit gas bound (L = 4), seg_scan.hip.h's combine.
+// (L = 9), settle.hip.h's 320-bit two's-complement balances (L = 10) and its 128-bit gas bound (L = 4), seg_scan.hip.h's combine,
+// fee_history.hip.h's 256-bit tips (L = 8) and the 128-bit products of its threshold test (L = 4, feehist_check.h).
 //
 // Plain C++ that needs <stdint.h> only: the same text is compiled for the device, for the host emulation of the kernels
 // (tests/emu.py) and by a bare g++ for the stand-alone programs under tests/native/.
@@ -34,6 +35,16 @@ PHANT_WIDE_FN void sub(uint32_t* a, const uint32_t* b) {
     for (int k = 0; k < L; ++k) {
         const uint64_t t = (uint64_t)a[k] - b[k] - borrow;
         a[k] = (uint32_t)t, borrow = (t >> 32) & 1u;
+    }
+}
+// a *= m, modulo 2^(32 L)
+template <int L>
+PHANT_WIDE_FN void mul_small(uint32_t* a, uint32_t m) {
+    uint64_t c = 0;
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+        c += (uint64_t)a[k] * m;
+        a[k] = (uint32_t)c, c >>= 32;
     }
 }
 // a = -a in two's complement

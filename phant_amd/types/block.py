@@ -399,7 +399,7 @@ def block_bodies(bodies, chain_id, fork, base_fee=None, gas_limit=None, blob_bas
     ctx.check(ctx._lib.phant_block_bodies(ctx.handle, C.byref(arg), C.byref(out)))
     arrays.update({name: x[:int(out.txs.n_auth)] for name, x in auth.items()})
     arrays.update(own)
-    arrays["blob"] = blob
+    arrays["blob"], arrays["block_first"] = blob, ins["block_first"]  # (block_first: what fee_history joins the receipts' rows by)
     return BlockBodies(arrays, int(out.first_bad_block), int(out.txs.base.first_bad), int(out.txs.n_auth), int(out.txs.blob_gas_used))
 
 
@@ -541,3 +541,115 @@ def candidate_blocks(headers, filters, ctx: Context | None = None):
         blooms = np.frombuffer(b"".join(bytes(h.logs_bloom) for h in headers), np.uint8).reshape(-1, 256)
     may, _ = bloom_candidates(blooms, filters, ctx=ctx)
     return [np.flatnonzero(row) for row in may]
+
+
+# ------------------------------------------------------------------------------------- fee history over a chain segment
+class RewardPercentiles:
+    """reward_percentiles' answer: `reward` ((n_blocks, n_percentiles, 32) uint8, big-endian), `tip` ((n, 32) uint8), `order` (n: the
+    global row with each rank, block by block), `block_gas_used`, `flags` (FEE_BELOW_BASE per block) and `first_bad_block`; host arrays,
+    or device tensors when the rows were.  rewards() = the rewards as Python integers (host arrays only)."""
+
+    def __init__(self, reward, tip, order, block_gas_used, flags, first_bad_block):
+        self.reward, self.tip, self.order, self.block_gas_used, self.flags, self.first_bad_block = reward, tip, order, block_gas_used, flags, first_bad_block
+
+    def rewards(self):
+        return [[int.from_bytes(bytes(r), "big") for r in row] for row in np.asarray(self.reward)]
+
+
+def reward_percentiles(block_first, price, gas_used, percentiles_bp, base_fee=None, ctx: Context | None = None) -> RewardPercentiles:
+    """phant_block_fee_history: per block the priority fee at the percentiles (basis points, at most 10000 each) of its gas used.
+    block_first (n_blocks + 1), price (n x 32 bytes big-endian: block_bodies' effective_gas_price), gas_used (n: receipt_segments'),
+    base_fee (n_blocks x 32 bytes big-endian, or None: zero) as numpy arrays, or as torch tensors on the device -- then the device form
+    runs on them without a copy, and the answer's arrays are device tensors."""
+    ctx = ctx or default_context()
+    dev = hasattr(price, "data_ptr")
+    pct = np.ascontiguousarray(percentiles_bp, np.uint32).reshape(-1)
+    rows = {"block_first": block_first, "price": price, "base_fee": base_fee, "gas_used": gas_used}
+    if dev:
+        import torch
+        device = price.device
+        kind = {"u4": torch.int32, "u1": torch.uint8, "u8": torch.int64}
+        rows = {k: None if v is None else v.contiguous().view(torch.uint8).view(kind[dt]) for (k, dt, _), v in ((f, rows[f[0]]) for f in L.FEEHIST_INPUTS[:4])}
+        count = lambda x: x.numel()  # noqa: E731
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+        new = lambda shape, dt: torch.zeros(shape, dtype=kind[dt], device=device)  # noqa: E731
+        fn = ctx._lib.phant_block_fee_history_dev
+    else:
+        rows = {k: None if v is None else np.ascontiguousarray(v, dt) for (k, dt, _), v in ((f, rows[f[0]]) for f in L.FEEHIST_INPUTS[:4])}
+        count = lambda x: x.size  # noqa: E731
+        ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
+        new = lambda shape, dt: np.zeros(shape, dt)  # noqa: E731
+        fn = ctx._lib.phant_block_fee_history
+    nb, n = count(rows["block_first"]) - 1, count(rows["gas_used"])
+    if count(rows["price"]) != 32 * n or (rows["base_fee"] is not None and count(rows["base_fee"]) != 32 * nb):
+        raise ValueError("price is n x 32 bytes, base_fee n_blocks x 32 bytes")
+    outs = {"reward": new((nb, len(pct), 32), "u1"), "tip": new((n, 32), "u1"), "order": new(n, "u4"), "block_gas_used": new(nb, "u8"), "block_flags": new(nb, "u4")}
+    arg = L.PhantFeeHistoryIn(C.sizeof(L.PhantFeeHistoryIn), nb, n, len(pct), rows["block_first"].data_ptr() if dev else rows["block_first"].ctypes.data,
+                              ptr(rows["price"]), ptr(rows["base_fee"]), ptr(rows["gas_used"]), pct.ctypes.data if len(pct) else None, 0)
+    out = L.PhantFeeHistoryOut(C.sizeof(L.PhantFeeHistoryOut), 0, *[ptr(outs[name]) for name, _, _ in L.FEEHIST_OUTPUTS], 0)
+    ctx.check(fn(ctx.handle, C.byref(arg), C.byref(out)))
+    if dev:
+        torch.cuda.synchronize(device)
+    return RewardPercentiles(outs["reward"], outs["tip"], outs["order"], outs["block_gas_used"], outs["block_flags"], int(out.first_bad_block))
+
+
+def next_base_fee(base_fee: int, gas_used: int, gas_limit: int) -> int:
+    """The base fee of the block after one with these fields: the EIP-1559 rule as include/phant_gpu.h states it for PHANT_HDR_BASE_FEE
+    (t = gas_limit / 2, all divisions floor).  A zero gas target with gas used has no answer (the header rule flags it): ValueError."""
+    t = gas_limit // 2
+    if gas_used == t:
+        return base_fee
+    if t == 0:
+        raise ValueError("a gas target of zero with gas used")
+    if gas_used > t:
+        return base_fee + max(base_fee * (gas_used - t) // t // 8, 1)
+    return base_fee - base_fee * (t - gas_used) // t // 8
+
+
+_BLOB_GAS = {L.TXS_FORK_CANCUN: (3 * 131072, 6 * 131072), L.TXS_FORK_PRAGUE: (6 * 131072, 9 * 131072)}  # (target, maximum) per block: EIP-4844, EIP-7691
+
+
+def _bp(percentiles):
+    """eth_feeHistory's rewardPercentiles, floats of at most two decimals in [0, 100] -> basis points"""
+    out = []
+    for p in percentiles:
+        bp = round(float(p) * 100)
+        if not 0 <= bp <= 10000 or abs(float(p) * 100 - bp) > 1e-6:
+            raise ValueError(f"a percentile is a number from 0 to 100 with at most two decimals, not {p!r}")
+        out.append(bp)
+    return out
+
+
+def fee_history(headers, bodies, receipts, percentiles, fork, ctx: Context | None = None) -> dict:
+    """The eth_feeHistory answer for a chain segment: `headers` are the segment's decoded headers (BlockHeader objects), `bodies` what
+    block_bodies answered for them (or a dict of its block_first and effective_gas_price), `receipts` what receipt_segments answered
+    (or a dict of its block_first and gas_used).  -> a dict of
+    oldestBlock, baseFeePerGas and baseFeePerBlobGas (n + 1 entries: the last is the next block's), gasUsedRatio, blobGasUsedRatio and
+    reward (per block, per percentile; phant_block_fee_history).  Everything but reward is host arithmetic on n + 1 numbers.  A
+    transaction i of a block must be its receipt i: a block_first that differs between bodies and receipts is a ValueError."""
+    from .transaction import blob_base_fee as _blob_base_fee
+    get = lambda src, k: src[k] if isinstance(src, dict) else getattr(src, k)  # noqa: E731
+    headers = list(headers)
+    n = len(headers)
+    bp = _bp(percentiles)
+    first = np.ascontiguousarray(get(bodies, "block_first"), np.uint32)
+    if first.tobytes() != np.ascontiguousarray(get(receipts, "block_first"), np.uint32).tobytes():
+        raise ValueError("the bodies' block_first differs from the receipts': transaction i of a block is not its receipt i")
+    if len(first) != n + 1:
+        raise ValueError("one header per block")
+    london = all(h.base_fee_per_gas is not None for h in headers)
+    base = [int(h.base_fee_per_gas) if london else 0 for h in headers]
+    res = reward_percentiles(first, get(bodies, "effective_gas_price"), get(receipts, "gas_used"), bp, base_fee=_rows32(base, n, "base_fee") if london and n else None, ctx=ctx)
+    out = {"oldestBlock": int(headers[0].block_number) if n else 0, "reward": res.rewards(),
+           "gasUsedRatio": [h.gas_used / h.gas_limit if h.gas_limit else 0.0 for h in headers]}
+    out["baseFeePerGas"] = base + ([next_base_fee(base[-1], int(headers[-1].gas_used), int(headers[-1].gas_limit))] if london and n else [0])
+    blob = fork >= L.TXS_FORK_CANCUN and all(h.excess_blob_gas is not None and h.blob_gas_used is not None for h in headers)
+    if blob and n:
+        target, most = _BLOB_GAS[fork]
+        last = headers[-1]
+        excess = [int(h.excess_blob_gas) for h in headers] + [max(int(last.excess_blob_gas) + int(last.blob_gas_used) - target, 0)]
+        out["baseFeePerBlobGas"] = [_blob_base_fee(x, fork) for x in excess]
+        out["blobGasUsedRatio"] = [h.blob_gas_used / most for h in headers]
+    else:
+        out["baseFeePerBlobGas"], out["blobGasUsedRatio"] = [0] * (n + 1), [0.0] * n
+    return out
